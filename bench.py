@@ -1,7 +1,13 @@
 """bench.py — decoded sequences/sec of the SVDD-MC hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up (W decodes), times K decodes and prints ONE JSON line with the headline only: metric, value,
+unit, higher_is_better, dtype, ms_per_step (wall milliseconds of one timed decode), x0_sha1, config (+ per_rank for N > 1).
+--dump-outputs DIR writes what the last timed decode returned to DIR/x0.npy (the decoded tokens of the whole batch as float32
+[rows, L]; a fixed, seeded sample of rows if that would exceed 64 MB). Everything else below (rooflines from per-dispatch
+events, split precisions, the other BASELINE configs, saturated sizes, precision evidence, CPU baselines) runs only with --full.
 
 `python bench.py --gpus N` with N > 1 from a bare shell (no WORLD_SIZE in the environment) starts the N ranks itself:
 the parent spawns `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD process before it has
@@ -16,7 +22,7 @@ the final x_0 including the noise-removal forward and, for N>1, the one all-gath
 tokens. Inputs are generated on the device (nothing crosses PCIe in the timed region).
 Weak scaling: every rank decodes its own 256 rows (global rows rank*256 .. rank*256+255).
 
-Prints ONE JSON line (rank 0). Extra objects:
+With --full, the ONE JSON line (rank 0) is the compact record with extra objects:
   roofline      the dominant kernel of the job by time: backbone_kernel, the whole dilated-CNN backbone forward in
                 one launch (svdd_backbone_cnn_f32; exact-fp32 MFMA, activations in LDS/registers). Useful FLOPs per
                 launch (20 convs: 2*B*Cin*Cout*sum_t max(0, L-|t-4|*dil) - multiplications with zero padding are
@@ -74,6 +80,20 @@ class _Legs:
 def _digest(tokens):
     import hashlib
     return hashlib.sha1(tokens.to(torch.uint8).cpu().numpy().tobytes()).hexdigest()[:16]
+
+
+DUMP_LIMIT = 60_000_000    # bytes of array data of --dump-outputs: under 64 MB in all, .npy header included
+
+
+def dump_outputs(out_dir, tokens):
+    """--dump-outputs: the decoded tokens the timed path returned, as float32 DIR/x0.npy; above DUMP_LIMIT a fixed, seeded
+    sample of rows (sorted), so that two builds given the same arguments can be compared output for output."""
+    x = tokens.cpu().numpy().astype(np.float32)
+    max_rows = max(1, DUMP_LIMIT // max(x[0].nbytes, 1))
+    if x.shape[0] > max_rows:
+        x = x[np.sort(np.random.default_rng(0).choice(x.shape[0], max_rows, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "x0.npy"), x)
 
 
 def host_cpu():
@@ -1110,6 +1130,28 @@ def dry_run(args):
         dist.destroy_process_group()
 
 
+def headline(args, world, elapsed, out):
+    """The keys every line carries, plain or --full: `elapsed` = wall seconds of the args.steps timed decodes (max over ranks),
+    `out` = the gathered tokens of the last one."""
+    import torch.distributed as dist
+    B, L, M, S = args.batch, args.length, args.sample_M, args.diffusion_steps
+    workload = (f"DNA enhancer SVDD-MC, batch={B}/GPU, L={L}, M={M}, {S} steps "
+                f"(BASELINE.json configs[1]); dilated-CNN backbone 3.3M params + ConvGRU value net")
+    if args.value_net != "convgru":
+        workload += " [value net: Enformer-shaped trunk, 230M params — BASELINE configs[3] shape]"
+    return {
+        "metric": "decoded sequences/sec (whole node), L=200 M=10 128-step SVDD-MC",
+        "value": round(B * world * args.steps / elapsed, 3), "unit": "sequences/s", "n_gpus": world,
+        "ranks_seen": dist.get_world_size() if world > 1 else 1,
+        "backend": ({"nccl": "nccl (RCCL)"}.get(dist.get_backend(), dist.get_backend()) if world > 1 else None),
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+        "data": "synthetic (random-init nets, all-MASK prior)",
+        "x0_sha1": _digest(out),       # of the gathered batch of the last timed decode: equal for any number of ranks (Philox is keyed by the global row)
+        "config": {"workload": workload, "global_batch": B * world, "rng": args.rng, "sharding": f"rows x{world}, 1 all-gather"},
+    }
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--cpu-sweep-only":          # child of cpu_baseline: never touches the GPU
         B, L, M, S, seed = (int(v) for v in sys.argv[2:7])
@@ -1143,10 +1185,17 @@ def main():
                     help="where the LONG record goes (every object of the run with its prose); stdout's last line is the compact record (<= 6 KB) the driver parses; '' = stderr only")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch / rendezvous / all-gather skeleton with a stand-in decode on the host (no GPU, gloo)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other leg (rooflines, alt precisions, other configs, CPU baselines) and the compact "
+                         "record; without it the line carries the headline only and no per-dispatch events are taken")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the decoded tokens of the last timed decode to DIR/x0.npy (float32)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
+    if args.steps < 1 or args.warmup < 0:        # checked in the ranks: a failing rank must fail the launcher's command
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.dry_run:
         return dry_run(args)
 
@@ -1209,21 +1258,13 @@ def main():
     legs.mark("warmup")
     t0 = time.perf_counter()
     for k in range(args.steps):
-        if k == args.steps - 1:
+        if args.full and k == args.steps - 1:
             _lib.profile_enable(True)      # per-dispatch HIP events on the LAST timed decode (a few us of host time per launch)
         out = one_decode()
     fence()
     elapsed = time.perf_counter() - t0
     legs.mark("headline")
     _lib.profile_enable(False)
-    k1_total_ms, k1_launches = _lib.profile_collect(0)
-    k2_total_ms, k2_launches = _lib.profile_collect(1)
-    conv_total_ms, conv_launches = _lib.profile_collect(2)
-    gru_total_ms, gru_launches = _lib.profile_collect(3)
-    epi_total_ms, epi_launches = _lib.profile_collect(4)
-    tower_total_ms, tower_launches = _lib.profile_collect(5)
-    bb_total_ms, bb_launches = _lib.profile_collect(6)
-    tail_total_ms, tail_launches = _lib.profile_collect(7)
     assert out.shape == (B * world, L) and int(out.max()) <= 3
     per_rank = None
     if world > 1:
@@ -1237,6 +1278,26 @@ def main():
         per_rank = {"decode_ms": [round(float(t[0]) * 1e3, 2) for t in allr],
                     "allgather_ms": [round(float(t[1]) * 1e3, 3) for t in allr],
                     "note": "mean over the timed decodes; the all-gather time of a rank includes its wait for the slowest rank"}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    if not args.full:
+        if rank == 0:
+            line = headline(args, world, elapsed, out)
+            if per_rank:
+                line["per_rank"] = per_rank
+            print(json.dumps(line, separators=(",", ":")), flush=True)
+        if world > 1:
+            barrier()
+            dist.destroy_process_group()
+        return
+    k1_total_ms, k1_launches = _lib.profile_collect(0)
+    k2_total_ms, k2_launches = _lib.profile_collect(1)
+    conv_total_ms, conv_launches = _lib.profile_collect(2)
+    gru_total_ms, gru_launches = _lib.profile_collect(3)
+    epi_total_ms, epi_launches = _lib.profile_collect(4)
+    tower_total_ms, tower_launches = _lib.profile_collect(5)
+    bb_total_ms, bb_launches = _lib.profile_collect(6)
+    tail_total_ms, tail_launches = _lib.profile_collect(7)
 
     # ---- the same workload with the nets on the 16-bit matrix cores (never the headline)
     H = 128
@@ -1332,18 +1393,8 @@ def main():
                         "traffic_source": pmc_src if pmc.get("conv_traffic_bytes_per_launch") else None,
                         "flops_per_launch": round(conv_flops_fwd / 20.0), "avg_launch_us": round(conv_ms * 1e3, 3),
                         "launches": conv_launches}
-        line = {
-            "metric": "decoded sequences/sec (whole node), L=200 M=10 128-step SVDD-MC",
-            "value": round(seqs / elapsed, 3), "unit": "sequences/s", "n_gpus": world,
-            "ranks_seen": dist.get_world_size() if world > 1 else 1,
-            "backend": ({"nccl": "nccl (RCCL)"}.get(dist.get_backend(), dist.get_backend()) if world > 1 else None),
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic (random-init nets, all-MASK prior)",
-            "x0_sha1": _digest(out),       # of the gathered batch of the last timed decode: equal for any number of ranks (Philox is keyed by the global row)
-            "config": {"workload": f"DNA enhancer SVDD-MC, batch={B}/GPU, L={L}, M={M}, {S} steps "
-                                   f"(BASELINE.json configs[1]); dilated-CNN backbone 3.3M params + ConvGRU value net",
-                       "global_batch": B * world, "rng": args.rng, "sharding": f"rows x{world}, 1 all-gather"},
+        line = headline(args, world, elapsed, out)
+        line.update({
             "roofline": roofline,
             "roofline_sampler": {"bound": "hbm", "kernel": "propose_kernel (K1)", "achieved": round(achieved, 2),
                                  "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
@@ -1363,7 +1414,7 @@ def main():
             # a throughput normalisation, not a utilisation — exact work-skipping executes fewer FLOPs than that
             "e2e_fp32_frac": round(flops_seq * seqs / elapsed / 1e12 / (FP32_PEAK_TFLOPS * world), 5),
             "alt_precision": alt or None,
-        }
+        })
         if per_rank:
             line["per_rank"] = per_rank
         if world == 1 and args.value_net == "convgru":
@@ -1401,7 +1452,6 @@ def main():
                 leg["roofline_value_net"] = rv
         legs.mark("value_net_roofline")
         if args.value_net != "convgru":
-            line["config"]["workload"] += " [value net: Enformer-shaped trunk, 230M params — BASELINE configs[3] shape]"
             line["e2e_fp32_frac"] = None
             # (the headline line of this workload is fp32: the trunk runs on the fp32-plane kernels; the split modes are in alt_precision)
             line["roofline_trunk_gemm"] = trunk_gemm_roofline(model, emb, head, dev, int(0.75 * B * M), L, precision="f32")

@@ -375,11 +375,12 @@ def test_rccl_collectives_of_the_bench_on_one_rank(tmp_path):
 
 
 @pytest.mark.parametrize("rng", ["philox", "replay"])
-def test_bench_real_two_rank_branch_equals_the_unsharded_decode(rng):
-    """bench.py's REAL multi-rank branch (not --dry-run): `python bench.py --gpus 2 ...` starts two ranks that share this box's one GPU
-    (gloo through the host, chosen by the launcher), each decodes its 64 rows (Philox keyed by the global row / the whole batch's
+def test_bench_real_two_rank_branch_equals_the_unsharded_decode(rng, tmp_path):
+    """bench.py's REAL multi-rank branch (not --dry-run): `python bench.py --gpus 2 --full ...` starts two ranks that share this box's
+    one GPU (gloo through the host, chosen by the launcher), each decodes its 64 rows (Philox keyed by the global row / the whole batch's
     mt19937 stream replayed per rank), max-over-ranks timing, per-rank times, the one all-gather, and one split-precision leg. The
-    digest of the gathered batch in the line must equal the digest of the SAME decode done unsharded in this process (128 rows)."""
+    digest of the gathered batch in the line, and the batch --dump-outputs wrote, must equal the SAME decode done unsharded in this
+    process (128 rows)."""
     import hashlib
     import json
     import os
@@ -390,7 +391,7 @@ def test_bench_real_two_rank_branch_equals_the_unsharded_decode(rng):
     B, S = 64, 16
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--batch", str(B),
            "--diffusion-steps", str(S), "--cpu-steps", "0", "--c4-steps", "0", "--c3-steps", "0", "--c5-steps", "0",
-           "--alt-precision", "f16x3", "--alt-steps", "1", "--rng", rng]
+           "--alt-precision", "f16x3", "--alt-steps", "1", "--rng", rng, "--full", "--dump-outputs", str(tmp_path)]
     env = dict(os.environ, OMP_NUM_THREADS="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
@@ -406,18 +407,20 @@ def test_bench_real_two_rank_branch_equals_the_unsharded_decode(rng):
     # the same decode unsharded, here
     model, emb, head, _ = synthetic.build("dna", "cuda:0")
     model.rng_mode, model.philox_seed, model.row_offset = rng, 0, 0
-    digest = {}
+    digest, x0 = {}, {}
     for mode in ("f32", "f16x3"):
         model.precision = mode
         torch.manual_seed(0)
-        x = model.controlled_sample(emb, head, num_steps=S, eval_sp_size=2 * B, sample_M=10)
-        digest[mode] = hashlib.sha1(x.to(torch.uint8).cpu().numpy().tobytes()).hexdigest()[:16]
+        x0[mode] = model.controlled_sample(emb, head, num_steps=S, eval_sp_size=2 * B, sample_M=10).cpu().numpy()
+        digest[mode] = hashlib.sha1(x0[mode].astype(np.uint8).tobytes()).hexdigest()[:16]
     assert line["x0_sha1"] == digest["f32"], (line["x0_sha1"], digest)
+    dumped = np.load(tmp_path / "x0.npy")
+    assert dumped.dtype == np.float32 and np.array_equal(dumped, x0["f32"].astype(np.float32))
     assert line["alt"]["f16x3"]["x0_sha1"] == digest["f16x3"], (line["alt"]["f16x3"]["x0_sha1"], digest)
 
 
 def test_bench_real_eight_rank_branch_equals_the_unsharded_decode():
-    """The first real `--gpus 8` run must not be the first execution of any branch: `python bench.py --gpus 8`
+    """The first real `--gpus 8` run must not be the first execution of any branch: `python bench.py --gpus 8 --full`
     from a bare shell starts EIGHT ranks (sharing this box's one GPU; gloo through the host, chosen by the launcher because there are
     fewer GPUs than ranks), each decodes its 8 rows keyed by the global row, max-over-ranks timing, eight per-rank times, one
     all-gather. ranks_seen == 8, the gathered 64 rows' digest equals the unsharded 64-row decode's, and the line is the compact one."""
@@ -430,7 +433,8 @@ def test_bench_real_eight_rank_branch_equals_the_unsharded_decode():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     B, S, W = 8, 4, 8
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(W), "--steps", "1", "--warmup", "0", "--batch", str(B),
-           "--diffusion-steps", str(S), "--cpu-steps", "0", "--c4-steps", "0", "--c3-steps", "0", "--c5-steps", "0", "--alt-precision", ""]
+           "--diffusion-steps", str(S), "--cpu-steps", "0", "--c4-steps", "0", "--c3-steps", "0", "--c5-steps", "0", "--alt-precision", "",
+           "--full"]
     env = dict(os.environ, OMP_NUM_THREADS="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, env=env)
@@ -446,6 +450,34 @@ def test_bench_real_eight_rank_branch_equals_the_unsharded_decode():
     model.rng_mode, model.philox_seed, model.row_offset = "philox", 0, 0
     x = model.controlled_sample(emb, head, num_steps=S, eval_sp_size=W * B, sample_M=10)
     assert line["x0_sha1"] == hashlib.sha1(x.to(torch.uint8).cpu().numpy().tobytes()).hexdigest()[:16]
+
+
+def test_bench_plain_run_prints_the_headline_and_dumps_the_last_decode(tmp_path):
+    """A plain `python bench.py` run (no --full) prints the headline keys and nothing else, times exactly --steps decodes, and
+    --dump-outputs writes the tokens of the last timed decode as float32 x0.npy: the SAME decode done here."""
+    import hashlib
+    import json
+    import os
+    import subprocess
+    import sys
+    from svdd_amd import synthetic
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B, S = 32, 8
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", str(B),
+           "--diffusion-steps", str(S), "--dump-outputs", str(tmp_path / "out")]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(os.environ, OMP_NUM_THREADS="1"))
+    assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
+    line = json.loads(res.stdout.splitlines()[-1])
+    assert set(line) == {"metric", "value", "unit", "n_gpus", "ranks_seen", "backend", "steps", "warmup", "ms_per_step",
+                         "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "x0_sha1", "config"}
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "sequences/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f32" and abs(line["value"] * line["ms_per_step"] - B * 1e3) <= 1e-3 * B * 1e3
+    dumped = np.load(tmp_path / "out" / "x0.npy")
+    model, emb, head, _ = synthetic.build("dna", "cuda:0")
+    model.rng_mode, model.philox_seed, model.row_offset = "philox", 0, 0
+    x = model.controlled_sample(emb, head, num_steps=S, eval_sp_size=B, sample_M=10).cpu().numpy()
+    assert dumped.dtype == np.float32 and np.array_equal(dumped, x.astype(np.float32))
+    assert line["x0_sha1"] == hashlib.sha1(x.astype(np.uint8).tobytes()).hexdigest()[:16]
 
 
 def test_gru_round_rows_follow_the_cu_count(monkeypatch):

@@ -402,6 +402,38 @@ def test_bench_emit_prints_the_compact_line_last(tmp_path, capsys):
     assert json.load(open(path))["cpu_baseline"] == full["cpu_baseline"]
 
 
+def test_bench_headline_names_the_workload_it_timed():
+    """bench.headline(): the keys of every line, plain or --full. value and ms_per_step come from the same wall time, and the
+    workload names the value net the run used (--value-net enformer: the Enformer-shaped trunk, in both modes)."""
+    import argparse
+    bench = _import_bench()
+    args = argparse.Namespace(batch=256, length=200, sample_M=10, diffusion_steps=128, steps=4, warmup=1, rng="philox",
+                              value_net="convgru")
+    out = torch.zeros(256, 200, dtype=torch.int64)
+    line = bench.headline(args, 1, 2.0, out)
+    assert line["value"] == 512.0 and line["ms_per_step"] == 500.0 and line["steps"] == 4 and line["dtype"] == "f32"
+    assert line["x0_sha1"] == bench._digest(out) and "ConvGRU value net" in line["config"]["workload"]
+    assert "Enformer" not in line["config"]["workload"]
+    args.value_net = "enformer"
+    assert "[value net: Enformer-shaped trunk" in bench.headline(args, 1, 2.0, out)["config"]["workload"]
+
+
+def test_bench_dump_outputs_is_float32_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs: the tokens as float32 x0.npy, whole when they fit; above the size limit the same seeded sample of rows on
+    every call (two builds given the same arguments must stay comparable)."""
+    bench = _import_bench()
+    x = torch.arange(50 * 7).view(50, 7)                      # row r starts with 7 r
+    bench.dump_outputs(str(tmp_path / "whole"), x)
+    whole = np.load(tmp_path / "whole" / "x0.npy")
+    assert whole.dtype == np.float32 and np.array_equal(whole, x.numpy().astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 10 * 7 * 4)
+    bench.dump_outputs(str(tmp_path / "a"), x)
+    bench.dump_outputs(str(tmp_path / "b"), x)
+    a, b = np.load(tmp_path / "a" / "x0.npy"), np.load(tmp_path / "b" / "x0.npy")
+    rows = (a[:, 0] / 7).astype(int)
+    assert a.shape == (10, 7) and np.array_equal(a, b) and np.array_equal(a, whole[rows]) and np.all(np.diff(rows) > 0)
+
+
 def test_dps_gradient_matches_reference_full_size(golden):
     """g20: compute_gradient_DPS of the PyTorch mirrors (CNNModel.forward2 + ConvGRU reward model, seed 44 in synthetic.build's
     order) against the gradients of the reference's own full-size controlled_sample_DPS run, on the CPU: same framework, same
