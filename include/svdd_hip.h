@@ -107,6 +107,24 @@ int svdd_sample_categorical(const float* q, const uint8_t* x, int B, int L, int 
                             const svdd_rng_t* rng, uint8_t* cand, float* onehot, void* stream);
 
 /*
+ * svdd_classifier_propose — ABI 12. One step of classifier guidance (reference diffusion_gosai.py:1332-1360) after the value net's
+ * input gradient, per position:
+ *   q_xs = exp(log p(x0 | x_t)) (mct - mcs), q_xs[MASK] = mcs                 (SUBS as svdd_propose; :1348-1353)
+ *   w    = q_xs + scale * cat(x_grad, 0)                                        (:1355-1357; SIGNED: w < 0 where the step lowers it)
+ *   one _sample_categorical(w) draw, merged with copy_flag                      (:30-34, :1358-1359)
+ * in fp32 with one rounding per operation: q = fl(exp(lp) * dm), w = fl(q + fl(scale * g)).
+ *  logits      [B,L,5] fp32 raw backbone output in `layout`
+ *  x           [B,L]   u8   current tokens x_t
+ *  grad4       [B][L][4] fp32 x_grad = d mean(head(embedding(onehot(x_t)))) / d onehot (contiguous)
+ *  rng         as svdd_propose with M = 1 (Philox: the same counters, so scale 0 draws what svdd_propose draws)
+ *  x_next      [B][L] u8   out
+ *  onehot_next [B][L][4] fp32 out, may be NULL: transform_samples(x_next) (MASK rows zero), the next step's value-net input
+ *  q_xs        [B,L,5] fp32 out in `layout`, may be NULL: the UN-guided q_xs (the per-step API's third output)
+ */
+int svdd_classifier_propose(const float* logits, int layout, const uint8_t* x, const float* grad4, float dm, float mcs, float scale,
+                            int B, int L, const svdd_rng_t* rng, uint8_t* x_next, float* onehot_next, float* q_xs, void* stream);
+
+/*
  * svdd_select — replaces torch.stack(scores,1) -> softmax(dim=1) -> argmax(dim=1) ->
  * per-row Python gather + stack                     diffusion_gosai.py:1219-1227 (= :1451-1459)
  *
@@ -476,7 +494,7 @@ int svdd_device_info(char* arch, int arch_len, int* num_cu);
 
 /* ABI version of this header: bumped on any signature change. */
 int svdd_abi_version(void);
-#define SVDD_ABI_VERSION 11
+#define SVDD_ABI_VERSION 12
 
 /*
  * Enformer-shaped value trunk (BASELINE.json configs[3]; reference decode.py:78-80, Enformer.py:1271-1334 trunk, :1807-1884

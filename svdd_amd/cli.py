@@ -1,8 +1,8 @@
 """Command-line decode drivers — the caller contract of the reference's `decode.py`,
-`decode_tweedie.py`, `decode_TDS.py`, `decode_DPS.py` (reference decode.py:52-211): seed, build the
+`decode_tweedie.py`, `decode_TDS.py`, `decode_DPS.py`, `decode_classfier.py` (reference decode.py:52-211): seed, build the
 nets, run `BaseModel.controlled_decode*`, write `./log/{task}-{reward_name}[_tw|_TDS|_DPS].npz` with
 the two arrays `decoding` and `baseline` (decode.py:117, decode_tweedie.py:118, decode_TDS.py:118,
-decode_DPS.py:119).
+decode_DPS.py:119, decode_classfier.py:119).
 
 Offline there are no W&B artifacts, so nets are random-init unless state_dicts are given
 (`--diffusion_ckpt`, `--load_checkpoint_path`, `--reward_ckpt`; reference key names load unchanged).
@@ -14,7 +14,8 @@ import random
 import numpy as np
 import torch
 
-SUFFIX = {"mc": "", "tweedie": "_tw", "tds": "_TDS", "dps": "_DPS"}
+SUFFIX = {"mc": "", "tweedie": "_tw", "tds": "_TDS", "dps": "_DPS", "classfier": "-classfier"}
+GUIDANCE_DEFAULT = {"dps": 1e5, "classfier": 1.5}                                   # decode_DPS.py:184, decode_classfier.py
 
 
 def set_seed(seed):
@@ -36,7 +37,8 @@ def build_parser(method="mc"):
     p.add_argument("--method", default=method, choices=list(SUFFIX))
     p.add_argument("--tweedie", default="True", help='"True": posterior-mean scoring (decode_tweedie.py:206)')
     p.add_argument("--alpha", type=float, default=0.5)                               # decode_TDS.py:183
-    p.add_argument("--guidance_scale", type=float, default=1e5)                      # decode_DPS.py:184
+    p.add_argument("--guidance_scale", type=float, default=None,
+                   help="guidance scale of --method dps (default 1e5) and classfier (default 1.5)")
     p.add_argument("--model", default="convgru", choices=["convgru", "enformer"],
                    help="value-function trunk: convgru = ConvGRUTrunk + ConvHead (Enformer.py:32-49; BASELINE configs 1-3, SURVEY "
                         "section 8d); enformer = the 230 M-parameter EnformerTrunk(7, 1536, 11, 8, 64) + ConvHead(1, 3072) the "
@@ -53,7 +55,13 @@ def build_parser(method="mc"):
     p.add_argument("--out_dir", default="./log")
     p.add_argument("--presample", action="store_true",
                    help="pre-sample val_batch_num batches at construction like the reference's BaseModel.__init__")
+    p.epilog = ("--method classfier evaluates the value net in eval mode for every task (the reference's decode_classfier.py leaves it in "
+                "train mode for --task rna: dropout on, batch-statistics BatchNorm, an irreproducible run).")
     return p
+
+
+def _guidance_scale(args):
+    return args.guidance_scale if args.guidance_scale is not None else GUIDANCE_DEFAULT.get(args.method, 1e5)
 
 
 def run(args):
@@ -89,9 +97,12 @@ def run(args):
         out = model.controlled_decode_tweedie(gen_batch_num=args.val_batch_num, sample_M=args.sample_M, options=args.tweedie)
     elif args.method == "tds":
         out = model.controlled_decode_TDS(gen_batch_num=args.val_batch_num, sample_M=args.sample_M, alpha=args.alpha)
-    else:
+    elif args.method == "dps":
         out = model.controlled_decode_DPS(gen_batch_num=args.val_batch_num, sample_M=args.sample_M,
-                                          guidance_scale=args.guidance_scale)
+                                          guidance_scale=_guidance_scale(args))
+    else:
+        out = model.controlled_decode_classfier(gen_batch_num=args.val_batch_num, guidance_scale=_guidance_scale(args),
+                                                sample_M=args.sample_M)
     gen_samples, value_func_preds, reward_model_preds, selected_baseline_preds, baseline_preds = out
     os.makedirs(args.out_dir, exist_ok=True)
     path = os.path.join(args.out_dir, f"{args.task}-{reward_name}{SUFFIX[args.method]}")

@@ -929,6 +929,65 @@ __global__ __launch_bounds__(256) void dps_guided_q_kernel(DpsArgs a) {
   }
 }
 
+// ------------------------------------------------- classifier guidance: the guided propose (ABI 12) ----
+// One step of the reference's controlled_sample_classfier (diffusion_gosai.py:1332-1360) after its two net passes, one thread per
+// (b, l): SUBS -> q_xs (:1350-1353) -> w = q_xs + scale * cat(x_grad, 0) (:1357) -> ONE exponential race (:30-34) -> copy_flag merge
+// (:1359) -> x_next and, optionally, its masked one-hot (the next step's value-net input, :1355) and the un-guided q_xs (the step's
+// third output). w is SIGNED (the scaled gradient is added to the weights): sample_categorical_1 takes it as it is — a negative w
+// gives a negative quotient, which loses the race exactly as it does in torch's argmax. No fast-path filter: one draw per position.
+// Exact fp32 order: q = fl(exp(lp) * dm), w = fl(q + fl(scale * g)), no contraction. Uniforms: the M = 1 case of K1 (replay: block 0
+// in `ulayout` of a batch of u_rows rows; Philox: (seed, (row_offset + b) L + l, step, m = 0)), so zero guidance draws what K1 draws.
+struct ClassifierArgs {
+  const float* logits; const uint8_t* x; const float* grad4; float dm, mcs, scale; int B, L, layout;
+  uint32_t step; const float* uniforms; uint64_t seed, row_offset; int ulayout;
+  uint8_t* x_next; float* onehot; float* q_xs;
+};
+
+template <bool REPLAY>
+__global__ __launch_bounds__(256) void classifier_propose_kernel(ClassifierArgs a) {
+  const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= (int64_t)a.B * a.L) return;
+  const int64_t b = n / a.L, l = n - b * a.L;
+  const int xt = a.x[n];
+  const bool masked = xt == MASK;
+  float q[V];
+  if (masked) {
+    float z[V], lp[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) z[v] = a.logits[at(a.layout, b, l, v, a.L)];
+    subs_logp_1(z, xt, lp);
+#pragma unroll
+    for (int v = 0; v < MASK; ++v) q[v] = __fmul_rn(expf_cr(lp[v]), a.dm);     // :1350-1351
+  } else {
+#pragma unroll
+    for (int v = 0; v < MASK; ++v) q[v] = (v == xt) ? a.dm : 0.0f;              // exp(0) * dm, exp(-1e6) * dm
+  }
+  q[MASK] = a.mcs;                                                             // :1352
+  if (a.q_xs) {
+#pragma unroll
+    for (int v = 0; v < V; ++v) a.q_xs[at(a.layout, b, l, v, a.L)] = q[v];
+  }
+  int c = xt;
+  if (masked) {                                  // an unmasked position keeps its token whatever it draws (:1359)
+    const float4 g4 = reinterpret_cast<const float4*>(a.grad4)[n];
+    const float g[V] = {g4.x, g4.y, g4.z, g4.w, 0.0f};                          // cat(x_grad, zero_pad), :1355-1356
+    float w[V], u[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) w[v] = __fadd_rn(q[v], __fmul_rn(a.scale, g[v]));   // :1357
+    if (REPLAY) {
+#pragma unroll
+      for (int v = 0; v < V; ++v) u[v] = a.uniforms[at(a.ulayout, b + (int64_t)a.row_offset, l, v, a.L)];
+    } else {
+      philox_uniform5(a.seed, (a.row_offset + (uint64_t)b) * (uint64_t)a.L + (uint64_t)l, a.step, 0u, u);
+    }
+    c = sample_categorical_1(w, u);
+  }
+  a.x_next[n] = (uint8_t)c;
+  if (a.onehot)
+    reinterpret_cast<float4*>(a.onehot)[n] = make_float4(c == 0 ? 1.0f : 0.0f, c == 1 ? 1.0f : 0.0f, c == 2 ? 1.0f : 0.0f,
+                                                         c == 3 ? 1.0f : 0.0f);
+}
+
 // -------------------------------------------------------------------- K4 TDS resample ----
 // numpy's pairwise float32 sum (np.add.reduce), the order `ratio.sum()` uses at :1282: the array is halved (left half
 // rounded down to a multiple of 8) until a block has <= 128 elements; a block is summed with 8 running accumulators.
@@ -1649,6 +1708,27 @@ int svdd_dps_guided_q(const float* logits, const uint8_t* x, const float* grad_b
   const int64_t N = (int64_t)B * L;
   hipLaunchKernelGGL(dps_guided_q_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      DpsArgs{logits, x, grad_backbone, grad_direct, q, nullptr, B, L, dm, mcs, scale});
+  return check_launch();
+}
+
+int svdd_classifier_propose(const float* logits, int layout, const uint8_t* x, const float* grad4, float dm, float mcs, float scale,
+                            int B, int L, const svdd_rng_t* rng, uint8_t* x_next, float* onehot_next, float* q_xs, void* stream) {
+  if (!logits || !x || !grad4 || !rng || !x_next || B <= 0 || L <= 0 || bad_layout(layout)) return SVDD_E_ARG;
+  if (rng->kind == SVDD_RNG_REPLAY ? (rng->uniforms == nullptr || bad_layout(rng->uniforms_layout))
+                                   : rng->kind != SVDD_RNG_PHILOX) return SVDD_E_ARG;
+  const int64_t N = (int64_t)B * L;
+  if (N * V >= (int64_t)1 << 31) return SVDD_E_ARG;
+  const bool replay = rng->kind == SVDD_RNG_REPLAY;
+  uint64_t row_offset = rng->row_offset;
+  if (replay) {
+    const int rows = replay_rows(rng, B);
+    if (rng->uniforms_rows <= 0) row_offset = 0;                     // plain replay: the block is this batch's own
+    if (rows < B || row_offset + (uint64_t)B > (uint64_t)rows || (int64_t)rows * L * V >= (int64_t)1 << 31) return SVDD_E_ARG;
+  }
+  const ClassifierArgs a{logits, x, grad4, dm, mcs, scale, B, L, layout, rng->step, rng->uniforms, rng->seed, row_offset,
+                         rng->uniforms_layout, x_next, onehot_next, q_xs};
+  hipLaunchKernelGGL(replay ? classifier_propose_kernel<true> : classifier_propose_kernel<false>, dim3((unsigned)((N + 255) / 256)),
+                     dim3(256), 0, (hipStream_t)stream, a);
   return check_launch();
 }
 

@@ -5,8 +5,9 @@ Same method names, keyword arguments, return types and error behaviour as the re
 methods on the SVDD decode path, so `BaseModel`/`decode.py`-style callers work unchanged:
 
     forward, _process_sigma, _sample_prior, _sample, decode_sample, controlled_sample,
-    controlled_sample_tweedie, controlled_sample_TDS, controlled_sample_DPS,
-    _ddpm_update_finetune[_controlled[_twedie|_TDS|_DPS]], transform_samples
+    controlled_sample_tweedie, controlled_sample_TDS, controlled_sample_DPS, controlled_sample_classfier,
+    _ddpm_update_finetune[_controlled[_twedie|_TDS|_DPS]], _ddpm_update_finetune_classfier, compute_gradient,
+    transform_samples
 
 What differs is where the work runs: everything between "backbone logits" and "next x_t" is one
 or two launches of the hand-written HIP kernels (svdd_amd/csrc, C ABI include/svdd_hip.h) instead
@@ -69,6 +70,7 @@ Engine knobs (attributes; defaults reproduce the reference's observable behaviou
                    first decode pays for every new live-batch size, rounded to 256 rows here), hence opt-in. The one-pass modes "bf16" / "f16" run an
                    opaque value / reward net under torch.autocast; the x3 modes leave it in fp32.
 """
+import contextlib
 import warnings
 import weakref
 
@@ -202,6 +204,7 @@ class Diffusion(nn.Module):
         self.replay_rng = "device"       # rng_mode "replay": "device" = torch's CPU mt19937 stream continued by K8 on the GPU for
         self._replay_stream = None       # the span of a sampler call; "host" = torch.rand on the host + upload (round 1-3)
         self._replay_checked = None      # scope id of the sharded replay decode whose generator state was compared across ranks
+        self._classifier_fused_last = None   # classifier guidance: whether the last step's gradient ran on the fused kernels (no autograd)
 
     # ------------------------------------------------------------------ plumbing ----
     @property
@@ -813,6 +816,112 @@ class Diffusion(nn.Module):
             x = self._dps_step(x, sched[i, 0], sched[i, 1], sched[i, 2], reward_model, guidance_scale, i)
         with torch.no_grad():
             return self._noise_removal(x)
+
+    # ------------------------------------------------------------ classifier guidance ----
+    def compute_gradient(self, x, pre_scorer_embedding, pre_scorer_head):
+        """d mean(head(embedding(x))) / d x for the masked one-hot x [B, L, 4] (reference :1362-1371): the mean runs over the batch AND
+        the tasks, so a row's gradient carries a 1 / B factor. Pure autograd, on whatever device x lives (CPU included). On the GPU a
+        64-unit bidirectional GRU runs on the hand-written forward + BPTT kernels and any other eval-mode GRU is switched to train() for
+        the call (MIOpen's fused RNN backward needs it; without inter-layer dropout it is the same function), as in
+        compute_gradient_DPS. The value net's modes are otherwise left as the caller set them."""
+        x.requires_grad_(True)
+        mods = [m for m in (pre_scorer_embedding, pre_scorer_head) if isinstance(m, nn.Module)]
+        hip = [b for m in mods for b in self._hip_gru_blocks(m)] if (self.fuse_nets and x.is_cuda) else []
+        taken = {id(b.gru) for b in hip}
+        rnns = [r for m in mods for r in m.modules() if isinstance(r, torch.nn.RNNBase) and id(r) not in taken]
+        flip = [r for r in rnns if isinstance(r, torch.nn.GRU) and r.dropout == 0 and not r.training] if x.is_cuda else []
+        native = x.is_cuda and len(flip) != len([r for r in rnns if not r.training])
+        for r in flip:
+            r.train()
+        try:
+            with torch.enable_grad(), (torch.backends.cudnn.flags(enabled=not native) if x.is_cuda else contextlib.nullcontext()):
+                scores = pre_scorer_head(pre_scorer_embedding(x))
+                scores.mean().backward()
+        finally:
+            for r in flip:
+                r.eval()
+            for b in hip:
+                b._hip_gru = None
+        return x.grad.clone()
+
+    def _classifier_fused_value(self, embedding, head, L):
+        """The value net as FusedValueNet when its input gradient can run without autograd (mean_score_input_grad: the reference-shaped
+        ConvGRU net with one task, at a length the gradient kernels take), else None."""
+        from .value_nets import ConvGRUTrunk
+        if not (self.fuse_nets and isinstance(embedding, ConvGRUTrunk)):
+            return None
+        from .fused import FusedValueNet
+        fn = self.value_callable(embedding, head)
+        if isinstance(fn, FusedValueNet) and fn.grad_ok(L) and fn.w_eff.shape[1] == 1:
+            return fn
+        return None
+
+    def _classifier_grad(self, onehot, embedding, head):
+        """x_grad [B, L, 4] of one classifier-guidance step (:1354) from the masked one-hot of x_t -> (grad, fused?)."""
+        fn = self._classifier_fused_value(embedding, head, onehot.shape[1]) if onehot.is_cuda else None
+        if fn is not None:
+            with torch.no_grad():
+                return fn.mean_score_input_grad(onehot), True
+        return self.compute_gradient(onehot.detach().clone(), embedding, head), False
+
+    def _classifier_step(self, x_u8, onehot, logits, dm, mcs, embedding, head, guidance_scale, step, want_q=False):
+        """x_grad (fused or autograd), then ONE svdd_classifier_propose launch: the guided draw, the copy_flag merge, the next step's
+        value-net input -> (x_next u8, onehot_next f32 [B, L, 4], un-guided q_xs | None)."""
+        B, L = x_u8.shape
+        grad, fused = self._classifier_grad(onehot, embedding, head)
+        self._classifier_fused_last = fused
+        with torch.no_grad():
+            return ops.classifier_propose(logits, x_u8, grad, dm, mcs, guidance_scale, self._rng(step, 1, B, L, logits), want_q=want_q)
+
+    def _classifier_checks(self, guidance_scale):
+        if guidance_scale is None:
+            raise ValueError("controlled_sample_classfier needs a guidance_scale (the reference's default None fails at "
+                             "`None * x_grad`, diffusion_gosai.py:1357)")
+        if self._shard is not None and self._shard[3] > 1:
+            raise NotImplementedError("classifier guidance is not batch-sharded: the gradient's batch mean would use the local batch")
+        self._require_gpu()
+
+    @_decode_scope
+    def _ddpm_update_finetune_classfier(self, x, t, dt, pre_scorer_embedding, pre_scorer_head, guidance_scale):
+        """One classifier-guidance step (:1332-1360) -> (x_next, x, q_xs, copy_flag); q_xs is the UN-guided one, as in the reference."""
+        self._classifier_checks(guidance_scale)
+        mct, mcs, dm = self._step_scalars(t, dt)
+        x_u8 = self._tokens_u8(x)
+        with torch.no_grad():
+            logits = self._backbone_logits(x_u8)
+            onehot = ops.transform_samples(x_u8)
+        x_next, _, q = self._classifier_step(x_u8, onehot, logits, dm, mcs, pre_scorer_embedding, pre_scorer_head, guidance_scale,
+                                             self._step_index(t, dt), want_q=True)
+        return x_next.long(), x, q, (x != self.mask_index).to(x.dtype)
+
+    @_decode_scope
+    def controlled_sample_classfier(self, pre_scorer_embedding, pre_scorer_head, num_steps=None, eps=1e-5, eval_sp_size=None,
+                                    guidance_scale=None):
+        """Classifier-guidance decode (reference :1064-1104): per step the backbone forward, the value net's input gradient
+        x_grad = d mean(head(embedding(onehot(x_t)))) / d onehot and one draw from the SIGNED weights q_xs + guidance_scale * x_grad,
+        then noise removal. With the reference-shaped ConvGRU value net (one task, fp32 gradient, L in the gradient kernels' set) a step
+        is the backbone launch, the gradient pass's launches (FusedValueNet.mean_score_input_grad) and one svdd_classifier_propose: no
+        autograd, no torch element-wise op. Any other value net takes its gradient through torch autograd (compute_gradient) before the
+        same propose kernel. `precision` applies to the backbone forward that gives q_xs; the gradient is always fp32.
+        Deviation from the reference: the value net is evaluated in the mode the caller left it in (the harness and the CLI put it in
+        eval mode for every task; the reference's decode_classfier.py leaves it in train mode for task "rna", i.e. dropout on and
+        batch-statistics BatchNorm, which makes that run irreproducible). guidance_scale=None raises ValueError (the reference fails
+        with a TypeError). A batch-sharded decode is refused."""
+        self._classifier_checks(guidance_scale)
+        B, L, S = self._batch_size(eval_sp_size), self.config.model.length, self._num_steps(num_steps)
+        sched, _, _ = self._schedule(S, eps)
+        x = torch.full((B, L), self.mask_index, dtype=torch.uint8, device=self.device)      # _sample_prior
+        onehot = torch.zeros((B, L, 4), dtype=torch.float32, device=self.device)            # transform_samples of the prior
+        for i in range(S):
+            with torch.no_grad():
+                logits = self._prior_logits(x) if i == 0 else self._backbone_logits(x)
+            self._record(logits, None, x)
+            x, onehot, _ = self._classifier_step(x, onehot, logits, sched[i, 2], sched[i, 1], pre_scorer_embedding, pre_scorer_head,
+                                                 guidance_scale, i)
+        with torch.no_grad():
+            return self._noise_removal(x)
+
+    controlled_sample_classifier = controlled_sample_classfier
 
     # ------------------------------------------------------------------ outer loops ----
     @_decode_scope

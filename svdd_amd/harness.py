@@ -1,5 +1,5 @@
 """Decode harness — mirror of the reference's `Enformer.BaseModel.controlled_decode*`
-(reference Enformer.py:399-477, 479-557, 719-813) for the SVDD decode path.
+(reference Enformer.py:399-477, 479-557, 560-637, 639-716, 719-813) for the SVDD decode path.
 
 The reference's `BaseModel.__init__` hard-wires checkpoint paths, Hydra and `.cuda()`
 (Enformer.py:75-131); there are no checkpoints offline, so here the three nets are passed in:
@@ -148,21 +148,34 @@ class BaseModel(nn.Module):
         return self._decode(gen_batch_num, sample_M, lambda: self.ref_model.controlled_sample_TDS(
             self.reward_model, alpha, eval_sp_size=self.NUM_SAMPLES_PER_BATCH, sample_M=sample_M))
 
-    def controlled_decode_DPS(self, gen_batch_num, sample_M, guidance_scale):
-        """DPS baseline (reference Enformer.py:560-637). The guided decodes back-propagate through the backbone
-        and the reward net, so they run with autograd on; the evaluation / baseline part runs under no_grad.
-        (Scoring consumes no RNG, so decoding all guided batches first keeps the reference's RNG order.)"""
+    def _decode_guided_with_grad(self, gen_batch_num, sample_M, guided):
+        """_decode for samplers whose guided decodes back-propagate: the gen_batch_num guided batches run first with autograd on (each
+        with the Philox key _decode would give it), then the evaluation / baseline part under no_grad. Scoring consumes no RNG, so
+        decoding all guided batches first keeps the reference's RNG order."""
         m = self.ref_model
         base, out = int(getattr(m, "philox_seed", 0)), []
         try:
             for k in range(gen_batch_num):
                 if getattr(m, "rng_mode", "replay") == "philox":
                     m.philox_seed = batch_seed(base, k)           # the key _decode would give guided batch k
-                out.append(m.controlled_sample_DPS(self.reward_model, guidance_scale,
-                                                   eval_sp_size=self.NUM_SAMPLES_PER_BATCH, sample_M=sample_M))
+                out.append(guided())
         finally:
             if hasattr(m, "philox_seed"):
                 m.philox_seed = base
         batches = iter(out)
         with torch.no_grad():
             return self._decode(gen_batch_num, sample_M, lambda: next(batches))
+
+    def controlled_decode_DPS(self, gen_batch_num, sample_M, guidance_scale):
+        """DPS baseline (reference Enformer.py:560-637). The guided decodes back-propagate through the backbone
+        and the reward net, so they run with autograd on; the evaluation / baseline part runs under no_grad."""
+        return self._decode_guided_with_grad(gen_batch_num, sample_M, lambda: self.ref_model.controlled_sample_DPS(
+            self.reward_model, guidance_scale, eval_sp_size=self.NUM_SAMPLES_PER_BATCH, sample_M=sample_M))
+
+    def controlled_decode_classfier(self, gen_batch_num, guidance_scale, sample_M=10):
+        """Classifier guidance (reference Enformer.py:639-716): gen_batch_num guided batches (sample_M is not passed to the sampler,
+        as in the reference), then gen_batch_num * sample_M un-guided baseline batches, then the top-k. The guided decodes need
+        autograd only where the value net's gradient does not run on the fused kernels. The value net is used in the mode it is in:
+        unlike the reference's decode_classfier.py for task "rna", nothing here switches it to train mode."""
+        return self._decode_guided_with_grad(gen_batch_num, sample_M, lambda: self.ref_model.controlled_sample_classfier(
+            self.embedding, self.head, eval_sp_size=self.NUM_SAMPLES_PER_BATCH, guidance_scale=guidance_scale))

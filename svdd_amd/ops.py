@@ -109,6 +109,33 @@ def sample_categorical(q, x, M, rng):
     return cand, onehot
 
 
+def classifier_propose(logits, x, grad4, dm, mcs, scale, rng, want_onehot=True, want_q=False, x_next=None, onehot=None):
+    """One classifier-guidance draw per position (svdd_classifier_propose): w = q_xs + scale * cat(grad4, 0), signed, one categorical
+    draw, merged with copy_flag. grad4 fp32 [B,L,4]. -> (x_next u8 [B,L], onehot f32 [B,L,4] | None, un-guided q_xs f32 [B,L,5] (same
+    strides as logits) | None)."""
+    logits = _need(logits, torch.float32, "logits")
+    x = _need(x, torch.uint8, "x").contiguous()
+    g = _need(grad4, torch.float32, "grad4").contiguous()
+    B, L = x.shape
+    logits, layout = layout_of(logits)
+    assert logits.shape == (B, L, 5) and g.shape == (B, L, 4), (logits.shape, g.shape, x.shape)
+    if x_next is None:
+        x_next = torch.empty((B, L), dtype=torch.uint8, device=x.device)
+    if want_onehot and onehot is None:
+        onehot = torch.empty((B, L, 4), dtype=torch.float32, device=x.device)
+    q = _empty_like_layout(logits, layout) if want_q else None
+    if rng.uniforms is not None:
+        u = _need(rng.uniforms, torch.float32, "uniforms")
+        rows = rng.uniforms_rows if rng.uniforms_rows else B
+        assert u.is_contiguous() and u.numel() == rows * L * 5 and rng.row_offset * bool(rng.uniforms_rows) + B <= rows, (u.shape, B, L)
+    rs = rng.c_struct(layout)
+    rc = _lib.lib().svdd_classifier_propose(logits.data_ptr(), layout, x.data_ptr(), g.data_ptr(), float(dm), float(mcs), float(scale),
+                                            B, L, ctypes.byref(rs), x_next.data_ptr(), onehot.data_ptr() if want_onehot else None,
+                                            q.data_ptr() if q is not None else None, _stream())
+    _lib.check(rc, "svdd_classifier_propose")
+    return x_next, (onehot if want_onehot else None), q
+
+
 def select(scores, cand, mode=SELECT_ARGMAX, rng=None, want_soft=True, x_next=None):
     """-> (x_next u8 [B,L], soft f32 [B,M] | None, idx i32 [B])."""
     cand = _need(cand, torch.uint8, "cand").contiguous()
