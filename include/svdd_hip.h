@@ -505,11 +505,12 @@ int svdd_abi_version(void);
  *
  * svdd_trunk_gemm        out[M, N] = act(sum_{t < T} A[rows + t - T/2, Cin] W_t[Cin, N] + bias) (+ resid), fp32 [M, ldo].
  *                        a_hi / a_lo: bf16 operand planes [>= M + 128 + T rows, lda] with T/2 readable rows before row 0;
+ *                        lda % 8 == 0 (fp32 planes: lda % 4 == 0) and ldo % 4 == 0: rows are moved in 16-byte pieces;
  *                        w: bf16 weight fragments packed by svdd_amd.fused_trunk.pack_gemm_weight ; N % 128 == 0, Cin % 32 == 0,
  *                        T odd ; act 0 none, 1 relu, 2 x * sigmoid(1.702 x).
  *                        Fused second output (out_hi != NULL; out may then be NULL): the operand planes of the NEXT GEMM,
  *                        post_act(post_scale[c] y + post_shift[c]) -> (out_hi, out_lo) [M, N] (scale / shift NULL: identity), zero in
- *                        the last `pad` rows of every sequence — what svdd_trunk_act_split would write from `out`. The
+ *                        the last `pad` rows of every sequence (row stride N, whatever ldo is) — what svdd_trunk_act_split would write from `out`. The
  *                        output planes must not be the input planes. Two kernels behind it (SVDD_OPT_TRUNK_GEMM_VERSION).
  * svdd_trunk_act_split   x fp32 [rows, C] -> act(scale[c] x + shift[c]) (scale / shift NULL: identity) -> planes hi (lo may be
  *                        NULL) ; the last `pad` rows of every sequence are written as zeros.

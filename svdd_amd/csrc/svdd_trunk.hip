@@ -882,8 +882,12 @@ int svdd_trunk_gemm(const void* a_hi, const void* a_lo, const void* w, const flo
                     int M, int N, int Cin, int T, int lda, int ldo, int act, const int32_t* count, int rows_per_seq,
                     void* out_hi, void* out_lo, const float* post_scale, const float* post_shift, int post_act, int pad,
                     void* stream) {
+  // lda: every A row is read in 16-byte pieces (uint4 loads of the 128 x 128 kernel, 16-byte LDS-DMA rows of the 256 x 256 one),
+  // so a row must start 16-byte aligned: lda % 8 == 0 for bf16 planes, % 4 for fp32 planes. ldo: the epilogue moves 4 floats
+  // of out / resid at a time (f32x4), ldo % 4 == 0. The fused second output is always [M, N] (row stride N).
   if (!a_hi || !w || (!out && !out_hi) || M <= 0 || N <= 0 || (N % G_BN) || Cin <= 0 || (Cin % G_BK) || T < 1 || !(T & 1) ||
-      lda < Cin || ldo < N || act < 0 || act > 2 || ((count || pad > 0) && rows_per_seq <= 0) || (out_lo && !out_hi) ||
+      lda < Cin || ldo < N || (lda % (g_trunk_planes_f32 ? 4 : 8)) || (ldo & 3) || act < 0 || act > 2 ||
+      ((count || pad > 0) && rows_per_seq <= 0) || (out_lo && !out_hi) ||
       ((post_scale == nullptr) != (post_shift == nullptr)) || post_act < 0 || post_act > 2 || pad < 0 ||
       out_hi == a_hi || (out_lo && out_lo == a_lo))
     return SVDD_E_ARG;

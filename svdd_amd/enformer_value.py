@@ -101,24 +101,25 @@ class EnformerConvTower(nn.Module):
         return x
 
 
-def _positional_features(length, num_features, device):
+def _positional_features(length, num_features, device, dtype=torch.float32):
     """Enformer's relative-position basis over distances -(L-1)..(L-1): three families (exponential decay,
-    central mask, gamma pdf), each num_features/6 wide, concatenated with their sign-antisymmetric copies."""
+    central mask, gamma pdf), each num_features/6 wide, concatenated with their sign-antisymmetric copies. Built in
+    `dtype` (the attention input's: a float64 module is float64 throughout)."""
     assert num_features % 6 == 0
     nb = num_features // 6
-    dist = torch.arange(-length + 1, length, device=device, dtype=torch.float32)
+    dist = torch.arange(-length + 1, length, device=device, dtype=dtype)
     ad = dist.abs()[:, None]
     # exponential: half-lives geometrically spaced between 3 and L
     max_range = math.log2(length)
-    half_life = 2 ** torch.linspace(3.0, max_range, nb, device=device)[None, :]
+    half_life = 2 ** torch.linspace(3.0, max_range, nb, device=device, dtype=dtype)[None, :]
     f_exp = torch.exp(-math.log(2.0) / half_life * ad)
     # central mask: |d| <= 2^(i+1) - 1
-    widths = (2 ** torch.arange(1, nb + 1, device=device, dtype=torch.float32) - 1)[None, :]
-    f_mask = (widths > ad).float()
+    widths = (2 ** torch.arange(1, nb + 1, device=device, dtype=dtype) - 1)[None, :]
+    f_mask = (widths > ad).to(dtype)
     # gamma pdf with means spread over the sequence
     stddev = length / (2 * nb)
     start_mean = length / nb
-    mean = torch.linspace(start_mean, float(length), nb, device=device)[None, :]
+    mean = torch.linspace(start_mean, float(length), nb, device=device, dtype=dtype)[None, :]
     conc = (mean / stddev) ** 2
     rate = mean / stddev ** 2
     log_unnorm = torch.xlogy(conc - 1.0, ad) - rate * ad
@@ -158,7 +159,7 @@ class RelPosAttention(nn.Module):
         q = self.to_q(x).view(n, length, h, self.dim_key).transpose(1, 2) * self.dim_key ** -0.5
         k = self.to_k(x).view(n, length, h, self.dim_key).transpose(1, 2)
         v = self.to_v(x).view(n, length, h, self.dim_value).transpose(1, 2)
-        pos = _positional_features(length, self.num_rel_pos_features, x.device)
+        pos = _positional_features(length, self.num_rel_pos_features, x.device, x.dtype)
         rel_k = self.to_rel_k(pos).view(2 * length - 1, h, self.dim_key).transpose(0, 1)        # [h, 2L-1, dk]
         rel_logits = _relative_shift(torch.einsum("bhid,hjd->bhij", q + self.rel_pos_bias, rel_k))
         # content logits (q + content bias) k^T plus the positional logits as an additive bias; scale already in q

@@ -439,8 +439,34 @@ class FusedEnformerValueNet(nn.Module):
 
     @torch.no_grad()
     def forward_tokens(self, tok, count=None, shared=None):
-        """See _forward_tokens. The plane format is a host-side switch of the library (svdd_set_option): set for the span of the
-        call (every launch of the call is enqueued inside it), restored on the way out."""
+        """See _forward_tokens: tok [n, L] u8 -> scores [n, n_tasks, 1]."""
+        zs, n, T, seqs = self._scoped_forward(tok, count, shared)
+        sc = self._head(zs, n, T)
+        if seqs is None:
+            return sc[:, :, None]
+        s = torch.empty_like(sc)
+        S = len(seqs)
+        for k, (a, b) in enumerate(seqs):
+            s[k::S] = sc[a:b]
+        return s[:, :, None]
+
+    @torch.no_grad()
+    def embed_tokens(self, tok, count=None):
+        """The trunk's output without the head: tok [n, L] u8 -> zs [n, T, pw_out] fp32 in row order (what the head reduces; the
+        same launches as forward_tokens). With `count`, rows beyond it are undefined."""
+        zs, n, T, seqs = self._scoped_forward(tok, count, None)
+        z = zs.view(n, T, -1)
+        if seqs is None:
+            return z
+        out = torch.empty_like(z)
+        S = len(seqs)
+        for k, (a, b) in enumerate(seqs):
+            out[k::S] = z[a:b]
+        return out
+
+    def _scoped_forward(self, tok, count, shared):
+        """_forward_tokens with the library's plane format set for the span of the call (a host-side switch, svdd_set_option:
+        every launch of the call is enqueued inside it), restored on the way out."""
         with _OPTION_LOCK:                       # (two value nets of different precision on two host threads must not interleave)
             prev_planes = _lib.set_option(6, 1 if self.f32 else 0)
             prev_conc = _lib.current_option(4, 51)
@@ -451,7 +477,9 @@ class FusedEnformerValueNet(nn.Module):
                 _lib.set_option(4, prev_conc)
 
     def _forward_tokens(self, tok, count=None, shared=None):
-        """tok [n, L] u8 -> scores [n, n_tasks, 1]; count: int32 device scalar = live rows (rows beyond it are undefined).
+        """tok [n, L] u8 -> (zs [n T, pw_out], n, T, seqs); count: int32 device scalar = live rows (rows beyond it are undefined).
+        seqs None: zs is in row order; else the batch ran as S = len(seqs) parts, rows k, k + S, ... of tok at sequences
+        seqs[k][0] .. seqs[k][1] - 1 of zs.
         shared = (parent_tok [B, L] u8, parent_idx int32 [n], div): row c of tok is a candidate of row parent_idx[c] // div of
         parent_tok and differs from it at a few positions; the first levels are then computed on those windows only (exact)."""
         assert tok.is_cuda and tok.dtype == torch.uint8 and tok.is_contiguous()
@@ -509,13 +537,8 @@ class FusedEnformerValueNet(nn.Module):
             for k in range(S):
                 main.wait_stream(self._side[k])
             self.last_window_rows = None if stats[0] is None else sum(stats[1:], stats[0])
-            sc = self._head(zs, n, T)
-            s = torch.empty_like(sc)
-            for k in range(S):
-                s[k::S] = sc[zoff[k] // T: zoff[k + 1] // T]
-            return s[:, :, None]
-        s = self._head(zs, n, T)
-        return s[:, :, None]
+            return zs, n, T, [(zoff[k] // T, zoff[k + 1] // T) for k in range(S)]
+        return zs, n, T, None
 
     def _head(self, zs, n, T):
         """ConvHead: 1 x 1 convolution to n_tasks + mean over the T tokens, [n T, pw_out] -> [n, n_tasks]. A row-wise reduction, not

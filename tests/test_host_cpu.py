@@ -46,6 +46,15 @@ def test_argument_validation_without_gpu():
     one = ctypes.c_void_p(64)                                              # a non-NULL pointer that is never dereferenced
     assert L.svdd_trunk_gemm(None, None, None, None, None, None, 1, 128, 32, 1, 32, 128, 0, None, 0, None, None, None, None, 0, 0, None) == _lib.E_ARG
     assert L.svdd_trunk_gemm(one, None, one, None, None, one, 1, 100, 32, 1, 32, 100, 0, None, 0, None, None, None, None, 0, 0, None) == _lib.E_ARG   # N % 128
+    # strides the 16-byte row pieces cannot honour: lda % 8 (bf16 planes) / % 4 (fp32 planes), ldo % 4
+    assert L.svdd_trunk_gemm(one, None, one, None, None, one, 1, 128, 32, 1, 36, 128, 0, None, 0, None, None, None, None, 0, 0, None) == _lib.E_ARG
+    assert L.svdd_trunk_gemm(one, None, one, None, None, one, 1, 128, 32, 1, 32, 130, 0, None, 0, None, None, None, None, 0, 0, None) == _lib.E_ARG
+    prev = _lib.set_option(6, 1)
+    try:
+        assert L.svdd_trunk_gemm(one, None, one, None, None, one, 1, 128, 32, 1, 34, 128, 0, None, 0, None, None, None, None, 0, 0, None) == _lib.E_ARG
+        assert L.svdd_trunk_gemm(one, None, one, None, None, one, 1, 128, 32, 1, 32, 129, 0, None, 0, None, None, None, None, 0, 0, None) == _lib.E_ARG
+    finally:
+        _lib.set_option(6, prev)
     assert L.svdd_trunk_windows(one, one, one, 1, 4, 201, 7, 2, 4, None, one, one, one, None) == _lib.E_ARG      # an odd length below the last shared level
     assert L.svdd_trunk_windows(one, one, one, 1, 4, 200, 7, 1, 5, None, one, one, one, None) == _lib.E_ARG      # more window slots than the kernels hold
     assert L.svdd_trunk_windows(one, one, one, 1, 4, 300, 7, 1, 4, None, one, one, one, None) == _lib.E_ARG      # L > 256

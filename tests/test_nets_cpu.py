@@ -2,6 +2,7 @@
 reproduce the reference's outputs from the reference's own weights (fixture nets_tiny.npz, made
 by tests/golden/make_golden.py). CPU, fp32; same ATen kernels => tight tolerance."""
 import numpy as np
+import pytest
 import torch
 
 from svdd_amd.backbone import CNNModel
@@ -166,6 +167,58 @@ def test_dit_equals_reference_fixture():
     assert float((out - torch.from_numpy(g["logits"])).abs().max()) <= 2e-5
     assert float((out0 - torch.from_numpy(g["logits_sigma0"])).abs().max()) <= 2e-5
 
+
+
+@pytest.mark.parametrize("L,kw,T", [(50, dict(n_conv=6, channels=768, n_transformers=2, n_heads=8, key_len=8), 1),
+                                    (37, dict(n_conv=4, channels=768, n_transformers=2, n_heads=2, key_len=64), 3)])
+def test_enformer_trunk_runs_in_float64(L, kw, T):
+    """The same trunk and head in .double() (positional features in the input's dtype) agree with fp32 to fp32 rounding, at
+    T = 1 and T = 3 tokens left for the transformer tower; the fp32 features are unchanged by the dtype argument."""
+    import copy
+    from svdd_amd.enformer_value import EnformerTrunk, _positional_features
+    from svdd_amd.value_nets import ConvHead
+    from tests.trunk_ref import randomise
+    torch.manual_seed(L)
+    trunk = EnformerTrunk(**kw).eval()
+    head = ConvHead(1, 2 * kw["channels"]).eval()
+    randomise(trunk, head, L)
+    x = torch.zeros(4, L, 4)
+    x.scatter_(2, torch.randint(0, 4, (4, L, 1)), 1.0)
+    x[0, L // 2:] = 0.0
+    t64, h64 = copy.deepcopy(trunk).double(), copy.deepcopy(head).double()
+    with torch.no_grad():
+        y32, y64 = trunk(x), t64(x.double())
+        s32, s64 = head(y32).reshape(-1), h64(y64).reshape(-1)
+    assert y64.dtype == torch.float64 and y64.shape[2] == T
+    ey = float((y32.double() - y64).abs().max()) / float(y64.abs().max())
+    es = float((s32.double() - s64).abs().max()) / float(s64.abs().max())
+    print(f"fp32 vs fp64 module: embedding {ey:.2e}, score {es:.2e}")
+    assert ey <= 2e-4 and es <= 1e-5, (ey, es)      # worst measured (T = 3): 6.0e-5 / 3.0e-6
+    assert torch.equal(_positional_features(T, 96, "cpu"), _positional_features(T, 96, "cpu", torch.float32))
+    p64 = _positional_features(T, 96, "cpu", torch.float64)
+    assert p64.dtype == torch.float64 and float((p64 - _positional_features(T, 96, "cpu").double()).abs().max()) <= 2e-4   # measured: 4.9e-5 (the fp32 lgamma)
+
+
+@pytest.mark.parametrize("T,heads,dk,dv", [(1, 2, 16, 48), (2, 8, 8, 12), (3, 2, 64, 24), (4, 4, 16, 6)])
+def test_attention_restatement_equals_the_module_fp64(T, heads, dk, dv):
+    """tests/trunk_ref.attn_small_ref (the float64 reference of svdd_trunk_attn_small: q k v from one row, relative-position
+    keys, the module's own relative shift) composed with the projections equals RelPosAttention.forward in float64."""
+    from svdd_amd.enformer_value import RelPosAttention, _positional_features
+    from tests.trunk_ref import attn_small_ref
+    torch.manual_seed(T * heads)
+    dim, n = 40, 3
+    m = RelPosAttention(dim, heads, dk, dv, dv).double()
+    with torch.no_grad():
+        m.to_out.weight.normal_(0, dim ** -0.5)
+        m.to_out.bias.normal_(0, 0.1)
+        x = torch.randn(n, T, dim, dtype=torch.float64)
+        want = m(x)
+        qkv = torch.cat([m.to_q(x), m.to_k(x), m.to_v(x)], dim=-1).reshape(n * T, -1)
+        rel_k = m.to_rel_k(_positional_features(T, dv, "cpu", torch.float64)).view(2 * T - 1, heads, dk).transpose(0, 1)
+        o = attn_small_ref(qkv, rel_k, m.rel_content_bias.reshape(heads, dk), m.rel_pos_bias.reshape(heads, dk), n, T, heads, dk, dv)
+        got = m.to_out(o).view(n, T, dim)
+    assert float((got - want).abs().max()) <= 1e-12 * float(want.abs().max())
+    assert float(want.std()) > 0
 
 def _g17_modules():
     """Builds this repo's EnformerTrunk + ConvHead at g17's size with the fixture's (seed-regenerated) reference weights,

@@ -6,27 +6,13 @@ import numpy as np
 import pytest
 import torch
 
+from tests.trunk_ref import randomise
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
-def _randomise(emb, head, seed):
-    """Non-trivial BatchNorm statistics, attention output projections (zero at init) and pooling logits."""
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    with torch.no_grad():
-        for m in emb.modules():
-            if isinstance(m, torch.nn.BatchNorm1d):
-                m.running_mean.copy_(torch.randn(m.num_features, generator=g) * 0.1)
-                m.running_var.copy_(torch.rand(m.num_features, generator=g) + 0.5)
-                m.weight.copy_(1.0 + 0.2 * torch.randn(m.num_features, generator=g))
-                m.bias.copy_(0.1 * torch.randn(m.num_features, generator=g))
-        for blk in emb.transformer_tower:
-            w = blk.mha.to_out.weight
-            w.copy_(torch.randn(w.shape, generator=g) * (w.shape[1] ** -0.5))
-            blk.mha.to_out.bias.copy_(torch.randn(w.shape[0], generator=g) * 0.05)
-        for blk in emb.conv_tower.blocks:
-            pw = blk[1].pool.to_attn_logits.weight
-            pw.add_((torch.randn(pw.shape, generator=g) * 0.05).to(pw.device))
+_randomise = randomise         # (tests/trunk_ref.py: shared with the kernel and CPU tests of the trunk)
 
 
 @pytest.mark.parametrize("precision,tol", [("f32", 2e-5), ("bf16x3", 1e-4), ("bf16", 3e-2)])
@@ -346,3 +332,109 @@ def test_cli_mc_with_the_enformer_value_trunk(tmp_path):
     z = np.load(path)
     assert path.endswith("dna-HepG2.npz") and set(z.files) == {"decoding", "baseline"}
     assert z["decoding"].shape == (3,) and np.isfinite(z["decoding"]).all() and np.isfinite(z["baseline"]).all()
+
+
+# ---------------------------------------------------------------------------------------------- against the float64 module
+def _module_fp64(emb, head, onehot):
+    """The same trunk and head in float64 -> (embedding [n, T, 2C], scores [n]); on the GPU, or on the CPU for an op the GPU has
+    no float64 kernel for."""
+    import copy
+    e64, h64 = copy.deepcopy(emb).double(), copy.deepcopy(head).double()
+    try:
+        z = e64(onehot.double())
+        dev = "gpu"
+    except RuntimeError:
+        e64, h64 = e64.cpu(), h64.cpu()
+        z = e64(onehot.double().cpu())
+        dev = "cpu"
+    return z.transpose(1, 2).to(DEV), h64(z).reshape(-1).to(DEV), dev
+
+
+E2E_CONFIGS = [   # name, L, trunk kwargs, rows, tokens left for the transformer tower
+    ("T1", 50, dict(n_conv=6, channels=768, n_transformers=2, n_heads=8, key_len=8), 24, 1),
+    ("T3", 37, dict(n_conv=4, channels=768, n_transformers=2, n_heads=2, key_len=64), 24, 3),
+    ("C4", 200, None, 6, 2),
+    ("T13", 200, dict(n_conv=4, channels=768, n_transformers=2, n_heads=4, key_len=16), 16, 13),
+]
+# worst case measured on the MI355X (embedding: max abs error / max |embedding|; scores: centred, / spread across rows)
+E2E_BARS = {"f32": (2e-4, 2.5e-3),          # measured: 6.5e-5 (T3) / 8.4e-4 (C4)
+            "bf16x3": (2e-4, 6e-3),       # measured: 7.1e-5 (T3) / 2.1e-3 (C4)
+            "bf16": (2.5e-2, 2.5)}        # measured: 8.9e-3 (C4) / 0.96 (T1): one-pass bf16 scores are as wide as their spread
+
+
+@pytest.mark.parametrize("name,L,kw,n,T", E2E_CONFIGS, ids=[c[0] for c in E2E_CONFIGS])
+def test_fused_trunk_against_the_fp64_module(name, L, kw, n, T):
+    """embed_tokens in every precision against the float64 module's embedding, elementwise (thousands of input-dependent
+    values per row, where the score is one near-constant number), and centred scores against the spread of the fp64 scores
+    across rows. f32: the fused error is at most a few times the fp32 module's own error against fp64. Configs with
+    T = 1 (an RNA-length sequence after 6 levels), T = 3 (odd lengths 37 / 19 / 5 / 3), T = 2 (full-size C4) and T = 13 (the
+    attention outside svdd_trunk_attn_small)."""
+    from svdd_amd import synthetic
+    from svdd_amd.fused_trunk import FusedEnformerValueNet, _level_len
+    small = dict(hidden_dim=32, num_cnn_stacks=1, enformer_kwargs=kw) if kw else {}
+    _, emb, head, _ = synthetic.build("dna", DEV, value="enformer", **small)
+    _randomise(emb, head, L + n)
+    assert _level_len(L, len(emb.conv_tower.blocks)) == T
+    g = torch.Generator(device=DEV).manual_seed(L + 7)
+    tok = torch.randint(0, 5, (n, L), device=DEV, generator=g, dtype=torch.uint8)
+    tok[0, L // 2:] = 4
+    onehot = (torch.nn.functional.one_hot(tok.long().clamp(max=3), 4) * (tok != 4)[..., None]).float()
+    with torch.no_grad():
+        z64, r64, where = _module_fp64(emb, head, onehot)
+        y32 = emb(onehot)
+        z32, r32 = y32.transpose(1, 2), head(y32).reshape(n)
+        zmax = float(z64.abs().max())
+        spread = float(r64.max() - r64.min())
+        rc = r64 - r64.mean()
+        mod_z = float((z32.double() - z64).abs().max()) / zmax
+        mod_s = float(((r32.double() - r32.double().mean()) - rc).abs().max()) / spread
+        print(f"ERR e2e[{name}] fp64 module on {where}: |z| max {zmax:.3f}, score spread {spread:.3e}; "
+              f"fp32 module: embedding {mod_z:.3e} scores {mod_s:.3e}")
+        assert spread > 0
+        errs = {}
+        for prec in ("f32", "bf16x3", "bf16"):
+            fn = FusedEnformerValueNet(emb, head, prec)
+            z = fn.embed_tokens(tok)
+            s = fn.forward_tokens(tok).reshape(n)
+            assert z.shape == (n, T, 2 * emb.pointwise_conv.conv.in_channels)
+            assert torch.equal(s, fn._head(z.reshape(n * T, -1), n, T).reshape(n))
+            ez = float((z.double() - z64).abs().max()) / zmax
+            es = float(((s.double() - s.double().mean()) - rc).abs().max()) / spread
+            print(f"ERR e2e[{name},{prec}] embedding {ez:.3e} scores {es:.3e}")
+            errs[prec] = (ez, es)
+    for prec, (ez, es) in errs.items():
+        bz, bs = E2E_BARS[prec]
+        assert ez <= bz and es <= bs, (prec, ez, es)
+    ez, es = errs["f32"]
+    # the fp32 module's own error against fp64 is the yardstick (it varies from run to run with the library kernels the module
+    # gets: C4 scores 1.6e-4 .. 3.5e-4); measured ratios: at most 5.1 (C4 scores), 2.5 (embedding)
+    assert ez <= 12 * mod_z and es <= 12 * mod_s, (ez, mod_z, es, mod_s)
+
+
+def test_embed_tokens_row_order_on_streams():
+    """embed_tokens is in row order when the tower runs as 2 / 3 parts on as many streams (rows k, k + S, ... of each part at
+    their offsets in zs), the same bits as one chain; forward_tokens is the head applied to it, bit for bit; with a live
+    count, the live rows are the same bits."""
+    from svdd_amd import synthetic
+    from svdd_amd.fused_trunk import FusedEnformerValueNet
+    kw = dict(n_conv=4, channels=768, n_transformers=1, n_heads=4, key_len=16)
+    _, emb, head, _ = synthetic.build("dna", DEV, hidden_dim=32, num_cnn_stacks=1, value="enformer", enformer_kwargs=kw)
+    _randomise(emb, head, 6)
+    g = torch.Generator(device=DEV).manual_seed(6)
+    n, L, T = 160, 200, 13                                              # 2080 token rows: the tower streams engage
+    tok = torch.randint(0, 5, (n, L), device=DEV, generator=g, dtype=torch.uint8)
+    with torch.no_grad():
+        fn = FusedEnformerValueNet(emb, head, "bf16x3")
+        fn.tower_streams = 1
+        one = fn.embed_tokens(tok).clone()
+        assert fn.last_streams == 1
+        assert torch.equal(fn.forward_tokens(tok).reshape(n), fn._head(one.reshape(n * T, -1), n, T).reshape(n))
+        for S in (2, 3):
+            fn.tower_streams = S
+            z = fn.embed_tokens(tok)
+            assert fn.last_streams == S
+            assert torch.equal(z, one), S
+            assert torch.equal(fn.forward_tokens(tok).reshape(n), fn._head(z.reshape(n * T, -1), n, T).reshape(n))
+            cnt = torch.tensor([101], dtype=torch.int32, device=DEV)
+            assert torch.equal(fn.embed_tokens(tok, count=cnt)[:101], one[:101])
+    assert float(one.std(dim=0).mean()) > 0
