@@ -125,6 +125,45 @@ int svdd_classifier_propose(const float* logits, int layout, const uint8_t* x, c
                             int B, int L, const svdd_rng_t* rng, uint8_t* x_next, float* onehot_next, float* q_xs, void* stream);
 
 /*
+ * ELBO scoring of clean sequences (ABI 13): the continuous-time SUBS loss of the reference's Diffusion with the gosai
+ * configuration (T = 0, time_conditioning off, antithetic sampling, LogLinear noise), around ONE backbone forward of the
+ * masked rows (svdd_backbone_cnn_f32 / _lp or the DiT, unchanged):
+ *   svdd_elbo_mask replaces   _sample_t                                     diffusion_gosai.py:1660-1669
+ *                             sigma, dsigma = noise(t); move_chance         :1725-1729, noise_schedule.py:126-145
+ *                             q_xt                                          :738-749
+ *   svdd_elbo_nll replaces    gather of log_p at x0, - log_p * dsigma / expm1(sigma)   :1745-1757
+ *                             (and the per-row / per-sequence sums _loss and the nll metric take, :1759-1779, :50-71)
+ * Row r = k n + b of a launch is draw k (0 <= k < K) of sequence b (0 <= b < n).
+ *
+ * svdd_elbo_mask — x0 [n, L] u8 (tokens 0..3) -> xt [n K, L] u8: MASK where u < move_chance of the row, else x0;
+ *   nmasked [n K] i32 (may be NULL): masked positions per row.
+ *   REPLAY (rng->uniforms, uniforms_rows == 0): uniforms = K blocks of n L fp32, block k in [b][l] order — the torch.rand(n, L)
+ *     of q_xt in each of K consecutive _forward_pass_diffusion calls; move_chance_in [n K] = the rows' move_chance, computed by
+ *     the caller with the reference's fp32 torch ops (a 1-ulp difference would flip mask decisions). t, move_chance, w must be NULL.
+ *   PHILOX: move_chance_in must be NULL. Counter (word 0, 1, 2, 3) = (row_offset + b low, high, k << 16 | j, 3): stream word 3
+ *     (0 = svdd_propose / svdd_classifier_propose, 2 = the multinomial select). Block j = 0 gives t: u = top 24 bits of word 0,
+ *     e = (u / K + k / K) mod 1 — stratified over the sequence's OWN K draws, so results do not depend on how rows are sharded
+ *     or chunked — t = (1 - eps) e + eps; block j >= 1 gives the mask uniforms of positions 4 (j - 1) .. 4 (j - 1) + 3 (words 0..3,
+ *     top 24 bits). Written per row (each may be NULL): t, move_chance = (1 - eps) t, w = dsigma / expm1(sigma) = 1 / t (the
+ *     LogLinear identities), each evaluated in fp64 and rounded once to fp32. rng->step is not used. eps in (0, 1).
+ *   K <= 65535, L <= 262136.
+ *
+ * svdd_elbo_nll — logits [n K, L, 5] fp32 raw backbone output in `layout` (as svdd_subs_logp), xt [n K, L], x0 [n, L], w [n K]:
+ *   nll      [n K, L] fp32 (may be NULL): -(log p at x0) * w at masked positions, log p = svdd_subs_logp's arithmetic, one fp32
+ *            multiply; +0 at unmasked positions
+ *   row_sum  [n K] fp64: sum over l of nll, accumulated in fp64 in position order
+ *   seq_mean [n] fp64 (may be NULL): (sum over k of row_sum[k n + b], in draw order) / K
+ *   err      device i32 (may be NULL, caller-zeroed): set to 1 if x0 holds a token > 3 (those rows' values are NaN). The library
+ *            cannot refuse a device-side value without a synchronisation: the caller reads err after the stream and treats 1
+ *            as SVDD_E_ARG.
+ *   No result depends on the launch shape (one workgroup per sequence; fixed summation orders).
+ */
+int svdd_elbo_mask(const uint8_t* x0, int n, int L, int K, double eps, const svdd_rng_t* rng, const float* move_chance_in,
+                   uint8_t* xt, float* t, float* move_chance, float* w, int32_t* nmasked, void* stream);
+int svdd_elbo_nll(const float* logits, int layout, const uint8_t* xt, const uint8_t* x0, const float* w, int n, int L, int K,
+                  float* nll, double* row_sum, double* seq_mean, int32_t* err, void* stream);
+
+/*
  * svdd_select — replaces torch.stack(scores,1) -> softmax(dim=1) -> argmax(dim=1) ->
  * per-row Python gather + stack                     diffusion_gosai.py:1219-1227 (= :1451-1459)
  *
@@ -494,7 +533,7 @@ int svdd_device_info(char* arch, int arch_len, int* num_cu);
 
 /* ABI version of this header: bumped on any signature change. */
 int svdd_abi_version(void);
-#define SVDD_ABI_VERSION 12
+#define SVDD_ABI_VERSION 13
 
 /*
  * Enformer-shaped value trunk (BASELINE.json configs[3]; reference decode.py:78-80, Enformer.py:1271-1334 trunk, :1807-1884

@@ -13,7 +13,7 @@ CSRC = os.path.join(_HERE, "csrc")
 # SVDD_HIP_LIB: load another build of the library instead (the timing-experiment scripts under tools/ build patched
 # copies of the kernels in a scratch directory; the tracked sources are never edited in place)
 SO_PATH = os.environ.get("SVDD_HIP_LIB") or os.path.join(CSRC, "libsvdd_hip.so")
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 OK, E_ARG, E_LAUNCH, E_NODEVICE = 0, -1, -2, -3
 LAYOUT_BLV, LAYOUT_BVL = 0, 1
@@ -37,7 +37,7 @@ EXPORTS = (
     "svdd_backbone_set_workspace", "svdd_backbone_split_status", "svdd_backbone_cnn_save_f32", "svdd_backbone_cnn_grad_f32",
     "svdd_dps_probs", "svdd_dps_probs_bwd", "svdd_dps_guided_q", "svdd_reward_stem_f32", "svdd_reward_stem_bwd_f32",
     "svdd_conv1d_cl_gated_f32", "svdd_reward_tail_grad_f32", "svdd_sum_gate_f32", "svdd_gru_bidir_train2_f32", "svdd_gru_bidir_bwd2_f32",
-    "svdd_classifier_propose",
+    "svdd_classifier_propose", "svdd_elbo_mask", "svdd_elbo_nll",
 )
 OPT_FORCE_EXACT = 0
 
@@ -141,6 +141,8 @@ def lib():
     L.svdd_dps_probs.argtypes = [vp, vp, i32, i32, vp, vp]
     L.svdd_dps_probs_bwd.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
     L.svdd_classifier_propose.argtypes = [vp, i32, vp, vp, f32, f32, f32, i32, i32, ctypes.POINTER(SvddRng), vp, vp, vp, vp]
+    L.svdd_elbo_mask.argtypes = [vp, i32, i32, i32, ctypes.c_double, ctypes.POINTER(SvddRng), vp, vp, vp, vp, vp, vp, vp]
+    L.svdd_elbo_nll.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
     L.svdd_dps_guided_q.argtypes = [vp, vp, vp, vp, f32, f32, f32, i32, i32, vp, vp]
     L.svdd_reward_stem_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
     L.svdd_reward_stem_bwd_f32.argtypes = [vp, vp, vp, i32, i32, i32, vp]

@@ -53,6 +53,9 @@ def build_parser(method="mc"):
     p.add_argument("--load_checkpoint_path", default=None, help="value-function checkpoint ('model_state_dict')")
     p.add_argument("--reward_ckpt", default=None)
     p.add_argument("--out_dir", default="./log")
+    p.add_argument("--eval_nll", type=int, default=0, metavar="K",
+                   help="K > 0: also score the decoded and the baseline sequences by the pretrained model's ELBO (K draws per "
+                        "sequence, nats): npz keys decoding_nll / baseline_nll")
     p.add_argument("--presample", action="store_true",
                    help="pre-sample val_batch_num batches at construction like the reference's BaseModel.__init__")
     p.epilog = ("--method classfier evaluates the value net in eval mode for every task (the reference's decode_classfier.py leaves it in "
@@ -106,9 +109,14 @@ def run(args):
     gen_samples, value_func_preds, reward_model_preds, selected_baseline_preds, baseline_preds = out
     os.makedirs(args.out_dir, exist_ok=True)
     path = os.path.join(args.out_dir, f"{args.task}-{reward_name}{SUFFIX[args.method]}")
-    np.savez(path, decoding=reward_model_preds.cpu().numpy(), baseline=baseline_preds.cpu().numpy())
+    extra, nll_note = {}, ""
+    if args.eval_nll > 0:
+        extra = dict(decoding_nll=model.evaluate_nll(gen_samples, args.eval_nll).cpu().numpy(),
+                     baseline_nll=model.evaluate_nll(model.baseline_samples, args.eval_nll).cpu().numpy())
+        nll_note = f", nll decoding {extra['decoding_nll'].mean():.4f} baseline {extra['baseline_nll'].mean():.4f} nats"
+    np.savez(path, decoding=reward_model_preds.cpu().numpy(), baseline=baseline_preds.cpu().numpy(), **extra)
     print(f"wrote {path}.npz: decoding mean {reward_model_preds.mean().item():.4f} (n={reward_model_preds.numel()}), "
-          f"baseline mean {baseline_preds.mean().item():.4f}")
+          f"baseline mean {baseline_preds.mean().item():.4f}{nll_note}")
     return path + ".npz", out
 
 

@@ -12,6 +12,7 @@
 //   K5 finalize_kernel   noise-removal argmax
 //   K6 transform_kernel  tokens -> one-hot
 //   K7 subs_logp_kernel  SUBS re-parameterisation alone
+//   K11 elbo_mask_kernel / K12 elbo_nll_kernel  ELBO scoring: masking of x0, the weighted SUBS token loss and its sums
 //   K4 tds_resample_kernel  SMC/TDS resampling (baseline)
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -988,6 +989,139 @@ __global__ __launch_bounds__(256) void classifier_propose_kernel(ClassifierArgs 
                                                          c == 3 ? 1.0f : 0.0f);
 }
 
+// ------------------------------------------------- ELBO scoring: the mask draw and the weighted token loss (ABI 13) ----
+// The reference's continuous-time SUBS loss (diffusion_gosai.py:1660-1669 _sample_t, :738-749 q_xt, :1709-1757
+// _forward_pass_diffusion) around ONE backbone forward of the masked rows. Row r = k n + b of a launch is draw k of sequence b.
+//   elbo_mask_kernel  one wave per row: the row's (t, move_chance, w) (Philox) or the caller's move_chance (replay), then
+//                     xt = u < move_chance ? MASK : x0 at every position, and the row's masked count (wave sum).
+//   elbo_nll_kernel   one workgroup per sequence, wave w takes the draws k = w, w + 4, ...: per position
+//                     -(SUBS log-prob at x0) * w at masked positions (subs_logp_1's arithmetic, one fp32 multiply), +0 elsewhere;
+//                     the row sum in fp64 in position order (every lane sums the wave's 64 values in lane order, read by
+//                     v_readlane), then the mean over the K rows of the sequence in fp64 in draw order.
+// Both are functions of (sequence, draw, position) only: no result depends on the launch shape or on the other rows.
+constexpr uint32_t ELBO_STREAM = 3u;   // Philox counter word 3: 0 = K1 / K10 draws, 2 = the multinomial select, 3 = this
+
+struct ElboMaskArgs {
+  const uint8_t* x0; int n, L, K; double eps;
+  const float* uniforms; const float* mc_in; uint64_t seed, row_offset;
+  uint8_t* xt; float* t; float* mc; float* w; int32_t* nmasked;
+};
+
+template <bool REPLAY>
+__global__ __launch_bounds__(256) void elbo_mask_kernel(ElboMaskArgs a) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= (int64_t)a.n * a.K) return;                              // whole waves only: the row is the wave's
+  const int64_t k = r / a.n, b = r - k * a.n;
+  const uint64_t grow = a.row_offset + (uint64_t)b;
+  float mc;
+  if (REPLAY) {
+    mc = a.mc_in[r];
+  } else {
+    // t: counter block 0 of (row, draw); e = (u / K + k / K) mod 1 (antithetic over the sequence's own K draws, :1662-1665),
+    // t = (1 - eps) e + eps (:1666); LogLinear (noise_schedule.py:126-145): 1 - exp(-sigma(t)) = (1 - eps) t and
+    // dsigma / expm1(sigma) = 1 / t. Each in fp64, rounded once to fp32.
+    uint32_t c[4] = {(uint32_t)grow, (uint32_t)(grow >> 32), (uint32_t)k << 16, ELBO_STREAM};
+    philox4x32_10(c, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
+    const double K = (double)a.K;
+    double e = __dadd_rn(__ddiv_rn((double)u24(c[0]), K), __ddiv_rn((double)k, K));
+    if (e >= 1.0) e = __dsub_rn(e, 1.0);
+    const double one_m = __dsub_rn(1.0, a.eps);
+    const float t = (float)__dadd_rn(__dmul_rn(one_m, e), a.eps);
+    mc = (float)__dmul_rn(one_m, (double)t);
+    if (lane == 0) {
+      if (a.t) a.t[r] = t;
+      if (a.mc) a.mc[r] = mc;
+      if (a.w) a.w[r] = (float)__ddiv_rn(1.0, (double)t);
+    }
+  }
+  const uint8_t* x0 = a.x0 + b * a.L;
+  uint8_t* xt = a.xt + r * a.L;
+  int cnt = 0;
+  for (int l0 = lane * 4; l0 < a.L; l0 += 4 * WAVE) {
+    float u[4];
+    if (REPLAY) {
+      const float* ur = a.uniforms + r * a.L;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) u[i] = l0 + i < a.L ? ur[l0 + i] : 1.0f;
+    } else {
+      uint32_t c[4] = {(uint32_t)grow, (uint32_t)(grow >> 32), ((uint32_t)k << 16) | (uint32_t)(1 + l0 / 4), ELBO_STREAM};
+      philox4x32_10(c, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
+#pragma unroll
+      for (int i = 0; i < 4; ++i) u[i] = u24(c[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (l0 + i < a.L) {
+        const bool m = u[i] < mc;                                   // torch.rand(*x.shape) < move_chance, :745-746
+        xt[l0 + i] = m ? (uint8_t)MASK : x0[l0 + i];
+        cnt += m ? 1 : 0;
+      }
+    }
+  }
+  if (a.nmasked) {
+#pragma unroll
+    for (int off = WAVE / 2; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, WAVE);
+    if (lane == 0) a.nmasked[r] = cnt;
+  }
+}
+
+struct ElboNllArgs {
+  const float* logits; int layout; const uint8_t* xt; const uint8_t* x0; const float* w; int n, L, K;
+  float* nll; double* row_sum; double* seq_mean; int32_t* err;
+};
+
+__global__ __launch_bounds__(256) void elbo_nll_kernel(ElboNllArgs a) {
+  __shared__ double part[4];
+  const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
+  const int64_t b = blockIdx.x;
+  const uint8_t* x0 = a.x0 + b * a.L;
+  double acc = 0.0;
+  for (int k0 = 0; k0 < a.K; k0 += 4) {
+    const int k = k0 + wave;
+    if (k < a.K) {
+      const int64_t r = (int64_t)k * a.n + b;
+      const float wr = a.w[r];
+      double s = 0.0;
+      for (int base = 0; base < a.L; base += WAVE) {
+        const int l = base + lane;
+        float v = 0.0f;
+        if (l < a.L) {
+          const int xt = a.xt[r * a.L + l], tok = x0[l];
+          if (tok > 3) {
+            v = __int_as_float(0x7fc00000);                         // refused token: NaN here, err raised
+            if (a.err) a.err[0] = 1;
+          } else if (xt == MASK) {
+            float z[V], lp[V];
+#pragma unroll
+            for (int i = 0; i < V; ++i) z[i] = a.logits[at(a.layout, r, l, i, a.L)];
+            subs_logp_1(z, xt, lp);
+            float lx = lp[0];
+#pragma unroll
+            for (int i = 1; i < 4; ++i) lx = tok == i ? lp[i] : lx;
+            v = __fmul_rn(-lx, wr);                                 // - log_p_theta * (dsigma / expm1(sigma)), :1755-1757
+          }
+          if (a.nll) a.nll[r * a.L + l] = v;
+        }
+        const int vb = __float_as_int(v);
+#pragma unroll
+        for (int j = 0; j < WAVE; ++j)                              // position order; lanes past L hold +0 (s + 0 == s)
+          s = __dadd_rn(s, (double)__int_as_float(__builtin_amdgcn_readlane(vb, j)));
+      }
+      if (lane == 0) a.row_sum[r] = s;
+      if (lane == 0) part[wave] = s;
+    }
+    if (a.seq_mean) {
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        for (int j = 0; j < 4 && k0 + j < a.K; ++j) acc = __dadd_rn(acc, part[j]);   // draw order
+      }
+      __syncthreads();
+    }
+  }
+  if (a.seq_mean && threadIdx.x == 0) a.seq_mean[b] = __ddiv_rn(acc, (double)a.K);
+}
+
 // -------------------------------------------------------------------- K4 TDS resample ----
 // numpy's pairwise float32 sum (np.add.reduce), the order `ratio.sum()` uses at :1282: the array is halved (left half
 // rounded down to a multiple of 8) until a block has <= 128 elements; a block is summed with 8 running accumulators.
@@ -1729,6 +1863,33 @@ int svdd_classifier_propose(const float* logits, int layout, const uint8_t* x, c
                          rng->uniforms_layout, x_next, onehot_next, q_xs};
   hipLaunchKernelGGL(replay ? classifier_propose_kernel<true> : classifier_propose_kernel<false>, dim3((unsigned)((N + 255) / 256)),
                      dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch();
+}
+
+int svdd_elbo_mask(const uint8_t* x0, int n, int L, int K, double eps, const svdd_rng_t* rng, const float* move_chance_in,
+                   uint8_t* xt, float* t, float* move_chance, float* w, int32_t* nmasked, void* stream) {
+  if (!x0 || !rng || !xt || n <= 0 || L <= 0 || K <= 0 || K > 65535 || L > 4 * 65534) return SVDD_E_ARG;
+  const int64_t R = (int64_t)n * K;
+  if ((R + 3) / 4 >= ((int64_t)1 << 31)) return SVDD_E_ARG;
+  const bool replay = rng->kind == SVDD_RNG_REPLAY;
+  if (replay) {
+    if (!rng->uniforms || !move_chance_in || t || move_chance || w || rng->uniforms_rows != 0) return SVDD_E_ARG;
+  } else {
+    if (rng->kind != SVDD_RNG_PHILOX || move_chance_in || !(eps > 0.0 && eps < 1.0)) return SVDD_E_ARG;
+  }
+  const ElboMaskArgs a{x0, n, L, K, eps, rng->uniforms, move_chance_in, rng->seed, replay ? 0 : rng->row_offset,
+                       xt, t, move_chance, w, nmasked};
+  hipLaunchKernelGGL(replay ? elbo_mask_kernel<true> : elbo_mask_kernel<false>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0,
+                     (hipStream_t)stream, a);
+  return check_launch();
+}
+
+int svdd_elbo_nll(const float* logits, int layout, const uint8_t* xt, const uint8_t* x0, const float* w, int n, int L, int K,
+                  float* nll, double* row_sum, double* seq_mean, int32_t* err, void* stream) {
+  if (!logits || !xt || !x0 || !w || !row_sum || n <= 0 || L <= 0 || K <= 0 || bad_layout(layout)) return SVDD_E_ARG;
+  if ((int64_t)n * K * L * V >= ((int64_t)1 << 40)) return SVDD_E_ARG;
+  const ElboNllArgs a{logits, layout, xt, x0, w, n, L, K, nll, row_sum, seq_mean, err};
+  hipLaunchKernelGGL(elbo_nll_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, a);
   return check_launch();
 }
 

@@ -7,7 +7,8 @@ methods on the SVDD decode path, so `BaseModel`/`decode.py`-style callers work u
     forward, _process_sigma, _sample_prior, _sample, decode_sample, controlled_sample,
     controlled_sample_tweedie, controlled_sample_TDS, controlled_sample_DPS, controlled_sample_classfier,
     _ddpm_update_finetune[_controlled[_twedie|_TDS|_DPS]], _ddpm_update_finetune_classfier, compute_gradient,
-    transform_samples
+    transform_samples, and the ELBO scoring of clean sequences: _sample_t, q_xt, _forward_pass_diffusion, _loss
+    (plus sequence_nll / nll_metrics, the per-sequence API built on them)
 
 What differs is where the work runs: everything between "backbone logits" and "next x_t" is one
 or two launches of the hand-written HIP kernels (svdd_amd/csrc, C ABI include/svdd_hip.h) instead
@@ -71,8 +72,10 @@ Engine knobs (attributes; defaults reproduce the reference's observable behaviou
                    opaque value / reward net under torch.autocast; the x3 modes leave it in fp32.
 """
 import contextlib
+import math
 import warnings
 import weakref
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -81,6 +84,14 @@ from torch import nn
 
 from . import noise_schedule, ops
 from .backbone import CNNModel
+
+
+@dataclass
+class Loss:
+    """The reference's loss record (diffusion_gosai.py:43-47), returned by Diffusion._loss."""
+    loss: torch.Tensor
+    nlls: torch.Tensor
+    token_mask: torch.Tensor
 
 
 def _capturing():
@@ -205,6 +216,7 @@ class Diffusion(nn.Module):
         self._replay_stream = None       # the span of a sampler call; "host" = torch.rand on the host + upload (round 1-3)
         self._replay_checked = None      # scope id of the sharded replay decode whose generator state was compared across ranks
         self._classifier_fused_last = None   # classifier guidance: whether the last step's gradient ran on the fused kernels (no autograd)
+        self.elbo_trace = None           # set to a list to record (t, sigma, dsigma, move_chance, w, xt) of every _forward_pass_diffusion
 
     # ------------------------------------------------------------------ plumbing ----
     @property
@@ -1250,3 +1262,188 @@ class Diffusion(nn.Module):
                 self.state_trace.append(x.detach().clone())
             x = self._tds_step(x, sched[i, 2], sched[i, 1], reward_model, alpha, i, carry)
         return self._noise_removal(x, carry.get("logits") if carry else None)
+
+    # ------------------------------------------------------------------ ELBO scoring (ABI 13) ----
+    # The continuous-time SUBS loss of the reference (diffusion_gosai.py:1660-1669, 738-749, 1709-1779) in its live configuration
+    # (T = 0, time_conditioning off, antithetic sampling, no importance sampling / change of variables): for a clean batch x0,
+    # draw t, mask x0 with move_chance(t), run the backbone on the masked rows, and weight -log p(x0 | xt) by dsigma / expm1(sigma).
+    # svdd_elbo_mask draws the mask and svdd_elbo_nll evaluates the weighted SUBS loss and its sums; the backbone between them is
+    # the samplers' own dispatch (_backbone_logits: precision and the DiT apply unchanged).
+    #   replay (rng_mode "replay"): the reference's uniforms, from torch's CPU generator in the reference's order (torch.rand(n),
+    #           then torch.rand(n, L), per call); the per-row scalars with the reference's fp32 torch ops on the host. Afterwards
+    #           the generator is where the reference's call leaves it.
+    #   philox: keyed by (philox_seed, row_offset + b, draw k, position), t stratified over each sequence's own draws: a function of
+    #           the sequence and its index alone, whatever the chunking or sharding. A repeated call draws the same masks.
+    ELBO_WAVES_PER_CHUNK = 32             # default rows per backbone launch = 32 x the CU count (8192 on MI355X): whole waves of workgroups
+
+    def _elbo_checks(self, x0):
+        """The configurations the ELBO path covers; -> x0 as u8 on the model's device."""
+        self._require_gpu()
+        tr = self.config.training
+        if self.time_conditioning:
+            raise NotImplementedError("ELBO scoring: time-conditioned backbones are not supported (the fused backbone runs at sigma = 0)")
+        if self.T > 0:
+            raise NotImplementedError("ELBO scoring: only the continuous-time loss (T = 0) is supported, not the discrete-time "
+                                      "D3PM loss (diffusion_gosai.py:1713-1718, 1738-1746)")
+        if getattr(tr, "importance_sampling", False) or getattr(tr, "change_of_variables", False):
+            raise NotImplementedError("ELBO scoring: importance_sampling and change_of_variables are not supported")
+        if not isinstance(x0, torch.Tensor) or not x0.is_cuda:
+            raise ops.SvddError("x0 must be a GPU tensor (the ELBO path has no CPU fallback)")
+        if x0.dim() != 2 or x0.shape[0] == 0 or x0.shape[1] == 0:
+            raise ValueError(f"x0 must be [n, L] with n, L > 0, got {tuple(x0.shape)}")
+        if x0.dtype != torch.uint8:
+            lo, hi = torch.aminmax(x0)
+            if int(lo) < 0 or int(hi) > 255:
+                raise ops.SvddError("x0 holds a token outside 0..3")
+            x0 = x0.to(torch.uint8)
+        return x0.to(self.device).contiguous()
+
+    def _elbo_scalars(self, e):
+        """(t, sigma, dsigma, move_chance [n, 1], w) from the uniforms e = torch.rand(n), with the reference's fp32 torch ops on
+        the CPU: _sample_t (:1660-1669), noise(t) and move_chance (:1725-1729), w = dsigma / expm1(sigma) (:1757)."""
+        n = e.shape[0]
+        if self.config.training.antithetic_sampling:
+            offset = torch.arange(n, device=e.device) / n
+            e = (e / n + offset) % 1
+        t = (1 - self.sampling_eps) * e + self.sampling_eps
+        sigma, dsigma = self.noise(t)
+        move_chance = 1 - torch.exp(-sigma[:, None])
+        return t, sigma, dsigma, move_chance, dsigma / torch.expm1(sigma)
+
+    def _elbo_chunk_rows(self, chunk_rows):
+        if chunk_rows is None:
+            return self.ELBO_WAVES_PER_CHUNK * torch.cuda.get_device_properties(self.device).multi_processor_count
+        if int(chunk_rows) <= 0:
+            raise ValueError(f"chunk_rows must be positive, got {chunk_rows}")
+        return int(chunk_rows)
+
+    def _elbo_rows(self, xt, x0, w, K, want_tokens, want_mean, err):
+        """One backbone launch on the masked rows xt [n K, L] and svdd_elbo_nll -> (nll | None, row_sum, seq_mean | None)."""
+        return ops.elbo_nll(self._backbone_logits(xt), xt, x0, w, K, want_tokens=want_tokens, want_mean=want_mean, err=err)
+
+    def _replay_draw(self, x0_u8, chunk, want_tokens, err):
+        """One _forward_pass_diffusion of the reference in replay mode, over row chunks -> (nll [n, L] | None, row_sum [n])."""
+        n, L = x0_u8.shape
+        dev = x0_u8.device
+        t, sigma, dsigma, mc, w = self._elbo_scalars(torch.rand(n))          # the reference's first draw
+        u = torch.rand(n, L)                                                   # ... and its second (q_xt)
+        mc_d, w_d = mc.view(-1).to(dev), w.to(dev)
+        nll = torch.empty((n, L), dtype=torch.float32, device=dev) if want_tokens else None
+        row_sum = torch.empty(n, dtype=torch.float64, device=dev)
+        xt_all = torch.empty((n, L), dtype=torch.uint8, device=dev) if self.elbo_trace is not None else None
+        for s0 in range(0, n, chunk):
+            s1 = min(n, s0 + chunk)
+            xt, *_ = ops.elbo_mask(x0_u8[s0:s1], 1, ops.Rng(uniforms=u[s0:s1].to(dev, non_blocking=True)), move_chance=mc_d[s0:s1])
+            tok, rs, _ = self._elbo_rows(xt, x0_u8[s0:s1], w_d[s0:s1], 1, want_tokens, False, err)
+            row_sum[s0:s1] = rs
+            if want_tokens:
+                nll[s0:s1] = tok
+            if xt_all is not None:
+                xt_all[s0:s1] = xt
+        if self.elbo_trace is not None:
+            self.elbo_trace.append(dict(t=t, sigma=sigma, dsigma=dsigma, move_chance=mc, w=w, xt=xt_all))
+        return nll, row_sum
+
+    @_decode_scope
+    @torch.no_grad()
+    def _sample_t(self, n, device):
+        """t of the ELBO (:1660-1669): uniforms from torch's CPU generator (the reference's stream), antithetic offsets, fp32 ops on
+        the host -> t fp32 [n] on `device`."""
+        return self._elbo_scalars(torch.rand(n))[0].to(device)
+
+    @_decode_scope
+    @torch.no_grad()
+    def q_xt(self, x, move_chance):
+        """xt = where(torch.rand(*x.shape) < move_chance, MASK, x) (:738-749): the uniforms from torch's CPU generator, the compare
+        and the masking in svdd_elbo_mask. move_chance fp32 [n, 1] or [n]; -> xt [n, L] with x's dtype, on the GPU."""
+        self._require_gpu()
+        x_u8 = self._elbo_checks(x)
+        n, L = x_u8.shape
+        u = torch.rand(n, L).to(x_u8.device)
+        mc = move_chance.detach().float().reshape(-1).to(x_u8.device)
+        xt, *_ = ops.elbo_mask(x_u8, 1, ops.Rng(uniforms=u), move_chance=mc.expand(n).contiguous() if mc.numel() == 1 else mc)
+        return xt if x.dtype == torch.uint8 else xt.to(x.dtype)
+
+    @_decode_scope
+    @torch.no_grad()
+    def _forward_pass_diffusion(self, x0):
+        """The SUBS continuous-time loss of every token (:1709-1757): -log p(x0 | xt) * dsigma / expm1(sigma) where xt is masked,
+        0 elsewhere -> fp32 [n, L]. Replay: the reference's draws (t, then the mask uniforms) from torch's CPU generator; Philox:
+        svdd_elbo_mask with one draw per row, keyed by (philox_seed, row_offset + b)."""
+        x0_u8 = self._elbo_checks(x0)
+        chunk = self._elbo_chunk_rows(None)
+        err = torch.zeros(1, dtype=torch.int32, device=x0_u8.device)
+        if self.rng_mode == "replay":
+            nll, _ = self._replay_draw(x0_u8, chunk, True, err)
+        elif self.rng_mode == "philox":
+            n, L = x0_u8.shape
+            nll = torch.empty((n, L), dtype=torch.float32, device=x0_u8.device)
+            for s0 in range(0, n, chunk):
+                s1 = min(n, s0 + chunk)
+                xt, t, mc, w, _ = ops.elbo_mask(x0_u8[s0:s1], 1, ops.Rng(seed=self.philox_seed, row_offset=self.row_offset + s0),
+                                                eps=self.sampling_eps)
+                nll[s0:s1] = self._elbo_rows(xt, x0_u8[s0:s1], w, 1, True, False, err)[0]
+                if self.elbo_trace is not None:
+                    self.elbo_trace.append(dict(t=t, move_chance=mc, w=w, xt=xt))
+        else:
+            raise ValueError(f"rng_mode {self.rng_mode!r}")
+        ops.check_elbo_err(err)
+        return nll
+
+    @_decode_scope
+    @torch.no_grad()
+    def _loss(self, x0, attention_mask):
+        """The reference's _loss for the diffusion parameterizations (:1759-1779) -> Loss(loss = sum(nlls) / count, nlls = loss *
+        attention_mask, token_mask = attention_mask). attention_mask None fails like the reference (loss * None)."""
+        if x0.shape[1] > self.config.model.length:
+            raise NotImplementedError("Sub-sampling not implemented")                       # _maybe_sub_sample, :1681-1683
+        loss = self._forward_pass_diffusion(x0)
+        nlls = loss * attention_mask
+        count = attention_mask.sum()
+        token_nll = nlls.sum() / count
+        return Loss(loss=token_nll, nlls=nlls, token_mask=attention_mask)
+
+    @_decode_scope
+    @torch.no_grad()
+    def sequence_nll(self, x0, n_draws=1, chunk_rows=None):
+        """ELBO estimate of -log p(x0) per sequence, in nats: fp64 [n], the mean over n_draws draws of the sum over positions of
+        the token loss. Replay: n_draws consecutive _forward_pass_diffusion calls of the reference (each draws t for the whole
+        batch, antithetic over its rows). Philox: the draws of a sequence are stratified over its own n_draws (t of draw k in the
+        k-th of n_draws equal slices of (eps, 1]), so the value of a sequence depends on its tokens, philox_seed and row_offset +
+        its index only. chunk_rows: rows per backbone launch (default 32 x the CU count; Philox: whole sequences with all their
+        draws, so n_draws <= chunk_rows)."""
+        x0_u8 = self._elbo_checks(x0)
+        K = int(n_draws)
+        if K <= 0:
+            raise ValueError(f"n_draws must be positive, got {n_draws}")
+        chunk = self._elbo_chunk_rows(chunk_rows)
+        n, L = x0_u8.shape
+        dev = x0_u8.device
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        if self.rng_mode == "replay":
+            rows = [self._replay_draw(x0_u8, chunk, False, err)[1] for _ in range(K)]
+            acc = rows[0].clone()
+            for r in rows[1:]:
+                acc += r                                                     # draw order, as svdd_elbo_nll's seq_mean
+            out = acc / K
+        elif self.rng_mode == "philox":
+            if K > chunk:
+                raise ValueError(f"n_draws ({K}) > chunk_rows ({chunk}): the draws of a sequence go through one backbone launch")
+            per = chunk // K
+            out = torch.empty(n, dtype=torch.float64, device=dev)
+            for s0 in range(0, n, per):
+                s1 = min(n, s0 + per)
+                xc = x0_u8[s0:s1]
+                xt, _, _, w, _ = ops.elbo_mask(xc, K, ops.Rng(seed=self.philox_seed, row_offset=self.row_offset + s0), eps=self.sampling_eps)
+                out[s0:s1] = self._elbo_rows(xt, xc, w, K, False, True, err)[2]
+        else:
+            raise ValueError(f"rng_mode {self.rng_mode!r}")
+        ops.check_elbo_err(err)
+        return out
+
+    def nll_metrics(self, x0, n_draws=1, chunk_rows=None):
+        """The reference's test metrics (:50-71, 128-133), per token, in float64: nll = sum of the token losses / token count,
+        bpd = nll / ln 2, ppl = exp(nll). With n_draws > 1 the token losses are averaged over the draws."""
+        seq = self.sequence_nll(x0, n_draws=n_draws, chunk_rows=chunk_rows)
+        nll = float(seq.sum()) / (seq.numel() * x0.shape[1])
+        return {"nll": nll, "bpd": nll / math.log(2), "ppl": math.exp(nll)}

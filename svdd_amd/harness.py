@@ -9,6 +9,8 @@ The reference's `BaseModel.__init__` hard-wires checkpoint paths, Hydra and `.cu
 `controlled_decode*` keep the reference's call order (guided batches first, then
 `gen_batch_num * sample_M` un-guided baseline batches, then the top-k) and return the same
 5-tuple: (samples list, value_func_preds [N], reward_model_preds [N], top_k_values, baseline_preds [N]).
+The tokens of the baseline batches behind baseline_preds are kept in `baseline_samples`; `evaluate_nll` scores any of them
+under the pretrained model (Diffusion.sequence_nll).
 """
 import torch
 from torch import nn
@@ -101,6 +103,7 @@ class BaseModel(nn.Module):
         [L] rows instead of a list of [B, L] batches (Enformer.py:766 vs :441) — and `top_k_values = cat(baseline_preds)`,
         the top-k being commented out there (:802-811)."""
         samples, value_func_preds, reward_model_preds = [], [], []
+        self.baseline_samples = []                                            # the batches behind baseline_preds (evaluate_nll)
         for _ in range(gen_batch_num):
             self._next_batch_seed()
             batch = guided()
@@ -118,6 +121,7 @@ class BaseModel(nn.Module):
             pred = self._reward(batch)
             if i < gen_batch_num:
                 baseline_preds.extend(pred)
+                self.baseline_samples.append(batch)
             all_preds.extend(pred)
         if tweedie_quirks:
             top_k_values = torch.cat(baseline_preds)                           # Enformer.py:802
@@ -179,3 +183,12 @@ class BaseModel(nn.Module):
         unlike the reference's decode_classfier.py for task "rna", nothing here switches it to train mode."""
         return self._decode_guided_with_grad(gen_batch_num, sample_M, lambda: self.ref_model.controlled_sample_classfier(
             self.embedding, self.head, eval_sp_size=self.NUM_SAMPLES_PER_BATCH, guidance_scale=guidance_scale))
+
+    @torch.no_grad()
+    def evaluate_nll(self, samples, n_draws=1):
+        """ELBO estimate of -log p(x) under the pretrained model (ref_model.sequence_nll), in nats per sequence: fp64 [N]. `samples`:
+        an [N, L] tensor, or a list of [B, L] batches or [L] rows as controlled_decode* return them (or `baseline_samples`)."""
+        m = self.ref_model
+        if isinstance(samples, (list, tuple)):
+            samples = torch.cat([s.reshape(-1, s.shape[-1]).to(m.device) for s in samples])
+        return m.sequence_nll(samples.to(m.device), n_draws=n_draws)

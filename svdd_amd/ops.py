@@ -136,6 +136,66 @@ def classifier_propose(logits, x, grad4, dm, mcs, scale, rng, want_onehot=True, 
     return x_next, (onehot if want_onehot else None), q
 
 
+def elbo_mask(x0, K, rng, eps=1e-3, move_chance=None, want_scalars=True, want_count=False, xt=None):
+    """svdd_elbo_mask: K masked copies of x0 u8 [n, L] -> xt u8 [n K, L] (row k n + b = draw k of sequence b) and per row
+    (t, move_chance, w) f32 [n K] (Philox; replay: None, the caller holds them) and the masked count i32 [n K] | None.
+    replay: rng.uniforms = K blocks of n L fp32 ([b][l]: torch.rand(n, L)), move_chance f32 [n K] given.
+    philox: keyed by (rng.seed, rng.row_offset + b, k, l); t stratified over each sequence's own K draws."""
+    x0 = _need(x0, torch.uint8, "x0").contiguous()
+    n, L = x0.shape
+    dev = x0.device
+    replay = rng.uniforms is not None
+    if replay:
+        u = _need(rng.uniforms, torch.float32, "uniforms")
+        mc_in = _need(move_chance, torch.float32, "move_chance").contiguous()
+        assert u.is_contiguous() and u.numel() == K * n * L and mc_in.numel() == K * n, (u.shape, mc_in.shape, K, n, L)
+        want_scalars = False
+    elif move_chance is not None:
+        raise SvddError("elbo_mask: move_chance is the replay mode's input; Philox computes it")
+    if xt is None:
+        xt = torch.empty((K * n, L), dtype=torch.uint8, device=dev)
+    t, mc, w = ((torch.empty(K * n, dtype=torch.float32, device=dev) for _ in range(3)) if want_scalars else (None, None, None))
+    cnt = torch.empty(K * n, dtype=torch.int32, device=dev) if want_count else None
+    rs = rng.c_struct()
+    rc = _lib.lib().svdd_elbo_mask(x0.data_ptr(), n, L, K, float(eps), ctypes.byref(rs), mc_in.data_ptr() if replay else None,
+                                   xt.data_ptr(), *(v.data_ptr() if v is not None else None for v in (t, mc, w, cnt)), _stream())
+    _lib.check(rc, "svdd_elbo_mask")
+    return xt, t, mc, w, cnt
+
+
+def elbo_nll(logits, xt, x0, w, K=1, want_tokens=True, want_mean=False, err=None):
+    """svdd_elbo_nll: logits [n K, L, 5] (either layout, as subs_logp), xt u8 [n K, L], x0 u8 [n, L], w f32 [n K] ->
+    (nll f32 [n K, L] | None, row_sum f64 [n K], seq_mean f64 [n] | None). err: a caller-zeroed device int32 [1] the kernel sets
+    for a token > 3 in x0 (checked by the caller later); None: checked here (one synchronisation)."""
+    logits = _need(logits, torch.float32, "logits")
+    xt = _need(xt, torch.uint8, "xt").contiguous()
+    x0 = _need(x0, torch.uint8, "x0").contiguous()
+    w = _need(w, torch.float32, "w").contiguous()
+    n, L = x0.shape
+    logits, layout = layout_of(logits)
+    assert logits.shape == (K * n, L, 5) and xt.shape == (K * n, L) and w.numel() == K * n, (logits.shape, xt.shape, w.shape, K, n)
+    dev = x0.device
+    nll = torch.empty((K * n, L), dtype=torch.float32, device=dev) if want_tokens else None
+    row_sum = torch.empty(K * n, dtype=torch.float64, device=dev)
+    mean = torch.empty(n, dtype=torch.float64, device=dev) if want_mean else None
+    check_here = err is None
+    if check_here:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    rc = _lib.lib().svdd_elbo_nll(logits.data_ptr(), layout, xt.data_ptr(), x0.data_ptr(), w.data_ptr(), n, L, K,
+                                  nll.data_ptr() if nll is not None else None, row_sum.data_ptr(),
+                                  mean.data_ptr() if mean is not None else None, err.data_ptr(), _stream())
+    _lib.check(rc, "svdd_elbo_nll")
+    if check_here:
+        check_elbo_err(err)
+    return nll, row_sum, mean
+
+
+def check_elbo_err(err):
+    """Raise if svdd_elbo_nll flagged a token > 3 in x0 (SVDD_E_ARG)."""
+    if int(err[0]) != 0:
+        _lib.check(_lib.E_ARG, "svdd_elbo_nll: x0 holds a token > 3")
+
+
 def select(scores, cand, mode=SELECT_ARGMAX, rng=None, want_soft=True, x_next=None):
     """-> (x_next u8 [B,L], soft f32 [B,M] | None, idx i32 [B])."""
     cand = _need(cand, torch.uint8, "cand").contiguous()
