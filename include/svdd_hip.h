@@ -640,8 +640,13 @@ int svdd_sum_gate_f32(const float* a, const float* b, const float* f, float* g, 
  * the two directions accumulate in one chain):
  *   svdd_gru_bidir_train2_f32: gi = caller scratch [2][n L][192] fp32 (receives b + W_i x of every step: one launch on the whole chip),
  *                              then the chain with W_h h only; out [2][n][L][64], save [2][n][L][4][64] as above.
- *   svdd_gru_bidir_bwd2_f32:   da = caller scratch [2][n L][192] (receives the gate derivatives), then
- *                              g [n][L][64] = gate > 0 ? da_fwd W_i,fwd + da_bwd W_i,bwd : 0 (gate [n][L][64] or NULL: no gate). */
+ *                              A row of gi is [r | z | n] x 64 with every bias outside the r-product folded in:
+ *                              b_ir + b_hr + W_ir x | b_iz + b_hz + W_iz x | b_in + W_in x (b_hn stays with W_hn h, save plane 3).
+ *   svdd_gru_bidir_bwd2_f32:   da = caller scratch [2][n L][192] (receives the gate derivatives: a row is [da_r | da_z | da_n] x 64 of
+ *                              one (sequence, step), rows in (n, L) order for both directions; every row is written), then
+ *                              g [n][L][64] = gate > 0 ? da_fwd W_i,fwd + da_bwd W_i,bwd : 0 (gate [n][L][64] or NULL: no gate).
+ * Aliasing: f_prev of svdd_conv1d_cl_gated_f32 may be x itself (same bits as a separate copy); gi and da may be one buffer across the
+ * two calls; every output is otherwise a buffer of its own. A shut gate (gate <= 0, either zero included) stores +0.0. */
 int svdd_gru_bidir_train2_f32(const float* x, const float* wpack, const float* bpack, float* gi, float* out, float* save, int n, int L,
                               void* stream);
 int svdd_gru_bidir_bwd2_f32(const float* grad_out, const float* out, const float* save, const float* wpack_bwd, float* da, const float* gate,

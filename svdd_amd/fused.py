@@ -757,6 +757,8 @@ class FusedValueNet(nn.Module):
         self._grad_packs = None
         self.gru_off_chain = True            # mean_score_input_grad: W_i x and W_i^T da as whole-chip launches beside the GRU's serial chains (A/B knob)
         self._ln_eps = d1.norm.layer.eps
+        self.keep_grad_pass = False          # tests: mean_score_input_grad leaves its tower activations, GRU outputs, tail gradient and result in
+        self.last_grad_pass = None           # last_grad_pass (the buffers it worked on: no launch and no copy more)
 
     def lp_ok(self, L):
         return self.precision != "f32" and self.tower_ok and self.tail_ok and L <= 208
@@ -872,6 +874,8 @@ class FusedValueNet(nn.Module):
         dx = torch.empty((n, L, 4), dtype=torch.float32, device=dev)
         _lib.check(lib.svdd_reward_stem_bwd_f32(g.data_ptr(), w_stem.data_ptr(), dx.data_ptr(), n, L, self._stem_w_raw.shape[2], st),
                    "svdd_reward_stem_bwd_f32")
+        if self.keep_grad_pass:
+            self.last_grad_pass = {"fs": fs, "out": out, "g_tail": gout[0], "grad": dx}
         return dx
 
     def kernels_ok(self, L):

@@ -64,6 +64,33 @@ def test_argument_validation_without_gpu():
     assert L.svdd_bb_layer_fwd_f32(None, None, None, None, None, None, 1e-5, None, None, None, 1, 1, 128, None) == _lib.E_ARG
     assert L.svdd_bb_layer_fwd_f32(one, one, one, None, None, None, 1e-5, one, one, None, 1, 1, 96, None) == _lib.E_ARG    # channels not 64 / 128 / 256
     assert L.svdd_bb_layer_bwd_f32(one, one, one, one, 1e-5, one, one, one, None, 1, 1, 128, None) == _lib.E_ARG          # mask without its output
+    # the reward net's gradient pass: the shapes its specialised kernels do not have, and NULLs
+    for L_bad, taps in ((100, 5), (208, 5), (1, 5), (200, 3), (50, 9)):
+        assert L.svdd_conv1d_cl_gated_f32(one, one, one, 1, L_bad, 64, 64, taps, 1, None, None, None) == _lib.E_ARG
+    assert L.svdd_conv1d_cl_gated_f32(one, one, one, 1, 200, 64, 128, 5, 1, None, None, None) == _lib.E_ARG
+    assert L.svdd_conv1d_cl_gated_f32(one, one, one, 1, 200, 64, 64, 5, 2, None, None, None) == _lib.E_ARG
+    assert L.svdd_conv1d_cl_gated_f32(one, one, one, 0, 200, 64, 64, 5, 1, None, None, None) == _lib.E_ARG
+    for args in ((None, one, one), (one, None, one), (one, one, None)):
+        assert L.svdd_conv1d_cl_gated_f32(*args, 1, 200, 64, 64, 5, 1, None, None, None) == _lib.E_ARG
+    for taps in (5, 13, 17):
+        assert L.svdd_reward_stem_f32(one, one, one, one, 1, 200, taps, None) == _lib.E_ARG
+        assert L.svdd_reward_stem_bwd_f32(one, one, one, 1, 200, taps, None) == _lib.E_ARG
+    for k in range(4):
+        assert L.svdd_reward_stem_f32(*[None if i == k else one for i in range(4)], 1, 200, 15, None) == _lib.E_ARG
+        assert L.svdd_sum_gate_f32(*[None if i == k else one for i in range(4)], 4, None) == _lib.E_ARG
+    for k in range(3):
+        assert L.svdd_reward_stem_bwd_f32(*[None if i == k else one for i in range(3)], 1, 200, 15, None) == _lib.E_ARG
+    assert L.svdd_reward_stem_f32(one, one, one, one, 0, 200, 15, None) == _lib.E_ARG
+    assert L.svdd_reward_stem_bwd_f32(one, one, one, 1, 0, 15, None) == _lib.E_ARG
+    for count in (1, 2, 3, 5, 1030, 0, -4):
+        assert L.svdd_sum_gate_f32(one, one, one, one, count, None) == _lib.E_ARG
+    for k in range(9):
+        ptrs = [None if i == k else one for i in range(9)]
+        assert L.svdd_reward_tail_grad_f32(*ptrs[:7], 1e-5, 1, 1, *ptrs[7:], None) == _lib.E_ARG
+    assert L.svdd_reward_tail_grad_f32(*[one] * 7, 1e-5, 0, 1, one, one, None) == _lib.E_ARG
+    assert L.svdd_gru_bidir_train2_f32(one, one, one, None, one, one, 1, 1, None) == _lib.E_ARG                            # no gi scratch
+    assert L.svdd_gru_bidir_bwd2_f32(one, one, one, one, None, None, one, 1, 1, None) == _lib.E_ARG                        # no da scratch
+    assert L.svdd_gru_bidir_bwd2_f32(one, one, one, one, one, None, None, 1, 1, None) == _lib.E_ARG                        # no output
 
 
 def test_schedule_table_equals_reference(golden):
