@@ -15,6 +15,10 @@ or two launches of the hand-written HIP kernels (svdd_amd/csrc, C ABI include/sv
 of ~16*M+20 tiny tensor ops and B host syncs per step; the nets stay PyTorch-ROCm modules.
 There is no CPU fallback: the sampler methods need a gfx950 GPU and raise otherwise.
 
+Whatever the engine derives from a module's weights — the fused formulations of the nets, the GRU packs of the gradient paths, the
+validity of the backbone's conv packs — is held in ONE WeightCache (`Diffusion._fused`): validated against the weights once per
+outermost sampler call (`_decode_scope`), at every call outside one, and dropped by `clear_fused()`.
+
 Engine knobs (attributes; defaults reproduce the reference's observable behaviour):
   rng_mode         "replay": the categorical uniforms are drawn from torch's global CPU mt19937
                    generator in exactly the order the reference's CPU path consumes them
@@ -72,6 +76,7 @@ Engine knobs (attributes; defaults reproduce the reference's observable behaviou
                    opaque value / reward net under torch.autocast; the x3 modes leave it in fp32.
 """
 import contextlib
+import functools
 import math
 import warnings
 import weakref
@@ -128,11 +133,44 @@ def _same_weights(a, b):
     return a[0] == b[0] and (a[1] is None or b[1] is None or a[1] == b[1])
 
 
+class WeightCache:
+    """Whatever is derived from the weights of modules (a fused formulation, re-packed GRU weights, the validity of the backbone's
+    conv packs) holds COPIES of them, so it is valid only for the very module objects it was built from (weak references: an id()
+    can be recycled after garbage collection) with the very weights (weight_fingerprint, content checksum included). Inside one
+    decode scope an entry is validated once; without a scope, at every call."""
+
+    def __init__(self):
+        self._entries = {}               # (kind, id(module), ...) -> (weak references, fingerprint, value, scope stamp)
+
+    def __len__(self):
+        return len(self._entries)
+
+    def clear(self):
+        self._entries.clear()
+
+    def get(self, kind, modules, build, scope):
+        """build()'s result for these very `modules` with these very weights. `scope`: the id of the running decode scope (an entry
+        already stamped with it is returned without fingerprinting: this keeps the check off the per-step path) or None. A None
+        from build() is cached like any other result."""
+        key = (kind,) + tuple(id(m) for m in modules)
+        ent = self._entries.get(key)
+        alive = ent is not None and all(r() is m for r, m in zip(ent[0], modules))
+        if alive and scope is not None and ent[3] == scope:
+            return ent[2]
+        fp = weight_fingerprint(*modules)
+        if alive and _same_weights(ent[1], fp):
+            value = ent[2]
+        else:
+            for k in [k for k, v in self._entries.items() if any(r() is None for r in v[0])]:
+                del self._entries[k]                                # entries of collected modules
+            value = build()
+        self._entries[key] = (tuple(weakref.ref(m) for m in modules), fp, value, scope)
+        return value
+
+
 def _decode_scope(fn):
     """Marks one call of a public sampler method: the fused-net caches are validated against the modules' weights once
     per outermost call (a decode), not at every diffusion step."""
-    import functools
-
     @functools.wraps(fn)
     def wrapped(self, *a, **k):
         if self._scope_depth == 0:
@@ -198,10 +236,9 @@ class Diffusion(nn.Module):
                                          # step's live count (read back asynchronously, never waited for) came within 3 % of one GRU round;
                                          # a number = from that fraction of the steps on (rounds 4-5: 0.8, tuned to the random-init benchmark)
         self.dedup_prior = True          # the prior's rows are identical (all MASK): its net evaluations run on ONE row (exact; see _prior_logits)
-        self.pm_two_part = False         # SVDD-PM skipping loop: the live candidates as whole backbone rounds + remainder, the first part's reward net under the remainder (_pm_split_rows)
         self.dps_fused = True            # DPS: the whole step on hand-written kernels, no autograd (_dps_fused_nets); False: round 5's autograd path between the same big kernels
         self.dps_one_launch = True       # DPS: the differentiable backbone pass as one launch each way (svdd_backbone_cnn_save_f32 / _grad_f32) where it applies
-        self._dps_hard_onehot, self._dps_raw_logits = False, None
+        self._dps_hard_onehot, self._dps_raw_logits, self._dps_logp = False, None, None
         self.dps_single_forward = False  # DPS opt-in: q_xs from the differentiable pass's log-probs, not from a second backbone forward per step
         self.logits_cache = "auto"
         self.skip_stats = None
@@ -209,7 +246,7 @@ class Diffusion(nn.Module):
         self.trace = None          # set to a list to record (logits, scores) of every step (tests / smoke)
         self.state_trace = None    # set to a list to record x_t (uint8 clone) at the start of every step + the final x
         self._sched_cache = {}
-        self._fused = {}
+        self._fused = WeightCache()      # everything derived from weights: fused nets, GRU packs, conv-pack validity (clear_fused drops it)
         self._scope_depth, self._scope_id = 0, 0
         self.fuse_trunk_f32 = True       # precision "f32" + Enformer-shaped value trunk: the hand-written fp32 trunk kernels (False: the PyTorch modules)
         self.replay_rng = "device"       # rng_mode "replay": "device" = torch's CPU mt19937 stream continued by K8 on the GPU for
@@ -239,102 +276,70 @@ class Diffusion(nn.Module):
         return x if x.dtype == torch.uint8 else x.to(torch.uint8)
 
     def clear_fused(self):
-        """Drop the cached fused formulations and the backbone's cached zero-sigma time biases. Every cache entry carries
-        a fingerprint of the weights it was built from (tensor identity, in-place version AND a content checksum, so
-        `.data` / EMA swaps are caught too) and is rebuilt at the next decode when that no longer matches; call this to
-        force it, or after changing weights in the middle of a per-step loop inside one sampler call."""
-        self._fused = {}
-        self._cpk_fp = None
+        """Drop everything cached from weights (the fused formulations, the GRU packs of the gradient paths, the validity of the
+        backbone's conv packs) and the backbone's cached zero-sigma time biases. Every cache entry carries a fingerprint of the
+        weights it was built from (tensor identity, in-place version AND a content checksum, so `.data` / EMA swaps are caught
+        too) and is rebuilt at the next decode when that no longer matches; call this to force it, or after changing weights
+        in the middle of a per-step loop inside one sampler call."""
+        self._fused.clear()
         if isinstance(self.backbone, CNNModel):
             self.backbone.clear_time_bias_cache()
             self.backbone._cpk_key = None
 
+    @property
+    def _scope(self):
+        """Id of the running decode scope (_decode_scope) for WeightCache.get, None outside one."""
+        return self._scope_id if self._scope_depth > 0 else None
+
     def _validate_conv_packs(self):
         """The packed dilated-conv weights of CNNModel._trunk_cl (DPS gradient path) are keyed by tensor identity + version
-        inside the backbone; a `.data` / EMA swap changes neither. Validate them like the fused nets: content fingerprint,
-        once per decode scope (every call outside one)."""
+        inside the backbone; a `.data` / EMA swap changes neither. Validated like the fused nets: a changed fingerprint (or a
+        cleared cache) makes the backbone re-pack."""
         bb = self.backbone
-        if self._checked_now(getattr(self, "_cpk_stamp", None)):
-            return
-        fp = weight_fingerprint(*bb.convs)
-        old = getattr(self, "_cpk_fp", None)
-        if old is None or not _same_weights(old, fp):
-            bb._cpk_key = None
-        self._cpk_fp, self._cpk_stamp = fp, self._scope_id
-
-    def _checked_now(self, stamp):
-        return self._scope_depth > 0 and stamp == self._scope_id
+        self._fused.get("conv_packs", (bb.convs,), lambda: setattr(bb, "_cpk_key", None), self._scope)
 
     def _fused_backbone(self):
-        ent = self._fused.get("backbone")
-        if ent is None or not self._checked_now(ent[2]):
-            fp = weight_fingerprint(self.backbone)
-            if ent is None or not _same_weights(ent[0], fp):
-                from .fused import FusedBackbone
-                self.backbone.clear_time_bias_cache()
-                ent = (fp, FusedBackbone(self.backbone).to(self.device).eval(), self._scope_id)
-            else:
-                ent = (ent[0], ent[1], self._scope_id)
-            self._fused["backbone"] = ent
-        ent[1].precision = self.precision
-        return ent[1]
+        def build():
+            from .fused import FusedBackbone
+            self.backbone.clear_time_bias_cache()
+            return FusedBackbone(self.backbone).to(self.device).eval()
+        fb = self._fused.get("backbone", (self.backbone,), build, self._scope)
+        fb.precision = self.precision
+        return fb
 
     def value_callable(self, embedding, head):
         """The callable the engine uses for `head(embedding(onehot))`: onehot fp32 [n,L,4] -> [n,1,1]."""
+        from .enformer_value import EnformerTrunk
         from .value_nets import ConvGRUTrunk, ConvHead
         if (self.fuse_nets and isinstance(embedding, ConvGRUTrunk) and isinstance(head, ConvHead)
                 and embedding.gru_tower.gru.hidden_size == 64 and embedding.gru_tower.gru.input_size == 64
                 and embedding.gru_tower.gru.num_layers == 1 and next(embedding.parameters()).is_cuda):
-            # The fused net holds re-packed COPIES of the weights, so an entry is valid only for these very module
-            # objects (weak references: id() alone can be recycled after garbage collection) with these very
-            # weights (fingerprint incl. a content checksum). Checked once per decode (_decode_scope), not per step.
-            key = ("value", id(embedding), id(head))
-            ent = self._fused.get(key)
-            alive = ent is not None and ent[0]() is embedding and ent[1]() is head
-            if not (alive and self._checked_now(ent[4])):
-                fp = weight_fingerprint(embedding, head)
-                if not (alive and _same_weights(ent[2], fp)):
-                    from .fused import FusedValueNet
-                    for k in [k for k, v in self._fused.items() if k != "backbone" and (v[0]() is None or v[1]() is None)]:
-                        del self._fused[k]                          # entries of collected modules
-                    ent = (weakref.ref(embedding), weakref.ref(head), fp,
-                           FusedValueNet(embedding, head).to(self.device).eval(), self._scope_id)
-                else:
-                    ent = ent[:4] + (self._scope_id,)
-                self._fused[key] = ent
-            ent[3].precision = self.precision
-            return ent[3]
-        from .enformer_value import EnformerTrunk
+            def build():
+                from .fused import FusedValueNet
+                return FusedValueNet(embedding, head).to(self.device).eval()
+            fused = self._fused.get("value", (embedding, head), build, self._scope)
+            fused.precision = self.precision
+            return fused
         if (self.fuse_nets and (self.precision != "f32" or self.fuse_trunk_f32) and isinstance(embedding, EnformerTrunk)
                 and isinstance(head, ConvHead) and next(embedding.parameters()).is_cuda):
             # BASELINE configs[3]'s Enformer-shaped trunk on the hand-written kernels (svdd_trunk.hip): "f32" = one fp32 operand
             # plane, fp32 MFMAs (the reference's precision; round 4); the x3 modes map to bf16x3 (bf16 keeps fp32's exponent
             # range: no operand scaling needed), the one-pass modes to bf16
             tp = "f32" if self.precision == "f32" else "bf16x3" if self.precision.endswith("x3") else "bf16"
-            key = ("trunk", id(embedding), id(head), tp)
-            ent = self._fused.get(key)
-            alive = ent is not None and ent[0]() is embedding and ent[1]() is head
-            if not (alive and self._checked_now(ent[4])):
-                fp = weight_fingerprint(embedding, head)
-                if not (alive and _same_weights(ent[2], fp)):
-                    from .fused_trunk import FusedEnformerValueNet
-                    for k in [k for k, v in self._fused.items() if k != "backbone" and (v[0]() is None or v[1]() is None)]:
-                        del self._fused[k]
-                    # a trunk whose GEMM shapes the kernels do not take (output channels must come in 128s, input channels in
-                    # 32s: a 384-channel toy trunk has a 192-channel stem) stays on the PyTorch modules — said once, and ONLY
-                    # for that documented reason: an assertion while packing a supported trunk is a bug and propagates
-                    ok, why = FusedEnformerValueNet.supports(embedding, head)
-                    if ok:
-                        fused_net = FusedEnformerValueNet(embedding, head, tp)
-                    else:
-                        fused_net = None
-                        warnings.warn(f"Enformer-shaped value trunk stays on the PyTorch modules: {why}", stacklevel=2)
-                    ent = (weakref.ref(embedding), weakref.ref(head), fp, fused_net, self._scope_id)
-                else:
-                    ent = ent[:4] + (self._scope_id,)
-                self._fused[key] = ent
-            if ent[3] is not None:
-                return ent[3]
+
+            def build():
+                from .fused_trunk import FusedEnformerValueNet
+                # a trunk whose GEMM shapes the kernels do not take (output channels must come in 128s, input channels in
+                # 32s: a 384-channel toy trunk has a 192-channel stem) stays on the PyTorch modules — said once per build, and
+                # ONLY for that documented reason: an assertion while packing a supported trunk is a bug and propagates
+                ok, why = FusedEnformerValueNet.supports(embedding, head)
+                if ok:
+                    return FusedEnformerValueNet(embedding, head, tp)
+                warnings.warn(f"Enformer-shaped value trunk stays on the PyTorch modules: {why}", stacklevel=4)   # value_callable's caller
+                return None
+            fused = self._fused.get(("trunk", tp), (embedding, head), build, self._scope)
+            if fused is not None:
+                return fused
         if self.precision in ("bf16", "f16"):                       # opaque nets: PyTorch-ROCm's own 16-bit kernels
             dt = torch.bfloat16 if self.precision == "bf16" else torch.float16
 
@@ -431,13 +436,17 @@ class Diffusion(nn.Module):
             return ops.Rng(seed=self.philox_seed, row_offset=self.row_offset, step=step)
         raise ValueError(f"rng_mode {self.rng_mode!r}")
 
-    def _select(self, scores, cand, step):
+    def _select_args(self, step):
+        """(ABI constant of select_mode, the Rng a multinomial select draws from at diffusion step `step` | None)."""
         mode = {"argmax": ops.SELECT_ARGMAX, "multinomial": ops.SELECT_MULTINOMIAL}[self.select_mode]
-        rng = None
-        if mode == ops.SELECT_MULTINOMIAL:
-            if self.rng_mode != "philox":
-                raise ValueError("select_mode='multinomial' needs rng_mode='philox'")
-            rng = ops.Rng(seed=self.philox_seed, row_offset=self.row_offset, step=step)
+        if mode != ops.SELECT_MULTINOMIAL:
+            return mode, None
+        if self.rng_mode != "philox":
+            raise ValueError("select_mode='multinomial' needs rng_mode='philox'")
+        return mode, ops.Rng(seed=self.philox_seed, row_offset=self.row_offset, step=step)
+
+    def _select(self, scores, cand, step):
+        mode, rng = self._select_args(step)
         x_next, _, _ = ops.select(scores, cand, mode=mode, rng=rng, want_soft=False)
         return x_next
 
@@ -456,6 +465,17 @@ class Diffusion(nn.Module):
 
     def _num_steps(self, num_steps):
         return self.config.sampling.steps if num_steps is None else num_steps
+
+    def _decode_start(self, num_steps, eps, eval_sp_size):
+        """What every sampler loop opens with -> (B, L, S, schedule table [S, 3], the all-MASK prior x_T as u8 [B, L], :751-753)."""
+        self._require_gpu()
+        B, L, S = self._batch_size(eval_sp_size), self.config.model.length, self._num_steps(num_steps)
+        sched, _, _ = self._schedule(S, eps)
+        return B, L, S, sched, torch.full((B, L), self.mask_index, dtype=torch.uint8, device=self.device)
+
+    def _step_result(self, x_next, x, q):
+        """What the reference's per-step methods return: (x_next int64, x, q_xs, copy_flag)."""
+        return x_next.long(), x, q, (x != self.mask_index).to(x.dtype)
 
     def _noise_removal(self, x_u8, logits=None):
         """:1049-1060 — x = forward(x, sigma(t_last))[:, :, :-1].argmax(-1) ; returns int64. `logits`: the backbone
@@ -547,19 +567,19 @@ class Diffusion(nn.Module):
     def _ddpm_update_finetune(self, x, t, dt):
         """Un-guided ancestral step (:1147-1172) -> (x_next, x, q_xs, copy_flag)."""
         self._require_gpu()
-        mct, mcs, dm = self._step_scalars(t, dt)
+        _, mcs, dm = self._step_scalars(t, dt)
         x_u8 = self._tokens_u8(x)
         logits = self._backbone_logits(x_u8)
         B, L = x_u8.shape
         cand, _, q = ops.propose(logits, x_u8, dm, mcs, 1, self._rng(self._step_index(t, dt), 1, B, L, logits), want_q=True)
-        return cand[:, 0].long(), x, q, (x != self.mask_index).to(x.dtype)
+        return self._step_result(cand[:, 0], x, q)
 
     @_decode_scope
     @torch.no_grad()
     def _ddpm_update_finetune_controlled(self, x, t, dt, pre_scorer_embedding, pre_scorer_head, repeats=10):
         """One SVDD-MC step (:1174-1228) -> (final_samples, x, q_xs, copy_flag)."""
         self._require_gpu()
-        mct, mcs, dm = self._step_scalars(t, dt)
+        _, mcs, dm = self._step_scalars(t, dt)
         x_u8 = self._tokens_u8(x)
         logits = self._backbone_logits(x_u8)
         B, L = x_u8.shape
@@ -567,14 +587,14 @@ class Diffusion(nn.Module):
         cand, onehot, q = ops.propose(logits, x_u8, dm, mcs, repeats, self._rng(step, repeats, B, L, logits), want_q=True)
         scores = self._value_scores(pre_scorer_embedding, pre_scorer_head, onehot, B, repeats, cand, x_u8)
         x_next = self._select(scores, cand, step)
-        return x_next.long(), x, q, (x != self.mask_index).to(x.dtype)
+        return self._step_result(x_next, x, q)
 
     @_decode_scope
     @torch.no_grad()
     def _ddpm_update_finetune_controlled_twedie(self, x, t, dt, reward_model, repeats=10, options="True", task="dna"):
         """One SVDD-PM step (:1373-1460) -> (final_samples, x, q_xs, copy_flag)."""
         self._require_gpu()
-        mct, mcs, dm = self._step_scalars(t, dt)
+        _, mcs, dm = self._step_scalars(t, dt)
         x_u8 = self._tokens_u8(x)
         logits = self._backbone_logits(x_u8)
         B, L = x_u8.shape
@@ -582,7 +602,7 @@ class Diffusion(nn.Module):
         cand, _, q = ops.propose(logits, x_u8, dm, mcs, repeats, self._rng(step, repeats, B, L, logits), want_q=True)
         scores = self._tweedie_scores(cand, reward_model, options, task)
         x_next = self._select(scores, cand, step)
-        return x_next.long(), x, q, (x != self.mask_index).to(x.dtype)
+        return self._step_result(x_next, x, q)
 
     def _tweedie_scores(self, cand, reward_model, options, task):
         """scores[b,m] = reward_model(x0hat(candidate))[:, 0] (:1413-1436)."""
@@ -603,7 +623,7 @@ class Diffusion(nn.Module):
         """One SMC/TDS step (:1230-1284) -> x_next. Consumes B doubles of numpy's global RandomState,
         like the reference's np.random.choice."""
         self._require_gpu()
-        mct, mcs, dm = self._step_scalars(t, dt)
+        _, mcs, dm = self._step_scalars(t, dt)
         x_u8 = self._tokens_u8(x)
         return self._tds_step(x_u8, dm, mcs, reward_model, alpha, self._step_index(t, dt)).long()
 
@@ -631,7 +651,7 @@ class Diffusion(nn.Module):
             reward_den = reward_fn(oh_den)[:, 0][:, 0].float()            # :1277
         keep_logits = carry is not None and carry.get("keep_logits")
         keep_den = carry is not None and carry.get("keep_den")
-        shard = getattr(self, "_shard", None)
+        shard = self._shard
         if shard is not None and shard[3] > 1:
             # batch sharded over GPUs: the resample draws ancestors from the WHOLE batch — one all-gather, then every rank
             # resamples the whole batch identically and keeps its rows (distributed.tds_exchange)
@@ -675,12 +695,6 @@ class Diffusion(nn.Module):
         self._dps_logp = logp.detach()                            # log p(x0 | x_t): _dps_guided_q takes its q_xs from it
         expected_x0 = keep * x_onehot + (1 - keep) * logp
         probs = torch.softmax(expected_x0, dim=2)
-        # MIOpen's fused RNN backward insists on train(). A GRU without inter-layer dropout computes the same function in
-        # both modes, so only those modules are switched for the call (BatchNorm / Dropout stay in eval): 113 -> 54 ms per
-        # gradient at B = 256 against the per-timestep native cells (400 cell launches forward + backward). Any other
-        # recurrent module falls back to the native cells.
-        # ... and where the GRU is the reward net's 64-unit bidirectional one, neither is used: the recurrence runs on the
-        # hand-written forward + BPTT kernels (csrc/svdd_gru_train.hip; 35.9 -> ~1 ms of the gradient at B = 256).
         fn = self.reward_callable(reward_model) if (self.fuse_nets and self.dps_one_launch and x_onehot.is_cuda) else None
         from .fused import FusedValueNet
         if isinstance(fn, FusedValueNet) and fn.grad_ok(x_onehot.shape[1]):
@@ -688,46 +702,52 @@ class Diffusion(nn.Module):
             scores = fn.forward_grad(probs[:, :, 0:4].contiguous())[:, 0]
             scores.mean().backward()
             return x_onehot.grad.clone()
-        hip = self._hip_gru_blocks(reward_model) if (self.fuse_nets and x_onehot.is_cuda) else []
+        with self._gru_backward_ready([reward_model], x_onehot.is_cuda):
+            reward_model(probs.transpose(1, 2)[:, 0:4, :])[:, 0].mean().backward()
+        return x_onehot.grad.clone()
+
+    @contextlib.contextmanager
+    def _gru_backward_ready(self, modules, on_gpu):
+        """The recurrent modules of `modules` made ready for a backward pass on the GPU, for the span of the context (the loss is
+        built AND back-propagated inside it). MIOpen's fused RNN backward insists on train(). A GRU without inter-layer dropout
+        computes the same function in both modes, so only those modules are switched (BatchNorm / Dropout stay in eval): 113 -> 54 ms
+        per gradient at B = 256 against the per-timestep native cells (400 cell launches forward + backward). Any other recurrent
+        module falls back to the native cells. Where the GRU is the reward net's 64-unit bidirectional one, neither is used: the
+        recurrence runs on the hand-written forward + BPTT kernels (csrc/svdd_gru_train.hip; 35.9 -> ~1 ms of the gradient at
+        B = 256). On the CPU nothing is touched: a dropout-free GRU is the same function in both modes there too."""
+        hip = [b for m in modules for b in self._hip_gru_blocks(m)] if (self.fuse_nets and on_gpu) else []
         taken = {id(b.gru) for b in hip}
-        rnns = [m for m in reward_model.modules() if isinstance(m, torch.nn.RNNBase) and id(m) not in taken]
-        flip = [m for m in rnns if isinstance(m, torch.nn.GRU) and m.dropout == 0 and not m.training]
-        native = len(flip) != len([m for m in rnns if not m.training])
-        for m in flip:
-            m.train()
+        rnns = [r for m in modules for r in m.modules() if isinstance(r, nn.RNNBase) and id(r) not in taken]
+        flip = [r for r in rnns if isinstance(r, nn.GRU) and r.dropout == 0 and not r.training] if on_gpu else []
+        native = on_gpu and len(flip) != len([r for r in rnns if not r.training])
+        for r in flip:
+            r.train()
         try:
-            with torch.backends.cudnn.flags(enabled=not native):
-                scores = reward_model(probs.transpose(1, 2)[:, 0:4, :])[:, 0]
-            scores.mean().backward()
+            with torch.backends.cudnn.flags(enabled=not native) if on_gpu else contextlib.nullcontext():
+                yield
         finally:
-            for m in flip:
-                m.eval()
+            for r in flip:
+                r.eval()
             for b in hip:
                 b._hip_gru = None
-        return x_onehot.grad.clone()
 
     def _hip_gru_blocks(self, reward_model):
         """GRUBlocks of `reward_model` whose nn.GRU the kernels of csrc/svdd_gru_train.hip take (64 -> 64, one layer,
-        bidirectional, eval mode or no dropout), switched to them; weights re-packed when their fingerprint changes."""
+        bidirectional, eval mode or no dropout), switched to them; their re-packed weights are cached like the fused nets."""
         from .fused import GruBidirFunction, pack_gru, pack_gru_bwd
         from .value_nets import GRUBlock
         blocks = []
         for b in reward_model.modules():
             g = getattr(b, "gru", None)
-            if not (isinstance(b, GRUBlock) and isinstance(g, torch.nn.GRU) and g.hidden_size == 64 and g.input_size == 64 and
+            if not (isinstance(b, GRUBlock) and isinstance(g, nn.GRU) and g.hidden_size == 64 and g.input_size == 64 and
                     g.num_layers == 1 and g.bidirectional and g.bias and g.batch_first and not g.training):
                 continue
-            cache = self.__dict__.setdefault("_gru_train_packs", {})   # id(gru) -> (weak ref, fingerprint, packs)
-            fp = weight_fingerprint(g)
-            ent = cache.get(id(g))
-            if ent is None or ent[0]() is not g or not _same_weights(ent[1], fp):
+
+            def build(g=g):
                 wpack, bpack = pack_gru(g)
                 dev = next(g.parameters()).device
-                ent = (weakref.ref(g), fp, (wpack.to(dev), bpack.to(dev), pack_gru_bwd(g).to(dev)))
-                for k in [k for k, v in cache.items() if v[0]() is None]:
-                    del cache[k]
-                cache[id(g)] = ent
-            packs = ent[2]
+                return wpack.to(dev), bpack.to(dev), pack_gru_bwd(g).to(dev)
+            packs = self._fused.get("gru_packs", (g,), build, self._scope)
             b._hip_gru = lambda xx, p=packs: GruBidirFunction.apply(xx, *p)
             blocks.append(b)
         return blocks
@@ -802,7 +822,7 @@ class Diffusion(nn.Module):
             return None
         return fb, fn
 
-    def _dps_step(self, x_u8, mct, mcs, dm, reward_model, guidance_scale, step):
+    def _dps_step(self, x_u8, mcs, dm, reward_model, guidance_scale, step):
         B, L = x_u8.shape
         q_xs = self._dps_guided_q(x_u8, mcs, dm, reward_model, guidance_scale)
         with torch.no_grad():
@@ -813,47 +833,29 @@ class Diffusion(nn.Module):
     def _ddpm_update_finetune_controlled_DPS(self, x, t, dt, reward_model, guidance_scale):
         """One DPS (gradient-guidance) step (:1286-1319) -> x_next."""
         self._require_gpu()
-        mct, mcs, dm = self._step_scalars(t, dt)
-        return self._dps_step(self._tokens_u8(x), mct, mcs, dm, reward_model, guidance_scale, self._step_index(t, dt)).long()
+        _, mcs, dm = self._step_scalars(t, dt)
+        return self._dps_step(self._tokens_u8(x), mcs, dm, reward_model, guidance_scale, self._step_index(t, dt)).long()
 
     @_decode_scope
     def controlled_sample_DPS(self, reward_model, guidance_scale, num_steps=None, eps=1e-5, eval_sp_size=None,
                               sample_M=10):
         """DPS baseline decode (:980-1019). Not under no_grad in the reference either: it back-propagates."""
-        self._require_gpu()
-        B, L, S = self._batch_size(eval_sp_size), self.config.model.length, self._num_steps(num_steps)
-        sched, _, _ = self._schedule(S, eps)
-        x = torch.full((B, L), self.mask_index, dtype=torch.uint8, device=self.device)
+        B, L, S, sched, x = self._decode_start(num_steps, eps, eval_sp_size)
         for i in range(S):
-            x = self._dps_step(x, sched[i, 0], sched[i, 1], sched[i, 2], reward_model, guidance_scale, i)
+            x = self._dps_step(x, sched[i, 1], sched[i, 2], reward_model, guidance_scale, i)
         with torch.no_grad():
             return self._noise_removal(x)
 
     # ------------------------------------------------------------ classifier guidance ----
     def compute_gradient(self, x, pre_scorer_embedding, pre_scorer_head):
         """d mean(head(embedding(x))) / d x for the masked one-hot x [B, L, 4] (reference :1362-1371): the mean runs over the batch AND
-        the tasks, so a row's gradient carries a 1 / B factor. Pure autograd, on whatever device x lives (CPU included). On the GPU a
-        64-unit bidirectional GRU runs on the hand-written forward + BPTT kernels and any other eval-mode GRU is switched to train() for
-        the call (MIOpen's fused RNN backward needs it; without inter-layer dropout it is the same function), as in
-        compute_gradient_DPS. The value net's modes are otherwise left as the caller set them."""
+        the tasks, so a row's gradient carries a 1 / B factor. Pure autograd, on whatever device x lives (CPU included); on the GPU the
+        value net's GRUs are prepared for the backward pass by _gru_backward_ready, as in compute_gradient_DPS. The value net's modes
+        are otherwise left as the caller set them."""
         x.requires_grad_(True)
         mods = [m for m in (pre_scorer_embedding, pre_scorer_head) if isinstance(m, nn.Module)]
-        hip = [b for m in mods for b in self._hip_gru_blocks(m)] if (self.fuse_nets and x.is_cuda) else []
-        taken = {id(b.gru) for b in hip}
-        rnns = [r for m in mods for r in m.modules() if isinstance(r, torch.nn.RNNBase) and id(r) not in taken]
-        flip = [r for r in rnns if isinstance(r, torch.nn.GRU) and r.dropout == 0 and not r.training] if x.is_cuda else []
-        native = x.is_cuda and len(flip) != len([r for r in rnns if not r.training])
-        for r in flip:
-            r.train()
-        try:
-            with torch.enable_grad(), (torch.backends.cudnn.flags(enabled=not native) if x.is_cuda else contextlib.nullcontext()):
-                scores = pre_scorer_head(pre_scorer_embedding(x))
-                scores.mean().backward()
-        finally:
-            for r in flip:
-                r.eval()
-            for b in hip:
-                b._hip_gru = None
+        with torch.enable_grad(), self._gru_backward_ready(mods, x.is_cuda):
+            pre_scorer_head(pre_scorer_embedding(x)).mean().backward()
         return x.grad.clone()
 
     def _classifier_fused_value(self, embedding, head, L):
@@ -897,14 +899,14 @@ class Diffusion(nn.Module):
     def _ddpm_update_finetune_classfier(self, x, t, dt, pre_scorer_embedding, pre_scorer_head, guidance_scale):
         """One classifier-guidance step (:1332-1360) -> (x_next, x, q_xs, copy_flag); q_xs is the UN-guided one, as in the reference."""
         self._classifier_checks(guidance_scale)
-        mct, mcs, dm = self._step_scalars(t, dt)
+        _, mcs, dm = self._step_scalars(t, dt)
         x_u8 = self._tokens_u8(x)
         with torch.no_grad():
             logits = self._backbone_logits(x_u8)
             onehot = ops.transform_samples(x_u8)
         x_next, _, q = self._classifier_step(x_u8, onehot, logits, dm, mcs, pre_scorer_embedding, pre_scorer_head, guidance_scale,
                                              self._step_index(t, dt), want_q=True)
-        return x_next.long(), x, q, (x != self.mask_index).to(x.dtype)
+        return self._step_result(x_next, x, q)
 
     @_decode_scope
     def controlled_sample_classfier(self, pre_scorer_embedding, pre_scorer_head, num_steps=None, eps=1e-5, eval_sp_size=None,
@@ -920,9 +922,7 @@ class Diffusion(nn.Module):
         batch-statistics BatchNorm, which makes that run irreproducible). guidance_scale=None raises ValueError (the reference fails
         with a TypeError). A batch-sharded decode is refused."""
         self._classifier_checks(guidance_scale)
-        B, L, S = self._batch_size(eval_sp_size), self.config.model.length, self._num_steps(num_steps)
-        sched, _, _ = self._schedule(S, eps)
-        x = torch.full((B, L), self.mask_index, dtype=torch.uint8, device=self.device)      # _sample_prior
+        B, L, S, sched, x = self._decode_start(num_steps, eps, eval_sp_size)
         onehot = torch.zeros((B, L, 4), dtype=torch.float32, device=self.device)            # transform_samples of the prior
         for i in range(S):
             with torch.no_grad():
@@ -940,15 +940,7 @@ class Diffusion(nn.Module):
     @torch.no_grad()
     def decode_sample(self, num_steps=None, eps=1e-5, eval_sp_size=None, cdq=False):
         """Un-guided decode (:888-936) -> LongTensor[B,L]."""
-        self._require_gpu()
-        B, L, S = self._batch_size(eval_sp_size), self.config.model.length, self._num_steps(num_steps)
-        sched, _, _ = self._schedule(S, eps)
-        x = torch.full((B, L), self.mask_index, dtype=torch.uint8, device=self.device)
-        for i in range(S):
-            logits = self._prior_logits(x) if i == 0 else self._backbone_logits(x)
-            cand, _, _ = ops.propose(logits, x, sched[i, 2], sched[i, 1], 1, self._rng(i, 1, B, L, logits))
-            x = cand.view(B, L)
-        return self._noise_removal(x)
+        return self._unguided_sample(num_steps, eps, eval_sp_size, keep_mid=False)[0]
 
     @_decode_scope
     @torch.no_grad()
@@ -957,15 +949,17 @@ class Diffusion(nn.Module):
         self._require_gpu()
         if cdq:
             raise NotImplementedError("cdq=True is a value-function *training* data path (Enformer.py:163-267)")
-        B, L, S = self._batch_size(eval_sp_size), self.config.model.length, self._num_steps(num_steps)
-        sched, _, _ = self._schedule(S, eps)
-        x = torch.full((B, L), self.mask_index, dtype=torch.uint8, device=self.device)
+        return self._unguided_sample(num_steps, eps, eval_sp_size, keep_mid=True)
+
+    def _unguided_sample(self, num_steps, eps, eval_sp_size, keep_mid):
+        """The un-guided loop -> (x_0 int64, [x_t int64 after every step but the last] if keep_mid else [])."""
+        B, L, S, sched, x = self._decode_start(num_steps, eps, eval_sp_size)
         mid_x = []
         for i in range(S):
             logits = self._prior_logits(x) if i == 0 else self._backbone_logits(x)
             cand, _, _ = ops.propose(logits, x, sched[i, 2], sched[i, 1], 1, self._rng(i, 1, B, L, logits))
             x = cand.view(B, L)
-            if i != S - 1:
+            if keep_mid and i != S - 1:
                 mid_x.append(x.long())
         return self._noise_removal(x), mid_x
 
@@ -974,10 +968,8 @@ class Diffusion(nn.Module):
     def controlled_sample(self, pre_scorer_embedding, pre_scorer_head, num_steps=None, eps=1e-5,
                           eval_sp_size=None, sample_M=10):
         """SVDD-MC decode (:1021-1061): S x [backbone -> propose -> value net -> select], then noise removal."""
-        self._require_gpu()
-        B, L, S, M = self._batch_size(eval_sp_size), self.config.model.length, self._num_steps(num_steps), sample_M
-        sched, _, _ = self._schedule(S, eps)
-        x = torch.full((B, L), self.mask_index, dtype=torch.uint8, device=self.device)   # _sample_prior
+        B, L, S, sched, x = self._decode_start(num_steps, eps, eval_sp_size)
+        M = sample_M
         cand = torch.empty((B, M, L), dtype=torch.uint8, device=self.device)
         onehot = torch.empty((B * M, L, 4), dtype=torch.float32, device=self.device)
         fn = self.value_callable(pre_scorer_embedding, pre_scorer_head)
@@ -1032,12 +1024,7 @@ class Diffusion(nn.Module):
             self.n_win_rows = None          # with skip_stats: rows the value net's tower computed (the candidates' row windows)
 
     def _select_compact(self, sc, ws, cand, step):
-        mode = {"argmax": ops.SELECT_ARGMAX, "multinomial": ops.SELECT_MULTINOMIAL}[self.select_mode]
-        rng = None
-        if mode == ops.SELECT_MULTINOMIAL:
-            if self.rng_mode != "philox":
-                raise ValueError("select_mode='multinomial' needs rng_mode='philox'")
-            rng = ops.Rng(seed=self.philox_seed, row_offset=self.row_offset, step=step)
+        mode, rng = self._select_args(step)
         x_next, _, _, _ = ops.select_compact(sc, ws.slot, ws.parent_score, cand, mode=mode, rng=rng, sel_score=ws.sel_score,
                                              changed=ws.changed, idx=ws.idx)
         ws.parent_score, ws.sel_score = ws.sel_score, ws.parent_score       # the selected candidate is the next parent
@@ -1154,16 +1141,6 @@ class Diffusion(nn.Module):
         self._finish_stats(ws, B, M, S, "mc-generic")
         return self._noise_removal(x)
 
-    def _pm_split_rows(self, fb, rf, n, L):
-        """Entries of part A of a two-part SVDD-PM step (0: one part): one full round of full backbone tiles — CUs x (208 // L)
-        sequences — when several sequences share a tile, the candidates can exceed it and the reward net takes an output buffer."""
-        from .fused import FusedValueNet
-        if not (self.pm_two_part and isinstance(rf, FusedValueNet) and rf.w_eff.shape[1] == 1 and 208 // L >= 2) or _capturing():
-            return 0
-        from . import _lib
-        n_a = _lib.device_info()[1] * (208 // L)
-        return n_a if n_a < n else 0
-
     def _tweedie_sample_skipping(self, rf, x, sched, B, L, S, M, fb):
         """SVDD-PM with exact work-skipping: per step ONE backbone forward, on the live candidates only."""
         dev = self.device
@@ -1180,42 +1157,14 @@ class Diffusion(nn.Module):
         ws.parent_score.copy_(rf.forward_tokens(xh[:1].contiguous()).reshape(1).expand(B) if dedup
                               else rf.forward_tokens(xh).reshape(B))          # reward of the parents' x0-hat
         from .fused import candidate_windows
-        # Two-part steps (round 6): the live candidates of a step are rarely a whole number of rounds of backbone tiles (1400 of L = 50
-        # are one full round of four-sequence tiles + a remainder round with a third of the chip idle). The compacted list runs as
-        # A = its first `n_a` entries (whole rounds) and B = the rest: backbone(A), then backbone(B) with A's x0-hat + reward net on a
-        # side stream filling the CUs B leaves idle. Same kernels on the same rows (a row's result does not depend on its batch or
-        # tile): same bits (tests/test_skip_gpu.py).
-        n_a = self._pm_split_rows(fb, rf, n, L)
-        if n_a:
-            side, ev_a, ev_done = ops.side_stream(dev, 0), torch.cuda.Event(), torch.cuda.Event()
-            sc_buf = torch.empty((n, rf.w_eff.shape[1]), dtype=torch.float32, device=dev)
-            c_a, c_b = ws.count3[1:2], ws.count3[2:3]
-            cand_rows = cand.view(n, L)
         for i in range(S):
             ops.propose(logits, x, sched[i, 2], sched[i, 1], M, self._rng(i, M, B, L, logits), cand=cand)
             candidate_windows(cand, x, margin=0, flags=ws.flags)
-            if n_a:
-                main = torch.cuda.current_stream()
-                ops.compact_by_key(ws.flags, ws.live_idx, ws.slot, ws.count3, split=n_a)     # keys are 0 / 1: the order of compact_flags
-                ops.gather_rows(cand_rows, ws.live_idx, ws.count, toks_c)
-                fb.forward_rows(cand_rows, count=c_a, out=lg_c[:n_a], row_idx=ws.live_idx, scatter=False)
-                ev_a.record(main)
-                fb.forward_rows(cand_rows, count=c_b, out=lg_c[n_a:], row_idx=ws.live_idx[n_a:], scatter=False)
-                with torch.cuda.stream(side):
-                    side.wait_event(ev_a)
-                    _, xh_a = ops.x0hat(lg_c[:n_a], toks_c[:n_a], want_tokens=True, want_onehot=False)
-                    rf.forward_tokens(xh_a, count=c_a, out=sc_buf[:n_a])
-                    ev_done.record(side)
-                _, xh_b = ops.x0hat(lg_c[n_a:], toks_c[n_a:], want_tokens=True, want_onehot=False)
-                rf.forward_tokens(xh_b, count=c_b, out=sc_buf[n_a:])
-                main.wait_event(ev_done)
-                sc = sc_buf.reshape(-1)
-            else:
-                ops.compact_flags(ws.flags, ws.live_idx, ws.slot, ws.count)
-                fb.forward_rows(cand.view(n, L), count=ws.count, out=lg_c, row_idx=ws.live_idx, scatter=False)
-                ops.gather_rows(cand.view(n, L), ws.live_idx, ws.count, toks_c)
-                _, xh = ops.x0hat(lg_c, toks_c, want_tokens=True, want_onehot=False)   # :1415-1419 on the compacted rows
-                sc = rf.forward_tokens(xh, count=ws.count).reshape(-1)                 # :1430
+            ops.compact_flags(ws.flags, ws.live_idx, ws.slot, ws.count)
+            fb.forward_rows(cand.view(n, L), count=ws.count, out=lg_c, row_idx=ws.live_idx, scatter=False)
+            ops.gather_rows(cand.view(n, L), ws.live_idx, ws.count, toks_c)
+            _, xh = ops.x0hat(lg_c, toks_c, want_tokens=True, want_onehot=False)   # :1415-1419 on the compacted rows
+            sc = rf.forward_tokens(xh, count=ws.count).reshape(-1)                 # :1430
             if self.trace is not None or self.state_trace is not None:
                 self._record(logits, self._dense_scores(sc, ws, B, M), x)
             x_next = self._select_compact(sc, ws, cand, i)
@@ -1230,10 +1179,8 @@ class Diffusion(nn.Module):
                                   options=True, task="dna"):
         """SVDD-PM decode (:1105-1145). NB the reference compares `options == "True"` (a string, :1414):
         the default `options=True` therefore takes the heuristic branch there too."""
-        self._require_gpu()
-        B, L, S, M = self._batch_size(eval_sp_size), self.config.model.length, self._num_steps(num_steps), sample_M
-        sched, _, _ = self._schedule(S, eps)
-        x = torch.full((B, L), self.mask_index, dtype=torch.uint8, device=self.device)
+        B, L, S, sched, x = self._decode_start(num_steps, eps, eval_sp_size)
+        M = sample_M
         rf = self.reward_callable(reward_model)
         fb = self._fused_backbone_or_none(L)
         if options == "True" and task != "rna_saluki" and fb is not None and self._can_skip(rf, L, M):
@@ -1250,10 +1197,7 @@ class Diffusion(nn.Module):
     @torch.no_grad()
     def controlled_sample_TDS(self, reward_model, alpha, num_steps=None, eps=1e-5, eval_sp_size=None, sample_M=10):
         """SMC/TDS baseline decode (:938-978)."""
-        self._require_gpu()
-        B, L, S = self._batch_size(eval_sp_size), self.config.model.length, self._num_steps(num_steps)
-        sched, _, _ = self._schedule(S, eps)
-        x = torch.full((B, L), self.mask_index, dtype=torch.uint8, device=self.device)
+        B, L, S, sched, x = self._decode_start(num_steps, eps, eval_sp_size)
         carry = self._tds_carry(reward_model, L)
         if carry is not None:
             carry["prior"] = True
