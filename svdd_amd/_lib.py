@@ -22,24 +22,9 @@ SELECT_ARGMAX, SELECT_MULTINOMIAL = 0, 1
 PRECISIONS = {"f32": 0, "f16x3": 1, "bf16x3": 2, "f16": 3, "bf16": 4}      # enum SVDD_PREC_* of include/svdd_hip.h
 MAX_M = 1024
 
-EXPORTS = (
-    "svdd_abi_version", "svdd_device_info", "svdd_propose", "svdd_sample_categorical", "svdd_select", "svdd_x0hat",
-    "svdd_finalize", "svdd_transform_samples", "svdd_subs_logp", "svdd_tds_resample",
-    "svdd_set_option", "svdd_selftest_fastmath", "svdd_profile_enable", "svdd_profile_collect",
-    "svdd_gru_bidir_f32", "svdd_gru_bidir_train_f32", "svdd_gru_bidir_bwd_f32", "svdd_epilogue_ln_f32", "svdd_conv1d_cl_f32",
-    "svdd_conv1d_set_dynamic", "svdd_gru_set_mode", "svdd_conv_tower_f32", "svdd_backbone_cnn_f32", "svdd_value_tail_f32",
-    "svdd_candidate_windows", "svdd_conv_tower_windows_f32", "svdd_k1_stats",
-    "svdd_backbone_cnn_lp", "svdd_conv_tower_lp", "svdd_conv_tower_windows_lp", "svdd_gru_bidir_lp", "svdd_value_tail_lp",
-    "svdd_compact_flags", "svdd_compact_by_key", "svdd_gather_rows", "svdd_advance_rows", "svdd_select_compact", "svdd_set_tower_version", "svdd_set_backbone_packing",
-    "svdd_trunk_gemm", "svdd_trunk_act_split", "svdd_trunk_layernorm_split", "svdd_trunk_attn_pool", "svdd_trunk_stem_unfold", "svdd_trunk_attn_small",
-    "svdd_trunk_windows", "svdd_trunk_stem_unfold_win", "svdd_trunk_attn_pool_win",
-    "svdd_bb_layer_fwd_f32", "svdd_bb_layer_bwd_f32", "svdd_mt19937_uniform_f32",
-    "svdd_backbone_set_workspace", "svdd_backbone_split_status", "svdd_backbone_cnn_save_f32", "svdd_backbone_cnn_grad_f32",
-    "svdd_dps_probs", "svdd_dps_probs_bwd", "svdd_dps_guided_q", "svdd_reward_stem_f32", "svdd_reward_stem_bwd_f32",
-    "svdd_conv1d_cl_gated_f32", "svdd_reward_tail_grad_f32", "svdd_sum_gate_f32", "svdd_gru_bidir_train2_f32", "svdd_gru_bidir_bwd2_f32",
-    "svdd_classifier_propose", "svdd_elbo_mask", "svdd_elbo_nll",
-)
-OPT_FORCE_EXACT = 0
+# enum SVDD_OPT_* of include/svdd_hip.h (tests/test_host_cpu.py compares names and values with the header)
+OPT_FORCE_EXACT, OPT_MSPLIT, OPT_SELECT_ONE_ROW, OPT_BACKBONE_LP_VERSION, OPT_TRUNK_GEMM_VERSION = 0, 1, 2, 3, 4
+OPT_CAND_ROW_STRIDE, OPT_TRUNK_PLANES_F32, OPT_BACKBONE_SPLIT, OPT_SELECT_BATCHES = 5, 6, 7, 8
 
 
 class SvddRng(ctypes.Structure):
@@ -51,6 +36,89 @@ class SvddRng(ctypes.Structure):
 
 class SvddError(RuntimeError):
     pass
+
+
+vp, cstr, i32, i64, f32, f64 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double
+pi32, pf64, RNG = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(SvddRng)      # host pointers
+
+
+class STREAM(ctypes.c_void_p):
+    """The hipStream_t a launch goes to. Always the last parameter; call() fills it with torch's current stream."""
+
+
+# Every exported function -> its parameter types, in the header's order (tests/test_host_cpu.py compares each entry with the
+# prototype in include/svdd_hip.h). All return int (0 or a negative SVDD_E_* code).
+SIGNATURES = {
+    "svdd_abi_version": (),
+    "svdd_device_info": (cstr, i32, pi32),
+    "svdd_propose": (vp, vp, f32, f32, i32, i32, i32, i32, RNG, vp, vp, vp, STREAM),
+    "svdd_sample_categorical": (vp, vp, i32, i32, i32, i32, RNG, vp, vp, STREAM),
+    "svdd_select": (vp, vp, i32, i32, i32, i32, RNG, vp, vp, vp, STREAM),
+    "svdd_x0hat": (vp, vp, i32, i32, i32, vp, vp, STREAM),
+    "svdd_finalize": (vp, vp, i32, i32, i32, vp, vp, STREAM),
+    "svdd_transform_samples": (vp, i32, i32, i32, vp, STREAM),
+    "svdd_subs_logp": (vp, vp, i32, i32, i32, vp, STREAM),
+    "svdd_tds_resample": (vp, vp, f64, vp, vp, i32, i32, vp, vp, vp, STREAM),
+    "svdd_set_option": (i32, i32),
+    "svdd_selftest_fastmath": (pf64,),
+    "svdd_profile_enable": (i32,),
+    "svdd_profile_collect": (i32, pf64, pi32),
+    "svdd_gru_bidir_f32": (vp, vp, vp, vp, i32, i32, vp, STREAM),
+    "svdd_gru_bidir_train_f32": (vp, vp, vp, vp, vp, i32, i32, STREAM),
+    "svdd_gru_bidir_bwd_f32": (vp, vp, vp, vp, vp, i32, i32, STREAM),
+    "svdd_epilogue_ln_f32": (vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, STREAM),
+    "svdd_conv1d_cl_f32": (vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, STREAM),
+    "svdd_conv1d_set_dynamic": (i32,),
+    "svdd_gru_set_mode": (i32,),
+    "svdd_conv_tower_f32": (vp, vp, vp, vp, i32, i32, i32, i32, vp, STREAM),
+    "svdd_backbone_cnn_f32": (vp, vp, vp, vp, vp, vp, i32, i32, i32, pi32, vp, vp, i32, STREAM),
+    "svdd_value_tail_f32": (vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, STREAM),
+    "svdd_candidate_windows": (vp, vp, i32, i32, i32, i32, vp, vp, STREAM),
+    "svdd_conv_tower_windows_f32": (vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, STREAM),
+    "svdd_k1_stats": (vp,),
+    "svdd_backbone_cnn_lp": (vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, pi32, i32, vp, vp, i32, STREAM),
+    "svdd_conv_tower_lp": (vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, STREAM),
+    "svdd_conv_tower_windows_lp": (vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, STREAM),
+    "svdd_gru_bidir_lp": (vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, STREAM),
+    "svdd_value_tail_lp": (vp, vp, vp, vp, vp, vp, f32, vp, i32, i32, i32, vp, i32, STREAM),
+    "svdd_compact_flags": (vp, i32, vp, vp, vp, STREAM),
+    "svdd_compact_by_key": (vp, i32, vp, vp, vp, i32, STREAM),
+    "svdd_gather_rows": (vp, vp, vp, i32, i32, vp, STREAM),
+    "svdd_advance_rows": (vp, vp, vp, i32, i32, i32, vp, STREAM),
+    "svdd_select_compact": (vp, vp, vp, vp, i32, i32, i32, i32, RNG, vp, vp, vp, vp, vp, STREAM),
+    "svdd_set_tower_version": (i32,),
+    "svdd_set_backbone_packing": (i32,),
+    "svdd_trunk_gemm": (vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, i32, i32, STREAM),
+    "svdd_trunk_act_split": (vp, vp, vp, i32, i64, i32, i32, i32, vp, vp, vp, STREAM),
+    "svdd_trunk_layernorm_split": (vp, vp, vp, f32, i64, i32, vp, vp, vp, i32, STREAM),
+    "svdd_trunk_attn_pool": (vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, STREAM),
+    "svdd_trunk_stem_unfold": (vp, i32, i32, vp, vp, STREAM),
+    "svdd_trunk_attn_small": (vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, STREAM),
+    "svdd_trunk_windows": (vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, STREAM),
+    "svdd_trunk_stem_unfold_win": (vp, i32, i32, i32, vp, vp, vp, vp, vp, STREAM),
+    "svdd_trunk_attn_pool_win": (vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, STREAM),
+    "svdd_bb_layer_fwd_f32": (vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, i64, i32, i32, STREAM),
+    "svdd_bb_layer_bwd_f32": (vp, vp, vp, vp, f32, vp, vp, vp, vp, i64, i32, i32, STREAM),
+    "svdd_mt19937_uniform_f32": (vp, vp, i64, STREAM),
+    "svdd_backbone_set_workspace": (vp, i64),
+    "svdd_backbone_split_status": (pi32,),
+    "svdd_backbone_cnn_save_f32": (vp, vp, vp, vp, vp, vp, i32, i32, i32, pi32, vp, vp, vp, STREAM),
+    "svdd_backbone_cnn_grad_f32": (vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, pi32, STREAM),
+    "svdd_dps_probs": (vp, vp, i32, i32, vp, STREAM),
+    "svdd_dps_probs_bwd": (vp, vp, vp, i32, i32, vp, vp, STREAM),
+    "svdd_dps_guided_q": (vp, vp, vp, vp, f32, f32, f32, i32, i32, vp, STREAM),
+    "svdd_reward_stem_f32": (vp, vp, vp, vp, i32, i32, i32, STREAM),
+    "svdd_reward_stem_bwd_f32": (vp, vp, vp, i32, i32, i32, STREAM),
+    "svdd_conv1d_cl_gated_f32": (vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, STREAM),
+    "svdd_reward_tail_grad_f32": (vp, vp, vp, vp, vp, vp, vp, f32, i32, i32, vp, vp, STREAM),
+    "svdd_sum_gate_f32": (vp, vp, vp, vp, i64, STREAM),
+    "svdd_gru_bidir_train2_f32": (vp, vp, vp, vp, vp, vp, i32, i32, STREAM),
+    "svdd_gru_bidir_bwd2_f32": (vp, vp, vp, vp, vp, vp, vp, i32, i32, STREAM),
+    "svdd_classifier_propose": (vp, i32, vp, vp, f32, f32, f32, i32, i32, RNG, vp, vp, vp, STREAM),
+    "svdd_elbo_mask": (vp, i32, i32, i32, f64, RNG, vp, vp, vp, vp, vp, vp, STREAM),
+    "svdd_elbo_nll": (vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, STREAM),
+}
+EXPORTS = tuple(SIGNATURES)
 
 
 def build(force=False):
@@ -85,79 +153,52 @@ def lib():
             raise SvddError(f"libsvdd_hip.so does not export {name}")
     if L.svdd_abi_version() != ABI_VERSION:
         raise SvddError(f"libsvdd_hip.so ABI {L.svdd_abi_version()} != binding ABI {ABI_VERSION}; rebuild")
-    vp, f32, i32 = ctypes.c_void_p, ctypes.c_float, ctypes.c_int
-    L.svdd_propose.argtypes = [vp, vp, f32, f32, i32, i32, i32, i32, ctypes.POINTER(SvddRng), vp, vp, vp, vp]
-    L.svdd_sample_categorical.argtypes = [vp, vp, i32, i32, i32, i32, ctypes.POINTER(SvddRng), vp, vp, vp]
-    L.svdd_select.argtypes = [vp, vp, i32, i32, i32, i32, ctypes.POINTER(SvddRng), vp, vp, vp, vp]
-    L.svdd_x0hat.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
-    L.svdd_finalize.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
-    L.svdd_transform_samples.argtypes = [vp, i32, i32, i32, vp, vp]
-    L.svdd_subs_logp.argtypes = [vp, vp, i32, i32, i32, vp, vp]
-    L.svdd_tds_resample.argtypes = [vp, vp, ctypes.c_double, vp, vp, i32, i32, vp, vp, vp, vp]
-    L.svdd_set_option.argtypes = [i32, i32]
-    L.svdd_mt19937_uniform_f32.argtypes = [vp, vp, ctypes.c_longlong, vp]
-    L.svdd_backbone_set_workspace.argtypes = [vp, ctypes.c_longlong]
-    L.svdd_backbone_split_status.argtypes = [ctypes.POINTER(ctypes.c_int)]
-    L.svdd_selftest_fastmath.argtypes = [ctypes.POINTER(ctypes.c_double)]
-    L.svdd_gru_bidir_f32.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
-    L.svdd_gru_bidir_train_f32.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
-    L.svdd_gru_bidir_bwd_f32.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
-    L.svdd_conv1d_set_dynamic.argtypes = [i32]
-    L.svdd_gru_set_mode.argtypes = [i32]
-    L.svdd_conv_tower_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
-    L.svdd_value_tail_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]
-    L.svdd_candidate_windows.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
-    L.svdd_conv_tower_windows_f32.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
-    L.svdd_backbone_cnn_f32.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, ctypes.POINTER(ctypes.c_int), vp, vp, i32, vp]
-    L.svdd_backbone_cnn_save_f32.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, ctypes.POINTER(ctypes.c_int), vp, vp, vp, vp]
-    L.svdd_backbone_cnn_grad_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, ctypes.POINTER(ctypes.c_int), vp]
-    L.svdd_conv1d_cl_f32.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp]
-    L.svdd_epilogue_ln_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int64, i32, i32, vp]
-    L.svdd_k1_stats.argtypes = [vp]
-    L.svdd_set_tower_version.argtypes = [i32]
-    L.svdd_set_backbone_packing.argtypes = [i32]
-    L.svdd_compact_flags.argtypes = [vp, i32, vp, vp, vp, vp]
-    L.svdd_compact_by_key.argtypes = [vp, i32, vp, vp, vp, i32, vp]
-    L.svdd_gather_rows.argtypes = [vp, vp, vp, i32, i32, vp, vp]
-    L.svdd_advance_rows.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
-    L.svdd_select_compact.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, ctypes.POINTER(SvddRng), vp, vp, vp, vp, vp, vp]
-    L.svdd_conv_tower_lp.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp]
-    L.svdd_conv_tower_windows_lp.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp]
-    L.svdd_gru_bidir_lp.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, vp]
-    L.svdd_value_tail_lp.argtypes = [vp, vp, vp, vp, vp, vp, f32, vp, i32, i32, i32, vp, i32, vp]
-    L.svdd_backbone_cnn_lp.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, ctypes.POINTER(ctypes.c_int), i32, vp, vp, i32, vp]
-    i64 = ctypes.c_int64
-    L.svdd_trunk_gemm.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, i32, i32, vp]
-    L.svdd_trunk_act_split.argtypes = [vp, vp, vp, i32, i64, i32, i32, i32, vp, vp, vp, vp]
-    L.svdd_trunk_layernorm_split.argtypes = [vp, vp, vp, f32, i64, i32, vp, vp, vp, i32, vp]
-    L.svdd_trunk_attn_pool.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp]
-    L.svdd_trunk_stem_unfold.argtypes = [vp, i32, i32, vp, vp, vp]
-    L.svdd_bb_layer_fwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, i64, i32, i32, vp]
-    L.svdd_bb_layer_bwd_f32.argtypes = [vp, vp, vp, vp, f32, vp, vp, vp, vp, i64, i32, i32, vp]
-    L.svdd_trunk_windows.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
-    L.svdd_trunk_stem_unfold_win.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
-    L.svdd_trunk_attn_pool_win.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
-    L.svdd_trunk_attn_small.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]
-    L.svdd_dps_probs.argtypes = [vp, vp, i32, i32, vp, vp]
-    L.svdd_dps_probs_bwd.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
-    L.svdd_classifier_propose.argtypes = [vp, i32, vp, vp, f32, f32, f32, i32, i32, ctypes.POINTER(SvddRng), vp, vp, vp, vp]
-    L.svdd_elbo_mask.argtypes = [vp, i32, i32, i32, ctypes.c_double, ctypes.POINTER(SvddRng), vp, vp, vp, vp, vp, vp, vp]
-    L.svdd_elbo_nll.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
-    L.svdd_dps_guided_q.argtypes = [vp, vp, vp, vp, f32, f32, f32, i32, i32, vp, vp]
-    L.svdd_reward_stem_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
-    L.svdd_reward_stem_bwd_f32.argtypes = [vp, vp, vp, i32, i32, i32, vp]
-    L.svdd_conv1d_cl_gated_f32.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]
-    L.svdd_reward_tail_grad_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, f32, i32, i32, vp, vp, vp]
-    L.svdd_sum_gate_f32.argtypes = [vp, vp, vp, vp, i64, vp]
-    L.svdd_gru_bidir_train2_f32.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp]
-    L.svdd_gru_bidir_bwd2_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
-    L.svdd_profile_enable.argtypes = [i32]
-    L.svdd_profile_collect.argtypes = [i32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]
-    L.svdd_device_info.argtypes = [ctypes.c_char_p, i32, ctypes.POINTER(ctypes.c_int)]
-    for name in EXPORTS:
-        getattr(L, name).restype = ctypes.c_int
+    for name, sig in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.argtypes, fn.restype = [vp if t is STREAM else t for t in sig], ctypes.c_int
     _lib = L
     return L
+
+
+_CALLS = {}            # name -> (ctypes function, parameters the caller passes, pointer positions, number positions, takes the stream)
+_NUMBERS = (int, float, bool)
+_Tensor = _current_stream = None
+
+
+def _resolve(name):
+    """The per-function facts of call(), read from SIGNATURES once per function."""
+    global _Tensor, _current_stream
+    if name not in SIGNATURES:
+        raise SvddError(f"{name} is not a function of libsvdd_hip.so (include/svdd_hip.h)")
+    import torch
+    _Tensor, _current_stream = torch.Tensor, torch.cuda.current_stream
+    sig = SIGNATURES[name]
+    stream = bool(sig) and sig[-1] is STREAM
+    sig = sig[:len(sig) - stream]
+    numbers = tuple(i for i, t in enumerate(sig) if t in (i32, i64, f32, f64))
+    ent = _CALLS[name] = (getattr(lib(), name), len(sig), tuple(i for i in range(len(sig)) if i not in numbers), numbers, stream)
+    return ent
+
+
+def call(name, *args):
+    """The one door to the library: svdd_<name>(*args) on torch's current stream, return code checked under the function's own
+    name. In a pointer parameter a tensor stands for its data_ptr() and None for NULL; ints and ctypes objects (byref(...), arrays)
+    pass as they are. A tensor where the function takes a number raises instead of being read as an address. The stream is
+    appended here for the functions whose entry in SIGNATURES ends in STREAM: callers never pass it."""
+    fn, n, pointers, numbers, stream = _CALLS.get(name) or _resolve(name)
+    if len(args) != n:
+        raise TypeError(f"{name} takes {n} arguments{' (and the stream, which call() adds)' if stream else ''}, got {len(args)}")
+    args = list(args)
+    for i in pointers:
+        a = args[i]
+        if a is not None and isinstance(a, _Tensor):
+            args[i] = a.data_ptr()
+    for i in numbers:
+        if args[i].__class__ not in _NUMBERS and isinstance(args[i], _Tensor):
+            raise TypeError(f"{name}: argument {i} is a number, got a tensor (pass int(...) / float(...) of it)")
+    if stream:
+        args.append(_current_stream().cuda_stream)
+    check(fn(*args), name)
 
 
 def device_info():
@@ -170,19 +211,19 @@ def device_info():
 
 
 _OPTIONS = {}          # (key, sub) -> the value this process last set through set_option (absent: the library default)
-_OPTION_DEFAULTS = {(4, "version"): 2, (4, "height"): 40, (4, "concurrency"): 51}
+_OPTION_DEFAULTS = {(OPT_TRUNK_GEMM_VERSION, "version"): 2, (OPT_TRUNK_GEMM_VERSION, "height"): 40, (OPT_TRUNK_GEMM_VERSION, "concurrency"): 51}
 
 
 def _option_slot(key, value):
     """SVDD_OPT_TRUNK_GEMM_VERSION multiplexes three settings on one key (include/svdd_hip.h): kernel version, tile height (40 - 42),
     chains sharing the chip (51 - 54). Each is remembered separately."""
-    if key == 4:
-        return (4, "height" if 40 <= value <= 42 else "concurrency" if 51 <= value <= 54 else "version")
+    if key == OPT_TRUNK_GEMM_VERSION:
+        return (key, "height" if 40 <= value <= 42 else "concurrency" if 51 <= value <= 54 else "version")
     return (key, None)
 
 
 def current_option(key, like=0):
-    """The value last set for `key` (for key 4: for the setting `like` belongs to)."""
+    """The value last set for `key` (for OPT_TRUNK_GEMM_VERSION: for the setting `like` belongs to)."""
     slot = _option_slot(key, like)
     return _OPTIONS.get(slot, _OPTION_DEFAULTS.get(slot, 0))
 
@@ -203,20 +244,20 @@ def set_force_exact(on):
 
 
 def profile_enable(on=True):
-    check(lib().svdd_profile_enable(int(bool(on))), "svdd_profile_enable")
+    call("svdd_profile_enable", int(bool(on)))
 
 
 def profile_collect(kernel):
     """(total_ms, launches) of kernel 0 = propose / 1 = select since profiling was enabled."""
     tot, n = ctypes.c_double(0.0), ctypes.c_int(0)
-    check(lib().svdd_profile_collect(kernel, ctypes.byref(tot), ctypes.byref(n)), "svdd_profile_collect")
+    call("svdd_profile_collect", kernel, ctypes.byref(tot), ctypes.byref(n))
     return tot.value, n.value
 
 
 def selftest_fastmath():
     """(max rel err of fast g over all 2^24 uniforms, of fast exp on [-80,0], of fast log on (1,4])."""
     out = (ctypes.c_double * 3)()
-    check(lib().svdd_selftest_fastmath(out), "svdd_selftest_fastmath")
+    call("svdd_selftest_fastmath", out)
     return tuple(out)
 
 

@@ -44,7 +44,7 @@ def init_from_env(backend=None):
         # once — which another process's kernels on the same CUs can prevent. One workgroup per sequence then (same bits, no
         # inter-workgroup wait).
         from . import _lib
-        _lib.set_option(7, 1)
+        _lib.set_option(_lib.OPT_BACKBONE_SPLIT, 1)
     return rank, world, local
 
 

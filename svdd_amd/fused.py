@@ -17,6 +17,7 @@ Numerics: fp32 throughout; results differ from the plain modules only by fp32 re
 well inside the 1e-4 soft-value tolerance of the north star (tests/test_fused_gpu.py).
 """
 import ctypes
+import math
 
 import torch
 import torch.nn.functional as F
@@ -61,14 +62,8 @@ def gru_bidir(x_nlc, wpack, bpack, count=None, out=None):
     n, L, _ = x_nlc.shape
     if out is None:
         out = torch.empty((2, n, L, 64), dtype=torch.float32, device=x_nlc.device)
-    rc = _lib.lib().svdd_gru_bidir_f32(x_nlc.data_ptr(), wpack.data_ptr(), bpack.data_ptr(), out.data_ptr(), n, L,
-                                       _ptr(count), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _lib.check(rc, "svdd_gru_bidir_f32")
+    _lib.call("svdd_gru_bidir_f32", x_nlc, wpack, bpack, out, n, L, count)
     return out
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
 
 
 def pack_gru_bwd(gru):
@@ -97,9 +92,7 @@ class GruBidirFunction(torch.autograd.Function):
         n, L, _ = x.shape
         out = torch.empty((2, n, L, 64), dtype=torch.float32, device=x.device)
         save = torch.empty((2, n, L, 4, 64), dtype=torch.float32, device=x.device)
-        rc = _lib.lib().svdd_gru_bidir_train_f32(x.data_ptr(), wpack.data_ptr(), bpack.data_ptr(), out.data_ptr(), save.data_ptr(),
-                                                 n, L, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(rc, "svdd_gru_bidir_train_f32")
+        _lib.call("svdd_gru_bidir_train_f32", x, wpack, bpack, out, save, n, L)
         ctx.save_for_backward(out, save, wpack_bwd)
         return out
 
@@ -109,9 +102,7 @@ class GruBidirFunction(torch.autograd.Function):
         _, n, L, _ = out.shape
         g = grad_out.contiguous().float()
         dx = torch.empty((2, n, L, 64), dtype=torch.float32, device=out.device)
-        rc = _lib.lib().svdd_gru_bidir_bwd_f32(g.data_ptr(), out.data_ptr(), save.data_ptr(), wpack_bwd.data_ptr(), dx.data_ptr(),
-                                               n, L, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(rc, "svdd_gru_bidir_bwd_f32")
+        _lib.call("svdd_gru_bidir_bwd_f32", g, out, save, wpack_bwd, dx, n, L)
         return dx[0] + dx[1], None, None, None
 
 
@@ -150,22 +141,17 @@ class BackboneLayersFunction(torch.autograd.Function):
         feat = feat.contiguous().float()
         B, L, C = feat.shape
         n = len(packs)
-        lib, st = _lib.lib(), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         rows = B * L
         feats = torch.empty((n + 1, B, L, C), dtype=torch.float32, device=feat.device)
         masks = torch.empty((n, B, L, C), dtype=torch.uint8, device=feat.device)
         hn = torch.empty_like(feat)
         feats[0].copy_(feat)
-        _lib.check(lib.svdd_bb_layer_fwd_f32(None, None, feats[0].data_ptr(), tb[0].data_ptr(), gamma[0].data_ptr(), beta[0].data_ptr(),
-                                             eps, None, None, hn.data_ptr(), rows, L, C, st), "svdd_bb_layer_fwd_f32")
+        _lib.call("svdd_bb_layer_fwd_f32", None, None, feats[0], tb[0], gamma[0], beta[0], eps, None, None, hn, rows, L, C)
         for i, (wp, _, d) in enumerate(packs):
             y = conv1d_cl(hn, wp, C, 9, d)
             last = i + 1 == n
-            _lib.check(lib.svdd_bb_layer_fwd_f32(y.data_ptr(), bias[i].data_ptr(), feats[i].data_ptr(),
-                                                 None if last else tb[i + 1].data_ptr(), None if last else gamma[i + 1].data_ptr(),
-                                                 None if last else beta[i + 1].data_ptr(), eps, feats[i + 1].data_ptr(),
-                                                 masks[i].data_ptr(), None if last else hn.data_ptr(), rows, L, C, st),
-                       "svdd_bb_layer_fwd_f32")
+            _lib.call("svdd_bb_layer_fwd_f32", y, bias[i], feats[i], None if last else tb[i + 1], None if last else gamma[i + 1],
+                      None if last else beta[i + 1], eps, feats[i + 1], masks[i], None if last else hn, rows, L, C)
         ctx.save_for_backward(feats, masks, tb, gamma)
         ctx.cfg = (eps, packs)
         if BackboneLayersFunction.keep_masks:                     # tests: the ReLU decisions of this forward pass
@@ -177,7 +163,6 @@ class BackboneLayersFunction(torch.autograd.Function):
         feats, masks, tb, gamma = ctx.saved_tensors
         eps, packs = ctx.cfg
         n, B, L, C = masks.shape
-        lib, st = _lib.lib(), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         rows = B * L
         G = G.contiguous().float()
         gt = G * masks[n - 1]                                      # gradient at the last layer's pre-activation
@@ -185,9 +170,7 @@ class BackboneLayersFunction(torch.autograd.Function):
             g_hn = conv1d_cl(gt, packs[i][1], C, 9, packs[i][2])
             G_new = torch.empty_like(G)
             gt = torch.empty_like(G) if i else None
-            _lib.check(lib.svdd_bb_layer_bwd_f32(g_hn.data_ptr(), feats[i].data_ptr(), tb[i].data_ptr(), gamma[i].data_ptr(), eps,
-                                                 G.data_ptr(), masks[i - 1].data_ptr() if i else None, G_new.data_ptr(),
-                                                 gt.data_ptr() if i else None, rows, L, C, st), "svdd_bb_layer_bwd_f32")
+            _lib.call("svdd_bb_layer_bwd_f32", g_hn, feats[i], tb[i], gamma[i], eps, G, masks[i - 1] if i else None, G_new, gt, rows, L, C)
             G = G_new
         return G, None, None, None, None, None, None
 
@@ -208,10 +191,7 @@ def conv1d_cl(x_nlc, wpack, cout, taps, dilation, bias=None, f_prev=None, act=-1
     y = torch.empty((n, L, cout), dtype=torch.float32, device=x_nlc.device)
     hn = torch.empty_like(y) if ln is not None else None
     tb, gamma, beta = ln if ln is not None else (None, None, None)
-    rc = _lib.lib().svdd_conv1d_cl_f32(x_nlc.data_ptr(), wpack.data_ptr(), y.data_ptr(), n, L, cin, cout, taps, dilation,
-                                       _ptr(bias), _ptr(f_prev), int(act), _ptr(tb), _ptr(gamma), _ptr(beta), _ptr(hn),
-                                       ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _lib.check(rc, "svdd_conv1d_cl_f32")
+    _lib.call("svdd_conv1d_cl_f32", x_nlc, wpack, y, n, L, cin, cout, taps, dilation, bias, f_prev, int(act), tb, gamma, beta, hn)
     return y if ln is None else (y, hn)
 
 
@@ -240,10 +220,7 @@ def conv_tower(onehot, tiles, bias, residual_mask, count=None):
     assert onehot.is_cuda and onehot.dtype == torch.float32 and onehot.is_contiguous() and onehot.shape[2] == 4
     n, L, _ = onehot.shape
     out = torch.empty((n, L, 64), dtype=torch.float32, device=onehot.device)
-    rc = _lib.lib().svdd_conv_tower_f32(onehot.data_ptr(), tiles.data_ptr(), bias.data_ptr(), out.data_ptr(), n, L,
-                                        bias.shape[0] - 1, int(residual_mask), _ptr(count),
-                                        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _lib.check(rc, "svdd_conv_tower_f32")
+    _lib.call("svdd_conv_tower_f32", onehot, tiles, bias, out, n, L, bias.shape[0] - 1, int(residual_mask), count)
     return out
 
 
@@ -268,10 +245,7 @@ def value_tail(h, w1pack, b1f, w_eff, b_eff, count=None, out=None):
     if out is None:
         out = torch.empty((n, T), dtype=torch.float32, device=h.device)
     assert out.is_contiguous() and out.shape == (n, T)
-    rc = _lib.lib().svdd_value_tail_f32(h[0].data_ptr(), h[1].data_ptr(), w1pack.data_ptr(), b1f.data_ptr(),
-                                        w_eff.data_ptr(), b_eff.data_ptr(), out.data_ptr(), n, L, T, _ptr(count),
-                                        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _lib.check(rc, "svdd_value_tail_f32")
+    _lib.call("svdd_value_tail_f32", h[0], h[1], w1pack, b1f, w_eff, b_eff, out, n, L, T, count)
     return out
 
 
@@ -306,19 +280,22 @@ def pack_backbone(cnn):
 
 
 _BB_SPLIT_WS = {}          # device -> the scratch tensor registered with svdd_backbone_set_workspace (kept alive here)
+_bb_split_registered = None    # the device whose tensor the library holds
+_bb_split_used = False         # a launch since the last check_backbone_split() may have been split
 BB_SPLIT_MAX_SEQ = 128     # the small-batch form splits a sequence over 2 workgroups up to 128 sequences, over 4 up to 64
 
 
 def _backbone_split_workspace(dev):
     """Caller-owned scratch of the small-batch backbone (svdd_backbone_cnn_f32 on 2 / 4 workgroups per sequence, same bits):
     the double-buffered LayerNorm images of up to 128 sequences + arrival counters (27 MB), registered once per process."""
+    global _bb_split_registered
     key = str(dev)
     nbytes = BB_SPLIT_MAX_SEQ * (2 * 208 * 128 * 4 + 4) + 4
     if key not in _BB_SPLIT_WS:
         _BB_SPLIT_WS[key] = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-    if _BB_SPLIT_WS.get("registered") != key:          # the library holds ONE workspace pointer: follow the device in use
-        _lib.check(_lib.lib().svdd_backbone_set_workspace(_BB_SPLIT_WS[key].data_ptr(), nbytes), "svdd_backbone_set_workspace")
-        _BB_SPLIT_WS["registered"] = key
+    if _bb_split_registered != key:                    # the library holds ONE workspace pointer: follow the device in use
+        _lib.call("svdd_backbone_set_workspace", _BB_SPLIT_WS[key], nbytes)
+        _bb_split_registered = key
     return _BB_SPLIT_WS[key]
 
 
@@ -351,10 +328,7 @@ def backbone_cnn_save(tokens, pk):
     rstd = torch.empty((n, nl, 208), dtype=torch.float32, device=dev)
     mask = torch.empty((n, nl + 2, 512), dtype=torch.int64, device=dev)
     dil = (ctypes.c_int * nl)(*pk["dil"])
-    rc = _lib.lib().svdd_backbone_cnn_save_f32(tokens.data_ptr(), pk["table0"].data_ptr(), pk["tiles"].data_ptr(), pk["vec"].data_ptr(),
-                                               pk["w2"].data_ptr(), out.data_ptr(), n, L, nl, dil, xhat.data_ptr(), rstd.data_ptr(),
-                                               mask.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _lib.check(rc, "svdd_backbone_cnn_save_f32")
+    _lib.call("svdd_backbone_cnn_save_f32", tokens, pk["table0"], pk["tiles"], pk["vec"], pk["w2"], out, n, L, nl, dil, xhat, rstd, mask)
     return out, (xhat, rstd, mask)
 
 
@@ -367,10 +341,7 @@ def backbone_cnn_grad(dlogits, pk, pkg, saved):
     g = dlogits.contiguous().float()
     dx = torch.empty((n, L, 5), dtype=torch.float32, device=g.device)
     dil = (ctypes.c_int * nl)(*pk["dil"])
-    rc = _lib.lib().svdd_backbone_cnn_grad_f32(g.data_ptr(), pkg["tiles_bwd"].data_ptr(), pkg["gamma"].data_ptr(), pk["w2"].data_ptr(),
-                                               pk["table0"].data_ptr(), xhat.data_ptr(), rstd.data_ptr(), mask.data_ptr(), dx.data_ptr(),
-                                               n, L, nl, dil, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _lib.check(rc, "svdd_backbone_cnn_grad_f32")
+    _lib.call("svdd_backbone_cnn_grad_f32", g, pkg["tiles_bwd"], pkg["gamma"], pk["w2"], pk["table0"], xhat, rstd, mask, dx, n, L, nl, dil)
     return dx
 
 
@@ -414,10 +385,12 @@ def check_backbone_split():
     """Raises if a group barrier of a small-batch backbone launch (several workgroups per sequence) timed out since the last
     check: its logits were computed from a partly exchanged image. Reads one int from the device (synchronises) — only after a
     split launch may have happened; the samplers call it at the end of every decode (Diffusion._decode_scope)."""
-    if not _BB_SPLIT_WS.pop("used", False):
+    global _bb_split_used
+    if not _bb_split_used:
         return
+    _bb_split_used = False
     err = ctypes.c_int(0)
-    _lib.check(_lib.lib().svdd_backbone_split_status(ctypes.byref(err)), "svdd_backbone_split_status")
+    _lib.call("svdd_backbone_split_status", ctypes.byref(err))
     if err.value:
         raise _lib.SvddError("svdd_backbone_cnn_f32: a workgroup of a small-batch (several workgroups per sequence) launch waited in vain "
                              "for its partners — something else occupied the CUs (another process or stream on this GPU). The logits "
@@ -427,19 +400,17 @@ def check_backbone_split():
 def backbone_cnn(tokens, pk, count=None, out=None, row_idx=None, scatter=False):
     """tokens [n, L] uint8 -> raw logits fp32 [n, L, 5]: the whole backbone forward in ONE launch
     (HIP kernel svdd_backbone_cnn_f32)."""
+    global _bb_split_used
     assert tokens.is_cuda and tokens.dtype == torch.uint8 and tokens.is_contiguous()
     n, L = tokens.shape
     if 104 < L <= 208 and count is None and row_idx is None and (n <= BB_SPLIT_MAX_SEQ or 0 < n % 256 <= BB_SPLIT_MAX_SEQ):
         _backbone_split_workspace(tokens.device)       # small batches, and the tail round of a batch that is not a multiple of the CUs
-        _BB_SPLIT_WS["used"] = True                    # -> check_backbone_split() at the end of the decode
+        _bb_split_used = True                          # -> check_backbone_split() at the end of the decode
     if out is None:
         out = torch.empty((n, L, 5), dtype=torch.float32, device=tokens.device)
     dil = (ctypes.c_int * len(pk["dil"]))(*pk["dil"])
-    rc = _lib.lib().svdd_backbone_cnn_f32(tokens.data_ptr(), pk["table0"].data_ptr(), pk["tiles"].data_ptr(),
-                                          pk["vec"].data_ptr(), pk["w2"].data_ptr(), out.data_ptr(), n, L,
-                                          len(pk["dil"]), dil, _ptr(count), _ptr(row_idx), int(scatter),
-                                          ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _lib.check(rc, "svdd_backbone_cnn_f32")
+    _lib.call("svdd_backbone_cnn_f32", tokens, pk["table0"], pk["tiles"], pk["vec"], pk["w2"], out, n, L, len(pk["dil"]), dil, count,
+              row_idx, int(scatter))
     return out
 
 
@@ -447,7 +418,6 @@ LP_DTYPES = {"f16x3": (torch.float16, 2), "bf16x3": (torch.bfloat16, 2), "f16": 
 
 
 def _pow2_floor(v):
-    import math
     return 2.0 ** math.floor(math.log2(v))
 
 
@@ -501,11 +471,8 @@ def backbone_cnn_lp(tokens, pk, count=None, out=None, row_idx=None, scatter=Fals
     if out is None:
         out = torch.empty((n, L, 5), dtype=torch.float32, device=tokens.device)
     dil = (ctypes.c_int * len(pk["dil"]))(*pk["dil"])
-    rc = _lib.lib().svdd_backbone_cnn_lp(tokens.data_ptr(), pk["table0"].data_ptr(), pk["tiles"].data_ptr(),
-                                         pk["vec"].data_ptr(), pk["lscale"].data_ptr(), pk["w2"].data_ptr(),
-                                         out.data_ptr(), n, L, len(pk["dil"]), dil, pk["prec"], _ptr(count), _ptr(row_idx),
-                                         int(scatter), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _lib.check(rc, "svdd_backbone_cnn_lp")
+    _lib.call("svdd_backbone_cnn_lp", tokens, pk["table0"], pk["tiles"], pk["vec"], pk["lscale"], pk["w2"], out, n, L, len(pk["dil"]), dil,
+              pk["prec"], count, row_idx, int(scatter))
     return out
 
 
@@ -572,10 +539,7 @@ def conv_tower_lp(tok, tiles, bias, inv, residual_mask, prec, count=None):
     assert tok.is_cuda and tok.dtype == torch.uint8 and tok.is_contiguous()
     n, L = tok.shape
     out = torch.empty((n, L, tiles_parts(tiles, bias), 64), dtype=tiles.dtype, device=tok.device)
-    rc = _lib.lib().svdd_conv_tower_lp(tok.data_ptr(), tiles.data_ptr(), bias.data_ptr(), inv.data_ptr(), out.data_ptr(),
-                                       n, L, bias.shape[0] - 1, int(residual_mask), _ptr(count), prec,
-                                       ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _lib.check(rc, "svdd_conv_tower_lp")
+    _lib.call("svdd_conv_tower_lp", tok, tiles, bias, inv, out, n, L, bias.shape[0] - 1, int(residual_mask), count, prec)
     return out
 
 
@@ -587,11 +551,8 @@ def conv_tower_windows_lp(cand, win, parent_out, tiles, bias, inv, residual_mask
     n = B * M
     if out is None:
         out = torch.empty((n, L, parent_out.shape[2], 64), dtype=tiles.dtype, device=cand.device)
-    rc = _lib.lib().svdd_conv_tower_windows_lp(cand.data_ptr(), tiles.data_ptr(), bias.data_ptr(), inv.data_ptr(),
-                                               win.data_ptr(), parent_out.data_ptr(), out.data_ptr(), n, L, M,
-                                               bias.shape[0] - 1, int(residual_mask), _ptr(live_idx), _ptr(count), prec,
-                                               ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _lib.check(rc, "svdd_conv_tower_windows_lp")
+    _lib.call("svdd_conv_tower_windows_lp", cand, tiles, bias, inv, win, parent_out, out, n, L, M, bias.shape[0] - 1, int(residual_mask),
+              live_idx, count, prec)
     return out
 
 
@@ -604,10 +565,7 @@ def gru_bidir_lp(x_nlc, wpack, bpack, inv, prec, count=None, out=None):
     n, L = x_nlc.shape[0], x_nlc.shape[1]
     if out is None:
         out = torch.empty((2, n, L, 64), dtype=torch.float32, device=x_nlc.device)
-    rc = _lib.lib().svdd_gru_bidir_lp(None if split else x_nlc.data_ptr(), x_nlc.data_ptr() if split else None,
-                                      wpack.data_ptr(), bpack.data_ptr(), inv.data_ptr(), out.data_ptr(),
-                                      n, L, _ptr(count), prec, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _lib.check(rc, "svdd_gru_bidir_lp")
+    _lib.call("svdd_gru_bidir_lp", None if split else x_nlc, x_nlc if split else None, wpack, bpack, inv, out, n, L, count, prec)
     return out
 
 
@@ -618,10 +576,7 @@ def value_tail_lp(h, w1pack, b1f, w_eff, b_eff, inv, prec, count=None, out=None)
     if out is None:
         out = torch.empty((n, T), dtype=torch.float32, device=h.device)
     assert out.is_contiguous() and out.shape == (n, T) and out.dtype == torch.float32
-    rc = _lib.lib().svdd_value_tail_lp(h[0].data_ptr(), h[1].data_ptr(), w1pack.data_ptr(), b1f.data_ptr(),
-                                       w_eff.data_ptr(), b_eff.data_ptr(), float(inv), out.data_ptr(), n, L, T,
-                                       _ptr(count), prec, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _lib.check(rc, "svdd_value_tail_lp")
+    _lib.call("svdd_value_tail_lp", h[0], h[1], w1pack, b1f, w_eff, b_eff, float(inv), out, n, L, T, count, prec)
     return out
 
 
@@ -634,9 +589,7 @@ def candidate_windows(cand, x, margin=TOWER_WINDOW_MARGIN, flags=None):
     assert cand.is_cuda and cand.dtype == torch.uint8 and cand.is_contiguous() and x.dtype == torch.uint8 and x.is_contiguous()
     B, M, L = cand.shape
     win = torch.empty((B * M, 2), dtype=torch.int32, device=cand.device)
-    rc = _lib.lib().svdd_candidate_windows(cand.data_ptr(), x.data_ptr(), B, L, M, margin, win.data_ptr(), _ptr(flags),
-                                           ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _lib.check(rc, "svdd_candidate_windows")
+    _lib.call("svdd_candidate_windows", cand, x, B, L, M, margin, win, flags)
     return win
 
 
@@ -653,11 +606,8 @@ def conv_tower_windows(onehot, win, parent_out, M, tiles, bias, residual_mask, l
     else:
         assert live_idx is not None and count is not None and out.is_contiguous() and out.shape[1:] == (L, 64)
         n = out.shape[0]
-    rc = _lib.lib().svdd_conv_tower_windows_f32(onehot.data_ptr(), tiles.data_ptr(), bias.data_ptr(), win.data_ptr(),
-                                                parent_out.data_ptr(), out.data_ptr(), n, L, M, bias.shape[0] - 1,
-                                                int(residual_mask), _ptr(live_idx), _ptr(count),
-                                                ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _lib.check(rc, "svdd_conv_tower_windows_f32")
+    _lib.call("svdd_conv_tower_windows_f32", onehot, tiles, bias, win, parent_out, out, n, L, M, bias.shape[0] - 1, int(residual_mask),
+              live_idx, count)
     return out
 
 
@@ -672,10 +622,7 @@ def epilogue_ln(y, bias=None, f_prev=None, tb=None, gamma=None, beta=None, act=A
     f = torch.empty_like(y) if want_sum else None
     hn = torch.empty_like(y) if want_norm else None
     assert y.dtype == torch.float32 and (f if f is not None else hn).stride() == y.stride()
-    rc = _lib.lib().svdd_epilogue_ln_f32(y.data_ptr(), _ptr(bias), _ptr(f_prev), _ptr(tb), _ptr(gamma), _ptr(beta),
-                                         _ptr(f), _ptr(hn), rows, C, int(act),
-                                         ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    _lib.check(rc, "svdd_epilogue_ln_f32")
+    _lib.call("svdd_epilogue_ln_f32", y, bias, f_prev, tb, gamma, beta, f, hn, rows, C, int(act))
     return f, hn
 
 
@@ -793,6 +740,16 @@ class FusedValueNet(nn.Module):
         """True when forward_grad applies: the reference-shaped net in fp32 at a length the static 64 -> 64 conv kernel has."""
         return self.tower_ok and self.tail_ok and L in (200, 50) and all(p.numel() for p in self.wpacks)   # (fp32 whatever self.precision)
 
+    def _grad_pack(self):
+        """(stem weight [4 t + c][co], the tower's transposed conv packs, the GRU's backward pack) of forward_grad and
+        mean_score_input_grad (packed on first use)."""
+        if self._grad_packs is None:
+            dev = self.tw_bias.device
+            w_stem = self._stem_w_raw.to(dev).float().permute(2, 1, 0).reshape(-1, self._stem_w_raw.shape[0]).contiguous()   # [4 t + c][co]
+            packs_t = [pack_conv(w.to(dev).float().flip(2).transpose(0, 1).contiguous()) for w in self._folded_ws]
+            self._grad_packs = (w_stem, packs_t, pack_gru_bwd(self._gru_mod[0]).to(dev))
+        return self._grad_packs
+
     def forward_grad(self, x):
         """Scores [n, n_tasks, 1] of a RELAXED input x [n, L, 4] (fp32, e.g. softmax probabilities) WITH autograd to x — the reward
         call of the DPS baseline (reference diffusion_gosai.py:1326-1329: reward_model(softmax(E[x0 | x_t]))) without MIOpen: the
@@ -801,12 +758,7 @@ class FusedValueNet(nn.Module):
         and the tail left to torch autograd on channels-last rows. MIOpen served these small convolutions' backward passes as
         im2col + one GEMM per sample (2.7 ms of a 8.3 ms DPS step at B = 256). Weights frozen: input gradient only."""
         n, L, _ = x.shape
-        if self._grad_packs is None:
-            dev = self.tw_bias.device
-            w_stem = self._stem_w_raw.to(dev).float().permute(2, 1, 0).reshape(-1, self._stem_w_raw.shape[0]).contiguous()   # [4 t + c][co]
-            packs_t = [pack_conv(w.to(dev).float().flip(2).transpose(0, 1).contiguous()) for w in self._folded_ws]
-            self._grad_packs = (w_stem, packs_t, pack_gru_bwd(self._gru_mod[0]).to(dev))
-        w_stem, packs_t, gru_bwd = self._grad_packs
+        w_stem, packs_t, gru_bwd = self._grad_pack()
         T = self._stem_w_raw.shape[2]
         xp = F.pad(x, (0, 0, T // 2, T // 2))
         cols = torch.cat([xp[:, k:k + L] for k in range(T)], dim=2)                          # [n, L, 4 T], tap-major
@@ -827,14 +779,10 @@ class FusedValueNet(nn.Module):
         (tests/test_fused_gpu.py compares the two). Only where grad_ok(L)."""
         x = x.contiguous().float()
         n, L, _ = x.shape
-        lib, st = _lib.lib(), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        if self._grad_packs is None:
-            self.forward_grad(torch.zeros(1, L, 4, device=x.device))                 # packs the transposed weights
-        w_stem, packs_t, gru_bwd = self._grad_packs
+        w_stem, packs_t, gru_bwd = self._grad_pack()
         dev = x.device
         f = torch.empty((n, L, 64), dtype=torch.float32, device=dev)
-        _lib.check(lib.svdd_reward_stem_f32(x.data_ptr(), w_stem.data_ptr(), self.stem_b.data_ptr(), f.data_ptr(), n, L,
-                                            self._stem_w_raw.shape[2], st), "svdd_reward_stem_f32")
+        _lib.call("svdd_reward_stem_f32", x, w_stem, self.stem_b, f, n, L, self._stem_w_raw.shape[2])
         fs = [f]
         for wp, b, res in zip(self.wpacks, self.bs, self.residual):
             fs.append(conv1d_cl(fs[-1], wp, 64, 5, 1, bias=b, f_prev=fs[-1] if res else None, act=ACT_ADD_THEN_RELU))
@@ -846,34 +794,25 @@ class FusedValueNet(nn.Module):
         dxg = torch.empty((2, n, L, 64), dtype=torch.float32, device=dev)             # work buffers of the tower's backward pass
         if self.gru_off_chain:
             # the non-recurrent halves (W_i x forwards, W_i^T da backwards) as whole-chip launches beside the serial chains
-            _lib.check(lib.svdd_gru_bidir_train2_f32(fs[-1].data_ptr(), self.wpack.data_ptr(), self.bpack.data_ptr(), gates.data_ptr(),
-                                                     out.data_ptr(), save.data_ptr(), n, L, st), "svdd_gru_bidir_train2_f32")
+            _lib.call("svdd_gru_bidir_train2_f32", fs[-1], self.wpack, self.bpack, gates, out, save, n, L)
         else:
-            _lib.check(lib.svdd_gru_bidir_train_f32(fs[-1].data_ptr(), self.wpack.data_ptr(), self.bpack.data_ptr(), out.data_ptr(),
-                                                    save.data_ptr(), n, L, st), "svdd_gru_bidir_train_f32")
-        _lib.check(lib.svdd_reward_tail_grad_f32(out[0].data_ptr(), out[1].data_ptr(), self.w1.data_ptr(), self.b1.data_ptr(),
-                                                 self.ln_w.data_ptr(), self.ln_b.data_ptr(), w_eff0.data_ptr(), float(self._ln_eps), n, L,
-                                                 gout[0].data_ptr(), gout[1].data_ptr(), st), "svdd_reward_tail_grad_f32")
+            _lib.call("svdd_gru_bidir_train_f32", fs[-1], self.wpack, self.bpack, out, save, n, L)
+        _lib.call("svdd_reward_tail_grad_f32", out[0], out[1], self.w1, self.b1, self.ln_w, self.ln_b, w_eff0, float(self._ln_eps), n, L,
+                  gout[0], gout[1])
         g = dxg[1]                                                                   # the gradient at the last layer's pre-activation
         if self.gru_off_chain:
-            _lib.check(lib.svdd_gru_bidir_bwd2_f32(gout.data_ptr(), out.data_ptr(), save.data_ptr(), gru_bwd.data_ptr(), gates.data_ptr(),
-                                                   fs[-1].data_ptr(), g.data_ptr(), n, L, st), "svdd_gru_bidir_bwd2_f32")
+            _lib.call("svdd_gru_bidir_bwd2_f32", gout, out, save, gru_bwd, gates, fs[-1], g, n, L)
         else:
             dxd = torch.empty_like(out)
-            _lib.check(lib.svdd_gru_bidir_bwd_f32(gout.data_ptr(), out.data_ptr(), save.data_ptr(), gru_bwd.data_ptr(), dxd.data_ptr(), n, L, st),
-                       "svdd_gru_bidir_bwd_f32")
-            _lib.check(lib.svdd_sum_gate_f32(dxd[0].data_ptr(), dxd[1].data_ptr(), fs[-1].data_ptr(), g.data_ptr(), n * L * 64, st),
-                       "svdd_sum_gate_f32")
+            _lib.call("svdd_gru_bidir_bwd_f32", gout, out, save, gru_bwd, dxd, n, L)
+            _lib.call("svdd_sum_gate_f32", dxd[0], dxd[1], fs[-1], g, n * L * 64)
         bufs = [gout[1], dxg[0]]
         for k in range(len(packs_t) - 1, -1, -1):                                    # block k + 1: fs[k + 1] = relu(conv_k(fs[k]) + b (+ fs[k]))
             y = bufs[k & 1]
-            _lib.check(lib.svdd_conv1d_cl_gated_f32(g.data_ptr(), packs_t[k].data_ptr(), y.data_ptr(), n, L, 64, 64, 5, 1,
-                                                    g.data_ptr() if self.residual[k] else None, fs[k].data_ptr(), st),
-                       "svdd_conv1d_cl_gated_f32")
+            _lib.call("svdd_conv1d_cl_gated_f32", g, packs_t[k], y, n, L, 64, 64, 5, 1, g if self.residual[k] else None, fs[k])
             g = y
         dx = torch.empty((n, L, 4), dtype=torch.float32, device=dev)
-        _lib.check(lib.svdd_reward_stem_bwd_f32(g.data_ptr(), w_stem.data_ptr(), dx.data_ptr(), n, L, self._stem_w_raw.shape[2], st),
-                   "svdd_reward_stem_bwd_f32")
+        _lib.call("svdd_reward_stem_bwd_f32", g, w_stem, dx, n, L, self._stem_w_raw.shape[2])
         if self.keep_grad_pass:
             self.last_grad_pass = {"fs": fs, "out": out, "g_tail": gout[0], "grad": dx}
         return dx
@@ -1120,25 +1059,25 @@ class FusedBackbone(nn.Module):
         hand it compacted batches whose size only the device knows)."""
         return self.one_launch and self.use_one_launch and L <= 208 and self.min_tiles_one_launch == 0
 
+    def _lp_pack(self):
+        """Operand images of svdd_backbone_cnn_lp for self.precision (packed on first use)."""
+        pk = self._lp.get(self.precision)
+        if pk is None:
+            pk = self._lp[self.precision] = pack_backbone_lp(self._cnn[0], self.precision)
+        return pk
+
     def forward_rows(self, tok, count=None, out=None, row_idx=None, scatter=False):
         """One-launch kernel on a compacted batch (see fused.backbone_cnn): tok [n, L] u8; count / row_idx int32 device
         tensors; out: logits buffer to write into."""
         if self.precision != "f32":
-            pk = self._lp.get(self.precision)
-            if pk is None:
-                pk = self._lp[self.precision] = pack_backbone_lp(self._cnn[0], self.precision)
-            return backbone_cnn_lp(tok, pk, count, out, row_idx, scatter)
-        return backbone_cnn(tok, dict(table0=self.ol_table0, tiles=self.ol_tiles, vec=self.ol_vec, w2=self.ol_w2,
-                                      dil=self.ol_dil), count, out, row_idx, scatter)
+            return backbone_cnn_lp(tok, self._lp_pack(), count, out, row_idx, scatter)
+        return backbone_cnn(tok, self.ol_pack(), count, out, row_idx, scatter)
 
     def forward(self, seq, sigma=None):
         B, L = seq.shape
         if self.precision != "f32" and self.one_launch and L <= 208 and seq.is_cuda:
-            pk = self._lp.get(self.precision)
-            if pk is None:
-                pk = self._lp[self.precision] = pack_backbone_lp(self._cnn[0], self.precision)
             tok = seq if seq.dtype == torch.uint8 else seq.to(torch.uint8)
-            return backbone_cnn_lp(tok.contiguous(), pk)
+            return backbone_cnn_lp(tok.contiguous(), self._lp_pack())
         # One workgroup per tile of whole sequences, ~2.2 ms per workgroup whatever the batch. Below ~192 tiles the
         # layer-wise path (MIOpen + our conv kernels, 41 launches) finishes sooner (0.9 ms at B = 32), but it is a
         # different fp32 summation order and MIOpen's algorithm choice is not reproducible run to run, so by default
@@ -1148,8 +1087,7 @@ class FusedBackbone(nn.Module):
         if (self.one_launch and self.use_one_launch and L <= 208 and seq.is_cuda and
                 (B + 208 // L - 1) // (208 // L) >= self.min_tiles_one_launch):
             tok = seq if seq.dtype == torch.uint8 else seq.to(torch.uint8)
-            return backbone_cnn(tok.contiguous(), dict(table0=self.ol_table0, tiles=self.ol_tiles, vec=self.ol_vec,
-                                                       w2=self.ol_w2, dil=self.ol_dil))
+            return backbone_cnn(tok.contiguous(), self.ol_pack())
         onehot = self.eye[seq.long()]                               # [B,L,5]
         f = onehot.view(B, 1, L, onehot.shape[2]).permute(0, 3, 1, 2)
         n = len(self.ws)

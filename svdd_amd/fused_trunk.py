@@ -18,7 +18,6 @@ of the SVDD-MC loop needs no host round trip.
 
 The module takes TOKENS ([n, L] uint8, 4 = MASK): the engine's one-hot rows are exact, and the stem's k = 15 convolution
 over a one-hot input is a K = 60 GEMM whose A operand is exactly representable in bf16."""
-import ctypes
 import threading
 import os
 
@@ -42,14 +41,6 @@ def _level_len(L, d):
     for _ in range(d):
         L = (L + 1) // 2
     return L
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def pack_gemm_weight(w, parts):
@@ -243,23 +234,17 @@ class FusedEnformerValueNet(nn.Module):
         self._gemm_launch(planes, w, bias, resid, out, M, N, Cin, T, act, count, rps, nxt, post, post_act, pad)
 
     def _gemm_launch(self, planes, w, bias, resid, out, M, N, Cin, T, act, count, rps, nxt, post, post_act, pad):
-        rc = _lib.lib().svdd_trunk_gemm(planes[0].data_ptr(), planes[1].data_ptr() if len(planes) > 1 else None, w.data_ptr(),
-                                        _ptr(bias), _ptr(resid), _ptr(out), M, N, Cin, T, Cin, N, act, _ptr(count), rps,
-                                        nxt[0].data_ptr() if nxt else None, nxt[1].data_ptr() if nxt and len(nxt) > 1 else None,
-                                        _ptr(post[0]) if post else None, _ptr(post[1]) if post else None, post_act, pad, _stream())
-        _lib.check(rc, "svdd_trunk_gemm")
+        _lib.call("svdd_trunk_gemm", planes[0], planes[1] if len(planes) > 1 else None, w, bias, resid, out, M, N, Cin, T, Cin, N, act,
+                  count, rps, nxt[0] if nxt else None, nxt[1] if nxt and len(nxt) > 1 else None, post[0] if post else None,
+                  post[1] if post else None, post_act, pad)
 
     def _act(self, x, bn, act, rows, C, rps, pad, planes, count):
-        rc = _lib.lib().svdd_trunk_act_split(x.data_ptr(), _ptr(bn[0]) if bn else None, _ptr(bn[1]) if bn else None, act, rows, C, rps,
-                                             pad, planes[0].data_ptr(), planes[1].data_ptr() if len(planes) > 1 else None,
-                                             _ptr(count), _stream())
-        _lib.check(rc, "svdd_trunk_act_split")
+        _lib.call("svdd_trunk_act_split", x, bn[0] if bn else None, bn[1] if bn else None, act, rows, C, rps, pad, planes[0],
+                  planes[1] if len(planes) > 1 else None, count)
 
     def _ln(self, x, ln, rows, C, planes, count, rps):
-        rc = _lib.lib().svdd_trunk_layernorm_split(x.data_ptr(), ln[0].data_ptr(), ln[1].data_ptr(), float(ln[2]), rows, C,
-                                                   planes[0].data_ptr(), planes[1].data_ptr() if len(planes) > 1 else None,
-                                                   _ptr(count), rps, _stream())
-        _lib.check(rc, "svdd_trunk_layernorm_split")
+        _lib.call("svdd_trunk_layernorm_split", x, ln[0], ln[1], float(ln[2]), rows, C, planes[0], planes[1] if len(planes) > 1 else None,
+                  count, rps)
 
     def _workspace(self, n, L, dev):
         """ONE workspace per (L, device), sized for the largest batch seen so far and reused for smaller ones (an SVDD-MC decode
@@ -320,12 +305,10 @@ class FusedEnformerValueNet(nn.Module):
     def _unfold(self, ws, tok, rows, count, win=None):
         n, L = tok.shape
         ph = ws["p"][0].view(rows, 64)[:self.parts]
-        lib = _lib.lib()
         if win is None:
-            _lib.check(lib.svdd_trunk_stem_unfold(tok.data_ptr(), n, L, ph[0].data_ptr(), _ptr(count), _stream()), "svdd_trunk_stem_unfold")
+            _lib.call("svdd_trunk_stem_unfold", tok, n, L, ph[0], count)
         else:
-            _lib.check(lib.svdd_trunk_stem_unfold_win(tok.data_ptr(), n, L, self.share_slots, win[0].data_ptr(), win[1].data_ptr(), win[2].data_ptr(),
-                                                      ph[0].data_ptr(), _ptr(count), _stream()), "svdd_trunk_stem_unfold_win")
+            _lib.call("svdd_trunk_stem_unfold_win", tok, n, L, self.share_slots, win[0], win[1], win[2], ph[0], count)
         if self.parts == 2:
             ph[1][: rows * 64].zero_()                           # the one-hot operand is exact: its lo plane is zero
         return ph
@@ -333,7 +316,7 @@ class FusedEnformerValueNet(nn.Module):
     def _parent_levels(self, ws, parent_tok, pp, depth):
         """Whole sequences: the pooled operand planes of the first `depth` levels of `parent_tok` -> pp[1 .. depth]."""
         B, L = parent_tok.shape
-        P, f, lib = self.parts, ws["f"], _lib.lib()
+        P, f = self.parts, ws["f"]
         Lc = L
         for d in range(depth):
             rps = Lc + 2
@@ -342,9 +325,8 @@ class FusedEnformerValueNet(nn.Module):
             self._convs(ws, d, src, rows, rps, 2, None)
             nx = self.levels[d + 1]
             tg = pp[d + 1].view(B * ((Lc + 1) // 2 + 2), nx["a_cin"])[:P]
-            rc = lib.svdd_trunk_attn_pool(f[2].data_ptr(), f[3].data_ptr(), B, Lc, self.levels[d]["C"], None, None, tg[0].data_ptr(),
-                                          tg[1].data_ptr() if P == 2 else None, _ptr(nx["a_bn"][0]), _ptr(nx["a_bn"][1]), ACT_GELU, _stream())
-            _lib.check(rc, "svdd_trunk_attn_pool")
+            _lib.call("svdd_trunk_attn_pool", f[2], f[3], B, Lc, self.levels[d]["C"], None, None, tg[0], tg[1] if P == 2 else None,
+                      nx["a_bn"][0], nx["a_bn"][1], ACT_GELU)
             Lc = (Lc + 1) // 2
 
     def _window_levels(self, ws, tok, count, parent_tok, pidx, div, pp, depth, win, whole):
@@ -353,11 +335,9 @@ class FusedEnformerValueNet(nn.Module):
         (pooled window rows + the parent's rows elsewhere); the last level's must be given."""
         n, L = tok.shape
         B = parent_tok.shape[0]
-        K, P, f, lib = self.share_slots, self.parts, ws["f"], _lib.lib()
+        K, P, f = self.share_slots, self.parts, ws["f"]
         w0, wlen, seg = win
-        rc = lib.svdd_trunk_windows(tok.data_ptr(), parent_tok.data_ptr(), pidx.data_ptr(), div, n, L, 7, depth, K, _ptr(count),
-                                    w0.data_ptr(), wlen.data_ptr(), seg.data_ptr(), _stream())
-        _lib.check(rc, "svdd_trunk_windows")
+        _lib.call("svdd_trunk_windows", tok, parent_tok, pidx, div, n, L, 7, depth, K, count, w0, wlen, seg)
         cs = torch.cumsum(seg, 1, dtype=torch.int32)
         off = cs - seg
         Lc = L
@@ -374,14 +354,11 @@ class FusedEnformerValueNet(nn.Module):
                 outs.append((whole[d], (None, None, None)))
             if not last:                                          # the compact segments of the next level (plane set 0: its GEMMs are done with it)
                 outs.append((ws["p"][0].view(n * (Lo + 4 * K), nx["a_cin"])[:P],
-                             (w0[d + 1].data_ptr(), wlen[d + 1].data_ptr(), off[d + 1].data_ptr())))
+                             (w0[d + 1], wlen[d + 1], off[d + 1])))
             for tg, nxt_win in outs:
-                rc = lib.svdd_trunk_attn_pool_win(f[2].data_ptr(), f[3].data_ptr(), n, Lc, lv["C"], 2 if d else 0, K, w0[d].data_ptr(),
-                                                  wlen[d].data_ptr(), off[d].data_ptr(), pidx.data_ptr(), div, ppl[0].data_ptr(),
-                                                  ppl[1].data_ptr() if P == 2 else None, _ptr(count), tg[0].data_ptr(),
-                                                  tg[1].data_ptr() if P == 2 else None, _ptr(nx["a_bn"][0]), _ptr(nx["a_bn"][1]), ACT_GELU,
-                                                  *nxt_win, _stream())
-                _lib.check(rc, "svdd_trunk_attn_pool_win")
+                _lib.call("svdd_trunk_attn_pool_win", f[2], f[3], n, Lc, lv["C"], 2 if d else 0, K, w0[d], wlen[d], off[d], pidx, div, ppl[0],
+                          ppl[1] if P == 2 else None, count, tg[0], tg[1] if P == 2 else None, nx["a_bn"][0], nx["a_bn"][1], ACT_GELU,
+                          *nxt_win)
             Lc = Lo
         return cs[:, n * K - 1]
 
@@ -468,13 +445,13 @@ class FusedEnformerValueNet(nn.Module):
         """_forward_tokens with the library's plane format set for the span of the call (a host-side switch, svdd_set_option:
         every launch of the call is enqueued inside it), restored on the way out."""
         with _OPTION_LOCK:                       # (two value nets of different precision on two host threads must not interleave)
-            prev_planes = _lib.set_option(6, 1 if self.f32 else 0)
-            prev_conc = _lib.current_option(4, 51)
+            prev_planes = _lib.set_option(_lib.OPT_TRUNK_PLANES_F32, 1 if self.f32 else 0)
+            prev_conc = _lib.current_option(_lib.OPT_TRUNK_GEMM_VERSION, 51)
             try:
                 return self._forward_tokens(tok, count, shared)
             finally:                             # what the caller had set, not constants
-                _lib.set_option(6, prev_planes)
-                _lib.set_option(4, prev_conc)
+                _lib.set_option(_lib.OPT_TRUNK_PLANES_F32, prev_planes)
+                _lib.set_option(_lib.OPT_TRUNK_GEMM_VERSION, prev_conc)
 
     def _forward_tokens(self, tok, count=None, shared=None):
         """tok [n, L] u8 -> (zs [n T, pw_out], n, T, seqs); count: int32 device scalar = live rows (rows beyond it are undefined).
@@ -504,7 +481,7 @@ class FusedEnformerValueNet(nn.Module):
         if S > 1 and not (n * T >= 2048 and need_f <= reg_f and need_p + 2 * 4096 <= reg_p):
             S = 1
         self.last_streams = S
-        _lib.set_option(4, 50 + (S if self.gemm_conc_hint else 1))   # the GEMMs' tile-height choice prices a launch against CUs / S
+        _lib.set_option(_lib.OPT_TRUNK_GEMM_VERSION, 50 + (S if self.gemm_conc_hint else 1))   # the GEMMs' tile-height choice prices a launch against CUs / S
         if S == 1:
             self.last_window_rows = self._candidates(ws, st, tok, count, shared, depth, zs, 0)
         else:
@@ -553,7 +530,6 @@ class FusedEnformerValueNet(nn.Module):
         """Conv tower (the first `depth` levels on windows), transformer tower and pointwise block of the rows `tok` -> zs."""
         n, L = tok.shape
         f, P = ws["f"], self.parts
-        lib = _lib.lib()
         side = 0                                                  # the plane set the NEXT GEMM reads
 
         def planes(rows, C, which):
@@ -597,14 +573,13 @@ class FusedEnformerValueNet(nn.Module):
             last = i + 1 == len(self.levels)
             xn = f[(cur + 3) % 4]
             if last:                                              # the transformer tower takes the fp32 rows
-                args = (xn.data_ptr(), _ptr(count), None, None, None, None, ACT_NONE)
+                args = (xn, count, None, None, None, None, ACT_NONE)
             else:                                                 # the next level's k = 5 block takes gelu(bn(x)) as planes only
                 nx = self.levels[i + 1]
                 pn = planes(n * (Lo + 2), nx["a_cin"], 1 - side)
-                args = (None, _ptr(count), pn[0].data_ptr(), pn[1].data_ptr() if P == 2 else None, _ptr(nx["a_bn"][0]),
-                        _ptr(nx["a_bn"][1]), ACT_GELU)
+                args = (None, count, pn[0], pn[1] if P == 2 else None, nx["a_bn"][0], nx["a_bn"][1], ACT_GELU)
                 side = 1 - side
-            _lib.check(lib.svdd_trunk_attn_pool(y.data_ptr(), lg.data_ptr(), n, Lc, C, *args, _stream()), "svdd_trunk_attn_pool")
+            _lib.call("svdd_trunk_attn_pool", y, lg, n, Lc, C, *args)
             cur = (cur + 3) % 4
             Lc = Lo
             rps = Lc + 2
@@ -617,7 +592,7 @@ class FusedEnformerValueNet(nn.Module):
 
     def _tower(self, ws, x, zs, n, T, count):
         """Transformer tower + pointwise block on rows x [n T, C] (fp32) -> zs [n T, pw_out]."""
-        f, P, lib, dev, C = ws["f"], self.parts, _lib.lib(), x.device, self.C
+        f, P, dev, C = ws["f"], self.parts, x.device, self.C
         rows = n * T
         cur = 0
 
@@ -633,10 +608,8 @@ class FusedEnformerValueNet(nn.Module):
             self._gemm(pl, d["qkv_w"], None, None, qkv, rows, nqkv, C, 1, ACT_NONE, count, T)
             pl = planes(rows, h * dv, 1)
             if T <= 4:                                            # one launch: logits, softmax, weighted sum, hi / lo split
-                rc = lib.svdd_trunk_attn_small(qkv.data_ptr(), self._rel_k(d, T, dev).data_ptr(), d["content_bias"].data_ptr(),
-                                               d["pos_bias"].data_ptr(), n, T, h, dk, dv, pl[0].data_ptr(),
-                                               pl[1].data_ptr() if P == 2 else None, _ptr(count), _stream())
-                _lib.check(rc, "svdd_trunk_attn_small")
+                _lib.call("svdd_trunk_attn_small", qkv, self._rel_k(d, T, dev), d["content_bias"], d["pos_bias"], n, T, h, dk, dv, pl[0],
+                          pl[1] if P == 2 else None, count)
             else:
                 q = qkv[:, :nq].view(n, T, h, dk).transpose(1, 2) * dk ** -0.5
                 k = qkv[:, nq:2 * nq].view(n, T, h, dk).transpose(1, 2)

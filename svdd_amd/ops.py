@@ -41,10 +41,6 @@ class Rng:
         return SvddRng(RNG_PHILOX, self.step, None, self.seed & 0xFFFFFFFFFFFFFFFF, self.row_offset, 0, 0)
 
 
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _need(t, dtype, name):
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise SvddError(f"{name} must be a GPU tensor (the SVDD hot path has no CPU fallback)")
@@ -87,10 +83,7 @@ def propose(logits, x, dm, mcs, M, rng, want_q=False, cand=None, onehot=None):
         rows = rng.uniforms_rows if rng.uniforms_rows else B       # (a shard of a batch of uniforms_rows rows: the whole batch's blocks)
         assert u.is_contiguous() and u.numel() == M * rows * L * 5 and rng.row_offset * bool(rng.uniforms_rows) + B <= rows, (u.shape, M, B, L)
     rs = rng.c_struct(layout)
-    rc = _lib.lib().svdd_propose(logits.data_ptr(), x.data_ptr(), float(dm), float(mcs), B, L, M, layout,
-                                 ctypes.byref(rs), cand.data_ptr(), onehot.data_ptr(),
-                                 q.data_ptr() if q is not None else None, _stream())
-    _lib.check(rc, "svdd_propose")
+    _lib.call("svdd_propose", logits, x, float(dm), float(mcs), B, L, M, layout, ctypes.byref(rs), cand, onehot, q)
     return cand, onehot, q
 
 
@@ -103,9 +96,7 @@ def sample_categorical(q, x, M, rng):
     cand = torch.empty((B, M, L), dtype=torch.uint8, device=x.device)
     onehot = torch.empty((B * M, L, 4), dtype=torch.float32, device=x.device)
     rs = rng.c_struct(layout)
-    rc = _lib.lib().svdd_sample_categorical(q.data_ptr(), x.data_ptr(), B, L, M, layout, ctypes.byref(rs),
-                                            cand.data_ptr(), onehot.data_ptr(), _stream())
-    _lib.check(rc, "svdd_sample_categorical")
+    _lib.call("svdd_sample_categorical", q, x, B, L, M, layout, ctypes.byref(rs), cand, onehot)
     return cand, onehot
 
 
@@ -129,10 +120,8 @@ def classifier_propose(logits, x, grad4, dm, mcs, scale, rng, want_onehot=True, 
         rows = rng.uniforms_rows if rng.uniforms_rows else B
         assert u.is_contiguous() and u.numel() == rows * L * 5 and rng.row_offset * bool(rng.uniforms_rows) + B <= rows, (u.shape, B, L)
     rs = rng.c_struct(layout)
-    rc = _lib.lib().svdd_classifier_propose(logits.data_ptr(), layout, x.data_ptr(), g.data_ptr(), float(dm), float(mcs), float(scale),
-                                            B, L, ctypes.byref(rs), x_next.data_ptr(), onehot.data_ptr() if want_onehot else None,
-                                            q.data_ptr() if q is not None else None, _stream())
-    _lib.check(rc, "svdd_classifier_propose")
+    _lib.call("svdd_classifier_propose", logits, layout, x, g, float(dm), float(mcs), float(scale), B, L, ctypes.byref(rs), x_next,
+              onehot if want_onehot else None, q)
     return x_next, (onehot if want_onehot else None), q
 
 
@@ -157,9 +146,7 @@ def elbo_mask(x0, K, rng, eps=1e-3, move_chance=None, want_scalars=True, want_co
     t, mc, w = ((torch.empty(K * n, dtype=torch.float32, device=dev) for _ in range(3)) if want_scalars else (None, None, None))
     cnt = torch.empty(K * n, dtype=torch.int32, device=dev) if want_count else None
     rs = rng.c_struct()
-    rc = _lib.lib().svdd_elbo_mask(x0.data_ptr(), n, L, K, float(eps), ctypes.byref(rs), mc_in.data_ptr() if replay else None,
-                                   xt.data_ptr(), *(v.data_ptr() if v is not None else None for v in (t, mc, w, cnt)), _stream())
-    _lib.check(rc, "svdd_elbo_mask")
+    _lib.call("svdd_elbo_mask", x0, n, L, K, float(eps), ctypes.byref(rs), mc_in if replay else None, xt, t, mc, w, cnt)
     return xt, t, mc, w, cnt
 
 
@@ -181,10 +168,7 @@ def elbo_nll(logits, xt, x0, w, K=1, want_tokens=True, want_mean=False, err=None
     check_here = err is None
     if check_here:
         err = torch.zeros(1, dtype=torch.int32, device=dev)
-    rc = _lib.lib().svdd_elbo_nll(logits.data_ptr(), layout, xt.data_ptr(), x0.data_ptr(), w.data_ptr(), n, L, K,
-                                  nll.data_ptr() if nll is not None else None, row_sum.data_ptr(),
-                                  mean.data_ptr() if mean is not None else None, err.data_ptr(), _stream())
-    _lib.check(rc, "svdd_elbo_nll")
+    _lib.call("svdd_elbo_nll", logits, layout, xt, x0, w, n, L, K, nll, row_sum, mean, err)
     if check_here:
         check_elbo_err(err)
     return nll, row_sum, mean
@@ -207,10 +191,7 @@ def select(scores, cand, mode=SELECT_ARGMAX, rng=None, want_soft=True, x_next=No
     soft = torch.empty((B, M), dtype=torch.float32, device=cand.device) if want_soft else None
     idx = torch.empty((B,), dtype=torch.int32, device=cand.device)
     rs = rng.c_struct() if rng is not None else None
-    rc = _lib.lib().svdd_select(scores.data_ptr(), cand.data_ptr(), B, L, M, mode,
-                                ctypes.byref(rs) if rs is not None else None, x_next.data_ptr(),
-                                soft.data_ptr() if soft is not None else None, idx.data_ptr(), _stream())
-    _lib.check(rc, "svdd_select")
+    _lib.call("svdd_select", scores, cand, B, L, M, mode, ctypes.byref(rs) if rs is not None else None, x_next, soft, idx)
     return x_next, soft, idx
 
 
@@ -228,37 +209,29 @@ def select_compact(scores_c, slot, parent_score, cand, mode=SELECT_ARGMAX, rng=N
     sel_score = torch.empty((B,), dtype=torch.float32, device=dev) if sel_score is None else sel_score
     changed = torch.empty((B,), dtype=torch.int32, device=dev) if changed is None else changed
     rs = rng.c_struct() if rng is not None else None
-    rc = _lib.lib().svdd_select_compact(scores_c.data_ptr(), slot.data_ptr(), parent_score.data_ptr(), cand.data_ptr(),
-                                        B, L, M, mode, ctypes.byref(rs) if rs is not None else None, x_next.data_ptr(),
-                                        None, idx.data_ptr(), sel_score.data_ptr(), changed.data_ptr(), _stream())
-    _lib.check(rc, "svdd_select_compact")
+    _lib.call("svdd_select_compact", scores_c, slot, parent_score, cand, B, L, M, mode, ctypes.byref(rs) if rs is not None else None,
+              x_next, None, idx, sel_score, changed)
     return x_next, idx, sel_score, changed
 
 
 def compact_flags(flags, live_idx, slot, count):
     """Stable device-side compaction (svdd_compact_flags): live_idx[k] = i, slot[i] = k for the k-th non-zero flag,
     slot[i] = -1 otherwise, count[0] = number of non-zero flags. All int32 device tensors; nothing returns to the host."""
-    rc = _lib.lib().svdd_compact_flags(flags.data_ptr(), flags.numel(), live_idx.data_ptr(), slot.data_ptr(), count.data_ptr(),
-                                       _stream())
-    _lib.check(rc, "svdd_compact_flags")
+    _lib.call("svdd_compact_flags", flags, flags.numel(), live_idx, slot, count)
 
 
 def compact_by_key(key, live_idx, slot, count, split=0):
     """The same compaction ordered by key, largest first, stable inside a key (svdd_compact_by_key): key[i] > 0 = live.
     split > 0: count has 3 entries and also receives the lengths of the list's parts [0, split) and [split, ...)."""
     assert split == 0 or count.numel() >= 3
-    rc = _lib.lib().svdd_compact_by_key(key.data_ptr(), key.numel(), live_idx.data_ptr(), slot.data_ptr(), count.data_ptr(), int(split),
-                                        _stream())
-    _lib.check(rc, "svdd_compact_by_key")
+    _lib.call("svdd_compact_by_key", key, key.numel(), live_idx, slot, count, int(split))
 
 
 def gather_rows(src, idx, count, dst):
     """dst[i] = src[idx[i]] for i < count[0] (row tensors of equal row size, contiguous)."""
     n = src.shape[0]
     row_bytes = src[0].numel() * src.element_size()
-    rc = _lib.lib().svdd_gather_rows(src.data_ptr(), idx.data_ptr(), count.data_ptr() if count is not None else None, n,
-                                     row_bytes, dst.data_ptr(), _stream())
-    _lib.check(rc, "svdd_gather_rows")
+    _lib.call("svdd_gather_rows", src, idx, count, n, row_bytes, dst)
     return dst
 
 
@@ -266,8 +239,7 @@ def advance_rows(src, slot, sel, dst, M):
     """The selected candidate becomes the next parent: dst[b] = src[slot[b*M + sel[b]]] where that slot is >= 0."""
     B = dst.shape[0]
     row_bytes = dst[0].numel() * dst.element_size()
-    rc = _lib.lib().svdd_advance_rows(src.data_ptr(), slot.data_ptr(), sel.data_ptr(), B, M, row_bytes, dst.data_ptr(), _stream())
-    _lib.check(rc, "svdd_advance_rows")
+    _lib.call("svdd_advance_rows", src, slot, sel, B, M, row_bytes, dst)
     return dst
 
 
@@ -279,9 +251,7 @@ def x0hat(logits, xt, want_tokens=False, want_onehot=True):
     logits, layout = layout_of(logits)
     oh = torch.empty((R, 4, L), dtype=torch.float32, device=xt.device) if want_onehot else None
     xh = torch.empty((R, L), dtype=torch.uint8, device=xt.device) if want_tokens else None
-    rc = _lib.lib().svdd_x0hat(logits.data_ptr(), xt.data_ptr(), R, L, layout, oh.data_ptr() if oh is not None else None,
-                               xh.data_ptr() if xh is not None else None, _stream())
-    _lib.check(rc, "svdd_x0hat")
+    _lib.call("svdd_x0hat", logits, xt, R, L, layout, oh, xh)
     return oh, xh
 
 
@@ -292,8 +262,7 @@ def finalize(logits, x):
     B, L = x.shape
     logits, layout = layout_of(logits)
     out = torch.empty((B, L), dtype=torch.int64, device=x.device)
-    rc = _lib.lib().svdd_finalize(logits.data_ptr(), x.data_ptr(), B, L, layout, out.data_ptr(), None, _stream())
-    _lib.check(rc, "svdd_finalize")
+    _lib.call("svdd_finalize", logits, x, B, L, layout, out, None)
     return out
 
 
@@ -302,8 +271,7 @@ def transform_samples(tok, transposed=False):
     tok = _need(tok, torch.uint8, "tok").contiguous()
     R, L = tok.shape
     out = torch.empty((R, 4, L) if transposed else (R, L, 4), dtype=torch.float32, device=tok.device)
-    rc = _lib.lib().svdd_transform_samples(tok.data_ptr(), R, L, int(bool(transposed)), out.data_ptr(), _stream())
-    _lib.check(rc, "svdd_transform_samples")
+    _lib.call("svdd_transform_samples", tok, R, L, int(bool(transposed)), out)
     return out
 
 
@@ -314,8 +282,7 @@ def subs_logp(logits, x):
     B, L = x.shape
     logits, layout = layout_of(logits)
     out = _empty_like_layout(logits, layout)
-    rc = _lib.lib().svdd_subs_logp(logits.data_ptr(), x.data_ptr(), B, L, layout, out.data_ptr(), _stream())
-    _lib.check(rc, "svdd_subs_logp")
+    _lib.call("svdd_subs_logp", logits, x, B, L, layout, out)
     return out
 
 
@@ -327,7 +294,7 @@ def dps_probs(logits, x):
     assert logits.is_contiguous() and logits.shape == (*x.shape, 5)
     B, L = x.shape
     out = torch.empty((B, L, 4), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().svdd_dps_probs(logits.data_ptr(), x.data_ptr(), B, L, out.data_ptr(), _stream()), "svdd_dps_probs")
+    _lib.call("svdd_dps_probs", logits, x, B, L, out)
     return out
 
 
@@ -340,8 +307,7 @@ def dps_probs_bwd(logits, x, dprobs4):
     assert logits.is_contiguous() and logits.shape == (B, L, 5) and g.shape == (B, L, 4)
     dlogits = torch.empty((B, L, 5), dtype=torch.float32, device=x.device)
     direct = torch.empty_like(dlogits)
-    _lib.check(_lib.lib().svdd_dps_probs_bwd(logits.data_ptr(), x.data_ptr(), g.data_ptr(), B, L, dlogits.data_ptr(), direct.data_ptr(),
-                                             _stream()), "svdd_dps_probs_bwd")
+    _lib.call("svdd_dps_probs_bwd", logits, x, g, B, L, dlogits, direct)
     return dlogits, direct
 
 
@@ -353,8 +319,7 @@ def dps_guided_q(logits, x, grad_backbone, grad_direct, dm, mcs, scale):
     gb, gd = grad_backbone.contiguous().float(), grad_direct.contiguous().float()
     assert logits.is_contiguous() and logits.shape == (B, L, 5) and gb.shape == (B, L, 5) and gd.shape == (B, L, 5)
     q = torch.empty((B, L, 5), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().svdd_dps_guided_q(logits.data_ptr(), x.data_ptr(), gb.data_ptr(), gd.data_ptr(), float(dm), float(mcs),
-                                            float(scale), B, L, q.data_ptr(), _stream()), "svdd_dps_guided_q")
+    _lib.call("svdd_dps_guided_q", logits, x, gb, gd, float(dm), float(mcs), float(scale), B, L, q)
     return q
 
 
@@ -369,9 +334,7 @@ def tds_resample(reward_num, reward_den, alpha, sample, u):
     x_next = torch.empty_like(sample)
     idx = torch.empty((B,), dtype=torch.int32, device=sample.device)
     work = torch.empty((2 * B,), dtype=torch.float64, device=sample.device)
-    rc = _lib.lib().svdd_tds_resample(num.data_ptr(), den.data_ptr(), float(alpha), sample.data_ptr(), u.data_ptr(),
-                                      B, L, x_next.data_ptr(), idx.data_ptr(), work.data_ptr(), _stream())
-    _lib.check(rc, "svdd_tds_resample")
+    _lib.call("svdd_tds_resample", num, den, float(alpha), sample, u, B, L, x_next, idx, work)
     return x_next, idx
 
 
@@ -409,9 +372,6 @@ def mt_state_to_torch(words_pos, template_u8):
     a[16:24].view(np.uint64)[0] = pos
     a[24:24 + 624 * 8].view(np.uint64)[:] = np.asarray(words_pos[:624], dtype=np.uint64)
     return torch.from_numpy(a)
-
-
-
 
 
 # ---- side streams, process-wide -----------------------------------------------------------------------------------------------
@@ -496,11 +456,6 @@ class DeviceReplayStream:
         self.ahead = None         # (n, tensor, state snapshot before it was drawn, event) of the block generated ahead of need
         self.drawn = 0
 
-    def _launch(self, n, out):
-        rc = _lib.lib().svdd_mt19937_uniform_f32(self.state.data_ptr(), out.data_ptr(), n,
-                                                 ctypes.c_void_p(self.side.cuda_stream))
-        _lib.check(rc, "svdd_mt19937_uniform_f32")
-
     def _generate(self, n, snapshot):
         """Enqueue the next n floats on the side stream -> (tensor, snapshot | None, event)."""
         pair = self.bufs.setdefault(n, [torch.empty(n, dtype=torch.float32, device=self.dev) for _ in range(2)])
@@ -508,7 +463,7 @@ class DeviceReplayStream:
         self.flip ^= 1
         with torch.cuda.stream(self.side):
             snap = self.state.clone() if snapshot else None
-            self._launch(n, out)
+            _lib.call("svdd_mt19937_uniform_f32", self.state, out, n)       # (the current stream here is the side stream)
             ev = torch.cuda.Event()
             ev.record(self.side)
         return out, snap, ev

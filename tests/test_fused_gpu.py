@@ -243,19 +243,19 @@ def test_backbone_on_several_workgroups_per_sequence_same_bits(n, L):
     pk = fused.pack_backbone(cnn)
     lib = _lib.lib()
     try:
-        _lib.check(lib.svdd_set_option(7, 1), "split off")
+        _lib.set_option(_lib.OPT_BACKBONE_SPLIT, 1)
         one = fused.backbone_cnn(x, pk).clone()
         outs = {}
         for R in (2, 4):
             if R * (n % 256 if n > 256 else n) > 256:      # (n > 256: the tail round after the whole rounds of one-workgroup tiles)
                 continue
-            _lib.check(lib.svdd_set_option(7, R), "split forced")
+            _lib.set_option(_lib.OPT_BACKBONE_SPLIT, R)
             outs[R] = [fused.backbone_cnn(x, pk).clone() for _ in range(3)]
-        _lib.check(lib.svdd_set_option(7, 0), "split auto")
+        _lib.set_option(_lib.OPT_BACKBONE_SPLIT, 0)
         auto = fused.backbone_cnn(x, pk).clone()
         torch.cuda.synchronize()
     finally:
-        lib.svdd_set_option(7, 0)
+        _lib.set_option(_lib.OPT_BACKBONE_SPLIT, 0)
     err = ctypes.c_int(-1)
     _lib.check(lib.svdd_backbone_split_status(ctypes.byref(err)), "status")
     assert err.value == 0

@@ -32,6 +32,113 @@ def test_library_exports_every_declared_symbol():
         assert "gfx950" in out.stdout
 
 
+def _header_without_comments():
+    hdr = open(os.path.join(ROOT, "include", "svdd_hip.h")).read()
+    return re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S))
+
+
+def _header_class(param):
+    """A C parameter declaration -> "ptr" | "f32" | "f64" | "i32" | "i64"."""
+    param = " ".join(param.split())
+    if "*" in param or "hipStream_t" in param:
+        return "ptr"
+    ctype = param.rsplit(" ", 1)[0].replace("const ", "").strip()            # drop the parameter's name
+    return {"float": "f32", "double": "f64", "int": "i32", "int32_t": "i32", "uint32_t": "i32", "long long": "i64",
+            "int64_t": "i64"}[ctype]
+
+
+def _table_class(t):
+    """An entry of _lib.SIGNATURES -> the same classes."""
+    if t is ctypes.c_float:
+        return "f32"
+    if t is ctypes.c_double:
+        return "f64"
+    if issubclass(t, (ctypes.c_void_p, ctypes.c_char_p, ctypes._Pointer)):
+        return "ptr"
+    assert issubclass(t, ctypes._SimpleCData) and t._type_ in "ilqIL", t   # an integer type: classed by its size
+    return {4: "i32", 8: "i64"}[ctypes.sizeof(t)]
+
+
+def _signature_mismatches(signatures):
+    """Every difference between a name -> parameter types table and the `int svdd_*(...);` prototypes of include/svdd_hip.h."""
+    from svdd_amd import _lib
+    protos = re.findall(r"\bint\s+(svdd_\w+)\s*\(([^)]*)\)\s*;", _header_without_comments())
+    assert len(protos) >= 68 and len(set(n for n, _ in protos)) == len(protos)
+    bad = [f"{n}: not in the {'table' if n not in signatures else 'header'}" for n in set(signatures) ^ set(n for n, _ in protos)]
+    for name, params in protos:
+        if name not in signatures:
+            continue
+        params = [] if params.strip() in ("", "void") else [p.strip() for p in params.split(",")]
+        sig = signatures[name]
+        if len(sig) != len(params):
+            bad.append(f"{name}: {len(params)} parameters in the header, {len(sig)} in the table")
+            continue
+        for i, (p, t) in enumerate(zip(params, sig)):
+            if _header_class(p) != _table_class(t):
+                bad.append(f"{name}: parameter {i} `{p}` is {_header_class(p)} in the header, {_table_class(t)} in the table")
+            is_stream = i == len(params) - 1 and p.split()[-1].lstrip("*") == "stream"
+            if is_stream != (t is _lib.STREAM):
+                bad.append(f"{name}: parameter {i} `{p}`: the table {'marks' if not is_stream else 'does not mark'} it as the stream")
+    return bad
+
+
+def test_signature_table_equals_the_header():
+    """_lib.SIGNATURES (the argtypes of every export, and which functions _lib.call hands the current stream) against the prototypes
+    of include/svdd_hip.h: the same functions, per function the same number of parameters, per parameter the same class (pointer,
+    float, double, 32-bit, 64-bit integer), and the stream marked exactly where the last parameter is `stream`."""
+    from svdd_amd import _lib
+    assert _lib.EXPORTS == tuple(_lib.SIGNATURES)
+    assert _signature_mismatches(_lib.SIGNATURES) == []
+    assert sum(1 for s in _lib.SIGNATURES.values() if s and s[-1] is _lib.STREAM) == 55
+    # the check bites: a 32-bit entry widened, an entry dropped, a stream mark lost
+    sig = dict(_lib.SIGNATURES)
+    g = list(sig["svdd_gather_rows"])
+    assert g[3] is _lib.i32
+    g[3] = _lib.i64
+    sig["svdd_gather_rows"] = tuple(g)
+    assert any("svdd_gather_rows: parameter 3" in m for m in _signature_mismatches(sig))
+    sig = dict(_lib.SIGNATURES)
+    sig["svdd_select"] = sig["svdd_select"][:-2] + (_lib.STREAM,)
+    assert any("svdd_select: 11 parameters in the header, 10" in m for m in _signature_mismatches(sig))
+    sig = dict(_lib.SIGNATURES)
+    del sig["svdd_elbo_nll"]
+    assert any("svdd_elbo_nll: not in the table" in m for m in _signature_mismatches(sig))
+    sig = dict(_lib.SIGNATURES)
+    sig["svdd_x0hat"] = sig["svdd_x0hat"][:-1] + (_lib.vp,)
+    assert any("svdd_x0hat: parameter 7" in m and "stream" in m for m in _signature_mismatches(sig))
+    # lib() sets the argtypes from the table (the stream as a plain pointer)
+    L = _lib.lib()
+    for name, s in _lib.SIGNATURES.items():
+        assert list(getattr(L, name).argtypes) == [ctypes.c_void_p if t is _lib.STREAM else t for t in s], name
+        assert getattr(L, name).restype is ctypes.c_int
+
+
+def test_option_constants_equal_the_header_enum():
+    """_lib.OPT_* against the SVDD_OPT_* enum of include/svdd_hip.h: the same names with the same values, both ways."""
+    from svdd_amd import _lib
+    declared = {n: int(v) for n, v in re.findall(r"\bSVDD_(OPT_\w+)\s*=\s*(-?\d+)", _header_without_comments())}
+    bound = {n: v for n, v in vars(_lib).items() if n.startswith("OPT_")}
+    assert len(declared) == 9 and sorted(declared.values()) == list(range(9))
+    assert bound == declared
+
+
+def test_call_door_checks_before_it_launches():
+    """_lib.call refuses, without a GPU: a name the library does not have, a wrong number of arguments (the stream is never the
+    caller's to pass), and a tensor where the function takes a number (it must not be read as an address)."""
+    from svdd_amd import _lib
+    with pytest.raises(_lib.SvddError, match="svdd_compact_flag "):
+        _lib.call("svdd_compact_flag", None, 0, None, None, None)
+    with pytest.raises(TypeError, match="svdd_compact_flags takes 5 arguments"):
+        _lib.call("svdd_compact_flags", None, 0, None, None, None, None)
+    with pytest.raises(TypeError, match="svdd_compact_flags: argument 1 is a number"):
+        _lib.call("svdd_compact_flags", None, torch.tensor(16), None, None, None)
+    with pytest.raises(TypeError, match="svdd_value_tail_lp: argument 6 is a number"):
+        _lib.call("svdd_value_tail_lp", None, None, None, None, None, None, torch.tensor(0.5), None, 1, 1, 1, None, 1)
+    # a function without a stream goes through the same door: its return code is checked under its own name
+    with pytest.raises(_lib.SvddError, match="svdd_set_option: invalid argument"):
+        _lib.call("svdd_set_option", 99, 0)
+
+
 def test_argument_validation_without_gpu():
     """Entry points reject bad arguments before touching the device."""
     from svdd_amd import _lib
@@ -49,12 +156,12 @@ def test_argument_validation_without_gpu():
     # strides the 16-byte row pieces cannot honour: lda % 8 (bf16 planes) / % 4 (fp32 planes), ldo % 4
     assert L.svdd_trunk_gemm(one, None, one, None, None, one, 1, 128, 32, 1, 36, 128, 0, None, 0, None, None, None, None, 0, 0, None) == _lib.E_ARG
     assert L.svdd_trunk_gemm(one, None, one, None, None, one, 1, 128, 32, 1, 32, 130, 0, None, 0, None, None, None, None, 0, 0, None) == _lib.E_ARG
-    prev = _lib.set_option(6, 1)
+    prev = _lib.set_option(_lib.OPT_TRUNK_PLANES_F32, 1)
     try:
         assert L.svdd_trunk_gemm(one, None, one, None, None, one, 1, 128, 32, 1, 34, 128, 0, None, 0, None, None, None, None, 0, 0, None) == _lib.E_ARG
         assert L.svdd_trunk_gemm(one, None, one, None, None, one, 1, 128, 32, 1, 32, 129, 0, None, 0, None, None, None, None, 0, 0, None) == _lib.E_ARG
     finally:
-        _lib.set_option(6, prev)
+        _lib.set_option(_lib.OPT_TRUNK_PLANES_F32, prev)
     assert L.svdd_trunk_windows(one, one, one, 1, 4, 201, 7, 2, 4, None, one, one, one, None) == _lib.E_ARG      # an odd length below the last shared level
     assert L.svdd_trunk_windows(one, one, one, 1, 4, 200, 7, 1, 5, None, one, one, one, None) == _lib.E_ARG      # more window slots than the kernels hold
     assert L.svdd_trunk_windows(one, one, one, 1, 4, 300, 7, 1, 4, None, one, one, one, None) == _lib.E_ARG      # L > 256

@@ -100,13 +100,13 @@ def test_propose_many_candidates_vs_oracle(ops, M, msplit):
     uni = rng.random((M, B, L, 5), dtype=np.float32)
     c_ref, oh_ref, _ = orc.propose(logits, x, dm, mcs, M, uniforms=uni, layout=orc.BLV)
     p_ref, _, _ = orc.propose(logits, x, dm, mcs, M, seed=11, row_offset=5, step=9, want_q=False)
-    _lib.check(_lib.lib().svdd_set_option(1, msplit), "msplit")
+    _lib.set_option(_lib.OPT_MSPLIT, msplit)
     try:
         cand, onehot, _ = ops.propose(dev(logits), dev(x), dm, mcs, M, ops.Rng(uniforms=dev(uni)))
         pc, _, _ = ops.propose(dev(logits), dev(x), dm, mcs, M, ops.Rng(seed=11, row_offset=5, step=9))
         torch.cuda.synchronize()
     finally:
-        _lib.check(_lib.lib().svdd_set_option(1, 0), "msplit")
+        _lib.set_option(_lib.OPT_MSPLIT, 0)
     assert np.array_equal(cand.cpu().numpy(), c_ref)
     assert np.array_equal(onehot.cpu().numpy(), oh_ref)
     assert np.array_equal(pc.cpu().numpy(), p_ref)
@@ -187,23 +187,23 @@ def test_select_rows_per_wave_equals_one_row_per_wave_and_oracle(ops, M, L, mode
     sc_d, cand_d = dev(scores), dev(cand)
     fast = ops.select(sc_d, cand_d, mode=mode, rng=r, want_soft=False)
     fast_soft = ops.select(sc_d, cand_d, mode=mode, rng=r, want_soft=True)
-    _lib.check(_lib.lib().svdd_set_option(2, 1), "one row per wave")
+    _lib.set_option(_lib.OPT_SELECT_ONE_ROW, 1)
     try:
         slow = ops.select(sc_d, cand_d, mode=mode, rng=r, want_soft=True)
         torch.cuda.synchronize()
     finally:
-        _lib.check(_lib.lib().svdd_set_option(2, 0), "rows per wave")
+        _lib.set_option(_lib.OPT_SELECT_ONE_ROW, 0)
     assert torch.equal(fast[2], slow[2]) and torch.equal(fast_soft[2], slow[2])        # idx
     assert torch.equal(fast[0], slow[0]) and torch.equal(fast_soft[0], slow[0])        # gathered rows
     assert torch.equal(fast_soft[1], slow[1])                                          # soft values, bit for bit
     # round 4: four row groups per wave with the gathers batched (what batches of >= 2^21 (row, candidate) slots take)
-    _lib.check(_lib.lib().svdd_set_option(2, 2), "four row groups per wave")
+    _lib.set_option(_lib.OPT_SELECT_ONE_ROW, 2)
     try:
         wide = ops.select(sc_d, cand_d, mode=mode, rng=r, want_soft=False)
         wide_soft = ops.select(sc_d, cand_d, mode=mode, rng=r, want_soft=True)
         torch.cuda.synchronize()
     finally:
-        _lib.check(_lib.lib().svdd_set_option(2, 0), "rows per wave")
+        _lib.set_option(_lib.OPT_SELECT_ONE_ROW, 0)
     assert torch.equal(wide[2], slow[2]) and torch.equal(wide[0], slow[0])
     assert torch.equal(wide_soft[2], slow[2]) and torch.equal(wide_soft[0], slow[0]) and torch.equal(wide_soft[1], slow[1])
     sl = np.r_[0:300, 9990:15100:7, 20000:20050, 21000:21300, B - 70:B]

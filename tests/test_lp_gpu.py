@@ -74,10 +74,10 @@ def test_backbone_lp_transposed_variants_same_bits(mode, L):
     outs = {}
     try:
         for v in (22, 21, 23):
-            _lib.check(_lib.lib().svdd_set_option(3, v), "svdd_set_option")
+            _lib.set_option(_lib.OPT_BACKBONE_LP_VERSION, v)
             outs[v] = fused.backbone_cnn_lp(x, pk).clone()
     finally:
-        _lib.check(_lib.lib().svdd_set_option(3, 22), "svdd_set_option")
+        _lib.set_option(_lib.OPT_BACKBONE_LP_VERSION, 22)
     torch.cuda.synchronize()
     assert torch.isfinite(outs[22]).all()
     assert torch.equal(outs[21], outs[22]) and torch.equal(outs[23], outs[22])
@@ -100,10 +100,10 @@ def test_backbone_lp_other_dilation_orders(dils, monkeypatch):
         outs = {}
         try:
             for v in (22, 21, 23):
-                _lib.check(_lib.lib().svdd_set_option(3, v), "svdd_set_option")
+                _lib.set_option(_lib.OPT_BACKBONE_LP_VERSION, v)
                 outs[v] = torch.stack([fused.backbone_cnn_lp(x, pk) for _ in range(3)])     # three launches each: a race is timing
         finally:
-            _lib.check(_lib.lib().svdd_set_option(3, 22), "svdd_set_option")
+            _lib.set_option(_lib.OPT_BACKBONE_LP_VERSION, 22)
         torch.cuda.synchronize()
         assert (outs[22][0] - f32).abs().max().item() <= TOL_LOGITS[mode], (mode, dils)
         for v in (22, 21, 23):

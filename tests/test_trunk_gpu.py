@@ -186,8 +186,8 @@ def test_gemm_256_tiles_equal_128_tiles(M, N, Cin, T, rps, live, parts):
     outs, pls = {}, {}
     ps, pb = (1.0 + 0.1 * torch.randn(N, generator=g)).to(DEV), (0.1 * torch.randn(N, generator=g)).to(DEV)
     for ver in (1, 3, 42):                                 # 42: the LDS-DMA kernel with 192-row tiles everywhere (round 4)
-        _lib.check(lib.svdd_set_option(4, 3 if ver == 42 else ver), "svdd_set_option")
-        _lib.check(lib.svdd_set_option(4, 42 if ver == 42 else 41), "svdd_set_option")
+        _lib.set_option(_lib.OPT_TRUNK_GEMM_VERSION, 3 if ver == 42 else ver)
+        _lib.set_option(_lib.OPT_TRUNK_GEMM_VERSION, 42 if ver == 42 else 41)
         out = torch.full((M, N), 7.0, device=DEV)
         o_hi = torch.full((M, N), 3.0, device=DEV, dtype=torch.bfloat16)
         o_lo = torch.full((M, N), 3.0, device=DEV, dtype=torch.bfloat16)
@@ -210,8 +210,8 @@ def test_gemm_256_tiles_equal_128_tiles(M, N, Cin, T, rps, live, parts):
         assert torch.equal(pls[ver][0], r_hi.float().cpu())
         if parts == 2:
             assert torch.equal(pls[ver][1], r_lo.float().cpu())
-    _lib.check(lib.svdd_set_option(4, 2), "svdd_set_option")
-    _lib.check(lib.svdd_set_option(4, 40), "svdd_set_option")           # tile height by cost again
+    _lib.set_option(_lib.OPT_TRUNK_GEMM_VERSION, 2)
+    _lib.set_option(_lib.OPT_TRUNK_GEMM_VERSION, 40)           # tile height by cost again
     assert torch.equal(outs[1][:m_live], outs[3][:m_live])
     assert torch.equal(outs[42][:m_live], outs[3][:m_live]) and bool((outs[42][m_live:] == 7.0).all())
     assert bool((outs[3][m_live:] == 7.0).all())                       # rows beyond the live count are not written

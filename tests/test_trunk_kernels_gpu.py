@@ -26,20 +26,20 @@ SENT16, SENT32 = 0x7FA5, 0x7FA5A5A5          # NaN bit patterns no kernel writes
 @contextlib.contextmanager
 def _planes(mode):
     """Plane format for the span of a block; restored even if an assertion inside fails (svdd_set_option is process-wide)."""
-    prev = _lib.set_option(6, 1 if mode == "f32" else 0)
+    prev = _lib.set_option(_lib.OPT_TRUNK_PLANES_F32, 1 if mode == "f32" else 0)
     try:
         yield
     finally:
-        _lib.set_option(6, prev)
+        _lib.set_option(_lib.OPT_TRUNK_PLANES_F32, prev)
 
 
 @contextlib.contextmanager
 def _gemm_option(v):
-    prev = _lib.set_option(4, v)
+    prev = _lib.set_option(_lib.OPT_TRUNK_GEMM_VERSION, v)
     try:
         yield
     finally:
-        _lib.set_option(4, prev)
+        _lib.set_option(_lib.OPT_TRUNK_GEMM_VERSION, prev)
 
 
 class _Buf:

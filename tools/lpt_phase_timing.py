@@ -22,7 +22,7 @@ args = [a for a in args if a not in (str(L), str(spt))] if ("--L" in sys.argv or
 B = int(args[1]) if len(args) > 1 else 256 * spt
 dev = "cuda:0"
 if os.environ.get("SVDD_BB_LP_VERSION"):               # 21 / 22 / 23: waves per SIMD of the transposed kernel
-    _lib.set_option(3, int(os.environ["SVDD_BB_LP_VERSION"]))
+    _lib.set_option(_lib.OPT_BACKBONE_LP_VERSION, int(os.environ["SVDD_BB_LP_VERSION"]))
 torch.manual_seed(0)
 cnn = backbone.CNNModel((config.dna_config() if L > 104 else config.rna_config()).model, alphabet_size=5).to(dev).eval()
 if L <= 104:

@@ -40,7 +40,7 @@ def k2(B, M, L=200, compact=False, ld=0, scale=1e-3):
         wide = torch.zeros(B, M, ld, dtype=torch.uint8, device=DEV)
         wide[:, :, :L] = cand
         cand_dense, cand = cand, wide
-        _lib.set_option(5, ld)
+        _lib.set_option(_lib.OPT_CAND_ROW_STRIDE, ld)
 
     if compact:
         live = torch.rand(B * M, device=DEV, generator=g) < 0.77
@@ -64,7 +64,7 @@ def k2(B, M, L=200, compact=False, ld=0, scale=1e-3):
         torch.cuda.synchronize()
         if not compact:
             assert torch.equal(x_next, ref), "padded-row select differs from the dense one"
-        _lib.set_option(5, 0)
+        _lib.set_option(_lib.OPT_CAND_ROW_STRIDE, 0)
     gbs = nbytes / us / 1e3
     print(f"K2 select{'_compact' if compact else ''} B={B} M={M} L={L} ld={ld or L} scores~{scale:g}: {us:9.1f} us  {gbs:8.1f} GB/s  frac {gbs / PEAK:.3f}  ({nbytes / 1e6:.1f} MB)")
 
@@ -106,7 +106,7 @@ def k2_gather_split(B=1 << 18, M=10, L=200, scale=1e-2):
     torch.cuda.synchronize()
     assert torch.equal(x2, x_next)
     for nb in (1, 2, 4, 3, 5):                                   # SVDD_OPT_SELECT_BATCHES: batches of row groups per wave (1 = the default; 2 / 4: the round-6 experiment)
-        _lib.set_option(8, nb)
+        _lib.set_option(_lib.OPT_SELECT_BATCHES, nb)
         x_next.zero_()
         us = timed(fused)
         torch.cuda.synchronize()
@@ -114,7 +114,7 @@ def k2_gather_split(B=1 << 18, M=10, L=200, scale=1e-2):
         nbytes = B * (4 * M + 2 * L + 4)
         what = {1: "1 batch of 4 row groups (shipped)", 2: "2 batches of 4 groups", 4: "4 batches of 4 groups", 3: "2 batches of 2 groups (same waves)", 5: "4 batches of 1 group (same waves)"}[nb]
         print(f"K2 split B={B} M={M} L={L} scores~{scale:g}  fused, {what:36s} {us:8.1f} us  {nbytes / us / 1e3:8.1f} GB/s  frac {nbytes / us / 1e3 / PEAK:.3f}")
-    _lib.set_option(8, 0)
+    _lib.set_option(_lib.OPT_SELECT_BATCHES, 0)
     for name, fn, nbytes in (("fused select + gather (the shipped K2)", fused, B * (4 * M + 2 * L + 4)),
                              ("decision only (x_next = NULL)", decide, B * (4 * M + 4)),
                              ("gather alone (svdd_gather_rows via idx)", gather, B * (2 * L + 4))):

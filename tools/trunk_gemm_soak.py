@@ -33,7 +33,7 @@ for rnd in range(rounds):
     bias = torch.randn(N, generator=g).to(DEV)
     outs = []
     for ver, reps in ((1, 1), (3, 6)):
-        _lib.set_option(4, ver)
+        _lib.set_option(_lib.OPT_TRUNK_GEMM_VERSION, ver)
         for _ in range(reps):
             out = torch.empty((M, N), device=DEV)
             rc = lib.svdd_trunk_gemm(planes[0].data_ptr(), planes[1].data_ptr() if parts == 2 else None, wp.data_ptr(), bias.data_ptr(),
@@ -46,5 +46,5 @@ for rnd in range(rounds):
         if not torch.equal(o, outs[0]):
             bad += 1
             print(f"MISMATCH M={M} N={N} Cin={Cin} T={T} parts={parts}: {int((o != outs[0]).sum())} elements")
-_lib.set_option(4, 2)
+_lib.set_option(_lib.OPT_TRUNK_GEMM_VERSION, 2)
 print(f"{total} runs of the 256 x 256 kernel over {rounds} random shapes compared bit for bit with the 128 x 128 kernel: {bad} mismatches")

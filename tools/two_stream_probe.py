@@ -18,7 +18,7 @@ B, L, M, S = 256, 200, 10, 128
 sched = model._schedule(S, 1e-5)[0]
 fn = model.value_callable(emb, head)
 from svdd_amd import _lib
-_lib.set_option(7, 1)        # halves of 128 rows would each take the small-batch backbone (2 workgroups per sequence that wait for each other): not with two launches in flight
+_lib.set_option(_lib.OPT_BACKBONE_SPLIT, 1)        # halves of 128 rows would each take the small-batch backbone (2 workgroups per sequence that wait for each other): not with two launches in flight
 
 
 def half_decode(rows, row0):
