@@ -312,7 +312,11 @@ int svdd_gru_bidir_bwd_f32(const float* grad_out, const float* out, const float*
  *   (reference Enformer.py:1617 direction sum; :2010-2047 FeedForwardBlock; :2131-2173 ConvHead with pool "avg").
  *   h_fwd, h_bwd [n,L,64] ; w1pack [64 lanes][128]: lane (j = lane & 15, g = lane >> 4) holds
  *   W1'[16 ct + j][16 (s / 4) + 4 g + s % 4] at 16 ct + s (svdd_amd/fused.py:pack_tail) ; b1 = b1' [128] ;
- *   w_eff [128][n_tasks] = (W_head W_2)^T, b_eff [n_tasks] = W_head b_2 + b_head ; out [n][n_tasks] ; n_tasks <= 4. */
+ *   w_eff [128][n_tasks] = (W_head W_2)^T, b_eff [n_tasks] = W_head b_2 + b_head ; out [n][n_tasks] ; n_tasks <= 4.
+ *   Summation order (what an fp32 restatement has to follow to carry this kernel's rounding error; tests/net_ref.py): the 64 -> 128
+ *   chain of a row starts at b1' ; one wave per sequence, whose lane (j, g) adds w_eff[c][t] relu(.) of rows 16 tile + 4 g + rho
+ *   (rho < 4) and columns c = 16 ct + j (ct < 8) to ONE fp32 accumulator in (tile, rho, ct) order — 32 ceil(L / 16) one-wide steps
+ *   from zero, not one chain per row — then the 64 lanes are summed by an xor butterfly, divided by L, and b_eff is added. */
 int svdd_value_tail_f32(const float* h_fwd, const float* h_bwd, const float* w1pack, const float* b1,
                         const float* w_eff, const float* b_eff, float* out, int n, int L, int n_tasks,
                         const int32_t* count, void* stream);
@@ -370,7 +374,8 @@ int svdd_set_tower_version(int v);
  *   them is computed, the other rows are copied from the parent's output. Bit-identical to svdd_conv_tower_f32 on
  *   the candidates (tests/test_fused_gpu.py::test_tower_windows_equal_full_tower).
  *   svdd_candidate_windows: cand [B,M,L] u8, x [B,L] u8 -> win [B*M][2] = (w0, w1), multiples of 16 covering the
- *     positions where the candidate differs from its parent +- margin (27 for the 5-layer tower); (0, 0) if none.
+ *     positions where the candidate differs from its parent +- margin (27 for the 5-layer tower); (0, 0) if none:
+ *     w0 = max(0, first - margin) rounded down, w1 = min(last + margin + 1, L) rounded up to a multiple of 16 (so w1 <= L rounded up).
  *   svdd_conv_tower_windows_f32: onehot [n = B*M, L, 4] (row b*M + m), win from above, parent_out [B, L, 64] =
  *     svdd_conv_tower_f32 of the parents' one-hot; out [n, L, 64]. 104 < L <= 208, nlayers = 5.
  *   flags [B*M] (may be NULL): the number of row tiles of the window ((w1 - w0) / 16 >= 1) if the candidate differs from its
@@ -404,6 +409,11 @@ int svdd_backbone_cnn_f32(const uint8_t* x, const float* table0, const float* ti
  *   svdd_backbone_cnn_save_f32: svdd_backbone_cnn_f32 on the tokens x (the SAME BITS in `out`) that also writes, in the kernel's
  *     lane-private layout, xhat [n][nlayers][56][512] f32 (LayerNorm'd value before the affine map), rstd [n][nlayers][208] f32
  *     and mask [n][nlayers + 2][512] u64 (ReLU decisions of the first layer, every conv layer and final_conv's first 1x1).
+ *     Layout and extents: thread tid = 64 w + 16 g + j of the sequence's workgroup (w = wave, cg = w & 3, rh = w >> 2) owns rows
+ *     16 (rh + 2 r) + 4 g + e (r < 7, e < 4) and channels 32 cg + j + 16 ct (ct < 2); slot s = (2 r + ct) 4 + e. xhat[..][s][tid] is
+ *     written for every slot whose row is < 208 and for no other (r = 6 of the waves with rh = 1 is never written), bit s of
+ *     mask[..][tid] is that element's decision (bits 56 .. 63 zero; every u64 is written), rstd[..][row] is written for all 208 rows
+ *     of the tile. Rows >= L hold values of the zero padding, not of the sequence.
  *   svdd_backbone_cnn_grad_f32: dlogits [n,L,5] = d loss / d `out` -> dx [n,L,5] = d loss / d onehot(x), through the transposed
  *     1x1 convs, 20 x [ReLU', transposed dilated conv (the same implicit GEMM on tiles_bwd), LayerNorm backward from xhat / rstd,
  *     residual] and the first conv's transpose. tiles_bwd: W_f1^T as [4][128][32], then layers nlayers-1 .. 0 as [4][9][128][32] of

@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.net_ref import distinct_layers
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
@@ -211,6 +213,7 @@ def test_one_launch_backbone_vs_plain(n, L):
         for nm in cnn.norms:
             nm.weight.uniform_(0.5, 1.5)
             nm.bias.uniform_(-0.3, 0.3)
+    distinct_layers(cnn, 1)                                           # 20 distinct layers (a random-init CNNModel has 5 x 4 copies)
     x = torch.randint(0, 5, (n, L), device=DEV, dtype=torch.uint8)
     pk = fused.pack_backbone(cnn)
     with torch.no_grad():
@@ -238,6 +241,7 @@ def test_backbone_on_several_workgroups_per_sequence_same_bits(n, L):
         for nm in cnn.norms:
             nm.weight.uniform_(0.5, 1.5)
             nm.bias.uniform_(-0.3, 0.3)
+    distinct_layers(cnn, 1)                                           # 20 distinct layers (a random-init CNNModel has 5 x 4 copies)
     x = torch.randint(0, 5, (n, L), device=DEV, dtype=torch.uint8)
     x[0, L // 2:] = 4
     pk = fused.pack_backbone(cnn)
@@ -396,7 +400,7 @@ def test_backbone_sequences_per_tile_choice_same_bits(n, L, mode):
     another: 1100 sequences of L = 50 = 256 tiles of four + 76 of one). Every variant gives the bits of the always-full tiles of round 1."""
     from svdd_amd import _lib, backbone, config, fused
     torch.manual_seed(L)
-    cnn = backbone.CNNModel(config.rna_config().model, alphabet_size=5).to(DEV).eval()
+    cnn = distinct_layers(backbone.CNNModel(config.rna_config().model, alphabet_size=5).to(DEV).eval(), 1)
     x = torch.randint(0, 5, (n, L), device=DEV, dtype=torch.uint8)
     pk = fused.pack_backbone(cnn) if mode == "f32" else fused.pack_backbone_lp(cnn, mode)
     fwd = fused.backbone_cnn if mode == "f32" else fused.backbone_cnn_lp
@@ -464,6 +468,7 @@ def test_backbone_forward2_on_the_hip_conv_kernel_both_directions(B, L):
         for nm in cnn.norms:
             nm.weight.uniform_(0.5, 1.5)
             nm.bias.uniform_(-0.3, 0.3)
+    distinct_layers(cnn, 1)                                           # 20 distinct layers (a random-init CNNModel has 5 x 4 copies)
     for p in cnn.parameters():
         p.requires_grad_(False)
     x = torch.softmax(torch.randn(B, L, 5, device=DEV), dim=-1)
@@ -524,6 +529,7 @@ def test_backbone_one_launch_forward_with_saved_statistics_and_its_gradient_kern
         for nm in cnn.norms:
             nm.weight.uniform_(0.5, 1.5)
             nm.bias.uniform_(-0.3, 0.3)
+    distinct_layers(cnn, 1)                                           # 20 distinct layers (a random-init CNNModel has 5 x 4 copies)
     for p in cnn.parameters():
         p.requires_grad_(False)
     fb = fused.FusedBackbone(cnn).to(DEV).eval()

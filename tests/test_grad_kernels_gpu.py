@@ -17,96 +17,15 @@ reduction plus element-wise work (stem pair, gated convolution, gi, dx from da, 
 or chained steps (GRU forward and BPTT, tail_grad, bb_layer_fwd, the whole pass). ReLU kinks are excluded by conditions on the
 float64 reference alone, under caps (grad_ref.near_kink / tail_kink_rows / tail_kink_seqs); tests/test_grad_ref_cpu.py shows the
 caps hold for these inputs. Exact comparisons stay exact. One line `ERR <name> <err> bar <bar>` is printed per comparison."""
-import ctypes
-
 import pytest
 import torch
 
 from svdd_amd import _lib
 from svdd_amd.fused import pack_conv, pack_gru, pack_gru_bwd
 from tests import grad_ref as R
+from tests.kernel_harness import DEV, _dev, _p, _report, _st, _twice
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-GUARD = 1024                                  # elements of guard space before and after every output
-SENT32, SENT8 = 0x7FA5A5A5, 0xA5              # a NaN bit pattern / a byte no kernel writes
-
-
-class _Buf:
-    """numel elements (fp32, or bytes) between two guards, all sentinel-filled; .ptr is element 0."""
-
-    def __init__(self, numel, dtype=torch.float32):
-        self.numel, self.dtype = numel, dtype
-        if dtype == torch.uint8:
-            self.raw, self.sent = torch.full((numel + 2 * GUARD,), SENT8, dtype=torch.uint8, device=DEV), SENT8
-        else:
-            self.raw, self.sent = torch.full((numel + 2 * GUARD,), SENT32, dtype=torch.int32, device=DEV), SENT32
-
-    @property
-    def ptr(self):
-        return self.raw[GUARD:].data_ptr()
-
-    def bits(self):
-        return self.raw[GUARD:GUARD + self.numel]
-
-    def body(self):
-        return self.bits().view(self.dtype)
-
-    def cpu(self, *shape):
-        v = self.body().cpu()
-        return v.view(*shape) if shape else v
-
-    def untouched(self):
-        """Bool mask of elements still holding the sentinel; asserts that both guards are intact."""
-        assert bool((self.raw[:GUARD] == self.sent).all()) and bool((self.raw[GUARD + self.numel:] == self.sent).all()), "guard overwritten"
-        return self.bits() == self.sent
-
-    def assert_written(self, what):
-        left = int(self.untouched().sum())
-        assert left == 0, f"{what}: {left} of {self.numel} elements were never written"
-
-    def assert_untouched(self, what):
-        assert bool(self.untouched().all()), f"{what}: written although the contract says it is not"
-
-
-def _st():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _dev(t):
-    return None if t is None else t.to(DEV).contiguous()
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _twice(name, launch, sizes, written=None):
-    """launch(*ptrs) on fresh sentinel buffers of `sizes` (numel, or (numel, dtype)), twice: guards intact, outputs fully written
-    (written[i] False: untouched instead), the two launches bit-identical. -> the first launch's buffers."""
-    runs = []
-    for _ in range(2):
-        bufs = [_Buf(*s) if isinstance(s, tuple) else _Buf(s) for s in sizes]
-        _lib.check(launch(*[b.ptr for b in bufs]), name)
-        torch.cuda.synchronize()
-        for i, b in enumerate(bufs):
-            if written is None or written[i]:
-                b.assert_written(f"{name} output {i}")
-            else:
-                b.assert_untouched(f"{name} output {i}")
-        runs.append(bufs)
-    for a, b in zip(*runs):
-        assert torch.equal(a.bits(), b.bits()), f"{name}: two launches differ"
-    return runs[0]
-
-
-def _report(name, got, r64, r32, margin, keep=None):
-    """max |got - ref64| (over `keep`) against grad_ref.bar(margin, ref32, ref64)."""
-    err = (got.double() - r64).abs()
-    err = float((err if keep is None else err[keep]).max()) if err.numel() else 0.0
-    b = R.bar(margin, r32, r64, keep)
-    print(f"ERR {name} {err:.3e} bar {b:.1e}")
-    assert err <= b, (name, err, b)
 
 
 # -------------------------------------------------------------------------------------------------------------------- stem

@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.net_ref import distinct_layers
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 X3 = ("f16x3", "bf16x3")
@@ -32,7 +34,7 @@ def _perturbed_cnn(L):
         for nm in cnn.norms:                         # non-trivial LayerNorm affine
             nm.weight.uniform_(0.5, 1.5)
             nm.bias.uniform_(-0.3, 0.3)
-    return cnn
+    return distinct_layers(cnn, 5)                   # 20 layers of their own, not 5 groups of 4 copies (tests/net_ref.py)
 
 
 @pytest.mark.parametrize("mode", ["f16x3", "bf16x3", "f16", "bf16"])

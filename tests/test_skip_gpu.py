@@ -136,14 +136,26 @@ def test_select_compact_equals_select_on_dense_scores(mode):
 @pytest.mark.parametrize("L", [200, 50])
 def test_backbone_on_compacted_rows(precision, L):
     """The one-launch backbone on a device-side row list: compacted output (candidate compaction) and in-place
-    scatter (per-row logits cache) give the same bits as the full forward for the listed rows and touch nothing else."""
+    scatter (per-row logits cache) give the same bits as the full forward for the listed rows and touch nothing else: the
+    forward is limited to the first count[0] compact rows (include/svdd_hip.h), the rest of the last tile included.
+    The backbone's 20 layers are re-drawn to be distinct (a random-init CNNModel holds 5 groups of 4 copies) AFTER the fused
+    kernels were attached: the weight-validated cache must pick the change up by itself, shown against a float64 forward of the
+    new weights."""
+    import copy
     from svdd_amd import ops, synthetic
+    from tests.net_ref import distinct_layers
     model, _, _, _ = synthetic.build("dna" if L == 200 else "rna", DEV)
     model.precision = precision
-    fb = model._fused_backbone()
     n = 77
     x = torch.randint(0, 5, (n, L), device=DEV, dtype=torch.uint8)
+    stale = model._fused_backbone().forward_rows(x).clone()
+    distinct_layers(model.backbone, 3)
+    fb = model._fused_backbone()
     full = fb.forward_rows(x).clone()
+    with torch.no_grad():
+        ref64 = copy.deepcopy(model.backbone).double()(x[:16], torch.zeros(16, device=DEV, dtype=torch.float64))
+    assert float((full[:16].double() - ref64).abs().max()) <= (2e-5 if precision == "f32" else 1e-4)
+    assert float((stale[:16].double() - ref64).abs().max()) > 1e-2            # (the old weights' logits are far away)
     flags = (torch.rand(n, device=DEV) < 0.4).to(torch.int32)
     idx, slot, count = torch.empty(n, dtype=torch.int32, device=DEV), torch.empty(n, dtype=torch.int32, device=DEV), torch.zeros(1, dtype=torch.int32, device=DEV)
     ops.compact_flags(flags, idx, slot, count)
@@ -151,8 +163,7 @@ def test_backbone_on_compacted_rows(precision, L):
     comp = torch.full((n, L, 5), 7.0, device=DEV)
     fb.forward_rows(x, count=count, out=comp, row_idx=idx, scatter=False)
     assert torch.equal(comp[:k], full[idx[:k].long()])
-    tiles = (k + (208 // L) - 1) // (208 // L)
-    assert bool((comp[tiles * (208 // L):] == 7.0).all())                         # rows of untouched tiles are untouched
+    assert bool((comp[k:] == 7.0).all())                                          # rows behind the count are untouched, in the last tile too
     inplace = torch.full((n, L, 5), 7.0, device=DEV)
     fb.forward_rows(x, count=count, out=inplace, row_idx=idx, scatter=True)
     live = flags.bool()
