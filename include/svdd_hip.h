@@ -425,6 +425,22 @@ int svdd_backbone_cnn_save_f32(const uint8_t* x, const float* table0, const floa
 int svdd_backbone_cnn_grad_f32(const float* dlogits, const float* tiles_bwd, const float* gamma, const float* w2,
                                const float* table0, const float* xhat, const float* rstd, const unsigned long long* mask,
                                float* dx, int n, int L, int nlayers, const int* dilations, void* stream);
+/* svdd_backbone_incr_f32 — svdd_backbone_cnn_f32 (the SAME BITS in `out`) for a decode that forwards the same n sequences step
+ *   after step with few tokens changed in between: the residual stream behind the leading run of `lead` dilation-1 conv layers
+ *   (lead >= 2, dilations[0 .. lead) all 1; 104 < L <= 208) is carried in caller-owned device memory and only the 16-row tiles
+ *   inside the reach of a changed token are recomputed. x, table0, tiles, vec, w2, out, dilations: as svdd_backbone_cnn_f32.
+ *   planes [lead][n][208][128] f32: plane k - 1 = the stream after conv layer k - 1 (rows >= L are never written) ;
+ *   x_prev [n][L] u8: the tokens the planes belong to ; items [lead][n][7] i32: the step's work list, first tile | tiles << 8 per
+ *   run of adjacent tiles inside p +- (4 + 4 k) of a changed position p for plane k, runs cut to max_item (2 or 4) tiles, 0 = empty
+ *   slot (all 7 slots of every row are rewritten each step) ; stat (may be NULL): device u64, += the tile-layers the step marked.
+ *   first != 0: the whole forward in one launch, which also fills planes and x_prev (the first step of a decode, or any step
+ *   after the planes went stale). first == 0: compares x with x_prev (and updates it), one launch per leading layer over the
+ *   items (each reads plane k - 1 of its tiles and one halo tile per side, writes plane k of its tiles and nothing else), then
+ *   the layers lead .. nlayers - 1 and final_conv from plane `lead` in one launch for every row. All launches go to the hipStream_t `on_stream`
+ *   (passed by the caller like any other argument: svdd_amd/_lib.call does not add it for this entry), none waits for another workgroup; the profile slot (6) records one span per call. */
+int svdd_backbone_incr_f32(const uint8_t* x, const float* table0, const float* tiles, const float* vec, const float* w2,
+                           float* out, int n, int L, int nlayers, const int* dilations, int lead, float* planes,
+                           uint8_t* x_prev, int32_t* items, unsigned long long* stat, int first, int max_item, void* on_stream);
 /* svdd_backbone_set_workspace — caller-owned scratch for the small-batch form of svdd_backbone_cnn_f32 (several workgroups per
  * sequence exchange the LayerNorm'd image of every layer through it): ws = device memory of `bytes` >= n_max * (2 * 208 * 128 * 4
  * + 4) + 4 bytes for batches of up to n_max sequences (n_max = 128 covers every case the split is used for); NULL: none (one
@@ -525,7 +541,7 @@ int svdd_set_option(int key, int value);
 int svdd_k1_stats(unsigned long long* device_counters2);
 
 /* Per-launch kernel timing (host). While enabled, svdd_propose (kernel 0), svdd_select (1), svdd_conv1d_cl_f32 (2),
- * svdd_gru_bidir_f32 (3), svdd_epilogue_ln_f32 (4), svdd_conv_tower_f32 (5), svdd_backbone_cnn_f32 / _save_f32 (6), svdd_value_tail_f32 (7), svdd_tds_resample (8), svdd_mt19937_uniform_f32 (9), svdd_backbone_cnn_grad_f32 (10), svdd_gru_bidir_train[2]_f32 (11) and svdd_gru_bidir_bwd[2]_f32 (12; the *2 forms as one span over their two launches) are dispatched (the reward net's DPS kernels share slots: svdd_reward_stem*_f32 5, svdd_reward_tail_grad_f32 7, svdd_conv1d_cl_gated_f32 2)
+ * svdd_gru_bidir_f32 (3), svdd_epilogue_ln_f32 (4), svdd_conv_tower_f32 (5), svdd_backbone_cnn_f32 / _save_f32 / svdd_backbone_incr_f32 (6; the latter as one span over its launches), svdd_value_tail_f32 (7), svdd_tds_resample (8), svdd_mt19937_uniform_f32 (9), svdd_backbone_cnn_grad_f32 (10), svdd_gru_bidir_train[2]_f32 (11) and svdd_gru_bidir_bwd[2]_f32 (12; the *2 forms as one span over their two launches) are dispatched (the reward net's DPS kernels share slots: svdd_reward_stem*_f32 5, svdd_reward_tail_grad_f32 7, svdd_conv1d_cl_gated_f32 2)
  * with HIP start/stop events bound to the dispatch on its launch stream
  * (hipExtLaunchKernelGGL); svdd_profile_collect waits for the recorded launches, returns the summed
  * hipEventElapsedTime and their count, and clears the record. Not for use during graph capture. */
@@ -543,7 +559,7 @@ int svdd_device_info(char* arch, int arch_len, int* num_cu);
 
 /* ABI version of this header: bumped on any signature change. */
 int svdd_abi_version(void);
-#define SVDD_ABI_VERSION 13
+#define SVDD_ABI_VERSION 14
 
 /*
  * Enformer-shaped value trunk (BASELINE.json configs[3]; reference decode.py:78-80, Enformer.py:1271-1334 trunk, :1807-1884

@@ -1403,6 +1403,8 @@ struct BackboneArgs {
   int out_scatter;         // ... and writes its logits to row row_idx[r] of out (1) or to row r (0)
   int auto_spt, ncu;       // auto_spt: the workgroups pick the sequences per tile from the device-side row count (svdd_spt.h)
   SvddTilePlan plan;       // several sequences per tile, row count known on the host: which tile takes how many (svdd_spt.h)
+  float* planes;           // PLN != 0: the carried stem planes [planes_P][n][208][128] (plane k - 1 = f after conv layer k - 1, k = 1 .. planes_P)
+  int planes_P;
 };
 
 // What the gradient kernel (backbone_grad_kernel, DPS) needs from a forward, all in the forward kernel's LANE-PRIVATE layout — lane
@@ -1436,9 +1438,13 @@ __device__ __forceinline__ float group16_sum(float v) {        // sum over the 1
 // (A first version gave each wave 16 channels of all 13 row tiles and skipped tiles in pairs: twice the LDS reads and
 //  address VALU per MFMA, 6 % more MFMAs; 2.31 vs 2.17 ms.)
 // LDS image rows: row -1 and rows >= L of a one-sequence tile are zero, so a tap is a clamped row offset.
-template <bool SPT1, bool SAVE = false>
+// PLN (the incremental stem, svdd_backbone_incr_f32): 1 = the forward also STORES f after each of the first planes_P conv layers
+// (the first step of a decode fills the carried planes); 2 = the TAIL forward: f is loaded from plane planes_P and the layers
+// planes_P .. nl - 1 plus final_conv run unchanged. Same operations on every element either way: same bits in `out`.
+template <bool SPT1, bool SAVE = false, int PLN = 0>
 __global__ __launch_bounds__(512, 2) void backbone_kernel(BackboneArgs a, BackboneSave sv) {
   static_assert(SPT1 || !SAVE, "the saving forward is the one-sequence-per-tile form");
+  static_assert(SPT1 || PLN == 0, "the carried planes belong to the one-sequence-per-tile form");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* img = smem + BB_AP;                              // rows -1 .. TW_ROWS ; [-1] and [TW_ROWS] stay zero
   float* Bs = smem + (TW_ROWS + 2) * BB_AP;               // [9][5][128] the first layer's lookup table
@@ -1529,8 +1535,23 @@ __global__ __launch_bounds__(512, 2) void backbone_kernel(BackboneArgs a, Backbo
   // ---- first layer: f[row][col] = relu(b + sum_t table[t][tok[row + t - 4]][col])   (dnaconv.py:177,184)
   f32x4 f[NR][2], acc[NR][2];
   unsigned long long relu_bits = 0ull;                    // SAVE: this lane's ReLU decisions of the current layer
+  // the sequence's rows of plane 0 (PLN): plane k is pl_stride floats further on
+  const size_t pl_stride = (size_t)a.n * TW_ROWS * BB_C;
+  float* pl0 = PLN ? a.planes + (size_t)(a.row_idx ? a.row_idx[seq0] : seq0) * TW_ROWS * BB_C : nullptr;
+  if (PLN == 2) {
+#pragma unroll
+    for (int r = 0; r < NR; ++r)
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int row = 16 * (rh + 2 * r) + 4 * g + e;
+          f[r][ct][e] = row < tile_rows ? pl0[(size_t)(a.planes_P - 1) * pl_stride + row * BB_C + col0 + 16 * ct] : 0.0f;
+        }
+  }
 #pragma unroll
   for (int ct = 0; ct < 2; ++ct) {
+    if (PLN == 2) break;
     const int col = col0 + 16 * ct;
     const float b0 = a.vec[col];
 #pragma unroll
@@ -1566,7 +1587,8 @@ __global__ __launch_bounds__(512, 2) void backbone_kernel(BackboneArgs a, Backbo
   // from L2 into the B-operand registers, one tile ahead (no LDS staging, no barrier inside a layer).
   const float* wsrc = a.tiles + col0 * CH + 8 * g;
   auto tile_of = [&](int k) { return k < nl * 36 ? k : nl * 36 + (k - nl * 36) / 9; };
-  int it = 0;
+  const int layer0 = PLN == 2 ? a.planes_P : 0;           // the tail forward starts behind the carried stem
+  int it = layer0 * 36;
   while (it < it_end && sched[it] == 0) ++it;
   it = __builtin_amdgcn_readfirstlane(it);
   int en = __builtin_amdgcn_readfirstlane(sched[it]);
@@ -1582,7 +1604,7 @@ __global__ __launch_bounds__(512, 2) void backbone_kernel(BackboneArgs a, Backbo
     bB[0] = bA[0]; bB[1] = bA[1]; bB[2] = bA[2]; bB[3] = bA[3];
   }
 
-  for (int layer = 0; layer <= nl; ++layer) {             // layer == nl: the first 1x1 conv of final_conv
+  for (int layer = layer0; layer <= nl; ++layer) {        // layer == nl: the first 1x1 conv of final_conv
     const float* vl = a.vec + (size_t)(layer + 1) * 4 * BB_C;
     if (layer < nl) {
       const float tb0 = vl[BB_C + col0], tb1 = vl[BB_C + col0 + 16];
@@ -1849,6 +1871,17 @@ __global__ __launch_bounds__(512, 2) void backbone_kernel(BackboneArgs a, Backbo
 #pragma unroll
           for (int e = 0; e < 4; ++e) f[r][ct][e] = fmaxf(acc[r][ct][e], 0.0f) + f[r][ct][e];   // relu(conv + b) + f
       }
+      if (PLN == 1 && layer < a.planes_P) {
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+#pragma unroll
+          for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const int row = 16 * (rh + 2 * r) + 4 * g + e;
+              if (row < tile_rows) pl0[(size_t)layer * pl_stride + row * BB_C + col0 + 16 * ct] = f[r][ct][e];
+            }
+      }
     } else {
 #pragma unroll
       for (int r = 0; r < NR; ++r) {
@@ -1880,6 +1913,297 @@ __global__ __launch_bounds__(512, 2) void backbone_kernel(BackboneArgs a, Backbo
   }
 }
 #undef BB_OWN
+
+// ------------------------------------------------- incremental stem: only what a step's new tokens can reach (svdd_backbone_incr_f32) ----
+// The backbone does not see the time step, so a row's activations depend on its tokens alone, and between two decode steps a row's
+// tokens change at a few positions. The leading run of P dilation-1 layers spreads a changed position p slowly: f after the first
+// convolution differs from the previous step's inside p +- 4, f after conv layer k - 1 ("plane k") inside p +- (4 + 4 k) — everything
+// else is the previous step's value, bit for bit. So f of every row is CARRIED in HBM across the decode, planes 1 .. P of
+// [n][208][128] fp32, and per step
+//   backbone_worklist_kernel   compares the old and the new tokens and writes, per layer, the row tiles inside the reach as items
+//                              (first tile, tile count <= max_item) over runs of adjacent tiles;
+//   backbone_seg_kernel        one launch per layer k = 1 .. P, one workgroup per item: plane k - 1 of the item's tiles and of one
+//                              halo tile on each side (k = 1: f_0 from the tokens, the table lookup of backbone_kernel's first
+//                              layer) -> LayerNorm image in LDS -> the 9-tap convolution of the item's own tiles -> ReLU + residual ->
+//                              plane k;
+//   backbone_kernel<.., 2>     the tail: layers P .. nl - 1 and final_conv from plane P, one workgroup per sequence as ever.
+// The work of the stem is then spread over the chip by ITEM, not tied to its row's CU (a per-row incremental kernel lasts as long
+// as the row with the widest change: 0.90 of the full stage in the per-step maximum over 256 rows, 0.34 on average).
+// Same bits: the segment kernel keeps backbone_kernel's lane-to-column ownership (wave = column group cg, lane (j, g) owns columns
+// 32 cg + j and + 16 of rows 4 g + e), its LayerNorm summation tree (lane pair, group16_sum read at j = 0, the four psum partials as
+// (p0 + p1) + (p2 + p3), the same rsqrtf), the accumulator start (the bias) and the (chunk outer, tap inner, 8 k-steps) order of
+// products. At dilation 1 every tap of every row tile is live in backbone_kernel's schedule, so all 36 entries run; a tap that
+// leaves the sequence reads a zero row there (clamped address) and a zero row of the halo tile here. A mask that marks too many
+// tiles is still exact (an unchanged tile recomputes to the same bits); no workgroup waits for another: the stream orders the layers.
+constexpr int SEG_SLOTS = 7;                   // items per (layer, row): 13 tiles in runs cut to <= 2 (or <= 4) tiles, at worst 7
+
+struct BackboneSegArgs {
+  const uint8_t* x;        // [n, L] the step's tokens (layer 1 builds f_0 from them)
+  const float* table0;     // as BackboneArgs
+  const float* tiles;
+  const float* vec;
+  float* planes;           // [P][n][208][128]
+  const int* items;        // [P][n][SEG_SLOTS] : first tile | tile count << 8 ; 0 = empty slot
+  int n, L, layer;         // layer k = 1 .. P: reads plane k - 1 (k = 1: the tokens), writes plane k
+};
+
+// One wave per row. Lane k - 1 cuts layer k's tile mask into items; stat (may be NULL) += the tile-layers marked.
+__global__ __launch_bounds__(256) void backbone_worklist_kernel(const uint8_t* __restrict__ x, uint8_t* __restrict__ x_prev, int n,
+                                                                int L, int P, int max_item, int* __restrict__ items,
+                                                                unsigned long long* __restrict__ stat) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n) return;
+  const int lane = threadIdx.x & 63;
+  const uint8_t* xn = x + (size_t)row * L;
+  uint8_t* xp = x_prev + (size_t)row * L;
+  int changed = 0;                                        // bit q: position lane + 64 q differs
+  for (int q = 0; q < 4; ++q) {
+    const int l = lane + 64 * q;
+    if (l < L && xn[l] != xp[l]) { changed |= 1 << q; xp[l] = xn[l]; }
+  }
+  int mine = 0;
+  for (int k = 1; k <= P; ++k) {
+    const int reach = 4 + 4 * k;
+    int m = 0;
+    for (int q = 0; q < 4; ++q)
+      if (changed >> q & 1) {
+        const int l = lane + 64 * q;
+        const int tlo = max(0, l - reach) >> 4, thi = min(L - 1, l + reach) >> 4;
+        m |= ((2 << thi) - 1) & ~((1 << tlo) - 1);
+      }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m |= __shfl_xor(m, off, 64);
+    if (lane == k - 1) mine = m;
+  }
+  if (lane >= P) return;
+  int* it = items + ((size_t)lane * n + row) * SEG_SLOTS;
+  int cnt = 0;
+  for (int t = 0; t < TW_RT;) {
+    if (!(mine >> t & 1)) { ++t; continue; }
+    int len = 1;
+    while (len < max_item && t + len < TW_RT && (mine >> (t + len) & 1)) ++len;
+    it[cnt++] = t | len << 8;
+    t += len;
+  }
+  for (; cnt < SEG_SLOTS; ++cnt) it[cnt] = 0;
+  if (stat && mine) atomicAdd(stat, (unsigned long long)__popc(mine));
+}
+
+// NC = the most own tiles an item may have (2 / 4); 4 waves, wave cg owns 32 output channels of EVERY tile of the item (slots
+// 0 .. NC + 1 = halo, own tiles, halo), so a weight fragment feeds up to NC row tiles and the register arrays are sized to the item.
+template <int NC>
+__global__ __launch_bounds__(256, NC == 4 ? 2 : 3) void backbone_seg_kernel(BackboneSegArgs a) {
+  constexpr int NS = NC + 2, ROWS = 16 * NS;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* img = smem;                                      // [ROWS][BB_AP] image row i = sequence row 16 (t0 - 1) + i
+  float* psum = img + ROWS * BB_AP;                       // [4][ROWS]
+  float* rstat = psum + 4 * ROWS;                         // [ROWS]
+  int* toks = reinterpret_cast<int*>(rstat + ROWS);       // [ROWS + 8] tokens of sequence rows 16 (t0 - 1) - 4 ..   (layer 1)
+
+  const int item = __builtin_amdgcn_readfirstlane(a.items[(size_t)(a.layer - 1) * a.n * SEG_SLOTS + blockIdx.x]);
+  const int nown = min(item >> 8, NC);
+  if (nown == 0) return;
+  const int t0 = item & 255;
+  const int seq = blockIdx.x / SEG_SLOTS;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int cg = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int j = lane & 15, g = lane >> 4;
+  const int col0 = 32 * cg + j;
+  const int L = a.L;
+  const int r0 = 16 * (t0 - 1);                           // sequence row of image row 0
+  const size_t pl_stride = (size_t)a.n * TW_ROWS * BB_C;
+  float* pl0 = a.planes + (size_t)seq * TW_ROWS * BB_C;
+  const int cl = a.layer - 1;                             // the conv layer this launch runs
+#define SEG_LIVE(S) ((S) <= nown + 1)
+
+  f32x4 f[NS][2], acc[NS][2];
+  if (a.layer == 1) {
+    for (int e = tid; e < ROWS + 8; e += 256) {
+      const int p = r0 - 4 + e;
+      toks[e] = (p >= 0 && p < L) ? (int)a.x[(size_t)seq * L + p] : -1;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) {
+      const int col = col0 + 16 * ct;
+      const float b0 = a.vec[col];
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        if (!SEG_LIVE(s)) continue;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int ri = 16 * s + 4 * g + e, row = r0 + ri;
+          float v = b0;
+#pragma unroll
+          for (int t = 0; t < 9; ++t) {
+            const int tk = toks[ri + t];                  // sequence row row + t - 4 ; -1 outside the sequence
+            if (tk >= 0) v += a.table0[(t * 5 + tk) * BB_C + col];
+          }
+          f[s][ct][e] = (row >= 0 && row < L) ? fmaxf(v, 0.0f) : 0.0f;
+        }
+      }
+    }
+  } else {
+    const float* src = pl0 + (size_t)(a.layer - 2) * pl_stride;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      if (!SEG_LIVE(s)) continue;
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int row = r0 + 16 * s + 4 * g + e;
+          f[s][ct][e] = (row >= 0 && row < L) ? src[row * BB_C + col0 + 16 * ct] : 0.0f;
+        }
+    }
+  }
+
+  // ---- LayerNorm(f + tb) of the item's tiles and its halo -> image (backbone_kernel's passes, row for row)
+  const float* vl = a.vec + (size_t)(cl + 1) * 4 * BB_C;
+  {
+    const float tb0 = vl[BB_C + col0], tb1 = vl[BB_C + col0 + 16];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      if (!SEG_LIVE(s)) continue;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float sm = group16_sum((f[s][0][e] + tb0) + (f[s][1][e] + tb1));
+        if (j == 0) psum[cg * ROWS + 16 * s + 4 * g + e] = sm;
+      }
+    }
+    __syncthreads();
+    if (tid < 16 * (nown + 2))
+      rstat[tid] = ((psum[tid] + psum[ROWS + tid]) + (psum[2 * ROWS + tid] + psum[3 * ROWS + tid])) * (1.0f / BB_C);
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      if (!SEG_LIVE(s)) continue;
+      const float4 cur4 = *reinterpret_cast<const float4*>(rstat + 16 * s + 4 * g);
+      const float mean4[4] = {cur4.x, cur4.y, cur4.z, cur4.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float mean = mean4[e];
+        const float d0 = f[s][0][e] + tb0 - mean, d1 = f[s][1][e] + tb1 - mean;
+        acc[s][0][e] = d0; acc[s][1][e] = d1;
+        const float sq = group16_sum(d0 * d0 + d1 * d1);
+        if (j == 0) psum[cg * ROWS + 16 * s + 4 * g + e] = sq;
+      }
+    }
+    __syncthreads();
+    if (tid < 16 * (nown + 2))
+      rstat[tid] = rsqrtf(((psum[tid] + psum[ROWS + tid]) + (psum[2 * ROWS + tid] + psum[3 * ROWS + tid])) * (1.0f / BB_C) + 1e-5f);
+    __syncthreads();
+    const float gm0 = vl[2 * BB_C + col0], gm1 = vl[2 * BB_C + col0 + 16];
+    const float bt0 = vl[3 * BB_C + col0], bt1 = vl[3 * BB_C + col0 + 16];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      if (!SEG_LIVE(s)) continue;
+      const float4 cur4 = *reinterpret_cast<const float4*>(rstat + 16 * s + 4 * g);
+      const float rs4[4] = {cur4.x, cur4.y, cur4.z, cur4.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int ri = 16 * s + 4 * g + e, row = r0 + ri;
+        const float rs = rs4[e];
+        const bool in = row >= 0 && row < L;              // rows outside the sequence are the zero padding of the convolution
+        img[ri * BB_AP + col0] = in ? acc[s][0][e] * rs * gm0 + bt0 : 0.0f;
+        img[ri * BB_AP + col0 + 16] = in ? acc[s][1][e] * rs * gm1 + bt1 : 0.0f;
+      }
+    }
+  }
+
+  // ---- the convolution of the own tiles (slots 1 .. nown): 36 (chunk, tap) entries, chunk outer
+  const float bl0 = vl[col0], bl1 = vl[col0 + 16];
+  f32x4 cacc[NC][2];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) { cacc[c][0] = f32x4{bl0, bl0, bl0, bl0}; cacc[c][1] = f32x4{bl1, bl1, bl1, bl1}; }
+  typedef __attribute__((address_space(3))) f32x4 LdsF4;
+  const int img_lds = (int)(unsigned)(size_t)(const __attribute__((address_space(3))) float*)img;
+  const int arow0 = img_lds + ((16 + j) * BB_AP + 8 * g) * 4;       // LDS byte address of (row j of slot 1, col 8 g)
+  const float* wsrc = a.tiles + (size_t)cl * 36 * BB_C * CH + col0 * CH + 8 * g;
+  const int live = (1 << nown) - 1;
+  float4 bA[4], bB[4];
+  bA[0] = *reinterpret_cast<const float4*>(wsrc);
+  bA[1] = *reinterpret_cast<const float4*>(wsrc + 4);
+  bA[2] = *reinterpret_cast<const float4*>(wsrc + 16 * CH);
+  bA[3] = *reinterpret_cast<const float4*>(wsrc + 16 * CH + 4);
+  bB[0] = bA[0]; bB[1] = bA[1]; bB[2] = bA[2]; bB[3] = bA[3];
+  __syncthreads();                                        // the image is complete
+#define SG_DBYTES(IT) ((((IT) % 9) - 4) * (BB_AP * 4) + ((IT) / 9) * (CH * 4))
+#define SG_ALOAD(C, V, DBYTES)                                                                               \
+      { const LdsF4* ap_ = reinterpret_cast<const LdsF4*>(arow0 + (DBYTES) + (C) * (16 * BB_AP * 4));         \
+        const f32x4 t0_ = ap_[0], t1_ = ap_[1];                                                              \
+        V[0] = make_float4(t0_[0], t0_[1], t0_[2], t0_[3]); V[1] = make_float4(t1_[0], t1_[1], t1_[2], t1_[3]); }
+#define SG_MM(C, U)                                                                                          \
+      __builtin_amdgcn_sched_barrier(0);                                                                     \
+      __builtin_amdgcn_s_waitcnt(0xC07F | (2 << 8));      /* at most the two reads of the other fragment set in flight */ \
+      if (live & (1 << (C))) {                                                                               \
+        _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                                      \
+          cacc[C][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].x, bf0[4 * q], cacc[C][0], 0, 0, 0);        \
+          cacc[C][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].x, bf1[4 * q], cacc[C][1], 0, 0, 0);        \
+          cacc[C][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].y, bf0[4 * q + 1], cacc[C][0], 0, 0, 0);    \
+          cacc[C][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].y, bf1[4 * q + 1], cacc[C][1], 0, 0, 0);    \
+          cacc[C][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].z, bf0[4 * q + 2], cacc[C][0], 0, 0, 0);    \
+          cacc[C][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].z, bf1[4 * q + 2], cacc[C][1], 0, 0, 0);    \
+          cacc[C][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].w, bf0[4 * q + 3], cacc[C][0], 0, 0, 0);    \
+          cacc[C][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].w, bf1[4 * q + 3], cacc[C][1], 0, 0, 0);    \
+        }                                                                                                    \
+      }                                                                                                      \
+      __builtin_amdgcn_sched_barrier(0);
+  // one entry: the next entry's weight tile goes to the idle fragment set, the A fragments of its first two tiles are requested
+  // under this entry's last MFMA groups (backbone_kernel's B2_ENTRY4 / B2_ENTRY2 without the schedule word)
+#define SG_ENTRY(BC, BN)                                                                                     \
+    { const int nxt = it + 1 < 36 ? it + 1 : it;                                                             \
+      const float bf0[8] = {BC[0].x, BC[0].y, BC[0].z, BC[0].w, BC[1].x, BC[1].y, BC[1].z, BC[1].w};         \
+      const float bf1[8] = {BC[2].x, BC[2].y, BC[2].z, BC[2].w, BC[3].x, BC[3].y, BC[3].z, BC[3].w};         \
+      { const float* src = wsrc + (size_t)nxt * BB_C * CH;                                                   \
+        BN[0] = *reinterpret_cast<const float4*>(src);                                                       \
+        BN[1] = *reinterpret_cast<const float4*>(src + 4);                                                   \
+        BN[2] = *reinterpret_cast<const float4*>(src + 16 * CH);                                             \
+        BN[3] = *reinterpret_cast<const float4*>(src + 16 * CH + 4);                                         \
+      }                                                                                                      \
+      const int dbytes = SG_DBYTES(it), dbytes2 = SG_DBYTES(nxt);                                            \
+      if (NC == 4) {                                                                                         \
+        SG_MM(0, ua)                                                                                         \
+        SG_ALOAD(2, ua, dbytes)                                                                              \
+        SG_MM(1, ub)                                                                                         \
+        SG_ALOAD(3, ub, dbytes)                                                                              \
+        SG_MM(NC - 2, ua)                                                                                    \
+        SG_ALOAD(0, ua, dbytes2)                                                                             \
+        SG_MM(NC - 1, ub)                                                                                    \
+        SG_ALOAD(1, ub, dbytes2)                                                                             \
+      } else {                                                                                               \
+        SG_MM(0, ua)                                                                                         \
+        SG_ALOAD(0, ua, dbytes2)                                                                             \
+        SG_MM(1, ub)                                                                                         \
+        SG_ALOAD(1, ub, dbytes2)                                                                             \
+      }                                                                                                      \
+      ++it; }
+  float4 ua[2], ub[2];
+  SG_ALOAD(0, ua, SG_DBYTES(0))
+  SG_ALOAD(1, ub, SG_DBYTES(0))
+  for (int it = 0; it < 36;) {
+    SG_ENTRY(bA, bB)
+    SG_ENTRY(bB, bA)
+  }
+#undef SG_ENTRY
+#undef SG_MM
+#undef SG_ALOAD
+#undef SG_DBYTES
+
+  float* dst = pl0 + (size_t)cl * pl_stride;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    if (c >= nown) continue;
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int row = r0 + 16 * (c + 1) + 4 * g + e;
+        if (row < L) dst[row * BB_C + col0 + 16 * ct] = fmaxf(cacc[c][ct][e], 0.0f) + f[c + 1][ct][e];   // relu(conv + b) + f
+      }
+  }
+#undef SEG_LIVE
+}
 
 // ------------------------------------------- gradient of the backbone with respect to its one-hot input, ONE launch (round 5) ----
 // The gradient-guidance baseline (DPS, reference diffusion_gosai.py:1321-1330 through models/dnaconv.py:212-247) needs
@@ -2847,6 +3171,7 @@ extern "C" int svdd_backbone_cnn_save_f32(const uint8_t* x, const float* table0,
   a.x = x; a.table0 = table0; a.tiles = tiles; a.vec = vec; a.w2 = w2; a.out = out;
   a.n = n; a.L = L; a.spt = 1; a.nl = nlayers; a.count = nullptr; a.row_idx = nullptr; a.out_scatter = 0;
   a.auto_spt = 0; a.ncu = svdd_internal_num_cus(); a.plan = SvddTilePlan{1, 0, 1};
+  a.planes = nullptr; a.planes_P = 0;
   for (int i = 0; i < BB_MAXL; ++i) a.dil[i] = i < nlayers ? dilations[i] : 1;
   for (int i = 0; i < nlayers; ++i) if (dilations[i] <= 0) return SVDD_E_ARG;
   const size_t lds = sizeof(float) * ((size_t)(TW_ROWS + 2) * BB_AP + 9 * 5 * (size_t)BB_C + 8 * (size_t)TW_ROWS +
@@ -2890,6 +3215,7 @@ extern "C" int svdd_backbone_cnn_f32(const uint8_t* x, const float* table0, cons
   a.x = x; a.table0 = table0; a.tiles = tiles; a.vec = vec; a.w2 = w2; a.out = out;
   a.n = n; a.L = L; a.spt = TW_ROWS / L; a.nl = nlayers; a.count = count; a.row_idx = row_idx; a.out_scatter = out_scatter;
   a.auto_spt = 0; a.ncu = svdd_internal_num_cus();
+  a.planes = nullptr; a.planes_P = 0;
   unsigned nwg = (unsigned)((n + a.spt - 1) / a.spt);
   a.plan = SvddTilePlan{a.spt, 0, a.spt};                // every tile full (one sequence per tile: never read)
   if (a.spt > 1 && g_fixed_spt <= 0) {                   // several sequences fit a tile: which tile takes how many (svdd_spt.h)
@@ -2942,6 +3268,50 @@ extern "C" int svdd_backbone_cnn_f32(const uint8_t* x, const float* table0, cons
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(backbone_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipExtLaunchKernelGGL(backbone_kernel<false>, grid, dim3(512), lds, (hipStream_t)stream, e0, e1, 0, a, BackboneSave{});
   }
+  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+}
+
+extern "C" int svdd_backbone_incr_f32(const uint8_t* x, const float* table0, const float* tiles, const float* vec, const float* w2,
+                                      float* out, int n, int L, int nlayers, const int* dilations, int lead, float* planes,
+                                      uint8_t* x_prev, int32_t* items, unsigned long long* stat, int first, int max_item,
+                                      void* on_stream) {
+  if (!x || !table0 || !tiles || !vec || !w2 || !out || !dilations || !planes || !x_prev || !items || n <= 0 || L <= TW_ROWS / 2 ||
+      L > TW_ROWS || nlayers <= 0 || nlayers > BB_MAXL || lead < 2 || lead > nlayers || (max_item != 2 && max_item != 4))
+    return SVDD_E_ARG;
+  for (int i = 0; i < nlayers; ++i) if (dilations[i] <= 0 || (i < lead && dilations[i] != 1)) return SVDD_E_ARG;
+  BackboneArgs a;
+  a.x = x; a.table0 = table0; a.tiles = tiles; a.vec = vec; a.w2 = w2; a.out = out;
+  a.n = n; a.L = L; a.spt = 1; a.nl = nlayers; a.count = nullptr; a.row_idx = nullptr; a.out_scatter = 0;
+  a.auto_spt = 0; a.ncu = svdd_internal_num_cus(); a.plan = SvddTilePlan{1, 0, 1};
+  a.planes = planes; a.planes_P = lead;
+  for (int i = 0; i < BB_MAXL; ++i) a.dil[i] = i < nlayers ? dilations[i] : 1;
+  const size_t lds = sizeof(float) * ((size_t)(TW_ROWS + 2) * BB_AP + 9 * 5 * (size_t)BB_C + 8 * (size_t)TW_ROWS +
+                                      3 * (size_t)TW_ROWS + BB_MAXL + 1 + (size_t)(nlayers + 1) * 36);
+  hipEvent_t e0, e1;
+  svdd_internal_timed_events(6, &e0, &e1);               // ONE span per forward over all its launches
+  hipStream_t st = (hipStream_t)on_stream;
+  if (first) {                                            // the whole forward, which also fills the planes; the tokens become the carried ones
+    if (hipMemcpyAsync(x_prev, x, (size_t)n * L, hipMemcpyDeviceToDevice, st) != hipSuccess) return SVDD_E_LAUNCH;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(backbone_kernel<true, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipExtLaunchKernelGGL((backbone_kernel<true, false, 1>), dim3((unsigned)n), dim3(512), lds, st, e0, e1, 0, a, BackboneSave{});
+    return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  }
+  hipExtLaunchKernelGGL(backbone_worklist_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, e0, nullptr, 0, x, x_prev, n, L,
+                        lead, max_item, items, stat);
+  BackboneSegArgs sa{x, table0, tiles, vec, planes, items, n, L, 0};
+  const int rows = 16 * (max_item + 2);
+  const size_t slds = sizeof(float) * ((size_t)rows * BB_AP + 5 * (size_t)rows + rows + 8);
+  const dim3 sgrid((unsigned)n * SEG_SLOTS);
+  (void)hipFuncSetAttribute(max_item == 4 ? reinterpret_cast<const void*>(backbone_seg_kernel<4>) : reinterpret_cast<const void*>(backbone_seg_kernel<2>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)slds);
+  for (int k = 1; k <= lead; ++k) {
+    sa.layer = k;
+    if (max_item == 4) hipLaunchKernelGGL(backbone_seg_kernel<4>, sgrid, dim3(256), slds, st, sa);
+    else hipLaunchKernelGGL(backbone_seg_kernel<2>, sgrid, dim3(256), slds, st, sa);
+  }
+  if (hipGetLastError() != hipSuccess) return SVDD_E_LAUNCH;
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(backbone_kernel<true, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipExtLaunchKernelGGL((backbone_kernel<true, false, 2>), dim3((unsigned)n), dim3(512), lds, st, nullptr, e1, 0, a, BackboneSave{});
   return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
 }
 

@@ -54,6 +54,13 @@ Engine knobs (attributes; defaults reproduce the reference's observable behaviou
   logits_cache     "auto" (default): SVDD-MC keeps a per-row logits cache when several sequences share a backbone tile
                    (L <= 104; at L = 200 one workgroup owns one sequence and skipping rows frees CUs but saves no
                    time); "on" / "off". (SVDD-PM always carries the selected candidate's logits forward.)
+  incremental_backbone  "auto" (default): the SVDD-MC skipping loop at 104 < L <= 208 (one sequence per backbone tile, fp32, CNN backbone
+                   with a leading run of dilation-1 layers, more than 128 rows) carries the residual stream behind those layers
+                   across the steps and recomputes, per step, only the 16-row tiles a changed token can reach
+                   (svdd_backbone_incr_f32; the remaining layers run from the last carried plane). Same logits bit for bit
+                   (tests/test_backbone_incremental_gpu.py). "on": wherever the kernels apply, whatever the batch; "off". Off under
+                   graph capture. The first forward of such a decode runs on all B rows (it fills the planes): dedup_prior does not
+                   apply to it.
   dedup_prior      True (default): every row of the prior x_T is the same all-MASK row (_sample_prior, :751-753), and with the hand-written
                    kernels a row's net output does not depend on the batch around it — so the FIRST backbone forward of a decode, the
                    parents' first value / reward score and their first tower pass run on one row and are broadcast. Bit-identical to
@@ -241,6 +248,7 @@ class Diffusion(nn.Module):
         self._dps_hard_onehot, self._dps_raw_logits, self._dps_logp = False, None, None
         self.dps_single_forward = False  # DPS opt-in: q_xs from the differentiable pass's log-probs, not from a second backbone forward per step
         self.logits_cache = "auto"
+        self.incremental_backbone = "auto"
         self.skip_stats = None
         self.skip_generic = False
         self.trace = None          # set to a list to record (logits, scores) of every step (tests / smoke)
@@ -1051,6 +1059,18 @@ class Diffusion(nn.Module):
         (L <= 104) — at L = 200 one workgroup owns one sequence and skipping rows frees CUs but saves no time."""
         return self.logits_cache == "on" or (self.logits_cache == "auto" and 208 // L >= 2)
 
+    def _incremental_stem(self, B, L):
+        """(FusedBackbone, its carried-stem state for this decode) where the SVDD-MC skipping loop forwards through
+        svdd_backbone_incr_f32 (see incremental_backbone), else (None, None)."""
+        if self.incremental_backbone not in ("auto", "on", "off"):
+            raise ValueError(f"incremental_backbone = {self.incremental_backbone!r}: expected 'auto', 'on' or 'off'")
+        if self.incremental_backbone == "off" or _capturing():
+            return None, None
+        fb = self._fused_backbone_or_none(L)
+        if fb is None or not fb.incremental_ok(B, L, any_batch=self.incremental_backbone == "on"):
+            return None, None
+        return fb, fb.incremental_stem(B, L)
+
     def _controlled_sample_skipping(self, fn, x, cand, onehot, sched, B, L, S, M):
         """SVDD-MC with exact work-skipping (same tokens as the plain loop, bit for bit). 104 < L <= 208 (one sequence per
         tile): the value net's tower also shares the parent's rows (candidate_scores_compact); shorter sequences: the
@@ -1068,6 +1088,10 @@ class Diffusion(nn.Module):
         share = hasattr(fn, "candidates_ok") and fn.candidates_ok(L, M)
         toks_c = None if share else torch.empty((B * M, L), dtype=torch.uint8, device=self.device)
         logits = None
+        inc, stem = (None, None) if fb is not None else self._incremental_stem(B, L)
+        if stem is not None:
+            stem.stat.zero_()
+            stem.forwards = 0
         # the two-part late steps adapt to the decode in hand: the live count of a step is copied to pinned host memory without
         # waiting; a later step looks at the newest count that has arrived (a trained value net, another M or L, another chip change
         # when the live candidates outgrow one GRU round — the fixed "last 20 % of the steps" of rounds 4-5 fitted random-init nets)
@@ -1077,7 +1101,9 @@ class Diffusion(nn.Module):
             live_ev, live_pending, live_last = torch.cuda.Event(), False, 0
             late_thr = 0.97 * fn.gru_round_rows()
         for i in range(S):
-            if fb is None or logits is None:
+            if inc is not None:                                               # only the stem tiles the last select's tokens reach
+                logits = inc.forward_incremental(x, stem, out=logits)
+            elif fb is None or logits is None:
                 logits = self._prior_logits(x) if i == 0 else self._backbone_logits(x)
             else:                                                             # only the rows the last select changed
                 ops.compact_flags(ws.changed, ws.row_idx, ws.row_slot, ws.row_count)
@@ -1108,7 +1134,14 @@ class Diffusion(nn.Module):
                 self._record(logits, self._dense_scores(sc, ws, B, M), x)
             x = self._select_compact(sc, ws, cand, i)
         self._finish_stats(ws, B, M, S, "mc")
-        return self._noise_removal(x)
+        if inc is None:
+            return self._noise_removal(x)
+        if self.config.sampling.noise_removal:
+            logits = inc.forward_incremental(x, stem, out=logits)
+        if self.skip_stats is not None:                                       # executed work of the carried stem, of what the one-launch kernel runs
+            self.skip_stats.update(backbone_stem_tile_layers=int(stem.stat),
+                                   backbone_stem_tile_layers_dense=stem.forwards * B * ((L + 15) // 16) * stem.lead)
+        return self._noise_removal(x, logits=logits)
 
     def _controlled_sample_generic_skipping(self, fn, x, cand, onehot, sched, B, L, S, M):
         """SVDD-MC work-skipping for an opaque value function: live candidates gathered into a smaller batch (its size is

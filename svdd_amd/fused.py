@@ -414,6 +414,50 @@ def backbone_cnn(tokens, pk, count=None, out=None, row_idx=None, scatter=False):
     return out
 
 
+INCR_MAX_ITEM = 2          # row tiles per work item of the incremental stem (2 or 4; tools/incremental_backbone_ab.py measures both)
+
+
+def leading_dilation1(dil):
+    """Length of the leading run of dilation-1 layers (the stem svdd_backbone_incr_f32 carries across steps)."""
+    n = 0
+    while n < len(dil) and dil[n] == 1:
+        n += 1
+    return n
+
+
+class IncrementalStem:
+    """Caller-owned state of svdd_backbone_incr_f32 for n sequences of length L: the carried planes, the tokens they belong to, the
+    step's work list and the device counter of marked tile-layers. Allocated once and reused across decodes (FusedBackbone keeps
+    one per shape); `valid` says whether planes / x_prev describe the tokens of the last forward of THIS decode."""
+
+    def __init__(self, n, L, lead, dev):
+        self.n, self.L, self.lead = n, L, lead
+        self.planes = torch.empty((lead, n, 208, 128), dtype=torch.float32, device=dev)
+        self.x_prev = torch.empty((n, L), dtype=torch.uint8, device=dev)
+        self.items = torch.zeros((lead, n, 7), dtype=torch.int32, device=dev)
+        self.stat = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.valid = False
+        self.forwards = 0                                # incremental (not first) forwards since the counter was last read
+
+
+def backbone_cnn_incremental(tokens, pk, st, out=None, max_item=None):
+    """backbone_cnn(tokens, pk) — the same bits — through the carried stem `st` (HIP entry svdd_backbone_incr_f32): the first call
+    after st.valid = False runs the whole forward and fills the planes, every later one recomputes only the tiles of the leading
+    dilation-1 layers that a changed token can reach, then the remaining layers from the last plane."""
+    assert tokens.is_cuda and tokens.dtype == torch.uint8 and tokens.is_contiguous() and tuple(tokens.shape) == (st.n, st.L)
+    n, L = tokens.shape
+    if out is None:
+        out = torch.empty((n, L, 5), dtype=torch.float32, device=tokens.device)
+    dil = (ctypes.c_int * len(pk["dil"]))(*pk["dil"])
+    first = not st.valid
+    _lib.call("svdd_backbone_incr_f32", tokens, pk["table0"], pk["tiles"], pk["vec"], pk["w2"], out, n, L, len(pk["dil"]), dil,
+              st.lead, st.planes, st.x_prev, st.items, st.stat, int(first), int(max_item or INCR_MAX_ITEM),
+              ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))      # this entry takes its stream as an explicit argument
+    st.valid = True
+    st.forwards += 0 if first else 1
+    return out
+
+
 LP_DTYPES = {"f16x3": (torch.float16, 2), "bf16x3": (torch.bfloat16, 2), "f16": (torch.float16, 1), "bf16": (torch.bfloat16, 1)}
 
 
@@ -1031,6 +1075,7 @@ class FusedBackbone(nn.Module):
         self._cnn = (cnn,)
         self._lp = {}
         self._grad_pack = None
+        self._incr = {}
         if self.one_launch:
             pk = pack_backbone(cnn)
             self.ol_dil = pk.pop("dil")
@@ -1058,6 +1103,26 @@ class FusedBackbone(nn.Module):
         """True when a forward of length-L sequences is the one-launch kernel (the work-skipping paths need it: they
         hand it compacted batches whose size only the device knows)."""
         return self.one_launch and self.use_one_launch and L <= 208 and self.min_tiles_one_launch == 0
+
+    def incremental_ok(self, n, L, any_batch=False):
+        """True where a decode's forwards may go through the carried stem (svdd_backbone_incr_f32): the fp32 one-launch kernel, one
+        sequence per tile, a leading run of at least two dilation-1 layers — and a batch that the one-workgroup-per-sequence
+        kernel takes whole (small batches and tail rounds run on several workgroups per sequence instead; any_batch: whatever n)."""
+        return (self.kernel_ok(L) and self.precision == "f32" and 104 < L <= 208 and leading_dilation1(self.ol_dil) >= 2 and
+                (any_batch or (n > BB_SPLIT_MAX_SEQ and not 0 < n % 256 <= BB_SPLIT_MAX_SEQ)))
+
+    def incremental_stem(self, n, L):
+        """The resident IncrementalStem for [n, L] on this module's device, marked stale (a new decode starts)."""
+        key = (n, L, self.ol_tiles.device)
+        st = self._incr.get(key)
+        if st is None:
+            self._incr.clear()                          # one shape at a time: the planes are ~0.85 MB per sequence
+            st = self._incr[key] = IncrementalStem(n, L, leading_dilation1(self.ol_dil), self.ol_tiles.device)
+        st.valid = False
+        return st
+
+    def forward_incremental(self, tok, st, out=None):
+        return backbone_cnn_incremental(tok, self.ol_pack(), st, out)
 
     def _lp_pack(self):
         """Operand images of svdd_backbone_cnn_lp for self.precision (packed on first use)."""
