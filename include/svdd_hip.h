@@ -598,13 +598,18 @@ int svdd_abi_version(void);
  *                            windows of level d in ascending order (level 0: one per position that differs, +- halo, windows that
  *                            touch merged, the last slot takes what is left; deeper: windows within 4 rows merged; wlen 0: unused
  *                            slot, and for c >= count), seg[.] = its compact rows (wlen, + 4 context rows for d >= 1).
+ *                            Every one of the depth x n x slots entries of the three tables is written: the used slots come first, an
+ *                            unused slot has w0 = wlen = seg = 0, and so has every slot of a candidate c >= count. Two windows of a
+ *                            level >= 1 are MORE than 4 rows apart, so their segments (window + 2 context rows on each side) never
+ *                            overlap; level-0 windows do not touch. The window rows of a candidate and level add up to <= its length.
  * svdd_trunk_stem_unfold_win the stem operand of the window rows: the r-th window row of candidate c at compact row off[c slots] + r
  *                            (off = exclusive prefix sum of seg over [n slots]).
  * svdd_trunk_attn_pool_win   x, logits fp32 (compact rows of a level of length L; the segment of slot s starts at off[s], its window
  *                            in_halo rows further) -> the next GEMM's operand planes: pooled window rows where a window covers the
  *                            pair, else the row of the parent's planes [., L/2 + 2, C] (zeros outside the sequence). v0 == NULL:
  *                            whole sequences [n, L/2 + 2, C], pad rows zero; else the compact segments of the next level: rows
- *                            v0[s] - 2 .. v0[s] + vlen[s] + 1 at off2[s].
+ *                            v0[s] - 2 .. v0[s] + vlen[s] + 1 at off2[s] (an even L only). Of x / logits only window rows are ever read:
+ *                            never a segment's context rows, never a row between two segments. Candidates c >= count write nothing.
  */
 int svdd_trunk_gemm(const void* a_hi, const void* a_lo, const void* w, const float* bias, const float* resid, float* out,
                     int M, int N, int Cin, int T, int lda, int ldo, int act, const int32_t* count, int rows_per_seq,

@@ -168,6 +168,35 @@ def test_argument_validation_without_gpu():
     assert L.svdd_trunk_stem_unfold_win(None, 1, 200, 4, one, one, one, one, None, None) == _lib.E_ARG
     assert L.svdd_trunk_attn_pool_win(one, one, 1, 200, 768, 0, 4, one, one, one, one, 1, one, None, None, one, one, None, None, 0, None, None, None,
                                       None) == _lib.E_ARG                  # lo plane without the parent's lo plane
+    # the remaining refusals of the three shared-level entries (svdd_trunk.hip): each call differs from an accepted one in one argument
+    def windows(div=1, n=4, L=200, halo=7, depth=1, slots=4, ptrs=(one,) * 6):
+        return L_.svdd_trunk_windows(*ptrs[:3], div, n, L, halo, depth, slots, None, *ptrs[3:], None)
+
+    def unfold_win(n=1, L=200, slots=4, ptrs=(one,) * 5):
+        return L_.svdd_trunk_stem_unfold_win(ptrs[0], n, L, slots, *ptrs[1:4], ptrs[4], None, None)
+
+    def pool_win(n=1, L=200, C=768, in_halo=0, slots=4, div=1, parent_lo=None, out_lo=None, scale=None, shift=None, post_act=0,
+                 v0=None, vlen=None, off2=None, ptrs=(one,) * 8):
+        x, lg, w0, wlen, off, pidx, parent_hi, out_hi = ptrs
+        return L_.svdd_trunk_attn_pool_win(x, lg, n, L, C, in_halo, slots, w0, wlen, off, pidx, div, parent_hi, parent_lo, None, out_hi, out_lo,
+                                           scale, shift, post_act, v0, vlen, off2, None)
+    L_ = L
+    for kw in (dict(slots=0), dict(slots=-1), dict(depth=0), dict(depth=9), dict(div=0), dict(div=-2), dict(n=0), dict(L=0), dict(L=257),
+               dict(halo=-1), dict(L=100, depth=4), dict(L=30, depth=3)):
+        assert windows(**kw) == _lib.E_ARG, kw
+    for k in range(6):
+        assert windows(ptrs=tuple(None if i == k else one for i in range(6))) == _lib.E_ARG, k
+    for kw in (dict(slots=0), dict(slots=5), dict(n=0), dict(L=0)):
+        assert unfold_win(**kw) == _lib.E_ARG, kw
+    for k in range(5):
+        assert unfold_win(ptrs=tuple(None if i == k else one for i in range(5))) == _lib.E_ARG, k
+    for kw in (dict(C=6), dict(C=0), dict(slots=0), dict(slots=5), dict(div=0), dict(in_halo=-1), dict(n=0), dict(L=0), dict(post_act=3),
+               dict(post_act=-1), dict(scale=one), dict(shift=one), dict(v0=one), dict(v0=one, vlen=one), dict(v0=one, off2=one),
+               dict(vlen=one), dict(off2=one), dict(vlen=one, off2=one), dict(out_lo=one), dict(parent_lo=one),
+               dict(L=201, v0=one, vlen=one, off2=one)):
+        assert pool_win(**kw) == _lib.E_ARG, kw
+    for k in range(8):
+        assert pool_win(ptrs=tuple(None if i == k else one for i in range(8))) == _lib.E_ARG, k
     assert L.svdd_bb_layer_fwd_f32(None, None, None, None, None, None, 1e-5, None, None, None, 1, 1, 128, None) == _lib.E_ARG
     assert L.svdd_bb_layer_fwd_f32(one, one, one, None, None, None, 1e-5, one, one, None, 1, 1, 96, None) == _lib.E_ARG    # channels not 64 / 128 / 256
     assert L.svdd_bb_layer_bwd_f32(one, one, one, one, 1e-5, one, one, one, None, 1, 1, 128, None) == _lib.E_ARG          # mask without its output

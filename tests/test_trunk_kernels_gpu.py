@@ -5,7 +5,12 @@ The element-wise kernels (act_split, layernorm_split, attn_pool, attn_small, ste
 format only in the store: the fp32-plane instantiation (SVDD_OPT_TRUNK_PLANES_F32) is compared with float64, and the bf16
 instantiations must then store exactly hi = bf16(v), lo = bf16(v - hi) of that fp32 result v (one-pass bf16: hi only). Every
 kernel that takes a live count must leave the rows beyond it untouched (sentinel-filled buffers), and its live rows must be
-the bits of the same call without a count. Bars: 2 - 4x the worst case measured on the MI355X, quoted beside each."""
+the bits of the same call without a count. Bars: 2 - 4x the worst case measured on the MI355X, quoted beside each.
+
+The three entries behind "first levels shared between a candidate and its parent" (svdd_trunk_windows, _stem_unfold_win,
+_attn_pool_win) are held to the integer restatement tests/trunk_ref.py windows_ref (proved against the dependency cone and the
+float64 tower in tests/test_trunk_ref_cpu.py) and, bit for bit, to the whole-sequence kernels above, on one case table
+(trunk_ref.WINDOW_CASES). What a wrong index does to them: profiles/trunk_windows_teeth.txt."""
 import contextlib
 
 import numpy as np
@@ -15,6 +20,7 @@ import torch
 from svdd_amd import _lib
 from svdd_amd.enformer_value import _positional_features
 from svdd_amd.fused_trunk import GUARD, TAIL, pack_gemm_weight, pack_gemm_weight_f32
+from tests import trunk_ref as R
 from tests.trunk_ref import act as act_ref, attn_small_ref
 
 pytestmark = pytest.mark.gpu
@@ -453,3 +459,236 @@ def test_gemm_against_fp64(case):
                 up = bp.untouched()
                 assert bool(up[m_live:].all())
                 assert torch.equal(bp.bits()[:m_live], bf.bits()[:m_live])
+
+
+# ------------------------------------------------------------------------------------------------------------ shared-level windows
+def _i32(a):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32).reshape(-1)).to(DEV)
+
+
+def _count(count):
+    ct = None if count is None else torch.tensor([count], dtype=torch.int32, device=DEV)
+    return ct, None if ct is None else ct.data_ptr()
+
+
+@pytest.mark.parametrize("case", R.WINDOW_CASES, ids=R.window_case_id)
+def test_trunk_windows_exact(case):
+    """svdd_trunk_windows: w0, wlen, seg equal trunk_ref.windows_ref in all depth x n x slots entries (unused slots and candidates
+    beyond the live count: zeros), every entry written, nothing around the tables written, a second launch the same bits.
+    Teeth (profiles/trunk_windows_teeth.txt): the next level's window end one pair short -> 37 cases red, a level-0 window one row
+    short of an odd position's reach -> 48; both also moved the end-to-end scores of tests/test_trunk_gpu.py. Deeper windows joined
+    within 2 rows instead of 4 -> 17 red here and nothing red there (the result stays exact: only this test holds the rule)."""
+    L, depth, slots, halo, count, perm = case
+    cand, parent, pidx, div, edits = R.window_case_tokens(case)
+    n = len(cand)
+    cg, pg, ig = torch.from_numpy(cand).to(DEV), torch.from_numpy(parent).to(DEV), torch.from_numpy(pidx).to(DEV)
+    ct, cp = _count(count)
+    want = R.windows_ref(cand, parent, pidx, div, L, halo, depth, slots, count)
+    lib = _lib.lib()
+    runs = []
+    for rep in range(2):
+        tabs = [_Buf(depth * n, slots, torch.float32) for _ in range(3)]                     # (int32 tables behind the fp32 sentinel)
+        _lib.check(lib.svdd_trunk_windows(cg.data_ptr(), pg.data_ptr(), ig.data_ptr(), div, n, L, halo, depth, slots, cp,
+                                          tabs[0].ptr, tabs[1].ptr, tabs[2].ptr, None), "svdd_trunk_windows")
+        torch.cuda.synchronize()
+        for buf in tabs:
+            assert not bool(buf.untouched().any())                                           # (asserts guard and tail rows too)
+        runs.append([buf.bits().cpu().numpy().reshape(depth, n, slots) for buf in tabs])
+    for name, got, again, ref in zip(("w0", "wlen", "seg"), runs[0], runs[1], want):
+        assert np.array_equal(got, ref), (name, np.argwhere(got != ref)[:4].tolist())
+        assert np.array_equal(got, again), name
+        if count is not None:
+            assert not got[:, count:].any()
+    assert want[1].any() == (count != 0)
+
+
+STEM_WIN_CASES = sorted({(L, 1, slots, halo, count, perm) for L, _, slots, halo, count, perm in R.WINDOW_CASES},
+                        key=lambda c: (c[0], c[2], c[3], -1 if c[4] is None else c[4], c[5]))
+
+
+@pytest.mark.parametrize("case", STEM_WIN_CASES, ids=R.window_case_id)
+def test_stem_unfold_win_exact(case):
+    """svdd_trunk_stem_unfold_win on the tables of windows_ref (off = exclusive prefix sum of the level-0 seg): compact row
+    off[c slots] + r is, bit for bit, the row svdd_trunk_stem_unfold writes for the r-th window row of candidate c, and the
+    brute-force one-hot unfold of test_stem_unfold_exact; the buffer holds the window rows and the tail, not n L rows; with a
+    live count (the tables still those of all candidates) the rows of the candidates beyond it stay untouched.
+    Teeth: the slot walk without `r -= wl` -> 16 of the 29 cases red (so is the end-to-end test)."""
+    L, _, slots, halo, count, perm = case
+    cand, parent, pidx, div, edits = R.window_case_tokens(case)
+    n = len(cand)
+    w0, wlen, seg = (t[0] for t in R.windows_ref(cand, parent, pidx, div, L, halo, 1, slots))
+    off, total = R.compact_offsets(seg)
+    live = n if count is None else count
+    live_total = total if live >= n else int(off[live * slots])
+    ref = np.zeros((n, L, 64), dtype=np.float32)
+    for b in range(n):
+        for l in range(L):
+            for t in range(15):
+                p = l + t - 7
+                if 0 <= p < L and cand[b, p] < 4:
+                    ref[b, l, 4 * t + cand[b, p]] = 1.0
+    src, dst, pos = [], [], []
+    for c in range(live):
+        r = 0
+        for j in range(slots):
+            for q in range(int(w0[c, j]), int(w0[c, j] + wlen[c, j])):
+                src.append(c * (L + 2) + q)
+                dst.append(int(off[c * slots]) + r)
+                pos.append((c, q))
+                r += 1
+    assert dst == list(range(live_total)) and total <= n * L
+    src_t = torch.tensor(src, dtype=torch.long, device=DEV)
+    want = torch.from_numpy(np.stack([ref[c, q] for c, q in pos]) if pos else np.zeros((0, 64), dtype=np.float32)).to(DEV)
+    cg = torch.from_numpy(cand).to(DEV)
+    w0g, wlg, ofg = _i32(w0), _i32(wlen), _i32(off)
+    ct, cp = _count(count)
+    lib = _lib.lib()
+    for mode in ("f32", "bf16"):
+        dt = torch.float32 if mode == "f32" else torch.bfloat16
+        dense, out = _Buf(n * (L + 2), 64, dt), _Buf(total, 64, dt)
+        with _planes(mode):
+            _lib.check(lib.svdd_trunk_stem_unfold(cg.data_ptr(), n, L, dense.ptr, None, None), "svdd_trunk_stem_unfold")
+            _lib.check(lib.svdd_trunk_stem_unfold_win(cg.data_ptr(), n, L, slots, w0g.data_ptr(), wlg.data_ptr(), ofg.data_ptr(), out.ptr,
+                                                      cp, None), "svdd_trunk_stem_unfold_win")
+            torch.cuda.synchronize()
+        u = out.untouched()
+        assert bool(u[live_total:].all()) and not bool(u[:live_total].any())
+        assert torch.equal(out.bits()[:live_total], dense.bits()[src_t])
+        assert torch.equal(out.body()[:live_total].float(), want)
+    assert count == 0 or float(want.sum()) > 0
+
+
+def _pool64(x, lg, L):
+    """AttentionPool(2) of x, logits [n, L, C] in float64 -> [n, ceil(L / 2), C]; an odd L pools its last row alone."""
+    n, _, C = x.shape
+    Lo, ev = (L + 1) // 2, L // 2
+    out = torch.zeros(n, Lo, C, dtype=torch.float64, device=x.device)
+    if ev:
+        w = torch.softmax(lg[:, :2 * ev].reshape(n, ev, 2, C), dim=2)
+        out[:, :ev] = (x[:, :2 * ev].reshape(n, ev, 2, C) * w).sum(dim=2)
+    if L % 2:
+        out[:, Lo - 1] = x[:, L - 1]
+    return out
+
+
+# the pooling cases: every length at its greatest depth with 4 slots, 1 and 2 slots at L = 200 and at the short / odd-level lengths,
+# and the table's halo / count / permuted cases — each at every one of its levels
+_POOL_BASE = [c for c in R.WINDOW_CASES[:-8] if (c[2] == 4 and c[1] == max(k[1] for k in R.WINDOW_CASES if k[0] == c[0]))
+              or c[:3] in ((200, 4, 1), (200, 4, 2), (16, 4, 2), (30, 2, 1))]
+POOL_WIN_CASES = [(c, d) for c in _POOL_BASE + R.WINDOW_CASES[-8:] for d in range(c[1])]
+POOL_POSTS = [(True, 2), (True, 1), (True, 0), (False, 0)]
+
+
+@pytest.mark.parametrize("C", [8, 64])
+@pytest.mark.parametrize("case,d", POOL_WIN_CASES, ids=[f"{R.window_case_id(c)}-lv{d}" for c, d in POOL_WIN_CASES])
+def test_attn_pool_win(case, d, C):
+    """svdd_trunk_attn_pool_win at level d of a case (length L >> d; in_halo 0 at level 0, 2 below it), in the three plane modes,
+    with post scale / shift and post_act 0 / 1 / 2 and without. The compact input rows are gathered from dense random rows (one
+    candidate with equal logits, two with logit gaps of +-80 and +-1e4) with NaN in every context row and between the segments
+    (3 free rows behind each): never read. The parents' planes come from svdd_trunk_attn_pool on the parents' dense rows (the rows
+    behind the last parent hold the sentinel). Whole-sequence output: where a window covers the pair, the bits of
+    svdd_trunk_attn_pool on the candidate's dense rows; elsewhere the bits of row parent_idx[c] / div of the parents' planes; the
+    two pad rows zero; candidates beyond the live count untouched. Compact output (v0, vlen, off2 = the next level of the tables):
+    row off2[s] + r is position v0[s] - 2 + r of that result, zeros outside [0, Lo), nothing from the total on. The bf16 planes
+    are the exact split of the fp32 plane, and the fp32 plane is within 5e-7 of float64 (the bar of test_attn_pool_against_fp64;
+    measured: 2.2e-7). An odd length: whole output only, and v0 is refused with every buffer untouched.
+    Teeth: in_halo dropped from the source row -> 72 cases red (levels >= 1: level 0 has in_halo 0); the parent's row without
+    / div, or the parent of the neighbouring candidate -> 96 of the 112 cases red; the live count ignored -> all 24 cases with a
+    count red (the end-to-end test notices the first three, not the last)."""
+    L0, depth, slots, halo, count, perm = case
+    cand, parent, pidx, div, edits = R.window_case_tokens(case)
+    n, B = len(cand), len(parent)
+    tabs = R.windows_ref(cand, parent, pidx, div, L0, halo, depth, slots)                    # of all candidates: the count is the kernel's
+    L = L0 >> d
+    Lo, in_halo = (L + 1) // 2, 2 if d else 0
+    w0, wlen, seg = (t[d] for t in tabs)
+    off, total = R.compact_offsets(seg, gap=3)
+    live = n if count is None else count
+    par = pidx // div
+    g = torch.Generator(device="cpu").manual_seed(1000 * L0 + 10 * d + C)
+    x, lg = torch.randn(n, L, C, generator=g) * 2, torch.randn(n, L, C, generator=g) * 3
+    xp, lgp = torch.randn(B, L, C, generator=g) * 2, torch.randn(B, L, C, generator=g) * 3
+    sgn = torch.where(torch.rand(L, C, generator=g) < 0.5, -1.0, 1.0) * torch.where(torch.arange(L)[:, None] % 2 == 0, 1.0, -1.0)
+    lg[3], lg[10], lg[9] = 0.7, 0.5 * 80.0 * sgn, 0.5 * 1e4 * sgn                           # both ends / every position / spread
+    nan = float("nan")
+    xc = torch.cat([R.to_compact(x, w0, wlen, off, in_halo, total, nan), torch.full((4, C), nan)]).to(DEV)
+    lc = torch.cat([R.to_compact(lg, w0, wlen, off, in_halo, total, nan), torch.full((4, C), nan)]).to(DEV)
+    pad = lambda t: torch.cat([t, torch.full((t.shape[0], 2, C), nan)], dim=1).to(DEV)       # noqa: E731
+    xd, ld, xpd, lpd = pad(x), pad(lg), pad(xp), pad(lgp)
+    ps, pb = (1.0 + 0.3 * torch.randn(C, generator=g)).to(DEV), (0.2 * torch.randn(C, generator=g)).to(DEV)
+    # which output rows are pooled from the candidate's window rows, and the compact rows of the next level
+    cov = np.zeros((n, Lo + 2), dtype=bool)
+    for c in range(n):
+        for j in range(slots):
+            for q in range(int(w0[c, j]), int(w0[c, j] + wlen[c, j]), 2):
+                cov[c, q // 2] = True
+    rows = n * (Lo + 2)
+    is_pad = torch.from_numpy(np.tile(np.arange(Lo + 2) >= Lo, n)).to(DEV)
+    cov_t = torch.from_numpy(cov.reshape(-1)).to(DEV)
+    prow = torch.from_numpy((par[:, None].astype(np.int64) * (Lo + 2) + np.arange(Lo + 2)[None, :]).reshape(-1)).to(DEV)
+    compact = d + 1 < depth
+    if compact:
+        assert L % 2 == 0
+        v0, vlen, seg2 = (t[d + 1] for t in tabs)
+        off2, total2 = R.compact_offsets(seg2)
+        live2 = total2 if live >= n else int(off2[live * slots])
+        src2 = []
+        for c in range(n):
+            for j in range(slots):
+                if vlen[c, j] > 0:
+                    assert len(src2) == off2[c * slots + j]
+                    src2 += [c * (Lo + 2) + (i if 0 <= i < Lo else Lo) for i in range(int(v0[c, j]) - 2, int(v0[c, j] + vlen[c, j]) + 2)]
+        assert len(src2) == total2
+        src2 = torch.tensor(src2, dtype=torch.long, device=DEV)
+        v0g, vlg, o2g = _i32(v0), _i32(vlen), _i32(off2)
+    w0g, wlg, ofg, ig = _i32(w0), _i32(wlen), _i32(off), _i32(pidx)
+    ct, cp = _count(count)
+    lib = _lib.lib()
+    ref_x, ref_p = _pool64(xd[:, :L].double(), ld[:, :L].double(), L), _pool64(xpd[:, :L].double(), lpd[:, :L].double(), L)
+    for post, pact in POOL_POSTS:
+        sp, bp = (ps.data_ptr(), pb.data_ptr()) if post else (None, None)
+        whole, comp = {}, {}
+        for mode in MODES:
+            lo_of = lambda bufs: bufs[1].ptr if mode == "bf16x3" else None                  # noqa: E731
+            dense, pp = _planes_out(mode, rows, C), _planes_out(mode, rows, C)
+            whole[mode] = _planes_out(mode, rows, C)
+            with _planes(mode):
+                _lib.check(lib.svdd_trunk_attn_pool(xd.data_ptr(), ld.data_ptr(), n, L, C, None, None, dense[0].ptr, lo_of(dense),
+                                                    sp, bp, pact, None), "svdd_trunk_attn_pool")
+                _lib.check(lib.svdd_trunk_attn_pool(xpd.data_ptr(), lpd.data_ptr(), B, L, C, None, None, pp[0].ptr, lo_of(pp),
+                                                    sp, bp, pact, None), "svdd_trunk_attn_pool")
+                win = lambda out, nxt: lib.svdd_trunk_attn_pool_win(                        # noqa: E731
+                    xc.data_ptr(), lc.data_ptr(), n, L, C, in_halo, slots, w0g.data_ptr(), wlg.data_ptr(), ofg.data_ptr(), ig.data_ptr(), div,
+                    pp[0].ptr, lo_of(pp), cp, out[0].ptr, lo_of(out), sp, bp, pact, *nxt, None)
+                _lib.check(win(whole[mode], (None, None, None)), "svdd_trunk_attn_pool_win")
+                if compact:
+                    comp[mode] = _planes_out(mode, total2, C)
+                    _lib.check(win(comp[mode], (v0g.data_ptr(), vlg.data_ptr(), o2g.data_ptr())), "svdd_trunk_attn_pool_win")
+                elif L % 2:                                                                 # an odd length has no compact output
+                    rej = _planes_out(mode, rows, C)
+                    assert win(rej, (w0g.data_ptr(), wlg.data_ptr(), ofg.data_ptr())) == _lib.E_ARG
+                torch.cuda.synchronize()
+            if not compact and L % 2:
+                assert all(bool(b.untouched().all()) for b in rej if b is not None)
+            planes = range(2 if mode == "bf16x3" else 1)
+            lr = live * (Lo + 2)
+            for k in planes:
+                want = torch.where(cov_t[:, None], dense[k].bits(), pp[k].bits()[prow])
+                want[is_pad] = 0
+                assert torch.equal(whole[mode][k].bits()[:lr], want[:lr]), (mode, post, pact, k)
+                if compact:
+                    assert torch.equal(comp[mode][k].bits()[:live2], want[src2[:live2]]), (mode, post, pact, k)
+            assert bool(pp[0].untouched()[B * (Lo + 2):].all())
+        _check_split(whole, lr)
+        if compact:
+            _check_split(comp, live2)
+        if live:
+            t = [r * ps.double() + pb.double() if post else r for r in (ref_x, ref_p)]
+            t = [act_ref(r, pact) for r in t]
+            covl = torch.from_numpy(cov[:live, :Lo]).to(DEV)
+            ref = torch.where(covl[:, :, None], t[0][:live], t[1][torch.from_numpy(par[:live].astype(np.int64)).to(DEV)])
+            v = whole["f32"][0].body().view(n, Lo + 2, C)[:live, :Lo].double()
+            assert torch.isfinite(v).all()
+            err = float((v - ref).abs().max()) / float(ref.abs().max())
+            _report(f"attn_pool_win[{R.window_case_id(case)},{d},{C},{post},{pact}]", err, 5e-7)
+    assert cov[:live].any() == (live > 0)
