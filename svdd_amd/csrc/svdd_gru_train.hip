@@ -21,18 +21,14 @@
 // Backward, given dh' (output gradient of the step + recurrent gradient from the step after it in walking order):
 //   dn = dh' (1 - z) ; dz = dh' (h - n) ; da_n = dn (1 - n^2) ; da_r = da_n (W_hn h + b_hn) r (1 - r) ; da_z = dz z (1 - z)
 //   dx = W_ir^T da_r + W_iz^T da_z + W_in^T da_n ; dh = dh' z + W_hr^T da_r + W_hz^T da_z + W_hn^T (da_n r)
-#include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
-#include <stdint.h>
-
-#include "svdd_hip.h"
+#include "svdd_host.h"
 
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int H = 64;          // hidden = input width
-constexpr int TS = 16;         // sequences per workgroup (MFMA M)
+// TS = 16 sequences per workgroup (MFMA M): svdd_host.h, shared with the inference GRU of svdd_nets.hip
 constexpr int HPAD = H + 4;    // LDS row stride of the hidden state (floats)
 constexpr int DP = 3 * H + 4;  // LDS row stride of a gate-derivative matrix (floats): 196 = 4 mod 64 banks per row
 
@@ -683,8 +679,6 @@ __global__ __launch_bounds__(256) void gru_dx_gate_kernel(const float* __restric
 
 }  // namespace
 
-extern "C" void svdd_internal_timed_events(int k, hipEvent_t* e0, hipEvent_t* e1);   // svdd_kernels.hip (profiling)
-
 extern "C" {
 
 int svdd_bb_layer_fwd_f32(const float* y, const float* bias, const float* f_prev, const float* tb, const float* gamma,
@@ -693,16 +687,17 @@ int svdd_bb_layer_fwd_f32(const float* y, const float* bias, const float* f_prev
   if (!f_prev || rows <= 0 || rows_per_seq <= 0 || (y && (!bias || !f_out || !mask)) || (gamma && (!beta || !tb || !hn)) ||
       (!y && !gamma))
     return SVDD_E_ARG;
+  void (*kern)(BbFwdArgs);
+  switch (channels) {
+    case 64: kern = bb_layer_fwd_kernel<1>; break;
+    case 128: kern = bb_layer_fwd_kernel<2>; break;
+    case 256: kern = bb_layer_fwd_kernel<4>; break;
+    default: return SVDD_E_ARG;
+  }
   BbFwdArgs a{y, bias, f_prev, tb, gamma, beta, eps, f_out, mask, hn, rows, rows_per_seq};
   const int64_t nb = (rows + 3) / 4;
   const dim3 grid((unsigned)(nb < 8192 ? nb : 8192));
-  switch (channels) {
-    case 64: hipLaunchKernelGGL(bb_layer_fwd_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, a); break;
-    case 128: hipLaunchKernelGGL(bb_layer_fwd_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, a); break;
-    case 256: hipLaunchKernelGGL(bb_layer_fwd_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, a); break;
-    default: return SVDD_E_ARG;
-  }
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  return svdd_launch(kern, grid, dim3(256), 0, stream, a);
 }
 
 int svdd_bb_layer_bwd_f32(const float* g_hn, const float* f_in, const float* tb, const float* gamma, float eps, const float* g_in,
@@ -710,65 +705,57 @@ int svdd_bb_layer_bwd_f32(const float* g_hn, const float* f_in, const float* tb,
                           void* stream) {
   if (!g_hn || !f_in || !tb || !gamma || !g_in || !g_out || rows <= 0 || rows_per_seq <= 0 || ((gt_out == nullptr) != (mask_prev == nullptr)))
     return SVDD_E_ARG;
+  void (*kern)(BbBwdArgs);
+  switch (channels) {
+    case 64: kern = bb_layer_bwd_kernel<1>; break;
+    case 128: kern = bb_layer_bwd_kernel<2>; break;
+    case 256: kern = bb_layer_bwd_kernel<4>; break;
+    default: return SVDD_E_ARG;
+  }
   BbBwdArgs a{g_hn, f_in, tb, gamma, eps, g_in, mask_prev, g_out, gt_out, rows, rows_per_seq};
   const int64_t nb = (rows + 3) / 4;
   const dim3 grid((unsigned)(nb < 8192 ? nb : 8192));
-  switch (channels) {
-    case 64: hipLaunchKernelGGL(bb_layer_bwd_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, a); break;
-    case 128: hipLaunchKernelGGL(bb_layer_bwd_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, a); break;
-    case 256: hipLaunchKernelGGL(bb_layer_bwd_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, a); break;
-    default: return SVDD_E_ARG;
-  }
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  return svdd_launch(kern, grid, dim3(256), 0, stream, a);
 }
 
 int svdd_gru_bidir_train_f32(const float* x, const float* wpack, const float* bpack, float* out, float* save, int n, int L,
                              void* stream) {
   if (!x || !wpack || !bpack || !out || !save || n <= 0 || L <= 0) return SVDD_E_ARG;
-  hipEvent_t e0, e1;
-  svdd_internal_timed_events(11, &e0, &e1);
-  hipExtLaunchKernelGGL(gru_train_fwd_kernel, dim3(2 * (unsigned)((n + TS - 1) / TS)), dim3(256), 0, (hipStream_t)stream, e0, e1, 0,
-                        x, wpack, bpack, out, save, n, L);
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  SvddSpan span(SVDD_SLOT_GRU_TRAIN);
+  return svdd_launch_timed(span.all(), gru_train_fwd_kernel, dim3(2 * (unsigned)((n + TS - 1) / TS)), dim3(256), 0, stream, x,
+                           wpack, bpack, out, save, n, L);
 }
 
 int svdd_gru_bidir_bwd_f32(const float* grad_out, const float* out, const float* save, const float* wpack_bwd, float* dx, int n,
                            int L, void* stream) {
   if (!grad_out || !out || !save || !wpack_bwd || !dx || n <= 0 || L <= 0) return SVDD_E_ARG;
-  hipEvent_t e0, e1;
-  svdd_internal_timed_events(12, &e0, &e1);
-  hipExtLaunchKernelGGL(gru_bwd_kernel, dim3(2 * (unsigned)((n + TS - 1) / TS)), dim3(256), 0, (hipStream_t)stream, e0, e1, 0,
-                        grad_out, out, save, wpack_bwd, dx, n, L);
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  SvddSpan span(SVDD_SLOT_GRU_BPTT);
+  return svdd_launch_timed(span.all(), gru_bwd_kernel, dim3(2 * (unsigned)((n + TS - 1) / TS)), dim3(256), 0, stream, grad_out, out,
+                           save, wpack_bwd, dx, n, L);
 }
 
 int svdd_reward_stem_f32(const float* x, const float* w, const float* b, float* out, int n, int L, int taps, void* stream) {
   if (!x || !w || !b || !out || n <= 0 || L <= 0 || taps != 15) return SVDD_E_ARG;
   const int64_t rows = (int64_t)n * L;
   const unsigned grid = (unsigned)((rows + 3) / 4 < 4096 ? (rows + 3) / 4 : 4096);   // latency-bound per position: many short-lived waves beat few long-lived ones (512 workgroups: 49 -> 69 us)
-  hipEvent_t e0, e1;
-  svdd_internal_timed_events(5, &e0, &e1);
-  hipExtLaunchKernelGGL(reward_stem_fwd_kernel<15>, dim3(grid), dim3(256), 0, (hipStream_t)stream, e0, e1, 0, x, w, b, out, rows, L);
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  SvddSpan span(SVDD_SLOT_CONV_TOWER);
+  return svdd_launch_timed(span.all(), reward_stem_fwd_kernel<15>, dim3(grid), dim3(256), 0, stream, x, w, b, out, rows, L);
 }
 
 int svdd_reward_stem_bwd_f32(const float* g, const float* w, float* dx, int n, int L, int taps, void* stream) {
   if (!g || !w || !dx || n <= 0 || L <= 0 || taps != 15) return SVDD_E_ARG;
   const int64_t rows = (int64_t)n * L;
   const unsigned grid = (unsigned)((rows + 3) / 4 < 4096 ? (rows + 3) / 4 : 4096);
-  hipEvent_t e0, e1;
-  svdd_internal_timed_events(5, &e0, &e1);
-  hipExtLaunchKernelGGL(reward_stem_bwd_kernel<15>, dim3(grid), dim3(256), 0, (hipStream_t)stream, e0, e1, 0, g, w, dx, rows, L);
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  SvddSpan span(SVDD_SLOT_CONV_TOWER);
+  return svdd_launch_timed(span.all(), reward_stem_bwd_kernel<15>, dim3(grid), dim3(256), 0, stream, g, w, dx, rows, L);
 }
 
 int svdd_sum_gate_f32(const float* a, const float* b, const float* f, float* g, int64_t count, void* stream) {
   if (!a || !b || !f || !g || count <= 0 || (count & 3)) return SVDD_E_ARG;
   const int64_t n4 = count / 4;
   const unsigned grid = (unsigned)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
-  hipLaunchKernelGGL(sum_gate_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float4*>(a),
+  return svdd_launch(sum_gate_kernel, dim3(grid), dim3(256), 0, stream, reinterpret_cast<const float4*>(a),
                      reinterpret_cast<const float4*>(b), reinterpret_cast<const float4*>(f), reinterpret_cast<float4*>(g), n4);
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
 }
 
 int svdd_reward_tail_grad_f32(const float* h_fwd, const float* h_bwd, const float* w1, const float* b1, const float* gamma,
@@ -776,13 +763,10 @@ int svdd_reward_tail_grad_f32(const float* h_fwd, const float* h_bwd, const floa
   if (!h_fwd || !h_bwd || !w1 || !b1 || !gamma || !beta || !w_eff || !g_fwd || !g_bwd || n <= 0 || L <= 0) return SVDD_E_ARG;
   const int64_t rows = (int64_t)n * L;
   const size_t lds = sizeof(float) * (2 * 128 * 64 + 4 * 4 * 192);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(reward_tail_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   const unsigned grid = (unsigned)((rows + 15) / 16 < 512 ? (rows + 15) / 16 : 512);   // 4 waves x 4 rows per iteration; 2 workgroups per CU (76 KB of LDS each)
-  hipEvent_t e0, e1;
-  svdd_internal_timed_events(7, &e0, &e1);
-  hipExtLaunchKernelGGL(reward_tail_grad_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, e0, e1, 0, h_fwd, h_bwd, w1, b1, gamma, beta,
-                        w_eff, eps, 1.0f / ((float)n * (float)L), g_fwd, g_bwd, rows);
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  SvddSpan span(SVDD_SLOT_VALUE_TAIL);
+  return svdd_launch_timed(span.all(), reward_tail_grad_kernel, dim3(grid), dim3(256), svdd_lds_raised(lds), stream, h_fwd, h_bwd, w1, b1, gamma,
+                           beta, w_eff, eps, 1.0f / ((float)n * (float)L), g_fwd, g_bwd, rows);
 }
 
 int svdd_gru_bidir_train2_f32(const float* x, const float* wpack, const float* bpack, float* gi, float* out, float* save, int n, int L,
@@ -790,29 +774,25 @@ int svdd_gru_bidir_train2_f32(const float* x, const float* wpack, const float* b
   if (!x || !wpack || !bpack || !gi || !out || !save || n <= 0 || L <= 0) return SVDD_E_ARG;
   const int64_t rows = (int64_t)n * L;
   const int64_t tiles = (rows + 15) / 16;
-  hipEvent_t e0, e1;
-  svdd_internal_timed_events(11, &e0, &e1);                          // one timed span over both launches
-  hipExtLaunchKernelGGL(gru_xproj_kernel, dim3((unsigned)(tiles < 512 ? tiles : 512), 2), dim3(256), 0, (hipStream_t)stream, e0, nullptr, 0,
-                        x, wpack, bpack, gi, rows);
-  if (hipGetLastError() != hipSuccess) return SVDD_E_LAUNCH;
-  hipExtLaunchKernelGGL(gru_train_fwd2_kernel, dim3(2 * (unsigned)((n + TS - 1) / TS)), dim3(256), 0, (hipStream_t)stream, nullptr, e1, 0,
-                        (const float*)gi, wpack, bpack, out, save, n, L);
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  SvddSpan span(SVDD_SLOT_GRU_TRAIN);                          // one timed span over both launches
+  if (svdd_launch_timed(span.first(), gru_xproj_kernel, dim3((unsigned)(tiles < 512 ? tiles : 512), 2), dim3(256), 0, stream, x, wpack,
+                        bpack, gi, rows) != SVDD_OK)
+    return SVDD_E_LAUNCH;
+  return svdd_launch_timed(span.last(), gru_train_fwd2_kernel, dim3(2 * (unsigned)((n + TS - 1) / TS)), dim3(256), 0, stream,
+                           (const float*)gi, wpack, bpack, out, save, n, L);
 }
 
 int svdd_gru_bidir_bwd2_f32(const float* grad_out, const float* out, const float* save, const float* wpack_bwd, float* da, const float* gate,
                             float* g, int n, int L, void* stream) {
   if (!grad_out || !out || !save || !wpack_bwd || !da || !g || n <= 0 || L <= 0) return SVDD_E_ARG;
-  hipEvent_t e0, e1;
-  svdd_internal_timed_events(12, &e0, &e1);
-  hipExtLaunchKernelGGL(gru_bwd2_kernel, dim3(2 * (unsigned)((n + TS - 1) / TS)), dim3(256), 0, (hipStream_t)stream, e0, nullptr, 0,
-                        grad_out, out, save, wpack_bwd, da, n, L);
-  if (hipGetLastError() != hipSuccess) return SVDD_E_LAUNCH;
+  SvddSpan span(SVDD_SLOT_GRU_BPTT);                           // one timed span over both launches
+  if (svdd_launch_timed(span.first(), gru_bwd2_kernel, dim3(2 * (unsigned)((n + TS - 1) / TS)), dim3(256), 0, stream, grad_out, out,
+                        save, wpack_bwd, da, n, L) != SVDD_OK)
+    return SVDD_E_LAUNCH;
   const int64_t rows = (int64_t)n * L;
   const int64_t tiles = (rows + 15) / 16;
-  hipExtLaunchKernelGGL(gru_dx_gate_kernel, dim3((unsigned)(tiles < 1024 ? tiles : 1024)), dim3(256), 0, (hipStream_t)stream, nullptr, e1, 0,
-                        (const float*)da, wpack_bwd, gate, g, rows);
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  return svdd_launch_timed(span.last(), gru_dx_gate_kernel, dim3((unsigned)(tiles < 1024 ? tiles : 1024)), dim3(256), 0, stream,
+                           (const float*)da, wpack_bwd, gate, g, rows);
 }
 
 }  // extern "C"

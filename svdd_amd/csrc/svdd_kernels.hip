@@ -14,13 +14,10 @@
 //   K7 subs_logp_kernel  SUBS re-parameterisation alone
 //   K11 elbo_mask_kernel / K12 elbo_nll_kernel  ELBO scoring: masking of x0, the weighted SUBS token loss and its sums
 //   K4 tds_resample_kernel  SMC/TDS resampling (baseline)
-#include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
-#include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include "svdd_hip.h"
+#include "svdd_host.h"
 
 namespace {
 
@@ -1494,8 +1491,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(16))) void mt19
 // Optional per-launch timing (bench.py's roofline leg): when enabled, K1/K2 are launched with
 // hipExtLaunchKernelGGL start/stop events, i.e. HIP events bound to the dispatch itself on the launch
 // stream; svdd_profile_collect() sums hipEventElapsedTime over the recorded launches.
+// The slots are named by enum SvddProfileSlot in svdd_host.h, which also holds the launch helper every entry goes through
+// (svdd_launch / svdd_launch_timed) and the span object (SvddSpan) that fetches a slot's events once. A new entry validates its
+// arguments first, then takes `SvddSpan span(SVDD_SLOT_...)` and returns svdd_launch_timed(span.all(), kernel, ...); a span over
+// several launches gives span.first() to the first and span.last() to the last. A new slot is appended to the enum (bench.py and
+// the tools use the numbers) and PROFILE_KERNELS follows.
 struct TimedLaunch { hipEvent_t start, stop; };
-constexpr int PROFILE_KERNELS = 13;           // 0 propose (K1), 1 select (K2), 2 conv1d, 3 gru, 4 epilogue_ln, 5 conv_tower, 6 backbone_cnn, 7 value_tail, 8 tds_resample (K4, both phases), 9 mt19937 (K8), 10 backbone gradient, 11 GRU forward that saves its gates (DPS), 12 GRU BPTT (DPS)
+constexpr int PROFILE_KERNELS = SVDD_SLOT_COUNT;   // the slots are named by enum SvddProfileSlot (svdd_host.h)
 bool g_profile = false;
 TimedLaunch* g_timed[PROFILE_KERNELS] = {};
 int g_timed_n[PROFILE_KERNELS] = {}, g_timed_cap[PROFILE_KERNELS] = {};
@@ -1522,15 +1524,9 @@ int g_select_batches = 0;   // svdd_set_option(SVDD_OPT_SELECT_BATCHES, n): batc
 int g_select_one_row_per_wave = 0;   // svdd_set_option(SVDD_OPT_SELECT_ONE_ROW, v): 1 = K2 as one wave per row for every M (A/B); 2 / 3 = the rows-per-wave kernel with 4 / 1 row groups per wave whatever the batch (0: by size)
 unsigned long long* g_k1_stats = nullptr;   // svdd_k1_stats: device counters K1 adds to
 
-inline int check_launch() { return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH; }
 inline bool bad_layout(int layout) { return layout != SVDD_LAYOUT_BLV && layout != SVDD_LAYOUT_BVL; }
 
 }  // namespace
-
-extern "C" void svdd_internal_set_bb_lp_version(int v);      // svdd_lp_backbone.hip
-extern "C" void svdd_internal_set_trunk_gemm_version(int v); // svdd_trunk.hip
-extern "C" void svdd_internal_set_trunk_planes_f32(int v);   // svdd_trunk.hip
-extern "C" void svdd_internal_set_bb_split(int v);           // svdd_nets.hip
 
 // ================================================================================ C ABI ====
 extern "C" {
@@ -1560,7 +1556,7 @@ int svdd_k1_stats(unsigned long long* device_counters2) {
   return SVDD_OK;
 }
 
-// used by svdd_nets.hip: start/stop events for a timed launch of net kernel k (nullptrs when profiling is off)
+// behind SvddSpan (svdd_host.h): start / stop events of one span of slot k (nullptrs when profiling is off)
 void svdd_internal_timed_events(int k, hipEvent_t* e0, hipEvent_t* e1) {
   TimedLaunch* t = timed_slot(k);
   *e0 = t ? t->start : nullptr;
@@ -1596,9 +1592,9 @@ int svdd_selftest_fastmath(double* out3) {
   const int nthreads = 256 * 1024;
   double* d = nullptr;
   if (hipMalloc(&d, sizeof(double) * 3 * nthreads) != hipSuccess) return SVDD_E_NODEVICE;
-  hipLaunchKernelGGL(selftest_kernel, dim3(1024), dim3(256), 0, 0, d, nthreads);
+  const bool launched = svdd_launch(selftest_kernel, dim3(1024), dim3(256), 0, nullptr, d, nthreads) == SVDD_OK;
   double* h = (double*)malloc(sizeof(double) * 3 * nthreads);
-  const bool ok = hipMemcpy(h, d, sizeof(double) * 3 * nthreads, hipMemcpyDeviceToHost) == hipSuccess;
+  const bool ok = launched && hipMemcpy(h, d, sizeof(double) * 3 * nthreads, hipMemcpyDeviceToHost) == hipSuccess;
   if (ok)
     for (int j = 0; j < 3; ++j) {
       double m = 0.0;
@@ -1680,10 +1676,8 @@ static int launch_propose(bool q_given, const float* logits, const uint8_t* x, f
   const int64_t nblocks = (ntiles * msplit + 3) / 4;
   const int64_t cap = (int64_t)s_cus * occ;
   const unsigned grid = (unsigned)(nblocks < cap ? nblocks : cap);
-  TimedLaunch* t = timed_slot(0);
-  hipEvent_t e0 = t ? t->start : nullptr, e1 = t ? t->stop : nullptr;
-  hipExtLaunchKernelGGL(k, dim3(grid), dim3(256), lds, (hipStream_t)stream, e0, e1, 0, a);
-  return check_launch();
+  SvddSpan span(SVDD_SLOT_PROPOSE);
+  return svdd_launch_timed(span.all(), k, dim3(grid), dim3(256), lds, stream, a);
 }
 
 int svdd_select(const float* scores, const uint8_t* cand, int B, int L, int M, int mode, const svdd_rng_t* rng,
@@ -1702,99 +1696,82 @@ int svdd_select_compact(const float* scores, const int32_t* slot, const float* p
   SelectArgs a{scores, cand, B, L, M, mode, rng ? rng->step : 0u, rng ? rng->seed : 0ull,
                rng ? rng->row_offset : 0ull, x_next, soft, idx, slot, parent_score, sel_score, changed,
                g_cand_ld >= L ? g_cand_ld : L};
-  TimedLaunch* t = timed_slot(1);
-  hipEvent_t e0 = t ? t->start : nullptr, e1 = t ? t->stop : nullptr;
+  // which kernel, on which grid — row groups per wave: 4 once there are enough rows to fill the chip several times over (memory-level
+  // parallelism), 1 at the decode's own sizes (a few hundred rows: latency, spread over as many waves as possible)
+  // (the winners of a wave's R * G rows travel in one lane each: R * G <= 64, i.e. R <= MP)
+  void (*kern)(SelectArgs) = select_kernel;
+  dim3 grid((unsigned)((B + 3) / 4));
   if (M <= WAVE && g_select_one_row_per_wave != 1) {
     int mp = 1;
     while (mp < M) mp <<= 1;
-    // row groups per wave: 4 once there are enough rows to fill the chip several times over (memory-level parallelism),
-    // 1 at the decode's own sizes (a few hundred rows: latency, spread over as many waves as possible)
-    // (the winners of a wave's R * G rows travel in one lane each: R * G <= 64, i.e. R <= MP)
     const int Rw = g_select_one_row_per_wave == 2 ? 4 : g_select_one_row_per_wave == 3 ? 1 : ((int64_t)B * mp >= (int64_t)1 << 21 ? 4 : 1);
     const int R = Rw > mp ? mp : Rw;
     const int64_t waves = ((int64_t)B + (WAVE / mp) * R - 1) / ((WAVE / mp) * R);
-    const dim3 grid((unsigned)((waves + 3) / 4));
-#define SVDD_SEL_LAUNCH(MP_)                                                                                                     \
-    if (R > 1) hipExtLaunchKernelGGL((select_rows_kernel<MP_, (MP_ >= 4 ? 4 : MP_)>), grid, dim3(256), 0, (hipStream_t)stream, e0, e1, 0, a); \
-    else hipExtLaunchKernelGGL((select_rows_kernel<MP_, 1>), grid, dim3(256), 0, (hipStream_t)stream, e0, e1, 0, a);
+    grid = dim3((unsigned)((waves + 3) / 4));
     if (M == 10 || M == 20) {                               // the BASELINE widths: the ordered sum stops at M
       // saturated launches (R > 1), EXPERIMENT (svdd_set_option(SVDD_OPT_SELECT_BATCHES, 2 | 4)): NB batches per wave, the next batch's
       // decision under the row gathers of the one before. Measured slower (profiles/r06_k2_gather_split.txt: 27.4 -> 35.8 / 41.5 us at
       // 2^18 rows, M = 10): a quarter of the waves means a quarter of the loads in flight — the kernel lives on memory-level
       // parallelism, not on overlap inside a wave. Default: one batch per wave (round 5's launch).
       const int nb = R > 1 ? (g_select_batches == 2 ? 2 : g_select_batches == 4 ? 4 : 1) : 1;
-      const dim3 gridb((unsigned)(((waves + nb - 1) / nb + 3) / 4));
       if (R > 1 && (g_select_batches == 3 || g_select_batches == 5)) {
         // the same experiment at an UNCHANGED wave count: the wave's 4 row groups as 2 batches of 2 (3) or 4 batches of 1 (5)
-        if (M == 10) {
-          if (g_select_batches == 3) hipExtLaunchKernelGGL((select_rows_kernel<16, 2, 10, 2>), grid, dim3(256), 0, (hipStream_t)stream, e0, e1, 0, a);
-          else hipExtLaunchKernelGGL((select_rows_kernel<16, 1, 10, 4>), grid, dim3(256), 0, (hipStream_t)stream, e0, e1, 0, a);
-        } else {
-          if (g_select_batches == 3) hipExtLaunchKernelGGL((select_rows_kernel<32, 2, 20, 2>), grid, dim3(256), 0, (hipStream_t)stream, e0, e1, 0, a);
-          else hipExtLaunchKernelGGL((select_rows_kernel<32, 1, 20, 4>), grid, dim3(256), 0, (hipStream_t)stream, e0, e1, 0, a);
-        }
-        return check_launch();
-      }
-      if (M == 10) {
-        if (nb == 4) hipExtLaunchKernelGGL((select_rows_kernel<16, 4, 10, 4>), gridb, dim3(256), 0, (hipStream_t)stream, e0, e1, 0, a);
-        else if (nb == 2) hipExtLaunchKernelGGL((select_rows_kernel<16, 4, 10, 2>), gridb, dim3(256), 0, (hipStream_t)stream, e0, e1, 0, a);
-        else if (R > 1) hipExtLaunchKernelGGL((select_rows_kernel<16, 4, 10>), grid, dim3(256), 0, (hipStream_t)stream, e0, e1, 0, a);
-        else hipExtLaunchKernelGGL((select_rows_kernel<16, 1, 10>), grid, dim3(256), 0, (hipStream_t)stream, e0, e1, 0, a);
+        if (M == 10) kern = g_select_batches == 3 ? select_rows_kernel<16, 2, 10, 2> : select_rows_kernel<16, 1, 10, 4>;
+        else kern = g_select_batches == 3 ? select_rows_kernel<32, 2, 20, 2> : select_rows_kernel<32, 1, 20, 4>;
       } else {
-        if (nb == 4) hipExtLaunchKernelGGL((select_rows_kernel<32, 4, 20, 4>), gridb, dim3(256), 0, (hipStream_t)stream, e0, e1, 0, a);
-        else if (nb == 2) hipExtLaunchKernelGGL((select_rows_kernel<32, 4, 20, 2>), gridb, dim3(256), 0, (hipStream_t)stream, e0, e1, 0, a);
-        else if (R > 1) hipExtLaunchKernelGGL((select_rows_kernel<32, 4, 20>), grid, dim3(256), 0, (hipStream_t)stream, e0, e1, 0, a);
-        else hipExtLaunchKernelGGL((select_rows_kernel<32, 1, 20>), grid, dim3(256), 0, (hipStream_t)stream, e0, e1, 0, a);
+        if (nb > 1) grid = dim3((unsigned)(((waves + nb - 1) / nb + 3) / 4));
+        if (M == 10) {
+          if (nb == 4) kern = select_rows_kernel<16, 4, 10, 4>;
+          else if (nb == 2) kern = select_rows_kernel<16, 4, 10, 2>;
+          else kern = R > 1 ? select_rows_kernel<16, 4, 10> : select_rows_kernel<16, 1, 10>;
+        } else {
+          if (nb == 4) kern = select_rows_kernel<32, 4, 20, 4>;
+          else if (nb == 2) kern = select_rows_kernel<32, 4, 20, 2>;
+          else kern = R > 1 ? select_rows_kernel<32, 4, 20> : select_rows_kernel<32, 1, 20>;
+        }
       }
-      return check_launch();
+    } else {
+      switch (mp) {
+        case 1: kern = select_rows_kernel<1, 1>; break;
+        case 2: kern = R > 1 ? select_rows_kernel<2, 2> : select_rows_kernel<2, 1>; break;
+        case 4: kern = R > 1 ? select_rows_kernel<4, 4> : select_rows_kernel<4, 1>; break;
+        case 8: kern = R > 1 ? select_rows_kernel<8, 4> : select_rows_kernel<8, 1>; break;
+        case 16: kern = R > 1 ? select_rows_kernel<16, 4> : select_rows_kernel<16, 1>; break;
+        case 32: kern = R > 1 ? select_rows_kernel<32, 4> : select_rows_kernel<32, 1>; break;
+        default: kern = R > 1 ? select_rows_kernel<64, 4> : select_rows_kernel<64, 1>; break;
+      }
     }
-    switch (mp) {
-      case 1: SVDD_SEL_LAUNCH(1) break;
-      case 2: SVDD_SEL_LAUNCH(2) break;
-      case 4: SVDD_SEL_LAUNCH(4) break;
-      case 8: SVDD_SEL_LAUNCH(8) break;
-      case 16: SVDD_SEL_LAUNCH(16) break;
-      case 32: SVDD_SEL_LAUNCH(32) break;
-      default: SVDD_SEL_LAUNCH(64) break;
-    }
-#undef SVDD_SEL_LAUNCH
-    return check_launch();
   }
-  hipExtLaunchKernelGGL(select_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, e0, e1, 0, a);
-  return check_launch();
+  SvddSpan span(SVDD_SLOT_SELECT);
+  return svdd_launch_timed(span.all(), kern, grid, dim3(256), 0, stream, a);
 }
 
 int svdd_compact_flags(const int32_t* flags, int n, int32_t* live_idx, int32_t* slot, int32_t* count, void* stream) {
   if (!flags || !live_idx || !slot || !count || n <= 0) return SVDD_E_ARG;
-  hipLaunchKernelGGL(compact_flags_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, flags, n, live_idx, slot, count);
-  return check_launch();
+  return svdd_launch(compact_flags_kernel, dim3(1), dim3(1024), 0, stream, flags, n, live_idx, slot, count);
 }
 
 int svdd_compact_by_key(const int32_t* key, int n, int32_t* live_idx, int32_t* slot, int32_t* count, int split, void* stream) {
   if (!key || !live_idx || !slot || !count || n <= 0 || split < 0) return SVDD_E_ARG;
-  hipLaunchKernelGGL(compact_by_key_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, key, n, live_idx, slot, count, split);
-  return check_launch();
+  return svdd_launch(compact_by_key_kernel, dim3(1), dim3(1024), 0, stream, key, n, live_idx, slot, count, split);
 }
 
 int svdd_gather_rows(const void* src, const int32_t* idx, const int32_t* count, int n, int row_bytes, void* dst, void* stream) {
   if (!src || !idx || !dst || n <= 0 || row_bytes <= 0) return SVDD_E_ARG;
-  hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                     (const uint8_t*)src, idx, count, n, row_bytes, (uint8_t*)dst);
-  return check_launch();
+  return svdd_launch(gather_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, (const uint8_t*)src, idx, count, n,
+                     row_bytes, (uint8_t*)dst);
 }
 
 int svdd_advance_rows(const void* src, const int32_t* slot, const int32_t* sel, int B, int M, int row_bytes, void* dst,
                       void* stream) {
   if (!src || !slot || !sel || !dst || B <= 0 || M <= 0 || row_bytes <= 0 || (row_bytes & 3)) return SVDD_E_ARG;
-  hipLaunchKernelGGL(advance_rows_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)src, slot, sel,
-                     B, M, row_bytes, (uint8_t*)dst);
-  return check_launch();
+  return svdd_launch(advance_rows_kernel, dim3((unsigned)B), dim3(256), 0, stream, (const uint8_t*)src, slot, sel, B, M, row_bytes,
+                     (uint8_t*)dst);
 }
 
 static int launch_pos(void (*k)(PosArgs), const PosArgs& a, void* stream) {
   const int64_t N = (int64_t)a.R * a.L;
-  hipLaunchKernelGGL(k, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch();
+  return svdd_launch(k, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, a);
 }
 
 int svdd_x0hat(const float* logits, const uint8_t* xt, int R, int L, int layout, float* onehot_t, uint8_t* x0hat,
@@ -1822,27 +1799,24 @@ int svdd_subs_logp(const float* logits, const uint8_t* x, int B, int L, int layo
 int svdd_dps_probs(const float* logits, const uint8_t* x, int B, int L, float* probs4, void* stream) {
   if (!logits || !x || !probs4 || B <= 0 || L <= 0) return SVDD_E_ARG;
   const int64_t N = (int64_t)B * L;
-  hipLaunchKernelGGL(dps_probs_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  return svdd_launch(dps_probs_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream,
                      DpsArgs{logits, x, nullptr, nullptr, probs4, nullptr, B, L, 0.0f, 0.0f, 0.0f});
-  return check_launch();
 }
 
 int svdd_dps_probs_bwd(const float* logits, const uint8_t* x, const float* dprobs4, int B, int L, float* dlogits, float* direct,
                        void* stream) {
   if (!logits || !x || !dprobs4 || !dlogits || !direct || B <= 0 || L <= 0) return SVDD_E_ARG;
   const int64_t N = (int64_t)B * L;
-  hipLaunchKernelGGL(dps_probs_bwd_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  return svdd_launch(dps_probs_bwd_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream,
                      DpsArgs{logits, x, dprobs4, nullptr, dlogits, direct, B, L, 0.0f, 0.0f, 0.0f});
-  return check_launch();
 }
 
 int svdd_dps_guided_q(const float* logits, const uint8_t* x, const float* grad_backbone, const float* grad_direct, float dm, float mcs,
                       float scale, int B, int L, float* q, void* stream) {
   if (!logits || !x || !grad_backbone || !grad_direct || !q || B <= 0 || L <= 0) return SVDD_E_ARG;
   const int64_t N = (int64_t)B * L;
-  hipLaunchKernelGGL(dps_guided_q_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  return svdd_launch(dps_guided_q_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream,
                      DpsArgs{logits, x, grad_backbone, grad_direct, q, nullptr, B, L, dm, mcs, scale});
-  return check_launch();
 }
 
 int svdd_classifier_propose(const float* logits, int layout, const uint8_t* x, const float* grad4, float dm, float mcs, float scale,
@@ -1861,9 +1835,8 @@ int svdd_classifier_propose(const float* logits, int layout, const uint8_t* x, c
   }
   const ClassifierArgs a{logits, x, grad4, dm, mcs, scale, B, L, layout, rng->step, rng->uniforms, rng->seed, row_offset,
                          rng->uniforms_layout, x_next, onehot_next, q_xs};
-  hipLaunchKernelGGL(replay ? classifier_propose_kernel<true> : classifier_propose_kernel<false>, dim3((unsigned)((N + 255) / 256)),
-                     dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch();
+  return svdd_launch(replay ? classifier_propose_kernel<true> : classifier_propose_kernel<false>, dim3((unsigned)((N + 255) / 256)),
+                     dim3(256), 0, stream, a);
 }
 
 int svdd_elbo_mask(const uint8_t* x0, int n, int L, int K, double eps, const svdd_rng_t* rng, const float* move_chance_in,
@@ -1879,9 +1852,8 @@ int svdd_elbo_mask(const uint8_t* x0, int n, int L, int K, double eps, const svd
   }
   const ElboMaskArgs a{x0, n, L, K, eps, rng->uniforms, move_chance_in, rng->seed, replay ? 0 : rng->row_offset,
                        xt, t, move_chance, w, nmasked};
-  hipLaunchKernelGGL(replay ? elbo_mask_kernel<true> : elbo_mask_kernel<false>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0,
-                     (hipStream_t)stream, a);
-  return check_launch();
+  return svdd_launch(replay ? elbo_mask_kernel<true> : elbo_mask_kernel<false>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, stream,
+                     a);
 }
 
 int svdd_elbo_nll(const float* logits, int layout, const uint8_t* xt, const uint8_t* x0, const float* w, int n, int L, int K,
@@ -1889,8 +1861,7 @@ int svdd_elbo_nll(const float* logits, int layout, const uint8_t* xt, const uint
   if (!logits || !xt || !x0 || !w || !row_sum || n <= 0 || L <= 0 || K <= 0 || bad_layout(layout)) return SVDD_E_ARG;
   if ((int64_t)n * K * L * V >= ((int64_t)1 << 40)) return SVDD_E_ARG;
   const ElboNllArgs a{logits, layout, xt, x0, w, n, L, K, nll, row_sum, seq_mean, err};
-  hipLaunchKernelGGL(elbo_nll_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch();
+  return svdd_launch(elbo_nll_kernel, dim3((unsigned)n), dim3(256), 0, stream, a);
 }
 
 int svdd_tds_resample(const float* reward_num, const float* reward_den, double alpha, const uint8_t* sample,
@@ -1898,21 +1869,16 @@ int svdd_tds_resample(const float* reward_num, const float* reward_den, double a
   if (!reward_num || !reward_den || !sample || !u || !x_next || !work || B <= 0 || L <= 0 || !(alpha != 0.0))
     return SVDD_E_ARG;
   TdsArgs a{reward_num, reward_den, alpha, sample, u, B, L, x_next, idx, work};
-  TimedLaunch* t = timed_slot(8);              // one timed span over both launches: start of phase 1 .. stop of phase 2
-  hipExtLaunchKernelGGL(tds_cdf_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, t ? t->start : nullptr, nullptr, 0, a);
-  if (check_launch() != SVDD_OK) return SVDD_E_LAUNCH;
-  hipExtLaunchKernelGGL(tds_gather_kernel, dim3((unsigned)(((int64_t)B + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                        nullptr, t ? t->stop : nullptr, 0, a);
-  return check_launch();
+  SvddSpan span(SVDD_SLOT_TDS_RESAMPLE);       // one timed span over both launches: start of phase 1 .. stop of phase 2
+  if (svdd_launch_timed(span.first(), tds_cdf_kernel, dim3(1), dim3(1024), 0, stream, a) != SVDD_OK) return SVDD_E_LAUNCH;
+  return svdd_launch_timed(span.last(), tds_gather_kernel, dim3((unsigned)(((int64_t)B + 255) / 256)), dim3(256), 0, stream, a);
 }
 
 int svdd_mt19937_uniform_f32(uint32_t* state, float* out, long long n, void* stream) {
   if (!state || !out || n < 0) return SVDD_E_ARG;
   if (n == 0) return SVDD_OK;
-  TimedLaunch* t = timed_slot(9);
-  hipExtLaunchKernelGGL(mt19937_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, t ? t->start : nullptr, t ? t->stop : nullptr, 0,
-                        state, out, n);
-  return check_launch();
+  SvddSpan span(SVDD_SLOT_MT19937);
+  return svdd_launch_timed(span.all(), mt19937_kernel, dim3(1), dim3(256), 0, stream, state, out, n);
 }
 
 }  // extern "C"

@@ -2,9 +2,6 @@
 // (split-precision net kernels on the 16-bit matrix cores: see svdd_lp_common.h for the arithmetic)
 #include "svdd_lp_common.h"
 
-extern "C" int svdd_internal_num_cus();      // svdd_nets.hip
-extern "C" int svdd_internal_fixed_spt();    // svdd_nets.hip (svdd_set_backbone_packing)
-
 static int g_bb_lp_version = 2;     // svdd_set_option(SVDD_OPT_BACKBONE_LP_VERSION, 1): the round-2 kernel for every shape (A/B)
 static int g_bb_lp_rg = 2;          // ... 21 / 22 / 23: the transposed kernel with 1 / 2 / 3 row groups (waves per SIMD); measured
                                     // (f16x3 / bf16, B = 256, L = 200, round 4d): 2: 0.652 / 0.339 ms ; 1: 0.74 / 0.51 ms (512 registers, but
@@ -909,6 +906,18 @@ __global__ __launch_bounds__(256 * RG, RG) void backbone_lp_t_kernel(BackboneLpA
 
 }  // namespace
 
+// the kernel of one precision mode: the transposed-accumulator kernel with `rg` row groups where one sequence per tile is the only
+// packing, its interleaved form for short sequences, else the round-2 kernel
+typedef void (*BackboneLpKernel)(BackboneLpArgs);
+template <typename T, int NP>
+static BackboneLpKernel backbone_lp_pick(bool transposed, bool interleaved, bool spt1, int rg) {
+  if (transposed && rg == 3) return backbone_lp_t_kernel<T, NP, 3>;
+  if (transposed && rg == 1) return backbone_lp_t_kernel<T, NP, 1>;
+  if (transposed) return backbone_lp_t_kernel<T, NP, 2>;
+  if (interleaved) return backbone_lp_t_kernel<T, NP, 2, true>;
+  return spt1 ? backbone_lp_kernel<T, NP, true> : backbone_lp_kernel<T, NP, false>;
+}
+
 extern "C" int svdd_backbone_cnn_lp(const uint8_t* x, const float* table0, const void* tiles, const float* vec,
                                     const float* lscale, const float* w2, float* out, int n, int L, int nlayers,
                                     const int* dilations, int prec, const int32_t* count, const int32_t* row_idx,
@@ -917,14 +926,11 @@ extern "C" int svdd_backbone_cnn_lp(const uint8_t* x, const float* table0, const
       nlayers <= 0 || nlayers > BB_MAXL || prec < SVDD_PREC_F16X3 || prec > SVDD_PREC_BF16)
     return SVDD_E_ARG;
   BackboneLpArgs a;
+  if (!svdd_fill_dilations(a.dil, dilations, nlayers)) return SVDD_E_ARG;
   a.x = x; a.table0 = table0; a.tiles = tiles; a.vec = vec; a.lscale = lscale; a.w2 = w2; a.out = out;
   a.n = n; a.L = L; a.spt = TW_ROWS / L; a.nl = nlayers; a.count = count; a.row_idx = row_idx; a.out_scatter = out_scatter;
-  for (int i = 0; i < nlayers; ++i) if (dilations[i] <= 0) return SVDD_E_ARG;
-  for (int i = 0; i < BB_MAXL; ++i) a.dil[i] = i < nlayers ? dilations[i] : 1;
   const size_t lds = (size_t)IMG_REGION_B + sizeof(float) * (9 * 5 * (size_t)BB_C + 8 * (size_t)TW_ROWS + 4 * (size_t)TW_ROWS +
                                                               BB_MAXL + 1 + (size_t)(nlayers + 1) * 36);
-  hipEvent_t e0, e1;
-  svdd_internal_timed_events(6, &e0, &e1);
   a.auto_spt = 0; a.ncu = svdd_internal_num_cus();
   a.fixed_half = (prec == SVDD_PREC_F16X3 || prec == SVDD_PREC_BF16X3) ? 58 : 90;   // svdd_spt.h: calibrated on the interleaved kernel
   unsigned nwg = (unsigned)((n + a.spt - 1) / a.spt);
@@ -939,41 +945,17 @@ extern "C" int svdd_backbone_cnn_lp(const uint8_t* x, const float* table0, const
     else if (interleaved) { a.plan = svdd_plan_tiles(n, L, a.ncu, a.fixed_half); a.spt = a.plan.s2; nwg = (unsigned)svdd_plan_num_tiles(a.plan, n); }
     else { a.spt = svdd_choose_spt(n, L, a.ncu, a.fixed_half); nwg = (unsigned)((n + a.spt - 1) / a.spt); }
   }
-  const dim3 grid(nwg);
   const bool spt1 = a.spt == 1 && !a.auto_spt && (a.plan.n1 == 0 || a.plan.s1 == 1);
   // the transposed-accumulator kernel (round 3) where one sequence per tile is the ONLY packing (104 < L <= 208)
   const bool transposed = spt1 && TW_ROWS / L == 1 && g_bb_lp_version != 1;
-#define LPT_LAUNCH_ONE(TT, NPP, RGG)                                                                                \
-  { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(backbone_lp_t_kernel<TT, NPP, RGG>),                    \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                 \
-    hipExtLaunchKernelGGL((backbone_lp_t_kernel<TT, NPP, RGG>), grid, dim3(256 * RGG), lds, (hipStream_t)stream, e0, e1, 0, a); }
-#define LPT_LAUNCH_RG(TT, NPP)                                                                                      \
-  if (g_bb_lp_rg == 3) LPT_LAUNCH_ONE(TT, NPP, 3) else if (g_bb_lp_rg == 1) LPT_LAUNCH_ONE(TT, NPP, 1) else LPT_LAUNCH_ONE(TT, NPP, 2)
-#define LP_LAUNCH(TT, NPP)                                                                                          \
-  do {                                                                                                               \
-    if (transposed) {                                                                                                \
-      LPT_LAUNCH_RG(TT, NPP)                                                                                         \
-    } else if (interleaved) {                                                                                        \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(backbone_lp_t_kernel<TT, NPP, 2, true>),               \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-      hipExtLaunchKernelGGL((backbone_lp_t_kernel<TT, NPP, 2, true>), grid, dim3(512), lds, (hipStream_t)stream, e0, e1, 0, a); \
-    } else if (spt1) {                                                                                               \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(backbone_lp_kernel<TT, NPP, true>),                    \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-      hipExtLaunchKernelGGL((backbone_lp_kernel<TT, NPP, true>), grid, dim3(512), lds, (hipStream_t)stream, e0, e1, 0, a);  \
-    } else {                                                                                                         \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(backbone_lp_kernel<TT, NPP, false>),                   \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-      hipExtLaunchKernelGGL((backbone_lp_kernel<TT, NPP, false>), grid, dim3(512), lds, (hipStream_t)stream, e0, e1, 0, a); \
-    }                                                                                                                \
-  } while (0)
+  BackboneLpKernel kern;
   switch (prec) {
-    case SVDD_PREC_F16X3: LP_LAUNCH(_Float16, 3); break;
-    case SVDD_PREC_BF16X3: LP_LAUNCH(__bf16, 3); break;
-    case SVDD_PREC_F16: LP_LAUNCH(_Float16, 1); break;
-    default: LP_LAUNCH(__bf16, 1); break;
+    case SVDD_PREC_F16X3: kern = backbone_lp_pick<_Float16, 3>(transposed, interleaved, spt1, g_bb_lp_rg); break;
+    case SVDD_PREC_BF16X3: kern = backbone_lp_pick<__bf16, 3>(transposed, interleaved, spt1, g_bb_lp_rg); break;
+    case SVDD_PREC_F16: kern = backbone_lp_pick<_Float16, 1>(transposed, interleaved, spt1, g_bb_lp_rg); break;
+    default: kern = backbone_lp_pick<__bf16, 1>(transposed, interleaved, spt1, g_bb_lp_rg); break;
   }
-#undef LP_LAUNCH
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  const unsigned threads = transposed ? 256u * (g_bb_lp_rg == 3 ? 3 : g_bb_lp_rg == 1 ? 1 : 2) : 512u;   // 256 per row group
+  SvddSpan span(SVDD_SLOT_BACKBONE);
+  return svdd_launch_timed(span.all(), kern, dim3(nwg), dim3(threads), svdd_lds_raised(lds), stream, a);
 }
-

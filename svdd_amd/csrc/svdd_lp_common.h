@@ -17,14 +17,7 @@
 // Everything that is not a matrix product (first-layer table lookup, LayerNorm statistics, residual stream, ReLU,
 // biases, the 128 -> 5 output map) is computed in fp32 exactly as in the fp32 kernels.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
-#include <stdint.h>
-
-#include "svdd_hip.h"
-#include "svdd_spt.h"
-
-extern "C" void svdd_internal_timed_events(int k, hipEvent_t* e0, hipEvent_t* e1);   // svdd_kernels.hip (profiling)
+#include "svdd_host.h"
 
 namespace {
 
@@ -61,11 +54,7 @@ __device__ __forceinline__ float group16_sum(float v) {
   return v;
 }
 
-constexpr int TW_ROWS = 208;               // 13 row tiles of 16
-constexpr int TW_RT = 13;
-constexpr int BB_C = 128;
-constexpr int BB_AP = BB_C + 4;            // fp32 row stride of the final-stage image
-constexpr int BB_MAXL = 32;
+// TW_ROWS, TW_RT, BB_C, BB_AP (also the fp32 row stride of the final-stage image) and BB_MAXL: svdd_host.h
 constexpr int LPS = 144;                   // 16-bit row stride of an operand plane (288 B: conflict-free ds_read_b128)
 constexpr int LPSB = LPS * 2;
 constexpr int PLANE_B = (TW_ROWS + 2) * LPSB;              // 60,480 B: rows -1 .. TW_ROWS

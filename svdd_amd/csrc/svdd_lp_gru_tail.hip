@@ -313,21 +313,31 @@ __global__ __launch_bounds__(256, 2) void tail_lp_kernel(const float* __restrict
 
 }  // namespace
 
+typedef decltype(&tail_lp_kernel<_Float16, 3, 1>) TailLpKernel;
+template <typename T, int NP>
+static TailLpKernel tail_lp_pick(int n_tasks) {
+  switch (n_tasks) {
+    case 1: return tail_lp_kernel<T, NP, 1>;
+    case 2: return tail_lp_kernel<T, NP, 2>;
+    case 3: return tail_lp_kernel<T, NP, 3>;
+    default: return tail_lp_kernel<T, NP, 4>;
+  }
+}
+
 extern "C" int svdd_gru_bidir_lp(const float* x, const void* x16, const void* wpack, const float* bpack, const float* inv,
                                  float* out, int n, int L, const int32_t* count, int prec, void* stream) {
   if ((!x && !x16) || !wpack || !bpack || !inv || !out || n <= 0 || L <= 0 || prec < SVDD_PREC_F16X3 || prec > SVDD_PREC_BF16)
     return SVDD_E_ARG;
   GruLpArgs a{x16 ? nullptr : x, x16, wpack, bpack, inv, out, n, L, count};
-  hipEvent_t e0, e1;
-  svdd_internal_timed_events(3, &e0, &e1);
-  const dim3 grid(2 * (unsigned)((n + 15) / 16));
+  void (*kern)(GruLpArgs);
   switch (prec) {
-    case SVDD_PREC_F16X3: hipExtLaunchKernelGGL((gru_lp_kernel<_Float16, 3>), grid, dim3(512), 0, (hipStream_t)stream, e0, e1, 0, a); break;
-    case SVDD_PREC_BF16X3: hipExtLaunchKernelGGL((gru_lp_kernel<__bf16, 3>), grid, dim3(512), 0, (hipStream_t)stream, e0, e1, 0, a); break;
-    case SVDD_PREC_F16: hipExtLaunchKernelGGL((gru_lp_kernel<_Float16, 1>), grid, dim3(512), 0, (hipStream_t)stream, e0, e1, 0, a); break;
-    default: hipExtLaunchKernelGGL((gru_lp_kernel<__bf16, 1>), grid, dim3(512), 0, (hipStream_t)stream, e0, e1, 0, a); break;
+    case SVDD_PREC_F16X3: kern = gru_lp_kernel<_Float16, 3>; break;
+    case SVDD_PREC_BF16X3: kern = gru_lp_kernel<__bf16, 3>; break;
+    case SVDD_PREC_F16: kern = gru_lp_kernel<_Float16, 1>; break;
+    default: kern = gru_lp_kernel<__bf16, 1>; break;
   }
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  SvddSpan span(SVDD_SLOT_GRU);
+  return svdd_launch_timed(span.all(), kern, dim3(2 * (unsigned)((n + 15) / 16)), dim3(512), 0, stream, a);
 }
 
 extern "C" int svdd_value_tail_lp(const float* h_fwd, const float* h_bwd, const void* w1pack, const float* b1,
@@ -336,23 +346,14 @@ extern "C" int svdd_value_tail_lp(const float* h_fwd, const float* h_bwd, const 
   if (!h_fwd || !h_bwd || !w1pack || !b1 || !w_eff || !b_eff || !out || n <= 0 || L <= 0 || n_tasks < 1 || n_tasks > 4 ||
       prec < SVDD_PREC_F16X3 || prec > SVDD_PREC_BF16)
     return SVDD_E_ARG;
-  hipEvent_t e0, e1;
-  svdd_internal_timed_events(7, &e0, &e1);
-  const dim3 grid((unsigned)((n + 3) / 4)), block(256);
-#define TAIL_LP(TY, NPP, TT)                                                                                           \
-  hipExtLaunchKernelGGL((tail_lp_kernel<TY, NPP, TT>), grid, block, 0, (hipStream_t)stream, e0, e1, 0, h_fwd, h_bwd, w1pack, \
-                        b1, w_eff, b_eff, inv, out, n, L, count)
-#define TAIL_LP_T(TY, NPP)                                                                                             \
-  switch (n_tasks) { case 1: TAIL_LP(TY, NPP, 1); break; case 2: TAIL_LP(TY, NPP, 2); break;                           \
-                     case 3: TAIL_LP(TY, NPP, 3); break; default: TAIL_LP(TY, NPP, 4); break; }
+  TailLpKernel kern;
   switch (prec) {
-    case SVDD_PREC_F16X3: TAIL_LP_T(_Float16, 3) break;
-    case SVDD_PREC_BF16X3: TAIL_LP_T(__bf16, 3) break;
-    case SVDD_PREC_F16: TAIL_LP_T(_Float16, 1) break;
-    default: TAIL_LP_T(__bf16, 1) break;
+    case SVDD_PREC_F16X3: kern = tail_lp_pick<_Float16, 3>(n_tasks); break;
+    case SVDD_PREC_BF16X3: kern = tail_lp_pick<__bf16, 3>(n_tasks); break;
+    case SVDD_PREC_F16: kern = tail_lp_pick<_Float16, 1>(n_tasks); break;
+    default: kern = tail_lp_pick<__bf16, 1>(n_tasks); break;
   }
-#undef TAIL_LP_T
-#undef TAIL_LP
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  SvddSpan span(SVDD_SLOT_VALUE_TAIL);
+  return svdd_launch_timed(span.all(), kern, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, h_fwd, h_bwd, w1pack, b1, w_eff, b_eff,
+                           inv, out, n, L, count);
 }
-

@@ -27,8 +27,7 @@ namespace {
 //     (live_idx / count: exact work-skipping without a host round trip); `count` == NULL means all n.
 constexpr int TW_C = 64;
 constexpr int TLSB = 160;                       // bytes per row of a 16-bit plane (64 channels + 32 B pad: conflict-free b128)
-constexpr int TPLANE_B = (TW_ROWS + 2) * TLSB;  // rows -1 .. TW_ROWS
-constexpr int TW_MAXL = 8;
+constexpr int TPLANE_B = (TW_ROWS + 2) * TLSB;  // rows -1 .. TW_ROWS (TW_ROWS, TW_MAXL: svdd_host.h)
 
 struct TowerLpArgs {
   const uint8_t* tok;      // [n, L] tokens (0..3, 4 = MASK -> zero row)
@@ -273,31 +272,25 @@ __global__ __launch_bounds__(512, 4) void tower_lp_kernel(TowerLpArgs a) {
 
 }  // namespace
 
+typedef void (*TowerLpKernel)(TowerLpArgs);
+template <typename T, int NP>
+static TowerLpKernel tower_lp_pick(bool win, bool spt1) {
+  if (win) return tower_lp_kernel<T, NP, true, true>;
+  return spt1 ? tower_lp_kernel<T, NP, true, false> : tower_lp_kernel<T, NP, false, false>;
+}
+
 static int launch_tower_lp(const TowerLpArgs& a, bool win, int prec, unsigned grid, void* stream) {
   const size_t lds = 2 * (size_t)TPLANE_B + (size_t)(TW_ROWS + 16) * 4 * 2;
-  hipEvent_t e0, e1;
-  svdd_internal_timed_events(5, &e0, &e1);
-#define TL_LAUNCH(TT, NPP, S1, WW)                                                                                 \
-  do {                                                                                                              \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(tower_lp_kernel<TT, NPP, S1, WW>),                      \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                \
-    hipExtLaunchKernelGGL((tower_lp_kernel<TT, NPP, S1, WW>), dim3(grid), dim3(512), lds, (hipStream_t)stream, e0, e1, 0, a); \
-  } while (0)
-#define TL_MODE(TT, NPP)                                                                                            \
-  do {                                                                                                              \
-    if (win) TL_LAUNCH(TT, NPP, true, true);                                                                        \
-    else if (a.spt == 1) TL_LAUNCH(TT, NPP, true, false);                                                           \
-    else TL_LAUNCH(TT, NPP, false, false);                                                                          \
-  } while (0)
+  const bool spt1 = a.spt == 1;
+  TowerLpKernel kern;
   switch (prec) {
-    case SVDD_PREC_F16X3: TL_MODE(_Float16, 3); break;
-    case SVDD_PREC_BF16X3: TL_MODE(__bf16, 3); break;
-    case SVDD_PREC_F16: TL_MODE(_Float16, 1); break;
-    default: TL_MODE(__bf16, 1); break;
+    case SVDD_PREC_F16X3: kern = tower_lp_pick<_Float16, 3>(win, spt1); break;
+    case SVDD_PREC_BF16X3: kern = tower_lp_pick<__bf16, 3>(win, spt1); break;
+    case SVDD_PREC_F16: kern = tower_lp_pick<_Float16, 1>(win, spt1); break;
+    default: kern = tower_lp_pick<__bf16, 1>(win, spt1); break;
   }
-#undef TL_MODE
-#undef TL_LAUNCH
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  SvddSpan span(SVDD_SLOT_CONV_TOWER);
+  return svdd_launch_timed(span.all(), kern, dim3(grid), dim3(512), svdd_lds_raised(lds), stream, a);
 }
 
 extern "C" int svdd_conv_tower_lp(const uint8_t* tok, const void* tiles, const float* bias, const float* inv, void* out,

@@ -11,14 +11,7 @@
 //                       workgroup, gate weights in registers as MFMA B operands, hidden state in LDS
 //   value_tail_kernel   direction sum + LayerNorm + FFN dense1 + ReLU + (dense2 o head) + mean over length
 //   conv1d_cl_*_kernel  one dilated conv layer (layer-wise path, small batches) ; epilogue_ln_kernel its epilogue
-#include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
-#include <stdint.h>
-
-#include "svdd_hip.h"
-#include "svdd_spt.h"
-
-extern "C" void svdd_internal_timed_events(int k, hipEvent_t* e0, hipEvent_t* e1);   // svdd_kernels.hip (profiling)
+#include "svdd_host.h"
 
 namespace {
 
@@ -32,7 +25,7 @@ __device__ __forceinline__ float wave_sum(float v) {
 
 
 constexpr int H = 64;          // hidden = input width
-constexpr int TS = 16;         // sequences per workgroup (MFMA M)
+// TS = 16 sequences per workgroup (MFMA M): svdd_host.h
 constexpr int HPAD = H + 4;    // LDS row stride (floats): shifts rows by 16 B -> ds_read_b128 conflict-light
 
 __device__ __forceinline__ float sigmoid_fast(float a) {
@@ -792,11 +785,9 @@ __global__ __launch_bounds__(256) void conv1d_cl_static_kernel(ConvArgs a) {
 // v_mfma_f32_16x16x4_f32 with 16-row tiles: 13 row tiles x 4 column tiles = 52 units = 13 per SIMD exactly
 // (200 rows pad to 208: 4 % waste instead of 12 % with 32-row tiles). 8 waves: wave w owns column tile w & 3 and
 // the row tiles of parity w >> 2, so the two waves of a SIMD interleave their MFMA streams.
-constexpr int TW_ROWS = 208;               // 13 row tiles of 16
-constexpr int TW_RT = 13;
+// TW_ROWS = 208 rows = TW_RT = 13 row tiles of 16, TW_MAXL = 8 conv layers after the stem: svdd_host.h
 constexpr int TW_C = 64;
 constexpr int TW_AP = TW_C + 4;            // LDS row stride of the activation images (floats)
-constexpr int TW_MAXL = 8;                 // max conv layers after the stem
 
 struct TowerArgs {
   const float* x;        // [n, L, 4] one-hot (value-function input)
@@ -1385,9 +1376,7 @@ __global__ __launch_bounds__(256) void candidate_windows_kernel(const uint8_t* _
 // straight from L2 into the B-operand registers, one tile ahead, so there is no barrier inside a layer.
 // LayerNorm statistics are two-pass (mean, then centred variance) with a 16-lane DPP reduction and a 4-way LDS
 // exchange. Measurements and the PMC-guided history of this kernel: DESIGN.md section 4.
-constexpr int BB_C = 128;
-constexpr int BB_AP = BB_C + 4;
-constexpr int BB_MAXL = 32;
+// BB_C = 128 channels, BB_AP = BB_C + 4 the LDS row stride, BB_MAXL = 32 layers: svdd_host.h
 
 struct BackboneArgs {
   const uint8_t* x;        // [n, L] tokens 0..4
@@ -2995,44 +2984,37 @@ extern "C" int svdd_gru_set_mode(int mode) { g_gru_mode = mode; return SVDD_OK; 
 extern "C" int svdd_gru_bidir_f32(const float* x, const float* wpack, const float* bpack, float* out, int n, int L,
                                   const int32_t* count, void* stream) {
   if (!x || !wpack || !bpack || !out || n <= 0 || L <= 0) return SVDD_E_ARG;
-  hipEvent_t e0, e1;
-  svdd_internal_timed_events(3, &e0, &e1);
+  SvddSpan span(SVDD_SLOT_GRU);
   // both directions per workgroup when that fills the chip evenly (<= 16 sequences per CU); else one direction each
   const int per_cu = (n + 255) / 256;
-  if (g_gru_mode == 0 || g_gru_mode == 4) {          // default: producer / consumer waves (same bits as mode 1)
-    hipExtLaunchKernelGGL(gru_pc_kernel, dim3(2 * (unsigned)((n + TS - 1) / TS)), dim3(512), 0, (hipStream_t)stream, e0, e1, 0,
-                          x, wpack, bpack, out, n, L, count);
-    return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
-  }
+  const dim3 grid_dirs(2 * (unsigned)((n + TS - 1) / TS));   // one workgroup per (tile of TS sequences, direction)
+  if (g_gru_mode == 0 || g_gru_mode == 4)            // default: producer / consumer waves (same bits as mode 1)
+    return svdd_launch_timed(span.all(), gru_pc_kernel, grid_dirs, dim3(512), 0, stream, x, wpack, bpack, out, n, L, count);
   if (g_gru_mode == 2 && per_cu <= TS && n >= 256)   // measured slower (841 vs 758 us at n=2560, L=200): opt-in only
-    hipExtLaunchKernelGGL(gru_bidir_kernel<true>, dim3((unsigned)((n + per_cu - 1) / per_cu)), dim3(512), 0,
-                          (hipStream_t)stream, e0, e1, 0, x, wpack, bpack, out, n, L, per_cu, count);
-  else {
-    // (Reserving > 80 KB of dynamic LDS to force one workgroup per CU was measured: 2560 sequences = 320 units take
-    //  749 us in two exclusive rounds against 678 us shared, and <= 256 units spread over the CUs by themselves: 367 us
-    //  either way. Kept as mode 3 for the record.)
-    const size_t pad = g_gru_mode == 3 ? 84 * 1024 : 0;
-    if (pad) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gru_bidir_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad);
-    hipExtLaunchKernelGGL(gru_bidir_kernel<false>, dim3(2 * (unsigned)((n + TS - 1) / TS)), dim3(256), pad,
-                          (hipStream_t)stream, e0, e1, 0, x, wpack, bpack, out, n, L, TS, count);
-  }
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+    return svdd_launch_timed(span.all(), gru_bidir_kernel<true>, dim3((unsigned)((n + per_cu - 1) / per_cu)), dim3(512), 0, stream, x,
+                             wpack, bpack, out, n, L, per_cu, count);
+  // (Reserving > 80 KB of dynamic LDS to force one workgroup per CU was measured: 2560 sequences = 320 units take
+  //  749 us in two exclusive rounds against 678 us shared, and <= 256 units spread over the CUs by themselves: 367 us
+  //  either way. Kept as mode 3 for the record.)
+  const SvddLds pad = g_gru_mode == 3 ? svdd_lds_raised(84 * 1024) : SvddLds(0);
+  return svdd_launch_timed(span.all(), gru_bidir_kernel<false>, grid_dirs, dim3(256), pad, stream, x, wpack, bpack, out, n, L, TS, count);
 }
 
 extern "C" int svdd_epilogue_ln_f32(const float* y, const float* bias, const float* f_prev, const float* tb,
                                     const float* gamma, const float* beta, float* f_out, float* hn, int64_t rows,
                                     int channels, int act, void* stream) {
-  if (!y || (!f_out && !hn) || rows <= 0 || (hn && (!gamma || !beta)) || act < 0 || act > 2) return SVDD_E_ARG;
+  if (!y || (!f_out && !hn) || rows <= 0 || (hn && (!gamma || !beta)) || act < 0 || act > 2 ||
+      (channels != 64 && channels != 128 && channels != 256))
+    return SVDD_E_ARG;
   EpiArgs a{y, bias, f_prev, tb, gamma, beta, f_out, hn, rows, act};
   const int64_t nblocks = (rows + 3) / 4;
   const unsigned grid = (unsigned)(nblocks < 4096 ? nblocks : 4096);
-  hipEvent_t e0, e1;
-  if (channels != 64 && channels != 128 && channels != 256) return SVDD_E_ARG;
-  svdd_internal_timed_events(4, &e0, &e1);
-  if (channels == 64) hipExtLaunchKernelGGL(epilogue_ln_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, e0, e1, 0, a);
-  else if (channels == 128) hipExtLaunchKernelGGL(epilogue_ln_kernel<2>, dim3(grid), dim3(256), 0, (hipStream_t)stream, e0, e1, 0, a);
-  else hipExtLaunchKernelGGL(epilogue_ln_kernel<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, e0, e1, 0, a);
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  void (*kern)(EpiArgs);
+  if (channels == 64) kern = epilogue_ln_kernel<1>;
+  else if (channels == 128) kern = epilogue_ln_kernel<2>;
+  else kern = epilogue_ln_kernel<4>;
+  SvddSpan span(SVDD_SLOT_EPILOGUE_LN);
+  return svdd_launch_timed(span.all(), kern, dim3(grid), dim3(256), 0, stream, a);
 }
 
 static int g_tower_ver = 0;        // svdd_set_tower_version: 0 = default (= 3), 1 = first generation, 2 / 3 = second generation
@@ -3041,41 +3023,44 @@ extern "C" int svdd_set_tower_version(int v) { g_tower_ver = v; return SVDD_OK; 
 static int g_conv_dynamic = 0;     // tests: force the dynamically scheduled kernel
 extern "C" int svdd_conv1d_set_dynamic(int on) { g_conv_dynamic = on; return SVDD_OK; }
 
+typedef void (*ConvKernel)(ConvArgs);
+// the 128 -> 128 x 9 taps kernel compiled for (dilation, L), or nullptr where there is none
+static ConvKernel conv128_static_kernel(int dilation, int L) {
+  if (dilation == 1 && L == 200) return conv1d_cl_static_kernel<128, 128, 9, 1, 200>;
+  if (dilation == 4 && L == 200) return conv1d_cl_static_kernel<128, 128, 9, 4, 200>;
+  if (dilation == 16 && L == 200) return conv1d_cl_static_kernel<128, 128, 9, 16, 200>;
+  if (dilation == 64 && L == 200) return conv1d_cl_static_kernel<128, 128, 9, 64, 200>;
+  if (dilation == 1 && L == 50) return conv1d_cl_static_kernel<128, 128, 9, 1, 50>;
+  if (dilation == 4 && L == 50) return conv1d_cl_static_kernel<128, 128, 9, 4, 50>;
+  if (dilation == 16 && L == 50) return conv1d_cl_static_kernel<128, 128, 9, 16, 50>;
+  if (dilation == 64 && L == 50) return conv1d_cl_static_kernel<128, 128, 9, 64, 50>;
+  return nullptr;
+}
+static size_t conv_lds_bytes(int cout) { return sizeof(float) * ((size_t)(CONV_ROWS + 1) * CHP + 2 * (size_t)cout * CHP); }
+
 extern "C" int svdd_conv1d_cl_f32(const float* x, const float* wpack, float* y, int n, int L, int cin, int cout,
                                   int taps, int dilation, const float* bias, const float* f_prev, int act,
                                   const float* tb, const float* gamma, const float* beta, float* hn, void* stream) {
   if (!x || !wpack || !y || n <= 0 || L <= 0 || L > CONV_ROWS || taps <= 0 || !(taps & 1) || dilation <= 0 ||
       act < -1 || act > 2 || (hn && (act < 0 || !gamma || !beta)))
     return SVDD_E_ARG;
+  const bool dyn = g_conv_dynamic != 0;
+  ConvKernel kern = nullptr;                                   // a statically scheduled kernel where one was compiled for the shape ...
+  if (!dyn && cin == 128 && cout == 128 && taps == 9 && (L == 200 || L == 50)) kern = conv128_static_kernel(dilation, L);
+  if (!kern && !dyn && cin == 64 && cout == 64 && taps == 5 && dilation == 1 && (L == 200 || L == 50))
+    kern = L == 200 ? conv1d_cl_static_kernel<64, 64, 5, 1, 200> : conv1d_cl_static_kernel<64, 64, 5, 1, 50>;
+  if (!kern) {                                                 // ... else the generic one
+    if (act >= 0) return SVDD_E_ARG;                           // the generic kernel has no fused epilogue
+    if (cin == 128 && cout == 128) kern = conv1d_cl_kernel<128, 128>;
+    else if (cin == 64 && cout == 64) kern = conv1d_cl_kernel<64, 64>;
+    else if (cin == 64 && cout == 128) kern = conv1d_cl_kernel<64, 128>;
+    else if (cin == 128 && cout == 64) kern = conv1d_cl_kernel<128, 64>;
+    else return SVDD_E_ARG;
+  }
   const int spt = CONV_ROWS / L;                               // whole sequences per workgroup tile
   ConvArgs a{x, wpack, y, n, L, spt, taps, dilation, bias, f_prev, act, tb, gamma, beta, hn};
-  const unsigned grid = (unsigned)((n + spt - 1) / spt);
-  auto launch = [&](auto kern, int co) {
-    const size_t lds = sizeof(float) * ((size_t)(CONV_ROWS + 1) * CHP + 2 * (size_t)co * CHP);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipEvent_t e0, e1;
-    svdd_internal_timed_events(2, &e0, &e1);
-    hipExtLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, (hipStream_t)stream, e0, e1, 0, a);
-  };
-  const bool dyn = g_conv_dynamic != 0;
-  if (!dyn && cin == 128 && cout == 128 && taps == 9 && (L == 200 || L == 50)) {
-#define SVDD_CONV_CASE(D, LL) if (dilation == D && L == LL) { launch(conv1d_cl_static_kernel<128, 128, 9, D, LL>, 128); return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH; }
-    SVDD_CONV_CASE(1, 200) SVDD_CONV_CASE(4, 200) SVDD_CONV_CASE(16, 200) SVDD_CONV_CASE(64, 200)
-    SVDD_CONV_CASE(1, 50) SVDD_CONV_CASE(4, 50) SVDD_CONV_CASE(16, 50) SVDD_CONV_CASE(64, 50)
-#undef SVDD_CONV_CASE
-  }
-  if (!dyn && cin == 64 && cout == 64 && taps == 5 && dilation == 1 && (L == 200 || L == 50)) {
-    if (L == 200) launch(conv1d_cl_static_kernel<64, 64, 5, 1, 200>, 64);
-    else launch(conv1d_cl_static_kernel<64, 64, 5, 1, 50>, 64);
-    return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
-  }
-  if (act >= 0) return SVDD_E_ARG;                             // the generic kernel has no fused epilogue
-  if (cin == 128 && cout == 128) launch(conv1d_cl_kernel<128, 128>, 128);
-  else if (cin == 64 && cout == 64) launch(conv1d_cl_kernel<64, 64>, 64);
-  else if (cin == 64 && cout == 128) launch(conv1d_cl_kernel<64, 128>, 128);
-  else if (cin == 128 && cout == 64) launch(conv1d_cl_kernel<128, 64>, 64);
-  else return SVDD_E_ARG;
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  SvddSpan span(SVDD_SLOT_CONV1D);
+  return svdd_launch_timed(span.all(), kern, dim3((unsigned)((n + spt - 1) / spt)), dim3(256), svdd_lds_raised(conv_lds_bytes(cout)), stream, a);
 }
 
 // y = gate > 0 ? conv(x) + f_prev : 0 — one layer of the reward tower's BACKWARD pass (DPS): x = the gradient at this layer's
@@ -3086,19 +3071,13 @@ extern "C" int svdd_conv1d_cl_gated_f32(const float* x, const float* wpack, floa
   if (!x || !wpack || !y || n <= 0 || cin != 64 || cout != 64 || taps != 5 || dilation != 1 || (L != 200 && L != 50)) return SVDD_E_ARG;
   const int spt = CONV_ROWS / L;
   ConvArgs a{x, wpack, y, n, L, spt, taps, dilation, nullptr, f_prev, gate ? 3 : 2, gate, nullptr, nullptr, nullptr};
-  const unsigned grid = (unsigned)((n + spt - 1) / spt);
-  const size_t lds = sizeof(float) * ((size_t)(CONV_ROWS + 1) * CHP + 2 * (size_t)64 * CHP);
-  hipEvent_t e0, e1;
-  svdd_internal_timed_events(2, &e0, &e1);
-  if (L == 200) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1d_cl_static_kernel<64, 64, 5, 1, 200>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipExtLaunchKernelGGL((conv1d_cl_static_kernel<64, 64, 5, 1, 200>), dim3(grid), dim3(256), lds, (hipStream_t)stream, e0, e1, 0, a);
-  } else {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1d_cl_static_kernel<64, 64, 5, 1, 50>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipExtLaunchKernelGGL((conv1d_cl_static_kernel<64, 64, 5, 1, 50>), dim3(grid), dim3(256), lds, (hipStream_t)stream, e0, e1, 0, a);
-  }
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  ConvKernel kern = L == 200 ? conv1d_cl_static_kernel<64, 64, 5, 1, 200> : conv1d_cl_static_kernel<64, 64, 5, 1, 50>;
+  SvddSpan span(SVDD_SLOT_CONV1D);
+  return svdd_launch_timed(span.all(), kern, dim3((unsigned)((n + spt - 1) / spt)), dim3(256), svdd_lds_raised(conv_lds_bytes(64)), stream, a);
 }
+
+// dynamic LDS of the second-generation tower (conv_tower2_kernel), whole sequences and windows
+static size_t tower2_lds_bytes() { return sizeof(float) * ((size_t)(TW_ROWS + 2) * TW_AP + (size_t)(TW_ROWS + 16) * 4); }
 
 extern "C" int svdd_conv_tower_f32(const float* onehot, const float* tiles, const float* bias, float* out, int n, int L,
                                    int nlayers, int residual_mask, const int32_t* count, void* stream) {
@@ -3106,29 +3085,18 @@ extern "C" int svdd_conv_tower_f32(const float* onehot, const float* tiles, cons
     return SVDD_E_ARG;
   const int spt = TW_ROWS / L;
   TowerArgs a{onehot, tiles, bias, out, n, L, spt, nlayers, residual_mask, count};
-  const size_t lds = sizeof(float) * ((size_t)(TW_ROWS + 2) * TW_AP + (size_t)(TW_ROWS + 2) * 4);
-  hipEvent_t e0, e1;
-  svdd_internal_timed_events(5, &e0, &e1);
+  SvddSpan span(SVDD_SLOT_CONV_TOWER);
   const dim3 grid((unsigned)((n + spt - 1) / spt));
   if (g_tower_ver != 1) {
     TowerWinArgs wa{a, nullptr, nullptr, 1, nullptr, nullptr};
-    const size_t lds2 = sizeof(float) * ((size_t)(TW_ROWS + 2) * TW_AP + (size_t)(TW_ROWS + 16) * 4);
-    auto go = [&](auto kern) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-      hipExtLaunchKernelGGL(kern, grid, dim3(512), lds2, (hipStream_t)stream, e0, e1, 0, wa);
-    };
-    if (g_tower_ver == 2) { if (spt == 1) go(conv_tower2_kernel<true, false, 2>); else go(conv_tower2_kernel<false, false, 2>); }
-    else { if (spt == 1) go(conv_tower2_kernel<true, false, 1>); else go(conv_tower2_kernel<false, false, 1>); }
-    return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+    void (*kern)(TowerWinArgs);
+    if (g_tower_ver == 2) kern = spt == 1 ? conv_tower2_kernel<true, false, 2> : conv_tower2_kernel<false, false, 2>;
+    else kern = spt == 1 ? conv_tower2_kernel<true, false, 1> : conv_tower2_kernel<false, false, 1>;
+    return svdd_launch_timed(span.all(), kern, grid, dim3(512), svdd_lds_raised(tower2_lds_bytes()), stream, wa);
   }
-  if (spt == 1) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_tower_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipExtLaunchKernelGGL(conv_tower_kernel<true>, grid, dim3(512), lds, (hipStream_t)stream, e0, e1, 0, a);
-  } else {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_tower_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipExtLaunchKernelGGL(conv_tower_kernel<false>, grid, dim3(512), lds, (hipStream_t)stream, e0, e1, 0, a);
-  }
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  const size_t lds = sizeof(float) * ((size_t)(TW_ROWS + 2) * TW_AP + (size_t)(TW_ROWS + 2) * 4);
+  return svdd_launch_timed(span.all(), spt == 1 ? conv_tower_kernel<true> : conv_tower_kernel<false>, grid, dim3(512),
+                           svdd_lds_raised(lds), stream, a);
 }
 
 // Scratch of backbone_split_kernel, owned by the caller (the library never allocates): `bytes` of device memory =
@@ -3160,6 +3128,24 @@ extern "C" int svdd_backbone_split_status(int* err_out) {
   return SVDD_OK;
 }
 
+// What every fp32 backbone entry sets the same way: the nets' tensors, the shape, `spt` sequences in every tile, the dilations; no
+// device-side row count or index list, no carried planes (the entries that have them set them afterwards). false: a dilation <= 0.
+static bool backbone_args(BackboneArgs& a, const uint8_t* x, const float* table0, const float* tiles, const float* vec, const float* w2,
+                          float* out, int n, int L, int spt, int nlayers, const int* dilations) {
+  if (!svdd_fill_dilations(a.dil, dilations, nlayers)) return false;
+  a.x = x; a.table0 = table0; a.tiles = tiles; a.vec = vec; a.w2 = w2; a.out = out;
+  a.n = n; a.L = L; a.spt = spt; a.nl = nlayers; a.count = nullptr; a.row_idx = nullptr; a.out_scatter = 0;
+  a.auto_spt = 0; a.ncu = svdd_internal_num_cus(); a.plan = SvddTilePlan{spt, 0, spt};   // every tile full (one sequence per tile: never read)
+  a.planes = nullptr; a.planes_P = 0;
+  return true;
+}
+// Dynamic LDS of the one-launch backbone kernels: the image, the first layer's table, the LayerNorm partial sums, `row_stats` per-row
+// arrays (3 in the forward kernels, 2 in backbone_grad_kernel), the dilations and the schedule of (nlayers + 1) x 36 weight tiles.
+static size_t backbone_lds_bytes(int nlayers, int row_stats) {
+  return sizeof(float) * ((size_t)(TW_ROWS + 2) * BB_AP + 9 * 5 * (size_t)BB_C + 8 * (size_t)TW_ROWS + (size_t)row_stats * TW_ROWS +
+                          BB_MAXL + 1 + (size_t)(nlayers + 1) * 36);
+}
+
 // DPS: the forward that also saves what the gradient kernel needs, and the gradient kernel (one launch each way)
 extern "C" int svdd_backbone_cnn_save_f32(const uint8_t* x, const float* table0, const float* tiles, const float* vec,
                                           const float* w2, float* out, int n, int L, int nlayers, const int* dilations,
@@ -3168,20 +3154,10 @@ extern "C" int svdd_backbone_cnn_save_f32(const uint8_t* x, const float* table0,
       L > TW_ROWS || nlayers <= 0 || nlayers > BB_MAXL)
     return SVDD_E_ARG;
   BackboneArgs a;
-  a.x = x; a.table0 = table0; a.tiles = tiles; a.vec = vec; a.w2 = w2; a.out = out;
-  a.n = n; a.L = L; a.spt = 1; a.nl = nlayers; a.count = nullptr; a.row_idx = nullptr; a.out_scatter = 0;
-  a.auto_spt = 0; a.ncu = svdd_internal_num_cus(); a.plan = SvddTilePlan{1, 0, 1};
-  a.planes = nullptr; a.planes_P = 0;
-  for (int i = 0; i < BB_MAXL; ++i) a.dil[i] = i < nlayers ? dilations[i] : 1;
-  for (int i = 0; i < nlayers; ++i) if (dilations[i] <= 0) return SVDD_E_ARG;
-  const size_t lds = sizeof(float) * ((size_t)(TW_ROWS + 2) * BB_AP + 9 * 5 * (size_t)BB_C + 8 * (size_t)TW_ROWS +
-                                      3 * (size_t)TW_ROWS + BB_MAXL + 1 + (size_t)(nlayers + 1) * 36);
-  hipEvent_t e0, e1;
-  svdd_internal_timed_events(6, &e0, &e1);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(backbone_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipExtLaunchKernelGGL((backbone_kernel<true, true>), dim3((unsigned)n), dim3(512), lds, (hipStream_t)stream, e0, e1, 0, a,
-                        BackboneSave{xhat, rstd, mask});
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  if (!backbone_args(a, x, table0, tiles, vec, w2, out, n, L, 1, nlayers, dilations)) return SVDD_E_ARG;
+  SvddSpan span(SVDD_SLOT_BACKBONE);
+  return svdd_launch_timed(span.all(), backbone_kernel<true, true>, dim3((unsigned)n), dim3(512), svdd_lds_raised(backbone_lds_bytes(nlayers, 3)),
+                           stream, a, BackboneSave{xhat, rstd, mask});
 }
 
 extern "C" int svdd_backbone_cnn_grad_f32(const float* dlogits, const float* tiles_bwd, const float* gamma, const float* w2,
@@ -3191,18 +3167,12 @@ extern "C" int svdd_backbone_cnn_grad_f32(const float* dlogits, const float* til
       L <= TW_ROWS / 2 || L > TW_ROWS || nlayers <= 0 || nlayers > BB_MAXL)
     return SVDD_E_ARG;
   BackboneGradArgs a;
+  if (!svdd_fill_dilations(a.dil, dilations, nlayers)) return SVDD_E_ARG;
   a.dlogits = dlogits; a.tiles = tiles_bwd; a.gamma = gamma; a.w2 = w2; a.table0 = table0; a.dx = dx;
   a.n = n; a.L = L; a.nl = nlayers;
-  for (int i = 0; i < BB_MAXL; ++i) a.dil[i] = i < nlayers ? dilations[i] : 1;
-  for (int i = 0; i < nlayers; ++i) if (dilations[i] <= 0) return SVDD_E_ARG;
-  const size_t lds = sizeof(float) * ((size_t)(TW_ROWS + 2) * BB_AP + 9 * 5 * (size_t)BB_C + 8 * (size_t)TW_ROWS +
-                                      2 * (size_t)TW_ROWS + BB_MAXL + 1 + (size_t)(nlayers + 1) * 36);
-  hipEvent_t e0, e1;
-  svdd_internal_timed_events(10, &e0, &e1);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(backbone_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipExtLaunchKernelGGL(backbone_grad_kernel, dim3((unsigned)n), dim3(512), lds, (hipStream_t)stream, e0, e1, 0, a,
-                        BackboneSave{const_cast<float*>(xhat), const_cast<float*>(rstd), const_cast<unsigned long long*>(mask)});
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  SvddSpan span(SVDD_SLOT_BACKBONE_GRAD);
+  return svdd_launch_timed(span.all(), backbone_grad_kernel, dim3((unsigned)n), dim3(512), svdd_lds_raised(backbone_lds_bytes(nlayers, 2)),
+                           stream, a, BackboneSave{const_cast<float*>(xhat), const_cast<float*>(rstd), const_cast<unsigned long long*>(mask)});
 }
 
 extern "C" int svdd_backbone_cnn_f32(const uint8_t* x, const float* table0, const float* tiles, const float* vec,
@@ -3212,23 +3182,17 @@ extern "C" int svdd_backbone_cnn_f32(const uint8_t* x, const float* table0, cons
       nlayers <= 0 || nlayers > BB_MAXL)
     return SVDD_E_ARG;
   BackboneArgs a;
-  a.x = x; a.table0 = table0; a.tiles = tiles; a.vec = vec; a.w2 = w2; a.out = out;
-  a.n = n; a.L = L; a.spt = TW_ROWS / L; a.nl = nlayers; a.count = count; a.row_idx = row_idx; a.out_scatter = out_scatter;
-  a.auto_spt = 0; a.ncu = svdd_internal_num_cus();
-  a.planes = nullptr; a.planes_P = 0;
+  if (!backbone_args(a, x, table0, tiles, vec, w2, out, n, L, TW_ROWS / L, nlayers, dilations)) return SVDD_E_ARG;
+  a.count = count; a.row_idx = row_idx; a.out_scatter = out_scatter;
   unsigned nwg = (unsigned)((n + a.spt - 1) / a.spt);
-  a.plan = SvddTilePlan{a.spt, 0, a.spt};                // every tile full (one sequence per tile: never read)
   if (a.spt > 1 && g_fixed_spt <= 0) {                   // several sequences fit a tile: which tile takes how many (svdd_spt.h)
     if (g_fixed_spt < 0) { a.spt = -g_fixed_spt < a.spt ? -g_fixed_spt : a.spt; a.plan = SvddTilePlan{a.spt, 0, a.spt}; nwg = (unsigned)((n + a.spt - 1) / a.spt); }
     else if (count) { a.auto_spt = 1; nwg = (unsigned)n; }   // decided on the device from *count; grid for one sequence per tile
     else { a.plan = svdd_plan_tiles(n, L, a.ncu, 9); a.spt = a.plan.s2; nwg = (unsigned)svdd_plan_num_tiles(a.plan, n); }
   }
-  for (int i = 0; i < BB_MAXL; ++i) a.dil[i] = i < nlayers ? dilations[i] : 1;
-  for (int i = 0; i < nlayers; ++i) if (dilations[i] <= 0) return SVDD_E_ARG;
-  const size_t lds = sizeof(float) * ((size_t)(TW_ROWS + 2) * BB_AP + 9 * 5 * (size_t)BB_C + 8 * (size_t)TW_ROWS +
-                                      3 * (size_t)TW_ROWS + BB_MAXL + 1 + (size_t)(nlayers + 1) * 36);
-  hipEvent_t e0, e1;
-  svdd_internal_timed_events(6, &e0, &e1);
+  const SvddLds lds = svdd_lds_raised(backbone_lds_bytes(nlayers, 3));
+  SvddSpan span(SVDD_SLOT_BACKBONE);
+  SvddEvents ev = span.all();
   // Small batches of one-sequence tiles: R = 2 / 4 workgroups per sequence (backbone_split_kernel; same bits). Needs the scratch
   // image of svdd_backbone_set_workspace, a row count known on the host (no device-side count / index list) and n R <= CUs
   // (every member of a group must be resident: they wait for each other).
@@ -3240,109 +3204,79 @@ extern "C" int svdd_backbone_cnn_f32(const uint8_t* x, const float* table0, cons
     int R = g_bb_split == 2 || g_bb_split == 4 ? g_bb_split : (4 * ns <= a.ncu ? 4 : 2 * ns <= a.ncu ? 2 : 1);
     if (ns > 0 && R > 1 && (int64_t)R * ns <= a.ncu && ns <= g_bb_ws.groups) {
       if (n_main > 0) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(backbone_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         BackboneArgs am = a;
         am.n = n_main;
-        hipExtLaunchKernelGGL(backbone_kernel<true>, dim3((unsigned)n_main), dim3(512), lds, (hipStream_t)stream, e0, nullptr, 0, am, BackboneSave{});
-        if (hipGetLastError() != hipSuccess) return SVDD_E_LAUNCH;
+        if (svdd_launch_timed(span.first(), backbone_kernel<true>, dim3((unsigned)n_main), dim3(512), lds, stream, am, BackboneSave{}) != SVDD_OK)
+          return SVDD_E_LAUNCH;
         a.x += (size_t)n_main * L; a.out += (size_t)n_main * L * 5; a.n = ns;
-        e0 = nullptr;                                     // one timed span over both launches
+        ev = span.last();                                 // one timed span over both launches
       }
       if (hipMemsetAsync(g_bb_ws.cnt, 0, sizeof(int) * (size_t)ns, (hipStream_t)stream) != hipSuccess) return SVDD_E_LAUNCH;
       const dim3 sgrid((unsigned)(((ns + 7) / 8) * 8 * R));
-      if (R == 2) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(backbone_split_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipExtLaunchKernelGGL(backbone_split_kernel<2>, sgrid, dim3(512), lds, (hipStream_t)stream, e0, e1, 0, a, g_bb_ws);
-      } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(backbone_split_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipExtLaunchKernelGGL(backbone_split_kernel<4>, sgrid, dim3(512), lds, (hipStream_t)stream, e0, e1, 0, a, g_bb_ws);
-      }
-      return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+      return svdd_launch_timed(ev, R == 2 ? backbone_split_kernel<2> : backbone_split_kernel<4>, sgrid, dim3(512), lds, stream, a, g_bb_ws);
     }
   }
-  const dim3 grid(nwg);
-  if (!a.auto_spt && a.plan.s2 == 1 && (a.plan.n1 == 0 || a.plan.s1 == 1)) {   // every tile holds one sequence
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(backbone_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipExtLaunchKernelGGL(backbone_kernel<true>, grid, dim3(512), lds, (hipStream_t)stream, e0, e1, 0, a, BackboneSave{});
-  } else {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(backbone_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipExtLaunchKernelGGL(backbone_kernel<false>, grid, dim3(512), lds, (hipStream_t)stream, e0, e1, 0, a, BackboneSave{});
-  }
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  const bool spt1 = !a.auto_spt && a.plan.s2 == 1 && (a.plan.n1 == 0 || a.plan.s1 == 1);   // every tile holds one sequence
+  return svdd_launch_timed(ev, spt1 ? backbone_kernel<true> : backbone_kernel<false>, dim3(nwg), dim3(512), lds, stream, a, BackboneSave{});
 }
 
 extern "C" int svdd_backbone_incr_f32(const uint8_t* x, const float* table0, const float* tiles, const float* vec, const float* w2,
                                       float* out, int n, int L, int nlayers, const int* dilations, int lead, float* planes,
                                       uint8_t* x_prev, int32_t* items, unsigned long long* stat, int first, int max_item,
-                                      void* on_stream) {
+                                      void* stream) {
   if (!x || !table0 || !tiles || !vec || !w2 || !out || !dilations || !planes || !x_prev || !items || n <= 0 || L <= TW_ROWS / 2 ||
       L > TW_ROWS || nlayers <= 0 || nlayers > BB_MAXL || lead < 2 || lead > nlayers || (max_item != 2 && max_item != 4))
     return SVDD_E_ARG;
-  for (int i = 0; i < nlayers; ++i) if (dilations[i] <= 0 || (i < lead && dilations[i] != 1)) return SVDD_E_ARG;
+  for (int i = 0; i < lead; ++i) if (dilations[i] != 1) return SVDD_E_ARG;
   BackboneArgs a;
-  a.x = x; a.table0 = table0; a.tiles = tiles; a.vec = vec; a.w2 = w2; a.out = out;
-  a.n = n; a.L = L; a.spt = 1; a.nl = nlayers; a.count = nullptr; a.row_idx = nullptr; a.out_scatter = 0;
-  a.auto_spt = 0; a.ncu = svdd_internal_num_cus(); a.plan = SvddTilePlan{1, 0, 1};
+  if (!backbone_args(a, x, table0, tiles, vec, w2, out, n, L, 1, nlayers, dilations)) return SVDD_E_ARG;
   a.planes = planes; a.planes_P = lead;
-  for (int i = 0; i < BB_MAXL; ++i) a.dil[i] = i < nlayers ? dilations[i] : 1;
-  const size_t lds = sizeof(float) * ((size_t)(TW_ROWS + 2) * BB_AP + 9 * 5 * (size_t)BB_C + 8 * (size_t)TW_ROWS +
-                                      3 * (size_t)TW_ROWS + BB_MAXL + 1 + (size_t)(nlayers + 1) * 36);
-  hipEvent_t e0, e1;
-  svdd_internal_timed_events(6, &e0, &e1);               // ONE span per forward over all its launches
-  hipStream_t st = (hipStream_t)on_stream;
+  const SvddLds lds = svdd_lds_raised(backbone_lds_bytes(nlayers, 3));
+  SvddSpan span(SVDD_SLOT_BACKBONE);                      // ONE span per forward over all its launches
   if (first) {                                            // the whole forward, which also fills the planes; the tokens become the carried ones
-    if (hipMemcpyAsync(x_prev, x, (size_t)n * L, hipMemcpyDeviceToDevice, st) != hipSuccess) return SVDD_E_LAUNCH;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(backbone_kernel<true, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipExtLaunchKernelGGL((backbone_kernel<true, false, 1>), dim3((unsigned)n), dim3(512), lds, st, e0, e1, 0, a, BackboneSave{});
-    return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+    if (hipMemcpyAsync(x_prev, x, (size_t)n * L, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return SVDD_E_LAUNCH;
+    return svdd_launch_timed(span.all(), backbone_kernel<true, false, 1>, dim3((unsigned)n), dim3(512), lds, stream, a, BackboneSave{});
   }
-  hipExtLaunchKernelGGL(backbone_worklist_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, e0, nullptr, 0, x, x_prev, n, L,
-                        lead, max_item, items, stat);
+  if (svdd_launch_timed(span.first(), backbone_worklist_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, x, x_prev, n, L, lead,
+                        max_item, items, stat) != SVDD_OK)
+    return SVDD_E_LAUNCH;
   BackboneSegArgs sa{x, table0, tiles, vec, planes, items, n, L, 0};
   const int rows = 16 * (max_item + 2);
   const size_t slds = sizeof(float) * ((size_t)rows * BB_AP + 5 * (size_t)rows + rows + 8);
   const dim3 sgrid((unsigned)n * SEG_SLOTS);
-  (void)hipFuncSetAttribute(max_item == 4 ? reinterpret_cast<const void*>(backbone_seg_kernel<4>) : reinterpret_cast<const void*>(backbone_seg_kernel<2>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)slds);
+  void (*seg)(BackboneSegArgs) = max_item == 4 ? backbone_seg_kernel<4> : backbone_seg_kernel<2>;
+  svdd_raise_lds_limit(seg, slds);                        // once for the `lead` launches below
   for (int k = 1; k <= lead; ++k) {
     sa.layer = k;
-    if (max_item == 4) hipLaunchKernelGGL(backbone_seg_kernel<4>, sgrid, dim3(256), slds, st, sa);
-    else hipLaunchKernelGGL(backbone_seg_kernel<2>, sgrid, dim3(256), slds, st, sa);
+    if (svdd_launch(seg, sgrid, dim3(256), slds, stream, sa) != SVDD_OK) return SVDD_E_LAUNCH;
   }
-  if (hipGetLastError() != hipSuccess) return SVDD_E_LAUNCH;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(backbone_kernel<true, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipExtLaunchKernelGGL((backbone_kernel<true, false, 2>), dim3((unsigned)n), dim3(512), lds, st, nullptr, e1, 0, a, BackboneSave{});
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  return svdd_launch_timed(span.last(), backbone_kernel<true, false, 2>, dim3((unsigned)n), dim3(512), lds, stream, a, BackboneSave{});
 }
+
+typedef decltype(&value_tail_kernel<1>) ValueTailKernel;
 
 extern "C" int svdd_value_tail_f32(const float* h_fwd, const float* h_bwd, const float* w1pack, const float* b1,
                                    const float* w_eff, const float* b_eff, float* out, int n, int L, int n_tasks,
                                    const int32_t* count, void* stream) {
   if (!h_fwd || !h_bwd || !w1pack || !b1 || !w_eff || !b_eff || !out || n <= 0 || L <= 0 || n_tasks < 1 || n_tasks > 4)
     return SVDD_E_ARG;
-  hipEvent_t e0, e1;
-  svdd_internal_timed_events(7, &e0, &e1);
-  const dim3 grid((unsigned)((n + 3) / 4)), block(256);
-#define SVDD_TAIL(TT)                                                                                              \
-  hipExtLaunchKernelGGL(value_tail_kernel<TT>, grid, block, 0, (hipStream_t)stream, e0, e1, 0, h_fwd, h_bwd, w1pack, b1, \
-                        w_eff, b_eff, out, n, L, count)
+  ValueTailKernel kern;
   switch (n_tasks) {
-    case 1: SVDD_TAIL(1); break;
-    case 2: SVDD_TAIL(2); break;
-    case 3: SVDD_TAIL(3); break;
-    default: SVDD_TAIL(4); break;
+    case 1: kern = value_tail_kernel<1>; break;
+    case 2: kern = value_tail_kernel<2>; break;
+    case 3: kern = value_tail_kernel<3>; break;
+    default: kern = value_tail_kernel<4>; break;
   }
-#undef SVDD_TAIL
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  SvddSpan span(SVDD_SLOT_VALUE_TAIL);
+  return svdd_launch_timed(span.all(), kern, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, h_fwd, h_bwd, w1pack, b1, w_eff, b_eff, out,
+                           n, L, count);
 }
 
 extern "C" int svdd_candidate_windows(const uint8_t* cand, const uint8_t* x, int B, int L, int M, int margin, int32_t* win,
                                       int32_t* flags, void* stream) {
   if (!cand || !x || !win || B <= 0 || L <= 0 || M <= 0 || margin < 0) return SVDD_E_ARG;
   const int n = B * M;
-  hipLaunchKernelGGL(candidate_windows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, cand, x,
-                     n, L, M, margin, win, flags);
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  return svdd_launch(candidate_windows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, cand, x, n, L, M, margin, win, flags);
 }
 
 extern "C" int svdd_conv_tower_windows_f32(const float* onehot, const float* tiles, const float* bias, const int32_t* win,
@@ -3353,18 +3287,8 @@ extern "C" int svdd_conv_tower_windows_f32(const float* onehot, const float* til
     return SVDD_E_ARG;                                   // one sequence per tile; margins below assume the 5-layer tower
   // (with an index list, n is only the number of list entries this launch may take: a launch over PART of a compacted list)
   TowerWinArgs wa{TowerArgs{onehot, tiles, bias, out, n, L, 1, nlayers, residual_mask, nullptr}, win, parent_out, M, live_idx, count};
-  const size_t lds = sizeof(float) * ((size_t)(TW_ROWS + 2) * TW_AP + (size_t)(TW_ROWS + 16) * 4);
-  hipEvent_t e0, e1;
-  svdd_internal_timed_events(5, &e0, &e1);
-  if (g_tower_ver != 1) {
-    auto go = [&](auto kern) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipExtLaunchKernelGGL(kern, dim3((unsigned)n), dim3(512), lds, (hipStream_t)stream, e0, e1, 0, wa);
-    };
-    if (g_tower_ver == 2) go(conv_tower2_kernel<true, true, 2>); else go(conv_tower2_kernel<true, true, 1>);
-    return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
-  }
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_tower_win_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipExtLaunchKernelGGL(conv_tower_win_kernel, dim3((unsigned)n), dim3(512), lds, (hipStream_t)stream, e0, e1, 0, wa);
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  void (*kern)(TowerWinArgs) = conv_tower_win_kernel;     // the first generation
+  if (g_tower_ver != 1) kern = g_tower_ver == 2 ? conv_tower2_kernel<true, true, 2> : conv_tower2_kernel<true, true, 1>;
+  SvddSpan span(SVDD_SLOT_CONV_TOWER);
+  return svdd_launch_timed(span.all(), kern, dim3((unsigned)n), dim3(512), svdd_lds_raised(tower2_lds_bytes()), stream, wa);
 }

@@ -26,8 +26,6 @@
 // of their parent never enter the trunk, and no host round trip is needed to know how many are left).
 #include "svdd_lp_common.h"
 
-extern "C" int svdd_internal_num_cus();      // svdd_nets.hip
-
 // svdd_set_option(SVDD_OPT_TRUNK_GEMM_VERSION, v): 1 = the 128 x 128 kernel everywhere (A/B), 2 = automatic (default),
 // 3 = the 256 x 256 kernel everywhere
 static int g_trunk_gemm_version = 2;
@@ -889,7 +887,7 @@ int svdd_trunk_gemm(const void* a_hi, const void* a_lo, const void* w, const flo
       lda < Cin || ldo < N || (lda % (g_trunk_planes_f32 ? 4 : 8)) || (ldo & 3) || act < 0 || act > 2 ||
       ((count || pad > 0) && rows_per_seq <= 0) || (out_lo && !out_hi) ||
       ((post_scale == nullptr) != (post_shift == nullptr)) || post_act < 0 || post_act > 2 || pad < 0 ||
-      out_hi == a_hi || (out_lo && out_lo == a_lo))
+      out_hi == a_hi || (out_lo && out_lo == a_lo) || (g_trunk_planes_f32 && (a_lo || out_lo)))   // fp32 planes: ONE plane
     return SVDD_E_ARG;
   GemmArgs a{(const bf16_t*)a_hi, (const bf16_t*)a_lo, (const BV8*)w, bias, resid, out, M, N, T * (Cin / G_BK), Cin / G_BK, T,
              lda, ldo, act, count, rows_per_seq, (bf16_t*)out_hi, (bf16_t*)out_lo, post_scale, post_shift, post_act, pad, g_trunk_gemm_dbg,
@@ -903,35 +901,27 @@ int svdd_trunk_gemm(const void* a_hi, const void* a_lo, const void* w, const flo
   const int bm = short_tiles ? 192 : 256;
   const int mb2 = (M + bm - 1) / bm;
   const dim3 grid2((unsigned)(((mb2 + 7) / 8) * 8 * nb2));
-#define SVDD_GEMM256(NP_, F32_, LDS_)                                                                                        \
-  { if (short_tiles) {                                                                                                      \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(trunk_gemm256_kernel<NP_, F32_, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_); \
-      hipLaunchKernelGGL((trunk_gemm256_kernel<NP_, F32_, 3>), grid2, dim3(512), LDS_, (hipStream_t)stream, a);              \
-    } else {                                                                                                                \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(trunk_gemm256_kernel<NP_, F32_, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_); \
-      hipLaunchKernelGGL((trunk_gemm256_kernel<NP_, F32_, 4>), grid2, dim3(512), LDS_, (hipStream_t)stream, a);              \
-    } }
+  // the LDS-DMA kernel by (operand parts, fp32 planes, tile height in 64-row blocks) and its dynamic LDS
+  constexpr size_t lds_two_parts = 5 * 16 * 2 * 1024;     // three A stages + two W stages = 163,840 B (all of a CU's LDS); the epilogue's 8 wave slabs take 139,264 B of it
+  constexpr size_t lds_one_part = 8 * 64 * 68 * 4;        // one-pass mode: the stages take 81,920 B, the epilogue slabs 139,264 B
   if (g_trunk_planes_f32) {
     // fp32 planes: one plane, fp32 MFMA, always the LDS-DMA kernel (its K loop is matrix-pipe bound at any tile count)
-    if (a_lo || out_lo) return SVDD_E_ARG;
-    SVDD_GEMM256(2, true, 5 * 16 * 2 * 1024)
-    return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+    return svdd_launch(short_tiles ? trunk_gemm256_kernel<2, true, 3> : trunk_gemm256_kernel<2, true, 4>, grid2, dim3(512),
+                       svdd_lds_raised(lds_two_parts), stream, a);
   }
   // 256 x 256 tiles from half a chip's worth of tiles on (the 7680-row GEMMs of the transformer tower make 180 - 360 of them and
   // still run 2.3x faster than on 128 x 128 tiles: 0.79 - 0.98 vs 0.37 - 0.42 PFLOP/s); the 128 x 128 kernel below that
   const bool big = g_trunk_gemm_version == 2 ? ((int64_t)((M + 255) / 256) * nb2 >= ncu / g_trunk_gemm_big_div)
                                               : g_trunk_gemm_version == 3;
   if (big) {
-    if (a_lo) SVDD_GEMM256(2, false, 5 * 16 * 2 * 1024)     // three A stages + two W stages = 163,840 B (all of a CU's LDS); the epilogue's 8 wave slabs take 139,264 B of it
-    else SVDD_GEMM256(1, false, 8 * 64 * 68 * 4)            // one-pass mode: the stages take 81,920 B, the epilogue slabs 139,264 B
-    return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+    if (a_lo) return svdd_launch(short_tiles ? trunk_gemm256_kernel<2, false, 3> : trunk_gemm256_kernel<2, false, 4>, grid2, dim3(512),
+                                 svdd_lds_raised(lds_two_parts), stream, a);
+    return svdd_launch(short_tiles ? trunk_gemm256_kernel<1, false, 3> : trunk_gemm256_kernel<1, false, 4>, grid2, dim3(512),
+                       svdd_lds_raised(lds_one_part), stream, a);
   }
-#undef SVDD_GEMM256
   const int mb = (M + G_BM - 1) / G_BM;
   const dim3 grid((unsigned)(((mb + 7) / 8) * 8 * (N / G_BN)));         // groups of 8 row tiles x N / 128 column tiles
-  if (a_lo) hipLaunchKernelGGL(trunk_gemm_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(trunk_gemm_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  return svdd_launch(a_lo ? trunk_gemm_kernel<2> : trunk_gemm_kernel<1>, grid, dim3(256), 0, stream, a);
 }
 
 int svdd_trunk_act_split(const float* x, const float* scale, const float* shift, int act, int64_t rows, int C,
@@ -941,18 +931,14 @@ int svdd_trunk_act_split(const float* x, const float* scale, const float* shift,
     return SVDD_E_ARG;
   ActArgs a{x, scale, shift, act, rows, C, rows_per_seq, pad, (bf16_t*)hi, (bf16_t*)lo, count};
   const int64_t nthr = rows * (C >> 3);
-  if (g_trunk_planes_f32) hipLaunchKernelGGL(trunk_act_split_kernel<true>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(trunk_act_split_kernel<false>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  return svdd_launch(g_trunk_planes_f32 ? trunk_act_split_kernel<true> : trunk_act_split_kernel<false>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, a);
 }
 
 int svdd_trunk_layernorm_split(const float* x, const float* gamma, const float* beta, float eps, int64_t rows, int C,
                                void* hi, void* lo, const int32_t* count, int rows_per_seq, void* stream) {
   if (!x || !gamma || !beta || !hi || rows <= 0 || C <= 0 || (C & 7) || C > 4096 || (count && rows_per_seq <= 0)) return SVDD_E_ARG;
   LnArgs a{x, gamma, beta, eps, rows, C, (bf16_t*)hi, (bf16_t*)lo, count, rows_per_seq};
-  if (g_trunk_planes_f32) hipLaunchKernelGGL(trunk_ln_split_kernel<true>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(trunk_ln_split_kernel<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  return svdd_launch(g_trunk_planes_f32 ? trunk_ln_split_kernel<true> : trunk_ln_split_kernel<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, a);
 }
 
 int svdd_trunk_attn_pool(const float* x, const float* logits, int n, int L, int C, float* out, const int32_t* count,
@@ -962,9 +948,7 @@ int svdd_trunk_attn_pool(const float* x, const float* logits, int n, int L, int 
     return SVDD_E_ARG;
   PoolArgs a{x, logits, n, L, C, out, count, (bf16_t*)out_hi, (bf16_t*)out_lo, post_scale, post_shift, post_act};
   const int64_t nthr = (int64_t)n * ((L + 1) / 2 + 2) * (C >> 2);
-  if (g_trunk_planes_f32) hipLaunchKernelGGL(trunk_attn_pool_kernel<true>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(trunk_attn_pool_kernel<false>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  return svdd_launch(g_trunk_planes_f32 ? trunk_attn_pool_kernel<true> : trunk_attn_pool_kernel<false>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, a);
 }
 
 int svdd_trunk_attn_small(const float* qkv, const float* rel_k, const float* content_bias, const float* pos_bias, int n, int T,
@@ -974,26 +958,22 @@ int svdd_trunk_attn_small(const float* qkv, const float* rel_k, const float* con
   AttnArgs a{qkv, rel_k, content_bias, pos_bias, n, heads, dk, dv, heads * (2 * dk + dv), 1.0f / sqrtf((float)dk),
              (bf16_t*)hi, (bf16_t*)lo, count};
   const dim3 grid((unsigned)(((int64_t)n * heads + 3) / 4));
-#define SVDD_ATTN(T_)                                                                                                  \
-  if (g_trunk_planes_f32) hipLaunchKernelGGL((trunk_attn_small_kernel<T_, true>), grid, dim3(256), 0, (hipStream_t)stream, a);  \
-  else hipLaunchKernelGGL((trunk_attn_small_kernel<T_, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  const bool f32 = g_trunk_planes_f32 != 0;
+  void (*kern)(AttnArgs);
   switch (T) {
-    case 1: SVDD_ATTN(1) break;
-    case 2: SVDD_ATTN(2) break;
-    case 3: SVDD_ATTN(3) break;
-    default: SVDD_ATTN(4) break;
+    case 1: kern = f32 ? trunk_attn_small_kernel<1, true> : trunk_attn_small_kernel<1, false>; break;
+    case 2: kern = f32 ? trunk_attn_small_kernel<2, true> : trunk_attn_small_kernel<2, false>; break;
+    case 3: kern = f32 ? trunk_attn_small_kernel<3, true> : trunk_attn_small_kernel<3, false>; break;
+    default: kern = f32 ? trunk_attn_small_kernel<4, true> : trunk_attn_small_kernel<4, false>; break;
   }
-#undef SVDD_ATTN
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  return svdd_launch(kern, grid, dim3(256), 0, stream, a);
 }
 
 int svdd_trunk_stem_unfold(const uint8_t* tok, int n, int L, void* hi, const int32_t* count, void* stream) {
   if (!tok || !hi || n <= 0 || L <= 0) return SVDD_E_ARG;
   StemArgs a{tok, n, L, (bf16_t*)hi, count};
   const int64_t nthr = (int64_t)n * (L + 2) * 8;
-  if (g_trunk_planes_f32) hipLaunchKernelGGL(trunk_stem_unfold_kernel<true>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(trunk_stem_unfold_kernel<false>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  return svdd_launch(g_trunk_planes_f32 ? trunk_stem_unfold_kernel<true> : trunk_stem_unfold_kernel<false>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, a);
 }
 
 int svdd_trunk_windows(const uint8_t* cand, const uint8_t* parent, const int32_t* parent_idx, int div, int n, int L, int halo,
@@ -1002,8 +982,7 @@ int svdd_trunk_windows(const uint8_t* cand, const uint8_t* parent, const int32_t
       depth > 8 || (L & ((1 << (depth - 1)) - 1)) || slots < 1 || slots > WIN_K)
     return SVDD_E_ARG;
   WinArgs a{cand, parent, parent_idx, div, n, L, halo, depth, slots, count, w0, wlen, seg};
-  hipLaunchKernelGGL(trunk_windows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  return svdd_launch(trunk_windows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, a);
 }
 
 int svdd_trunk_stem_unfold_win(const uint8_t* tok, int n, int L, int slots, const int32_t* w0, const int32_t* wlen,
@@ -1011,9 +990,7 @@ int svdd_trunk_stem_unfold_win(const uint8_t* tok, int n, int L, int slots, cons
   if (!tok || !hi || !w0 || !wlen || !off || n <= 0 || L <= 0 || slots < 1 || slots > WIN_K) return SVDD_E_ARG;
   StemWinArgs a{tok, n, L, slots, w0, wlen, off, (bf16_t*)hi, count};
   const int64_t nthr = (int64_t)n * L * 8;
-  if (g_trunk_planes_f32) hipLaunchKernelGGL(trunk_stem_unfold_win_kernel<true>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(trunk_stem_unfold_win_kernel<false>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  return svdd_launch(g_trunk_planes_f32 ? trunk_stem_unfold_win_kernel<true> : trunk_stem_unfold_win_kernel<false>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, a);
 }
 
 int svdd_trunk_attn_pool_win(const float* x, const float* logits, int n, int L, int C, int in_halo, int slots, const int32_t* w0,
@@ -1028,9 +1005,7 @@ int svdd_trunk_attn_pool_win(const float* x, const float* logits, int n, int L, 
     return SVDD_E_ARG;
   PoolWinArgs a{x, logits, n, L, C, in_halo, slots, w0, wlen, off, parent_idx, div, (const bf16_t*)parent_hi, (const bf16_t*)parent_lo,
                 count, (bf16_t*)out_hi, (bf16_t*)out_lo, post_scale, post_shift, post_act, v0, vlen, off2};
-  if (g_trunk_planes_f32) hipLaunchKernelGGL(trunk_attn_pool_win_kernel<true>, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(trunk_attn_pool_win_kernel<false>, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? SVDD_OK : SVDD_E_LAUNCH;
+  return svdd_launch(g_trunk_planes_f32 ? trunk_attn_pool_win_kernel<true> : trunk_attn_pool_win_kernel<false>, dim3((unsigned)n), dim3(256), 0, stream, a);
 }
 
 }  // extern "C"

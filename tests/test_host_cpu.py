@@ -139,6 +139,25 @@ def test_call_door_checks_before_it_launches():
         _lib.call("svdd_set_option", 99, 0)
 
 
+def test_every_entry_refuses_nulls_before_it_touches_the_device():
+    """Every export that takes a device pointer (`vp` in _lib.SIGNATURES) and more than two parameters, called with zeros and NULLs
+    — a NULL rng and a NULL stream included — returns E_ARG, in this process on a machine without a GPU: the validation comes
+    before the profile span and before any HIP call (an entry that reached either would answer E_LAUNCH / E_NODEVICE, or take the
+    process down). Table-driven, so an entry added later is held to the same order. The two host-side queries with pointer
+    parameters (svdd_device_info, svdd_profile_collect) take no device pointer and are not launches."""
+    from svdd_amd import _lib
+    L = _lib.lib()
+    zero = {_lib.i32: 0, _lib.i64: 0, _lib.f32: 0.0, _lib.f64: 0.0}
+    entries = [name for name, sig in _lib.SIGNATURES.items() if len(sig) > 2 and _lib.vp in sig]
+    assert len(entries) >= 56 and "svdd_backbone_incr_f32" in entries and "svdd_elbo_nll" in entries
+    wrong = {}
+    for name in entries:
+        rc = getattr(L, name)(*[zero.get(t) for t in _lib.SIGNATURES[name]])     # every pointer type -> None = NULL
+        if rc != _lib.E_ARG:
+            wrong[name] = rc
+    assert not wrong, wrong
+
+
 def test_argument_validation_without_gpu():
     """Entry points reject bad arguments before touching the device."""
     from svdd_amd import _lib
