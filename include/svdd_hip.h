@@ -327,6 +327,8 @@ int svdd_gru_set_mode(int mode);
  *   C in {64,128,256}: t = y + bias ; f_out = relu(t) + f_prev (act 0) | relu(t + f_prev) (act 1) | t + f_prev (act 2);
  *   hn = LayerNorm(f_out + tb) * gamma + beta (eps 1e-5).  bias, f_prev, tb may be NULL; hn NULL skips the norm;
  *   f_out NULL skips storing the pre-norm sum.
+ *   Shapes: y, f_prev, f_out, hn [rows, C] ; bias, tb, gamma, beta [C] — tb is ONE time bias per channel, shared by every row (the
+ *   sigma = 0 bias of inference; svdd_bb_layer_fwd_f32 is the entry with a time bias per sequence). tb is read only with hn.
  *   Replaces the bias/ReLU/residual/LayerNorm tensor ops between two convolutions of the dilated-CNN backbone
  *   (reference models/dnaconv.py:188-197) and of the value net's conv tower (Enformer.py:2269-2285). */
 int svdd_epilogue_ln_f32(const float* y, const float* bias, const float* f_prev, const float* tb,
@@ -345,7 +347,9 @@ int svdd_conv1d_cl_f32(const float* x, const float* wpack, float* y, int n, int 
 /*   fused epilogue (specialised shapes only: 128->128 x 9 taps x dilation {1,4,16,64}, 64->64 x 5 taps; L in {200,50}):
  *   act -1: y = conv ; 0: y = relu(conv + bias) + f_prev ; 1: y = relu(conv + bias + f_prev) ; 2: y = conv + bias + f_prev
  *   (bias, f_prev may be NULL); with hn != NULL additionally hn = LayerNorm(y + tb) * gamma + beta (eps 1e-5), the
- *   next layer's normalised input (tb may be NULL).  Other shapes take the generic kernel and require act = -1. */
+ *   next layer's normalised input (tb may be NULL).  Other shapes take the generic kernel and require act = -1.
+ *   Shapes: f_prev, hn [n,L,cout] like y ; bias, tb, gamma, beta [cout] — tb is ONE time bias per channel, shared by every row and
+ *   sequence, as in svdd_epilogue_ln_f32. With act = -1 bias and f_prev are not read. */
 /* tests only: != 0 forces the dynamically scheduled kernel instead of the per-(dilation,L) specialisations */
 int svdd_conv1d_set_dynamic(int on);
 
@@ -413,7 +417,8 @@ int svdd_backbone_cnn_f32(const uint8_t* x, const float* table0, const float* ti
  *     16 (rh + 2 r) + 4 g + e (r < 7, e < 4) and channels 32 cg + j + 16 ct (ct < 2); slot s = (2 r + ct) 4 + e. xhat[..][s][tid] is
  *     written for every slot whose row is < 208 and for no other (r = 6 of the waves with rh = 1 is never written), bit s of
  *     mask[..][tid] is that element's decision (bits 56 .. 63 zero; every u64 is written), rstd[..][row] is written for all 208 rows
- *     of the tile. Rows >= L hold values of the zero padding, not of the sequence.
+ *     of the tile. Rows >= L hold values of the zero padding, not of the sequence: svdd_backbone_cnn_grad_f32 reads them (they must
+ *     be finite) but no bit of dx depends on them, nor on the mask bits of those rows (tests/test_backbone_grad_kernel_gpu.py).
  *   svdd_backbone_cnn_grad_f32: dlogits [n,L,5] = d loss / d `out` -> dx [n,L,5] = d loss / d onehot(x), through the transposed
  *     1x1 convs, 20 x [ReLU', transposed dilated conv (the same implicit GEMM on tiles_bwd), LayerNorm backward from xhat / rstd,
  *     residual] and the first conv's transpose. tiles_bwd: W_f1^T as [4][128][32], then layers nlayers-1 .. 0 as [4][9][128][32] of

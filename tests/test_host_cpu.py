@@ -219,6 +219,37 @@ def test_argument_validation_without_gpu():
     assert L.svdd_bb_layer_fwd_f32(None, None, None, None, None, None, 1e-5, None, None, None, 1, 1, 128, None) == _lib.E_ARG
     assert L.svdd_bb_layer_fwd_f32(one, one, one, None, None, None, 1e-5, one, one, None, 1, 1, 96, None) == _lib.E_ARG    # channels not 64 / 128 / 256
     assert L.svdd_bb_layer_bwd_f32(one, one, one, one, 1e-5, one, one, one, None, 1, 1, 128, None) == _lib.E_ARG          # mask without its output
+    # the one-launch backbone pair of DPS: lengths outside 104 < L <= 208, layer counts outside 1 .. 32, a dilation of 0, each NULL
+    def bb_save(n=1, L=200, nl=2, dil=(1, 4), ptrs=(one,) * 9):
+        d = None if dil is None else (ctypes.c_int * max(1, len(dil)))(*dil)
+        return L_.svdd_backbone_cnn_save_f32(*ptrs[:6], n, L, nl, d, *ptrs[6:], None)
+
+    def bb_grad(n=1, L=200, nl=2, dil=(1, 4), ptrs=(one,) * 9):
+        d = None if dil is None else (ctypes.c_int * max(1, len(dil)))(*dil)
+        return L_.svdd_backbone_cnn_grad_f32(*ptrs, n, L, nl, d, None)
+    for entry in (bb_save, bb_grad):
+        for kw in (dict(L=104), dict(L=209), dict(L=0), dict(nl=0, dil=()), dict(nl=33, dil=(1,) * 33), dict(dil=(1, 0)), dict(dil=(0, 1)),
+                   dict(dil=(1, -4)), dict(dil=None), dict(n=0)):
+            assert entry(**kw) == _lib.E_ARG, (entry.__name__, kw)
+        for k in range(9):
+            assert entry(ptrs=tuple(None if i == k else one for i in range(9))) == _lib.E_ARG, (entry.__name__, k)
+    # svdd_conv1d_cl_f32: a tile holds 224 rows, taps are odd, four channel pairs, the fused epilogue only on the static shapes
+    def conv(n=1, L=200, cin=128, cout=128, taps=9, dil=1, bias=None, f_prev=None, act=-1, tb=None, gamma=None, beta=None, hn=None, ptrs=(one,) * 3):
+        return L_.svdd_conv1d_cl_f32(*ptrs, n, L, cin, cout, taps, dil, bias, f_prev, act, tb, gamma, beta, hn, None)
+    for kw in (dict(L=225), dict(L=0), dict(n=0), dict(taps=8), dict(taps=0), dict(dil=0), dict(cin=32, cout=64), dict(cin=64, cout=256),
+               dict(cin=96, cout=96), dict(act=3), dict(act=-2),
+               dict(L=113, act=0), dict(taps=7, act=2), dict(dil=2, act=1), dict(cin=64, cout=128, taps=5, act=0),      # act >= 0 on a generic shape
+               dict(act=0, hn=one), dict(act=0, hn=one, beta=one), dict(act=0, hn=one, gamma=one),                      # hn without gamma / beta
+               dict(act=-1, hn=one, gamma=one, beta=one)):                                                             # hn without an epilogue
+        assert conv(**kw) == _lib.E_ARG, kw
+    for k in range(3):
+        assert conv(ptrs=tuple(None if i == k else one for i in range(3))) == _lib.E_ARG, k
+    # svdd_epilogue_ln_f32: y, f_out, hn at positions 0, 6, 7
+    def epi(rows=4, C=128, act=0, y=one, gamma=one, beta=one, f_out=one, hn=one):
+        return L_.svdd_epilogue_ln_f32(y, None, None, None, gamma, beta, f_out, hn, rows, C, act, None)
+    for kw in (dict(C=96), dict(C=0), dict(C=512), dict(act=3), dict(act=-1), dict(f_out=None, hn=None), dict(y=None), dict(rows=0),
+               dict(gamma=None), dict(beta=None)):
+        assert epi(**kw) == _lib.E_ARG, kw
     # the reward net's gradient pass: the shapes its specialised kernels do not have, and NULLs
     for L_bad, taps in ((100, 5), (208, 5), (1, 5), (200, 3), (50, 9)):
         assert L.svdd_conv1d_cl_gated_f32(one, one, one, 1, L_bad, 64, 64, taps, 1, None, None, None) == _lib.E_ARG

@@ -33,6 +33,7 @@ import torch
 from svdd_amd import _lib, fused
 from tests import grad_ref as R
 from tests import net_ref as N
+from tests.bb_grad_ref import save_layout as _save_layout
 from tests.kernel_harness import DEV, _dev, _p, _report, _st, _twice
 
 pytestmark = pytest.mark.gpu
@@ -179,23 +180,11 @@ def test_backbone_f32_count_and_row_idx(n, L, k):
         _rep(f"backbone {tag} n={n} L={L} k={k}", got, r64[d2], r32[d2])
 
 
-def _save_layout():
-    """The lane-private layout of svdd_backbone_cnn_save_f32's xhat [56 slots][512 threads] as include/svdd_hip.h states it: thread
-    tid = 64 w + 16 g + j (w = wave, cg = w & 3, rh = w >> 2) keeps in slot (2 r + ct) 4 + e the value of row 16 (rh + 2 r) + 4 g + e,
-    channel 32 cg + j + 16 ct; a slot whose row is >= 208 is never written. -> (row, col) int64 [56, 512], valid bool [56, 512]."""
-    tid, slot = torch.arange(512)[None, :], torch.arange(56)[:, None]
-    w, lane = tid >> 6, tid & 63
-    cg, rh, j, g = w & 3, w >> 2, lane & 15, lane >> 4
-    r, ct, e = slot // 8, (slot // 4) % 2, slot % 4
-    row, col = 16 * (rh + 2 * r) + 4 * g + e, 32 * cg + j + 16 * ct + 0 * slot
-    return row, col, row < 208
-
-
 @pytest.mark.parametrize("n,L", [(3, 200), (37, 105), (5, 208)])
 def test_backbone_save_f32(n, L):
     """svdd_backbone_cnn_save_f32: the inference kernel's bits in `out`, and xhat / rstd / mask written over exactly the extents the
     header states: mask [n][nl + 2][512] u64 in full (bits 56 .. 63 zero), rstd [n][nl][208] in full (all 208 rows of the tile,
-    whatever L is), xhat [n][nl][56][512] in every slot whose row is < 208 and in no other (_save_layout). rstd and xhat of the L
+    whatever L is), xhat [n][nl][56][512] in every slot whose row is < 208 and in no other (bb_grad_ref.save_layout). rstd and xhat of the L
     live rows, xhat brought back to [row][channel] by the stated index map, equal float64's 1 / sqrt(var + eps) and LayerNorm'd value
     before the affine map. (The ReLU decisions in mask are discontinuous in the inputs: their values are held by the gradient test of
     tests/test_fused_gpu.py, which decodes them and pins a float64 forward to them.) The same bits on a second launch.
