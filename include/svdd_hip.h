@@ -446,6 +446,24 @@ int svdd_backbone_cnn_grad_f32(const float* dlogits, const float* tiles_bwd, con
 int svdd_backbone_incr_f32(const uint8_t* x, const float* table0, const float* tiles, const float* vec, const float* w2,
                            float* out, int n, int L, int nlayers, const int* dilations, int lead, float* planes,
                            uint8_t* x_prev, int32_t* items, unsigned long long* stat, int first, int max_item, void* on_stream);
+/* svdd_backbone_incr2_f32 (ABI 15) — svdd_backbone_incr_f32 with the segment launches dealt from a compact, size-ordered list, so
+ *   that the dispatcher balances the CUs: the items of most tiles come first and every empty workgroup comes after the work.
+ *   Arguments, results, planes, x_prev, stat and `first` as svdd_backbone_incr_f32. max_item is 1, 2 or 4. With S = 7 slots per
+ *   (layer, row) for max_item 2 and 4, and S = 13 for max_item 1 (a row that changed everywhere has 13 one-tile items):
+ *   items [lead][n][S] i32: written exactly as svdd_backbone_incr_f32 writes it (every slot rewritten each step, 0 = empty) ;
+ *   order [lead][n * S] i32, order_count [lead] i32 (caller-owned, n <= 65536): order_count[k] = the non-empty items of layer k + 1,
+ *   order[k][0 .. order_count[k]) = one entry row << 16 | item (item = first tile | tiles << 8) per non-empty item, SORTED BY TILE
+ *   COUNT, largest first. The build is deterministic — inside a size class the entries are in (row, slot) order — but callers may
+ *   rely only on the sort by size and on the multiset of entries; entries at and beyond order_count[k] are unspecified. Workgroup
+ *   b of layer k's launch (grid n * S) takes order[k][b] and returns at once if b >= order_count[k]. first != 0 writes neither list.
+ *   svdd_backbone_incr_set_residency(r): the most segment workgroups resident per CU from the next call on — the launch's LDS
+ *   request is padded until only r fit (1 .. 8 ; 0 = no padding: what the kernel's own image and registers allow, 4 workgroups
+ *   for max_item 2, 6 for max_item 1, 3 for max_item 4). Process-wide, like svdd_set_option; not a per-call argument. */
+int svdd_backbone_incr2_f32(const uint8_t* x, const float* table0, const float* tiles, const float* vec, const float* w2,
+                            float* out, int n, int L, int nlayers, const int* dilations, int lead, float* planes,
+                            uint8_t* x_prev, int32_t* items, unsigned long long* stat, int first, int max_item,
+                            int32_t* order, int32_t* order_count, void* on_stream);
+int svdd_backbone_incr_set_residency(int wg_per_cu);
 /* svdd_backbone_set_workspace — caller-owned scratch for the small-batch form of svdd_backbone_cnn_f32 (several workgroups per
  * sequence exchange the LayerNorm'd image of every layer through it): ws = device memory of `bytes` >= n_max * (2 * 208 * 128 * 4
  * + 4) + 4 bytes for batches of up to n_max sequences (n_max = 128 covers every case the split is used for); NULL: none (one
@@ -564,7 +582,7 @@ int svdd_device_info(char* arch, int arch_len, int* num_cu);
 
 /* ABI version of this header: bumped on any signature change. */
 int svdd_abi_version(void);
-#define SVDD_ABI_VERSION 14
+#define SVDD_ABI_VERSION 15
 
 /*
  * Enformer-shaped value trunk (BASELINE.json configs[3]; reference decode.py:78-80, Enformer.py:1271-1334 trunk, :1807-1884

@@ -13,7 +13,7 @@ CSRC = os.path.join(_HERE, "csrc")
 # SVDD_HIP_LIB: load another build of the library instead (the timing-experiment scripts under tools/ build patched
 # copies of the kernels in a scratch directory; the tracked sources are never edited in place)
 SO_PATH = os.environ.get("SVDD_HIP_LIB") or os.path.join(CSRC, "libsvdd_hip.so")
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 OK, E_ARG, E_LAUNCH, E_NODEVICE = 0, -1, -2, -3
 LAYOUT_BLV, LAYOUT_BVL = 0, 1
@@ -73,6 +73,8 @@ SIGNATURES = {
     "svdd_conv_tower_f32": (vp, vp, vp, vp, i32, i32, i32, i32, vp, STREAM),
     "svdd_backbone_cnn_f32": (vp, vp, vp, vp, vp, vp, i32, i32, i32, pi32, vp, vp, i32, STREAM),
     "svdd_backbone_incr_f32": (vp, vp, vp, vp, vp, vp, i32, i32, i32, pi32, i32, vp, vp, vp, vp, i32, i32, vp),
+    "svdd_backbone_incr2_f32": (vp, vp, vp, vp, vp, vp, i32, i32, i32, pi32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp),
+    "svdd_backbone_incr_set_residency": (i32,),
     "svdd_value_tail_f32": (vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, STREAM),
     "svdd_candidate_windows": (vp, vp, i32, i32, i32, i32, vp, vp, STREAM),
     "svdd_conv_tower_windows_f32": (vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, STREAM),

@@ -52,7 +52,7 @@ enum SvddProfileSlot {
   SVDD_SLOT_GRU = 3,             // svdd_gru_bidir_f32, svdd_gru_bidir_lp
   SVDD_SLOT_EPILOGUE_LN = 4,     // svdd_epilogue_ln_f32
   SVDD_SLOT_CONV_TOWER = 5,      // svdd_conv_tower[_windows]_{f32,lp}, svdd_reward_stem[_bwd]_f32
-  SVDD_SLOT_BACKBONE = 6,        // svdd_backbone_cnn_{f32,save_f32,lp}, svdd_backbone_incr_f32 (one span per forward)
+  SVDD_SLOT_BACKBONE = 6,        // svdd_backbone_cnn_{f32,save_f32,lp}, svdd_backbone_incr[2]_f32 (one span per forward)
   SVDD_SLOT_VALUE_TAIL = 7,      // svdd_value_tail_{f32,lp}, svdd_reward_tail_grad_f32
   SVDD_SLOT_TDS_RESAMPLE = 8,    // K4: svdd_tds_resample (one span over both phases)
   SVDD_SLOT_MT19937 = 9,         // K8: svdd_mt19937_uniform_f32

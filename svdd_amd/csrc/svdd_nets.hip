@@ -1903,7 +1903,7 @@ __global__ __launch_bounds__(512, 2) void backbone_kernel(BackboneArgs a, Backbo
 }
 #undef BB_OWN
 
-// ------------------------------------------------- incremental stem: only what a step's new tokens can reach (svdd_backbone_incr_f32) ----
+// ------------------------------------------------- incremental stem: only what a step's new tokens can reach (svdd_backbone_incr[2]_f32) ----
 // The backbone does not see the time step, so a row's activations depend on its tokens alone, and between two decode steps a row's
 // tokens change at a few positions. The leading run of P dilation-1 layers spreads a changed position p slowly: f after the first
 // convolution differs from the previous step's inside p +- 4, f after conv layer k - 1 ("plane k") inside p +- (4 + 4 k) — everything
@@ -1911,6 +1911,8 @@ __global__ __launch_bounds__(512, 2) void backbone_kernel(BackboneArgs a, Backbo
 // [n][208][128] fp32, and per step
 //   backbone_worklist_kernel   compares the old and the new tokens and writes, per layer, the row tiles inside the reach as items
 //                              (first tile, tile count <= max_item) over runs of adjacent tiles;
+//   backbone_order_kernel      (svdd_backbone_incr2_f32) packs each layer's non-empty items into a list, most tiles first, so that
+//                              the dispatcher — which hands workgroups out in index order — balances the CUs by itself;
 //   backbone_seg_kernel        one launch per layer k = 1 .. P, one workgroup per item: plane k - 1 of the item's tiles and of one
 //                              halo tile on each side (k = 1: f_0 from the tokens, the table lookup of backbone_kernel's first
 //                              layer) -> LayerNorm image in LDS -> the 9-tap convolution of the item's own tiles -> ReLU + residual ->
@@ -1934,9 +1936,14 @@ struct BackboneSegArgs {
   float* planes;           // [P][n][208][128]
   const int* items;        // [P][n][SEG_SLOTS] : first tile | tile count << 8 ; 0 = empty slot
   int n, L, layer;         // layer k = 1 .. P: reads plane k - 1 (k = 1: the tokens), writes plane k
+  const int* order;        // [P][order_stride] : row << 16 | item, the layer's non-empty items, most tiles first   (ORD kernels only)
+  const int* order_count;  // [P] : entries of order[k] that are set
+  int order_stride;        // n * (items per row)
 };
 
-// One wave per row. Lane k - 1 cuts layer k's tile mask into items; stat (may be NULL) += the tile-layers marked.
+// One wave per row. Lane k - 1 cuts layer k's tile mask into items; stat (may be NULL) += the tile-layers marked. SLOTS = items per
+// (layer, row): SEG_SLOTS for runs cut to 2 or 4 tiles, TW_RT for 1-tile items (svdd_backbone_incr2_f32 only).
+template <int SLOTS = SEG_SLOTS>
 __global__ __launch_bounds__(256) void backbone_worklist_kernel(const uint8_t* __restrict__ x, uint8_t* __restrict__ x_prev, int n,
                                                                 int L, int P, int max_item, int* __restrict__ items,
                                                                 unsigned long long* __restrict__ stat) {
@@ -1965,7 +1972,7 @@ __global__ __launch_bounds__(256) void backbone_worklist_kernel(const uint8_t* _
     if (lane == k - 1) mine = m;
   }
   if (lane >= P) return;
-  int* it = items + ((size_t)lane * n + row) * SEG_SLOTS;
+  int* it = items + ((size_t)lane * n + row) * SLOTS;
   int cnt = 0;
   for (int t = 0; t < TW_RT;) {
     if (!(mine >> t & 1)) { ++t; continue; }
@@ -1974,14 +1981,76 @@ __global__ __launch_bounds__(256) void backbone_worklist_kernel(const uint8_t* _
     it[cnt++] = t | len << 8;
     t += len;
   }
-  for (; cnt < SEG_SLOTS; ++cnt) it[cnt] = 0;
+  for (; cnt < SLOTS; ++cnt) it[cnt] = 0;
   if (stat && mine) atomicAdd(stat, (unsigned long long)__popc(mine));
+}
+
+// The size-ordered list of svdd_backbone_incr2_f32: workgroup k packs layer k + 1's non-empty items into order[k] as
+// row << 16 | item, the items of 4 tiles first, then 3, 2, 1; inside a size class in (row, slot) order — a deterministic build (two
+// passes over the rows: the class totals, then a block scan per class), so two forwards of the same tokens write the same list. The
+// dispatcher hands workgroups out in index order: with the large items in front, a CU that finishes early draws the next one, and
+// the empty workgroups all come after the work instead of between it.
+template <int SLOTS>
+__global__ __launch_bounds__(256) void backbone_order_kernel(const int* __restrict__ items, int n, int* __restrict__ order,
+                                                             int* __restrict__ order_count) {
+  __shared__ int wtot[4][4];                              // [wave][class]: class c holds the items of 4 - c tiles
+  __shared__ int base[4];                                 // where the class continues in order[k]
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int* it = items + (size_t)blockIdx.x * n * SLOTS;
+  int* ord = order + (size_t)blockIdx.x * n * SLOTS;
+  int cnt[4] = {0, 0, 0, 0};
+  for (int r = tid; r < n; r += 256)
+    for (int s = 0; s < SLOTS; ++s) {
+      const int len = it[r * SLOTS + s] >> 8;
+      for (int c = 0; c < 4; ++c) cnt[c] += len == 4 - c;
+    }
+  for (int c = 0; c < 4; ++c) {
+    int v = cnt[c];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    if (lane == 0) wtot[w][c] = v;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int run = 0;
+    for (int c = 0; c < 4; ++c) { base[c] = run; run += wtot[0][c] + wtot[1][c] + wtot[2][c] + wtot[3][c]; }
+    order_count[blockIdx.x] = run;
+  }
+  __syncthreads();
+  for (int r0 = 0; r0 < n; r0 += 256) {
+    const int r = r0 + tid;
+    int item[SLOTS], pos[4];
+    for (int c = 0; c < 4; ++c) cnt[c] = 0;
+    for (int s = 0; s < SLOTS; ++s) {
+      item[s] = r < n ? it[r * SLOTS + s] : 0;
+      for (int c = 0; c < 4; ++c) cnt[c] += (item[s] >> 8) == 4 - c;
+    }
+    for (int c = 0; c < 4; ++c) {                         // inclusive scan inside the wave, wave totals through LDS
+      int v = cnt[c];
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) { const int u = __shfl_up(v, off, 64); if (lane >= off) v += u; }
+      pos[c] = v - cnt[c];
+      if (lane == 63) wtot[w][c] = v;
+    }
+    __syncthreads();
+    for (int c = 0; c < 4; ++c) {
+      int at = base[c] + pos[c];
+      for (int q = 0; q < w; ++q) at += wtot[q][c];
+      for (int s = 0; s < SLOTS; ++s)
+        if ((item[s] >> 8) == 4 - c) ord[at++] = r << 16 | item[s];
+    }
+    __syncthreads();
+    if (tid < 4) base[tid] += wtot[0][tid] + wtot[1][tid] + wtot[2][tid] + wtot[3][tid];
+    __syncthreads();
+  }
 }
 
 // NC = the most own tiles an item may have (2 / 4); 4 waves, wave cg owns 32 output channels of EVERY tile of the item (slots
 // 0 .. NC + 1 = halo, own tiles, halo), so a weight fragment feeds up to NC row tiles and the register arrays are sized to the item.
-template <int NC>
-__global__ __launch_bounds__(256, NC == 4 ? 2 : 3) void backbone_seg_kernel(BackboneSegArgs a) {
+// ORD: workgroup b takes entry b of the layer's size-ordered list (svdd_backbone_incr2_f32) instead of slot b of `items`; NC = 1
+// exists for that list only (3 image slots, one fragment set per entry, 4 workgroups per CU).
+template <int NC, bool ORD = false>
+__global__ __launch_bounds__(256, NC == 4 ? 2 : NC == 1 ? 4 : 3) void backbone_seg_kernel(BackboneSegArgs a) {
   constexpr int NS = NC + 2, ROWS = 16 * NS;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* img = smem;                                      // [ROWS][BB_AP] image row i = sequence row 16 (t0 - 1) + i
@@ -1989,11 +2058,19 @@ __global__ __launch_bounds__(256, NC == 4 ? 2 : 3) void backbone_seg_kernel(Back
   float* rstat = psum + 4 * ROWS;                         // [ROWS]
   int* toks = reinterpret_cast<int*>(rstat + ROWS);       // [ROWS + 8] tokens of sequence rows 16 (t0 - 1) - 4 ..   (layer 1)
 
-  const int item = __builtin_amdgcn_readfirstlane(a.items[(size_t)(a.layer - 1) * a.n * SEG_SLOTS + blockIdx.x]);
+  int item, seq;
+  if (ORD) {
+    if ((int)blockIdx.x >= a.order_count[a.layer - 1]) return;
+    const unsigned ent = (unsigned)__builtin_amdgcn_readfirstlane(a.order[(size_t)(a.layer - 1) * a.order_stride + blockIdx.x]);
+    item = (int)(ent & 0xFFFFu);
+    seq = (int)(ent >> 16);
+  } else {
+    item = __builtin_amdgcn_readfirstlane(a.items[(size_t)(a.layer - 1) * a.n * SEG_SLOTS + blockIdx.x]);
+    seq = blockIdx.x / SEG_SLOTS;
+  }
   const int nown = min(item >> 8, NC);
   if (nown == 0) return;
   const int t0 = item & 255;
-  const int seq = blockIdx.x / SEG_SLOTS;
   const int tid = threadIdx.x, lane = tid & 63;
   const int cg = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j = lane & 15, g = lane >> 4;
@@ -2140,7 +2217,7 @@ __global__ __launch_bounds__(256, NC == 4 ? 2 : 3) void backbone_seg_kernel(Back
       __builtin_amdgcn_sched_barrier(0);
   // one entry: the next entry's weight tile goes to the idle fragment set, the A fragments of its first two tiles are requested
   // under this entry's last MFMA groups (backbone_kernel's B2_ENTRY4 / B2_ENTRY2 without the schedule word)
-#define SG_ENTRY(BC, BN)                                                                                     \
+#define SG_ENTRY(BC, BN, UC, UN)                                                                             \
     { const int nxt = it + 1 < 36 ? it + 1 : it;                                                             \
       const float bf0[8] = {BC[0].x, BC[0].y, BC[0].z, BC[0].w, BC[1].x, BC[1].y, BC[1].z, BC[1].w};         \
       const float bf1[8] = {BC[2].x, BC[2].y, BC[2].z, BC[2].w, BC[3].x, BC[3].y, BC[3].z, BC[3].w};         \
@@ -2151,7 +2228,7 @@ __global__ __launch_bounds__(256, NC == 4 ? 2 : 3) void backbone_seg_kernel(Back
         BN[3] = *reinterpret_cast<const float4*>(src + 16 * CH + 4);                                         \
       }                                                                                                      \
       const int dbytes = SG_DBYTES(it), dbytes2 = SG_DBYTES(nxt);                                            \
-      if (NC == 4) {                                                                                         \
+      if constexpr (NC == 4) {                                                                               \
         SG_MM(0, ua)                                                                                         \
         SG_ALOAD(2, ua, dbytes)                                                                              \
         SG_MM(1, ub)                                                                                         \
@@ -2160,6 +2237,9 @@ __global__ __launch_bounds__(256, NC == 4 ? 2 : 3) void backbone_seg_kernel(Back
         SG_ALOAD(0, ua, dbytes2)                                                                             \
         SG_MM(NC - 1, ub)                                                                                    \
         SG_ALOAD(1, ub, dbytes2)                                                                             \
+      } else if constexpr (NC == 1) {                    /* one tile: the fragment sets alternate by entry */ \
+        SG_ALOAD(0, UN, dbytes2)                                                                             \
+        SG_MM(0, UC)                                                                                         \
       } else {                                                                                               \
         SG_MM(0, ua)                                                                                         \
         SG_ALOAD(0, ua, dbytes2)                                                                             \
@@ -2169,10 +2249,10 @@ __global__ __launch_bounds__(256, NC == 4 ? 2 : 3) void backbone_seg_kernel(Back
       ++it; }
   float4 ua[2], ub[2];
   SG_ALOAD(0, ua, SG_DBYTES(0))
-  SG_ALOAD(1, ub, SG_DBYTES(0))
+  if constexpr (NC > 1) SG_ALOAD(1, ub, SG_DBYTES(0))
   for (int it = 0; it < 36;) {
-    SG_ENTRY(bA, bB)
-    SG_ENTRY(bB, bA)
+    SG_ENTRY(bA, bB, ua, ub)
+    SG_ENTRY(bB, bA, ub, ua)
   }
 #undef SG_ENTRY
 #undef SG_MM
@@ -3237,14 +3317,70 @@ extern "C" int svdd_backbone_incr_f32(const uint8_t* x, const float* table0, con
     if (hipMemcpyAsync(x_prev, x, (size_t)n * L, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return SVDD_E_LAUNCH;
     return svdd_launch_timed(span.all(), backbone_kernel<true, false, 1>, dim3((unsigned)n), dim3(512), lds, stream, a, BackboneSave{});
   }
-  if (svdd_launch_timed(span.first(), backbone_worklist_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, x, x_prev, n, L, lead,
+  if (svdd_launch_timed(span.first(), backbone_worklist_kernel<>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, x, x_prev, n, L, lead,
                         max_item, items, stat) != SVDD_OK)
     return SVDD_E_LAUNCH;
-  BackboneSegArgs sa{x, table0, tiles, vec, planes, items, n, L, 0};
+  BackboneSegArgs sa{x, table0, tiles, vec, planes, items, n, L, 0, nullptr, nullptr, 0};
   const int rows = 16 * (max_item + 2);
   const size_t slds = sizeof(float) * ((size_t)rows * BB_AP + 5 * (size_t)rows + rows + 8);
   const dim3 sgrid((unsigned)n * SEG_SLOTS);
   void (*seg)(BackboneSegArgs) = max_item == 4 ? backbone_seg_kernel<4> : backbone_seg_kernel<2>;
+  svdd_raise_lds_limit(seg, slds);                        // once for the `lead` launches below
+  for (int k = 1; k <= lead; ++k) {
+    sa.layer = k;
+    if (svdd_launch(seg, sgrid, dim3(256), slds, stream, sa) != SVDD_OK) return SVDD_E_LAUNCH;
+  }
+  return svdd_launch_timed(span.last(), backbone_kernel<true, false, 2>, dim3((unsigned)n), dim3(512), lds, stream, a, BackboneSave{});
+}
+
+// svdd_backbone_incr2_f32: the same forward with the segment launches reading a compact, size-ordered list. Workgroups per CU of
+// a segment launch: the dynamic-LDS request is padded until only g_incr_residency fit (0: no padding, as many as the kernel's own
+// image and registers allow — 4 for items of <= 2 tiles, 6 for 1-tile items, 3 for <= 4).
+constexpr int INCR_DEFAULT_RESIDENCY = 0;
+constexpr size_t CU_LDS_BYTES = 160 * 1024;              // gfx950
+static int g_incr_residency = INCR_DEFAULT_RESIDENCY;
+
+extern "C" int svdd_backbone_incr_set_residency(int wg_per_cu) {
+  if (wg_per_cu < 0 || wg_per_cu > 8) return SVDD_E_ARG;
+  g_incr_residency = wg_per_cu;
+  return SVDD_OK;
+}
+
+extern "C" int svdd_backbone_incr2_f32(const uint8_t* x, const float* table0, const float* tiles, const float* vec, const float* w2,
+                                       float* out, int n, int L, int nlayers, const int* dilations, int lead, float* planes,
+                                       uint8_t* x_prev, int32_t* items, unsigned long long* stat, int first, int max_item,
+                                       int32_t* order, int32_t* order_count, void* stream) {
+  if (!x || !table0 || !tiles || !vec || !w2 || !out || !dilations || !planes || !x_prev || !items || !order || !order_count ||
+      n <= 0 || n > 65536 || L <= TW_ROWS / 2 || L > TW_ROWS || nlayers <= 0 || nlayers > BB_MAXL || lead < 2 || lead > nlayers ||
+      (max_item != 1 && max_item != 2 && max_item != 4))
+    return SVDD_E_ARG;
+  for (int i = 0; i < lead; ++i) if (dilations[i] != 1) return SVDD_E_ARG;
+  BackboneArgs a;
+  if (!backbone_args(a, x, table0, tiles, vec, w2, out, n, L, 1, nlayers, dilations)) return SVDD_E_ARG;
+  a.planes = planes; a.planes_P = lead;
+  const SvddLds lds = svdd_lds_raised(backbone_lds_bytes(nlayers, 3));
+  SvddSpan span(SVDD_SLOT_BACKBONE);                      // ONE span per forward over all its launches
+  if (first) {
+    if (hipMemcpyAsync(x_prev, x, (size_t)n * L, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return SVDD_E_LAUNCH;
+    return svdd_launch_timed(span.all(), backbone_kernel<true, false, 1>, dim3((unsigned)n), dim3(512), lds, stream, a, BackboneSave{});
+  }
+  const int slots = max_item == 1 ? TW_RT : SEG_SLOTS;    // 13 one-tile items in a row that changed everywhere
+  if (svdd_launch_timed(span.first(), max_item == 1 ? backbone_worklist_kernel<TW_RT> : backbone_worklist_kernel<SEG_SLOTS>,
+                        dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, x, x_prev, n, L, lead, max_item, items, stat) != SVDD_OK)
+    return SVDD_E_LAUNCH;
+  if (svdd_launch(max_item == 1 ? backbone_order_kernel<TW_RT> : backbone_order_kernel<SEG_SLOTS>, dim3((unsigned)lead), dim3(256), 0, stream,
+                  items, n, order, order_count) != SVDD_OK)
+    return SVDD_E_LAUNCH;
+  BackboneSegArgs sa{x, table0, tiles, vec, planes, items, n, L, 0, order, order_count, n * slots};
+  const int rows = 16 * (max_item + 2);
+  size_t slds = sizeof(float) * ((size_t)rows * BB_AP + 5 * (size_t)rows + rows + 8);
+  if (g_incr_residency > 0) {                             // one request more than CU_LDS_BYTES / (r + 1): r + 1 workgroups no longer fit
+    const size_t pad = (CU_LDS_BYTES / (size_t)(g_incr_residency + 1) / 1024 + 1) * 1024;
+    if (pad > slds) slds = pad;
+  }
+  const dim3 sgrid((unsigned)(n * slots));
+  void (*seg)(BackboneSegArgs) = max_item == 4 ? backbone_seg_kernel<4, true> : max_item == 2 ? backbone_seg_kernel<2, true>
+                                                                                                : backbone_seg_kernel<1, true>;
   svdd_raise_lds_limit(seg, slds);                        // once for the `lead` launches below
   for (int k = 1; k <= lead; ++k) {
     sa.layer = k;

@@ -57,7 +57,7 @@ Engine knobs (attributes; defaults reproduce the reference's observable behaviou
   incremental_backbone  "auto" (default): the SVDD-MC skipping loop at 104 < L <= 208 (one sequence per backbone tile, fp32, CNN backbone
                    with a leading run of dilation-1 layers, more than 128 rows) carries the residual stream behind those layers
                    across the steps and recomputes, per step, only the 16-row tiles a changed token can reach
-                   (svdd_backbone_incr_f32; the remaining layers run from the last carried plane). Same logits bit for bit
+                   (svdd_backbone_incr2_f32; the remaining layers run from the last carried plane). Same logits bit for bit
                    (tests/test_backbone_incremental_gpu.py). "on": wherever the kernels apply, whatever the batch; "off". Off under
                    graph capture. The first forward of such a decode runs on all B rows (it fills the planes): dedup_prior does not
                    apply to it.
@@ -1061,7 +1061,7 @@ class Diffusion(nn.Module):
 
     def _incremental_stem(self, B, L):
         """(FusedBackbone, its carried-stem state for this decode) where the SVDD-MC skipping loop forwards through
-        svdd_backbone_incr_f32 (see incremental_backbone), else (None, None)."""
+        svdd_backbone_incr2_f32 (see incremental_backbone), else (None, None)."""
         if self.incremental_backbone not in ("auto", "on", "off"):
             raise ValueError(f"incremental_backbone = {self.incremental_backbone!r}: expected 'auto', 'on' or 'off'")
         if self.incremental_backbone == "off" or _capturing():

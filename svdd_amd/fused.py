@@ -414,11 +414,21 @@ def backbone_cnn(tokens, pk, count=None, out=None, row_idx=None, scatter=False):
     return out
 
 
-INCR_MAX_ITEM = 2          # row tiles per work item of the incremental stem (2 or 4; tools/incremental_backbone_ab.py measures both)
+INCR_MAX_ITEM = 2          # row tiles per work item of the incremental stem (1, 2 or 4; tools/incremental_backbone_ab.py measures them)
+INCR_ORDERED = True        # True: svdd_backbone_incr2_f32 (segment launches dealt from the size-ordered list); False: svdd_backbone_incr_f32
+INCR_RESIDENCY = 0         # segment workgroups per CU under the ordered list (0 = no LDS padding); set with set_incr_residency
+INCR_SLOTS = 13            # work-list slots per (layer, row) the buffers are sized for: 7 for items <= 2 / 4, 13 for 1-tile items
+
+
+def set_incr_residency(r):
+    """svdd_backbone_incr_set_residency: at most r segment workgroups per CU from the next forward on (0 = no LDS padding)."""
+    global INCR_RESIDENCY
+    _lib.call("svdd_backbone_incr_set_residency", int(r))
+    INCR_RESIDENCY = int(r)
 
 
 def leading_dilation1(dil):
-    """Length of the leading run of dilation-1 layers (the stem svdd_backbone_incr_f32 carries across steps)."""
+    """Length of the leading run of dilation-1 layers (the stem svdd_backbone_incr2_f32 carries across steps)."""
     n = 0
     while n < len(dil) and dil[n] == 1:
         n += 1
@@ -426,22 +436,24 @@ def leading_dilation1(dil):
 
 
 class IncrementalStem:
-    """Caller-owned state of svdd_backbone_incr_f32 for n sequences of length L: the carried planes, the tokens they belong to, the
-    step's work list and the device counter of marked tile-layers. Allocated once and reused across decodes (FusedBackbone keeps
+    """Caller-owned state of svdd_backbone_incr2_f32 for n sequences of length L: the carried planes, the tokens they belong to, the
+    step's work list, its size-ordered form (order, order_count) and the device counter of marked tile-layers. Allocated once and reused across decodes (FusedBackbone keeps
     one per shape); `valid` says whether planes / x_prev describe the tokens of the last forward of THIS decode."""
 
     def __init__(self, n, L, lead, dev):
         self.n, self.L, self.lead = n, L, lead
         self.planes = torch.empty((lead, n, 208, 128), dtype=torch.float32, device=dev)
         self.x_prev = torch.empty((n, L), dtype=torch.uint8, device=dev)
-        self.items = torch.zeros((lead, n, 7), dtype=torch.int32, device=dev)
+        self.items = torch.zeros((lead, n, INCR_SLOTS), dtype=torch.int32, device=dev)      # read as [lead][n][7] for items <= 2 / 4
+        self.order = torch.zeros((lead, n * INCR_SLOTS), dtype=torch.int32, device=dev)
+        self.order_count = torch.zeros(lead, dtype=torch.int32, device=dev)
         self.stat = torch.zeros(1, dtype=torch.int64, device=dev)
         self.valid = False
         self.forwards = 0                                # incremental (not first) forwards since the counter was last read
 
 
 def backbone_cnn_incremental(tokens, pk, st, out=None, max_item=None):
-    """backbone_cnn(tokens, pk) — the same bits — through the carried stem `st` (HIP entry svdd_backbone_incr_f32): the first call
+    """backbone_cnn(tokens, pk) — the same bits — through the carried stem `st` (HIP entry svdd_backbone_incr2_f32): the first call
     after st.valid = False runs the whole forward and fills the planes, every later one recomputes only the tiles of the leading
     dilation-1 layers that a changed token can reach, then the remaining layers from the last plane."""
     assert tokens.is_cuda and tokens.dtype == torch.uint8 and tokens.is_contiguous() and tuple(tokens.shape) == (st.n, st.L)
@@ -450,9 +462,14 @@ def backbone_cnn_incremental(tokens, pk, st, out=None, max_item=None):
         out = torch.empty((n, L, 5), dtype=torch.float32, device=tokens.device)
     dil = (ctypes.c_int * len(pk["dil"]))(*pk["dil"])
     first = not st.valid
-    _lib.call("svdd_backbone_incr_f32", tokens, pk["table0"], pk["tiles"], pk["vec"], pk["w2"], out, n, L, len(pk["dil"]), dil,
-              st.lead, st.planes, st.x_prev, st.items, st.stat, int(first), int(max_item or INCR_MAX_ITEM),
-              ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))      # this entry takes its stream as an explicit argument
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)        # these entries take their stream as an explicit argument
+    if INCR_ORDERED:
+        _lib.call("svdd_backbone_incr2_f32", tokens, pk["table0"], pk["tiles"], pk["vec"], pk["w2"], out, n, L, len(pk["dil"]), dil,
+                  st.lead, st.planes, st.x_prev, st.items, st.stat, int(first), int(max_item or INCR_MAX_ITEM), st.order,
+                  st.order_count, stream)
+    else:
+        _lib.call("svdd_backbone_incr_f32", tokens, pk["table0"], pk["tiles"], pk["vec"], pk["w2"], out, n, L, len(pk["dil"]), dil,
+                  st.lead, st.planes, st.x_prev, st.items, st.stat, int(first), int(max_item or INCR_MAX_ITEM), stream)
     st.valid = True
     st.forwards += 0 if first else 1
     return out
@@ -1105,7 +1122,7 @@ class FusedBackbone(nn.Module):
         return self.one_launch and self.use_one_launch and L <= 208 and self.min_tiles_one_launch == 0
 
     def incremental_ok(self, n, L, any_batch=False):
-        """True where a decode's forwards may go through the carried stem (svdd_backbone_incr_f32): the fp32 one-launch kernel, one
+        """True where a decode's forwards may go through the carried stem (svdd_backbone_incr2_f32): the fp32 one-launch kernel, one
         sequence per tile, a leading run of at least two dilation-1 layers — and a batch that the one-workgroup-per-sequence
         kernel takes whole (small batches and tail rounds run on several workgroups per sequence instead; any_batch: whatever n)."""
         return (self.kernel_ok(L) and self.precision == "f32" and 104 < L <= 208 and leading_dilation1(self.ol_dil) >= 2 and

@@ -7,7 +7,7 @@
 cd "$(dirname "$0")/.."
 TAG=${1:-r06}
 OUT=gpurun_out/${TAG}_tools_check.txt
-SKIP="exp_variants.py lpt_phase_timing.py lpt_step_stamps.py tower_lp_timing.py gen_lpt_taps.py stats_summary.py trace_summary.py kernel_stats_top.py perturbation_f16x3_droplo.py"
+SKIP="exp_variants.py lpt_phase_timing.py lpt_step_stamps.py tower_lp_timing.py gen_lpt_taps.py stats_summary.py trace_summary.py stem_dispatch_trace.py kernel_stats_top.py perturbation_f16x3_droplo.py"
 : > $OUT
 for f in tools/*.py; do
   b=$(basename $f)
