@@ -164,6 +164,35 @@ int svdd_elbo_nll(const float* logits, int layout, const uint8_t* xt, const uint
                   float* nll, double* row_sum, double* seq_mean, int32_t* err, void* stream);
 
 /*
+ * Re-mask refinement and template-constrained design (ABI 16): the boundary between two guided decodes of the same rows, in
+ * ONE launch and without a synchronisation. Per row b:
+ *   accept   only when x_old, score_new and score_old are all given (x_keep and score_keep are then required): the row keeps its
+ *            new version iff score_new[b] > score_old[b] — a NaN score_new and a tie keep the old row. Otherwise the new row is
+ *            kept. x_keep [B, L] u8 = the kept row (may be NULL when nothing is judged), score_keep [B] f32 = its score (may be
+ *            NULL; needs score_new), accepted [B] i32 (may be NULL) = 1 where the new row was kept.
+ *            x_keep MAY BE x_old (a lane writes only the positions it has read), and score_keep may be score_old (the row's wave
+ *            reads both scores before its one store); x_keep must not be x_new.
+ *   re-mask  x_t[b, l] = MASK iff u[b, l] < move_chance and frozen[b, l] == 0, else x_keep[b, l]  (q_xt, diffusion_gosai.py:738-749,
+ *            under a frozen mask). frozen [B, L] u8 or NULL (nothing frozen). A MASK token of the kept row stays MASK, frozen or
+ *            not. nmasked [B] i32 (may be NULL) = MASK tokens of x_t[b], those included. x_t may be NULL: accept only (frozen
+ *            and nmasked must then be NULL; rng is not read). x_t must be none of the other buffers, frozen none of the token buffers (SVDD_E_ARG).
+ *   err      device i32 (may be NULL, caller-zeroed): set to 1 if the kept row holds a token > 4 (copied through as it is); read by
+ *            the caller after the stream, as svdd_elbo_nll's.
+ *  move_chance  ONE fp32 scalar in [0, 1], computed by the caller in both rng modes with the reference's fp32 torch ops
+ *            (1 - exp(-sigma(t))): a 1-ulp difference flips masks.
+ *  REPLAY    rng->uniforms = one block of B L fp32 in [b][l] order, the torch.rand(*x.shape) of q_xt; uniforms_rows must be 0.
+ *  PHILOX    counter (word 0, 1, 2, 3) = (row_offset + b low, high, round << 16 | j, 1) with round = rng->step <= 65535: stream
+ *            word 1 (0 = svdd_propose / svdd_classifier_propose, 2 = the multinomial select, 3 = ELBO). Block j gives the
+ *            uniforms of positions 4 j .. 4 j + 3 (words 0..3, top 24 bits). L <= 262144.
+ *  Rows of a multiple-of-4 length in 4-byte aligned buffers move as 32-bit words, any other shape byte by byte: same results.
+ *  No result depends on the launch shape or on how rows are split over calls (one wave per row, keyed by the global row).
+ *  The stream is an explicit argument (as svdd_backbone_incr*_f32).
+ */
+int svdd_refine_remask(const uint8_t* x_new, const uint8_t* x_old, const float* score_new, const float* score_old,
+                       const uint8_t* frozen, float move_chance, int B, int L, const svdd_rng_t* rng, uint8_t* x_keep,
+                       float* score_keep, int32_t* accepted, uint8_t* x_t, int32_t* nmasked, int32_t* err, void* on_stream);
+
+/*
  * svdd_select — replaces torch.stack(scores,1) -> softmax(dim=1) -> argmax(dim=1) ->
  * per-row Python gather + stack                     diffusion_gosai.py:1219-1227 (= :1451-1459)
  *
@@ -582,7 +611,7 @@ int svdd_device_info(char* arch, int arch_len, int* num_cu);
 
 /* ABI version of this header: bumped on any signature change. */
 int svdd_abi_version(void);
-#define SVDD_ABI_VERSION 15
+#define SVDD_ABI_VERSION 16
 
 /*
  * Enformer-shaped value trunk (BASELINE.json configs[3]; reference decode.py:78-80, Enformer.py:1271-1334 trunk, :1807-1884

@@ -13,7 +13,7 @@ CSRC = os.path.join(_HERE, "csrc")
 # SVDD_HIP_LIB: load another build of the library instead (the timing-experiment scripts under tools/ build patched
 # copies of the kernels in a scratch directory; the tracked sources are never edited in place)
 SO_PATH = os.environ.get("SVDD_HIP_LIB") or os.path.join(CSRC, "libsvdd_hip.so")
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 OK, E_ARG, E_LAUNCH, E_NODEVICE = 0, -1, -2, -3
 LAYOUT_BLV, LAYOUT_BVL = 0, 1
@@ -120,6 +120,7 @@ SIGNATURES = {
     "svdd_classifier_propose": (vp, i32, vp, vp, f32, f32, f32, i32, i32, RNG, vp, vp, vp, STREAM),
     "svdd_elbo_mask": (vp, i32, i32, i32, f64, RNG, vp, vp, vp, vp, vp, vp, STREAM),
     "svdd_elbo_nll": (vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, STREAM),
+    "svdd_refine_remask": (vp, vp, vp, vp, vp, f32, i32, i32, RNG, vp, vp, vp, vp, vp, vp, vp),
 }
 EXPORTS = tuple(SIGNATURES)
 

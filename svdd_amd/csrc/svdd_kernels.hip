@@ -13,6 +13,7 @@
 //   K6 transform_kernel  tokens -> one-hot
 //   K7 subs_logp_kernel  SUBS re-parameterisation alone
 //   K11 elbo_mask_kernel / K12 elbo_nll_kernel  ELBO scoring: masking of x0, the weighted SUBS token loss and its sums
+//   K13 refine_remask_kernel  the round boundary of re-mask refinement: accept the better version of a row, re-mask it
 //   K4 tds_resample_kernel  SMC/TDS resampling (baseline)
 #include <stdlib.h>
 #include <string.h>
@@ -1119,6 +1120,107 @@ __global__ __launch_bounds__(256) void elbo_nll_kernel(ElboNllArgs a) {
   if (a.seq_mean && threadIdx.x == 0) a.seq_mean[b] = __ddiv_rn(acc, (double)a.K);
 }
 
+// ------------------------------------------------- K13 the round boundary of re-mask refinement (ABI 16) ----
+// One wave per row, in one launch: ACCEPT (keep the new version of the row iff score_new > score_old; a NaN or a tie keeps the
+// old one) and RE-MASK (x_t = MASK where u < move_chance and the position is not frozen; q_xt, diffusion_gosai.py:738-749,
+// under a frozen mask). The accept decision is the row's, so every lane reads the two scores itself: nothing is exchanged
+// between lanes but the two counts. A lane owns the four positions of one Philox block; with L a multiple of 4 and aligned
+// rows (VEC) it moves them as one 32-bit word. Every output element is a function of (row, position) and the row's scores
+// alone, and a lane writes only positions it read itself: x_keep may be x_old.
+constexpr uint32_t REFINE_STREAM = 1u;   // Philox counter word 3: 0 = K1 / K10 draws, 2 = the multinomial select, 3 = ELBO, 1 = this
+
+struct RefineArgs {
+  const uint8_t* x_new; const uint8_t* x_old; const float* score_new; const float* score_old; const uint8_t* frozen;
+  float mc; int B, L; const float* uniforms; uint64_t seed, row_offset; uint32_t round;
+  uint8_t* x_keep; float* score_keep; int32_t* accepted; uint8_t* x_t; int32_t* nmasked; int32_t* err;
+};
+
+template <bool VEC>
+__device__ __forceinline__ uint32_t load4_u8(const uint8_t* p, int l0, int L) {
+  if (VEC) return *reinterpret_cast<const uint32_t*>(p + l0);
+  uint32_t v = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) v |= (l0 + i < L ? (uint32_t)p[l0 + i] : 0u) << (8 * i);
+  return v;
+}
+
+template <bool VEC>
+__device__ __forceinline__ void store4_u8(uint8_t* p, int l0, int L, uint32_t v) {
+  if (VEC) { *reinterpret_cast<uint32_t*>(p + l0) = v; return; }
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if (l0 + i < L) p[l0 + i] = (uint8_t)(v >> (8 * i));
+}
+
+template <bool REPLAY, bool VEC>
+__global__ __launch_bounds__(256) void refine_remask_kernel(RefineArgs a) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= a.B) return;                                             // whole waves only: the row is the wave's
+  const bool judged = a.x_old && a.score_new && a.score_old;
+  bool take_new = true;
+  float sk = a.score_new ? a.score_new[b] : 0.0f;
+  if (judged) {
+    const float so = a.score_old[b];
+    take_new = sk > so;                                             // false for a NaN and for a tie: the old row stays
+    sk = take_new ? sk : so;
+  }
+  if (lane == 0) {
+    if (a.score_keep) a.score_keep[b] = sk;
+    if (a.accepted) a.accepted[b] = take_new ? 1 : 0;
+  }
+  const uint8_t* src = (take_new ? a.x_new : a.x_old) + b * a.L;
+  const uint8_t* fz = a.frozen ? a.frozen + b * a.L : nullptr;
+  uint8_t* keep = a.x_keep ? a.x_keep + b * a.L : nullptr;
+  uint8_t* xt = a.x_t ? a.x_t + b * a.L : nullptr;
+  const uint64_t grow = a.row_offset + (uint64_t)b;
+  int cnt = 0;
+  bool bad = false;
+  for (int l0 = lane * 4; l0 < a.L; l0 += 4 * WAVE) {
+    const uint32_t tok4 = load4_u8<VEC>(src, l0, a.L);
+    if (keep) store4_u8<VEC>(keep, l0, a.L, tok4);
+    if (!xt) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) bad |= ((tok4 >> (8 * i)) & 0xFFu) > (uint32_t)MASK;
+      continue;
+    }
+    const uint32_t fz4 = fz ? load4_u8<VEC>(fz, l0, a.L) : 0u;
+    float u[4];
+    if (REPLAY) {
+      const float* ur = a.uniforms + b * a.L;
+      if (VEC) {
+        const float4 v = *reinterpret_cast<const float4*>(ur + l0);
+        u[0] = v.x; u[1] = v.y; u[2] = v.z; u[3] = v.w;
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) u[i] = l0 + i < a.L ? ur[l0 + i] : 1.0f;
+      }
+    } else {
+      uint32_t c[4] = {(uint32_t)grow, (uint32_t)(grow >> 32), (a.round << 16) | (uint32_t)(l0 / 4), REFINE_STREAM};
+      philox4x32_10(c, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
+#pragma unroll
+      for (int i = 0; i < 4; ++i) u[i] = u24(c[i]);
+    }
+    uint32_t out4 = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const uint32_t tok = (tok4 >> (8 * i)) & 0xFFu;
+      const bool open = ((fz4 >> (8 * i)) & 0xFFu) == 0u;
+      const bool m = l0 + i < a.L && (tok == (uint32_t)MASK || (u[i] < a.mc && open));   // torch.rand(*x.shape) < move_chance, :745-746
+      bad |= tok > (uint32_t)MASK;
+      out4 |= (m ? (uint32_t)MASK : tok) << (8 * i);
+      cnt += m ? 1 : 0;
+    }
+    store4_u8<VEC>(xt, l0, a.L, out4);
+  }
+  if (bad && a.err) a.err[0] = 1;
+  if (a.nmasked && xt) {
+#pragma unroll
+    for (int off = WAVE / 2; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, WAVE);
+    if (lane == 0) a.nmasked[b] = cnt;
+  }
+}
+
 // -------------------------------------------------------------------- K4 TDS resample ----
 // numpy's pairwise float32 sum (np.add.reduce), the order `ratio.sum()` uses at :1282: the array is halved (left half
 // rounded down to a multiple of 8) until a block has <= 128 elements; a block is summed with 8 running accumulators.
@@ -1862,6 +1964,35 @@ int svdd_elbo_nll(const float* logits, int layout, const uint8_t* xt, const uint
   if ((int64_t)n * K * L * V >= ((int64_t)1 << 40)) return SVDD_E_ARG;
   const ElboNllArgs a{logits, layout, xt, x0, w, n, L, K, nll, row_sum, seq_mean, err};
   return svdd_launch(elbo_nll_kernel, dim3((unsigned)n), dim3(256), 0, stream, a);
+}
+
+int svdd_refine_remask(const uint8_t* x_new, const uint8_t* x_old, const float* score_new, const float* score_old,
+                       const uint8_t* frozen, float move_chance, int B, int L, const svdd_rng_t* rng, uint8_t* x_keep,
+                       float* score_keep, int32_t* accepted, uint8_t* x_t, int32_t* nmasked, int32_t* err, void* on_stream) {
+  if (!x_new || (!x_keep && !x_t) || B <= 0 || L <= 0 || L > 4 * 65536) return SVDD_E_ARG;
+  if ((int64_t)B * L >= (int64_t)1 << 40) return SVDD_E_ARG;
+  const bool judged = x_old && score_new && score_old;
+  if (judged && (!x_keep || !score_keep)) return SVDD_E_ARG;        // a decision nobody could see
+  if (score_keep && !score_new) return SVDD_E_ARG;
+  if (x_keep == x_new || (x_t && (x_t == x_new || x_t == x_old || x_t == x_keep || x_t == frozen)) ||
+      (frozen && (frozen == x_keep || frozen == x_new))) return SVDD_E_ARG;   // an output that is another row's input
+  bool replay = false;
+  if (x_t) {
+    if (!rng || !(move_chance >= 0.0f && move_chance <= 1.0f)) return SVDD_E_ARG;
+    replay = rng->kind == SVDD_RNG_REPLAY;
+    if (replay ? (!rng->uniforms || rng->uniforms_rows != 0) : (rng->kind != SVDD_RNG_PHILOX || rng->step > 65535u)) return SVDD_E_ARG;
+  } else if (nmasked || frozen) {
+    return SVDD_E_ARG;
+  }
+  const auto al = [](const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; };
+  const bool vec = L % 4 == 0 && al(x_new, 4) && al(x_old, 4) && al(frozen, 4) && al(x_keep, 4) && al(x_t, 4) &&
+                   (!replay || al(rng->uniforms, 16));
+  const RefineArgs a{x_new, x_old, score_new, score_old, frozen, move_chance, B, L, replay ? rng->uniforms : nullptr,
+                     x_t && !replay ? rng->seed : 0, x_t && !replay ? rng->row_offset : 0, x_t && !replay ? rng->step : 0u,
+                     x_keep, score_keep, accepted, x_t, nmasked, err};
+  auto k = replay ? (vec ? refine_remask_kernel<true, true> : refine_remask_kernel<true, false>)
+                  : (vec ? refine_remask_kernel<false, true> : refine_remask_kernel<false, false>);
+  return svdd_launch(k, dim3((unsigned)(((int64_t)B + 3) / 4)), dim3(256), 0, on_stream, a);
 }
 
 int svdd_tds_resample(const float* reward_num, const float* reward_den, double alpha, const uint8_t* sample,

@@ -9,6 +9,8 @@ methods on the SVDD decode path, so `BaseModel`/`decode.py`-style callers work u
     _ddpm_update_finetune[_controlled[_twedie|_TDS|_DPS]], _ddpm_update_finetune_classfier, compute_gradient,
     transform_samples, and the ELBO scoring of clean sequences: _sample_t, q_xt, _forward_pass_diffusion, _loss
     (plus sequence_nll / nll_metrics, the per-sequence API built on them)
+and, without a reference method of their own (a loop of the reference's q_xt and per-step updates from a given state):
+    decode_sample_from, controlled_sample_from (template-constrained design), renoise, refine (re-mask refinement)
 
 What differs is where the work runs: everything between "backbone logits" and "next x_t" is one
 or two launches of the hand-written HIP kernels (svdd_amd/csrc, C ABI include/svdd_hip.h) instead
@@ -262,6 +264,8 @@ class Diffusion(nn.Module):
         self._replay_checked = None      # scope id of the sharded replay decode whose generator state was compared across ranks
         self._classifier_fused_last = None   # classifier guidance: whether the last step's gradient ran on the fused kernels (no autograd)
         self.elbo_trace = None           # set to a list to record (t, sigma, dsigma, move_chance, w, xt) of every _forward_pass_diffusion
+        self._from_state = False         # set by _decode_start: the running decode starts from a caller's state, not from the all-MASK prior
+        self._step_base = 0              # added to the step index in every Philox key: refine() gives each round its own range of keys
 
     # ------------------------------------------------------------------ plumbing ----
     @property
@@ -273,10 +277,10 @@ class Diffusion(nn.Module):
             raise ops.SvddError("the SVDD sampler runs on the GPU only (move the model with .cuda()); "
                                 "there is no CPU fallback for the hot path")
 
-    def _schedule(self, num_steps, eps):
-        key = (num_steps, eps)
+    def _schedule(self, num_steps, eps, t_start=1.0):
+        key = (num_steps, eps, float(t_start))
         if key not in self._sched_cache:
-            tab, timesteps, dt = noise_schedule.move_chance_table(self.noise, num_steps, eps)
+            tab, timesteps, dt = noise_schedule.move_chance_table(self.noise, num_steps, eps, float(t_start))
             self._sched_cache[key] = (tab.numpy().copy(), timesteps, dt)
         return self._sched_cache[key]
 
@@ -378,7 +382,7 @@ class Diffusion(nn.Module):
     def _prior_dedup_ok(self, x_u8):
         """True when the net evaluations of the prior state x_u8 (every row all-MASK by construction) may run on one row: more than
         one row, and the one-launch backbone kernel (a row's logits are then the same bits wherever and with whomever it is evaluated)."""
-        return (self.dedup_prior and x_u8.shape[0] > 1 and x_u8.is_cuda and not _capturing() and
+        return (self.dedup_prior and not self._from_state and x_u8.shape[0] > 1 and x_u8.is_cuda and not _capturing() and
                 self._fused_backbone_or_none(x_u8.shape[1]) is not None)
 
     def _prior_logits(self, x_u8):
@@ -441,7 +445,7 @@ class Diffusion(nn.Module):
                 u = torch.rand(shape).to(logits.device, non_blocking=True)   # torch's global CPU generator
             return ops.Rng(uniforms=u, uniforms_layout=ul, **extra)
         if self.rng_mode == "philox":
-            return ops.Rng(seed=self.philox_seed, row_offset=self.row_offset, step=step)
+            return ops.Rng(seed=self.philox_seed, row_offset=self.row_offset, step=self._step_base + step)
         raise ValueError(f"rng_mode {self.rng_mode!r}")
 
     def _select_args(self, step):
@@ -451,7 +455,7 @@ class Diffusion(nn.Module):
             return mode, None
         if self.rng_mode != "philox":
             raise ValueError("select_mode='multinomial' needs rng_mode='philox'")
-        return mode, ops.Rng(seed=self.philox_seed, row_offset=self.row_offset, step=step)
+        return mode, ops.Rng(seed=self.philox_seed, row_offset=self.row_offset, step=self._step_base + step)
 
     def _select(self, scores, cand, step):
         mode, rng = self._select_args(step)
@@ -474,12 +478,45 @@ class Diffusion(nn.Module):
     def _num_steps(self, num_steps):
         return self.config.sampling.steps if num_steps is None else num_steps
 
-    def _decode_start(self, num_steps, eps, eval_sp_size):
-        """What every sampler loop opens with -> (B, L, S, schedule table [S, 3], the all-MASK prior x_T as u8 [B, L], :751-753)."""
+    def _decode_start(self, num_steps, eps, eval_sp_size, x_init=None, t_start=1.0, check_tokens=True):
+        """What every sampler loop opens with -> (B, L, S, schedule table [S, 3], the all-MASK prior x_T as u8 [B, L], :751-753).
+        x_init [B, L] (tokens 0..3, 4 = MASK, on the model's device): the decode starts from this state at t = t_start instead — the
+        schedule is linspace(t_start, eps, S + 1), S = max(1, ceil(t_start * config.sampling.steps)) unless given (the full decode's
+        dt), and the shortcuts that rely on B identical all-MASK rows are off for the decode (self._from_state; _prior_dedup_ok).
+        check_tokens False: the caller vouches for the tokens (a state svdd_refine_remask wrote) and no value is read back."""
         self._require_gpu()
-        B, L, S = self._batch_size(eval_sp_size), self.config.model.length, self._num_steps(num_steps)
-        sched, _, _ = self._schedule(S, eps)
-        return B, L, S, sched, torch.full((B, L), self.mask_index, dtype=torch.uint8, device=self.device)
+        self._from_state = x_init is not None
+        if x_init is None:
+            if float(t_start) != 1.0:
+                raise ValueError("t_start needs a start state (x_init): the all-MASK prior belongs to t = 1")
+            B, L, S = self._batch_size(eval_sp_size), self.config.model.length, self._num_steps(num_steps)
+            sched, _, _ = self._schedule(S, eps)
+            return B, L, S, sched, torch.full((B, L), self.mask_index, dtype=torch.uint8, device=self.device)
+        if self.time_conditioning:
+            raise NotImplementedError("decoding from a given state: time-conditioned backbones are not supported (the work-skipping "
+                                      "loops and the fused backbone run at sigma = 0)")
+        if not isinstance(x_init, torch.Tensor) or not x_init.is_cuda or x_init.device != self.device:
+            raise ops.SvddError("x_init must be a tensor on the model's GPU (the SVDD hot path has no CPU fallback)")
+        L = self.config.model.length
+        if x_init.dim() != 2 or x_init.shape[0] == 0 or x_init.shape[1] != L:
+            raise ValueError(f"x_init must be [B, {L}] (config.model.length) with B > 0, got {tuple(x_init.shape)}")
+        if x_init.dtype.is_floating_point or x_init.dtype == torch.bool:
+            raise ValueError(f"x_init must hold integer tokens, got {x_init.dtype}")
+        self._check_t(t_start, eps, "t_start")
+        if check_tokens:
+            lo, hi = torch.aminmax(x_init)
+            if int(lo) < 0 or int(hi) > self.mask_index:
+                raise ops.SvddError(f"x_init holds a token outside 0..{self.mask_index} (0..3 = A, C, G, T; {self.mask_index} = MASK)")
+        S = max(1, math.ceil(float(t_start) * self.config.sampling.steps)) if num_steps is None else int(num_steps)
+        if S <= 0:
+            raise ValueError(f"num_steps must be positive, got {num_steps}")
+        sched, _, _ = self._schedule(S, eps, t_start)
+        return x_init.shape[0], L, S, sched, self._tokens_u8(x_init).contiguous().clone()
+
+    @staticmethod
+    def _check_t(t, eps, name):
+        if not (float(eps) < float(t) <= 1.0):
+            raise ValueError(f"{name} must lie in (eps, 1] = ({eps}, 1], got {t}")
 
     def _step_result(self, x_next, x, q):
         """What the reference's per-step methods return: (x_next int64, x, q_xs, copy_flag)."""
@@ -959,9 +996,9 @@ class Diffusion(nn.Module):
             raise NotImplementedError("cdq=True is a value-function *training* data path (Enformer.py:163-267)")
         return self._unguided_sample(num_steps, eps, eval_sp_size, keep_mid=True)
 
-    def _unguided_sample(self, num_steps, eps, eval_sp_size, keep_mid):
+    def _unguided_sample(self, num_steps, eps, eval_sp_size, keep_mid, x_init=None, t_start=1.0):
         """The un-guided loop -> (x_0 int64, [x_t int64 after every step but the last] if keep_mid else [])."""
-        B, L, S, sched, x = self._decode_start(num_steps, eps, eval_sp_size)
+        B, L, S, sched, x = self._decode_start(num_steps, eps, eval_sp_size, x_init, t_start)
         mid_x = []
         for i in range(S):
             logits = self._prior_logits(x) if i == 0 else self._backbone_logits(x)
@@ -976,8 +1013,11 @@ class Diffusion(nn.Module):
     def controlled_sample(self, pre_scorer_embedding, pre_scorer_head, num_steps=None, eps=1e-5,
                           eval_sp_size=None, sample_M=10):
         """SVDD-MC decode (:1021-1061): S x [backbone -> propose -> value net -> select], then noise removal."""
-        B, L, S, sched, x = self._decode_start(num_steps, eps, eval_sp_size)
-        M = sample_M
+        return self._controlled_sample(pre_scorer_embedding, pre_scorer_head, sample_M,
+                                       *self._decode_start(num_steps, eps, eval_sp_size))
+
+    def _controlled_sample(self, pre_scorer_embedding, pre_scorer_head, M, B, L, S, sched, x):
+        """The SVDD-MC loops from the start state x (the prior, or a caller's state: _decode_start)."""
         cand = torch.empty((B, M, L), dtype=torch.uint8, device=self.device)
         onehot = torch.empty((B * M, L, 4), dtype=torch.float32, device=self.device)
         fn = self.value_callable(pre_scorer_embedding, pre_scorer_head)
@@ -993,6 +1033,183 @@ class Diffusion(nn.Module):
             self._record(logits, scores, x)
             x = self._select(scores, cand, i)
         return self._noise_removal(x)
+
+    # ------------------------------------------- decoding from a given state: templates and re-mask refinement (ABI 16) ----
+    # The per-step updates take any (x, t, dt) and carry every non-MASK token forward (copy_flag, :1199, :1203), and SUBS keeps an
+    # unmasked position at the final argmax: a decode may therefore start from ANY state — a template whose open positions are
+    # MASK (t_start = 1), or a finished design re-noised to t0 < 1 by q_xt (:738-749) — over linspace(t_start, eps, S + 1). The
+    # loops are the samplers' own; only the shortcuts that rely on B identical all-MASK rows are off (_decode_start, _from_state).
+    #   replay: a reference-side loop of q_xt + per-step updates draws torch.rand(B, L) for the mask, then the decode's own
+    #           uniforms; the generator ends where that loop leaves it. Refused under a batch-sharded run (the mask block is the
+    #           batch's own, svdd_refine_remask takes no row slice of a larger block).
+    #   philox: the mask is keyed by (philox_seed, row_offset + b, round, position) on stream word 1; the decode of round r uses the
+    #           step keys steps_full + r S .. steps_full + (r + 1) S - 1 (steps_full = config.sampling.steps, S = steps per round):
+    #           svdd_propose packs the step into the top 16 bits of counter word 2, so every key must stay below 65536, and no
+    #           (round, step) of a row shares a key with another — nor with a default-length decode from the prior, whose design
+    #           the rounds usually refine.
+    def _from_state_checks(self):
+        self._require_gpu()
+        if self.rng_mode == "replay" and self._shard is not None and self._shard[3] > 1:
+            raise ops.SvddError("decoding from a given state in replay mode is not batch-sharded (use rng_mode = 'philox': its "
+                                "counters are keyed by the global row)")
+
+    def _move_chance(self, t):
+        """1 - exp(-sigma(t)) of ONE t, with the reference's fp32 torch ops on the host (:1725-1729), as _elbo_scalars."""
+        sigma, _ = self.noise(torch.tensor([float(t)], dtype=torch.float32))
+        return float((1 - torch.exp(-sigma))[0])
+
+    def _mask_rng(self, B, L, round):
+        """The Rng of one svdd_refine_remask launch: replay = the next torch.rand(B, L) of the reference's stream (generated on the
+        device inside a sampler call, like the decode's own uniforms); philox = (philox_seed, row_offset, round)."""
+        if self.rng_mode == "replay":
+            if self.replay_rng == "device" and self._scope_depth > 0 and not _capturing():
+                if self._replay_stream is None:
+                    self._replay_stream = ops.DeviceReplayStream(self.device)
+                return ops.Rng(uniforms=self._replay_stream.uniforms(B * L, prefetch=False).view(B, L))
+            return ops.Rng(uniforms=torch.rand(B, L).to(self.device, non_blocking=True))
+        if self.rng_mode == "philox":
+            if not 0 <= int(round) <= 65535:
+                raise ops.SvddError(f"round {round}: the Philox counter of svdd_refine_remask holds 16 bits of it")
+            return ops.Rng(seed=self.philox_seed, row_offset=self.row_offset, step=int(round))
+        raise ValueError(f"rng_mode {self.rng_mode!r}")
+
+    @_decode_scope
+    @torch.no_grad()
+    def decode_sample_from(self, x_init, t_start=1.0, num_steps=None, eps=1e-5):
+        """Un-guided decode from the state x_init [B, L] (tokens 0..3 are kept, 4 = MASK is filled in) at t = t_start -> LongTensor[B, L]."""
+        self._from_state_checks()
+        return self._unguided_sample(num_steps, eps, None, keep_mid=False, x_init=x_init, t_start=t_start)[0]
+
+    @_decode_scope
+    @torch.no_grad()
+    def controlled_sample_from(self, x_init, pre_scorer_embedding, pre_scorer_head, t_start=1.0, num_steps=None, eps=1e-5,
+                               sample_M=10):
+        """SVDD-MC decode from the state x_init [B, L] at t = t_start -> LongTensor[B, L]: the loops of controlled_sample over
+        linspace(t_start, eps, S + 1). Every non-MASK token of x_init is in the result (a template: MASK marks the open positions,
+        t_start = 1; a re-noised design: renoise(x0, t0), t_start = t0). num_steps None: max(1, ceil(t_start * config.sampling.steps))."""
+        self._from_state_checks()
+        return self._controlled_sample(pre_scorer_embedding, pre_scorer_head, sample_M,
+                                       *self._decode_start(num_steps, eps, None, x_init, t_start))
+
+    @_decode_scope
+    @torch.no_grad()
+    def renoise(self, x0, t, frozen=None, round=0):
+        """q_xt (:738-749) under a frozen mask: x_t = MASK where u < move_chance(t) and frozen == 0, else x0 — one
+        svdd_refine_remask launch with the accept step off. x0 [B, L] on the GPU (a MASK token stays MASK), frozen [B, L] (non-zero =
+        keep) or None; round keys the Philox draw. -> x_t with x0's dtype."""
+        self._from_state_checks()
+        if self.time_conditioning:
+            raise NotImplementedError("renoise: time-conditioned backbones are not supported")
+        self._check_t(t, 0.0, "t")
+        x_u8, fz = self._refine_inputs(x0, frozen)
+        B, L = x_u8.shape
+        xt, _, _ = ops.refine_remask(x_u8, self._move_chance(t), self._mask_rng(B, L, round), frozen=fz)
+        return xt if x0.dtype == torch.uint8 else xt.to(x0.dtype)
+
+    def _refine_inputs(self, x0, frozen):
+        """(x0 as u8 [B, L], frozen as u8 [B, L] | None), both contiguous on the model's device; CPU tensors and tokens > 4 are
+        refused here (one read-back, before the first launch)."""
+        for name, t in (("x0", x0), ("frozen", frozen)):
+            if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != self.device):
+                raise ops.SvddError(f"{name} must be a tensor on the model's GPU (the SVDD hot path has no CPU fallback)")
+        if x0.dim() != 2 or x0.shape[0] == 0 or x0.shape[1] == 0:
+            raise ValueError(f"x0 must be [B, L] with B, L > 0, got {tuple(x0.shape)}")
+        if x0.dtype.is_floating_point or x0.dtype == torch.bool:
+            raise ValueError(f"x0 must hold integer tokens, got {x0.dtype}")
+        lo, hi = torch.aminmax(x0)                        # once, at entry: a bad token is refused before any launch (whatever the dtype)
+        if int(lo) < 0 or int(hi) > self.mask_index:
+            raise ops.SvddError(f"x0 holds a token outside 0..{self.mask_index} (0..3 = A, C, G, T; {self.mask_index} = MASK)")
+        if frozen is not None and tuple(frozen.shape) != tuple(x0.shape):
+            raise ValueError(f"frozen must have x0's shape {tuple(x0.shape)}, got {tuple(frozen.shape)}")
+        fz = None if frozen is None else (frozen != 0).to(torch.uint8).contiguous()
+        return self._tokens_u8(x0).contiguous(), fz
+
+    def _design_scorer(self, pre_scorer_embedding, pre_scorer_head, reward_model):
+        """tokens u8 [B, L] -> fp32 [B]: the score refine() judges a finished row by — the value function on the clean tokens, or
+        (reward_model given) the reward; task 0 of a multi-task net. One kernel path for every call, so scores compare exactly."""
+        if reward_model is None:
+            fn = self.value_callable(pre_scorer_embedding, pre_scorer_head)
+            opaque = lambda x: fn(ops.transform_samples(x))                                     # noqa: E731
+        else:
+            fn = self.reward_callable(reward_model)
+            opaque = lambda x: fn(ops.transform_samples(x, transposed=True))                    # noqa: E731
+        run = fn.forward_tokens if hasattr(fn, "forward_tokens") else opaque
+        return lambda x: run(x).reshape(x.shape[0], -1)[:, 0].float().contiguous()
+
+    @_decode_scope
+    @torch.no_grad()
+    def refine(self, x0, pre_scorer_embedding, pre_scorer_head, rounds, t_renoise, num_steps=None, eps=1e-5, sample_M=10,
+               frozen=None, accept="improve", reward_model=None):
+        """Test-time refinement of finished designs x0 [B, L]: `rounds` times, re-mask every row at noise level t_renoise (frozen
+        positions excepted), decode it again from there with SVDD-MC (controlled_sample_from) and score the result; with accept =
+        "improve" a row keeps its new version only if it scores higher than the version it had ("always": the new version is kept).
+        The score is the value function on the clean tokens (pre_scorer_head(pre_scorer_embedding(.)), or reward_model's if given.
+        Per round: one svdd_refine_remask launch (accept the last round's rows + re-mask), one decode, one scoring pass of B rows;
+        no host round trip inside or between rounds. -> (x int64 [B, L], score fp32 [B], stats) with stats = {"accepted": rows
+        that took their new version per round, "masked": MASK tokens of the re-masked batch per round}, read once at the end.
+        rounds = 0 returns x0 and its score."""
+        self._from_state_checks()
+        if self.time_conditioning:
+            raise NotImplementedError("refine: time-conditioned backbones are not supported")
+        if accept not in ("improve", "always"):
+            raise ValueError(f"accept = {accept!r}: expected 'improve' or 'always'")
+        rounds = int(rounds)
+        if rounds < 0:
+            raise ValueError(f"rounds must be >= 0, got {rounds}")
+        self._check_t(t_renoise, eps, "t_renoise")
+        x_keep, fz = self._refine_inputs(x0, frozen)
+        x_keep = x_keep.clone()
+        B, L = x_keep.shape
+        if L != self.config.model.length:
+            raise ValueError(f"x0 must be [B, {self.config.model.length}] (config.model.length), got {tuple(x0.shape)}")
+        steps_full = int(self.config.sampling.steps)
+        S = max(1, math.ceil(float(t_renoise) * steps_full)) if num_steps is None else int(num_steps)
+        if S <= 0:
+            raise ValueError(f"num_steps must be positive, got {num_steps}")
+        if self.rng_mode == "philox" and (rounds > 65536 or steps_full + rounds * S > 65536):
+            raise ops.SvddError(f"refine: {rounds} rounds of {S} steps after {steps_full} need Philox step keys beyond 65535 (the "
+                                "counter of svdd_propose holds 16 bits of the step)")
+        score_fn = self._design_scorer(pre_scorer_embedding, pre_scorer_head, reward_model)
+        dev = self.device
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        accepted = torch.zeros((max(rounds, 1), B), dtype=torch.int32, device=dev)
+        nmasked = torch.zeros((max(rounds, 1), B), dtype=torch.int32, device=dev)
+        score_keep = score_fn(x_keep)                              # the input's score: what round 0's result has to beat
+        mc = self._move_chance(t_renoise)
+        x_new = score_new = None
+        x_t = torch.empty((B, L), dtype=torch.uint8, device=dev)
+        base = self._step_base
+        try:
+            for r in range(rounds):
+                rng = self._mask_rng(B, L, r)
+                if r == 0:
+                    ops.refine_remask(x_keep, mc, rng, frozen=fz, x_t=x_t, nmasked=nmasked[0], err=err)
+                else:                                              # accept round r - 1's rows, re-mask what is kept
+                    self._refine_boundary(x_new, score_new, x_keep, score_keep, accept, accepted[r - 1], err,
+                                          mc=mc, rng=rng, frozen=fz, x_t=x_t, nmasked=nmasked[r])
+                self._step_base = base + steps_full + r * S
+                out = self._controlled_sample(pre_scorer_embedding, pre_scorer_head, sample_M,
+                                              *self._decode_start(S, eps, None, x_t, t_renoise, check_tokens=False))
+                x_new = self._tokens_u8(out).contiguous()
+                score_new = score_fn(x_new)
+        finally:
+            self._step_base = base
+        if rounds:
+            self._refine_boundary(x_new, score_new, x_keep, score_keep, accept, accepted[rounds - 1], err)
+        ops.check_refine_err(err)                                   # the one read-back (with the counters below)
+        stats = {"rounds": rounds, "steps_per_round": S, "move_chance": mc,
+                 "accepted": accepted[:rounds].sum(1).tolist(), "masked": nmasked[:rounds].sum(1).tolist()}
+        return x_keep.long(), score_keep, stats
+
+    def _refine_boundary(self, x_new, score_new, x_keep, score_keep, accept, accepted, err, mc=0.0, rng=None, **remask):
+        """One svdd_refine_remask launch at a round boundary: x_keep / score_keep (updated in place) take the new row where it is
+        accepted; with `remask` arguments the kept rows are re-masked into x_t as well."""
+        if accept == "improve":
+            ops.refine_remask(x_new, mc, rng, x_old=x_keep, score_new=score_new, score_old=score_keep, x_keep=x_keep,
+                              score_keep=score_keep, accepted=accepted, err=err, remask=bool(remask), **remask)
+        else:
+            ops.refine_remask(x_new, mc, rng, score_new=score_new, x_keep=x_keep, score_keep=score_keep, accepted=accepted,
+                              err=err, remask=bool(remask), **remask)
 
     # ------------------------------------------------------------- exact work-skipping ----
     def _can_skip(self, fn, L, M):

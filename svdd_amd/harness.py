@@ -140,6 +140,22 @@ class BaseModel(nn.Module):
             self.embedding, self.head, eval_sp_size=self.NUM_SAMPLES_PER_BATCH, sample_M=sample_M))
 
     @torch.no_grad()
+    def controlled_decode_refine(self, gen_batch_num, sample_M, rounds, t_renoise, frozen=None):
+        """SVDD-MC followed by `rounds` rounds of re-mask refinement at noise level t_renoise (Diffusion.refine, accept = "improve";
+        no reference counterpart): every guided batch is decoded like controlled_decode's, then refined under the same Philox key
+        (the rounds use step keys of their own). frozen [NUM_SAMPLES_PER_BATCH, L] or None: positions no round re-masks. Returns
+        what controlled_decode returns; `refine_stats` holds the per-batch stats of Diffusion.refine."""
+        m = self.ref_model
+        self.refine_stats = []
+
+        def guided():
+            x = m.controlled_sample(self.embedding, self.head, eval_sp_size=self.NUM_SAMPLES_PER_BATCH, sample_M=sample_M)
+            x, _, stats = m.refine(x, self.embedding, self.head, rounds, t_renoise, sample_M=sample_M, frozen=frozen)
+            self.refine_stats.append(stats)
+            return x
+        return self._decode(gen_batch_num, sample_M, guided)
+
+    @torch.no_grad()
     def controlled_decode_tweedie(self, gen_batch_num, sample_M, options):
         """SVDD-PM (reference Enformer.py:719-813)."""
         return self._decode(gen_batch_num, sample_M, lambda: self.ref_model.controlled_sample_tweedie(

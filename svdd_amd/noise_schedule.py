@@ -30,14 +30,15 @@ def get_noise(config):
     return LogLinearNoise()
 
 
-def move_chance_table(noise, num_steps, eps=1e-5):
+def move_chance_table(noise, num_steps, eps=1e-5, t_start=1.0):
     """The scalars every `_ddpm_update_*` recomputes (diffusion_gosai.py:1036-1038, 1176-1187),
     evaluated once on the host with the same fp32 torch ops, in the same order:
-      timesteps = linspace(1, eps, S+1); dt = (1-eps)/S
+      timesteps = linspace(t_start, eps, S+1); dt = (t_start-eps)/S     (t_start = 1: the reference's loops)
       sigma_t = noise(t); sigma_s = noise(t - dt); move_chance = 1 - exp(-sigma)
-    Returns (table fp32 [S,3] = (mct, mcs, mct - mcs), timesteps fp32 [S+1], dt float)."""
-    timesteps = torch.linspace(1, eps, num_steps + 1)
-    dt = (1 - eps) / num_steps
+    Returns (table fp32 [S,3] = (mct, mcs, mct - mcs), timesteps fp32 [S+1], dt float). t_start < 1: a decode that starts from a
+    state noised to t_start (Diffusion.controlled_sample_from / refine), driving the same per-step updates."""
+    timesteps = torch.linspace(t_start, eps, num_steps + 1)
+    dt = (t_start - eps) / num_steps
     t = timesteps[:num_steps].view(-1, 1)
     sigma_t, _ = noise(t)
     sigma_s, _ = noise(t - dt)

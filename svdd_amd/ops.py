@@ -180,6 +180,58 @@ def check_elbo_err(err):
         _lib.check(_lib.E_ARG, "svdd_elbo_nll: x0 holds a token > 3")
 
 
+def refine_remask(x_new, move_chance, rng, x_old=None, score_new=None, score_old=None, frozen=None, x_keep=None, score_keep=None,
+                  accepted=None, x_t=None, nmasked=None, err=None, remask=True):
+    """svdd_refine_remask, the round boundary of re-mask refinement, one launch: per row keep x_new iff score_new > score_old (only
+    when x_old, score_new and score_old are all given; a NaN or a tie keeps x_old; otherwise x_new is kept), then x_t = MASK where
+    u < move_chance and frozen == 0, else the kept row. -> (x_t u8 [B, L] | None, x_keep u8 [B, L] | None, score_keep f32 [B] | None).
+    x_keep may be x_old. accepted / nmasked: caller-owned i32 [B] outputs (new row kept / MASK tokens of x_t). move_chance: ONE
+    fp32 scalar the caller computed with the reference's fp32 torch ops. remask=False: the accept step alone (x_t is None, rng unused).
+    replay: rng.uniforms = torch.rand(B, L) ([b][l]); philox: keyed by (rng.seed, rng.row_offset + b, round = rng.step, l).
+    err: a caller-zeroed device int32 [1] the kernel sets for a token > 4 (checked by the caller later); None: checked here (one
+    synchronisation)."""
+    x_new = _need(x_new, torch.uint8, "x_new").contiguous()
+    B, L = x_new.shape
+    dev = x_new.device
+    judged = x_old is not None and score_new is not None and score_old is not None
+    for name, t in (("x_old", x_old), ("frozen", frozen), ("x_keep", x_keep), ("x_t", x_t)):
+        if t is not None and not (_need(t, torch.uint8, name).is_contiguous() and tuple(t.shape) == (B, L)):
+            raise SvddError(f"{name} must be a contiguous u8 [{B}, {L}] tensor, got {tuple(t.shape)}")
+    for name, t, dt in (("score_new", score_new, torch.float32), ("score_old", score_old, torch.float32),
+                        ("score_keep", score_keep, torch.float32), ("accepted", accepted, torch.int32), ("nmasked", nmasked, torch.int32)):
+        if t is not None and not (_need(t, dt, name).is_contiguous() and t.numel() == B):
+            raise SvddError(f"{name} must be a contiguous [{B}] tensor, got {tuple(t.shape)}")
+    if judged and x_keep is None:
+        x_keep = torch.empty((B, L), dtype=torch.uint8, device=dev)
+    if score_new is not None and score_keep is None:
+        score_keep = torch.empty(B, dtype=torch.float32, device=dev)
+    rs = None
+    if remask:
+        if x_t is None:
+            x_t = torch.empty((B, L), dtype=torch.uint8, device=dev)
+        if rng.uniforms is not None:
+            u = _need(rng.uniforms, torch.float32, "uniforms")
+            assert u.is_contiguous() and u.numel() == B * L and not rng.uniforms_rows, (u.shape, B, L, rng.uniforms_rows)
+        rs = ctypes.byref(rng.c_struct())
+    else:
+        x_t = None
+    check_here = err is None
+    if check_here:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)         # this entry takes its stream as an explicit argument
+    _lib.call("svdd_refine_remask", x_new, x_old, score_new, score_old, frozen, float(move_chance), B, L, rs, x_keep, score_keep,
+              accepted, x_t, nmasked if remask else None, err, stream)
+    if check_here:
+        check_refine_err(err)
+    return x_t, x_keep, score_keep
+
+
+def check_refine_err(err):
+    """Raise if svdd_refine_remask flagged a token > 4 (SVDD_E_ARG)."""
+    if int(err[0]) != 0:
+        _lib.check(_lib.E_ARG, "svdd_refine_remask: a row holds a token > 4")
+
+
 def select(scores, cand, mode=SELECT_ARGMAX, rng=None, want_soft=True, x_next=None):
     """-> (x_next u8 [B,L], soft f32 [B,M] | None, idx i32 [B])."""
     cand = _need(cand, torch.uint8, "cand").contiguous()
