@@ -193,6 +193,32 @@ int svdd_refine_remask(const uint8_t* x_new, const uint8_t* x_old, const float* 
                        float* score_keep, int32_t* accepted, uint8_t* x_t, int32_t* nmasked, int32_t* err, void* on_stream);
 
 /*
+ * Value-function training data (ABI 17): the per-step boundary of a CD-Q rollout (reference Enformer.py:226-259 with
+ * diffusion_gosai.py:839-853), in ONE launch and without a synchronisation. Per row b:
+ *   continue  x_next[b, :] = cand[b, M - 1, :]: the reference continues from its LAST draw (`x = x0` after `for j in range(10)`,
+ *             diffusion_gosai.py:845-851). cand [B, M, L] u8 (svdd_propose's), x_next [B, L] u8, not cand itself.
+ *             onehot_next [B, L, 4] f32 (may be NULL) = transform_samples(x_next), MASK rows zero: written straight into the
+ *             caller's training-input slab.
+ *   reduce    target[b] from scores[b, 0 .. M - 1] (the value net on the M draws). scores [B, M] f32 and target [B] f32 are both
+ *             given or both NULL (step 0 has no target: the reference skips time == 0, Enformer.py:233-234); not each other.
+ *     SVDD_TARGET_MEAN        target[b] = fl(fl(...fl(fl(0 + s_0) + s_1)... + s_{M-1}) / fl(M)): a sequential fp32 sum in ascending m
+ *                             and one fp32 division, bit for bit the reference's `case_sum = case_sum + v; case_sum / len(...)`
+ *                             (Enformer.py:235-238). Not a tree reduction, not a multiplication by 1 / M. NaN and +-inf follow IEEE.
+ *                             alpha is ignored.
+ *     SVDD_TARGET_LOGMEANEXP  the soft backup alpha log mean exp(v / alpha) (no reference counterpart): mx = max_m s_m,
+ *                             target[b] = mx + alpha * logf(sum_m expf((s_m - mx) / alpha) / M), the sum in ascending m, one rounding
+ *                             per operation. A NaN score gives NaN, mx = +inf gives +inf, all scores -inf give -inf. alpha must be
+ *                             finite and > 0.
+ *  Rows of a multiple-of-4 length in aligned buffers (tokens 4 bytes, one-hot 16) move as 32-bit words, any other shape byte by
+ *  byte: same results. No result depends on the launch shape (one wave per row). M <= SVDD_MAX_M.
+ *  The stream is an explicit argument (as svdd_refine_remask).
+ */
+#define SVDD_TARGET_MEAN 0
+#define SVDD_TARGET_LOGMEANEXP 1
+int svdd_value_target(const float* scores, const uint8_t* cand, int B, int L, int M, int reduce, float alpha,
+                      uint8_t* x_next, float* onehot_next, float* target, void* on_stream);
+
+/*
  * svdd_select — replaces torch.stack(scores,1) -> softmax(dim=1) -> argmax(dim=1) ->
  * per-row Python gather + stack                     diffusion_gosai.py:1219-1227 (= :1451-1459)
  *
@@ -611,7 +637,7 @@ int svdd_device_info(char* arch, int arch_len, int* num_cu);
 
 /* ABI version of this header: bumped on any signature change. */
 int svdd_abi_version(void);
-#define SVDD_ABI_VERSION 16
+#define SVDD_ABI_VERSION 17
 
 /*
  * Enformer-shaped value trunk (BASELINE.json configs[3]; reference decode.py:78-80, Enformer.py:1271-1334 trunk, :1807-1884

@@ -13,12 +13,13 @@ CSRC = os.path.join(_HERE, "csrc")
 # SVDD_HIP_LIB: load another build of the library instead (the timing-experiment scripts under tools/ build patched
 # copies of the kernels in a scratch directory; the tracked sources are never edited in place)
 SO_PATH = os.environ.get("SVDD_HIP_LIB") or os.path.join(CSRC, "libsvdd_hip.so")
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 OK, E_ARG, E_LAUNCH, E_NODEVICE = 0, -1, -2, -3
 LAYOUT_BLV, LAYOUT_BVL = 0, 1
 RNG_REPLAY, RNG_PHILOX = 0, 1
 SELECT_ARGMAX, SELECT_MULTINOMIAL = 0, 1
+TARGET_MEAN, TARGET_LOGMEANEXP = 0, 1                              # SVDD_TARGET_* of include/svdd_hip.h
 PRECISIONS = {"f32": 0, "f16x3": 1, "bf16x3": 2, "f16": 3, "bf16": 4}      # enum SVDD_PREC_* of include/svdd_hip.h
 MAX_M = 1024
 
@@ -121,6 +122,7 @@ SIGNATURES = {
     "svdd_elbo_mask": (vp, i32, i32, i32, f64, RNG, vp, vp, vp, vp, vp, vp, STREAM),
     "svdd_elbo_nll": (vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, STREAM),
     "svdd_refine_remask": (vp, vp, vp, vp, vp, f32, i32, i32, RNG, vp, vp, vp, vp, vp, vp, vp),
+    "svdd_value_target": (vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp),
 }
 EXPORTS = tuple(SIGNATURES)
 

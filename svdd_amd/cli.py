@@ -124,5 +124,62 @@ def main(method="mc", argv=None):
     return run(build_parser(method).parse_args(argv))
 
 
+# ------------------------------------------------------------------ value-function training (train_value.py) ----
+def build_train_parser():
+    p = argparse.ArgumentParser(description="Train the SVDD value function on MI355X: Monte-Carlo regression or CD-Q "
+                                            "(reference Enformer.BaseModel.forward, Enformer.py:163-267)")
+    p.add_argument("--task", default="dna", choices=["dna", "rna"])
+    p.add_argument("--cdq", action="store_true", help="CD-Q: regress every state onto the value net's own mean over 10 next states "
+                                                      "(default: Monte-Carlo regression onto r(x_0))")
+    p.add_argument("--cdq_alpha", type=float, default=None,
+                   help="CD-Q with the soft backup alpha log mean exp(v / alpha) instead of the reference's mean")
+    p.add_argument("--iters", type=int, default=10)
+    p.add_argument("--lr", type=float, default=1e-4)
+    p.add_argument("--batch_size", type=int, default=256)
+    p.add_argument("--steps", type=int, default=None, help="diffusion steps of a rollout (default: the task's config, 128)")
+    p.add_argument("--seed", type=int, default=44)
+    p.add_argument("--rng", default="philox", choices=["replay", "philox"])
+    p.add_argument("--out", default="./log/value_net.pt", help="where the value net's state_dict is saved ('model_state_dict', the "
+                                                               "layout --load_checkpoint_path of the decode scripts reads)")
+    return p
+
+
+def train_value(args):
+    """N AdamW iterations of BaseModel.forward on the synthetic nets -> (path of the saved state_dict, losses). Every iteration
+    builds its training set with one rollout on the device (Diffusion.value_targets) and takes one optimiser step on it."""
+    from . import synthetic
+    from .harness import BaseModel
+
+    set_seed(args.seed)
+    ref_model, embedding, head, reward = synthetic.build(args.task, "cuda", seed=args.seed)
+    if args.steps is not None:
+        ref_model.config.sampling.steps = args.steps
+    ref_model.rng_mode, ref_model.philox_seed = args.rng, args.seed
+    for p in list(embedding.parameters()) + list(head.parameters()):
+        p.requires_grad_(True)
+    model = BaseModel(embedding, head, ref_model, reward, args.batch_size, task=args.task, cdq=args.cdq or args.cdq_alpha is not None,
+                      cdq_alpha=args.cdq_alpha).cuda().train()
+    opt = torch.optim.AdamW([p for p in model.parameters() if p.requires_grad], lr=args.lr)
+    losses = []
+    for it in range(args.iters):
+        ref_model.philox_seed = args.seed + it                # Philox: a rollout is a function of the key; replay draws on
+        opt.zero_grad(set_to_none=True)
+        loss = model()
+        loss.backward()
+        opt.step()
+        losses.append(float(loss.detach()))
+        print(f"iter {it}: loss {losses[-1]:.6f}")
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    sd = {f"embedding.{k}": v for k, v in embedding.state_dict().items()}
+    sd.update({f"head.{k}": v for k, v in head.state_dict().items()})
+    torch.save({"model_state_dict": sd}, args.out)
+    print(f"wrote {args.out}")
+    return args.out, losses
+
+
+def main_train(argv=None):
+    return train_value(build_train_parser().parse_args(argv))
+
+
 if __name__ == "__main__":
     main()

@@ -14,7 +14,9 @@
 //   K7 subs_logp_kernel  SUBS re-parameterisation alone
 //   K11 elbo_mask_kernel / K12 elbo_nll_kernel  ELBO scoring: masking of x0, the weighted SUBS token loss and its sums
 //   K13 refine_remask_kernel  the round boundary of re-mask refinement: accept the better version of a row, re-mask it
+//   K14 value_target_kernel  the step boundary of a CD-Q rollout: continue from the last draw, reduce the draws' values to a target
 //   K4 tds_resample_kernel  SMC/TDS resampling (baseline)
+#include <float.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -1221,6 +1223,73 @@ __global__ __launch_bounds__(256) void refine_remask_kernel(RefineArgs a) {
   }
 }
 
+// ------------------------------------------------- K14 the step boundary of a CD-Q rollout (ABI 17) ----
+// One wave per row, in one launch: CONTINUE (x_next = the row's LAST draw cand[b, M - 1, :], diffusion_gosai.py:845-851, and its
+// one-hot, MASK rows zero, straight into the caller's training-input slab) and REDUCE (target[b] from the row's M values).
+//   MEAN        the reference's `case_sum = case_sum + v` over the draws then `/ len` (Enformer.py:235-238): a SEQUENTIAL fp32 sum in
+//               ascending m from 0.0f and ONE fp32 division by (float)M. Every lane of the wave runs the same chain on the same
+//               (broadcast) loads; lane 0 stores. No tree, no multiplication by 1 / M: either changes the last bit.
+//   LOGMEANEXP  mx + alpha * logf(sum_m expf((s_m - mx) / alpha) / M), mx = max_m s_m, the sum in ascending m. A NaN value gives
+//               NaN, mx = +inf gives +inf, all -inf gives -inf.
+// A lane owns four positions; with L a multiple of 4 and aligned rows (VEC) they move as one 32-bit word and four float4.
+struct ValueTargetArgs {
+  const float* scores; const uint8_t* cand; int B, L, M, reduce; float alpha;
+  uint8_t* x_next; float* onehot_next; float* target;
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void value_target_kernel(ValueTargetArgs a) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= a.B) return;                                             // whole waves only: the row is the wave's
+  const uint8_t* src = a.cand + (b * a.M + (a.M - 1)) * a.L;
+  uint8_t* dst = a.x_next + b * a.L;
+  float* oh = a.onehot_next ? a.onehot_next + b * a.L * 4 : nullptr;
+  for (int l0 = lane * 4; l0 < a.L; l0 += 4 * WAVE) {
+    const uint32_t tok4 = load4_u8<VEC>(src, l0, a.L);
+    store4_u8<VEC>(dst, l0, a.L, tok4);
+    if (!oh) continue;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const uint32_t c = (tok4 >> (8 * i)) & 0xFFu;
+      float4 v;
+      v.x = c == 0u ? 1.0f : 0.0f; v.y = c == 1u ? 1.0f : 0.0f; v.z = c == 2u ? 1.0f : 0.0f; v.w = c == 3u ? 1.0f : 0.0f;
+      if (VEC) {
+        reinterpret_cast<float4*>(oh)[l0 + i] = v;
+      } else if (l0 + i < a.L) {
+        float* o = oh + (int64_t)(l0 + i) * 4;
+        o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+      }
+    }
+  }
+  if (!a.target) return;
+  const float* s = a.scores + b * a.M;
+  float out;
+  if (a.reduce == SVDD_TARGET_MEAN) {
+    float acc = 0.0f;
+    for (int m = 0; m < a.M; ++m) acc = __fadd_rn(acc, s[m]);       // case_sum = case_sum + v, Enformer.py:237
+    out = __fdiv_rn(acc, (float)a.M);                               // case_sum / len(time_samples), :238
+  } else {
+    float mx = -INFINITY;
+    bool nan = false;
+    for (int m = 0; m < a.M; ++m) {
+      const float v = s[m];
+      nan |= v != v;
+      mx = fmaxf(mx, v);
+    }
+    if (nan) {
+      out = __builtin_nanf("");
+    } else if (mx == INFINITY || mx == -INFINITY) {
+      out = mx;
+    } else {
+      float acc = 0.0f;
+      for (int m = 0; m < a.M; ++m) acc = __fadd_rn(acc, expf(__fdiv_rn(__fsub_rn(s[m], mx), a.alpha)));
+      out = __fadd_rn(mx, __fmul_rn(a.alpha, logf(__fdiv_rn(acc, (float)a.M))));
+    }
+  }
+  if (lane == 0) a.target[b] = out;
+}
+
 // -------------------------------------------------------------------- K4 TDS resample ----
 // numpy's pairwise float32 sum (np.add.reduce), the order `ratio.sum()` uses at :1282: the array is halved (left half
 // rounded down to a multiple of 8) until a block has <= 128 elements; a block is summed with 8 running accumulators.
@@ -1993,6 +2062,21 @@ int svdd_refine_remask(const uint8_t* x_new, const uint8_t* x_old, const float* 
   auto k = replay ? (vec ? refine_remask_kernel<true, true> : refine_remask_kernel<true, false>)
                   : (vec ? refine_remask_kernel<false, true> : refine_remask_kernel<false, false>);
   return svdd_launch(k, dim3((unsigned)(((int64_t)B + 3) / 4)), dim3(256), 0, on_stream, a);
+}
+
+int svdd_value_target(const float* scores, const uint8_t* cand, int B, int L, int M, int reduce, float alpha,
+                      uint8_t* x_next, float* onehot_next, float* target, void* on_stream) {
+  if (!cand || !x_next || B <= 0 || L <= 0 || M <= 0 || M > SVDD_MAX_M) return SVDD_E_ARG;
+  if (reduce != SVDD_TARGET_MEAN && reduce != SVDD_TARGET_LOGMEANEXP) return SVDD_E_ARG;
+  if (reduce == SVDD_TARGET_LOGMEANEXP && !(alpha > 0.0f && alpha <= FLT_MAX)) return SVDD_E_ARG;   // finite and > 0 (a NaN fails both)
+  if ((scores == nullptr) != (target == nullptr)) return SVDD_E_ARG;  // a target from nothing, or values nobody reduces
+  if (x_next == cand || (target && target == scores)) return SVDD_E_ARG;   // an output that is another row's input
+  if ((int64_t)B * M * L >= (int64_t)1 << 40) return SVDD_E_ARG;
+  const auto al = [](const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; };
+  const bool vec = L % 4 == 0 && al(cand, 4) && al(x_next, 4) && al(onehot_next, 16);
+  const ValueTargetArgs a{scores, cand, B, L, M, reduce, alpha, x_next, onehot_next, target};
+  return svdd_launch(vec ? value_target_kernel<true> : value_target_kernel<false>, dim3((unsigned)(((int64_t)B + 3) / 4)), dim3(256),
+                     0, on_stream, a);
 }
 
 int svdd_tds_resample(const float* reward_num, const float* reward_den, double alpha, const uint8_t* sample,

@@ -11,6 +11,7 @@ methods on the SVDD decode path, so `BaseModel`/`decode.py`-style callers work u
     (plus sequence_nll / nll_metrics, the per-sequence API built on them)
 and, without a reference method of their own (a loop of the reference's q_xt and per-step updates from a given state):
     decode_sample_from, controlled_sample_from (template-constrained design), renoise, refine (re-mask refinement)
+and the data path that trains the value function (reference Enformer.py:163-267): _sample(cdq=True) and value_targets
 
 What differs is where the work runs: everything between "backbone logits" and "next x_t" is one
 or two launches of the hand-written HIP kernels (svdd_amd/csrc, C ABI include/svdd_hip.h) instead
@@ -75,6 +76,7 @@ Engine knobs (attributes; defaults reproduce the reference's observable behaviou
                    like the reference (:1306 and :1324 evaluate one function twice). True (opt-in): the differentiable pass
                    (forward2) also supplies the log-probs of q_xs — equal to round-off (~1e-6), so zero guidance is no longer
                    bit-for-bit the un-guided decode at near-ties.
+  cdq_draws        10 (the reference's hard-coded count, :846): next states _sample(cdq=True) draws per step.
   skip_stats       None, or a dict the samplers fill with device-side hit counters (live candidates, changed rows).
   skip_generic     False (default). True: SVDD-MC also skips the copies of the parent for an OPAQUE value function (any
                    nn.Module, e.g. the Enformer-shaped trunk): the live candidates are gathered into a smaller batch whose
@@ -90,6 +92,7 @@ import math
 import warnings
 import weakref
 from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 import torch
@@ -106,6 +109,17 @@ class Loss:
     loss: torch.Tensor
     nlls: torch.Tensor
     token_mask: torch.Tensor
+
+
+@dataclass
+class ValueTargets:
+    """The training set of one value-function iteration (Diffusion.value_targets), rows step-major (row k B + b = state k of
+    sequence b): states u8 [S, B, L], their one-hot f32 [S B, L, 4] (MASK rows zero) or None, the regression targets y f32 [S B],
+    and the rollout's x_0 int64 [B, L] (= states[S - 1])."""
+    states: torch.Tensor
+    onehot: Optional[torch.Tensor]
+    y: torch.Tensor
+    x0: torch.Tensor
 
 
 def _capturing():
@@ -265,6 +279,7 @@ class Diffusion(nn.Module):
         self._classifier_fused_last = None   # classifier guidance: whether the last step's gradient ran on the fused kernels (no autograd)
         self.elbo_trace = None           # set to a list to record (t, sigma, dsigma, move_chance, w, xt) of every _forward_pass_diffusion
         self._from_state = False         # set by _decode_start: the running decode starts from a caller's state, not from the all-MASK prior
+        self.cdq_draws = 10              # _sample(cdq=True): next states drawn per step (the reference's `for j in range(10)`, :846)
         self._step_base = 0              # added to the step index in every Philox key: refine() gives each round its own range of keys
 
     # ------------------------------------------------------------------ plumbing ----
@@ -990,11 +1005,122 @@ class Diffusion(nn.Module):
     @_decode_scope
     @torch.no_grad()
     def _sample(self, num_steps=None, eps=1e-5, eval_sp_size=None, cdq=False):
-        """Un-guided decode that also returns the S-1 intermediate states (:820-886)."""
+        """Un-guided decode that also returns the S-1 intermediate states (:820-886). cdq=True: the reference's CD-Q rollout
+        (:839-853) -> (x_0 int64 [B, L], mid_x: S - 1 x int64 [B, L], all_time_mid_x: S x cdq_draws x int64 [B, L]): every step draws
+        cdq_draws next states from the same q_xs (ONE backbone forward and one propose with M = cdq_draws here; the reference forwards
+        10 times on identical input) and continues from the last one; mid_x[i] is all_time_mid_x[i][-1]. Replay mode consumes
+        torch's generator as the reference's loop does (cdq_draws consecutive rand_like(q_xs) blocks per step). For drop-in
+        parity: value_targets() builds the training set without these lists. The draw count is the engine knob `cdq_draws` (the
+        reference hard-codes 10, :846; the parameter list is the reference's and stays)."""
         self._require_gpu()
-        if cdq:
-            raise NotImplementedError("cdq=True is a value-function *training* data path (Enformer.py:163-267)")
-        return self._unguided_sample(num_steps, eps, eval_sp_size, keep_mid=True)
+        if not cdq:
+            return self._unguided_sample(num_steps, eps, eval_sp_size, keep_mid=True)
+        M = self._check_draws(self.cdq_draws)
+        B, L, S, sched, x = self._decode_start(num_steps, eps, eval_sp_size)
+        mid_x, all_time_mid_x = [], []
+        for i in range(S):
+            logits = self._prior_logits(x) if i == 0 else self._backbone_logits(x)
+            cand, _, _ = ops.propose(logits, x, sched[i, 2], sched[i, 1], M, self._rng(i, M, B, L, logits))
+            all_time_mid_x.append([cand[:, j].long() for j in range(M)])
+            x, _, _ = ops.value_target(None, cand)                            # x = x0 after the draws' loop, :851
+            if i != S - 1:
+                mid_x.append(all_time_mid_x[i][-1])
+        return self._noise_removal(x), mid_x, all_time_mid_x
+
+    @staticmethod
+    def _check_draws(draws):
+        if int(draws) != draws or not 1 <= int(draws) <= ops._lib.MAX_M:
+            raise ValueError(f"draws must be an integer in 1..{ops._lib.MAX_M}, got {draws}")
+        return int(draws)
+
+    # ------------------------------------------------- value-function training data: MC and CD-Q rollouts (ABI 17) ----
+    @_decode_scope
+    @torch.no_grad()
+    def value_targets(self, pre_scorer_embedding, pre_scorer_head, reward_model, mode="mc", draws=10, reduce="mean", alpha=1.0,
+                      num_steps=None, eps=1e-5, eval_sp_size=None, want_onehot=True):
+        """The training set of one value-function iteration (reference Enformer.py:192-259), built on the device in one pass:
+        -> ValueTargets(states u8 [S, B, L], onehot f32 [S B, L, 4] | None, y f32 [S B], x0 int64 [B, L]), rows step-major in the
+        reference's torch.cat order: states[k] = mid_x[k] for k < S - 1, states[S - 1] = x_0.
+          mode "mc"   (:192-225) the un-guided rollout; y[k B + b] = r(x_0)[b] for every k, the reward evaluated once.
+          mode "cdq"  (:226-259) per step i >= 1 the value net on the B * draws candidates drawn from states[i - 1], reduced by
+                      svdd_value_target into y[(i - 1) B + b] (which also writes states[i] = the last draw and its one-hot); step 0
+                      runs no value net; the last block is r(x_0). reduce "mean" is the reference's sequential fp32 mean, bit for bit
+                      given the same scores; "logmeanexp" the soft backup alpha log mean exp(v / alpha) (alpha > 0; an extension).
+        One backbone launch per step, no materialised draws, no host round trip. One task only (NotImplementedError otherwise).
+        DEPARTURE FROM THE REFERENCE: the targets are evaluated with EVAL-MODE nets (BatchNorm running statistics, dropout off). The
+        reference evaluates head(embedding(.)) in whatever mode the module is in - while training that is batch statistics and live
+        dropout inside the regression target, which the inference kernels cannot reproduce and nobody wants. embedding / head are put
+        into eval() for the call and every submodule's mode is restored afterwards. Their weights may change between calls (they
+        are being trained): the weight-validated cache rebuilds the fused net when they do."""
+        self._require_gpu()
+        if mode not in ("mc", "cdq"):
+            raise ValueError(f"mode = {mode!r}: expected 'mc' or 'cdq'")
+        if reduce not in ops.TARGET_REDUCE:
+            raise ValueError(f"reduce = {reduce!r}: expected 'mean' or 'logmeanexp'")
+        if not (float(alpha) > 0.0 and math.isfinite(float(alpha))):
+            raise ValueError(f"alpha must be finite and > 0, got {alpha}")
+        M = self._check_draws(draws) if mode == "cdq" else 1
+        for m in (pre_scorer_embedding, pre_scorer_head, reward_model):
+            p = next(m.parameters(), None)
+            if p is not None and (not p.is_cuda or p.device != self.device):
+                raise ops.SvddError("value_targets: the value and reward nets must be on the model's GPU (the SVDD hot path has no "
+                                    "CPU fallback)")
+        from .value_nets import ConvHead
+        for head in (pre_scorer_head, getattr(reward_model, "head", None)):
+            if isinstance(head, ConvHead) and head.channel_transform.conv.layer.out_channels != 1:
+                raise NotImplementedError("value_targets: one task only (multi-task heads are out of scope)")
+        was = [(sm, sm.training) for m in (pre_scorer_embedding, pre_scorer_head) for sm in m.modules()]
+        try:
+            pre_scorer_embedding.eval()
+            pre_scorer_head.eval()
+            return self._value_targets(pre_scorer_embedding, pre_scorer_head, reward_model, M if mode == "cdq" else 0, reduce,
+                                       float(alpha), want_onehot, *self._decode_start(num_steps, eps, eval_sp_size))
+        finally:
+            for sm, training in was:
+                sm.training = training
+
+    def _value_targets(self, embedding, head, reward_model, M, reduce, alpha, want_onehot, B, L, S, sched, x):
+        """The rollout behind value_targets: M = 0 the un-guided loop (MC), M >= 1 the CD-Q loop with M draws per step."""
+        dev = self.device
+        states = torch.empty((S, B, L), dtype=torch.uint8, device=dev)
+        y = torch.empty((S, B), dtype=torch.float32, device=dev)
+        slab = torch.empty((S, B, L, 4), dtype=torch.float32, device=dev) if want_onehot else None
+        if M:
+            cand = torch.empty((B, M, L), dtype=torch.uint8, device=dev)
+            onehot = torch.empty((B * M, L, 4), dtype=torch.float32, device=dev)
+        else:
+            scratch = torch.empty((B, L, 4), dtype=torch.float32, device=dev)        # propose always writes a one-hot
+        x_last = torch.empty((B, L), dtype=torch.uint8, device=dev)                  # the state before the noise removal
+        for i in range(S):
+            logits = self._prior_logits(x) if i == 0 else self._backbone_logits(x)
+            nxt = states[i] if i != S - 1 else x_last
+            oh = slab[i] if (want_onehot and i != S - 1) else None
+            if M:
+                ops.propose(logits, x, sched[i, 2], sched[i, 1], M, self._rng(i, M, B, L, logits), cand=cand, onehot=onehot)
+                scores = None
+                if i > 0:                                                            # the reference skips time == 0, Enformer.py:233-234
+                    scores = self._value_scores(embedding, head, onehot, B, M, cand, x)
+                    if scores.numel() != B * M:
+                        raise NotImplementedError("value_targets: one task only (the value net returned more than one)")
+                self._record(logits, scores, x)
+                ops.value_target(scores, cand, reduce, alpha, x_next=nxt, onehot_next=oh, target=y[i - 1] if i > 0 else None)
+            else:
+                ops.propose(logits, x, sched[i, 2], sched[i, 1], 1, self._rng(i, 1, B, L, logits), cand=nxt.view(B, 1, L),
+                            onehot=oh if oh is not None else scratch)
+            x = nxt
+        x0 = self._noise_removal(x)
+        states[S - 1] = x0
+        if want_onehot:
+            slab[S - 1].copy_(ops.transform_samples(states[S - 1]))
+        r = self.reward_callable(reward_model)(ops.transform_samples(states[S - 1], transposed=True))
+        if r.dim() < 2 or r.shape[1] != 1 or r.numel() != B:
+            raise NotImplementedError(f"value_targets: one task only (the reward model returned {tuple(r.shape)})")
+        r = r.reshape(B).float()
+        if M:
+            y[S - 1] = r
+        else:
+            y.copy_(r.expand(S, B))
+        return ValueTargets(states, slab.view(S * B, L, 4) if want_onehot else None, y.view(S * B), x0)
 
     def _unguided_sample(self, num_steps, eps, eval_sp_size, keep_mid, x_init=None, t_start=1.0):
         """The un-guided loop -> (x_0 int64, [x_t int64 after every step but the last] if keep_mid else [])."""

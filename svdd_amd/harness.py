@@ -30,8 +30,13 @@ def batch_seed(base, k):
 
 class BaseModel(nn.Module):
     def __init__(self, embedding, head, ref_model, reward_model, batch_size, task="dna", n_tasks=1,
-                 val_batch_num=0):
+                 val_batch_num=0, cdq=False, cdq_alpha=None):
         super().__init__()
+        self.cdq = bool(cdq)                      # training: CD-Q targets (Enformer.py:226-259) instead of Monte-Carlo ones (:192-225)
+        self.cdq_alpha = cdq_alpha                # None: the reference's mean over the draws; a number: alpha log mean exp(v / alpha)
+        self.cdq_draws = 10                       # the reference's `for j in range(10)`, diffusion_gosai.py:846
+        self.timed = False                        # time-conditioned value nets (Enformer.py:204-214) are not supported
+        self.loss_fct = nn.MSELoss()
         self.task = task
         self.n_tasks = n_tasks
         self.embedding = embedding
@@ -64,6 +69,37 @@ class BaseModel(nn.Module):
                 per_t_targets[j].append(target)
         self.eval_time_step_batches = [torch.cat(s, dim=0) for s in per_t_samples]
         self.eval_time_step_targets = [torch.cat(t, dim=0) for t in per_t_targets]
+
+    def train(self, mode=True):
+        """nn.Module.train would flip every child: the frozen nets (ref_model, reward_model) stay in eval mode, so that they never
+        pick up dropout or batch statistics (the reference calls .eval() on them once and never trains the wrapper around them
+        in another mode, Enformer.py:97-133)."""
+        super().train(mode)
+        self.ref_model.eval()
+        self.reward_model.eval()
+        return self
+
+    def forward(self, x0=None, y=None):
+        """The value function's loss (reference Enformer.py:163-267).
+          training, not cdq  Monte-Carlo regression (:192-225): every state of an un-guided rollout is regressed onto r(x_0).
+          training, cdq      CD-Q (:226-259): every state is regressed onto the mean (cdq_alpha: the soft log-mean-exp) of the value
+                             net's own predictions on cdq_draws next states; the last state onto r(x_0).
+          otherwise          loss_fct(head(embedding(x0)).view(-1), y.view(-1)) on the caller's batch (:260-265).
+        The training set comes from ref_model.value_targets (one pass on the device, targets from EVAL-mode nets: see there); the
+        loss itself runs the torch modules in their own (train) mode under autograd, as in the reference. Philox mode: the rollout is
+        a function of ref_model.philox_seed - advance it between iterations."""
+        if not self.training:
+            return self.loss_fct(self.head(self.embedding(x0)).view(-1), y.view(-1))
+        if self.timed:
+            raise NotImplementedError("time-conditioned value nets (Enformer.py:204-214) are not supported")
+        if self.n_tasks != 1:
+            raise NotImplementedError("value-function training: one task only")
+        vt = self.ref_model.value_targets(self.embedding, self.head, self.reward_model, mode="cdq" if self.cdq else "mc",
+                                          draws=self.cdq_draws, reduce="mean" if self.cdq_alpha is None else "logmeanexp",
+                                          alpha=1.0 if self.cdq_alpha is None else self.cdq_alpha,
+                                          eval_sp_size=self.NUM_SAMPLES_PER_BATCH)
+        self.last_targets = vt
+        return self.loss_fct(self.head(self.embedding(vt.onehot)).view(-1), vt.y.view(-1))
 
     def transform_samples(self, samples, num_classes=4):
         return self.ref_model.transform_samples(samples, num_classes)        # Enformer.py:269-277

@@ -232,6 +232,46 @@ def check_refine_err(err):
         _lib.check(_lib.E_ARG, "svdd_refine_remask: a row holds a token > 4")
 
 
+TARGET_REDUCE = {"mean": _lib.TARGET_MEAN, "logmeanexp": _lib.TARGET_LOGMEANEXP}
+
+
+def value_target(scores, cand, reduce="mean", alpha=1.0, x_next=None, onehot_next=None, target=None):
+    """svdd_value_target, the step boundary of a CD-Q rollout, one launch: x_next = cand[:, M - 1] (the reference continues from its
+    last draw), onehot_next = its one-hot (MASK rows zero) and target[b] = the reduction of scores[b, :] — "mean": the reference's
+    sequential fp32 sum in ascending m and one division (Enformer.py:235-238), bit for bit; "logmeanexp": alpha log mean exp(s / alpha).
+    -> (x_next u8 [B, L], onehot_next f32 [B, L, 4] | None, target f32 [B] | None). cand u8 [B, M, L]; scores f32 [B, M] or None (no
+    target: step 0 of a rollout). x_next / onehot_next / target: caller-owned outputs (slices of a training-set slab); x_next and
+    target are allocated when missing, onehot_next is written only when given."""
+    cand = _need(cand, torch.uint8, "cand").contiguous()
+    if cand.dim() != 3:
+        raise SvddError(f"cand must be u8 [B, M, L], got {tuple(cand.shape)}")
+    B, M, L = cand.shape
+    dev = cand.device
+    if reduce not in TARGET_REDUCE:
+        raise ValueError(f"reduce = {reduce!r}: expected 'mean' or 'logmeanexp'")
+    if x_next is None:
+        x_next = torch.empty((B, L), dtype=torch.uint8, device=dev)
+    elif not (_need(x_next, torch.uint8, "x_next").is_contiguous() and tuple(x_next.shape) == (B, L)):
+        raise SvddError(f"x_next must be a contiguous u8 [{B}, {L}] tensor, got {tuple(x_next.shape)}")
+    if onehot_next is not None and not (_need(onehot_next, torch.float32, "onehot_next").is_contiguous()
+                                        and onehot_next.numel() == B * L * 4):
+        raise SvddError(f"onehot_next must be a contiguous f32 [{B}, {L}, 4] tensor, got {tuple(onehot_next.shape)}")
+    if scores is None:
+        if target is not None:
+            raise SvddError("value_target: a target needs scores")
+    else:
+        scores = _need(scores, torch.float32, "scores").contiguous()
+        if scores.numel() != B * M:
+            raise SvddError(f"scores must be f32 [{B}, {M}], got {tuple(scores.shape)}")
+        if target is None:
+            target = torch.empty(B, dtype=torch.float32, device=dev)
+        elif not (_need(target, torch.float32, "target").is_contiguous() and target.numel() == B):
+            raise SvddError(f"target must be a contiguous f32 [{B}] tensor, got {tuple(target.shape)}")
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)         # this entry takes its stream as an explicit argument
+    _lib.call("svdd_value_target", scores, cand, B, L, M, TARGET_REDUCE[reduce], float(alpha), x_next, onehot_next, target, stream)
+    return x_next, onehot_next, target
+
+
 def select(scores, cand, mode=SELECT_ARGMAX, rng=None, want_soft=True, x_next=None):
     """-> (x_next u8 [B,L], soft f32 [B,M] | None, idx i32 [B])."""
     cand = _need(cand, torch.uint8, "cand").contiguous()

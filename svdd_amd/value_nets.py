@@ -116,12 +116,26 @@ class GRUBlock(nn.Module):
 
     _hip_gru = None                            # set by Diffusion.compute_gradient_DPS: x [n, L, C] -> [2, n, L, C] with a gradient
 
+    gru_call_bytes = 1 << 31                   # largest gate workspace (rows x L x 2 directions x 3 gates x hidden, fp32) of one self.gru call
+
+    def _gru_rows(self, x):
+        """self.gru(x)[0] for x [n, L, C]. The vendor RNN library counts a call's gate workspace in 32 bits: a value-function
+        training batch (steps x batch rows: 32,768 sequences of 200 positions) overflows it and the call is refused. Sequences
+        are independent in a GRU, so beyond gru_call_bytes the rows go through in chunks (the same function of every row, autograd
+        included; round-off may differ with the chunk size as with any batch size); a batch below the limit is the one call it
+        always was."""
+        n, L, _ = x.shape
+        rows = max(1, self.gru_call_bytes // (L * 6 * self.gru.hidden_size * 4))
+        if n <= rows:
+            return self.gru(x)[0]
+        return torch.cat([self.gru(x[i:i + rows])[0] for i in range(0, n, rows)], dim=0)
+
     def forward(self, x):                     # [n, C, L]
         if self._hip_gru is not None and x.is_cuda:
             y2 = self._hip_gru(x.transpose(1, 2))          # hand-written forward + BPTT kernels (csrc/svdd_gru_train.hip)
             y = y2[0] + y2[1]
         else:
-            y = self.gru(x.transpose(1, 2))[0]    # [n, L, 2C]
+            y = self._gru_rows(x.transpose(1, 2))  # [n, L, 2C]
             h = self.gru.hidden_size
             y = y[:, :, :h] + y[:, :, h:]
         return self.ffn(y).transpose(1, 2)
