@@ -219,6 +219,69 @@ int svdd_value_target(const float* scores, const uint8_t* cand, int B, int L, in
                       uint8_t* x_next, float* onehot_next, float* target, void* on_stream);
 
 /*
+ * In-silico mutagenesis and ISM-driven directed evolution (added under ABI 17: three new entries, nothing existing changed). The
+ * boundary kernels around an unchanged value-net path (reference score.py ISM_predict, design.py:124-160 evolve(method="ism",
+ * for_each=True)). Every entry takes its stream explicitly (as svdd_refine_remask).
+ *
+ * svdd_ism_mutants: the 3 P single-base mutants of every row. x [B, L] u8 (tokens 0..3), positions [P] i32 ascending (device),
+ *   live [B] u8 or NULL. cand [B, 3P, L] u8; onehot [B * 3P, L, 4] f32 or NULL (the split-precision tower takes tokens).
+ *   Mutant (b, j, k), row b * 3P + 3j + k, is row b with position positions[j] replaced by the k-th base of A, C, G, T that is NOT
+ *   x[b, positions[j]], k = 0, 1, 2: the order of the reference's ISMDataset(..., drop_ref=True) (sequence, position, allele in
+ *   ACGT order with the reference base skipped). A row with live[b] == 0 gets exact copies of its parent (svdd_candidate_windows
+ *   flags those 0 and the compaction drops them). A parent token > 3 sets err[0] = 1 (err: caller-zeroed device word or NULL, read
+ *   later) and is copied through unchanged (one-hot: a zero row); where it sits AT positions[j] the mutant is a copy. A position
+ *   outside 0 .. L - 1 sets err[0] as well and gives copies: nothing is read or written out of bounds. cand must not be x.
+ *   Rows of a multiple-of-4 length in aligned buffers (tokens 4 bytes, one-hot 16) move as 32-bit words, any other shape byte by
+ *   byte: same results. One wave per mutant: no result depends on the launch shape. SVDD_E_ARG: B, L or P <= 0, a NULL x, positions
+ *   or cand, cand == x, B * 3P * L >= 2^40.
+ *
+ * svdd_ism_fold: folds the scores of one chunk of positions (columns p0 .. p0 + Pc - 1 of positions [P]) into the ISM table and
+ *   the per-row running best. scores: dense [B, 3 Pc] f32 in the order above when slot is NULL; with slot [B * 3 Pc] i32
+ *   (svdd_compact_flags' map) the score of mutant i is scores[slot[i]], or parent_score[b] where slot[i] < 0 (an exact copy, not
+ *   computed). parent_score [B] f32; x [B, L] u8 the parents (which base is the reference at each position).
+ *   ism [B, P, 4] f32 or NULL: entry (b, p0 + j, a) = the score of the mutant carrying base a there, the entry of the parent's own
+ *   base = parent_score[b] (a position whose parent token is > 3 or that is out of range: all four = parent_score[b], no pick).
+ *   best_score [B] f32, best_pos [B] i32, best_allele [B] i32 (all three or none; ism or the three must be given): the running
+ *   best over the chunks folded so far. The chunk with p0 == 0 starts it at (-inf, -1, -1); later chunks read what the earlier
+ *   ones left, so chunks are folded in ascending p0 and the result does not depend on the chunking. A mutant replaces the running
+ *   best only if its score is STRICTLY greater: the first mutant in (position, allele) order wins a tie (pandas idxmax), a NaN
+ *   never wins, and neither does -inf. best_pos is the sequence position positions[j], best_allele the token 0..3. live [B] u8 or
+ *   NULL: a row with live[b] == 0 offers no pick (its best stays (-inf, -1, -1)); its ism columns are still written.
+ *   One wave per row, the wave's reduction is by comparison on (score, order index): no float atomics, no result depends on the
+ *   launch shape. SVDD_E_ARG: B, L, P or Pc <= 0, p0 < 0, p0 + Pc > P, a NULL scores, parent_score, x or positions, neither
+ *   output, a partial best triple, ism == scores.
+ *
+ * svdd_evolve_apply: one iteration's boundary of directed evolution, ONE launch of ONE workgroup (the per-row state score_cur /
+ *   live is both an input of the batch-wide decision and an output of the launch: a second workgroup could read a row after its
+ *   owner rewrote it; B rows of L bytes are a few microseconds for one workgroup). No grid-wide synchronisation, no float atomics.
+ *   If stopped[0] != 0 at entry NOTHING is written. A row's pick is valid when the row is live (live NULL: every row) and
+ *   0 <= best_pos < L, 0 <= best_allele <= 3.
+ *     SVDD_EVOLVE_GLOBAL  the reference's rule (design.py:124-160, for_each=True): m = max of best_score over the rows with a valid
+ *                         pick (by comparison; a NaN never wins). If m > best_so_far[0]: best_so_far[0] = m and EVERY row with a
+ *                         valid pick takes it, whether or not that improves on the row's score_cur. Otherwise stopped[0] = 1 and
+ *                         no row changes. live may be NULL and is never written.
+ *     SVDD_EVOLVE_ROW     a row takes its pick only if best_score[b] > score_cur[b] (strictly; a NaN does not); otherwise
+ *                         live[b] = 0 and the row never changes again. stopped[0] = 1 when no row took a pick. live is required.
+ *   Taking a pick: x[b, best_pos] = best_allele in place, score_cur[b] = best_score[b]; then, if score_cur[b] > score_best[b]
+ *   (strictly: the first occurrence of a row's highest score is kept), x_best[b, :] = x[b, :] and score_best[b] = score_cur[b].
+ *   Trace (each NULL or [B]; written whenever the launch was not stopped at entry, also by the launch that sets stopped: the
+ *   reference records the iteration before it breaks): tr_pos / tr_allele i32 = the pick (-1, -1 without a valid one), tr_score
+ *   f32 = best_score[b] (score_cur[b] without a valid pick), tr_taken u8.
+ *   x [B, L] u8, score_cur [B], best_so_far [1], stopped [1] i32, x_best [B, L] u8 (not x), score_best [B]: all required.
+ *   SVDD_E_ARG: B or L <= 0, a stop mode other than the two, a NULL among the required pointers, ROW without live, x_best == x.
+ */
+#define SVDD_EVOLVE_GLOBAL 0
+#define SVDD_EVOLVE_ROW 1
+int svdd_ism_mutants(const uint8_t* x, const int32_t* positions, const uint8_t* live, int B, int L, int P, uint8_t* cand,
+                     float* onehot, int32_t* err, void* on_stream);
+int svdd_ism_fold(const float* scores, const int32_t* slot, const float* parent_score, const uint8_t* x, const int32_t* positions,
+                  const uint8_t* live, int B, int L, int P, int p0, int Pc, float* ism, float* best_score, int32_t* best_pos,
+                  int32_t* best_allele, void* on_stream);
+int svdd_evolve_apply(const float* best_score, const int32_t* best_pos, const int32_t* best_allele, int B, int L, int stop,
+                      uint8_t* x, float* score_cur, uint8_t* live, float* best_so_far, int32_t* stopped, uint8_t* x_best,
+                      float* score_best, int32_t* tr_pos, int32_t* tr_allele, float* tr_score, uint8_t* tr_taken, void* on_stream);
+
+/*
  * svdd_select — replaces torch.stack(scores,1) -> softmax(dim=1) -> argmax(dim=1) ->
  * per-row Python gather + stack                     diffusion_gosai.py:1219-1227 (= :1451-1459)
  *

@@ -20,6 +20,7 @@ LAYOUT_BLV, LAYOUT_BVL = 0, 1
 RNG_REPLAY, RNG_PHILOX = 0, 1
 SELECT_ARGMAX, SELECT_MULTINOMIAL = 0, 1
 TARGET_MEAN, TARGET_LOGMEANEXP = 0, 1                              # SVDD_TARGET_* of include/svdd_hip.h
+EVOLVE_GLOBAL, EVOLVE_ROW = 0, 1                                   # SVDD_EVOLVE_* of include/svdd_hip.h
 PRECISIONS = {"f32": 0, "f16x3": 1, "bf16x3": 2, "f16": 3, "bf16": 4}      # enum SVDD_PREC_* of include/svdd_hip.h
 MAX_M = 1024
 
@@ -123,6 +124,9 @@ SIGNATURES = {
     "svdd_elbo_nll": (vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, STREAM),
     "svdd_refine_remask": (vp, vp, vp, vp, vp, f32, i32, i32, RNG, vp, vp, vp, vp, vp, vp, vp),
     "svdd_value_target": (vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp),
+    "svdd_ism_mutants": (vp, vp, vp, i32, i32, i32, vp, vp, vp, vp),
+    "svdd_ism_fold": (vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp),
+    "svdd_evolve_apply": (vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp),
 }
 EXPORTS = tuple(SIGNATURES)
 

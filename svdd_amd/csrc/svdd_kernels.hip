@@ -15,6 +15,8 @@
 //   K11 elbo_mask_kernel / K12 elbo_nll_kernel  ELBO scoring: masking of x0, the weighted SUBS token loss and its sums
 //   K13 refine_remask_kernel  the round boundary of re-mask refinement: accept the better version of a row, re-mask it
 //   K14 value_target_kernel  the step boundary of a CD-Q rollout: continue from the last draw, reduce the draws' values to a target
+//   K15 ism_mutants_kernel / K16 ism_fold_kernel / K17 evolve_apply_kernel  in-silico mutagenesis: the single-base mutants of a
+//       batch, their scores folded into the ISM table and a per-row best, one iteration's boundary of ISM-driven evolution
 //   K4 tds_resample_kernel  SMC/TDS resampling (baseline)
 #include <float.h>
 #include <stdlib.h>
@@ -1290,6 +1292,201 @@ __global__ __launch_bounds__(256) void value_target_kernel(ValueTargetArgs a) {
   if (lane == 0) a.target[b] = out;
 }
 
+// ------------------------------------------------- K15-K17 in-silico mutagenesis and ISM-driven evolution (under ABI 17) ----
+// K15 ism_mutants_kernel: one wave per mutant (b, j, k) = row b with position positions[j] replaced by the k-th base that is not
+// the parent's (ISMDataset(drop_ref=True) order). The wave copies the parent row four positions per lane and swaps the one byte;
+// a dead row (live[b] == 0), a parent token > 3 at the position or a position out of range gives an exact copy.
+struct IsmMutantsArgs {
+  const uint8_t* x; const int32_t* positions; const uint8_t* live; int B, L, P;
+  uint8_t* cand; float* onehot; int32_t* err;
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void ism_mutants_kernel(IsmMutantsArgs a) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int M = 3 * a.P;
+  if (c >= (int64_t)a.B * M) return;                                // whole waves only: the mutant is the wave's
+  const int64_t b = c / M;
+  const int r = (int)(c - b * M), j = r / 3, k = r - 3 * j;
+  const uint8_t* src = a.x + b * a.L;
+  int pos = a.positions[j];
+  bool bad = pos < 0 || pos >= a.L;
+  const uint32_t ref = bad ? 255u : (uint32_t)src[pos];
+  const uint32_t alt = (uint32_t)k + ((uint32_t)k >= ref ? 1u : 0u);  // the k-th of A, C, G, T with the parent's base skipped
+  if (bad || ref > 3u || (a.live && a.live[b] == 0)) pos = -1;      // an exact copy
+  uint8_t* dst = a.cand + c * a.L;
+  float* oh = a.onehot ? a.onehot + c * a.L * 4 : nullptr;
+  for (int l0 = lane * 4; l0 < a.L; l0 += 4 * WAVE) {
+    uint32_t tok4 = load4_u8<VEC>(src, l0, a.L);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) bad |= ((tok4 >> (8 * i)) & 0xFFu) > 3u;
+    if (pos >= l0 && pos < l0 + 4) {
+      const int sh = 8 * (pos - l0);
+      tok4 = (tok4 & ~(0xFFu << sh)) | (alt << sh);
+    }
+    store4_u8<VEC>(dst, l0, a.L, tok4);
+    if (!oh) continue;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const uint32_t t = (tok4 >> (8 * i)) & 0xFFu;
+      float4 v;
+      v.x = t == 0u ? 1.0f : 0.0f; v.y = t == 1u ? 1.0f : 0.0f; v.z = t == 2u ? 1.0f : 0.0f; v.w = t == 3u ? 1.0f : 0.0f;
+      if (VEC) {
+        reinterpret_cast<float4*>(oh)[l0 + i] = v;
+      } else if (l0 + i < a.L) {
+        float* o = oh + (int64_t)(l0 + i) * 4;
+        o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+      }
+    }
+  }
+  if (bad && a.err) a.err[0] = 1;
+}
+
+// K16 ism_fold_kernel: one wave per row folds one chunk of positions. A lane takes the chunk's positions j = lane, lane + 64, ...
+// in ascending order and keeps its own best (score, order index 4 (p0 + j) + allele) under `strictly greater`; the wave then
+// reduces by comparison on (score, index), the smaller index winning equal scores, and lane 0 merges with the running best of
+// the earlier chunks, which wins a tie because it comes first. A NaN compares false everywhere: it never wins.
+struct IsmFoldArgs {
+  const float* scores; const int32_t* slot; const float* parent_score; const uint8_t* x; const int32_t* positions;
+  const uint8_t* live; int B, L, P, p0, Pc;
+  float* ism; float* best_score; int32_t* best_pos; int32_t* best_allele;
+};
+
+__global__ __launch_bounds__(256) void ism_fold_kernel(IsmFoldArgs a) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= a.B) return;
+  const float ps = a.parent_score[b];
+  const bool offers = !a.live || a.live[b] != 0;
+  const uint8_t* xr = a.x + b * a.L;
+  float bs = -INFINITY;
+  int bi = -1;
+  for (int j = lane; j < a.Pc; j += WAVE) {
+    const int jp = a.p0 + j;
+    const int pos = a.positions[jp];
+    const uint32_t ref = pos >= 0 && pos < a.L ? (uint32_t)xr[pos] : 255u;
+    float row[4] = {ps, ps, ps, ps};
+    if (ref <= 3u) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const int64_t i = (b * a.Pc + j) * 3 + k;
+        float s;
+        if (a.slot) {
+          const int sl = a.slot[i];
+          s = sl >= 0 ? a.scores[sl] : ps;
+        } else {
+          s = a.scores[i];
+        }
+        const int al = k + ((uint32_t)k >= ref ? 1 : 0);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) row[q] = q == al ? s : row[q];
+        if (offers && s > bs) { bs = s; bi = 4 * jp + al; }
+      }
+    }
+    if (a.ism) {
+      float* o = a.ism + (b * a.P + jp) * 4;
+      o[0] = row[0]; o[1] = row[1]; o[2] = row[2]; o[3] = row[3];
+    }
+  }
+  if (!a.best_score) return;
+#pragma unroll
+  for (int off = WAVE / 2; off > 0; off >>= 1) {
+    const float os = __shfl_xor(bs, off, WAVE);
+    const int oi = __shfl_xor(bi, off, WAVE);
+    if (os > bs || (os == bs && oi >= 0 && (bi < 0 || oi < bi))) { bs = os; bi = oi; }
+  }
+  if (lane == 0) {
+    float rs = -INFINITY;
+    int rp = -1, ra = -1;
+    if (a.p0 > 0) { rs = a.best_score[b]; rp = a.best_pos[b]; ra = a.best_allele[b]; }
+    if (bi >= 0 && bs > rs) { rs = bs; rp = a.positions[bi >> 2]; ra = bi & 3; }
+    a.best_score[b] = rs; a.best_pos[b] = rp; a.best_allele[b] = ra;
+  }
+}
+
+// K17 evolve_apply_kernel: ONE workgroup of 16 waves. Phase 1: a thread per row (strided) reads the row's pick and decides; the
+// batch maximum (GLOBAL) or `any row takes` (ROW) is reduced by comparison through the waves and LDS. Thread 0 settles
+// best_so_far / stopped. Phase 2: a wave per row (strided) writes the trace, applies the pick and keeps x_best. Every global
+// word another row's decision depends on (best_so_far, stopped) is read before the first barrier and written after the second;
+// score_cur / live of a row are read by that row's wave alone in phase 2 and by its phase-1 thread before the barriers.
+struct EvolveArgs {
+  const float* best_score; const int32_t* best_pos; const int32_t* best_allele; int B, L, stop;
+  uint8_t* x; float* score_cur; uint8_t* live; float* best_so_far; int32_t* stopped; uint8_t* x_best; float* score_best;
+  int32_t* tr_pos; int32_t* tr_allele; float* tr_score; uint8_t* tr_taken;
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(1024) void evolve_apply_kernel(EvolveArgs a) {
+  __shared__ float s_max[16];
+  __shared__ int s_any[16];
+  __shared__ int s_go;
+  if (a.stopped[0] != 0) return;                                    // uniform: nothing is written once stopped
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid >> 6;
+  const bool global = a.stop == SVDD_EVOLVE_GLOBAL;
+  float m = -INFINITY;
+  int any = 0;
+  for (int b = tid; b < a.B; b += 1024) {
+    const int pos = a.best_pos[b], al = a.best_allele[b];
+    const bool valid = (!a.live || a.live[b] != 0) && pos >= 0 && pos < a.L && al >= 0 && al <= 3;
+    const float s = a.best_score[b];
+    if (valid && global && s > m) m = s;
+    if (valid && !global && s > a.score_cur[b]) any = 1;
+  }
+#pragma unroll
+  for (int off = WAVE / 2; off > 0; off >>= 1) {
+    const float om = __shfl_xor(m, off, WAVE);
+    m = om > m ? om : m;
+    any |= __shfl_xor(any, off, WAVE);
+  }
+  if (lane == 0) { s_max[wave] = m; s_any[wave] = any; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 0; w < 16; ++w) { m = s_max[w] > m ? s_max[w] : m; any |= s_any[w]; }
+    int go;
+    if (global) {
+      go = m > a.best_so_far[0] ? 1 : 0;
+      if (go) a.best_so_far[0] = m; else a.stopped[0] = 1;
+    } else {
+      go = 1;
+      if (!any) a.stopped[0] = 1;
+    }
+    s_go = go;
+  }
+  __syncthreads();
+  const bool go = s_go != 0;
+  for (int b = wave; b < a.B; b += 16) {
+    const bool lv = !a.live || a.live[b] != 0;
+    const int pos = a.best_pos[b], al = a.best_allele[b];
+    const bool valid = lv && pos >= 0 && pos < a.L && al >= 0 && al <= 3;
+    const float s = a.best_score[b], cur = a.score_cur[b], sb = a.score_best[b];
+    const bool take = valid && (global ? go : s > cur);
+    const bool better = take && s > sb;                             // the first occurrence of the row's highest score stays
+    uint8_t* xr = a.x + (int64_t)b * a.L;
+    if (better) {                                                   // x_best[b, :] = the row with its pick applied
+      uint8_t* xb = a.x_best + (int64_t)b * a.L;
+      for (int l0 = lane * 4; l0 < a.L; l0 += 4 * WAVE) {
+        uint32_t tok4 = load4_u8<VEC>(xr, l0, a.L);
+        if (pos >= l0 && pos < l0 + 4) {
+          const int sh = 8 * (pos - l0);
+          tok4 = (tok4 & ~(0xFFu << sh)) | ((uint32_t)al << sh);
+        }
+        store4_u8<VEC>(xb, l0, a.L, tok4);
+      }
+    }
+    if (lane == 0) {
+      if (a.tr_pos) a.tr_pos[b] = valid ? pos : -1;
+      if (a.tr_allele) a.tr_allele[b] = valid ? al : -1;
+      if (a.tr_score) a.tr_score[b] = valid ? s : cur;
+      if (a.tr_taken) a.tr_taken[b] = take ? 1 : 0;
+      if (better) a.score_best[b] = s;
+      if (!global && lv && !take) a.live[b] = 0;
+    }
+    // the one byte of x goes last, by the lane that read its word above: no lane reads the row after this store
+    if (take && lane == ((pos >> 2) & (WAVE - 1))) { xr[pos] = (uint8_t)al; a.score_cur[b] = s; }
+  }
+}
+
 // -------------------------------------------------------------------- K4 TDS resample ----
 // numpy's pairwise float32 sum (np.add.reduce), the order `ratio.sum()` uses at :1282: the array is halved (left half
 // rounded down to a multiple of 8) until a block has <= 128 elements; a block is summed with 8 running accumulators.
@@ -2077,6 +2274,44 @@ int svdd_value_target(const float* scores, const uint8_t* cand, int B, int L, in
   const ValueTargetArgs a{scores, cand, B, L, M, reduce, alpha, x_next, onehot_next, target};
   return svdd_launch(vec ? value_target_kernel<true> : value_target_kernel<false>, dim3((unsigned)(((int64_t)B + 3) / 4)), dim3(256),
                      0, on_stream, a);
+}
+
+int svdd_ism_mutants(const uint8_t* x, const int32_t* positions, const uint8_t* live, int B, int L, int P, uint8_t* cand,
+                     float* onehot, int32_t* err, void* on_stream) {
+  if (!x || !positions || !cand || B <= 0 || L <= 0 || P <= 0 || cand == x) return SVDD_E_ARG;
+  if (P > (1 << 24) || (int64_t)B * 3 * P * L >= (int64_t)1 << 40 || (int64_t)B * 3 * P >= (int64_t)1 << 32) return SVDD_E_ARG;
+  const auto al = [](const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; };
+  const bool vec = L % 4 == 0 && al(x, 4) && al(cand, 4) && al(onehot, 16);
+  const IsmMutantsArgs a{x, positions, live, B, L, P, cand, onehot, err};
+  return svdd_launch(vec ? ism_mutants_kernel<true> : ism_mutants_kernel<false>, dim3((unsigned)(((int64_t)B * 3 * P + 3) / 4)),
+                     dim3(256), 0, on_stream, a);
+}
+
+int svdd_ism_fold(const float* scores, const int32_t* slot, const float* parent_score, const uint8_t* x, const int32_t* positions,
+                  const uint8_t* live, int B, int L, int P, int p0, int Pc, float* ism, float* best_score, int32_t* best_pos,
+                  int32_t* best_allele, void* on_stream) {
+  if (!scores || !parent_score || !x || !positions || B <= 0 || L <= 0 || P <= 0 || Pc <= 0 || p0 < 0 || P > (1 << 24)) return SVDD_E_ARG;
+  if ((int64_t)p0 + Pc > P) return SVDD_E_ARG;
+  const int nbest = (best_score != nullptr) + (best_pos != nullptr) + (best_allele != nullptr);
+  if ((nbest != 0 && nbest != 3) || (!ism && nbest == 0)) return SVDD_E_ARG;   // a partial triple, or nothing to write
+  if ((const float*)ism == scores || (const float*)best_score == scores || (const float*)best_score == parent_score) return SVDD_E_ARG;
+  if ((int64_t)B * 3 * P >= (int64_t)1 << 40) return SVDD_E_ARG;
+  const IsmFoldArgs a{scores, slot, parent_score, x, positions, live, B, L, P, p0, Pc, ism, best_score, best_pos, best_allele};
+  return svdd_launch(ism_fold_kernel, dim3((unsigned)(((int64_t)B + 3) / 4)), dim3(256), 0, on_stream, a);
+}
+
+int svdd_evolve_apply(const float* best_score, const int32_t* best_pos, const int32_t* best_allele, int B, int L, int stop,
+                      uint8_t* x, float* score_cur, uint8_t* live, float* best_so_far, int32_t* stopped, uint8_t* x_best,
+                      float* score_best, int32_t* tr_pos, int32_t* tr_allele, float* tr_score, uint8_t* tr_taken, void* on_stream) {
+  if (B <= 0 || L <= 0 || (stop != SVDD_EVOLVE_GLOBAL && stop != SVDD_EVOLVE_ROW)) return SVDD_E_ARG;
+  if (!best_score || !best_pos || !best_allele || !x || !score_cur || !best_so_far || !stopped || !x_best || !score_best) return SVDD_E_ARG;
+  if ((stop == SVDD_EVOLVE_ROW && !live) || x_best == x || score_best == score_cur) return SVDD_E_ARG;
+  if ((const float*)score_cur == best_score || (const float*)score_best == best_score) return SVDD_E_ARG;
+  const auto al = [](const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; };
+  const bool vec = L % 4 == 0 && al(x, 4) && al(x_best, 4);
+  const EvolveArgs a{best_score, best_pos, best_allele, B, L, stop, x, score_cur, live, best_so_far, stopped, x_best, score_best,
+                     tr_pos, tr_allele, tr_score, tr_taken};
+  return svdd_launch(vec ? evolve_apply_kernel<true> : evolve_apply_kernel<false>, dim3(1), dim3(1024), 0, on_stream, a);
 }
 
 int svdd_tds_resample(const float* reward_num, const float* reward_den, double alpha, const uint8_t* sample,

@@ -1337,6 +1337,174 @@ class Diffusion(nn.Module):
             ops.refine_remask(x_new, mc, rng, score_new=score_new, x_keep=x_keep, score_keep=score_keep, accepted=accepted,
                               err=err, remask=bool(remask), **remask)
 
+    # ------------------------------------------------------------- in-silico mutagenesis, ISM-driven evolution ----
+    ISM_WAVES_PER_CHUNK = 32              # default mutant rows per value-net pass = 32 x the CU count (8192 on MI355X): the [rows, L, 64]
+                                          # tower buffer and the GRU's two output planes are 1.26 GB at L = 200
+    ISM_COMPARE = (None, "subtract", "divide", "log2FC")
+
+    def _ism_positions(self, positions, L):
+        """-> (python list, int32 device tensor [P]); None = every position."""
+        if positions is None:
+            pos = list(range(L))
+        else:
+            pos = [int(p) for p in (positions.tolist() if isinstance(positions, torch.Tensor) else positions)]
+            if not pos:
+                raise ValueError("positions must not be empty")
+            if any(p < 0 or p >= L for p in pos):
+                raise ValueError(f"positions must lie in 0..{L - 1}, got {pos}")
+            if any(b <= a for a, b in zip(pos, pos[1:])):
+                raise ValueError(f"positions must be strictly ascending (no duplicates), got {pos}")
+        return pos, torch.tensor(pos, dtype=torch.int32, device=self.device)
+
+    def _ism_inputs(self, x, positions, chunk_rows):
+        """Checks in an order that needs no device until the last one: the shape, the positions, a MASK token, then
+        _refine_inputs' (a CPU tensor, a token outside 0..4)."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] == 0 or x.shape[1] == 0:
+            raise ValueError(f"x must be a [B, L] tensor with B, L > 0, got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)}")
+        pos, pos_dev = self._ism_positions(positions, x.shape[1])
+        if chunk_rows is not None and int(chunk_rows) <= 0:
+            raise ValueError(f"chunk_rows must be positive, got {chunk_rows}")
+        if not x.dtype.is_floating_point and x.dtype != torch.bool and bool((x == self.mask_index).any()):
+            raise ops.SvddError("x holds a MASK token: in-silico mutagenesis scores finished sequences (tokens 0..3)")
+        x_u8, _ = self._refine_inputs(x, None)
+        self._require_gpu()
+        B, L = x_u8.shape
+        if chunk_rows is None:
+            chunk_rows = self.ISM_WAVES_PER_CHUNK * torch.cuda.get_device_properties(self.device).multi_processor_count
+        Pc = max(1, min(len(pos), int(chunk_rows) // (3 * B)))      # B * 3 * Pc <= chunk_rows (never less than one position)
+        return x_u8, pos_dev, len(pos), Pc
+
+    class _IsmWorkspace:
+        def __init__(self, B, L, Pc, dev, windowed):
+            n = B * 3 * Pc
+            self.cand = torch.empty(n * L, dtype=torch.uint8, device=dev)
+            self.onehot = self.flags = self.live_idx = self.slot = self.count = None
+            if windowed:
+                self.onehot = torch.empty(n * L * 4, dtype=torch.float32, device=dev)
+                self.flags, self.live_idx, self.slot = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
+                self.count = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.err = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def _ism_route(self, pre_scorer_embedding, pre_scorer_head, reward_model, L):
+        """(score_fn: tokens u8 [n, L] -> fp32 [n], fused net or None). The fused net is given when the windowed tower applies
+        (FusedValueNet, 104 < L <= 208, candidates_ok): the mutants' towers are then computed on their row windows only. Otherwise
+        score_fn runs on the mutants' tokens: forward_tokens of a fused net, or the opaque fn(transform_samples(.)) call."""
+        from .fused import FusedValueNet
+        score_fn = self._design_scorer(pre_scorer_embedding, pre_scorer_head, reward_model)
+        fn = (self.value_callable(pre_scorer_embedding, pre_scorer_head) if reward_model is None
+              else self.reward_callable(reward_model))
+        windowed = isinstance(fn, FusedValueNet) and fn.kernels_ok(L) and fn.candidates_ok(L, 3)
+        return score_fn, (fn if windowed else None)
+
+    def _ism_pass(self, x, pos_dev, P, Pc, score_fn, fused, ws, parent_score, live=None, ism=None, best=None):
+        """The mutants of x at every position, chunk by chunk in ascending position order: svdd_ism_mutants, the value net, and
+        svdd_ism_fold into ism [B, P, 4] and / or the running best. Nothing returns to the host."""
+        from . import fused as F_
+        B, L = x.shape
+        lp = fused is not None and fused.precision != "f32"
+        if fused is not None:                                       # the parents' tower output, once per pass
+            parent_out = fused.parent_tower(x)
+        for p0 in range(0, P, Pc):
+            pc = min(Pc, P - p0)
+            n = B * 3 * pc
+            cand = ws.cand[:n * L].view(B, 3 * pc, L)
+            if fused is None:
+                ops.ism_mutants(x, pos_dev[p0:p0 + pc], live, cand=cand, want_onehot=False, err=ws.err)
+                ops.ism_fold(score_fn(cand.view(n, L)), parent_score, x, pos_dev, p0, pc, live=live, ism=ism, best=best)
+                continue
+            onehot = None if lp else ws.onehot[:n * L * 4].view(n, L, 4)
+            ops.ism_mutants(x, pos_dev[p0:p0 + pc], live, cand=cand, onehot=onehot, want_onehot=False, err=ws.err)
+            if live is None:
+                win = F_.candidate_windows(cand, x)
+                sc = fused.forward_candidates_from(onehot, cand, win, parent_out)
+                slot = None
+            else:                                                   # stopped rows' mutants are exact copies: flagged 0, dropped
+                flags, live_idx, slot = ws.flags[:n], ws.live_idx[:n], ws.slot[:n]
+                win = F_.candidate_windows(cand, x, flags=flags)
+                ops.compact_flags(flags, live_idx, slot, ws.count)
+                sc = fused.forward_candidates_from(onehot, cand, win, parent_out, live_idx=live_idx, count=ws.count)
+            sc = sc.reshape(n, -1)
+            sc = sc.reshape(n) if sc.shape[1] == 1 else sc[:, 0].contiguous()
+            ops.ism_fold(sc, parent_score, x, pos_dev, p0, pc, slot=slot, live=live, ism=ism, best=best)
+
+    @torch.no_grad()
+    def ism_scores(self, x, pre_scorer_embedding, pre_scorer_head, reward_model=None, positions=None, compare=None, chunk_rows=None):
+        """In-silico mutagenesis (reference score.py ISM_predict): the score of every single-base mutant of x [B, L] (tokens 0..3, on
+        the GPU) -> fp32 [B, P, 4]; entry (b, j, a) is the score of row b with base a at positions[j], the entry of the row's own
+        base its own score. The score is pre_scorer_head(pre_scorer_embedding(.)), or reward_model's if given (task 0 of a
+        multi-task net). positions: None = all, or a strictly ascending list of ints in 0..L-1. compare: None, or "subtract" /
+        "divide" / "log2FC" against the parent's score. chunk_rows: mutant rows per value-net pass (whole positions; default 32 x the
+        CU count). Per chunk of positions: svdd_ism_mutants, the value net (a fused ConvGRU net at 104 < L <= 208 computes each
+        mutant's tower on the row window around its one changed position and copies the rest from the parent's tower output: same
+        bits as the whole tower), svdd_ism_fold. No mutant and no score crosses to the host."""
+        if compare not in self.ISM_COMPARE:
+            raise ValueError(f"compare = {compare!r}: expected None, 'subtract', 'divide' or 'log2FC'")
+        x_u8, pos_dev, P, Pc = self._ism_inputs(x, positions, chunk_rows)
+        B, L = x_u8.shape
+        score_fn, fused = self._ism_route(pre_scorer_embedding, pre_scorer_head, reward_model, L)
+        ws = self._IsmWorkspace(B, L, Pc, self.device, fused is not None)
+        parent_score = score_fn(x_u8)
+        ism = torch.empty((B, P, 4), dtype=torch.float32, device=self.device)
+        self._ism_pass(x_u8, pos_dev, P, Pc, score_fn, fused, ws, parent_score, ism=ism)
+        ops.check_ism_err(ws.err)
+        if compare is not None:
+            ref = parent_score[:, None, None]
+            ism = ism - ref if compare == "subtract" else ism / ref if compare == "divide" else torch.log2(ism / ref)
+        return ism
+
+    @torch.no_grad()
+    def evolve(self, x, pre_scorer_embedding, pre_scorer_head, reward_model=None, max_iter=10, positions=None, stop="global",
+               chunk_rows=None):
+        """Greedy directed evolution on the ISM table (reference design.py evolve(method="ism", for_each=True)): per iteration
+        every row's 3 P single-base mutants are scored and the row's best one (the first in (position, allele) order among equal
+        scores; a NaN never) is its pick.
+          stop = "global"  the reference's rule: every row takes its pick whether or not it improves on the row's score; the run
+                           stops at the first iteration whose best pick over the batch does not beat the best seen so far (that
+                           iteration changes no row but is in the trace, as in the reference's dataframe).
+          stop = "row"     a row takes its pick only if it strictly beats the row's score, otherwise it stops for good (its mutants
+                           are not computed again); the run stops at the iteration in which no row moved.
+        -> (x_best int64 [B, L], score_best fp32 [B], trace): the highest-scoring state along each row's trajectory (the first one
+        among equals) and trace = {"iters": iterations executed (the stopping one included), "position", "allele" (token 0..3),
+        "taken": [iters, B] (-1 / -1 / 0: a row without a pick), "score": [iters + 1, B], row 0 the input's scores, row i + 1 the
+        picks' scores of iteration i}: the reference dataframe's best_in_iter rows. max_iter = 0 returns the input and its score.
+        Per iteration: one pass of ism_scores' path folded into a per-row best, one svdd_evolve_apply launch; the host reads the
+        one `stopped` word per iteration and nothing else before the end."""
+        if stop not in ops.EVOLVE_STOP:
+            raise ValueError(f"stop = {stop!r}: expected 'global' or 'row'")
+        max_iter = int(max_iter)
+        if max_iter < 0:
+            raise ValueError(f"max_iter must be >= 0, got {max_iter}")
+        x_u8, pos_dev, P, Pc = self._ism_inputs(x, positions, chunk_rows)
+        x_u8 = x_u8.clone()
+        B, L = x_u8.shape
+        dev = self.device
+        score_fn, fused = self._ism_route(pre_scorer_embedding, pre_scorer_head, reward_model, L)
+        ws = self._IsmWorkspace(B, L, Pc, dev, fused is not None)
+        score_cur = score_fn(x_u8).clone()
+        x_best, score_best = x_u8.clone(), score_cur.clone()
+        neg = torch.full_like(score_cur, float("-inf"))
+        best_so_far = torch.where(score_cur != score_cur, neg, score_cur).max().reshape(1)   # iteration 0 of the reference: the inputs
+        stopped = torch.zeros(1, dtype=torch.int32, device=dev)
+        live = torch.ones(B, dtype=torch.uint8, device=dev) if stop == "row" else None
+        best = (torch.empty(B, device=dev), torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+        rows = max(max_iter, 1)
+        tr_pos, tr_al = (torch.full((rows, B), -1, dtype=torch.int32, device=dev) for _ in range(2))
+        tr_taken = torch.zeros((rows, B), dtype=torch.uint8, device=dev)
+        tr_score = torch.empty((rows + 1, B), dtype=torch.float32, device=dev)
+        tr_score[0] = score_cur
+        iters = 0
+        for it in range(max_iter):
+            self._ism_pass(x_u8, pos_dev, P, Pc, score_fn, fused, ws, score_cur, live=live, best=best)
+            ops.evolve_apply(best, x_u8, score_cur, best_so_far, stopped, x_best, score_best, stop=stop, live=live,
+                             trace=(tr_pos[it], tr_al[it], tr_score[it + 1], tr_taken[it]))
+            iters = it + 1
+            if int(stopped[0]) != 0:                                # the one word the host reads per iteration
+                break
+        ops.check_ism_err(ws.err)
+        trace = {"iters": iters, "position": tr_pos[:iters], "allele": tr_al[:iters], "taken": tr_taken[:iters],
+                 "score": tr_score[:iters + 1]}
+        return x_best.long(), score_best, trace
+
     # ------------------------------------------------------------- exact work-skipping ----
     def _can_skip(self, fn, L, M):
         """The skipping paths hand the nets compacted batches whose size only the device knows: they need the

@@ -1041,6 +1041,28 @@ class FusedValueNet(nn.Module):
         seq = conv_tower_windows(onehot, win, parent_out, M, self.tw_tiles, self.tw_bias, self.tw_resmask)
         return self._after_tower(seq, B * M, L)
 
+    def parent_tower(self, x):
+        """The tower output of the parents x [B, L] u8 in the module's precision: what forward_candidates computes first, for a
+        caller that scores several candidate batches of the same parents (in-silico mutagenesis: one batch per chunk of positions)."""
+        from . import ops
+        if self.lp_ok(x.shape[1]):
+            pk = self._lp_pack()
+            return conv_tower_lp(x, pk["tiles"], self.tw_bias, pk["tinv"], self.tw_resmask, pk["prec"])
+        return conv_tower(ops.transform_samples(x), self.tw_tiles, self.tw_bias, self.tw_resmask)
+
+    def forward_candidates_from(self, onehot, cand, win, parent_out, live_idx=None, count=None):
+        """forward_candidates with the parents' tower output and the candidates' windows given: windowed tower, GRU, tail ->
+        scores [B * M, n_tasks, 1]. onehot is not read in a split precision (may be None). live_idx / count (int32 device tensors):
+        only the listed candidates, compacted into the first count[0] rows of the result. Same kernels, same bits per candidate."""
+        B, M, L = cand.shape
+        if self.lp_ok(L):
+            pk = self._lp_pack()
+            seq = conv_tower_windows_lp(cand, win, parent_out, pk["tiles"], self.tw_bias, pk["tinv"], self.tw_resmask, pk["prec"],
+                                        live_idx=live_idx, count=count)
+            return self._after_tower_lp(seq, pk, count)
+        seq = conv_tower_windows(onehot, win, parent_out, M, self.tw_tiles, self.tw_bias, self.tw_resmask, live_idx=live_idx, count=count)
+        return self._after_tower(seq, B * M, L, count)
+
     def _after_tower(self, seq, n, L, count=None, out=None):
         h = gru_bidir(seq, self.wpack, self.bpack, count)
         if self.use_fused_tail and self.tail_ok:

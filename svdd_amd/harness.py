@@ -192,6 +192,20 @@ class BaseModel(nn.Module):
         return self._decode(gen_batch_num, sample_M, guided)
 
     @torch.no_grad()
+    def ism_predict(self, samples, positions=None, compare=None):
+        """In-silico mutagenesis of finished designs under the harness's reward model (reference score.py ISM_predict): samples
+        [B, L] tokens 0..3 -> fp32 [B, P, 4], the reward of every single-base mutant (Diffusion.ism_scores)."""
+        return self.ref_model.ism_scores(samples, self.embedding, self.head, reward_model=self.reward_model, positions=positions,
+                                         compare=compare)
+
+    @torch.no_grad()
+    def evolve(self, samples, max_iter=10, positions=None, stop="global"):
+        """ISM-driven directed evolution of samples [B, L] under the harness's reward model (reference design.py evolve(method="ism",
+        for_each=True); Diffusion.evolve) -> (x_best int64 [B, L], score_best fp32 [B], trace)."""
+        return self.ref_model.evolve(samples, self.embedding, self.head, reward_model=self.reward_model, max_iter=max_iter,
+                                     positions=positions, stop=stop)
+
+    @torch.no_grad()
     def controlled_decode_tweedie(self, gen_batch_num, sample_M, options):
         """SVDD-PM (reference Enformer.py:719-813)."""
         return self._decode(gen_batch_num, sample_M, lambda: self.ref_model.controlled_sample_tweedie(

@@ -272,6 +272,105 @@ def value_target(scores, cand, reduce="mean", alpha=1.0, x_next=None, onehot_nex
     return x_next, onehot_next, target
 
 
+EVOLVE_STOP = {"global": _lib.EVOLVE_GLOBAL, "row": _lib.EVOLVE_ROW}
+
+
+def _this_stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)           # the ISM entries take their stream as an explicit argument
+
+
+def _is(t, dtype, shape, name):
+    if not (_need(t, dtype, name).is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise SvddError(f"{name} must be a contiguous {dtype} {list(shape)} tensor, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def ism_mutants(x, positions, live=None, cand=None, onehot=None, want_onehot=True, err=None):
+    """svdd_ism_mutants: the 3 P single-base mutants of every row of x u8 [B, L] at positions i32 [P] (device, ascending), in
+    ISMDataset(drop_ref=True) order: mutant (b, j, k) = row b with positions[j] set to the k-th base that is not the parent's.
+    -> (cand u8 [B, 3P, L], onehot f32 [B * 3P, L, 4] | None). live u8 [B]: a row with live[b] == 0 gets exact copies. err: a
+    caller-zeroed device int32 [1] the kernel sets for a parent token > 3 or a position outside 0..L-1 (checked by the caller later
+    with check_ism_err); None: checked here (one synchronisation)."""
+    x = _need(x, torch.uint8, "x").contiguous()
+    if x.dim() != 2:
+        raise SvddError(f"x must be u8 [B, L], got {tuple(x.shape)}")
+    B, L = x.shape
+    positions = _need(positions, torch.int32, "positions").contiguous()
+    P = positions.numel()
+    dev = x.device
+    if live is not None:
+        _is(live, torch.uint8, (B,), "live")
+    cand = torch.empty((B, 3 * P, L), dtype=torch.uint8, device=dev) if cand is None else _is(cand, torch.uint8, (B, 3 * P, L), "cand")
+    if onehot is None and want_onehot:
+        onehot = torch.empty((B * 3 * P, L, 4), dtype=torch.float32, device=dev)
+    elif onehot is not None:
+        _is(onehot, torch.float32, (B * 3 * P, L, 4), "onehot")
+    check_here = err is None
+    if check_here:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.call("svdd_ism_mutants", x, positions, live, B, L, P, cand, onehot, err, _this_stream())
+    if check_here:
+        check_ism_err(err)
+    return cand, onehot
+
+
+def check_ism_err(err):
+    """Raise if svdd_ism_mutants flagged a parent token > 3 or a position out of range (SVDD_E_ARG)."""
+    if int(err[0]) != 0:
+        _lib.check(_lib.E_ARG, "svdd_ism_mutants: a row holds a token > 3, or a position is outside 0..L-1")
+
+
+def ism_fold(scores, parent_score, x, positions, p0, Pc, slot=None, live=None, ism=None, best=None):
+    """svdd_ism_fold: fold the scores of the mutants of positions[p0 : p0 + Pc] into ism f32 [B, P, 4] (or None) and the running
+    best = (best_score f32 [B], best_pos i32 [B], best_allele i32 [B]) (or None). scores: dense f32 [B, 3 Pc], or with slot (i32
+    [B * 3 Pc], svdd_compact_flags' map) the compacted scores: mutant i has scores[slot[i]], or the parent's score where slot[i] < 0.
+    The chunk with p0 == 0 starts the running best at (-inf, -1, -1); fold chunks in ascending p0."""
+    x = _need(x, torch.uint8, "x")
+    B, L = x.shape
+    P = positions.numel()
+    scores = _need(scores, torch.float32, "scores")
+    if not x.is_contiguous() or not scores.is_contiguous() or (slot is None and scores.numel() != B * 3 * Pc):
+        raise SvddError(f"ism_fold: x [{B}, {L}] and scores [{B}, {3 * Pc}] must be contiguous, got scores {tuple(scores.shape)}")
+    _is(_need(positions, torch.int32, "positions"), torch.int32, (P,), "positions")
+    _is(parent_score, torch.float32, (B,), "parent_score")
+    if slot is not None:
+        _is(slot, torch.int32, (B * 3 * Pc,), "slot")
+    if live is not None:
+        _is(live, torch.uint8, (B,), "live")
+    if ism is not None:
+        _is(ism, torch.float32, (B, P, 4), "ism")
+    bs = bp = ba = None
+    if best is not None:
+        bs, bp, ba = best
+        _is(bs, torch.float32, (B,), "best_score"), _is(bp, torch.int32, (B,), "best_pos"), _is(ba, torch.int32, (B,), "best_allele")
+    _lib.call("svdd_ism_fold", scores, slot, parent_score, x, positions, live, B, L, P, int(p0), int(Pc), ism, bs, bp, ba, _this_stream())
+
+
+def evolve_apply(best, x, score_cur, best_so_far, stopped, x_best, score_best, stop="global", live=None, trace=None):
+    """svdd_evolve_apply, one iteration's boundary of ISM-driven evolution, one launch: best = (best_score, best_pos, best_allele)
+    of svdd_ism_fold; x u8 [B, L], score_cur f32 [B], live u8 [B] (required for stop = "row"), best_so_far f32 [1], stopped i32 [1],
+    x_best u8 [B, L], score_best f32 [B] are updated in place; trace = (position i32 [B], allele i32 [B], score f32 [B], taken u8 [B])
+    of this iteration or None. Nothing is written once stopped[0] != 0."""
+    if stop not in EVOLVE_STOP:
+        raise ValueError(f"stop = {stop!r}: expected 'global' or 'row'")
+    _need(x, torch.uint8, "x")
+    B, L = x.shape
+    bs, bp, ba = best
+    _is(bs, torch.float32, (B,), "best_score"), _is(bp, torch.int32, (B,), "best_pos"), _is(ba, torch.int32, (B,), "best_allele")
+    _is(x, torch.uint8, (B, L), "x"), _is(x_best, torch.uint8, (B, L), "x_best")
+    _is(score_cur, torch.float32, (B,), "score_cur"), _is(score_best, torch.float32, (B,), "score_best")
+    _is(best_so_far, torch.float32, (1,), "best_so_far"), _is(stopped, torch.int32, (1,), "stopped")
+    if live is not None:
+        _is(live, torch.uint8, (B,), "live")
+    tp = ta = ts = tt = None
+    if trace is not None:
+        tp, ta, ts, tt = trace
+        _is(tp, torch.int32, (B,), "trace position"), _is(ta, torch.int32, (B,), "trace allele")
+        _is(ts, torch.float32, (B,), "trace score"), _is(tt, torch.uint8, (B,), "trace taken")
+    _lib.call("svdd_evolve_apply", bs, bp, ba, B, L, EVOLVE_STOP[stop], x, score_cur, live, best_so_far, stopped, x_best, score_best,
+              tp, ta, ts, tt, _this_stream())
+
+
 def select(scores, cand, mode=SELECT_ARGMAX, rng=None, want_soft=True, x_next=None):
     """-> (x_next u8 [B,L], soft f32 [B,M] | None, idx i32 [B])."""
     cand = _need(cand, torch.uint8, "cand").contiguous()
