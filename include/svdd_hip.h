@@ -282,6 +282,44 @@ int svdd_evolve_apply(const float* best_score, const int32_t* best_pos, const in
                       float* score_best, int32_t* tr_pos, int32_t* tr_allele, float* tr_score, uint8_t* tr_taken, void* on_stream);
 
 /*
+ * Gradient attributions (added under ABI 17: two new entries, nothing existing changed): gradient, input x gradient and integrated
+ * gradients of a row's score (reference score.py get_attributions). The boundary kernels around an unchanged input-gradient pass.
+ * A call's work is the B * S (row, step) pairs r = b * S + k in that order (S = 1 for the one-pass methods); a pass takes the
+ * pairs r0 .. r0 + n_rows - 1 and may cut a row's steps. Both entries take their stream explicitly (as svdd_ism_*).
+ *
+ * svdd_attr_path: the interpolants of one pass. x [B, L] u8 (tokens 0..4; 4 = MASK: a zero one-hot row), baseline f32 [L, 4]
+ *   (baseline_rows == 1), [B, L, 4] (baseline_rows == B) or NULL (zeros; baseline_rows ignored), alpha [S] f32 (device).
+ *   out [n_rows + n_pad, L, 4] f32: row i < n_rows, pair r0 + i = (b, k), is base + alpha[k] * (onehot(x[b]) - base) evaluated as
+ *   three separately rounded fp32 operations (sub, mul, add; no contraction): with baseline NULL and alpha[k] == 1 the exact
+ *   one-hot. Rows n_rows .. n_rows + n_pad - 1 are copies of row 0 (a pass padded to a row count of the caller's choosing). A token
+ *   > 4 sets err[0] = 1 (err: caller-zeroed device word or NULL, read later) and is treated as 4. One thread per position (16
+ *   bytes: float4 where out and baseline are 16-byte aligned, scalars otherwise, same results), grid-stride: no result depends on
+ *   the launch shape. SVDD_E_ARG: B, L, S or n_rows <= 0, n_pad < 0, r0 < 0, r0 + n_rows > B * S, a NULL x, alpha or out,
+ *   baseline given with baseline_rows not 1 or B, (n_rows + n_pad) * L >= 2^40.
+ *
+ * svdd_attr_fold: folds one pass's gradients grad [>= n_rows, L, 4] f32 (svdd_attr_path's row order; rows beyond n_rows are not
+ *   read) into acc [B, L, 4] f32. For every row b with pairs in the pass, in ascending k:
+ *       acc[b, l, c] = acc[b, l, c] + weight[k] * (scale * grad[i, l, c])          (three separately rounded fp32 operations)
+ *   A row's accumulator starts from 0 at its pair k == 0 (acc is not read there) and continues from acc otherwise: passes are
+ *   folded in ascending r0, and the result does not depend on where they were cut. weight [S] f32 (device); scale: the factor that
+ *   turns the pass's gradient into the row's (the row count of a pass that differentiated the mean over its rows). When the row's
+ *   last pair k == S - 1 lies in the pass the row is finished, attr [B, 4, L] f32 (transposed):
+ *     SVDD_ATTR_GRADIENT     attr[b, c, l] = acc[b, l, c]
+ *     SVDD_ATTR_TIMES_INPUT  attr[b, c, l] = (onehot(x[b])[l, c] - base[l, c]) * acc[b, l, c]     (base as in svdd_attr_path)
+ *   and, rowsum [B] f32 non-NULL, rowsum[b] = the sum of the row's 4 L attr values in a fixed order: lane j of the row's wave adds
+ *   the positions l = j, j + 64, ... in ascending l, channels 0..3 inside a position, onto 0; then the 64 partial sums meet in an
+ *   xor butterfly (offsets 32, 16, .. 1). No float atomics; one wave per row, rows are independent (a NaN stays in its row), no
+ *   result depends on the launch shape. SVDD_E_ARG: B, L, S or n_rows <= 0, r0 < 0, r0 + n_rows > B * S, a mode other than the
+ *   two, a NULL grad, weight, x, acc or attr, baseline given with baseline_rows not 1 or B, attr / acc / grad not pairwise distinct.
+ */
+#define SVDD_ATTR_GRADIENT 0
+#define SVDD_ATTR_TIMES_INPUT 1
+int svdd_attr_path(const uint8_t* x, const float* baseline, int baseline_rows, const float* alpha, int B, int L, int S, int r0,
+                   int n_rows, int n_pad, float* out, int32_t* err, void* on_stream);
+int svdd_attr_fold(const float* grad, float scale, const float* weight, const uint8_t* x, const float* baseline, int baseline_rows,
+                   int B, int L, int S, int r0, int n_rows, int mode, float* acc, float* attr, float* rowsum, void* on_stream);
+
+/*
  * svdd_select — replaces torch.stack(scores,1) -> softmax(dim=1) -> argmax(dim=1) ->
  * per-row Python gather + stack                     diffusion_gosai.py:1219-1227 (= :1451-1459)
  *

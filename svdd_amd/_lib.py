@@ -21,6 +21,7 @@ RNG_REPLAY, RNG_PHILOX = 0, 1
 SELECT_ARGMAX, SELECT_MULTINOMIAL = 0, 1
 TARGET_MEAN, TARGET_LOGMEANEXP = 0, 1                              # SVDD_TARGET_* of include/svdd_hip.h
 EVOLVE_GLOBAL, EVOLVE_ROW = 0, 1                                   # SVDD_EVOLVE_* of include/svdd_hip.h
+ATTR_GRADIENT, ATTR_TIMES_INPUT = 0, 1                             # SVDD_ATTR_* of include/svdd_hip.h
 PRECISIONS = {"f32": 0, "f16x3": 1, "bf16x3": 2, "f16": 3, "bf16": 4}      # enum SVDD_PREC_* of include/svdd_hip.h
 MAX_M = 1024
 
@@ -127,6 +128,8 @@ SIGNATURES = {
     "svdd_ism_mutants": (vp, vp, vp, i32, i32, i32, vp, vp, vp, vp),
     "svdd_ism_fold": (vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp),
     "svdd_evolve_apply": (vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp),
+    "svdd_attr_path": (vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp),
+    "svdd_attr_fold": (vp, f32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp),
 }
 EXPORTS = tuple(SIGNATURES)
 

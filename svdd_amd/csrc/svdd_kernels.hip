@@ -17,6 +17,8 @@
 //   K14 value_target_kernel  the step boundary of a CD-Q rollout: continue from the last draw, reduce the draws' values to a target
 //   K15 ism_mutants_kernel / K16 ism_fold_kernel / K17 evolve_apply_kernel  in-silico mutagenesis: the single-base mutants of a
 //       batch, their scores folded into the ISM table and a per-row best, one iteration's boundary of ISM-driven evolution
+//   K18 attr_path_kernel / K19 attr_fold_kernel  gradient attributions: the interpolants of a chunk of (row, step) pairs, their
+//       gradients folded into the per-row accumulator and the finished [B, 4, L] table
 //   K4 tds_resample_kernel  SMC/TDS resampling (baseline)
 #include <float.h>
 #include <stdlib.h>
@@ -1487,6 +1489,114 @@ __global__ __launch_bounds__(1024) void evolve_apply_kernel(EvolveArgs a) {
   }
 }
 
+// ------------------------------------------------- K18-K19 gradient attributions (under ABI 17) ----
+// A position's four channels as one 16-byte access where the pointers are 16-byte aligned (VEC), four scalars otherwise.
+template <bool VEC>
+__device__ __forceinline__ float4 attr_ld4(const float* p) {
+  if (VEC) return *reinterpret_cast<const float4*>(p);
+  return make_float4(p[0], p[1], p[2], p[3]);
+}
+
+template <bool VEC>
+__device__ __forceinline__ void attr_st4(float* p, float4 v) {
+  if (VEC) {
+    *reinterpret_cast<float4*>(p) = v;
+  } else {
+    p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
+  }
+}
+
+__device__ __forceinline__ float4 attr_onehot(uint32_t t) {
+  return make_float4(t == 0u ? 1.0f : 0.0f, t == 1u ? 1.0f : 0.0f, t == 2u ? 1.0f : 0.0f, t == 3u ? 1.0f : 0.0f);
+}
+
+// K18 attr_path_kernel: one thread per (output row, position), grid-stride. Output row i < n_rows is the global (row, step) pair
+// r = r0 + i = (b, k); a pad row recomputes output row 0 from the same inputs (the same bits). Three separately rounded operations.
+struct AttrPathArgs {
+  const uint8_t* x; const float* baseline; int per_row; const float* alpha; int L, S, r0, n_rows; int64_t total;
+  float* out; int32_t* err;
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void attr_path_kernel(AttrPathArgs a) {
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  bool bad = false;
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < a.total; e += stride) {
+    const int64_t i = e / a.L;
+    const int l = (int)(e - i * a.L);
+    const int64_t r = (int64_t)a.r0 + (i < a.n_rows ? i : 0);
+    const int64_t b = r / a.S;
+    const float al = a.alpha[r - b * a.S];
+    uint32_t t = a.x[b * a.L + l];
+    if (t > 4u) { bad = true; t = 4u; }
+    const float4 oh = attr_onehot(t);
+    float4 base = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (a.baseline) base = attr_ld4<VEC>(a.baseline + ((a.per_row ? b * a.L : 0) + l) * 4);
+    float4 v;
+    v.x = __fadd_rn(base.x, __fmul_rn(al, __fsub_rn(oh.x, base.x)));
+    v.y = __fadd_rn(base.y, __fmul_rn(al, __fsub_rn(oh.y, base.y)));
+    v.z = __fadd_rn(base.z, __fmul_rn(al, __fsub_rn(oh.z, base.z)));
+    v.w = __fadd_rn(base.w, __fmul_rn(al, __fsub_rn(oh.w, base.w)));
+    attr_st4<VEC>(a.out + e * 4, v);
+  }
+  if (bad && a.err) a.err[0] = 1;
+}
+
+// K19 attr_fold_kernel: one wave per row b that has pairs in this pass; a lane takes the positions l = lane, lane + 64, ... and runs
+// the row's steps of this pass in ascending k on each: acc = acc + weight[k] * (scale * grad). The row whose last step is in the
+// pass is finished: attr [B, 4, L] (transposed: consecutive lanes write consecutive l of one channel), and the row sum as the
+// lane's sequential sum over its elements in (l, c) order, then a fixed xor butterfly.
+struct AttrFoldArgs {
+  const float* grad; float scale; const float* weight; const uint8_t* x; const float* baseline; int per_row;
+  int B, L, S, r0, n_rows, mode; float* acc; float* attr; float* rowsum;
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void attr_fold_kernel(AttrFoldArgs a) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int b_first = a.r0 / a.S, b_last = (int)(((int64_t)a.r0 + a.n_rows - 1) / a.S);
+  const int64_t bw = (int64_t)b_first + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (bw > b_last) return;                                          // whole waves only: the row is the wave's
+  const int b = (int)bw;
+  const int64_t p0 = (int64_t)b * a.S;                              // the row's first pair
+  const int k_lo = p0 >= a.r0 ? 0 : (int)(a.r0 - p0);
+  const int64_t end = (int64_t)a.r0 + a.n_rows - p0;
+  const int k_hi = end < a.S ? (int)end : a.S;
+  const bool last = k_hi == a.S;
+  float sum = 0.0f;
+  for (int l = lane; l < a.L; l += WAVE) {
+    float* ap = a.acc + ((int64_t)b * a.L + l) * 4;
+    float4 v = k_lo == 0 ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : attr_ld4<VEC>(ap);
+    for (int k = k_lo; k < k_hi; ++k) {
+      const float4 g = attr_ld4<VEC>(a.grad + ((p0 + k - a.r0) * a.L + l) * 4);
+      const float w = a.weight[k];
+      v.x = __fadd_rn(v.x, __fmul_rn(w, __fmul_rn(a.scale, g.x)));
+      v.y = __fadd_rn(v.y, __fmul_rn(w, __fmul_rn(a.scale, g.y)));
+      v.z = __fadd_rn(v.z, __fmul_rn(w, __fmul_rn(a.scale, g.z)));
+      v.w = __fadd_rn(v.w, __fmul_rn(w, __fmul_rn(a.scale, g.w)));
+    }
+    attr_st4<VEC>(ap, v);
+    if (!last) continue;
+    if (a.mode == SVDD_ATTR_TIMES_INPUT) {
+      uint32_t t = a.x[(int64_t)b * a.L + l];
+      const float4 oh = attr_onehot(t > 4u ? 4u : t);
+      float4 base = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (a.baseline) base = attr_ld4<VEC>(a.baseline + (((int64_t)(a.per_row ? b : 0)) * a.L + l) * 4);
+      v.x = __fmul_rn(__fsub_rn(oh.x, base.x), v.x);
+      v.y = __fmul_rn(__fsub_rn(oh.y, base.y), v.y);
+      v.z = __fmul_rn(__fsub_rn(oh.z, base.z), v.z);
+      v.w = __fmul_rn(__fsub_rn(oh.w, base.w), v.w);
+    }
+    float* o = a.attr + (int64_t)b * 4 * a.L + l;
+    o[0] = v.x; o[a.L] = v.y; o[2 * (int64_t)a.L] = v.z; o[3 * (int64_t)a.L] = v.w;
+    sum = __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(sum, v.x), v.y), v.z), v.w);
+  }
+  if (!last || !a.rowsum) return;
+#pragma unroll
+  for (int off = WAVE / 2; off > 0; off >>= 1) sum = __fadd_rn(sum, __shfl_xor(sum, off, WAVE));
+  if (lane == 0) a.rowsum[b] = sum;
+}
+
 // -------------------------------------------------------------------- K4 TDS resample ----
 // numpy's pairwise float32 sum (np.add.reduce), the order `ratio.sum()` uses at :1282: the array is halved (left half
 // rounded down to a multiple of 8) until a block has <= 128 elements; a block is summed with 8 running accumulators.
@@ -2312,6 +2422,36 @@ int svdd_evolve_apply(const float* best_score, const int32_t* best_pos, const in
   const EvolveArgs a{best_score, best_pos, best_allele, B, L, stop, x, score_cur, live, best_so_far, stopped, x_best, score_best,
                      tr_pos, tr_allele, tr_score, tr_taken};
   return svdd_launch(vec ? evolve_apply_kernel<true> : evolve_apply_kernel<false>, dim3(1), dim3(1024), 0, on_stream, a);
+}
+
+int svdd_attr_path(const uint8_t* x, const float* baseline, int baseline_rows, const float* alpha, int B, int L, int S, int r0,
+                   int n_rows, int n_pad, float* out, int32_t* err, void* on_stream) {
+  if (!x || !alpha || !out || B <= 0 || L <= 0 || S <= 0 || n_rows <= 0 || n_pad < 0 || r0 < 0) return SVDD_E_ARG;
+  if ((int64_t)r0 + n_rows > (int64_t)B * S) return SVDD_E_ARG;
+  if (baseline && baseline_rows != 1 && baseline_rows != B) return SVDD_E_ARG;
+  const int64_t total = ((int64_t)n_rows + n_pad) * L;
+  if (total >= (int64_t)1 << 40) return SVDD_E_ARG;
+  const auto al = [](const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; };
+  const bool vec = al(out, 16) && al(baseline, 16);
+  const AttrPathArgs a{x, baseline, baseline && baseline_rows != 1, alpha, L, S, r0, n_rows, total, out, err};
+  const int64_t blocks = (total + 255) / 256;
+  return svdd_launch(vec ? attr_path_kernel<true> : attr_path_kernel<false>, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256),
+                     0, on_stream, a);
+}
+
+int svdd_attr_fold(const float* grad, float scale, const float* weight, const uint8_t* x, const float* baseline, int baseline_rows,
+                   int B, int L, int S, int r0, int n_rows, int mode, float* acc, float* attr, float* rowsum, void* on_stream) {
+  if (!grad || !weight || !x || !acc || !attr || B <= 0 || L <= 0 || S <= 0 || n_rows <= 0 || r0 < 0) return SVDD_E_ARG;
+  if ((int64_t)r0 + n_rows > (int64_t)B * S) return SVDD_E_ARG;
+  if (mode != SVDD_ATTR_GRADIENT && mode != SVDD_ATTR_TIMES_INPUT) return SVDD_E_ARG;
+  if (baseline && baseline_rows != 1 && baseline_rows != B) return SVDD_E_ARG;
+  if (attr == acc || (const float*)attr == grad || (const float*)acc == grad) return SVDD_E_ARG;
+  if ((int64_t)B * L >= (int64_t)1 << 40 || (int64_t)n_rows * L >= (int64_t)1 << 40) return SVDD_E_ARG;
+  const auto al = [](const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; };
+  const bool vec = al(grad, 16) && al(acc, 16) && al(baseline, 16);
+  const AttrFoldArgs a{grad, scale, weight, x, baseline, baseline && baseline_rows != 1, B, L, S, r0, n_rows, mode, acc, attr, rowsum};
+  const int64_t rows = ((int64_t)r0 + n_rows - 1) / S - r0 / S + 1;
+  return svdd_launch(vec ? attr_fold_kernel<true> : attr_fold_kernel<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, on_stream, a);
 }
 
 int svdd_tds_resample(const float* reward_num, const float* reward_den, double alpha, const uint8_t* sample,

@@ -1505,6 +1505,154 @@ class Diffusion(nn.Module):
                  "score": tr_score[:iters + 1]}
         return x_best.long(), score_best, trace
 
+    # ------------------------------------------------------------- gradient attributions ----
+    ATTR_METHODS = ("gradient", "inputxgradient", "integratedgradients")
+    ATTR_CHUNK_ROWS = 1024                # default rows per gradient pass: mean_score_input_grad's work buffers (save, gates, out, gout,
+                                          # dxg and the seven tower activations) are 1.38 MB per row at L = 200, 1.4 GiB per pass
+
+    @staticmethod
+    def _attr_quadrature(n_steps, quadrature):
+        """-> (alphas, weights) as float32 numpy arrays [S]. None: Gauss-Legendre on [0, 1] (captum's default rule), computed in
+        float64 and rounded once."""
+        if quadrature is None:
+            node, weight = np.polynomial.legendre.leggauss(int(n_steps))
+            return ((1.0 + node) / 2.0).astype(np.float32), (weight / 2.0).astype(np.float32)
+        if not isinstance(quadrature, (tuple, list)) or len(quadrature) != 2:
+            raise ValueError("quadrature must be None or a pair (alphas, weights)")
+        a, w = (torch.as_tensor(q).detach().cpu().double().numpy() for q in quadrature)
+        if a.ndim != 1 or w.ndim != 1 or a.size == 0 or a.size != w.size:
+            raise ValueError(f"quadrature: alphas and weights must be 1-D of one (non-zero) length, got {a.shape} and {w.shape}")
+        return a.astype(np.float32), w.astype(np.float32)
+
+    def _attr_inputs(self, x, method, baseline, n_steps, quadrature, chunk_rows, return_delta):
+        """Checks in an order that needs no device until the last one (as _ism_inputs) -> (x u8 [B, L], baseline | None, alphas,
+        weights: fp32 device [S], chunk_rows)."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] == 0 or x.shape[1] == 0:
+            raise ValueError(f"x must be a [B, L] tensor with B, L > 0, got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)}")
+        B, L = x.shape
+        if method not in self.ATTR_METHODS:
+            raise ValueError(f"method = {method!r}: expected one of {self.ATTR_METHODS}")
+        ig = method == "integratedgradients"
+        if return_delta and not ig:
+            raise ValueError(f"return_delta is the completeness gap of integrated gradients; method = {method!r} has none")
+        if baseline is not None:
+            if not isinstance(baseline, torch.Tensor) or baseline.dtype != torch.float32:
+                raise ValueError(f"baseline must be None or an fp32 tensor, got {getattr(baseline, 'dtype', type(baseline))}")
+            if tuple(baseline.shape) not in ((L, 4), (B, L, 4)):
+                raise ValueError(f"baseline must be [{L}, 4] or [{B}, {L}, 4], got {tuple(baseline.shape)}")
+        if ig:
+            if quadrature is None and int(n_steps) <= 0:
+                raise ValueError(f"n_steps must be positive, got {n_steps}")
+            alphas, weights = self._attr_quadrature(n_steps, quadrature)
+        else:
+            alphas = weights = np.ones(1, np.float32)               # one pass at the input itself
+        if chunk_rows is not None and int(chunk_rows) <= 0:
+            raise ValueError(f"chunk_rows must be positive, got {chunk_rows}")
+        x_u8, _ = self._refine_inputs(x, None)
+        self._require_gpu()
+        if baseline is not None:
+            if baseline.device != self.device:
+                raise ops.SvddError("baseline must be a tensor on the model's GPU (the SVDD hot path has no CPU fallback)")
+            baseline = baseline.contiguous()
+        dev = self.device
+        return (x_u8, baseline, torch.from_numpy(alphas).to(dev), torch.from_numpy(weights).to(dev),
+                self.ATTR_CHUNK_ROWS if chunk_rows is None else int(chunk_rows))
+
+    def _attr_route(self, pre_scorer_embedding, pre_scorer_head, reward_model, L):
+        """-> (fused net | None, score_fn). fused: the FusedValueNet whose mean_score_input_grad gives the pass's gradient without
+        autograd (the reference-shaped ConvGRU net, one task, grad_ok(L): _classifier_fused_value's condition). score_fn: relaxed
+        input fp32 [n, L, 4] -> task-0 scores [n], differentiable, always fp32: forward_grad of a fused ConvGRU net at any length its
+        kernels take, else the modules themselves (the reward model is fed [n, 4, L], as in _design_scorer) inside
+        _gru_backward_ready."""
+        from .fused import FusedValueNet
+        fn = (self.value_callable(pre_scorer_embedding, pre_scorer_head) if reward_model is None
+              else self.reward_callable(reward_model))
+        if isinstance(fn, FusedValueNet) and fn.tower_ok and fn.tail_ok and L <= 208 and all(p.numel() for p in fn.wpacks):
+            fused = fn if fn.grad_ok(L) and fn.w_eff.shape[1] == 1 else None
+            return fused, lambda xin: fn.forward_grad(xin).reshape(xin.shape[0], -1)[:, 0]
+        if reward_model is None:
+            mods = [m for m in (pre_scorer_embedding, pre_scorer_head) if isinstance(m, nn.Module)]
+            run = lambda xin: pre_scorer_head(pre_scorer_embedding(xin))                        # noqa: E731
+        else:
+            mods = [reward_model] if isinstance(reward_model, nn.Module) else []
+            run = lambda xin: reward_model(xin.transpose(1, 2))                                 # noqa: E731
+
+        def score_fn(xin):
+            with self._gru_backward_ready(mods, xin.is_cuda):
+                s = run(xin).float().reshape(xin.shape[0], -1)[:, 0]
+                if not xin.requires_grad:
+                    return s
+                return s, torch.autograd.grad(s.sum(), xin)[0]      # the backward pass inside the context too
+        return None, score_fn
+
+    def attributions(self, x, pre_scorer_embedding, pre_scorer_head, reward_model=None, method="inputxgradient", baseline=None,
+                     n_steps=50, quadrature=None, chunk_rows=None, return_delta=False):
+        """Per-nucleotide gradient attributions of a row's score (reference score.py get_attributions, the last step of the
+        reference's evolution script): x [B, L] tokens 0..4 on the GPU -> fp32 [B, 4, L]. The score is PER ROW, task 0 of
+        pre_scorer_head(pre_scorer_embedding(.)), or reward_model's if given (no 1 / B factor, unlike compute_gradient). MASK (4) is
+        allowed: its one-hot row is zero, so its input x gradient / IG column is 0 with baseline None.
+          method = "gradient"             d score / d onehot: all four bases per position (the hypothetical table)
+                   "inputxgradient"       onehot * gradient (the reference script's choice)
+                   "integratedgradients"  (onehot - baseline) * sum_k w_k grad(baseline + alpha_k (onehot - baseline))
+          baseline    None = zeros (captum's default), or fp32 [L, 4] (shared) / [B, L, 4] (per row); the x input methods multiply by
+                      (onehot - baseline)
+          quadrature  None = Gauss-Legendre with n_steps nodes on [0, 1] (captum's default; float64 on the host, rounded once to
+                      fp32), or a pair (alphas, weights) of equal-length 1-D tensors; n_steps is ignored by the one-pass methods
+          chunk_rows  rows per gradient pass (default ATTR_CHUNK_ROWS = 1024: 1.4 GiB of work buffers at L = 200). On the fused route a
+                      pass runs on a power-of-two number of rows (the largest <= chunk_rows, at most the next one >= the rows left;
+                      the last pass is padded with copies of its first row), so that the 1 / n of mean_score_input_grad's mean is
+                      undone exactly: the table does not depend on chunk_rows
+          return_delta  (IG only) also the completeness gap per row, sum(attr[b]) - (score(x_b) - score(baseline_b)) fp32 [B]
+        The B * S (row, step) pairs run in passes of svdd_attr_path, the gradient, svdd_attr_fold; nothing crosses to the host. The
+        fused ConvGRU value net (one task, L = 200 or 50) takes mean_score_input_grad as it is, no autograd; any other net or length
+        takes torch autograd of the sum of the pass's scores. The gradient is fp32 whatever self.precision says."""
+        x_u8, baseline, alphas, weights, chunk_rows = self._attr_inputs(x, method, baseline, n_steps, quadrature, chunk_rows,
+                                                                         return_delta)
+        B, L = x_u8.shape
+        S = alphas.numel()
+        dev = self.device
+        fused, score_fn = self._attr_route(pre_scorer_embedding, pre_scorer_head, reward_model, L)
+        total = B * S
+        cap = 1 << (chunk_rows.bit_length() - 1)                    # the largest power of two <= chunk_rows
+        rows_buf = min(cap, 1 << (total - 1).bit_length()) if fused is not None else min(chunk_rows, total)
+        path = torch.empty((rows_buf, L, 4), dtype=torch.float32, device=dev)
+        acc = torch.empty((B, L, 4), dtype=torch.float32, device=dev)
+        attr = torch.empty((B, 4, L), dtype=torch.float32, device=dev)
+        rowsum = torch.empty(B, dtype=torch.float32, device=dev) if return_delta else None
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        mode = "gradient" if method == "gradient" else "times_input"
+        path_base = baseline if method == "integratedgradients" else None      # the one-pass methods differentiate at the exact one-hot
+        r0 = 0
+        while r0 < total:
+            left = total - r0
+            if fused is not None:
+                n_pass = min(cap, 1 << (left - 1).bit_length())
+                n = min(n_pass, left)
+                with torch.no_grad():
+                    xin = ops.attr_path(x_u8, alphas, r0, n, path[:n_pass], baseline=path_base, n_pad=n_pass - n, err=err)
+                    grad, scale = fused.mean_score_input_grad(xin), float(n_pass)
+            else:
+                n = min(rows_buf, left)
+                with torch.no_grad():
+                    ops.attr_path(x_u8, alphas, r0, n, path[:n], baseline=path_base, err=err)
+                xin = path[:n].detach().requires_grad_(True)
+                with torch.enable_grad():                           # the gradient of the SUM of the pass's scores: scale 1
+                    out = score_fn(xin)
+                    grad = out[1] if isinstance(out, tuple) else torch.autograd.grad(out.sum(), xin)[0]
+                grad, scale = grad.contiguous(), 1.0
+            with torch.no_grad():
+                ops.attr_fold(grad, scale, weights, x_u8, r0, n, acc, attr, mode=mode, baseline=baseline, rowsum=rowsum)
+            r0 += n
+        ops.check_attr_err(err)
+        if not return_delta:
+            return attr
+        with torch.no_grad():                                       # score(x) - score(baseline): one forward call on [x; baseline]
+            ends = torch.empty((2 * B, L, 4), dtype=torch.float32, device=dev)
+            ends[:B] = ops.transform_samples(x_u8)
+            ends[B:] = 0.0 if baseline is None else baseline
+            sc = score_fn(ends)
+            return attr, rowsum - (sc[:B] - sc[B:])
+
     # ------------------------------------------------------------- exact work-skipping ----
     def _can_skip(self, fn, L, M):
         """The skipping paths hand the nets compacted batches whose size only the device knows: they need the

@@ -205,6 +205,12 @@ class BaseModel(nn.Module):
         return self.ref_model.evolve(samples, self.embedding, self.head, reward_model=self.reward_model, max_iter=max_iter,
                                      positions=positions, stop=stop)
 
+    def get_attributions(self, samples, method="inputxgradient", **kw):
+        """Per-nucleotide attributions of samples [B, L] under the harness's reward model (reference score.py get_attributions;
+        Diffusion.attributions: method "gradient" / "inputxgradient" / "integratedgradients", baseline, n_steps, quadrature,
+        chunk_rows, return_delta) -> fp32 [B, 4, L]."""
+        return self.ref_model.attributions(samples, self.embedding, self.head, reward_model=self.reward_model, method=method, **kw)
+
     @torch.no_grad()
     def controlled_decode_tweedie(self, gen_batch_num, sample_M, options):
         """SVDD-PM (reference Enformer.py:719-813)."""

@@ -371,6 +371,67 @@ def evolve_apply(best, x, score_cur, best_so_far, stopped, x_best, score_best, s
               tp, ta, ts, tt, _this_stream())
 
 
+ATTR_MODE = {"gradient": _lib.ATTR_GRADIENT, "times_input": _lib.ATTR_TIMES_INPUT}
+
+
+def _attr_baseline(baseline, B, L):
+    """-> baseline_rows of the two attribution entries: baseline f32 [L, 4] (1), [B, L, 4] (B) or None (0: zeros)."""
+    if baseline is None:
+        return 0
+    _need(baseline, torch.float32, "baseline")
+    if not baseline.is_contiguous() or tuple(baseline.shape) not in ((L, 4), (B, L, 4)):
+        raise SvddError(f"baseline must be a contiguous fp32 [{L}, 4] or [{B}, {L}, 4] tensor, got {tuple(baseline.shape)}")
+    return 1 if baseline.dim() == 2 else B
+
+
+def attr_path(x, alpha, r0, n_rows, out, baseline=None, n_pad=0, err=None):
+    """svdd_attr_path: the interpolants base + alpha[k] * (onehot(x[b]) - base) of the (row, step) pairs r0 .. r0 + n_rows - 1
+    (pair r = b * S + k, S = alpha.numel()) into out f32 [n_rows + n_pad, L, 4] (caller-owned); the n_pad rows after them are
+    copies of row 0. x u8 [B, L] (4 = MASK: a zero one-hot row), alpha f32 [S], baseline f32 [L, 4] / [B, L, 4] / None (zeros).
+    err: a caller-zeroed device int32 [1] the kernel sets for a token > 4 (check_attr_err), or None."""
+    x = _need(x, torch.uint8, "x")
+    if x.dim() != 2 or not x.is_contiguous():
+        raise SvddError(f"x must be a contiguous u8 [B, L] tensor, got {tuple(x.shape)}")
+    B, L = x.shape
+    S = _need(alpha, torch.float32, "alpha").numel()
+    _is(alpha, torch.float32, (S,), "alpha")
+    _is(out, torch.float32, (int(n_rows) + int(n_pad), L, 4), "out")
+    if err is not None:
+        _is(err, torch.int32, (1,), "err")
+    _lib.call("svdd_attr_path", x, baseline, _attr_baseline(baseline, B, L), alpha, B, L, S, int(r0), int(n_rows), int(n_pad), out,
+              err, _this_stream())
+    return out
+
+
+def check_attr_err(err):
+    """Raise if svdd_attr_path flagged a token > 4 (SVDD_E_ARG)."""
+    if int(err[0]) != 0:
+        _lib.check(_lib.E_ARG, "svdd_attr_path: a row holds a token > 4")
+
+
+def attr_fold(grad, scale, weight, x, r0, n_rows, acc, attr, mode="times_input", baseline=None, rowsum=None):
+    """svdd_attr_fold: acc[b] += weight[k] * (scale * grad[i]) for the pairs r0 .. r0 + n_rows - 1 of svdd_attr_path's order (grad
+    f32 [>= n_rows, L, 4]; a row starts from 0 at its step 0), and every row whose last step is among them finished into attr f32
+    [B, 4, L]: acc itself (mode "gradient") or (onehot(x) - baseline) * acc ("times_input"); rowsum f32 [B] or None: the finished
+    rows' sums. acc f32 [B, L, 4], attr and rowsum are caller-owned; fold passes in ascending r0."""
+    if mode not in ATTR_MODE:
+        raise ValueError(f"mode = {mode!r}: expected 'gradient' or 'times_input'")
+    x = _need(x, torch.uint8, "x")
+    if x.dim() != 2 or not x.is_contiguous():
+        raise SvddError(f"x must be a contiguous u8 [B, L] tensor, got {tuple(x.shape)}")
+    B, L = x.shape
+    S = _need(weight, torch.float32, "weight").numel()
+    _is(weight, torch.float32, (S,), "weight")
+    _need(grad, torch.float32, "grad")
+    if not grad.is_contiguous() or grad.dim() != 3 or grad.shape[0] < int(n_rows) or tuple(grad.shape[1:]) != (L, 4):
+        raise SvddError(f"grad must be a contiguous fp32 [>= {n_rows}, {L}, 4] tensor, got {tuple(grad.shape)}")
+    _is(acc, torch.float32, (B, L, 4), "acc"), _is(attr, torch.float32, (B, 4, L), "attr")
+    if rowsum is not None:
+        _is(rowsum, torch.float32, (B,), "rowsum")
+    _lib.call("svdd_attr_fold", grad, float(scale), weight, x, baseline, _attr_baseline(baseline, B, L), B, L, S, int(r0), int(n_rows),
+              ATTR_MODE[mode], acc, attr, rowsum, _this_stream())
+
+
 def select(scores, cand, mode=SELECT_ARGMAX, rng=None, want_soft=True, x_next=None):
     """-> (x_next u8 [B,L], soft f32 [B,M] | None, idx i32 [B])."""
     cand = _need(cand, torch.uint8, "cand").contiguous()
