@@ -547,6 +547,17 @@ int svdd_conv_tower_windows_f32(const float* onehot, const float* tiles, const f
                                 const float* parent_out, float* out, int n, int L, int M, int nlayers,
                                 int residual_mask, const int32_t* live_idx, const int32_t* count, void* stream);
 
+/* svdd_candidate_windows_tight — svdd_candidate_windows with the window aligned at ONE end: same arguments, and
+ *     w0 = max(0, first - margin),  w1 = w0 + 16 * ceil((min(L, last + margin + 1) - w0) / 16),  flags = (w1 - w0) / 16,
+ *   (0, 0) and flag 0 for an exact copy. w0 is any row; w1 may pass L rounded up to 16, by less than a tile ((w1 - w0) / 16 <=
+ *   ceil(L / 16)). For svdd_conv_tower_windows_f32 only, whose kernels address everything relative to w0 and need a multiple of 16
+ *   of the LENGTH alone: any window that covers [first - margin, last + margin] gives the same rows inside its keep range, so the
+ *   tower output equals the aligned windows' bit for bit (tests/test_tower_tight_windows_gpu.py), with 0.33 row tiles less per
+ *   window over a decode (6.98 -> 6.65; a window that starts at row 0 was aligned already). The split-precision tower (svdd_conv_tower_windows_lp) takes aligned windows. The stream is the
+ *   explicit last argument. SVDD_E_ARG: a NULL cand, x or win; B, L or M <= 0; margin < 0 or > 2^20; B * M >= 2^31. */
+int svdd_candidate_windows_tight(const uint8_t* cand, const uint8_t* x, int B, int L, int M, int margin, int32_t* win,
+                                 int32_t* flags, void* on_stream);
+
 /* svdd_backbone_cnn_f32 — the whole dilated-CNN masked-diffusion backbone at sigma = 0 in ONE launch
  *   (reference models/dnaconv.py:176-210 as called from diffusion_gosai.py:334-340): one-hot + 9-tap first conv,
  *   nlayers x [LayerNorm(f + tb_i) -> dilated 9-tap conv 128->128 -> ReLU -> + f], then the two 1x1 convs of

@@ -130,6 +130,7 @@ SIGNATURES = {
     "svdd_evolve_apply": (vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp),
     "svdd_attr_path": (vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp),
     "svdd_attr_fold": (vp, f32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp),
+    "svdd_candidate_windows_tight": (vp, vp, i32, i32, i32, i32, vp, vp, vp),
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -1335,7 +1335,11 @@ __global__ __launch_bounds__(512, 4) void conv_tower2_kernel(TowerWinArgs wa) {
   }
 }
 
-// (w0, w1) of every candidate: one wave per candidate compares it with its parent.
+// (w0, w1) of every candidate: one wave per candidate compares it with its parent. TIGHT (svdd_candidate_windows_tight): the window
+// starts AT the first row it needs, w0 = max(0, lo - margin), and only its length is a multiple of 16 — the window kernels address
+// the one-hot rows, the LDS image, the keep range and the row stores relative to w0 and need nothing of w0 itself; w1 may then pass
+// L rounded up to 16 (never by a whole tile: (w1 - w0) / 16 <= ceil(L / 16)).
+template <bool TIGHT>
 __global__ __launch_bounds__(256) void candidate_windows_kernel(const uint8_t* __restrict__ cand, const uint8_t* __restrict__ x,
                                                                int n, int L, int M, int margin, int* __restrict__ win,
                                                                int* __restrict__ flags) {
@@ -1351,7 +1355,10 @@ __global__ __launch_bounds__(256) void candidate_windows_kernel(const uint8_t* _
   for (int off = 32; off > 0; off >>= 1) { lo = min(lo, __shfl_xor(lo, off, 64)); hi = max(hi, __shfl_xor(hi, off, 64)); }
   if (lane == 0) {
     int w0 = 0, w1 = 0;
-    if (hi >= 0) {
+    if (hi >= 0 && TIGHT) {
+      w0 = max(0, lo - margin);
+      w1 = w0 + ((min(L, hi + margin + 1) - w0 + 15) & ~15);
+    } else if (hi >= 0) {
       w0 = max(0, lo - margin) & ~15;
       w1 = min((L + 15) & ~15, (hi + margin + 1 + 15) & ~15);
     }
@@ -2089,25 +2096,40 @@ __global__ __launch_bounds__(256, NC == 4 ? 2 : NC == 1 ? 4 : 3) void backbone_s
       toks[e] = (p >= 0 && p < L) ? (int)a.x[(size_t)seq * L + p] : -1;
     }
     __syncthreads();
+    // f_0 of the item's rows goes through the (still unused) image: thread (ri, c) builds row ri, channel c with its nine table
+    // reads issued together, at a clamped index and with no branch between them — four elements (36 reads) per wait, 32 (ri, c)
+    // pairs per thread for a 2-tile item. (Built straight into the MFMA layout, every lane made 9 dependent, branch-guarded reads
+    // for each of its 32 elements: 288 round trips to L2 in a row, 24 us per launch; batching them THERE costs 128 - 168 VGPRs and
+    // scratch.) A wave shares the row, so the reads of a tap are 256 consecutive bytes and the tokens are wave-uniform. The sum is
+    // backbone_kernel's: start b0, taps in order, a tap outside the sequence SKIPPED (a select, never an added 0.0f: -0.0 must
+    // stay -0.0).
+    {
+      const int c = tid & (BB_C - 1);
+      const float b0 = a.vec[c];
+#pragma unroll 4
+      for (int ri = tid >> 7; ri < 16 * (nown + 2); ri += 2) {
+        int tk[9];
+        float tv[9];
 #pragma unroll
-    for (int ct = 0; ct < 2; ++ct) {
-      const int col = col0 + 16 * ct;
-      const float b0 = a.vec[col];
-#pragma unroll
-      for (int s = 0; s < NS; ++s) {
-        if (!SEG_LIVE(s)) continue;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int ri = 16 * s + 4 * g + e, row = r0 + ri;
-          float v = b0;
-#pragma unroll
-          for (int t = 0; t < 9; ++t) {
-            const int tk = toks[ri + t];                  // sequence row row + t - 4 ; -1 outside the sequence
-            if (tk >= 0) v += a.table0[(t * 5 + tk) * BB_C + col];
-          }
-          f[s][ct][e] = (row >= 0 && row < L) ? fmaxf(v, 0.0f) : 0.0f;
+        for (int t = 0; t < 9; ++t) {
+          tk[t] = toks[ri + t];                           // sequence row r0 + ri + t - 4 ; -1 outside the sequence
+          tv[t] = a.table0[(unsigned)((t * 5 + max(tk[t], 0)) * BB_C + c)];
         }
+        float v = b0;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) v = tk[t] >= 0 ? v + tv[t] : v;
+        const int row = r0 + ri;
+        img[ri * BB_AP + c] = (row >= 0 && row < L) ? fmaxf(v, 0.0f) : 0.0f;
       }
+    }
+    __syncthreads();                                      // (the image is next written behind the LayerNorm barriers below)
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      if (!SEG_LIVE(s)) continue;
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) f[s][ct][e] = img[(16 * s + 4 * g + e) * BB_AP + col0 + 16 * ct];
     }
   } else {
     const float* src = pl0 + (size_t)(a.layer - 2) * pl_stride;
@@ -3412,7 +3434,16 @@ extern "C" int svdd_candidate_windows(const uint8_t* cand, const uint8_t* x, int
                                       int32_t* flags, void* stream) {
   if (!cand || !x || !win || B <= 0 || L <= 0 || M <= 0 || margin < 0) return SVDD_E_ARG;
   const int n = B * M;
-  return svdd_launch(candidate_windows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, cand, x, n, L, M, margin, win, flags);
+  return svdd_launch(candidate_windows_kernel<false>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, cand, x, n, L, M, margin, win, flags);
+}
+
+extern "C" int svdd_candidate_windows_tight(const uint8_t* cand, const uint8_t* x, int B, int L, int M, int margin, int32_t* win,
+                                            int32_t* flags, void* on_stream) {
+  if (!cand || !x || !win || B <= 0 || L <= 0 || M <= 0 || margin < 0 || margin > (1 << 20) ||
+      (long long)B * M > 0x7fffffffLL)
+    return SVDD_E_ARG;
+  const int n = B * M;
+  return svdd_launch(candidate_windows_kernel<true>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, on_stream, cand, x, n, L, M, margin, win, flags);
 }
 
 extern "C" int svdd_conv_tower_windows_f32(const float* onehot, const float* tiles, const float* bias, const int32_t* win,

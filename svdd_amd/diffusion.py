@@ -1399,7 +1399,6 @@ class Diffusion(nn.Module):
     def _ism_pass(self, x, pos_dev, P, Pc, score_fn, fused, ws, parent_score, live=None, ism=None, best=None):
         """The mutants of x at every position, chunk by chunk in ascending position order: svdd_ism_mutants, the value net, and
         svdd_ism_fold into ism [B, P, 4] and / or the running best. Nothing returns to the host."""
-        from . import fused as F_
         B, L = x.shape
         lp = fused is not None and fused.precision != "f32"
         if fused is not None:                                       # the parents' tower output, once per pass
@@ -1415,12 +1414,12 @@ class Diffusion(nn.Module):
             onehot = None if lp else ws.onehot[:n * L * 4].view(n, L, 4)
             ops.ism_mutants(x, pos_dev[p0:p0 + pc], live, cand=cand, onehot=onehot, want_onehot=False, err=ws.err)
             if live is None:
-                win = F_.candidate_windows(cand, x)
+                win = fused.windows_of(cand, x)
                 sc = fused.forward_candidates_from(onehot, cand, win, parent_out)
                 slot = None
             else:                                                   # stopped rows' mutants are exact copies: flagged 0, dropped
                 flags, live_idx, slot = ws.flags[:n], ws.live_idx[:n], ws.slot[:n]
-                win = F_.candidate_windows(cand, x, flags=flags)
+                win = fused.windows_of(cand, x, flags=flags)
                 ops.compact_flags(flags, live_idx, slot, ws.count)
                 sc = fused.forward_candidates_from(onehot, cand, win, parent_out, live_idx=live_idx, count=ws.count)
             sc = sc.reshape(n, -1)

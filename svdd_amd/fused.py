@@ -644,13 +644,19 @@ def value_tail_lp(h, w1pack, b1f, w_eff, b_eff, inv, prec, count=None, out=None)
 TOWER_WINDOW_MARGIN = 27     # +-17 rows receptive field of the 5-layer tower + 10 rows of window-edge error
 
 
-def candidate_windows(cand, x, margin=TOWER_WINDOW_MARGIN, flags=None):
+def candidate_windows(cand, x, margin=TOWER_WINDOW_MARGIN, flags=None, tight=False):
     """cand [B, M, L] u8, x [B, L] u8 -> int32 [B*M, 2]: the 16-aligned row window (w0, w1) around the positions where a
-    candidate differs from its parent, (0, 0) for an exact copy (HIP kernel svdd_candidate_windows)."""
+    candidate differs from its parent, (0, 0) for an exact copy (HIP kernel svdd_candidate_windows). tight: the window starts at
+    the first row it needs and only its length is a multiple of 16 (svdd_candidate_windows_tight; for the fp32 windowed tower).
+    flags (int32 [B*M], optional) receives the windows' tile counts."""
     assert cand.is_cuda and cand.dtype == torch.uint8 and cand.is_contiguous() and x.dtype == torch.uint8 and x.is_contiguous()
     B, M, L = cand.shape
     win = torch.empty((B * M, 2), dtype=torch.int32, device=cand.device)
-    _lib.call("svdd_candidate_windows", cand, x, B, L, M, margin, win, flags)
+    if tight:                                                                  # this entry takes its stream as an explicit argument
+        _lib.call("svdd_candidate_windows_tight", cand, x, B, L, M, margin, win, flags,
+                  ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    else:
+        _lib.call("svdd_candidate_windows", cand, x, B, L, M, margin, win, flags)
     return win
 
 
@@ -755,6 +761,7 @@ class FusedValueNet(nn.Module):
         self.split_gru_rounds = True         # candidate_scores_compact, late steps: the live candidates as two parts so that the GRU's second round
                                              # hides under the first part's tower (same bits; _windows_gru_tail_split)
         self.sort_live_by_window = True      # candidate_scores_compact: live candidates ordered by window size, largest first (A/B knob; same bits)
+        self.tight_windows = True            # fp32 windowed tower: windows aligned at one end only (candidate_windows(tight=True); A/B knob; same bits)
         # "f32" (exact, default) or one of LP_DTYPES: the conv tower, GRU and tail on the 16-bit matrix cores
         # (csrc/svdd_lp_*.hip). Needs the reference-shaped net (tower_ok, tail_ok).
         self.precision = "f32"
@@ -889,7 +896,7 @@ class FusedValueNet(nn.Module):
         valid, in live_idx order). Same kernels, same bits per candidate as forward_candidates; no host round trip."""
         from . import ops
         B, M, L = cand.shape
-        win = candidate_windows(cand, x, flags=ws.flags)
+        win = self.windows_of(cand, x, flags=ws.flags)   # ws.flags = the windows' tile counts: the sort key below
         # the live candidates by DESCENDING window size: a windowed-tower workgroup takes as many row tiles as its window has, and
         # with the long ones dispatched first the launch does not end on a few CUs that began a 13-tile window last (fp32 tower
         # 487 -> 395 us per launch on a C2 decode's states, tools/tower_order_probe.py). A row's result does not depend on its
@@ -1024,6 +1031,12 @@ class FusedValueNet(nn.Module):
         return (self.use_fused_tower and self.tower_ok and self.share_parent_tower and M > 1 and 104 < L <= 208 and
                 self.tw_bias.shape[0] == 6)
 
+    def windows_of(self, cand, x, flags=None):
+        """candidate_windows for this net's windowed tower: tight windows on the fp32 kernels (conv_tower_win_kernel and
+        conv_tower2_kernel take any w0), 16-aligned ones whenever a split precision is set (svdd_conv_tower_windows_lp needs them;
+        the fp32 kernels take either)."""
+        return candidate_windows(cand, x, flags=flags, tight=self.tight_windows and self.precision == "f32")
+
     def forward_candidates(self, onehot, cand, x):
         """Scores of the B*M candidates (onehot [B*M, L, 4], row b*M + m; cand [B, M, L] u8) of the parents x [B, L] u8.
         Same result as forward(onehot), bit for bit; the conv tower is evaluated once per parent and, per candidate,
@@ -1037,7 +1050,7 @@ class FusedValueNet(nn.Module):
             seq = conv_tower_windows_lp(cand, win, parent_out, pk["tiles"], self.tw_bias, pk["tinv"], self.tw_resmask, pk["prec"])
             return self._after_tower_lp(seq, pk)
         parent_out = conv_tower(ops.transform_samples(x), self.tw_tiles, self.tw_bias, self.tw_resmask)
-        win = candidate_windows(cand, x)
+        win = self.windows_of(cand, x)
         seq = conv_tower_windows(onehot, win, parent_out, M, self.tw_tiles, self.tw_bias, self.tw_resmask)
         return self._after_tower(seq, B * M, L)
 
