@@ -320,6 +320,41 @@ int svdd_attr_fold(const float* grad, float scale, const float* weight, const ui
                    int B, int L, int S, int r0, int n_rows, int mode, float* acc, float* attr, float* rowsum, void* on_stream);
 
 /*
+ * Sample-quality metrics of a set of sequences (added under ABI 17: three new entries, nothing existing changed): k-mer spectra
+ * (reference oracle.py count_kmers, diffusion_gosai.py compare_kmer) and Hamming distances on 2-bit-packed rows (nearest
+ * neighbour and the histogram of all pairs: diversity and novelty, which the reference does not have). All three are integer
+ * arithmetic with integer atomics only: no result depends on the launch shape or on how the caller cuts its rows into chunks.
+ * Every entry takes its stream explicitly (as svdd_ism_* and svdd_attr_*).
+ *
+ * svdd_kmer_counts: x [N, L] u8. counts [4^k] i64 and skipped [1] i64 or NULL are ACCUMULATED INTO (the caller zeroes them), so
+ *   a set can be fed in chunks of rows. The window of row r at i = 0 .. L - k has bin sum_j x[r, i + j] 4^(k - 1 - j): the
+ *   lexicographic rank of its detokenised ACGT string. A window that holds a token > 3 (MASK included) is not counted and adds 1
+ *   to skipped. k > L is valid: there are no windows and nothing is written. k = 1 .. 6 (4096 bins). A workgroup counts a run of
+ *   rows into a u32 histogram in LDS and adds its non-zero bins with 64-bit integer atomics; it takes at most
+ *   floor((2^32 - 1) / (L - k + 1)) rows, so no u32 bin can wrap. SVDD_E_ARG: N or L <= 0, k outside 1 .. 6, a NULL x or counts.
+ *
+ * svdd_pack_tokens: x [N, L] u8 (tokens 0..3) -> packed [N, W] u32, W = ceil(L / 16): position l sits in word l / 16 at bits
+ *   2 (l mod 16), 2 (l mod 16) + 1; the padding bits of the last word are zero. A token > 3 sets err[0] = 1 (err: caller-zeroed
+ *   device word or NULL, read later) and packs as 0. One thread per word, grid-stride. SVDD_E_ARG: N or L <= 0, L > 1024, a NULL
+ *   x or packed.
+ *
+ * svdd_hamming_nn: q [B, W] and db [N, W] packed u32 (svdd_pack_tokens). For every pair (i, j), d = the number of positions at
+ *   which the rows differ, per word popc((v | v >> 1) & 0x55555555) of v = q ^ db (the padding bits of the last word are masked
+ *   out on both sides). With exclude_diag != 0 the pairs with q_base + i == db_base + j are left out of everything.
+ *   nn_key [B] u64 or NULL, initialised by the caller to all ones: nn_key[i] = min(nn_key[i], (uint64(d) << 32) | uint32(db_base
+ *   + j)) by 64-bit integer atomic min: the smallest distance and, among ties, the smallest database index (first wins); a query
+ *   with no pair keeps its value. hist [L + 1] i64 or NULL, ACCUMULATED INTO: the number of pairs at each distance. Both are exact
+ *   and independent of how the database (db_base) and the queries (q_base) are cut into calls. A thread keeps one query's W <= 64
+ *   words in registers, a workgroup of 256 queries walks a segment of at most 2^22 database rows in tiles staged in LDS (every
+ *   lane reads the same address: a broadcast) and counts into u32 bins in LDS (at most 256 * 2^22 < 2^32 pairs per workgroup).
+ *   SVDD_E_ARG: B, N or L <= 0, L > 1024, a negative base, db_base + N or q_base + B >= 2^31, a NULL q or db, neither output.
+ */
+int svdd_kmer_counts(const uint8_t* x, int N, int L, int k, int64_t* counts, int64_t* skipped, void* on_stream);
+int svdd_pack_tokens(const uint8_t* x, int N, int L, uint32_t* packed, int32_t* err, void* on_stream);
+int svdd_hamming_nn(const uint32_t* q, const uint32_t* db, int B, int N, int L, int q_base, int db_base, int exclude_diag,
+                    uint64_t* nn_key, int64_t* hist, void* on_stream);
+
+/*
  * svdd_select — replaces torch.stack(scores,1) -> softmax(dim=1) -> argmax(dim=1) ->
  * per-row Python gather + stack                     diffusion_gosai.py:1219-1227 (= :1451-1459)
  *

@@ -131,6 +131,9 @@ SIGNATURES = {
     "svdd_attr_path": (vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp),
     "svdd_attr_fold": (vp, f32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp),
     "svdd_candidate_windows_tight": (vp, vp, i32, i32, i32, i32, vp, vp, vp),
+    "svdd_kmer_counts": (vp, i32, i32, i32, vp, vp, vp),
+    "svdd_pack_tokens": (vp, i32, i32, vp, vp, vp),
+    "svdd_hamming_nn": (vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp),
 }
 EXPORTS = tuple(SIGNATURES)
 

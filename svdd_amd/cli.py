@@ -56,6 +56,10 @@ def build_parser(method="mc"):
     p.add_argument("--eval_nll", type=int, default=0, metavar="K",
                    help="K > 0: also score the decoded and the baseline sequences by the pretrained model's ELBO (K draws per "
                         "sequence, nats): npz keys decoding_nll / baseline_nll")
+    p.add_argument("--eval_quality", default=argparse.SUPPRESS, metavar="FILE.npz",      # absent unless given: without it the namespace is unchanged
+                   help="also report the set-level quality of the decoded sequences (k-mer Pearson r, diversity, novelty, score "
+                        "Wasserstein distance) against the token arrays train / valid / test of FILE.npz (any subset): printed, and "
+                        "saved as npz keys quality_<metric>")
     p.add_argument("--presample", action="store_true",
                    help="pre-sample val_batch_num batches at construction like the reference's BaseModel.__init__")
     p.epilog = ("--method classfier evaluates the value net in eval mode for every task (the reference's decode_classfier.py leaves it in "
@@ -114,9 +118,17 @@ def run(args):
         extra = dict(decoding_nll=model.evaluate_nll(gen_samples, args.eval_nll).cpu().numpy(),
                      baseline_nll=model.evaluate_nll(model.baseline_samples, args.eval_nll).cpu().numpy())
         nll_note = f", nll decoding {extra['decoding_nll'].mean():.4f} baseline {extra['baseline_nll'].mean():.4f} nats"
+    report = None
+    if getattr(args, "eval_quality", None):
+        with np.load(args.eval_quality) as f:
+            sets = {name: f[name] for name in ("train", "valid", "test") if name in f.files}
+        report = model.evaluate_quality(gen_samples, refs=sets, train=sets.get("train"))
+        extra.update({f"quality_{key}": np.float64(v) for key, v in report.items()})
     np.savez(path, decoding=reward_model_preds.cpu().numpy(), baseline=baseline_preds.cpu().numpy(), **extra)
     print(f"wrote {path}.npz: decoding mean {reward_model_preds.mean().item():.4f} (n={reward_model_preds.numel()}), "
           f"baseline mean {baseline_preds.mean().item():.4f}{nll_note}")
+    if report is not None:
+        print("quality: " + ", ".join(f"{key} {v:.4f}" for key, v in report.items()))
     return path + ".npz", out
 
 

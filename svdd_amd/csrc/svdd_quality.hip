@@ -1,0 +1,222 @@
+// svdd_quality.hip — sample-quality metrics of a decoded batch AS A SET: k-mer spectra (reference oracle.count_kmers,
+// diffusion_gosai.py compare_kmer) and nearest-neighbour / pairwise Hamming distances on 2-bit-packed sequences (diversity and
+// novelty: not in the reference). Everything here is integer arithmetic with integer atomics: no result depends on the launch
+// shape or on how the caller cuts its rows into chunks.
+//
+//   svdd_kmer_counts   one workgroup takes a run of rows, counts their windows into a u32 histogram of 4^k bins in LDS and adds
+//                      the non-zero bins to the caller's i64 counts with 64-bit atomics
+//   svdd_pack_tokens   16 tokens per u32, one thread per word
+//   svdd_hamming_nn    a thread keeps ONE query's W words in registers; a workgroup of 256 queries walks a segment of the
+//                      database in tiles of HM_TILE rows staged in LDS. Every lane reads the same tile address (a broadcast: one
+//                      LDS cycle per lane group, no bank conflict), so a pair costs W xor / fold / popcount steps and, with hist,
+//                      one LDS atomic. The query's minimum is kept in registers (ascending rows, strictly smaller wins: the first
+//                      row of a tie) and meets the other segments' in one 64-bit atomic min per query on the key
+//                      (distance << 32 | database index).
+#include "svdd_host.h"
+
+namespace {
+
+constexpr int QB = 256;                     // threads per workgroup of all three kernels
+constexpr int KM_MAXK = 6;
+constexpr int KM_BINS = 1 << (2 * KM_MAXK); // 4096 bins, 16 KB
+constexpr int HM_TILE = 64;                 // database rows per LDS tile
+constexpr int HM_MAXL = 1024;               // 64 words per row: the register budget of a query
+
+struct KmerArgs {
+  const uint8_t* x;
+  int N, L, k, rows_per_wg;
+  unsigned long long* counts;
+  unsigned long long* skipped;
+};
+
+// Rows [wg * rows_per_wg, ...) of x: window (r, i) -> bin sum_j x[r, i + j] 4^(k - 1 - j); a window with a token > 3 counts as
+// skipped. rows_per_wg * (L - k + 1) < 2^32 (the host's bound), so no u32 bin wraps.
+__global__ __launch_bounds__(QB) void kmer_counts_kernel(KmerArgs a) {
+  __shared__ unsigned int h[KM_BINS];
+  __shared__ unsigned int skip;
+  const int nb = 1 << (2 * a.k);
+  for (int i = threadIdx.x; i < nb; i += QB) h[i] = 0;
+  if (threadIdx.x == 0) skip = 0;
+  __syncthreads();
+  const long long r0 = (long long)blockIdx.x * a.rows_per_wg;
+  const long long rows = min((long long)a.rows_per_wg, (long long)a.N - r0);
+  const int nw = a.L - a.k + 1;                                   // > 0: the host launches nothing otherwise
+  const long long total = rows * nw;
+  unsigned int my_skip = 0;
+  for (long long w = threadIdx.x; w < total; w += QB) {
+    const long long r = w / nw;
+    const int i = (int)(w - r * nw);
+    const uint8_t* p = a.x + (r0 + r) * a.L + i;
+    unsigned int bin = 0, bad = 0;
+    for (int j = 0; j < a.k; ++j) {
+      const unsigned int t = p[j];
+      bad |= t > 3u;
+      bin = (bin << 2) | (t & 3u);
+    }
+    if (bad) ++my_skip;
+    else atomicAdd(&h[bin], 1u);
+  }
+  if (my_skip) atomicAdd(&skip, my_skip);
+  __syncthreads();
+  for (int i = threadIdx.x; i < nb; i += QB)
+    if (h[i]) atomicAdd(&a.counts[i], (unsigned long long)h[i]);
+  if (threadIdx.x == 0 && a.skipped && skip) atomicAdd(a.skipped, (unsigned long long)skip);
+}
+
+struct PackArgs {
+  const uint8_t* x;
+  int N, L, W;
+  uint32_t* packed;
+  int32_t* err;
+};
+
+// one thread per packed word, grid-stride
+__global__ __launch_bounds__(QB) void pack_tokens_kernel(PackArgs a) {
+  const long long total = (long long)a.N * a.W;
+  bool bad = false;
+  for (long long i = (long long)blockIdx.x * QB + threadIdx.x; i < total; i += (long long)gridDim.x * QB) {
+    const long long r = i / a.W;
+    const int w = (int)(i - r * a.W);
+    const int l0 = 16 * w, n = min(16, a.L - l0);
+    const uint8_t* p = a.x + r * a.L + l0;
+    uint32_t v = 0;
+    for (int j = 0; j < n; ++j) {
+      const uint32_t t = p[j];
+      if (t > 3u) bad = true;
+      else v |= t << (2 * j);
+    }
+    a.packed[i] = v;
+  }
+  if (bad && a.err) a.err[0] = 1;
+}
+
+struct HammingArgs {
+  const uint32_t* q;
+  const uint32_t* db;
+  int B, N, L, W;
+  int q_base, db_base, exclude_diag, seg_rows;
+  uint32_t last_mask;                       // the valid bits of a row's last word (the padding is never trusted)
+  unsigned long long* nn_key;
+  unsigned long long* hist;
+};
+
+__device__ __forceinline__ int diff_positions(uint32_t v) {       // positions (bit pairs) at which v = a ^ b is non-zero
+  return __popc((v | (v >> 1)) & 0x55555555u);
+}
+
+// WT words of a row take part, WS is the row stride of the tile in LDS (a multiple of 4 where the row is read as uint4).
+template <int WT, int WS>
+__device__ __forceinline__ int row_distance(const uint32_t (&q)[WT], const uint32_t* row) {
+  int d = 0;
+  if constexpr (WS % 4 == 0) {
+#pragma unroll
+    for (int v = 0; v < WS / 4; ++v) {
+      const uint4 t = reinterpret_cast<const uint4*>(row)[v];
+      const uint32_t tt[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (4 * v + c < WT) d += diff_positions(q[4 * v + c] ^ tt[c]);
+    }
+  } else {
+#pragma unroll
+    for (int w = 0; w < WT; ++w) d += diff_positions(q[w] ^ row[w]);
+  }
+  return d;
+}
+
+// grid (ceil(B / QB), segments of seg_rows database rows). W <= WT; the words W .. WT - 1 are zero on both sides.
+// A workgroup's u32 bins hold at most QB * seg_rows < 2^32 pairs (the host keeps seg_rows <= 2^22).
+template <int WT, int WS>
+__global__ __launch_bounds__(QB) void hamming_nn_kernel(HammingArgs a) {
+  __shared__ __attribute__((aligned(16))) uint32_t tile[HM_TILE * WS];
+  __shared__ unsigned int h[HM_MAXL + 1];
+  const bool want_hist = a.hist != nullptr;
+  if (want_hist) {
+    for (int i = threadIdx.x; i <= a.L; i += QB) h[i] = 0;
+  }
+  const int qi = blockIdx.x * QB + threadIdx.x;
+  const bool live = qi < a.B;
+  uint32_t q[WT];
+#pragma unroll
+  for (int w = 0; w < WT; ++w) q[w] = live && w < a.W ? a.q[(long long)qi * a.W + w] & (w == a.W - 1 ? a.last_mask : 0xFFFFFFFFu) : 0u;
+  const int seg0 = (int)min((long long)blockIdx.y * a.seg_rows, (long long)a.N);
+  const int seg1 = (int)min((long long)seg0 + a.seg_rows, (long long)a.N);
+  // the database row this query must leave out: q_base + qi == db_base + j  <=>  j = q_base + qi - db_base
+  const long long diag = a.exclude_diag ? (long long)a.q_base + qi - a.db_base : -1;
+  unsigned int best_d = 0xFFFFFFFFu;
+  int best_j = 0;
+  for (int t0 = seg0; t0 < seg1; t0 += HM_TILE) {
+    const int nr = min(HM_TILE, seg1 - t0);
+    __syncthreads();                                            // the previous tile is read (and h is zeroed)
+    for (int i = threadIdx.x; i < nr * WS; i += QB) {
+      const int r = i / WS, w = i - r * WS;
+      tile[i] = w < a.W ? a.db[(long long)(t0 + r) * a.W + w] & (w == a.W - 1 ? a.last_mask : 0xFFFFFFFFu) : 0u;
+    }
+    __syncthreads();
+    if (live) {
+#pragma unroll 2
+      for (int r = 0; r < nr; ++r) {
+        const int d = row_distance<WT, WS>(q, &tile[r * WS]);
+        if ((long long)(t0 + r) != diag) {
+          if (want_hist) atomicAdd(&h[d], 1u);
+          if ((unsigned int)d < best_d) { best_d = (unsigned int)d; best_j = t0 + r; }
+        }
+      }
+    }
+  }
+  if (live && a.nn_key && best_d != 0xFFFFFFFFu)
+    atomicMin(&a.nn_key[qi], ((unsigned long long)best_d << 32) | (unsigned long long)(uint32_t)(a.db_base + best_j));
+  if (want_hist) {
+    __syncthreads();
+    for (int i = threadIdx.x; i <= a.L; i += QB)
+      if (h[i]) atomicAdd(&a.hist[i], (unsigned long long)h[i]);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int svdd_kmer_counts(const uint8_t* x, int N, int L, int k, int64_t* counts, int64_t* skipped, void* on_stream) {
+  if (!x || !counts || N <= 0 || L <= 0 || k < 1 || k > KM_MAXK) return SVDD_E_ARG;
+  if (k > L) return SVDD_OK;                                      // no windows: nothing is written
+  // rows per workgroup: enough workgroups to fill the chip, few enough rows that rows * windows stays below 2^32
+  const long long nw = L - k + 1;
+  long long rows = ((long long)N + 2047) / 2048;
+  const long long cap = 0xFFFFFFFFll / nw;                         // >= 1: nw < 2^31
+  if (rows > cap) rows = cap;
+  const long long wgs = ((long long)N + rows - 1) / rows;
+  const KmerArgs a{x, N, L, k, (int)rows, (unsigned long long*)counts, (unsigned long long*)skipped};
+  return svdd_launch(kmer_counts_kernel, dim3((unsigned)wgs), dim3(QB), 0, on_stream, a);
+}
+
+int svdd_pack_tokens(const uint8_t* x, int N, int L, uint32_t* packed, int32_t* err, void* on_stream) {
+  if (!x || !packed || N <= 0 || L <= 0 || L > HM_MAXL) return SVDD_E_ARG;
+  const int W = (L + 15) / 16;
+  const long long blocks = ((long long)N * W + QB - 1) / QB;
+  const PackArgs a{x, N, L, W, packed, err};
+  return svdd_launch(pack_tokens_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(QB), 0, on_stream, a);
+}
+
+int svdd_hamming_nn(const uint32_t* q, const uint32_t* db, int B, int N, int L, int q_base, int db_base, int exclude_diag,
+                    uint64_t* nn_key, int64_t* hist, void* on_stream) {
+  if (!q || !db || (!nn_key && !hist) || B <= 0 || N <= 0 || L <= 0 || L > HM_MAXL || q_base < 0 || db_base < 0) return SVDD_E_ARG;
+  if ((long long)db_base + N >= (long long)1 << 31 || (long long)q_base + B >= (long long)1 << 31) return SVDD_E_ARG;
+  const int W = (L + 15) / 16;
+  const unsigned gx = (unsigned)((B + QB - 1) / QB);
+  // segments: about 1024 workgroups in all, whole tiles, at most 2^22 rows (QB * 2^22 pairs < 2^32 in a workgroup's u32 bins)
+  const long long want = (1024 + gx - 1) / gx;
+  long long seg = ((long long)N + want - 1) / want;
+  seg = (seg + HM_TILE - 1) / HM_TILE * HM_TILE;
+  if (seg > (1 << 22)) seg = 1 << 22;
+  const unsigned gy = (unsigned)(((long long)N + seg - 1) / seg);
+  const uint32_t last_mask = L % 16 ? (1u << (2 * (L % 16))) - 1u : 0xFFFFFFFFu;
+  const HammingArgs a{q, db, B, N, L, W, q_base, db_base, exclude_diag, (int)seg, last_mask, (unsigned long long*)nn_key,
+                      (unsigned long long*)hist};
+  void (*k)(HammingArgs) = W <= 1 ? hamming_nn_kernel<1, 1> : W <= 2 ? hamming_nn_kernel<2, 2> : W <= 4 ? hamming_nn_kernel<4, 4>
+                         : W <= 8 ? hamming_nn_kernel<8, 8> : W <= 13 ? hamming_nn_kernel<13, 16> : W <= 16 ? hamming_nn_kernel<16, 16>
+                         : W <= 32 ? hamming_nn_kernel<32, 32> : hamming_nn_kernel<64, 64>;
+  return svdd_launch(k, dim3(gx, gy), dim3(QB), 0, on_stream, a);
+}
+
+}  // extern "C"

@@ -10,7 +10,7 @@ The reference's `BaseModel.__init__` hard-wires checkpoint paths, Hydra and `.cu
 `gen_batch_num * sample_M` un-guided baseline batches, then the top-k) and return the same
 5-tuple: (samples list, value_func_preds [N], reward_model_preds [N], top_k_values, baseline_preds [N]).
 The tokens of the baseline batches behind baseline_preds are kept in `baseline_samples`; `evaluate_nll` scores any of them
-under the pretrained model (Diffusion.sequence_nll).
+under the pretrained model (Diffusion.sequence_nll); `evaluate_quality` reports set-level metrics of them (svdd_amd.quality).
 """
 import torch
 from torch import nn
@@ -264,3 +264,24 @@ class BaseModel(nn.Module):
         if isinstance(samples, (list, tuple)):
             samples = torch.cat([s.reshape(-1, s.shape[-1]).to(m.device) for s in samples])
         return m.sequence_nll(samples.to(m.device), n_draws=n_draws)
+
+    @torch.no_grad()
+    def evaluate_quality(self, samples, refs=None, train=None, k=3):
+        """Set-level quality of decoded designs (svdd_amd.quality.sample_quality; the reference's on_validation_epoch_end numbers
+        plus diversity and novelty) -> a flat dict. `samples` as in evaluate_nll; refs {name: tokens [N', L'] or k-mer counts
+        [4^k]}: kmer_pearsonr_<name>, and for the token sets ws_scores_<name>, the 1-D Wasserstein distance between the harness's
+        reward predictions on the designs and on that set; train [N, L]: the novelty keys."""
+        from . import quality
+        dev = self.ref_model.device
+        if isinstance(samples, (list, tuple)):
+            samples = torch.cat([torch.as_tensor(s).reshape(-1, s.shape[-1]).to(dev) for s in samples])
+        samples = torch.as_tensor(samples).to(dev)
+        n = self.NUM_SAMPLES_PER_BATCH
+
+        def reward(t):
+            t = torch.as_tensor(t).to(dev).long()
+            pred = torch.cat([self._reward(t[i:i + n]) for i in range(0, t.shape[0], n)])
+            return pred if self.n_tasks == 1 else pred[:, 0]
+        token_refs = {name: r for name, r in (refs or {}).items() if getattr(r, "ndim", 0) == 2}
+        return quality.sample_quality(samples, refs=refs, train=train, k=k, scores=reward(samples),
+                                      ref_scores={name: reward(r) for name, r in token_refs.items()})

@@ -432,6 +432,93 @@ def attr_fold(grad, scale, weight, x, r0, n_rows, acc, attr, mode="times_input",
               ATTR_MODE[mode], acc, attr, rowsum, _this_stream())
 
 
+KMER_MAX_K, PACK_MAX_L = 6, 1024                                          # svdd_kmer_counts / svdd_pack_tokens (include/svdd_hip.h)
+NN_KEY_INIT = -1                                                         # all ones: the value svdd_hamming_nn's nn_key starts from
+
+
+def _tokens2d(x, name="x"):
+    x = _need(x, torch.uint8, name)
+    if x.dim() != 2 or not x.is_contiguous() or x.numel() == 0:
+        raise SvddError(f"{name} must be a contiguous non-empty u8 [N, L] tensor, got {tuple(x.shape)}")
+    return x
+
+
+def kmer_counts(x, k, counts, skipped=None):
+    """svdd_kmer_counts: ADD the k-mer counts of x u8 [N, L] to counts i64 [4^k] (bin = the lexicographic rank of the ACGT string)
+    and the number of windows that hold a token > 3 to skipped i64 [1] (or None). Both are the caller's and start from what they
+    hold. k > L: no windows, nothing written."""
+    if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= KMER_MAX_K:
+        raise ValueError(f"k = {k!r}: expected an int in 1 .. {KMER_MAX_K}")
+    x = _tokens2d(x)
+    _is(counts, torch.int64, (4 ** k,), "counts")
+    if skipped is not None:
+        _is(skipped, torch.int64, (1,), "skipped")
+    _lib.call("svdd_kmer_counts", x, x.shape[0], x.shape[1], k, counts, skipped, _this_stream())
+    return counts, skipped
+
+
+def packed_words(L):
+    return (int(L) + 15) // 16
+
+
+def pack_tokens(x, packed=None, err=None):
+    """svdd_pack_tokens: x u8 [N, L] (tokens 0..3, L <= 1024) -> packed int32 [N, ceil(L / 16)] (the bits of the u32 words: position
+    l in word l // 16 at bits 2 (l % 16); padding bits zero). err: a caller-zeroed device int32 [1] the kernel sets for a token > 3
+    (checked by the caller later with check_pack_err); None: checked here (one synchronisation)."""
+    x = _tokens2d(x)
+    N, L = x.shape
+    if L > PACK_MAX_L:
+        raise SvddError(f"pack_tokens: L = {L} > {PACK_MAX_L}")
+    W = packed_words(L)
+    packed = torch.empty((N, W), dtype=torch.int32, device=x.device) if packed is None else _is(packed, torch.int32, (N, W), "packed")
+    check_here = err is None
+    if check_here:
+        err = torch.zeros(1, dtype=torch.int32, device=x.device)
+    else:
+        _is(err, torch.int32, (1,), "err")
+    _lib.call("svdd_pack_tokens", x, N, L, packed, err, _this_stream())
+    if check_here:
+        check_pack_err(err)
+    return packed
+
+
+def check_pack_err(err):
+    """Raise if svdd_pack_tokens flagged a token > 3 (SVDD_E_ARG)."""
+    if int(err[0]) != 0:
+        _lib.check(_lib.E_ARG, "svdd_pack_tokens: a row holds a token > 3 (MASK included)")
+
+
+def hamming_nn(q, db, L, nn_key=None, hist=None, q_base=0, db_base=0, exclude_diag=False):
+    """svdd_hamming_nn on packed rows (pack_tokens): q int32 [B, W], db int32 [N, W], W = ceil(L / 16). nn_key i64 [B] (or None),
+    started by the caller at NN_KEY_INIT, is lowered to (distance << 32) | (db_base + j) of the nearest database row (the lowest
+    index among ties); hist i64 [L + 1] (or None) is ADDED the number of pairs at each distance. exclude_diag: the pairs with
+    q_base + i == db_base + j are left out. Decode a key with nn_decode."""
+    W = packed_words(L)
+    if not 1 <= int(L) <= PACK_MAX_L:
+        raise SvddError(f"hamming_nn: L = {L} outside 1 .. {PACK_MAX_L}")
+    _need(q, torch.int32, "q"), _need(db, torch.int32, "db")
+    if q.dim() != 2 or db.dim() != 2 or q.shape[1] != W or db.shape[1] != W or not q.is_contiguous() or not db.is_contiguous() \
+            or q.shape[0] == 0 or db.shape[0] == 0:
+        raise SvddError(f"hamming_nn: q and db must be contiguous non-empty int32 [*, {W}] tensors, got {tuple(q.shape)} and {tuple(db.shape)}")
+    B, N = q.shape[0], db.shape[0]
+    if nn_key is None and hist is None:
+        raise SvddError("hamming_nn: give nn_key, hist or both")
+    if nn_key is not None:
+        _is(nn_key, torch.int64, (B,), "nn_key")
+    if hist is not None:
+        _is(hist, torch.int64, (int(L) + 1,), "hist")
+    _lib.call("svdd_hamming_nn", q, db, B, N, int(L), int(q_base), int(db_base), int(bool(exclude_diag)), nn_key, hist, _this_stream())
+    return nn_key, hist
+
+
+def nn_decode(nn_key):
+    """nn_key i64 [B] of hamming_nn -> (dist i32 [B], idx i64 [B]); a key nobody lowered (no pair) gives (-1, -1)."""
+    none = nn_key == NN_KEY_INIT
+    dist = torch.where(none, torch.full_like(nn_key, -1), nn_key >> 32).to(torch.int32)
+    idx = torch.where(none, torch.full_like(nn_key, -1), nn_key & 0xFFFFFFFF)
+    return dist, idx
+
+
 def select(scores, cand, mode=SELECT_ARGMAX, rng=None, want_soft=True, x_next=None):
     """-> (x_next u8 [B,L], soft f32 [B,M] | None, idx i32 [B])."""
     cand = _need(cand, torch.uint8, "cand").contiguous()

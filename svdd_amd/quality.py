@@ -1,0 +1,243 @@
+"""Quality of a decoded batch AS A SET: what the reference reports after every sampling run
+(diffusion_gosai.py on_validation_epoch_end: cal_kmer_pearsonr, cal_wasserstein_distance, oracle.get_wasserstein_dist) plus the two
+standard companions of a reward table that it does not have, diversity and novelty.
+
+  kmer_counts / kmer_pearsonr      k-mer spectrum on the device (svdd_kmer_counts), Pearson r by the reference's compare_kmer rule
+  pack_tokens / hamming_nn / pairwise_hamming_hist
+                                    Hamming distances on 2-bit-packed rows (svdd_pack_tokens, svdd_hamming_nn): exact integers,
+                                    independent of every chunking
+  wasserstein_1d / frechet_distance host-level float64 (torch), no kernel
+  sample_quality                    the flat report
+
+Token inputs are [N, L] integer tensors (any integer dtype; a CPU tensor or a numpy array is checked on the host and moved to the
+GPU). The kernels have no CPU fallback."""
+import math
+
+import numpy as np
+import torch
+
+from . import ops
+from .ops import SvddError
+
+HAMMING_CHUNK_ROWS = 1 << 20             # database rows per svdd_hamming_nn call (any value gives the same result)
+KMER_CHUNK_ROWS = 1 << 22
+
+
+def _checked(x, name, max_token):
+    """Shape and dtype of a token set, and for host data its values (device data: the kernels flag them) -> an integer tensor."""
+    if isinstance(x, np.ndarray):
+        if x.dtype.kind not in "iu":
+            raise ValueError(f"{name} must hold integer tokens, got {x.dtype}")
+        x = torch.from_numpy(np.ascontiguousarray(x).astype(np.int64, copy=False))
+    if not isinstance(x, torch.Tensor) or x.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+        raise ValueError(f"{name} must be an integer tensor of tokens, got {getattr(x, 'dtype', type(x))}")
+    if x.dim() != 2 or x.numel() == 0:
+        raise ValueError(f"{name} must be a non-empty [N, L] tensor, got {tuple(x.shape)}")
+    if not x.is_cuda and (int(x.min()) < 0 or int(x.max()) > max_token):
+        raise ValueError(f"{name} holds a token outside 0 .. {max_token}")
+    return x
+
+
+def _on_device(x, name):
+    """A checked token set -> u8 [N, L] contiguous on the GPU."""
+    if not x.is_cuda:
+        if not torch.cuda.is_available():
+            raise SvddError(f"{name}: the quality kernels run on the GPU (the SVDD hot path has no CPU fallback)")
+        x = x.to(torch.uint8).cuda()
+    elif x.dtype != torch.uint8:
+        x = torch.where((x < 0) | (x > 255), torch.full_like(x, 255), x).to(torch.uint8)     # out of range stays out of range
+    return x.contiguous()
+
+
+def _tokens(x, name, max_token):
+    return _on_device(_checked(x, name, max_token), name)
+
+
+def _chunk_rows(chunk_rows, default):
+    if chunk_rows is None:
+        return default
+    if not isinstance(chunk_rows, int) or isinstance(chunk_rows, bool) or chunk_rows <= 0:
+        raise ValueError(f"chunk_rows = {chunk_rows!r}: expected a positive int or None")
+    return chunk_rows
+
+
+def _check_k(k):
+    if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= ops.KMER_MAX_K:
+        raise ValueError(f"k = {k!r}: expected an int in 1 .. {ops.KMER_MAX_K}")
+
+
+# ----------------------------------------------------------------------------------------------------- k-mer spectra ----
+def kmer_counts(x, k=3, chunk_rows=None):
+    """-> (counts i64 [4^k] on the device, skipped int). Bin = the lexicographic rank of the k-mer's ACGT string (reference
+    oracle.count_kmers' dictionary as a vector); a window that holds a token > 3 (MASK) is not counted but counted in skipped.
+    chunk_rows: rows per launch (the counts are integers: every chunking gives the same result)."""
+    _check_k(k)
+    rows = _chunk_rows(chunk_rows, KMER_CHUNK_ROWS)
+    x = _tokens(x, "x", 255)
+    counts = torch.zeros(4 ** k, dtype=torch.int64, device=x.device)
+    skipped = torch.zeros(1, dtype=torch.int64, device=x.device)
+    for r0 in range(0, x.shape[0], rows):
+        ops.kmer_counts(x[r0:r0 + rows], k, counts, skipped)
+    return counts, int(skipped[0])
+
+
+def _pearson_union(c1, c2):
+    """Pearson r of two count vectors over the bins that are non-zero in either (float64 on the host); NaN when fewer than two
+    bins are left or a side has no variance."""
+    keep = (c1 != 0) | (c2 != 0)
+    a, b = c1[keep].double(), c2[keep].double()
+    if a.numel() < 2:
+        return float("nan")
+    a, b = a - a.mean(), b - b.mean()
+    den = math.sqrt(float((a * a).sum()) * float((b * b).sum()))
+    return float((a * b).sum()) / den if den > 0 else float("nan")
+
+
+def _ref_counts(ref, k, name="ref"):
+    """ref: tokens [N', L'] or a ready count vector [4^k] -> i64 [4^k] on the host."""
+    if isinstance(ref, np.ndarray):
+        ref = torch.from_numpy(np.ascontiguousarray(ref))
+    if isinstance(ref, torch.Tensor) and ref.dim() == 1:
+        if ref.numel() != 4 ** k or ref.dtype.is_floating_point and bool((ref != ref.round()).any()):
+            raise ValueError(f"{name}: a count vector must hold 4^k = {4 ** k} integers, got {tuple(ref.shape)} {ref.dtype}")
+        return ref.detach().cpu().to(torch.int64)
+    return kmer_counts(ref, k)[0].cpu()
+
+
+def kmer_pearsonr(x, ref, k=3):
+    """Pearson correlation of the k-mer spectra of x and ref (tokens [N', L'] or a count vector [4^k]) by the reference's
+    Diffusion.compare_kmer rule: over the union of the k-mers present in either set; a bin that is zero in both is left out.
+    The reference scales one side by n2 / n1 first: a positive factor, which does not change r, so it is skipped.
+    Float64 on the host from the exact counts. < 2 bins in the union or zero variance on a side: NaN."""
+    _check_k(k)
+    return _pearson_union(kmer_counts(x, k)[0].cpu(), _ref_counts(ref, k))
+
+
+# ------------------------------------------------------------------------------------------------- Hamming distances ----
+def pack_tokens(x):
+    """x [N, L] tokens 0..3, L <= 1024 -> int32 [N, ceil(L / 16)]: 2 bits per token, 16 per word. Raises on a token > 3."""
+    x = _checked(x, "x", 3)
+    if x.shape[1] > ops.PACK_MAX_L:
+        raise ValueError(f"L = {x.shape[1]} > {ops.PACK_MAX_L}")
+    return ops.pack_tokens(_on_device(x, "x"))
+
+
+def _pair(x, db):
+    x = _checked(x, "x", 3)
+    xd = None if db is None else _checked(db, "db", 3)
+    if xd is not None and xd.shape[1] != x.shape[1]:
+        raise ValueError(f"x and db must have one length, got {x.shape[1]} and {xd.shape[1]}")
+    if x.shape[1] > ops.PACK_MAX_L:
+        raise ValueError(f"L = {x.shape[1]} > {ops.PACK_MAX_L}")
+    return _on_device(x, "x"), None if xd is None else _on_device(xd, "db")
+
+
+def _hamming(x, db, chunk_rows, want_key, want_hist):
+    """-> (nn_key i64 [B] | None, hist i64 [L + 1] | None) of x against db (None: x against itself without the diagonal)."""
+    rows = _chunk_rows(chunk_rows, HAMMING_CHUNK_ROWS)
+    x, xd = _pair(x, db)
+    B, L = x.shape
+    err = torch.zeros(1, dtype=torch.int32, device=x.device)
+    q = ops.pack_tokens(x, err=err)
+    key = torch.full((B,), ops.NN_KEY_INIT, dtype=torch.int64, device=x.device) if want_key else None
+    hist = torch.zeros(L + 1, dtype=torch.int64, device=x.device) if want_hist else None
+    src = x if xd is None else xd
+    for r0 in range(0, src.shape[0], rows):
+        d = q[r0:r0 + rows] if xd is None else ops.pack_tokens(xd[r0:r0 + rows], err=err)
+        ops.hamming_nn(q, d, L, key, hist, db_base=r0, exclude_diag=xd is None)
+    ops.check_pack_err(err)
+    return key, hist
+
+
+def hamming_nn(x, db=None, chunk_rows=None):
+    """Nearest neighbour of every row of x in db by Hamming distance -> (dist i32 [B], idx i64 [B]); among equally near rows the
+    lowest index. db None: x against itself with the diagonal excluded (a one-row set gives (-1, -1)). chunk_rows: database rows
+    per launch (every value gives the same result)."""
+    return ops.nn_decode(_hamming(x, db, chunk_rows, True, False)[0])
+
+
+def pairwise_hamming_hist(x, db=None):
+    """i64 [L + 1]: the number of pairs (row of x, row of db) at each Hamming distance; db None: the ordered pairs i != j of x."""
+    return _hamming(x, db, None, False, True)[1]
+
+
+# ------------------------------------------------------------------------------------------ host-level float64 rules ----
+def _f64(a):
+    if isinstance(a, np.ndarray):
+        a = torch.from_numpy(np.ascontiguousarray(a))
+    if not isinstance(a, torch.Tensor):
+        a = torch.as_tensor(a)
+    return a.detach().to(torch.float64).cpu()                    # host-level: these samples are small
+
+
+def wasserstein_1d(a, b):
+    """The 1-D Wasserstein-1 distance of two samples (any sizes): the integral of |F_a - F_b| over the merged support, float64;
+    the quantity scipy.stats.wasserstein_distance returns (reference cal_wasserstein_distance). An empty side gives NaN."""
+    a, b = _f64(a).reshape(-1), _f64(b).reshape(-1)
+    if a.numel() == 0 or b.numel() == 0:
+        return float("nan")
+    a, b = a.sort().values, b.sort().values
+    allv = torch.cat([a, b]).sort().values
+    fa = torch.searchsorted(a, allv[:-1], right=True).double() / a.numel()
+    fb = torch.searchsorted(b, allv[:-1], right=True).double() / b.numel()
+    return float(((fa - fb).abs() * (allv[1:] - allv[:-1])).sum())
+
+
+def _cov(e):
+    return torch.atleast_2d(torch.cov(e.T))
+
+
+def frechet_distance(e1, e2):
+    """|mu1 - mu2|^2 + tr(S1 + S2 - 2 (S1 S2)^(1/2)) of two embedding sets [n, D] in float64 (reference oracle.get_wasserstein_dist).
+    tr (S1 S2)^(1/2) = the sum of the square roots of the eigenvalues of S1 S2 (real parts, negatives clamped at 0). NaN or empty
+    input returns NaN, as the reference does."""
+    e1, e2 = _f64(e1), _f64(e2)
+    if e1.numel() == 0 or e2.numel() == 0 or bool(torch.isnan(e1).any()) or bool(torch.isnan(e2).any()):
+        return float("nan")
+    if e1.dim() != 2 or e2.dim() != 2 or e1.shape[1] != e2.shape[1]:
+        raise ValueError(f"embeddings must be [n, D] with one D, got {tuple(e1.shape)} and {tuple(e2.shape)}")
+    s1, s2 = _cov(e1), _cov(e2)
+    ev = torch.linalg.eigvals(s1 @ s2).real.clamp(min=0.0)
+    return float(((e1.mean(0) - e2.mean(0)) ** 2).sum() + torch.trace(s1) + torch.trace(s2) - 2.0 * ev.sqrt().sum())
+
+
+def _median(v):
+    return float(torch.quantile(v.double(), 0.5)) if v.numel() else float("nan")
+
+
+# -------------------------------------------------------------------------------------------------------- the report ----
+def sample_quality(x, refs=None, train=None, k=3, scores=None, ref_scores=None):
+    """A flat dict of set-level metrics of the designs x [B, L] (tokens 0..3):
+      kmer_pearsonr_<name>   for every set of refs {name: tokens [N', L'] or counts [4^k]}
+      diversity_mean         mean Hamming distance over the pairs i != j of the batch (NaN for one row)
+      diversity_nn_median    median distance of a row to its nearest OTHER row
+      unique_fraction        distinct rows / rows: the rows whose nearest other row is at distance > 0, plus one representative
+                             (the lowest index) of every group of duplicates
+      novelty_nn_median / novelty_nn_min / memorised_fraction   with train [N, L]: the distance to the nearest training row, and
+                             the share of designs that ARE a training row (distance 0)
+      ws_scores_<name>       with scores [B] and ref_scores {name: [n]}: the 1-D Wasserstein distance of the two score samples
+    Diversity and novelty are not in the reference."""
+    _check_k(k)
+    x = _tokens(x, "x", 3)
+    B, L = x.shape
+    out = {}
+    if refs:
+        cx = kmer_counts(x, k)[0].cpu()
+        for name, ref in refs.items():
+            out[f"kmer_pearsonr_{name}"] = _pearson_union(cx, _ref_counts(ref, k, name))
+    key, hist = _hamming(x, None, None, True, True)
+    dist, idx = ops.nn_decode(key)
+    hist = hist.cpu()
+    pairs = int(hist.sum())
+    out["diversity_mean"] = float((hist * torch.arange(L + 1)).sum()) / pairs if pairs else float("nan")
+    out["diversity_nn_median"] = _median(dist) if B > 1 else float("nan")
+    first = torch.arange(B, device=x.device)
+    out["unique_fraction"] = int(((dist != 0) | (idx > first)).sum()) / B
+    if train is not None:
+        dist, _ = hamming_nn(x, train)
+        out["novelty_nn_median"], out["novelty_nn_min"] = _median(dist), int(dist.min())
+        out["memorised_fraction"] = int((dist == 0).sum()) / B
+    if scores is not None and ref_scores is not None:
+        for name, rs in ref_scores.items():
+            out[f"ws_scores_{name}"] = wasserstein_1d(scores, rs)
+    return out
