@@ -593,6 +593,34 @@ int svdd_conv_tower_windows_f32(const float* onehot, const float* tiles, const f
 int svdd_candidate_windows_tight(const uint8_t* cand, const uint8_t* x, int B, int L, int M, int margin, int32_t* win,
                                  int32_t* flags, void* on_stream);
 
+/* svdd_candidate_parts + svdd_conv_tower_parts_f32 — the windowed fp32 tower with PER-LAYER row ranges and separate parts for
+ *   changes far apart: the same output as svdd_candidate_windows_tight + svdd_conv_tower_windows_f32, bit for bit
+ *   (tests/test_tower_parts_gpu.py), on fewer row tiles. Layer k of the tower (0 = stem, 5 = last block) has to be right only on
+ *   the changed positions +- (reach + 2 (5 - k)) rows, reach = 17 for this tower: 55, 51, ... 35 rows for one changed position,
+ *   20 tile-layers where the one window takes 24 — and nothing between two neighbourhoods that are far apart.
+ *   svdd_candidate_parts: the positions where a candidate differs from its parent, ascending, are cut into parts wherever two
+ *     consecutive ones are >= gap apart; at most 3 parts, later ones are merged into the third. parts [B*M][3][2] = (first, last)
+ *     changed position of each part, (-1, -1) where there is none; nparts [B*M] (may be NULL) their number; flags [B*M] (may be
+ *     NULL) the candidate's tile-layers = sum over parts and the six layers of ceil(rows of [max(0, first - h), min(L, last + h + 1)) / 16),
+ *     h = reach + 2 (5 - k); 0 for an exact copy. key [B*M] (may be NULL) = ceil(flags / 6), the average tiles per layer, 0 .. 13:
+ *     what the compactions take in place of the window entries' flags (svdd_compact_flags: > 0 = live; svdd_compact_by_key tells only
+ *     15 keys apart and tile-layers reach 78, so flags itself would lose the order) — fused.py hands its flags workspace to `key`.
+ *     gap >= 2 (reach + 10) + 16 (70 for this tower), so that two parts' computed tiles never touch on any layer, each range being
+ *     rounded up to whole tiles from its own first row; a gap above L gives one part always (per-layer ranges alone).
+ *     SVDD_E_ARG: a NULL cand, x or parts; B, L or M <= 0; reach < 0 or > 2^20; a smaller gap; B * M > 2^31 - 4.
+ *   svdd_conv_tower_parts_f32: svdd_conv_tower_windows_f32 with parts in place of win (same onehot, parent_out, out, live_idx,
+ *     count and profile slot; one workgroup per listed candidate): every layer runs on the tiles that cover its range of every
+ *     part, the rows [max(0, first - reach), min(L, last + reach + 1)) of each part come from this computation, all others are
+ *     copied from the parent's output. 104 < L <= 208, nlayers = 5, reach = 17 (anything else: SVDD_E_ARG) — and the parts must have
+ *     been cut by svdd_candidate_parts with that reach: its gap rule is what keeps two parts' tiles apart. One kernel generation
+ *     (svdd_set_tower_version does not apply).
+ *   Both take their stream as the explicit last argument. */
+int svdd_candidate_parts(const uint8_t* cand, const uint8_t* x, int B, int L, int M, int reach, int gap, int32_t* parts,
+                         int32_t* nparts, int32_t* flags, int32_t* key, void* on_stream);
+int svdd_conv_tower_parts_f32(const float* onehot, const float* tiles, const float* bias, const int32_t* parts,
+                              const float* parent_out, float* out, int n, int L, int M, int nlayers, int residual_mask,
+                              int reach, const int32_t* live_idx, const int32_t* count, void* on_stream);
+
 /* svdd_backbone_cnn_f32 — the whole dilated-CNN masked-diffusion backbone at sigma = 0 in ONE launch
  *   (reference models/dnaconv.py:176-210 as called from diffusion_gosai.py:334-340): one-hot + 9-tap first conv,
  *   nlayers x [LayerNorm(f + tb_i) -> dilated 9-tap conv 128->128 -> ReLU -> + f], then the two 1x1 convs of

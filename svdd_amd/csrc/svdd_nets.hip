@@ -1367,6 +1367,266 @@ __global__ __launch_bounds__(256) void candidate_windows_kernel(const uint8_t* _
   }
 }
 
+// ------------------------------------------------ conv tower on candidate PARTS (per-layer row ranges, far changes apart) ----
+// The tight window computes all six layers on one range [lo - 27, hi + 28). Two things in it nobody reads:
+//   * only the stem needs +-27. Read from the output side, block 5 must be right on [lo - 17, hi + 18) (the rows that can differ
+//     from the parent's), block 4 on two rows more per side, ... : layer k (0 = stem, 5 = last block) on +- (R + 2 (5 - k)), R = 17;
+//   * changed positions far apart need no rows between them: the changed positions, ascending, are cut into PARTS wherever two
+//     consecutive ones are >= G apart (at most TP_PARTS; further ones are merged into the last).
+// Per part [a, b] and layer k the needed range is [max(0, a - R - 2 (5 - k)), min(L, b + R + 1 + 2 (5 - k))); the layer computes the
+// 16-row tiles that cover it, counted from the range's own first row. Rows of a computed tile past the needed range hold GARBAGE
+// (their inputs were outside the previous layer's needed range): the next layer's needed range is two rows shorter at each end
+// and never reads them, and a row's result depends on no other row of its tile (one MFMA column). G >= 2 (R + 10) + 16 keeps two
+// parts' computed tiles disjoint on every layer. A kept row is the same chain of MFMAs on the same inputs as in the whole-sequence
+// kernel, whichever tile and lane it sits in: same bits (tests/test_tower_parts_gpu.py).
+constexpr int TP_PARTS = 3;        // parts per candidate
+constexpr int TP_BLOCKS = 5;       // conv blocks after the stem: the tower the part rule is written for
+constexpr int TP_REACH = 17;       // receptive field of that tower, rows per side: the reach svdd_conv_tower_parts_f32 takes
+constexpr int TP_LT = 16;          // stride of a layer's tile-origin list in LDS: <= TW_RT origins, [TP_LT - 1] = their number
+
+// tile-layers of one part: sum over the six layers of the 16-row tiles covering the layer's needed range
+__device__ __forceinline__ int tower_part_tile_layers(int a, int b, int L, int R) {
+  int t = 0;
+#pragma unroll
+  for (int k = 0; k <= TP_BLOCKS; ++k) {
+    const int h = R + 2 * (TP_BLOCKS - k);
+    t += (min(L, b + h + 1) - max(0, a - h) + 15) >> 4;
+  }
+  return t;
+}
+
+// parts [n][3][2] = (first, last) changed position of each part, (-1, -1) where there is none; nparts [n]; flags [n] = tile-layers
+// of the candidate (0: a copy of its parent); key [n] = ceil(flags / 6), 1 .. TW_RT: the average tiles per layer, a sort key within
+// svdd_compact_by_key's 15 bins. One wave per candidate; the cut runs on wave-uniform values (a ballot per 64 positions).
+__global__ __launch_bounds__(256) void candidate_parts_kernel(const uint8_t* __restrict__ cand, const uint8_t* __restrict__ x, int n, int L,
+                                                             int M, int R, int G, int* __restrict__ parts, int* __restrict__ nparts,
+                                                             int* __restrict__ flags, int* __restrict__ key) {
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (c >= n) return;
+  const int lane = threadIdx.x & 63;
+  const uint8_t* cp = cand + (size_t)c * L;
+  const uint8_t* xp = x + (size_t)(c / M) * L;
+  int np = 0, prev = 0;
+  int a0 = -1, a1 = -1, a2 = -1, b0 = -1, b1 = -1, b2 = -1;
+  for (int l0 = 0; l0 < L; l0 += 64) {
+    const int l = l0 + lane;
+    unsigned long long m = __ballot(l < L && cp[l] != xp[l]);
+    while (m) {
+      const int p = l0 + __builtin_ctzll(m);
+      m &= m - 1;
+      if (np == 0 || (np < TP_PARTS && p - prev >= G)) {
+        if (np == 0) a0 = p; else if (np == 1) a1 = p; else a2 = p;
+        ++np;
+      }
+      if (np == 1) b0 = p; else if (np == 2) b1 = p; else b2 = p;
+      prev = p;
+    }
+  }
+  if (lane == 0) {
+    int* pp = parts + (size_t)c * (2 * TP_PARTS);
+    pp[0] = a0; pp[1] = b0; pp[2] = a1; pp[3] = b1; pp[4] = a2; pp[5] = b2;
+    int t = 0;
+    if (np > 0) t += tower_part_tile_layers(a0, b0, L, R);
+    if (np > 1) t += tower_part_tile_layers(a1, b1, L, R);
+    if (np > 2) t += tower_part_tile_layers(a2, b2, L, R);
+    if (nparts) nparts[c] = np;
+    if (flags) flags[c] = t;
+    if (key) key[c] = (t + TP_BLOCKS) / (TP_BLOCKS + 1);
+  }
+}
+
+struct TowerPartArgs {
+  TowerArgs t;             // x = candidates' one-hot [n, L, 4], out [n, L, 64]
+  const int* parts;        // [n][TP_PARTS][2] (first, last) changed position ; first < 0: no such part
+  const float* parent_out; // [n / M, L, 64]
+  int M, reach;
+  const int* live_idx;     // [count] candidate ids to process (NULL: identity); workgroup i writes out[i]
+  const int* count;        // device scalar (NULL: n)
+};
+
+// One layer (layer = -1: the stem) on this wave's NL tiles: the origins tl[rq], tl[rq + 2], ... of the layer's list. The image is
+// addressed by SEQUENCE row (row r at act + r TW_AP). Same weight stream, same products in the same order as tower2_layers<true, NL, 1>.
+template <int NL>
+__device__ __forceinline__ void tower_parts_layer(const TowerCtx2& c, int layer, const int* tl, float4 (&bn)[2], int& it) {
+  constexpr int NA = NL > 0 ? NL : 1;
+  const int niter = layer < 0 ? 2 : 10;
+  const int nit = 2 + 10 * c.nlayers;
+  if constexpr (NL == 0) {                                       // no tile on this layer: keep the weight stream and the barriers in step
+    it += niter;
+    if (it < nit) {
+      const float* src = c.wsrc + (size_t)it * TW_C * CH;
+      bn[0] = *reinterpret_cast<const float4*>(src);
+      bn[1] = *reinterpret_cast<const float4*>(src + 4);
+    }
+    if (layer >= 0) __syncthreads();
+    __syncthreads();
+    return;
+  }
+  const int j = c.j, g = c.g;
+  int org[NA];                                                   // first sequence row of each tile (wave-uniform)
+#pragma unroll
+  for (int r = 0; r < NL; ++r) org[r] = __builtin_amdgcn_readfirstlane(tl[c.rq + 2 * r]);
+  const int lbase = (j * TW_AP + 8 * g) * 4;                     // byte offset of (row j, channel 8 g)
+  const int a_lo = (8 * g - TW_AP) * 4;                          // row -1
+  const int a_hi = (TW_ROWS * TW_AP + 8 * g) * 4;                // row TW_ROWS
+  const char* actb = reinterpret_cast<const char*>(c.act);
+  const int cb = 16 * c.cp + 4 * g;                              // this lane's OUTPUT channels cb + e (transposed tiles)
+  f32x4 acc[NA];
+  {
+    const f32x4 bl = *reinterpret_cast<const f32x4*>(c.bias + (layer + 1) * TW_C + cb);
+#pragma unroll
+    for (int r = 0; r < NL; ++r) acc[r] = bl;
+  }
+  for (int ci = 0; ci < niter; ++ci, ++it) {
+    const float b[8] = {bn[0].x, bn[0].y, bn[0].z, bn[0].w, bn[1].x, bn[1].y, bn[1].z, bn[1].w};
+    if (it + 1 < nit) {
+      const float* src = c.wsrc + (size_t)(it + 1) * TW_C * CH;
+      bn[0] = *reinterpret_cast<const float4*>(src);
+      bn[1] = *reinterpret_cast<const float4*>(src + 4);
+    }
+    float4 af[NA][2];
+    int og[NA];                                                  // the origins, opaque per iteration: the lane's addresses are summed
+#pragma unroll                                                   // here, one at a time — hoisted out of the loop they would hold 7 VGPRs
+    for (int r = 0; r < NL; ++r) { og[r] = org[r]; asm volatile("" : "+s"(og[r])); }
+    if (layer < 0) {
+      const int t0 = 8 * ci + 2 * g;                             // k = 32 ci + 8 g + s: taps t0, t0 + 1 (4 channels each)
+#pragma unroll
+      for (int r = 0; r < NL; ++r)
+#pragma unroll
+        for (int q = 0; q < 2; ++q)                              // xs holds zero rows outside the sequence, up to row TW_ROWS + 7
+          af[r][q] = *reinterpret_cast<const float4*>(c.xs + 4 * min(og[r] + j + t0 + q - 7, TW_ROWS + 7));
+    } else {
+      const int chk = ci / 5, delta = ci - 5 * chk - 2;
+      const int dbytes = delta * (TW_AP * 4) + chk * (CH * 4);
+#pragma unroll
+      for (int r = 0; r < NL; ++r) {                             // rows before 0 read the zero row -1, rows past TW_ROWS the zero row TW_ROWS
+        const int o = min(max(lbase + dbytes + og[r] * (TW_AP * 4), a_lo + chk * (CH * 4)), a_hi + chk * (CH * 4));
+        const float4* ap = reinterpret_cast<const float4*>(actb + o);
+        af[r][0] = ap[0]; af[r][1] = ap[1];
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < NL; ++r)
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const float av[4] = {af[r][q].x, af[r][q].y, af[r][q].z, af[r][q].w};
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) acc[r] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[4 * q + s4], av[s4], acc[r], 0, 0, 0);
+      }
+  }
+  if (layer >= 0) __syncthreads();                               // every wave is done reading the image (the stem reads xs)
+  const bool res = layer >= 0 && ((c.residual_mask >> layer) & 1);
+#pragma unroll
+  for (int r = 0; r < NL; ++r) {
+    const int row = org[r] + j;
+    if (row < c.L) {                                             // rows from L on are never written: they stay the zeros the taps past the end read
+      f32x4* dst = reinterpret_cast<f32x4*>(c.act + row * TW_AP + cb);
+      const f32x4 z = {0.0f, 0.0f, 0.0f, 0.0f};
+      const f32x4 v = acc[r] + (res ? *dst : z);
+      *dst = __builtin_elementwise_max(v, z);
+    }
+  }
+  __syncthreads();                                               // the image is complete
+}
+
+__global__ __launch_bounds__(512, 4) void conv_tower_parts_kernel(TowerPartArgs pa) {
+  const TowerArgs& a = pa.t;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  __shared__ int tl[TP_BLOCKS + 1][TP_LT];              // per layer: the tile origins of all parts, then their number
+  float* act = smem + TW_AP;                            // rows -1 .. TW_ROWS, by SEQUENCE row ; [-1] and [TW_ROWS] are zero where read
+  float* xs = smem + (TW_ROWS + 2) * TW_AP + 8 * 4;     // one-hot rows -8 .. TW_ROWS + 8
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int L = a.L, R = pa.reach, nl = a.nlayers;
+  if (pa.count && (int)blockIdx.x >= __builtin_amdgcn_readfirstlane(*pa.count)) return;
+  int cand = blockIdx.x;
+  if (pa.live_idx) cand = __builtin_amdgcn_readfirstlane(pa.live_idx[blockIdx.x]);
+  int np = 0, p0[TP_PARTS], p1[TP_PARTS];               // the parts, clamped into the sequence (whatever the array holds)
+#pragma unroll
+  for (int p = 0; p < TP_PARTS; ++p) {
+    const int f = __builtin_amdgcn_readfirstlane(pa.parts[(size_t)cand * (2 * TP_PARTS) + 2 * p]);
+    const int l = __builtin_amdgcn_readfirstlane(pa.parts[(size_t)cand * (2 * TP_PARTS) + 2 * p + 1]);
+    p0[p] = min(max(f, 0), L - 1); p1[p] = min(max(l, p0[p]), L - 1);
+    if (f >= 0 && np == p) np = p + 1;                  // parts are listed without holes
+  }
+  float* outc = a.out + (size_t)blockIdx.x * L * TW_C;
+  {
+    const float* par = pa.parent_out + (size_t)(cand / pa.M) * L * TW_C;
+    for (int e = tid; e < L * 16; e += 512) {           // rows that are the parent's, straight from its output
+      const int row = e >> 4;
+      bool kept = false;
+#pragma unroll
+      for (int p = 0; p < TP_PARTS; ++p) kept |= p < np && row >= p0[p] - R && row <= p1[p] + R;
+      if (!kept)
+        *reinterpret_cast<float4*>(outc + (size_t)row * TW_C + 4 * (e & 15)) = *reinterpret_cast<const float4*>(par + (size_t)row * TW_C + 4 * (e & 15));
+    }
+    if (np == 0) return;
+  }
+  {
+    const float* xc = a.x + (size_t)cand * L * 4;
+    for (int e = tid - 8; e < TW_ROWS + 8; e += 512) {
+      float4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (e >= 0 && e < L) v = *reinterpret_cast<const float4*>(xc + (size_t)e * 4);
+      *reinterpret_cast<float4*>(xs + 4 * e) = v;
+    }
+  }
+  // Zero only the image rows that are read: a block reads two rows around its tiles, so per part everything any layer reads lies
+  // in [s - 2, e + 18), s / e = the stem's needed range (the tiles of a layer pass its needed end by at most 15 rows) — the rows
+  // before 0 and from L on among them are the zero rows of the sequence ends and are never written.
+  const int h0 = R + 2 * nl;
+#pragma unroll
+  for (int p = 0; p < TP_PARTS; ++p) {
+    if (p >= np) break;
+    const int z0 = max(-1, max(0, p0[p] - h0) - 2), z1 = min(TW_ROWS + 1, min(L, p1[p] + h0 + 1) + 18);
+    const float4 z = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int e = tid; e < (z1 - z0) * (TW_AP / 4); e += 512) *reinterpret_cast<float4*>(act + z0 * TW_AP + 4 * e) = z;
+  }
+  if (tid <= nl) {                                      // layer tid's tile origins: every part's needed range in steps of 16 from its first row
+    const int h = R + 2 * (nl - tid);
+    int cnt = 0;
+#pragma unroll
+    for (int p = 0; p < TP_PARTS; ++p) {
+      if (p >= np) break;
+      const int e = min(L, p1[p] + h + 1);
+      for (int o = max(0, p0[p] - h); o < e && cnt < TW_RT; o += 16) tl[tid][cnt++] = o;   // (disjoint ranges in <= 208 rows: <= TW_RT tiles)
+    }
+    tl[tid][TP_LT - 1] = cnt;
+  }
+
+  TowerCtx2 c;
+  c.act = act; c.xs = xs; c.bias = a.bias;
+  c.L = L; c.tile_rows = L; c.nlayers = nl; c.residual_mask = a.residual_mask;
+  c.cp = w & 3; c.rq = w >> 2; c.j = lane & 15; c.g = lane >> 4;
+  c.wsrc = a.tiles + (16 * c.cp + c.j) * CH + 8 * c.g;
+  __syncthreads();
+  float4 bn[2] = {*reinterpret_cast<const float4*>(c.wsrc), *reinterpret_cast<const float4*>(c.wsrc + 4)};
+  int it = 0;
+  for (int layer = -1; layer < nl; ++layer) {
+    const int* tlk = tl[layer + 1];
+    const int nlive = (__builtin_amdgcn_readfirstlane(tlk[TP_LT - 1]) - c.rq + 1) >> 1;
+    switch (nlive) {                                    // wave-uniform; every path runs the same barriers
+      case 7: tower_parts_layer<7>(c, layer, tlk, bn, it); break;
+      case 6: tower_parts_layer<6>(c, layer, tlk, bn, it); break;
+      case 5: tower_parts_layer<5>(c, layer, tlk, bn, it); break;
+      case 4: tower_parts_layer<4>(c, layer, tlk, bn, it); break;
+      case 3: tower_parts_layer<3>(c, layer, tlk, bn, it); break;
+      case 2: tower_parts_layer<2>(c, layer, tlk, bn, it); break;
+      case 1: tower_parts_layer<1>(c, layer, tlk, bn, it); break;
+      default: tower_parts_layer<0>(c, layer, tlk, bn, it); break;
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < TP_PARTS; ++p) {                  // the kept rows of each part: the last block's needed range
+    if (p >= np) break;
+    const int k0 = max(0, p0[p] - R), k1 = min(L, p1[p] + R + 1);
+    for (int e = tid; e < (k1 - k0) * 16; e += 512) {
+      const int row = k0 + (e >> 4), q = e & 15;
+      *reinterpret_cast<float4*>(outc + (size_t)row * TW_C + 4 * q) = *reinterpret_cast<const float4*>(act + row * TW_AP + 4 * q);
+    }
+  }
+}
+
 // --------------------------------------------------------- fused dilated-CNN backbone (one launch per forward) ----
 // The whole masked-diffusion backbone of the reference (models/dnaconv.py:176-210, sigma = 0):
 //     f_0 = relu(conv9(onehot5(x)) + b)                      first layer as a 9-entry table lookup per output
@@ -3458,4 +3718,26 @@ extern "C" int svdd_conv_tower_windows_f32(const float* onehot, const float* til
   if (g_tower_ver != 1) kern = g_tower_ver == 2 ? conv_tower2_kernel<true, true, 2> : conv_tower2_kernel<true, true, 1>;
   SvddSpan span(SVDD_SLOT_CONV_TOWER);
   return svdd_launch_timed(span.all(), kern, dim3((unsigned)n), dim3(512), svdd_lds_raised(tower2_lds_bytes()), stream, wa);
+}
+
+extern "C" int svdd_candidate_parts(const uint8_t* cand, const uint8_t* x, int B, int L, int M, int reach, int gap, int32_t* parts,
+                                    int32_t* nparts, int32_t* flags, int32_t* key, void* on_stream) {
+  if (!cand || !x || !parts || B <= 0 || L <= 0 || M <= 0 || reach < 0 || reach > (1 << 20) || (long long)B * M > 0x7fffffffLL - 3 ||
+      gap < 2 * (reach + 2 * TP_BLOCKS) + 16)
+    return SVDD_E_ARG;                                   // a smaller gap would let two parts' computed tiles touch on the stem
+  const int n = B * M;
+  return svdd_launch(candidate_parts_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, on_stream, cand, x, n, L, M, reach, gap, parts,
+                     nparts, flags, key);
+}
+
+extern "C" int svdd_conv_tower_parts_f32(const float* onehot, const float* tiles, const float* bias, const int32_t* parts,
+                                         const float* parent_out, float* out, int n, int L, int M, int nlayers, int residual_mask,
+                                         int reach, const int32_t* live_idx, const int32_t* count, void* on_stream) {
+  if (!onehot || !tiles || !bias || !parts || !parent_out || !out || n <= 0 || M <= 0 || (n % M && !live_idx) || L <= TW_ROWS / 2 ||
+      L > TW_ROWS || nlayers != TP_BLOCKS || reach != TP_REACH)
+    return SVDD_E_ARG;                                   // one sequence per tile; the part rule is the 5-block tower's, and the parts must
+                                                         // have been cut for this reach (a larger one here would make their tiles overlap)
+  TowerPartArgs pa{TowerArgs{onehot, tiles, bias, out, n, L, 1, nlayers, residual_mask, nullptr}, parts, parent_out, M, reach, live_idx, count};
+  SvddSpan span(SVDD_SLOT_CONV_TOWER);
+  return svdd_launch_timed(span.all(), conv_tower_parts_kernel, dim3((unsigned)n), dim3(512), svdd_lds_raised(tower2_lds_bytes()), on_stream, pa);
 }

@@ -1414,12 +1414,12 @@ class Diffusion(nn.Module):
             onehot = None if lp else ws.onehot[:n * L * 4].view(n, L, 4)
             ops.ism_mutants(x, pos_dev[p0:p0 + pc], live, cand=cand, onehot=onehot, want_onehot=False, err=ws.err)
             if live is None:
-                win = fused.windows_of(cand, x)
+                win = fused.tower_ranges_of(cand, x)
                 sc = fused.forward_candidates_from(onehot, cand, win, parent_out)
                 slot = None
             else:                                                   # stopped rows' mutants are exact copies: flagged 0, dropped
                 flags, live_idx, slot = ws.flags[:n], ws.live_idx[:n], ws.slot[:n]
-                win = fused.windows_of(cand, x, flags=flags)
+                win = fused.tower_ranges_of(cand, x, key=flags)
                 ops.compact_flags(flags, live_idx, slot, ws.count)
                 sc = fused.forward_candidates_from(onehot, cand, win, parent_out, live_idx=live_idx, count=ws.count)
             sc = sc.reshape(n, -1)
@@ -1687,7 +1687,9 @@ class Diffusion(nn.Module):
             self.late = False                   # set by the sampler per step: the live candidates may exceed one GRU round (FusedValueNet.split_gru_rounds)
             self.split_bufs = None              # persistent buffers + side stream of that path
             self.prior_rows_identical = False   # set by the sampler when x is the prior: the parents' first tower pass runs on one row
-            self.n_win_rows = None          # with skip_stats: rows the value net's tower computed (the candidates' row windows)
+            self.n_win_rows = None          # with skip_stats: rows the value net's tower computed (the candidates' row windows; with per-layer
+                                            # ranges the FLOP-equivalent number of full-depth rows) ...
+            self.n_tile_layers = None       # ... and its 16-row tiles summed over the six layers
 
     def _select_compact(self, sc, ws, cand, step):
         mode, rng = self._select_args(step)
@@ -1710,7 +1712,8 @@ class Diffusion(nn.Module):
         if self.skip_stats is not None:
             self.skip_stats.update(kind=kind, steps=S, candidates=B * M * S, live_candidates=int(ws.n_live),
                                    row_steps=B * S, changed_row_steps=int(ws.n_changed),
-                                   tower_window_rows=None if ws.n_win_rows is None else int(ws.n_win_rows))
+                                   tower_window_rows=None if ws.n_win_rows is None else int(round(float(ws.n_win_rows))),
+                                   tower_tile_layers=None if ws.n_tile_layers is None else int(ws.n_tile_layers))
 
     def _use_logits_cache(self, L):
         """Per-row logits cache of the SVDD-MC skipping loop. "auto": where several sequences share a backbone tile
@@ -1736,7 +1739,8 @@ class Diffusion(nn.Module):
         from .fused import candidate_windows
         ws = self._SkipWorkspace(B, M, self.device)
         if self.skip_stats is not None:
-            ws.n_win_rows = torch.zeros(1, dtype=torch.int64, device=self.device)
+            ws.n_win_rows = torch.zeros(1, dtype=torch.float64, device=self.device)
+            ws.n_tile_layers = torch.zeros(1, dtype=torch.int64, device=self.device)
         from .fused import FusedValueNet
         dedup = self._prior_dedup_ok(x) and isinstance(fn, FusedValueNet)   # the parents are B copies of the all-MASK row
         ws.parent_score.copy_(fn.forward_tokens(x[:1].contiguous()).reshape(1).expand(B) if dedup

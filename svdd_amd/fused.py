@@ -17,6 +17,7 @@ Numerics: fp32 throughout; results differ from the plain modules only by fp32 re
 well inside the 1e-4 soft-value tolerance of the north star (tests/test_fused_gpu.py).
 """
 import ctypes
+import os
 import math
 
 import torch
@@ -660,21 +661,57 @@ def candidate_windows(cand, x, margin=TOWER_WINDOW_MARGIN, flags=None, tight=Fal
     return win
 
 
+TOWER_REACH = 17             # the receptive field alone: stem 15 taps + 5 x 5 taps
+TOWER_PART_GAP = 2 * TOWER_WINDOW_MARGIN + 16    # 70: the smallest gap at which two parts' computed tiles never touch (svdd_candidate_parts)
+TOWER_PARTS_DEFAULT = "on"   # FusedValueNet.tower_parts of a new net (profiles/tower_parts_bench_ab.txt)
+TOWER_LAYER_FLOP_WEIGHTS = (3, 16, 16, 16, 16, 16)   # a row's FLOPs by layer: stem 4 x 15 x 64 : block 64 x 5 x 64 = 3 : 16 (83 in all)
+
+
+def candidate_parts(cand, x, reach=TOWER_REACH, gap=TOWER_PART_GAP, flags=None, key=None, nparts=None):
+    """cand [B, M, L] u8, x [B, L] u8 -> int32 [B*M, 3, 2]: (first, last) changed position of each PART of a candidate — its changed
+    positions cut wherever two consecutive ones are >= gap apart, at most 3 parts, (-1, -1) where there is none (HIP kernel
+    svdd_candidate_parts; for conv_tower_windows, which runs every layer only on the tiles that cover its own range of each part).
+    Optional int32 [B*M] outputs: nparts, flags (the candidate's tile-layers, 0 = a copy of its parent) and key (ceil(flags / 6):
+    the order of flags within the 15 keys ops.compact_by_key tells apart)."""
+    assert cand.is_cuda and cand.dtype == torch.uint8 and cand.is_contiguous() and x.dtype == torch.uint8 and x.is_contiguous()
+    B, M, L = cand.shape
+    parts = torch.empty((B * M, 3, 2), dtype=torch.int32, device=cand.device)
+    _lib.call("svdd_candidate_parts", cand, x, B, L, M, int(reach), int(gap), parts, nparts, flags, key,
+              ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))       # these entries take their stream as an explicit argument
+    return parts
+
+
+def part_layer_tiles(parts, L, reach=TOWER_REACH):
+    """int64 [n, 6]: the 16-row tiles each tower layer (0 = stem) computes for the candidates' parts [n, 3, 2] — the count
+    svdd_candidate_parts sums into flags, per layer (Diffusion.skip_stats; plain tensor arithmetic, off the timed path)."""
+    a, b = parts[:, :, 0].long(), parts[:, :, 1].long()
+    h = (reach + 2 * (5 - torch.arange(6, device=parts.device))).view(1, 1, 6)
+    rows = (b[:, :, None] + h + 1).clamp(max=L) - (a[:, :, None] - h).clamp(min=0)
+    return (((rows + 15) // 16) * (a >= 0)[:, :, None]).sum(dim=1)
+
+
 def conv_tower_windows(onehot, win, parent_out, M, tiles, bias, residual_mask, live_idx=None, count=None, out=None):
     """Tower output [n, L, 64] of the candidates' one-hot [n = B*M, L, 4], computing only the row windows `win` and
-    copying the rest from the parents' tower output [B, L, 64] (HIP kernel svdd_conv_tower_windows_f32).
+    copying the rest from the parents' tower output [B, L, 64] (HIP kernel svdd_conv_tower_windows_f32). win [n, 3, 2]
+    (candidate_parts) instead of [n, 2]: per-layer row ranges on each part (svdd_conv_tower_parts_f32; the same bits).
     out: a [k, L, 64] buffer for a launch over PART of a compacted list — live_idx is then a slice of the list, count the
     device-side length of that part, and the launch takes at most k entries."""
     assert onehot.is_cuda and onehot.dtype == torch.float32 and onehot.is_contiguous() and onehot.shape[2] == 4
     n, L, _ = onehot.shape
-    assert parent_out.is_contiguous() and parent_out.shape == (n // M, L, 64) and win.shape == (n, 2)
+    parts = win.dim() == 3
+    assert parent_out.is_contiguous() and parent_out.shape == (n // M, L, 64) and win.shape == ((n, 3, 2) if parts else (n, 2))
+    assert win.dtype == torch.int32 and win.is_contiguous()
     if out is None:
         out = torch.empty((n, L, 64), dtype=torch.float32, device=onehot.device)
     else:
         assert live_idx is not None and count is not None and out.is_contiguous() and out.shape[1:] == (L, 64)
         n = out.shape[0]
-    _lib.call("svdd_conv_tower_windows_f32", onehot, tiles, bias, win, parent_out, out, n, L, M, bias.shape[0] - 1, int(residual_mask),
-              live_idx, count)
+    if parts:
+        _lib.call("svdd_conv_tower_parts_f32", onehot, tiles, bias, win, parent_out, out, n, L, M, bias.shape[0] - 1, int(residual_mask),
+                  TOWER_REACH, live_idx, count, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    else:
+        _lib.call("svdd_conv_tower_windows_f32", onehot, tiles, bias, win, parent_out, out, n, L, M, bias.shape[0] - 1, int(residual_mask),
+                  live_idx, count)
     return out
 
 
@@ -761,7 +798,16 @@ class FusedValueNet(nn.Module):
         self.split_gru_rounds = True         # candidate_scores_compact, late steps: the live candidates as two parts so that the GRU's second round
                                              # hides under the first part's tower (same bits; _windows_gru_tail_split)
         self.sort_live_by_window = True      # candidate_scores_compact: live candidates ordered by window size, largest first (A/B knob; same bits)
-        self.tight_windows = True            # fp32 windowed tower: windows aligned at one end only (candidate_windows(tight=True); A/B knob; same bits)
+        self.tight_windows = True            # fp32 windowed tower: windows aligned at one end only (candidate_windows(tight=True); A/B knob; same bits).
+                                             # Reached only with tower_parts = "off": the parts path has no windows
+        # fp32 windowed tower: "on" = per-layer row ranges and separate parts for changes >= 70 rows apart (candidate_parts), "layers" =
+        # per-layer ranges on one part, "off" = one window per candidate (A/B knob; same bits). With "on" / "layers" the routed paths run
+        # conv_tower_parts_kernel, which has one generation: tight_windows and svdd_set_tower_version apply to "off" (and to
+        # conv_tower_windows called with windows) only. The environment variable SVDD_TOWER_PARTS sets the value every new net starts
+        # with (for A/B runs of programs that build their own net, bench.py among them).
+        self.tower_parts = os.environ.get("SVDD_TOWER_PARTS") or TOWER_PARTS_DEFAULT
+        if self.tower_parts not in ("on", "layers", "off"):
+            raise ValueError(f"SVDD_TOWER_PARTS = {self.tower_parts!r}: expected 'on', 'layers' or 'off'")
         # "f32" (exact, default) or one of LP_DTYPES: the conv tower, GRU and tail on the 16-bit matrix cores
         # (csrc/svdd_lp_*.hip). Needs the reference-shaped net (tower_ok, tail_ok).
         self.precision = "f32"
@@ -896,7 +942,7 @@ class FusedValueNet(nn.Module):
         valid, in live_idx order). Same kernels, same bits per candidate as forward_candidates; no host round trip."""
         from . import ops
         B, M, L = cand.shape
-        win = self.windows_of(cand, x, flags=ws.flags)   # ws.flags = the windows' tile counts: the sort key below
+        win = self.tower_ranges_of(cand, x, key=ws.flags)   # ws.flags = live flag and sort key: tiles of the window / ceil(tile-layers / 6) of the parts
         # the live candidates by DESCENDING window size: a windowed-tower workgroup takes as many row tiles as its window has, and
         # with the long ones dispatched first the launch does not end on a few CUs that began a 13-tile window last (fp32 tower
         # 487 -> 395 us per launch on a C2 decode's states, tools/tower_order_probe.py). A row's result does not depend on its
@@ -907,7 +953,14 @@ class FusedValueNet(nn.Module):
         else:
             (ops.compact_by_key if self.sort_live_by_window else ops.compact_flags)(ws.flags, ws.live_idx, ws.slot, ws.count)
         if getattr(ws, "n_win_rows", None) is not None:                     # Diffusion.skip_stats: rows the tower computes this step
-            ws.n_win_rows += (win[:, 1] - win[:, 0]).sum()
+            if win.dim() == 3:                # parts: the layers run on different tiles -> the FLOP-equivalent number of full-depth rows,
+                t = part_layer_tiles(win, L).sum(dim=0)                     # 16 x sum of tiles per layer x the layer's share of a row's FLOPs
+                wt = torch.tensor(TOWER_LAYER_FLOP_WEIGHTS, dtype=torch.float64, device=t.device)
+                ws.n_win_rows += 16.0 * (t * wt).sum() / float(sum(TOWER_LAYER_FLOP_WEIGHTS))
+                ws.n_tile_layers += t.sum()
+            else:
+                ws.n_win_rows += (win[:, 1] - win[:, 0]).sum()
+                ws.n_tile_layers += 6 * ((win[:, 1] - win[:, 0]) // 16).sum()
         # The parents' tower output is carried from step to step: the next parent IS the selected candidate, whose tower
         # output this step computes (bit-identical to a full tower pass on it) — ws.advance_parent copies it over after
         # the select. Only the first step runs the tower on the parents.
@@ -1037,6 +1090,19 @@ class FusedValueNet(nn.Module):
         the fp32 kernels take either)."""
         return candidate_windows(cand, x, flags=flags, tight=self.tight_windows and self.precision == "f32")
 
+    def tower_ranges_of(self, cand, x, key=None):
+        """What this net's windowed tower computes of every candidate, for conv_tower_windows / forward_candidates_from: the
+        candidates' parts [n, 3, 2] (candidate_parts; fp32 with tower_parts "on" or "layers": per-layer row ranges) or their windows
+        [n, 2] (windows_of). key (int32 [B*M], optional) receives what the compactions take (ops.compact_flags, compact_by_key): > 0 =
+        differs from its parent, larger = more tiles — the `flags` output of the window entries (tiles of the window), the `key`
+        output of svdd_candidate_parts (ceil(tile-layers / 6); its `flags` output, the tile-layers themselves, is not asked for here)."""
+        if self.tower_parts not in ("on", "layers", "off"):
+            raise ValueError(f"tower_parts = {self.tower_parts!r}: expected 'on', 'layers' or 'off'")
+        if self.tower_parts == "off" or self.precision != "f32":
+            return self.windows_of(cand, x, flags=key)
+        gap = TOWER_PART_GAP if self.tower_parts == "on" else max(TOWER_PART_GAP, cand.shape[2] + 1)   # a gap above L: one part always
+        return candidate_parts(cand, x, gap=gap, key=key)
+
     def forward_candidates(self, onehot, cand, x):
         """Scores of the B*M candidates (onehot [B*M, L, 4], row b*M + m; cand [B, M, L] u8) of the parents x [B, L] u8.
         Same result as forward(onehot), bit for bit; the conv tower is evaluated once per parent and, per candidate,
@@ -1050,7 +1116,7 @@ class FusedValueNet(nn.Module):
             seq = conv_tower_windows_lp(cand, win, parent_out, pk["tiles"], self.tw_bias, pk["tinv"], self.tw_resmask, pk["prec"])
             return self._after_tower_lp(seq, pk)
         parent_out = conv_tower(ops.transform_samples(x), self.tw_tiles, self.tw_bias, self.tw_resmask)
-        win = self.windows_of(cand, x)
+        win = self.tower_ranges_of(cand, x)
         seq = conv_tower_windows(onehot, win, parent_out, M, self.tw_tiles, self.tw_bias, self.tw_resmask)
         return self._after_tower(seq, B * M, L)
 
@@ -1064,7 +1130,7 @@ class FusedValueNet(nn.Module):
         return conv_tower(ops.transform_samples(x), self.tw_tiles, self.tw_bias, self.tw_resmask)
 
     def forward_candidates_from(self, onehot, cand, win, parent_out, live_idx=None, count=None):
-        """forward_candidates with the parents' tower output and the candidates' windows given: windowed tower, GRU, tail ->
+        """forward_candidates with the parents' tower output and the candidates' windows (or parts: tower_ranges_of) given: windowed tower, GRU, tail ->
         scores [B * M, n_tasks, 1]. onehot is not read in a split precision (may be None). live_idx / count (int32 device tensors):
         only the listed candidates, compacted into the first count[0] rows of the result. Same kernels, same bits per candidate."""
         B, M, L = cand.shape
