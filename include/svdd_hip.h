@@ -693,6 +693,20 @@ int svdd_backbone_incr2_f32(const uint8_t* x, const float* table0, const float* 
                             float* out, int n, int L, int nlayers, const int* dilations, int lead, float* planes,
                             uint8_t* x_prev, int32_t* items, unsigned long long* stat, int first, int max_item,
                             int32_t* order, int32_t* order_count, void* on_stream);
+/* svdd_backbone_incr3_f32 — svdd_backbone_incr2_f32 with the carried planes extended through the dilation-4 layers that follow the
+ *   `lead` dilation-1 layers: planes 1 .. depth are carried, lead <= depth <= nlayers, dilations[0 .. lead) all 1 and
+ *   dilations[lead .. depth) all 4 (anything else: SVDD_E_ARG; depth == lead is svdd_backbone_incr2_f32's forward). A changed
+ *   position p has reached p +- (4 + sum_{i<k} 4 dilations[i]) in plane k: 8 .. 36 behind eight dilation-1 layers, 52, 68, 84, 100
+ *   behind four dilation-4 layers. planes [depth][n][208][128], items [depth][n][S], order [depth][n * S], order_count [depth] ;
+ *   stat (may be NULL): TWO device u64, stat[0] += the marked tile-layers of planes 1 .. lead, stat[1] += those of the deeper
+ *   planes. first != 0 fills all `depth` planes; first == 0: work list, order, one segment launch per carried layer (the dilation-4
+ *   layers skip exactly the (row tile, tap) pairs the one-launch kernel's schedule skips), then layers depth .. nlayers - 1 and
+ *   final_conv from plane `depth`. Everything else — bits of `out`, x_prev, max_item, the lists, on_stream, the profile span,
+ *   svdd_backbone_incr_set_residency — as svdd_backbone_incr2_f32. */
+int svdd_backbone_incr3_f32(const uint8_t* x, const float* table0, const float* tiles, const float* vec, const float* w2,
+                            float* out, int n, int L, int nlayers, const int* dilations, int lead, float* planes,
+                            uint8_t* x_prev, int32_t* items, unsigned long long* stat, int first, int max_item,
+                            int32_t* order, int32_t* order_count, int depth, void* on_stream);
 int svdd_backbone_incr_set_residency(int wg_per_cu);
 /* svdd_backbone_set_workspace — caller-owned scratch for the small-batch form of svdd_backbone_cnn_f32 (several workgroups per
  * sequence exchange the LayerNorm'd image of every layer through it): ws = device memory of `bytes` >= n_max * (2 * 208 * 128 * 4

@@ -77,6 +77,7 @@ SIGNATURES = {
     "svdd_backbone_cnn_f32": (vp, vp, vp, vp, vp, vp, i32, i32, i32, pi32, vp, vp, i32, STREAM),
     "svdd_backbone_incr_f32": (vp, vp, vp, vp, vp, vp, i32, i32, i32, pi32, i32, vp, vp, vp, vp, i32, i32, vp),
     "svdd_backbone_incr2_f32": (vp, vp, vp, vp, vp, vp, i32, i32, i32, pi32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp),
+    "svdd_backbone_incr3_f32": (vp, vp, vp, vp, vp, vp, i32, i32, i32, pi32, i32, vp, vp, vp, vp, i32, i32, vp, vp, i32, vp),
     "svdd_backbone_incr_set_residency": (i32,),
     "svdd_value_tail_f32": (vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, STREAM),
     "svdd_candidate_windows": (vp, vp, i32, i32, i32, i32, vp, vp, STREAM),

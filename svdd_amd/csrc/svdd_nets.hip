@@ -2193,6 +2193,8 @@ __global__ __launch_bounds__(512, 2) void backbone_kernel(BackboneArgs a, Backbo
 // products. At dilation 1 every tap of every row tile is live in backbone_kernel's schedule, so all 36 entries run; a tap that
 // leaves the sequence reads a zero row there (clamped address) and a zero row of the halo tile here. A mask that marks too many
 // tiles is still exact (an unchanged tile recomputes to the same bits); no workgroup waits for another: the stream orders the layers.
+// svdd_backbone_incr3_f32 carries the planes on through the dilation-4 layers behind the stem: the reach grows by 16 rows per layer
+// (BackboneReach), the same kernel runs them as backbone_seg_kernel<.., DIL = 4>, and the tail starts behind the last carried plane.
 constexpr int SEG_SLOTS = 7;                   // items per (layer, row): 13 tiles in runs cut to <= 2 (or <= 4) tiles, at worst 7
 
 struct BackboneSegArgs {
@@ -2208,12 +2210,27 @@ struct BackboneSegArgs {
   int order_stride;        // n * (items per row)
 };
 
-// One wave per row. Lane k - 1 cuts layer k's tile mask into items; stat (may be NULL) += the tile-layers marked. SLOTS = items per
-// (layer, row): SEG_SLOTS for runs cut to 2 or 4 tiles, TW_RT for 1-tile items (svdd_backbone_incr2_f32 only).
+// How far a changed position has spread in plane k, k = 1 .. P: r[k - 1] = 4 + sum over i < k of 4 dil[i] (4 + 4 k over the leading
+// dilation-1 layers; 52, 68, 84, 100 over the four dilation-4 layers behind eight of them). lead1 = the leading dilation-1 layers:
+// the marked tile-layers of planes 1 .. lead1 are counted in stat[0], those of the deeper planes in stat[1].
+struct BackboneReach {
+  int r[BB_MAXL];
+  int lead1;
+};
+static BackboneReach backbone_reach(const int* dilations, int P, int lead1) {
+  BackboneReach rc{};
+  int reach = 4;
+  for (int k = 1; k <= P; ++k) { reach += 4 * dilations[k - 1]; rc.r[k - 1] = reach; }
+  rc.lead1 = lead1;
+  return rc;
+}
+
+// One wave per row. Lane k - 1 cuts layer k's tile mask into items; stat (may be NULL) += the tile-layers marked (see BackboneReach).
+// SLOTS = items per (layer, row): SEG_SLOTS for runs cut to 2 or 4 tiles, TW_RT for 1-tile items (the ordered entries only).
 template <int SLOTS = SEG_SLOTS>
 __global__ __launch_bounds__(256) void backbone_worklist_kernel(const uint8_t* __restrict__ x, uint8_t* __restrict__ x_prev, int n,
                                                                 int L, int P, int max_item, int* __restrict__ items,
-                                                                unsigned long long* __restrict__ stat) {
+                                                                unsigned long long* __restrict__ stat, BackboneReach rc) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= n) return;
   const int lane = threadIdx.x & 63;
@@ -2226,7 +2243,7 @@ __global__ __launch_bounds__(256) void backbone_worklist_kernel(const uint8_t* _
   }
   int mine = 0;
   for (int k = 1; k <= P; ++k) {
-    const int reach = 4 + 4 * k;
+    const int reach = rc.r[k - 1];
     int m = 0;
     for (int q = 0; q < 4; ++q)
       if (changed >> q & 1) {
@@ -2237,6 +2254,13 @@ __global__ __launch_bounds__(256) void backbone_worklist_kernel(const uint8_t* _
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) m |= __shfl_xor(m, off, 64);
     if (lane == k - 1) mine = m;
+  }
+  if (stat) {                                             // one add per wave and counter: the lanes' adds to one address would queue up in L2
+    int c0 = lane < rc.lead1 ? __popc(mine) : 0, c1 = lane < rc.lead1 ? 0 : __popc(mine);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { c0 += __shfl_xor(c0, off, 64); c1 += __shfl_xor(c1, off, 64); }
+    if (lane == 0 && c0) atomicAdd(stat, (unsigned long long)c0);
+    if (lane == 0 && c1) atomicAdd(stat + 1, (unsigned long long)c1);
   }
   if (lane >= P) return;
   int* it = items + ((size_t)lane * n + row) * SLOTS;
@@ -2249,7 +2273,6 @@ __global__ __launch_bounds__(256) void backbone_worklist_kernel(const uint8_t* _
     t += len;
   }
   for (; cnt < SLOTS; ++cnt) it[cnt] = 0;
-  if (stat && mine) atomicAdd(stat, (unsigned long long)__popc(mine));
 }
 
 // The size-ordered list of svdd_backbone_incr2_f32: workgroup k packs layer k + 1's non-empty items into order[k] as
@@ -2316,8 +2339,13 @@ __global__ __launch_bounds__(256) void backbone_order_kernel(const int* __restri
 // 0 .. NC + 1 = halo, own tiles, halo), so a weight fragment feeds up to NC row tiles and the register arrays are sized to the item.
 // ORD: workgroup b takes entry b of the layer's size-ordered list (svdd_backbone_incr2_f32) instead of slot b of `items`; NC = 1
 // exists for that list only (3 image slots, one fragment set per entry, 4 workgroups per CU).
-template <int NC, bool ORD = false>
+// DIL = the layer's dilation, 1 or 4 (svdd_backbone_incr3_f32): tap t reads image row + (t - 4) DIL, at most the 16 rows of one halo
+// tile away. At dilation 4 backbone_kernel's schedule drops a (row tile, tap) pair whose inputs are all padding — with
+// d = (t - 4) DIL, tile T is live iff max(0, -d) < 16 T + 16 and min(L, L - d) > 16 T; at L = 200 tile 0 drops tap -16, tile 12 taps
+// +8, +12, +16 — and exactly those pairs issue no MFMA here (tapmask), so the accumulators see the same operations in the same order.
+template <int NC, bool ORD = false, int DIL = 1>
 __global__ __launch_bounds__(256, NC == 4 ? 2 : NC == 1 ? 4 : 3) void backbone_seg_kernel(BackboneSegArgs a) {
+  static_assert(DIL == 1 || DIL == 4, "one halo tile per side holds taps of dilation <= 4");
   constexpr int NS = NC + 2, ROWS = 16 * NS;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* img = smem;                                      // [ROWS][BB_AP] image row i = sequence row 16 (t0 - 1) + i
@@ -2469,6 +2497,20 @@ __global__ __launch_bounds__(256, NC == 4 ? 2 : NC == 1 ? 4 : 3) void backbone_s
   const int arow0 = img_lds + ((16 + j) * BB_AP + 8 * g) * 4;       // LDS byte address of (row j of slot 1, col 8 g)
   const float* wsrc = a.tiles + (size_t)cl * 36 * BB_C * CH + col0 * CH + 8 * g;
   const int live = (1 << nown) - 1;
+  int tapmask[NC];                                        // DIL > 1: bit t = tap t of own tile c is live in backbone_kernel's schedule (wave-uniform)
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    int m = 0;
+    if (DIL > 1 && c < nown) {
+      const int T = t0 + c;
+#pragma unroll
+      for (int t = 0; t < 9; ++t) {
+        const int d = (t - 4) * DIL;
+        if (max(0, -d) < 16 * T + 16 && min(L, L - d) > 16 * T) m |= 1 << t;
+      }
+    }
+    tapmask[c] = __builtin_amdgcn_readfirstlane(m);
+  }
   float4 bA[4], bB[4];
   bA[0] = *reinterpret_cast<const float4*>(wsrc);
   bA[1] = *reinterpret_cast<const float4*>(wsrc + 4);
@@ -2476,7 +2518,7 @@ __global__ __launch_bounds__(256, NC == 4 ? 2 : NC == 1 ? 4 : 3) void backbone_s
   bA[3] = *reinterpret_cast<const float4*>(wsrc + 16 * CH + 4);
   bB[0] = bA[0]; bB[1] = bA[1]; bB[2] = bA[2]; bB[3] = bA[3];
   __syncthreads();                                        // the image is complete
-#define SG_DBYTES(IT) ((((IT) % 9) - 4) * (BB_AP * 4) + ((IT) / 9) * (CH * 4))
+#define SG_DBYTES(IT) ((((IT) % 9) - 4) * DIL * (BB_AP * 4) + ((IT) / 9) * (CH * 4))
 #define SG_ALOAD(C, V, DBYTES)                                                                               \
       { const LdsF4* ap_ = reinterpret_cast<const LdsF4*>(arow0 + (DBYTES) + (C) * (16 * BB_AP * 4));         \
         const f32x4 t0_ = ap_[0], t1_ = ap_[1];                                                              \
@@ -2484,7 +2526,7 @@ __global__ __launch_bounds__(256, NC == 4 ? 2 : NC == 1 ? 4 : 3) void backbone_s
 #define SG_MM(C, U)                                                                                          \
       __builtin_amdgcn_sched_barrier(0);                                                                     \
       __builtin_amdgcn_s_waitcnt(0xC07F | (2 << 8));      /* at most the two reads of the other fragment set in flight */ \
-      if (live & (1 << (C))) {                                                                               \
+      if (DIL == 1 ? (live & (1 << (C))) : (tapmask[C] >> (it % 9) & 1)) {                                   \
         _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                                      \
           cacc[C][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].x, bf0[4 * q], cacc[C][0], 0, 0, 0);        \
           cacc[C][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].x, bf1[4 * q], cacc[C][1], 0, 0, 0);        \
@@ -3600,7 +3642,7 @@ extern "C" int svdd_backbone_incr_f32(const uint8_t* x, const float* table0, con
     return svdd_launch_timed(span.all(), backbone_kernel<true, false, 1>, dim3((unsigned)n), dim3(512), lds, stream, a, BackboneSave{});
   }
   if (svdd_launch_timed(span.first(), backbone_worklist_kernel<>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, x, x_prev, n, L, lead,
-                        max_item, items, stat) != SVDD_OK)
+                        max_item, items, stat, backbone_reach(dilations, lead, lead)) != SVDD_OK)
     return SVDD_E_LAUNCH;
   BackboneSegArgs sa{x, table0, tiles, vec, planes, items, n, L, 0, nullptr, nullptr, 0};
   const int rows = 16 * (max_item + 2);
@@ -3648,7 +3690,8 @@ extern "C" int svdd_backbone_incr2_f32(const uint8_t* x, const float* table0, co
   }
   const int slots = max_item == 1 ? TW_RT : SEG_SLOTS;    // 13 one-tile items in a row that changed everywhere
   if (svdd_launch_timed(span.first(), max_item == 1 ? backbone_worklist_kernel<TW_RT> : backbone_worklist_kernel<SEG_SLOTS>,
-                        dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, x, x_prev, n, L, lead, max_item, items, stat) != SVDD_OK)
+                        dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, x, x_prev, n, L, lead, max_item, items, stat,
+                        backbone_reach(dilations, lead, lead)) != SVDD_OK)
     return SVDD_E_LAUNCH;
   if (svdd_launch(max_item == 1 ? backbone_order_kernel<TW_RT> : backbone_order_kernel<SEG_SLOTS>, dim3((unsigned)lead), dim3(256), 0, stream,
                   items, n, order, order_count) != SVDD_OK)
@@ -3667,6 +3710,55 @@ extern "C" int svdd_backbone_incr2_f32(const uint8_t* x, const float* table0, co
   for (int k = 1; k <= lead; ++k) {
     sa.layer = k;
     if (svdd_launch(seg, sgrid, dim3(256), slds, stream, sa) != SVDD_OK) return SVDD_E_LAUNCH;
+  }
+  return svdd_launch_timed(span.last(), backbone_kernel<true, false, 2>, dim3((unsigned)n), dim3(512), lds, stream, a, BackboneSave{});
+}
+
+// svdd_backbone_incr3_f32: svdd_backbone_incr2_f32 with the carried planes extended through the run of dilation-4 layers behind the
+// `lead` dilation-1 layers: planes 1 .. depth, layers lead + 1 .. depth on backbone_seg_kernel<.., 4>, the tail from plane `depth`.
+extern "C" int svdd_backbone_incr3_f32(const uint8_t* x, const float* table0, const float* tiles, const float* vec, const float* w2,
+                                       float* out, int n, int L, int nlayers, const int* dilations, int lead, float* planes,
+                                       uint8_t* x_prev, int32_t* items, unsigned long long* stat, int first, int max_item,
+                                       int32_t* order, int32_t* order_count, int depth, void* stream) {
+  if (!x || !table0 || !tiles || !vec || !w2 || !out || !dilations || !planes || !x_prev || !items || !order || !order_count ||
+      n <= 0 || n > 65536 || L <= TW_ROWS / 2 || L > TW_ROWS || nlayers <= 0 || nlayers > BB_MAXL || lead < 2 || lead > nlayers ||
+      (max_item != 1 && max_item != 2 && max_item != 4) || depth < lead || depth > nlayers)
+    return SVDD_E_ARG;
+  for (int i = 0; i < depth; ++i) if (dilations[i] != (i < lead ? 1 : 4)) return SVDD_E_ARG;
+  BackboneArgs a;
+  if (!backbone_args(a, x, table0, tiles, vec, w2, out, n, L, 1, nlayers, dilations)) return SVDD_E_ARG;
+  a.planes = planes; a.planes_P = depth;
+  const SvddLds lds = svdd_lds_raised(backbone_lds_bytes(nlayers, 3));
+  SvddSpan span(SVDD_SLOT_BACKBONE);                      // ONE span per forward over all its launches
+  if (first) {
+    if (hipMemcpyAsync(x_prev, x, (size_t)n * L, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return SVDD_E_LAUNCH;
+    return svdd_launch_timed(span.all(), backbone_kernel<true, false, 1>, dim3((unsigned)n), dim3(512), lds, stream, a, BackboneSave{});
+  }
+  const int slots = max_item == 1 ? TW_RT : SEG_SLOTS;
+  if (svdd_launch_timed(span.first(), max_item == 1 ? backbone_worklist_kernel<TW_RT> : backbone_worklist_kernel<SEG_SLOTS>,
+                        dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, x, x_prev, n, L, depth, max_item, items, stat,
+                        backbone_reach(dilations, depth, lead)) != SVDD_OK)
+    return SVDD_E_LAUNCH;
+  if (svdd_launch(max_item == 1 ? backbone_order_kernel<TW_RT> : backbone_order_kernel<SEG_SLOTS>, dim3((unsigned)depth), dim3(256), 0, stream,
+                  items, n, order, order_count) != SVDD_OK)
+    return SVDD_E_LAUNCH;
+  BackboneSegArgs sa{x, table0, tiles, vec, planes, items, n, L, 0, order, order_count, n * slots};
+  const int rows = 16 * (max_item + 2);
+  size_t slds = sizeof(float) * ((size_t)rows * BB_AP + 5 * (size_t)rows + rows + 8);
+  if (g_incr_residency > 0) {
+    const size_t pad = (CU_LDS_BYTES / (size_t)(g_incr_residency + 1) / 1024 + 1) * 1024;
+    if (pad > slds) slds = pad;
+  }
+  const dim3 sgrid((unsigned)(n * slots));
+  void (*seg1)(BackboneSegArgs) = max_item == 4 ? backbone_seg_kernel<4, true> : max_item == 2 ? backbone_seg_kernel<2, true>
+                                                                                                 : backbone_seg_kernel<1, true>;
+  void (*seg4)(BackboneSegArgs) = max_item == 4 ? backbone_seg_kernel<4, true, 4> : max_item == 2 ? backbone_seg_kernel<2, true, 4>
+                                                                                                    : backbone_seg_kernel<1, true, 4>;
+  svdd_raise_lds_limit(seg1, slds);
+  if (depth > lead) svdd_raise_lds_limit(seg4, slds);
+  for (int k = 1; k <= depth; ++k) {
+    sa.layer = k;
+    if (svdd_launch(k <= lead ? seg1 : seg4, sgrid, dim3(256), slds, stream, sa) != SVDD_OK) return SVDD_E_LAUNCH;
   }
   return svdd_launch_timed(span.last(), backbone_kernel<true, false, 2>, dim3((unsigned)n), dim3(512), lds, stream, a, BackboneSave{});
 }

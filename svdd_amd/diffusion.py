@@ -64,6 +64,11 @@ Engine knobs (attributes; defaults reproduce the reference's observable behaviou
                    (tests/test_backbone_incremental_gpu.py). "on": wherever the kernels apply, whatever the batch; "off". Off under
                    graph capture. The first forward of such a decode runs on all B rows (it fills the planes): dedup_prior does not
                    apply to it.
+  incremental_depth  how many conv layers the incremental backbone carries: an int from the leading run of dilation-1 layers (8)
+                   up to the end of the dilation-4 run behind them (12; svdd_backbone_incr3_f32 — a change has reached +- 52 .. 100
+                   rows there), or "auto" (default) = fused.INCR_DEPTH_AUTO, the depth the measurement of
+                   profiles/deep_planes_depth.txt picked. The environment variable SVDD_INCR_DEPTH sets the value every new model
+                   starts with (A/B runs). Same bits at every depth (tests/test_backbone_incr3_gpu.py).
   dedup_prior      True (default): every row of the prior x_T is the same all-MASK row (_sample_prior, :751-753), and with the hand-written
                    kernels a row's net output does not depend on the batch around it — so the FIRST backbone forward of a decode, the
                    parents' first value / reward score and their first tower pass run on one row and are broadcast. Bit-identical to
@@ -89,6 +94,7 @@ Engine knobs (attributes; defaults reproduce the reference's observable behaviou
 import contextlib
 import functools
 import math
+import os
 import warnings
 import weakref
 from dataclasses import dataclass
@@ -265,6 +271,7 @@ class Diffusion(nn.Module):
         self.dps_single_forward = False  # DPS opt-in: q_xs from the differentiable pass's log-probs, not from a second backbone forward per step
         self.logits_cache = "auto"
         self.incremental_backbone = "auto"
+        self.incremental_depth = os.environ.get("SVDD_INCR_DEPTH") or "auto"   # carried layers of the incremental backbone (see the module docstring)
         self.skip_stats = None
         self.skip_generic = False
         self.trace = None          # set to a list to record (logits, scores) of every step (tests / smoke)
@@ -1730,7 +1737,22 @@ class Diffusion(nn.Module):
         fb = self._fused_backbone_or_none(L)
         if fb is None or not fb.incremental_ok(B, L, any_batch=self.incremental_backbone == "on"):
             return None, None
-        return fb, fb.incremental_stem(B, L)
+        return fb, fb.incremental_stem(B, L, self._incremental_depth(fb))
+
+    def _incremental_depth(self, fb):
+        """incremental_depth as a number of carried layers of fb: "auto" = INCR_DEPTH_AUTO, held to what the backbone's dilations allow."""
+        from .fused import INCR_DEPTH_AUTO, leading_dilation1, following_dilation4
+        lead = leading_dilation1(fb.ol_dil)
+        most = lead + following_dilation4(fb.ol_dil)
+        if self.incremental_depth == "auto":
+            return min(max(INCR_DEPTH_AUTO, lead), most)
+        try:
+            depth = int(self.incremental_depth)
+        except (TypeError, ValueError):
+            depth = -1
+        if not lead <= depth <= most:
+            raise ValueError(f"incremental_depth = {self.incremental_depth!r}: expected 'auto' or {lead} .. {most}")
+        return depth
 
     def _controlled_sample_skipping(self, fn, x, cand, onehot, sched, B, L, S, M):
         """SVDD-MC with exact work-skipping (same tokens as the plain loop, bit for bit). 104 < L <= 208 (one sequence per
@@ -1801,8 +1823,11 @@ class Diffusion(nn.Module):
         if self.config.sampling.noise_removal:
             logits = inc.forward_incremental(x, stem, out=logits)
         if self.skip_stats is not None:                                       # executed work of the carried stem, of what the one-launch kernel runs
-            self.skip_stats.update(backbone_stem_tile_layers=int(stem.stat),
-                                   backbone_stem_tile_layers_dense=stem.forwards * B * ((L + 15) // 16) * stem.lead)
+            marked = stem.stat.tolist()
+            self.skip_stats.update(backbone_stem_tile_layers=marked[0],
+                                   backbone_stem_tile_layers_dense=stem.forwards * B * ((L + 15) // 16) * stem.lead,
+                                   backbone_deep_tile_layers=marked[1],
+                                   backbone_deep_tile_layers_dense=stem.forwards * B * ((L + 15) // 16) * stem.deep)
         return self._noise_removal(x, logits=logits)
 
     def _controlled_sample_generic_skipping(self, fn, x, cand, onehot, sched, B, L, S, M):

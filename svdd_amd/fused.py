@@ -418,6 +418,7 @@ def backbone_cnn(tokens, pk, count=None, out=None, row_idx=None, scatter=False):
 INCR_MAX_ITEM = 2          # row tiles per work item of the incremental stem (1, 2 or 4; tools/incremental_backbone_ab.py measures them)
 INCR_ORDERED = True        # True: svdd_backbone_incr2_f32 (segment launches dealt from the size-ordered list); False: svdd_backbone_incr_f32
 INCR_RESIDENCY = 0         # segment workgroups per CU under the ordered list (0 = no LDS padding); set with set_incr_residency
+INCR_DEPTH_AUTO = 10       # conv layers Diffusion.incremental_depth = "auto" carries (profiles/deep_planes_depth.txt; 8 = the dilation-1 layers only)
 INCR_SLOTS = 13            # work-list slots per (layer, row) the buffers are sized for: 7 for items <= 2 / 4, 13 for 1-tile items
 
 
@@ -436,27 +437,38 @@ def leading_dilation1(dil):
     return n
 
 
-class IncrementalStem:
-    """Caller-owned state of svdd_backbone_incr2_f32 for n sequences of length L: the carried planes, the tokens they belong to, the
-    step's work list, its size-ordered form (order, order_count) and the device counter of marked tile-layers. Allocated once and reused across decodes (FusedBackbone keeps
-    one per shape); `valid` says whether planes / x_prev describe the tokens of the last forward of THIS decode."""
+def following_dilation4(dil):
+    """Length of the run of dilation-4 layers right behind the leading dilation-1 layers (what svdd_backbone_incr3_f32 may carry on top)."""
+    lead = n = leading_dilation1(dil)
+    while n < len(dil) and dil[n] == 4:
+        n += 1
+    return n - lead
 
-    def __init__(self, n, L, lead, dev):
-        self.n, self.L, self.lead = n, L, lead
-        self.planes = torch.empty((lead, n, 208, 128), dtype=torch.float32, device=dev)
+
+class IncrementalStem:
+    """Caller-owned state of svdd_backbone_incr2_f32 / svdd_backbone_incr3_f32 for n sequences of length L: the carried planes (the
+    `lead` dilation-1 layers and `deep` dilation-4 layers behind them), the tokens they belong to, the step's work list, its
+    size-ordered form (order, order_count) and the device counters of marked tile-layers (stat[0]: the dilation-1 layers, stat[1]: the
+    deeper ones). Allocated once and reused across decodes (FusedBackbone keeps one per shape); `valid` says whether planes / x_prev
+    describe the tokens of the last forward of THIS decode."""
+
+    def __init__(self, n, L, lead, dev, deep=0):
+        self.n, self.L, self.lead, self.deep = n, L, lead, deep
+        depth = lead + deep
+        self.planes = torch.empty((depth, n, 208, 128), dtype=torch.float32, device=dev)
         self.x_prev = torch.empty((n, L), dtype=torch.uint8, device=dev)
-        self.items = torch.zeros((lead, n, INCR_SLOTS), dtype=torch.int32, device=dev)      # read as [lead][n][7] for items <= 2 / 4
-        self.order = torch.zeros((lead, n * INCR_SLOTS), dtype=torch.int32, device=dev)
-        self.order_count = torch.zeros(lead, dtype=torch.int32, device=dev)
-        self.stat = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.items = torch.zeros((depth, n, INCR_SLOTS), dtype=torch.int32, device=dev)     # read as [depth][n][7] for items <= 2 / 4
+        self.order = torch.zeros((depth, n * INCR_SLOTS), dtype=torch.int32, device=dev)
+        self.order_count = torch.zeros(depth, dtype=torch.int32, device=dev)
+        self.stat = torch.zeros(2, dtype=torch.int64, device=dev)
         self.valid = False
         self.forwards = 0                                # incremental (not first) forwards since the counter was last read
 
 
 def backbone_cnn_incremental(tokens, pk, st, out=None, max_item=None):
-    """backbone_cnn(tokens, pk) — the same bits — through the carried stem `st` (HIP entry svdd_backbone_incr2_f32): the first call
-    after st.valid = False runs the whole forward and fills the planes, every later one recomputes only the tiles of the leading
-    dilation-1 layers that a changed token can reach, then the remaining layers from the last plane."""
+    """backbone_cnn(tokens, pk) — the same bits — through the carried stem `st` (HIP entry svdd_backbone_incr2_f32; with st.deep > 0
+    svdd_backbone_incr3_f32): the first call after st.valid = False runs the whole forward and fills the planes, every later one
+    recomputes only the tiles of the carried layers that a changed token can reach, then the remaining layers from the last plane."""
     assert tokens.is_cuda and tokens.dtype == torch.uint8 and tokens.is_contiguous() and tuple(tokens.shape) == (st.n, st.L)
     n, L = tokens.shape
     if out is None:
@@ -464,7 +476,11 @@ def backbone_cnn_incremental(tokens, pk, st, out=None, max_item=None):
     dil = (ctypes.c_int * len(pk["dil"]))(*pk["dil"])
     first = not st.valid
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)        # these entries take their stream as an explicit argument
-    if INCR_ORDERED:
+    if st.deep > 0:
+        _lib.call("svdd_backbone_incr3_f32", tokens, pk["table0"], pk["tiles"], pk["vec"], pk["w2"], out, n, L, len(pk["dil"]), dil,
+                  st.lead, st.planes, st.x_prev, st.items, st.stat, int(first), int(max_item or INCR_MAX_ITEM), st.order,
+                  st.order_count, st.lead + st.deep, stream)
+    elif INCR_ORDERED:
         _lib.call("svdd_backbone_incr2_f32", tokens, pk["table0"], pk["tiles"], pk["vec"], pk["w2"], out, n, L, len(pk["dil"]), dil,
                   st.lead, st.planes, st.x_prev, st.items, st.stat, int(first), int(max_item or INCR_MAX_ITEM), st.order,
                   st.order_count, stream)
@@ -1229,13 +1245,18 @@ class FusedBackbone(nn.Module):
         return (self.kernel_ok(L) and self.precision == "f32" and 104 < L <= 208 and leading_dilation1(self.ol_dil) >= 2 and
                 (any_batch or (n > BB_SPLIT_MAX_SEQ and not 0 < n % 256 <= BB_SPLIT_MAX_SEQ)))
 
-    def incremental_stem(self, n, L):
-        """The resident IncrementalStem for [n, L] on this module's device, marked stale (a new decode starts)."""
-        key = (n, L, self.ol_tiles.device)
+    def incremental_stem(self, n, L, depth=None):
+        """The resident IncrementalStem for [n, L] on this module's device, marked stale (a new decode starts). depth: carried layers,
+        from leading_dilation1 (None: that) up to the end of the dilation-4 run behind them."""
+        lead = leading_dilation1(self.ol_dil)
+        deep = 0 if depth is None else int(depth) - lead
+        if not 0 <= deep <= following_dilation4(self.ol_dil):
+            raise ValueError(f"incremental depth {depth}: expected {lead} .. {lead + following_dilation4(self.ol_dil)}")
+        key = (n, L, deep, self.ol_tiles.device)
         st = self._incr.get(key)
         if st is None:
-            self._incr.clear()                          # one shape at a time: the planes are ~0.85 MB per sequence
-            st = self._incr[key] = IncrementalStem(n, L, leading_dilation1(self.ol_dil), self.ol_tiles.device)
+            self._incr.clear()                          # one shape at a time: the planes are ~0.1 MB per sequence and carried layer
+            st = self._incr[key] = IncrementalStem(n, L, lead, self.ol_tiles.device, deep)
         st.valid = False
         return st
 

@@ -10,9 +10,11 @@ A setting is NAME or items:residency:list — items = most row tiles per work it
 (0 = no LDS padding: 4 for items <= 2, 6 for 1-tile items, 3 for <= 4); list = slot (the old entry, one workgroup per (row, slot))
 or ordered (the compact list, most tiles first). Names: today = 2:0:slot, today4 = 4:0:slot, A = 2:0:ordered, A3 = 2:3:ordered,
 B = 2:2:ordered, C = 1:3:ordered, D = 1:4:ordered, E = 1:0:ordered.
+--depth 8,10,12: the carried layers (Diffusion.incremental_depth; 8 = the dilation-1 layers, up to 12 = through the dilation-4 layers,
+svdd_backbone_incr3_f32); every setting runs at every depth given, as NAME@depth. Default: 8.
 Usage: python tools/incremental_backbone_ab.py [decodes per leg, default 3] [--settings today,A,A3,B,C,D,E] [--steps 1,8,32,...]
-           [--rounds 2] [--no-decodes]
-       python tools/incremental_backbone_ab.py --profile SETTING --marks marks.json [--steps ...] [--reps 5]
+           [--rounds 2] [--no-decodes] [--depth 8,12]
+       python tools/incremental_backbone_ab.py --profile SETTING --marks marks.json [--steps ...] [--reps 5] [--depth 12]
            (for rocprofv3 --kernel-trace: per step and repeat one full forward, then ONE incremental forward; marks.json gets the
            per-layer tile and item counts of every such forward, in launch order, for tools/stem_dispatch_trace.py)"""
 import argparse, json, os, sys, time
@@ -31,6 +33,7 @@ ap.add_argument("--rounds", type=int, default=2)
 ap.add_argument("--no-decodes", action="store_true")
 ap.add_argument("--profile", default=None)
 ap.add_argument("--marks", default=None)
+ap.add_argument("--depth", default="8")
 ap.add_argument("--reps-profile", "--reps", dest="preps", type=int, default=5)
 args = ap.parse_args()
 
@@ -41,15 +44,30 @@ def parse(name):
     return name, int(mi), int(res), lst == "ordered"
 
 
+def legs(names, depths):
+    """Every setting at every depth: (NAME or NAME@depth, items, residency, ordered, depth). The deep planes need the ordered list."""
+    out = []
+    for s in names:
+        name, mi, res, ordered = parse(s)
+        for d in depths:
+            assert d == 8 or ordered, f"{name}: depth {d} needs an ordered setting"
+            out.append((name if d == 8 else f"{name}@{d}", mi, res, ordered, d))
+    return out
+
+
 def apply(setting):
-    _, mi, res, ordered = setting
+    global stem
+    _, mi, res, ordered, depth = setting
     fused.INCR_MAX_ITEM, fused.INCR_ORDERED = mi, ordered
     fused.set_incr_residency(res)
+    model.incremental_depth = depth
+    if stem is None or stem.lead + stem.deep != depth:
+        stem = fb.incremental_stem(B, L, depth)
 
 
 B, L, M, S = 256, 200, 10, 128
 reps = args.reps
-settings = [parse(s) for s in (args.profile or args.settings).split(",")]
+settings = legs((args.profile or args.settings).split(","), [int(d) for d in args.depth.split(",")])
 steps = [int(s) for s in args.steps.split(",")]
 model, emb, head, _ = synthetic.build("dna", "cuda:0")
 model.rng_mode, model.philox_seed = "philox", 0
@@ -63,20 +81,20 @@ states = [s.to("cuda:0").contiguous() for s in model.state_trace]
 model.state_trace = None
 fb = model._fused_backbone()
 pk = fb.ol_pack()
-stem = fb.incremental_stem(B, L)
+stem = None                                              # the carried state of the depth in hand (apply)
 out = torch.empty((B, L, 5), device="cuda:0")
 
 
 def marks(a, b, mi):
-    """Per layer k = 1 .. lead of the forward a -> b: marked tiles (the brute-force rule of tests/test_backbone_incremental_gpu.py:
-    tile T is marked iff a changed position lies within 4 + 4 k of one of its positions), items of at most mi tiles, and the tiles on
+    """Per carried layer k of the forward a -> b: marked tiles (the brute-force rule of tests/test_backbone_incremental_gpu.py:
+    tile T is marked iff a changed position lies within 4 + sum_{i<k} 4 dil[i] of one of its positions), items of at most mi tiles, and the tiles on
     the fullest of 256 CUs when the non-empty items are dealt to the CUs in turn, in (row, slot) order and largest first."""
     a, b = a.cpu().numpy(), b.cpu().numpy()
     lo = 16 * np.arange(13)
     hi = np.minimum(lo + 15, L - 1)
     res = []
-    for k in range(1, stem.lead + 1):
-        reach, sizes = 4 + 4 * k, []
+    for k in range(1, stem.lead + stem.deep + 1):
+        reach, sizes = 4 + 4 * sum(pk["dil"][:k]), []
         for r in range(a.shape[0]):
             c = np.nonzero(a[r] != b[r])[0]
             m = ((c[:, None] >= lo[None] - reach) & (c[:, None] <= hi[None] + reach)).any(0) & (lo <= L - 1)
@@ -127,8 +145,8 @@ def timed(fn, n=5):
 
 
 print("settings: " + " ; ".join(f"{n} = items <= {mi}, {'no LDS padding' if not res else f'{res} / CU'}, {'ordered' if o else 'slot'} list"
-                                for n, mi, res, o in settings))
-print(f"per step (us, median of 5): one launch | " + " | ".join(f"{s[0]:>6s}" for s in settings) + f" | marked share of {B * 13 * stem.lead} tile-layers")
+                                for n, mi, res, o, _ in settings))
+print(f"per step (us, median of 5): one launch | " + " | ".join(f"{s[0]:>6s}" for s in settings) + f" | marked share of the carried tile-layers")
 for i in steps:
     if i + 1 >= len(states):
         continue
@@ -152,7 +170,7 @@ for i in steps:
         assert torch.equal(out, ref), f"{st[0]}: the incremental forward differs from the one-launch kernel"
     changed = int((a != b).sum())
     print(f"step {i:3d} ({changed:4d} tokens changed): {one:7.1f} | " + " | ".join(f"{r:7.1f}" for r in res) +
-          f" | {int(stem.stat) / (B * 13 * stem.lead):.3f}")
+          f" | {int(stem.stat.sum()) / (B * 13 * (stem.lead + stem.deep)):.3f}")
 
 if args.no_decodes:
     sys.exit(0)
@@ -176,5 +194,7 @@ for rnd in range(args.rounds):
         sk, model.skip_stats = model.skip_stats, None
         share = (f" ; stem tile-layers {sk['backbone_stem_tile_layers'] / sk['backbone_stem_tile_layers_dense']:.3f} of the dense count"
                  if "backbone_stem_tile_layers" in sk else "")
+        if sk.get("backbone_deep_tile_layers_dense"):
+            share += f" ; deep {sk['backbone_deep_tile_layers'] / sk['backbone_deep_tile_layers_dense']:.3f}"
         print(f"round {rnd + 1} {'one launch (off)' if st is None else 'setting ' + st[0]:>16s}: {dt * 1e3:.1f} ms/decode = {B / dt:.1f} seq/s ; "
               f"backbone {bb[0]:.1f} ms in {bb[1]} forwards ({bb[0] / bb[1] * 1e3:.1f} us each){share}")
