@@ -707,6 +707,25 @@ int svdd_backbone_incr3_f32(const uint8_t* x, const float* table0, const float* 
                             float* out, int n, int L, int nlayers, const int* dilations, int lead, float* planes,
                             uint8_t* x_prev, int32_t* items, unsigned long long* stat, int first, int max_item,
                             int32_t* order, int32_t* order_count, int depth, void* on_stream);
+/* svdd_backbone_incr4_f32 — svdd_backbone_incr3_f32 (the SAME BITS in `out` and in every plane) with less work in the stem.
+ *   max_item is 2 (anything else: SVDD_E_ARG); S = 7 slots per (layer, row). Arguments as svdd_backbone_incr3_f32, and:
+ *   x_prev2 [n][L] u8, parity: the carried tokens are a ping-pong pair. parity (0 or 1) names the buffer that holds the tokens the
+ *   planes belong to, 0 = x_prev, 1 = x_prev2. first != 0 writes x into THAT buffer; first == 0 reads it and writes x into the other
+ *   one, so the next call passes parity ^ 1. (The list is built in ONE launch, one workgroup per carried layer, each reading the
+ *   tokens for itself: no workgroup reads what another writes.)
+ *   items of layers 1 .. lead are TIGHT: entry = origin row | tiles << 8 (origin 0 .. L - 1, any value; tiles >= 1, so the word is
+ *   never 0 for an item). Per (layer k, row): the rows within 4 + 4 k of a changed position form maximal runs [a, b]; a run is covered
+ *   by 16-row tiles at a, a + 16, .. ; a tile that reaches the next run's first row takes that run into the same cover; tiles are
+ *   disjoint, at most 13, and runs of adjacent tiles (origins 16 apart) are cut to max_item. If that needs more than 7 items (four
+ *   3-tile runs cut 2 + 1 each need 8) the (layer, row) takes svdd_backbone_incr3_f32's aligned tiles, as origins 16 T. The segment
+ *   launch of such a layer reads rows origin - 4 .. origin + 16 tiles + 3 of plane k - 1 and writes rows origin .. + 16 tiles - 1
+ *   (< L) of plane k. items of layers lead + 1 .. depth: as svdd_backbone_incr3_f32 (first tile | tiles << 8).
+ *   order / order_count: svdd_backbone_incr2_f32's contract over these items. stat[0] += the tiles cut for layers 1 .. lead (tight
+ *   ones, or aligned where the fallback fired), stat[1] += those of the deeper layers. */
+int svdd_backbone_incr4_f32(const uint8_t* x, const float* table0, const float* tiles, const float* vec, const float* w2,
+                            float* out, int n, int L, int nlayers, const int* dilations, int lead, float* planes,
+                            uint8_t* x_prev, int32_t* items, unsigned long long* stat, int first, int max_item,
+                            int32_t* order, int32_t* order_count, int depth, uint8_t* x_prev2, int parity, void* on_stream);
 int svdd_backbone_incr_set_residency(int wg_per_cu);
 /* svdd_backbone_set_workspace — caller-owned scratch for the small-batch form of svdd_backbone_cnn_f32 (several workgroups per
  * sequence exchange the LayerNorm'd image of every layer through it): ws = device memory of `bytes` >= n_max * (2 * 208 * 128 * 4

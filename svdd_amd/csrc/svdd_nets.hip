@@ -2335,6 +2335,182 @@ __global__ __launch_bounds__(256) void backbone_order_kernel(const int* __restri
   }
 }
 
+// The list of svdd_backbone_incr4_f32 in ONE launch: workgroup k - 1 builds layer k's items of every row straight from the tokens
+// (it compares 256 rows at a time, then thread t cuts row t's items in LDS) and then packs order[k - 1] as backbone_order_kernel
+// does, from the registers when n <= 256.
+// Every workgroup compares x with x_cur; workgroup 0 alone writes x into x_next, the OTHER buffer of the ping-pong pair, so no
+// workgroup reads what another writes.
+// Layers k <= rc.lead1 (dilation 1) get TIGHT items, origin row | tiles << 8: every maximal run [a, b] of rows within the reach of
+// a changed position is covered by 16-row tiles at a, a + 16, ..; a tile that reaches the next run's first row takes that run into
+// the same cover, so the tiles of a row are disjoint (at most 13, origins < L). Runs of adjacent tiles are cut to max_item as ever.
+// Tight cutting can need SEG_SLOTS + 1 items (four 3-tile runs cut 2 + 1 each): such a (layer, row) takes the aligned cover, as
+// origins 16 T. The deeper layers get backbone_worklist_kernel's aligned items, first tile | tiles << 8, unchanged. At dilation 1
+// no bit depends on the origin: every tap of every live tile runs in backbone_kernel's schedule, and an output row's accumulator
+// and a row's LayerNorm do not depend on which tile holds the row (the tight windows of the tower rest on the same fact).
+// stat[0] += the tiles cut for layers <= lead1, stat[1] += those of the deeper layers, one add per wave.
+__global__ __launch_bounds__(256) void backbone_list_kernel(const uint8_t* __restrict__ x, const uint8_t* __restrict__ x_cur,
+                                                            uint8_t* __restrict__ x_next, int n, int L, int max_item,
+                                                            int* __restrict__ items, int* __restrict__ order,
+                                                            int* __restrict__ order_count, unsigned long long* __restrict__ stat,
+                                                            BackboneReach rc) {
+  typedef unsigned long long u64;
+  __shared__ u64 chs[256][4];                             // bit p & 63 of chs[row][p >> 6]: position p of the chunk's row differs
+  __shared__ int its[256][SEG_SLOTS];                     // the chunk's items
+  __shared__ int wtot[4][4];                              // [wave][class]: class c holds the items of 4 - c tiles
+  __shared__ int base[4];                                 // where the class continues in order[k]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int reach = rc.r[blockIdx.x];
+  const bool tight = (int)blockIdx.x < rc.lead1, keep = blockIdx.x == 0;
+  int* itk = items + (size_t)blockIdx.x * n * SEG_SLOTS;
+  int* ord = order + (size_t)blockIdx.x * n * SEG_SLOTS;
+  const bool words = L % 8 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(x_cur) |
+                                     reinterpret_cast<uintptr_t>(x_next)) & 7) == 0;
+  // The compare, 256 rows at a time: lane (half, w8) of a wave takes positions 8 w8 .. + 7 of row 2 i + half, so one read of the
+  // wave is two whole rows, and all 64 reads of a lane are in flight together. The 8 bits go to LDS, where thread t then finds the
+  // 256 bits of row t. (A thread reading its own row word by word costs the CU 64 cache lines per instruction.)
+  unsigned char* chb = reinterpret_cast<unsigned char*>(chs);
+  const int half = lane >> 5, w8 = lane & 31;
+  int tiles = 0, item[SEG_SLOTS], cnt4[4] = {0, 0, 0, 0};
+  for (int r0 = 0; r0 < n; r0 += 256) {
+    if (words) {
+      u64 a[32], c[32];
+#pragma unroll
+      for (int i = 0; i < 32; ++i) {
+        const int rr = r0 + 64 * wave + 2 * i + half;
+        const bool in = rr < n && 8 * w8 < L;
+        const size_t at = in ? (size_t)rr * L + 8 * w8 : 0;
+        a[i] = *reinterpret_cast<const u64*>(x + at);
+        c[i] = *reinterpret_cast<const u64*>(x_cur + at);
+        if (!in) c[i] = a[i];
+      }
+#pragma unroll
+      for (int i = 0; i < 32; ++i) {
+        const int rl = 64 * wave + 2 * i + half;
+        if (keep && r0 + rl < n && 8 * w8 < L) *reinterpret_cast<u64*>(x_next + (size_t)(r0 + rl) * L + 8 * w8) = a[i];
+        const u64 d = a[i] ^ c[i];                        // -> bit e = byte e of d is not zero: high bit per non-zero byte, gathered by a multiply
+        const unsigned dl = (unsigned)d, dh = (unsigned)(d >> 32);
+        const unsigned zl = (((dl & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | dl) & 0x80808080u, zh = (((dh & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | dh) & 0x80808080u;
+        const unsigned m = ((zl >> 7) * 0x10204080u) >> 28 | (((zh >> 7) * 0x10204080u) >> 28) << 4;
+        chb[rl * 32 + w8] = (unsigned char)m;
+      }
+    } else {
+      for (int i = 0; i < 32; ++i) {
+        const int rl = 64 * wave + 2 * i + half, rr = r0 + rl;
+        unsigned m = 0;
+        if (rr < n)
+          for (int e = 0; e < 8 && 8 * w8 + e < L; ++e) {
+            const size_t at = (size_t)rr * L + 8 * w8 + e;
+            const uint8_t a = x[at];
+            if (keep) x_next[at] = a;
+            m |= (unsigned)(a != x_cur[at]) << e;
+          }
+        chb[rl * 32 + w8] = (unsigned char)m;
+      }
+    }
+    __syncthreads();
+    const int r = r0 + tid;
+    const u64 ch[4] = {chs[tid][0], chs[tid][1], chs[tid][2], chs[tid][3]};   // all zero for a row >= n
+    int* it = its[tid];
+    int cnt = 0, nt = 0;
+    if (tight) {
+      int cend = -1, io = 0, il = 0;                      // last row the cover holds ; the open item's origin and tiles
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        for (u64 b = ch[q]; b; b &= b - 1) {
+          const int p = 64 * q + __builtin_ctzll(b);
+          const int lo = max(0, p - reach), hi = min(L - 1, p + reach);
+          int o = lo > cend ? lo : cend + 1;              // a new run starts its own cover; a run the cover has reached continues it
+          for (; o <= hi; o += 16) {
+            ++nt;
+            if (il > 0 && il < max_item && o == io + 16 * il) { ++il; continue; }
+            if (il > 0) { if (cnt < SEG_SLOTS) it[cnt] = io | il << 8; ++cnt; }
+            io = o; il = 1;
+          }
+          cend = o - 1;
+        }
+      if (il > 0) { if (cnt < SEG_SLOTS) it[cnt] = io | il << 8; ++cnt; }
+    }
+    if (!tight || cnt > SEG_SLOTS) {                      // aligned tiles: backbone_worklist_kernel's mask and cut
+      int m = 0;
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        for (u64 b = ch[q]; b; b &= b - 1) {
+          const int p = 64 * q + __builtin_ctzll(b);
+          const int tlo = max(0, p - reach) >> 4, thi = min(L - 1, p + reach) >> 4;
+          m |= ((2 << thi) - 1) & ~((1 << tlo) - 1);
+        }
+      cnt = 0; nt = __popc(m);
+      for (int t = 0; t < TW_RT;) {
+        if (!(m >> t & 1)) { ++t; continue; }
+        int len = 1;
+        while (len < max_item && t + len < TW_RT && (m >> (t + len) & 1)) ++len;
+        it[cnt++] = (tight ? 16 * t : t) | len << 8;
+        t += len;
+      }
+    }
+    for (; cnt < SEG_SLOTS; ++cnt) it[cnt] = 0;
+    tiles += nt;
+#pragma unroll
+    for (int s = 0; s < SEG_SLOTS; ++s) {                 // the thread's own slots back into registers, and out
+      item[s] = its[tid][s];
+      if (r < n) itk[(size_t)r * SEG_SLOTS + s] = item[s];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) cnt4[c] += (item[s] >> 8) == 4 - c;
+    }
+    __syncthreads();                                      // (the next 256 rows overwrite chs)
+  }
+  if (stat) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) tiles += __shfl_xor(tiles, off, 64);
+    if (lane == 0 && tiles) atomicAdd(stat + (tight ? 0 : 1), (unsigned long long)tiles);
+  }
+  // ---- order[k], as backbone_order_kernel packs it: the class totals, then a block scan per class over 256 rows at a time
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    int v = cnt4[c];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    if (lane == 0) wtot[wave][c] = v;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int run = 0;
+    for (int c = 0; c < 4; ++c) { base[c] = run; run += wtot[0][c] + wtot[1][c] + wtot[2][c] + wtot[3][c]; }
+    order_count[blockIdx.x] = run;
+  }
+  __syncthreads();
+  for (int r0 = 0; r0 < n; r0 += 256) {
+    const int r = r0 + tid;
+    int pos[4], cl[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int s = 0; s < SEG_SLOTS; ++s) {
+      if (n > 256) item[s] = r < n ? itk[(size_t)r * SEG_SLOTS + s] : 0;   // one chunk: the registers still hold it
+#pragma unroll
+      for (int c = 0; c < 4; ++c) cl[c] += (item[s] >> 8) == 4 - c;
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {                         // inclusive scan inside the wave, wave totals through LDS
+      int v = cl[c];
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) { const int u = __shfl_up(v, off, 64); if (lane >= off) v += u; }
+      pos[c] = v - cl[c];
+      if (lane == 63) wtot[wave][c] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      int at = base[c] + pos[c];
+      for (int q = 0; q < wave; ++q) at += wtot[q][c];
+#pragma unroll
+      for (int s = 0; s < SEG_SLOTS; ++s)
+        if ((item[s] >> 8) == 4 - c) ord[at++] = r << 16 | item[s];
+    }
+    __syncthreads();
+    if (tid < 4) base[tid] += wtot[0][tid] + wtot[1][tid] + wtot[2][tid] + wtot[3][tid];
+    __syncthreads();
+  }
+}
+
 // NC = the most own tiles an item may have (2 / 4); 4 waves, wave cg owns 32 output channels of EVERY tile of the item (slots
 // 0 .. NC + 1 = halo, own tiles, halo), so a weight fragment feeds up to NC row tiles and the register arrays are sized to the item.
 // ORD: workgroup b takes entry b of the layer's size-ordered list (svdd_backbone_incr2_f32) instead of slot b of `items`; NC = 1
@@ -2596,6 +2772,232 @@ __global__ __launch_bounds__(256, NC == 4 ? 2 : NC == 1 ? 4 : 3) void backbone_s
       }
   }
 #undef SEG_LIVE
+}
+
+// backbone_seg_kernel<2, true, 1> for the TIGHT items of svdd_backbone_incr4_f32 (origin row | tiles << 8, any origin), with the
+// halo packed: a dilation-1 item reads 4 rows beyond its tiles on each side, so the image is rows origin - 4 .. origin + 16 nown + 3
+// (40 rows for two tiles where the aligned kernel holds 64) and the register arrays have THREE slots, not four: slots 0, 1 = the own
+// tiles (image rows 4 + 16 s + 4 g + e), slot 2 = both halos — the lanes with g = 0 hold the left one (image rows 0 .. 3), those
+// with g = 1 the right one (image rows 16 nown + 4 .. + 7), those with g = 2, 3 nothing (they neither load nor store; the VALU runs
+// them along). A row's LayerNorm sums over the 16 lanes of one g and the four waves, so it is the same tree whichever slot holds the
+// row. Everything else is backbone_seg_kernel's, line for line: lane-to-column ownership, (p0 + p1) + (p2 + p3), rsqrtf, the
+// accumulator starting at the bias, chunk outer / tap inner / 8 k-steps, a zero image row for a tap that leaves the sequence,
+// layer 1 through the image with the batched, clamped, select-not-add table reads, row < L on the plane stores.
+__global__ __launch_bounds__(256, 5) void backbone_seg_tight_kernel(BackboneSegArgs a) {
+  constexpr int NC = 2, NS = NC + 1, PK = NC, ROWS = 16 * NC + 8;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* img = smem;                                      // [ROWS][BB_AP] image row i = sequence row origin - 4 + i
+  float* psum = img + ROWS * BB_AP;                       // [4][ROWS]
+  float* rstat = psum + 4 * ROWS;                         // [ROWS]
+  int* toks = reinterpret_cast<int*>(rstat + ROWS);       // [ROWS + 8] tokens of sequence rows origin - 8 ..   (layer 1)
+
+  if ((int)blockIdx.x >= a.order_count[a.layer - 1]) return;
+  const unsigned ent = (unsigned)__builtin_amdgcn_readfirstlane(a.order[(size_t)(a.layer - 1) * a.order_stride + blockIdx.x]);
+  const int item = (int)(ent & 0xFFFFu), seq = (int)(ent >> 16);
+  const int nown = min(item >> 8, NC);
+  if (nown == 0) return;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int cg = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int j = lane & 15, g = lane >> 4;
+  const int col0 = 32 * cg + j;
+  const int L = a.L;
+  const int r0 = (item & 255) - 4;                        // sequence row of image row 0
+  const int nrows = 16 * nown + 8;                        // image rows the item uses
+  const bool halo = g < 2;                                // this lane holds rows of the packed slot
+  const int hrow = g == 1 ? 16 * nown + 4 : 0;            // ... from this image row on
+  const size_t pl_stride = (size_t)a.n * TW_ROWS * BB_C;
+  float* pl0 = a.planes + (size_t)seq * TW_ROWS * BB_C;
+  const int cl = a.layer - 1;                             // the conv layer this launch runs
+#define SGT_LIVE(S) ((S) < nown || (S) == PK)
+#define SGT_MINE(S) ((S) < PK || halo)
+#define SGT_IROW(S) ((S) < PK ? 4 + 16 * (S) + 4 * g : hrow)
+
+  f32x4 f[NS][2], acc[NS][2];
+  if (a.layer == 1) {
+    for (int e = tid; e < nrows + 8; e += 256) {
+      const int p = r0 - 4 + e;
+      toks[e] = (p >= 0 && p < L) ? (int)a.x[(size_t)seq * L + p] : -1;
+    }
+    __syncthreads();
+    {                                                     // f_0 of the item's rows through the image (see backbone_seg_kernel)
+      const int c = tid & (BB_C - 1);
+      const float b0 = a.vec[c];
+#pragma unroll 4
+      for (int ri = tid >> 7; ri < nrows; ri += 2) {
+        int tk[9];
+        float tv[9];
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+          tk[t] = toks[ri + t];                           // sequence row r0 + ri + t - 4 ; -1 outside the sequence
+          tv[t] = a.table0[(unsigned)((t * 5 + max(tk[t], 0)) * BB_C + c)];
+        }
+        float v = b0;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) v = tk[t] >= 0 ? v + tv[t] : v;
+        const int row = r0 + ri;
+        img[ri * BB_AP + c] = (row >= 0 && row < L) ? fmaxf(v, 0.0f) : 0.0f;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      if (!SGT_LIVE(s)) continue;
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) f[s][ct][e] = SGT_MINE(s) ? img[(SGT_IROW(s) + e) * BB_AP + col0 + 16 * ct] : 0.0f;
+    }
+  } else {
+    const float* src = pl0 + (size_t)(a.layer - 2) * pl_stride;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      if (!SGT_LIVE(s)) continue;
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int row = r0 + SGT_IROW(s) + e;
+          f[s][ct][e] = (SGT_MINE(s) && row >= 0 && row < L) ? src[row * BB_C + col0 + 16 * ct] : 0.0f;
+        }
+    }
+  }
+
+  // ---- LayerNorm(f + tb) of the item's tiles and its halo rows -> image
+  const float* vl = a.vec + (size_t)(cl + 1) * 4 * BB_C;
+  {
+    const float tb0 = vl[BB_C + col0], tb1 = vl[BB_C + col0 + 16];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      if (!SGT_LIVE(s)) continue;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float sm = group16_sum((f[s][0][e] + tb0) + (f[s][1][e] + tb1));
+        if (j == 0 && SGT_MINE(s)) psum[cg * ROWS + SGT_IROW(s) + e] = sm;
+      }
+    }
+    __syncthreads();
+    if (tid < nrows)
+      rstat[tid] = ((psum[tid] + psum[ROWS + tid]) + (psum[2 * ROWS + tid] + psum[3 * ROWS + tid])) * (1.0f / BB_C);
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      if (!SGT_LIVE(s)) continue;
+      const float4 cur4 = *reinterpret_cast<const float4*>(rstat + SGT_IROW(s));
+      const float mean4[4] = {cur4.x, cur4.y, cur4.z, cur4.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float mean = mean4[e];
+        const float d0 = f[s][0][e] + tb0 - mean, d1 = f[s][1][e] + tb1 - mean;
+        acc[s][0][e] = d0; acc[s][1][e] = d1;
+        const float sq = group16_sum(d0 * d0 + d1 * d1);
+        if (j == 0 && SGT_MINE(s)) psum[cg * ROWS + SGT_IROW(s) + e] = sq;
+      }
+    }
+    __syncthreads();
+    if (tid < nrows)
+      rstat[tid] = rsqrtf(((psum[tid] + psum[ROWS + tid]) + (psum[2 * ROWS + tid] + psum[3 * ROWS + tid])) * (1.0f / BB_C) + 1e-5f);
+    __syncthreads();
+    const float gm0 = vl[2 * BB_C + col0], gm1 = vl[2 * BB_C + col0 + 16];
+    const float bt0 = vl[3 * BB_C + col0], bt1 = vl[3 * BB_C + col0 + 16];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      if (!SGT_LIVE(s)) continue;
+      const float4 cur4 = *reinterpret_cast<const float4*>(rstat + SGT_IROW(s));
+      const float rs4[4] = {cur4.x, cur4.y, cur4.z, cur4.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int ri = SGT_IROW(s) + e, row = r0 + ri;
+        const float rs = rs4[e];
+        const bool in = row >= 0 && row < L;              // rows outside the sequence are the zero padding of the convolution
+        if (SGT_MINE(s)) {
+          img[ri * BB_AP + col0] = in ? acc[s][0][e] * rs * gm0 + bt0 : 0.0f;
+          img[ri * BB_AP + col0 + 16] = in ? acc[s][1][e] * rs * gm1 + bt1 : 0.0f;
+        }
+      }
+    }
+  }
+
+  // ---- the convolution of the own tiles: output row j of tile c reads image rows 16 c + j + t, t = 0 .. 8
+  const float bl0 = vl[col0], bl1 = vl[col0 + 16];
+  f32x4 cacc[NC][2];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) { cacc[c][0] = f32x4{bl0, bl0, bl0, bl0}; cacc[c][1] = f32x4{bl1, bl1, bl1, bl1}; }
+  typedef __attribute__((address_space(3))) f32x4 LdsF4;
+  const int img_lds = (int)(unsigned)(size_t)(const __attribute__((address_space(3))) float*)img;
+  const int arow0 = img_lds + (j * BB_AP + 8 * g) * 4;    // LDS byte address of (image row j, col 8 g)
+  const float* wsrc = a.tiles + (size_t)cl * 36 * BB_C * CH + col0 * CH + 8 * g;
+  const int live = (1 << nown) - 1;
+  float4 bA[4], bB[4];
+  bA[0] = *reinterpret_cast<const float4*>(wsrc);
+  bA[1] = *reinterpret_cast<const float4*>(wsrc + 4);
+  bA[2] = *reinterpret_cast<const float4*>(wsrc + 16 * CH);
+  bA[3] = *reinterpret_cast<const float4*>(wsrc + 16 * CH + 4);
+  bB[0] = bA[0]; bB[1] = bA[1]; bB[2] = bA[2]; bB[3] = bA[3];
+  __syncthreads();                                        // the image is complete
+#define SGT_DBYTES(IT) (((IT) % 9) * (BB_AP * 4) + ((IT) / 9) * (CH * 4))
+#define SGT_ALOAD(C, V, DBYTES)                                                                              \
+      { const LdsF4* ap_ = reinterpret_cast<const LdsF4*>(arow0 + (DBYTES) + (C) * (16 * BB_AP * 4));         \
+        const f32x4 t0_ = ap_[0], t1_ = ap_[1];                                                              \
+        V[0] = make_float4(t0_[0], t0_[1], t0_[2], t0_[3]); V[1] = make_float4(t1_[0], t1_[1], t1_[2], t1_[3]); }
+#define SGT_MM(C, U)                                                                                         \
+      __builtin_amdgcn_sched_barrier(0);                                                                     \
+      __builtin_amdgcn_s_waitcnt(0xC07F | (2 << 8));      /* at most the two reads of the other fragment set in flight */ \
+      if (live & (1 << (C))) {                                                                               \
+        _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                                      \
+          cacc[C][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].x, bf0[4 * q], cacc[C][0], 0, 0, 0);        \
+          cacc[C][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].x, bf1[4 * q], cacc[C][1], 0, 0, 0);        \
+          cacc[C][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].y, bf0[4 * q + 1], cacc[C][0], 0, 0, 0);    \
+          cacc[C][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].y, bf1[4 * q + 1], cacc[C][1], 0, 0, 0);    \
+          cacc[C][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].z, bf0[4 * q + 2], cacc[C][0], 0, 0, 0);    \
+          cacc[C][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].z, bf1[4 * q + 2], cacc[C][1], 0, 0, 0);    \
+          cacc[C][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].w, bf0[4 * q + 3], cacc[C][0], 0, 0, 0);    \
+          cacc[C][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].w, bf1[4 * q + 3], cacc[C][1], 0, 0, 0);    \
+        }                                                                                                    \
+      }                                                                                                      \
+      __builtin_amdgcn_sched_barrier(0);
+#define SGT_ENTRY(BC, BN)                                                                                    \
+    { const int nxt = it + 1 < 36 ? it + 1 : it;                                                             \
+      const float bf0[8] = {BC[0].x, BC[0].y, BC[0].z, BC[0].w, BC[1].x, BC[1].y, BC[1].z, BC[1].w};         \
+      const float bf1[8] = {BC[2].x, BC[2].y, BC[2].z, BC[2].w, BC[3].x, BC[3].y, BC[3].z, BC[3].w};         \
+      { const float* src = wsrc + (size_t)nxt * BB_C * CH;                                                   \
+        BN[0] = *reinterpret_cast<const float4*>(src);                                                       \
+        BN[1] = *reinterpret_cast<const float4*>(src + 4);                                                   \
+        BN[2] = *reinterpret_cast<const float4*>(src + 16 * CH);                                             \
+        BN[3] = *reinterpret_cast<const float4*>(src + 16 * CH + 4);                                         \
+      }                                                                                                      \
+      const int dbytes2 = SGT_DBYTES(nxt);                                                                   \
+      SGT_MM(0, ua)                                                                                          \
+      SGT_ALOAD(0, ua, dbytes2)                                                                              \
+      SGT_MM(1, ub)                                                                                          \
+      SGT_ALOAD(1, ub, dbytes2)                                                                              \
+      ++it; }
+  float4 ua[2], ub[2];
+  SGT_ALOAD(0, ua, SGT_DBYTES(0))
+  SGT_ALOAD(1, ub, SGT_DBYTES(0))
+  for (int it = 0; it < 36;) {
+    SGT_ENTRY(bA, bB)
+    SGT_ENTRY(bB, bA)
+  }
+#undef SGT_ENTRY
+#undef SGT_MM
+#undef SGT_ALOAD
+#undef SGT_DBYTES
+
+  float* dst = pl0 + (size_t)cl * pl_stride;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    if (c >= nown) continue;
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int row = r0 + 4 + 16 * c + 4 * g + e;
+        if (row < L) dst[row * BB_C + col0 + 16 * ct] = fmaxf(cacc[c][ct][e], 0.0f) + f[c][ct][e];   // relu(conv + b) + f
+      }
+  }
+#undef SGT_LIVE
+#undef SGT_MINE
+#undef SGT_IROW
 }
 
 // ------------------------------------------- gradient of the backbone with respect to its one-hot input, ONE launch (round 5) ----
@@ -3759,6 +4161,57 @@ extern "C" int svdd_backbone_incr3_f32(const uint8_t* x, const float* table0, co
   for (int k = 1; k <= depth; ++k) {
     sa.layer = k;
     if (svdd_launch(k <= lead ? seg1 : seg4, sgrid, dim3(256), slds, stream, sa) != SVDD_OK) return SVDD_E_LAUNCH;
+  }
+  return svdd_launch_timed(span.last(), backbone_kernel<true, false, 2>, dim3((unsigned)n), dim3(512), lds, stream, a, BackboneSave{});
+}
+
+// svdd_backbone_incr4_f32: svdd_backbone_incr3_f32 with the stem doing less. ONE list launch (backbone_list_kernel) instead of work
+// list + order; the dilation-1 layers run TIGHT items (tiles that start at the first row a change reaches, not at a multiple of 16)
+// on backbone_seg_tight_kernel, whose image holds the 4 halo rows per side instead of a halo tile; the dilation-4 layers keep their
+// aligned items and backbone_seg_kernel<2, true, 4>. The carried tokens are a ping-pong pair, so the list launch never reads what
+// it writes: `parity` names the buffer that holds them (0: x_prev, 1: x_prev2); a first == 0 call writes x into the other one.
+extern "C" int svdd_backbone_incr4_f32(const uint8_t* x, const float* table0, const float* tiles, const float* vec, const float* w2,
+                                       float* out, int n, int L, int nlayers, const int* dilations, int lead, float* planes,
+                                       uint8_t* x_prev, int32_t* items, unsigned long long* stat, int first, int max_item,
+                                       int32_t* order, int32_t* order_count, int depth, uint8_t* x_prev2, int parity,
+                                       void* on_stream) {
+  if (!x || !table0 || !tiles || !vec || !w2 || !out || !dilations || !planes || !x_prev || !items || !order || !order_count ||
+      !x_prev2 || x_prev2 == x_prev || n <= 0 || n > 65536 || L <= TW_ROWS / 2 || L > TW_ROWS || nlayers <= 0 || nlayers > BB_MAXL ||
+      lead < 2 || lead > nlayers || max_item != 2 || depth < lead || depth > nlayers || (parity != 0 && parity != 1))
+    return SVDD_E_ARG;
+  for (int i = 0; i < depth; ++i) if (dilations[i] != (i < lead ? 1 : 4)) return SVDD_E_ARG;
+  BackboneArgs a;
+  if (!backbone_args(a, x, table0, tiles, vec, w2, out, n, L, 1, nlayers, dilations)) return SVDD_E_ARG;
+  a.planes = planes; a.planes_P = depth;
+  hipStream_t stream = (hipStream_t)on_stream;
+  uint8_t* x_cur = parity ? x_prev2 : x_prev;
+  uint8_t* x_next = parity ? x_prev : x_prev2;
+  const SvddLds lds = svdd_lds_raised(backbone_lds_bytes(nlayers, 3));
+  SvddSpan span(SVDD_SLOT_BACKBONE);                      // ONE span per forward over all its launches
+  if (first) {
+    if (hipMemcpyAsync(x_cur, x, (size_t)n * L, hipMemcpyDeviceToDevice, stream) != hipSuccess) return SVDD_E_LAUNCH;
+    return svdd_launch_timed(span.all(), backbone_kernel<true, false, 1>, dim3((unsigned)n), dim3(512), lds, stream, a, BackboneSave{});
+  }
+  if (svdd_launch_timed(span.first(), backbone_list_kernel, dim3((unsigned)depth), dim3(256), 0, stream, x, (const uint8_t*)x_cur, x_next, n,
+                        L, max_item, items, order, order_count, stat, backbone_reach(dilations, depth, lead)) != SVDD_OK)
+    return SVDD_E_LAUNCH;
+  BackboneSegArgs sa{x, table0, tiles, vec, planes, items, n, L, 0, order, order_count, n * SEG_SLOTS};
+  const int rows1 = 16 * max_item + 8, rows4 = 16 * (max_item + 2);
+  size_t slds1 = sizeof(float) * ((size_t)rows1 * BB_AP + 5 * (size_t)rows1 + rows1 + 8);
+  size_t slds4 = sizeof(float) * ((size_t)rows4 * BB_AP + 5 * (size_t)rows4 + rows4 + 8);
+  if (g_incr_residency > 0) {
+    const size_t pad = (CU_LDS_BYTES / (size_t)(g_incr_residency + 1) / 1024 + 1) * 1024;
+    if (pad > slds1) slds1 = pad;
+    if (pad > slds4) slds4 = pad;
+  }
+  const dim3 sgrid((unsigned)(n * SEG_SLOTS));
+  void (*seg1)(BackboneSegArgs) = backbone_seg_tight_kernel;
+  void (*seg4)(BackboneSegArgs) = backbone_seg_kernel<2, true, 4>;
+  svdd_raise_lds_limit(seg1, slds1);
+  if (depth > lead) svdd_raise_lds_limit(seg4, slds4);
+  for (int k = 1; k <= depth; ++k) {
+    sa.layer = k;
+    if (svdd_launch(k <= lead ? seg1 : seg4, sgrid, dim3(256), k <= lead ? slds1 : slds4, stream, sa) != SVDD_OK) return SVDD_E_LAUNCH;
   }
   return svdd_launch_timed(span.last(), backbone_kernel<true, false, 2>, dim3((unsigned)n), dim3(512), lds, stream, a, BackboneSave{});
 }

@@ -69,6 +69,10 @@ Engine knobs (attributes; defaults reproduce the reference's observable behaviou
                    rows there), or "auto" (default) = fused.INCR_DEPTH_AUTO, the depth the measurement of
                    profiles/deep_planes_depth.txt picked. The environment variable SVDD_INCR_DEPTH sets the value every new model
                    starts with (A/B runs). Same bits at every depth (tests/test_backbone_incr3_gpu.py).
+  incremental_items  "tight" (default): the dilation-1 layers of the incremental backbone recompute 16-row tiles that start at the first
+                   row a changed token reaches, with a 4-row halo, and the step's work list is built in one launch
+                   (svdd_backbone_incr4_f32); "aligned": tiles at multiples of 16 (svdd_backbone_incr3_f32). The environment variable
+                   SVDD_INCR_ITEMS sets the value every new model starts with (A/B runs). Same bits (tests/test_backbone_incr4_gpu.py).
   dedup_prior      True (default): every row of the prior x_T is the same all-MASK row (_sample_prior, :751-753), and with the hand-written
                    kernels a row's net output does not depend on the batch around it — so the FIRST backbone forward of a decode, the
                    parents' first value / reward score and their first tower pass run on one row and are broadcast. Bit-identical to
@@ -272,6 +276,7 @@ class Diffusion(nn.Module):
         self.logits_cache = "auto"
         self.incremental_backbone = "auto"
         self.incremental_depth = os.environ.get("SVDD_INCR_DEPTH") or "auto"   # carried layers of the incremental backbone (see the module docstring)
+        self.incremental_items = os.environ.get("SVDD_INCR_ITEMS") or "tight"  # "tight" / "aligned" tiles in its dilation-1 layers
         self.skip_stats = None
         self.skip_generic = False
         self.trace = None          # set to a list to record (logits, scores) of every step (tests / smoke)
@@ -1737,7 +1742,9 @@ class Diffusion(nn.Module):
         fb = self._fused_backbone_or_none(L)
         if fb is None or not fb.incremental_ok(B, L, any_batch=self.incremental_backbone == "on"):
             return None, None
-        return fb, fb.incremental_stem(B, L, self._incremental_depth(fb))
+        if self.incremental_items not in ("tight", "aligned"):
+            raise ValueError(f"incremental_items = {self.incremental_items!r}: expected 'tight' or 'aligned'")
+        return fb, fb.incremental_stem(B, L, self._incremental_depth(fb), tight=self.incremental_items == "tight")
 
     def _incremental_depth(self, fb):
         """incremental_depth as a number of carried layers of fb: "auto" = INCR_DEPTH_AUTO, held to what the backbone's dilations allow."""

@@ -450,13 +450,17 @@ class IncrementalStem:
     `lead` dilation-1 layers and `deep` dilation-4 layers behind them), the tokens they belong to, the step's work list, its
     size-ordered form (order, order_count) and the device counters of marked tile-layers (stat[0]: the dilation-1 layers, stat[1]: the
     deeper ones). Allocated once and reused across decodes (FusedBackbone keeps one per shape); `valid` says whether planes / x_prev
-    describe the tokens of the last forward of THIS decode."""
+    describe the tokens of the last forward of THIS decode. tight: forwards go through svdd_backbone_incr4_f32 (tight items for the
+    dilation-1 layers, the list in one launch), which keeps the tokens in the pair (x_prev, x_prev2); `parity` says which of the two
+    holds them."""
 
-    def __init__(self, n, L, lead, dev, deep=0):
-        self.n, self.L, self.lead, self.deep = n, L, lead, deep
+    def __init__(self, n, L, lead, dev, deep=0, tight=False):
+        self.n, self.L, self.lead, self.deep, self.tight = n, L, lead, deep, tight
         depth = lead + deep
         self.planes = torch.empty((depth, n, 208, 128), dtype=torch.float32, device=dev)
         self.x_prev = torch.empty((n, L), dtype=torch.uint8, device=dev)
+        self.x_prev2 = torch.empty((n, L), dtype=torch.uint8, device=dev)
+        self.parity = 0
         self.items = torch.zeros((depth, n, INCR_SLOTS), dtype=torch.int32, device=dev)     # read as [depth][n][7] for items <= 2 / 4
         self.order = torch.zeros((depth, n * INCR_SLOTS), dtype=torch.int32, device=dev)
         self.order_count = torch.zeros(depth, dtype=torch.int32, device=dev)
@@ -468,7 +472,8 @@ class IncrementalStem:
 def backbone_cnn_incremental(tokens, pk, st, out=None, max_item=None):
     """backbone_cnn(tokens, pk) — the same bits — through the carried stem `st` (HIP entry svdd_backbone_incr2_f32; with st.deep > 0
     svdd_backbone_incr3_f32): the first call after st.valid = False runs the whole forward and fills the planes, every later one
-    recomputes only the tiles of the carried layers that a changed token can reach, then the remaining layers from the last plane."""
+    recomputes only the tiles of the carried layers that a changed token can reach, then the remaining layers from the last plane.
+    With st.tight (and items of 2 tiles) the entry is svdd_backbone_incr4_f32."""
     assert tokens.is_cuda and tokens.dtype == torch.uint8 and tokens.is_contiguous() and tuple(tokens.shape) == (st.n, st.L)
     n, L = tokens.shape
     if out is None:
@@ -476,7 +481,12 @@ def backbone_cnn_incremental(tokens, pk, st, out=None, max_item=None):
     dil = (ctypes.c_int * len(pk["dil"]))(*pk["dil"])
     first = not st.valid
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)        # these entries take their stream as an explicit argument
-    if st.deep > 0:
+    if st.tight and int(max_item or INCR_MAX_ITEM) == 2:
+        _lib.call("svdd_backbone_incr4_f32", tokens, pk["table0"], pk["tiles"], pk["vec"], pk["w2"], out, n, L, len(pk["dil"]), dil,
+                  st.lead, st.planes, st.x_prev, st.items, st.stat, int(first), 2, st.order, st.order_count, st.lead + st.deep,
+                  st.x_prev2, st.parity, stream)
+        st.parity ^= 0 if first else 1                   # an incremental forward leaves the tokens in the other buffer
+    elif st.deep > 0:
         _lib.call("svdd_backbone_incr3_f32", tokens, pk["table0"], pk["tiles"], pk["vec"], pk["w2"], out, n, L, len(pk["dil"]), dil,
                   st.lead, st.planes, st.x_prev, st.items, st.stat, int(first), int(max_item or INCR_MAX_ITEM), st.order,
                   st.order_count, st.lead + st.deep, stream)
@@ -1245,9 +1255,9 @@ class FusedBackbone(nn.Module):
         return (self.kernel_ok(L) and self.precision == "f32" and 104 < L <= 208 and leading_dilation1(self.ol_dil) >= 2 and
                 (any_batch or (n > BB_SPLIT_MAX_SEQ and not 0 < n % 256 <= BB_SPLIT_MAX_SEQ)))
 
-    def incremental_stem(self, n, L, depth=None):
+    def incremental_stem(self, n, L, depth=None, tight=False):
         """The resident IncrementalStem for [n, L] on this module's device, marked stale (a new decode starts). depth: carried layers,
-        from leading_dilation1 (None: that) up to the end of the dilation-4 run behind them."""
+        from leading_dilation1 (None: that) up to the end of the dilation-4 run behind them. tight: see IncrementalStem."""
         lead = leading_dilation1(self.ol_dil)
         deep = 0 if depth is None else int(depth) - lead
         if not 0 <= deep <= following_dilation4(self.ol_dil):
@@ -1257,7 +1267,7 @@ class FusedBackbone(nn.Module):
         if st is None:
             self._incr.clear()                          # one shape at a time: the planes are ~0.1 MB per sequence and carried layer
             st = self._incr[key] = IncrementalStem(n, L, lead, self.ol_tiles.device, deep)
-        st.valid = False
+        st.valid, st.tight = False, bool(tight)
         return st
 
     def forward_incremental(self, tok, st, out=None):

@@ -8,8 +8,9 @@ L = 200, M = 10, 128 steps, fp32), in one process.
      and the backbone's profile slot.
 A setting is NAME or items:residency:list — items = most row tiles per work item (1, 2, 4); residency = segment workgroups per CU
 (0 = no LDS padding: 4 for items <= 2, 6 for 1-tile items, 3 for <= 4); list = slot (the old entry, one workgroup per (row, slot))
-or ordered (the compact list, most tiles first). Names: today = 2:0:slot, today4 = 4:0:slot, A = 2:0:ordered, A3 = 2:3:ordered,
-B = 2:2:ordered, C = 1:3:ordered, D = 1:4:ordered, E = 1:0:ordered.
+ordered (the compact list, most tiles first) or tight (svdd_backbone_incr4_f32: the ordered list built in one launch by
+backbone_list_kernel, tight items on backbone_seg_tight_kernel in the dilation-1 layers; items = 2). Names: today = 2:0:slot,
+today4 = 4:0:slot, A = 2:0:ordered, A3 = 2:3:ordered, B = 2:2:ordered, C = 1:3:ordered, D = 1:4:ordered, E = 1:0:ordered, T = 2:0:tight.
 --depth 8,10,12: the carried layers (Diffusion.incremental_depth; 8 = the dilation-1 layers, up to 12 = through the dilation-4 layers,
 svdd_backbone_incr3_f32); every setting runs at every depth given, as NAME@depth. Default: 8.
 Usage: python tools/incremental_backbone_ab.py [decodes per leg, default 3] [--settings today,A,A3,B,C,D,E] [--steps 1,8,32,...]
@@ -24,7 +25,7 @@ import torch
 from svdd_amd import _lib, fused, synthetic
 
 NAMED = {"today": "2:0:slot", "today4": "4:0:slot", "A": "2:0:ordered", "A3": "2:3:ordered", "B": "2:2:ordered", "C": "1:3:ordered",
-         "D": "1:4:ordered", "E": "1:0:ordered"}
+         "D": "1:4:ordered", "E": "1:0:ordered", "T": "2:0:tight"}
 ap = argparse.ArgumentParser()
 ap.add_argument("reps", nargs="?", type=int, default=3)
 ap.add_argument("--settings", default="today,A,A3,B,C,D,E")
@@ -40,29 +41,30 @@ args = ap.parse_args()
 
 def parse(name):
     mi, res, lst = NAMED.get(name, name).split(":")
-    assert int(mi) in (1, 2, 4) and lst in ("slot", "ordered") and (lst == "ordered" or (int(mi) != 1 and int(res) == 0)), name
-    return name, int(mi), int(res), lst == "ordered"
+    assert int(mi) in (1, 2, 4) and lst in ("slot", "ordered", "tight") and (lst != "slot" or (int(mi) != 1 and int(res) == 0)), name
+    assert lst != "tight" or int(mi) == 2, name
+    return name, int(mi), int(res), lst != "slot", lst == "tight"
 
 
 def legs(names, depths):
-    """Every setting at every depth: (NAME or NAME@depth, items, residency, ordered, depth). The deep planes need the ordered list."""
+    """Every setting at every depth: (NAME or NAME@depth, items, residency, ordered, depth, tight). The deep planes need the ordered list."""
     out = []
     for s in names:
-        name, mi, res, ordered = parse(s)
+        name, mi, res, ordered, tight = parse(s)
         for d in depths:
             assert d == 8 or ordered, f"{name}: depth {d} needs an ordered setting"
-            out.append((name if d == 8 else f"{name}@{d}", mi, res, ordered, d))
+            out.append((name if d == 8 else f"{name}@{d}", mi, res, ordered, d, tight))
     return out
 
 
 def apply(setting):
     global stem
-    _, mi, res, ordered, depth = setting
+    _, mi, res, ordered, depth, tight = setting
     fused.INCR_MAX_ITEM, fused.INCR_ORDERED = mi, ordered
     fused.set_incr_residency(res)
-    model.incremental_depth = depth
-    if stem is None or stem.lead + stem.deep != depth:
-        stem = fb.incremental_stem(B, L, depth)
+    model.incremental_depth, model.incremental_items = depth, "tight" if tight else "aligned"
+    if stem is None or stem.lead + stem.deep != depth or stem.tight != tight:
+        stem = fb.incremental_stem(B, L, depth, tight=tight)
 
 
 B, L, M, S = 256, 200, 10, 128
@@ -85,10 +87,13 @@ stem = None                                              # the carried state of 
 out = torch.empty((B, L, 5), device="cuda:0")
 
 
-def marks(a, b, mi):
+def marks(a, b, mi, tight=False):
     """Per carried layer k of the forward a -> b: marked tiles (the brute-force rule of tests/test_backbone_incremental_gpu.py:
     tile T is marked iff a changed position lies within 4 + sum_{i<k} 4 dil[i] of one of its positions), items of at most mi tiles, and the tiles on
-    the fullest of 256 CUs when the non-empty items are dealt to the CUs in turn, in (row, slot) order and largest first."""
+    the fullest of 256 CUs when the non-empty items are dealt to the CUs in turn, in (row, slot) order and largest first. tight: the
+    dilation-1 layers hold the tight items of svdd_backbone_incr4_f32 instead (tests/incr4_ref.py)."""
+    if tight:
+        from tests import incr4_ref
     a, b = a.cpu().numpy(), b.cpu().numpy()
     lo = 16 * np.arange(13)
     hi = np.minimum(lo + 15, L - 1)
@@ -97,6 +102,9 @@ def marks(a, b, mi):
         reach, sizes = 4 + 4 * sum(pk["dil"][:k]), []
         for r in range(a.shape[0]):
             c = np.nonzero(a[r] != b[r])[0]
+            if tight and k <= stem.lead:
+                sizes += [n for _, n in incr4_ref.row_items(c.tolist(), L, reach, mi)[0]]
+                continue
             m = ((c[:, None] >= lo[None] - reach) & (c[:, None] <= hi[None] + reach)).any(0) & (lo <= L - 1)
             t = 0
             while t < 13:
@@ -126,7 +134,7 @@ if args.profile:
             fused.backbone_cnn_incremental(b, pk, stem, out=out)
             torch.cuda.synchronize()
             assert torch.equal(out, ref), "the incremental forward differs from the one-launch kernel"
-        log.append({"step": i, "reps": args.preps, "changed": int((a != b).sum()), "layers": marks(a, b, settings[0][1])})
+        log.append({"step": i, "reps": args.preps, "changed": int((a != b).sum()), "layers": marks(a, b, settings[0][1], settings[0][5])})
     json.dump({"setting": settings[0][0], "spec": NAMED.get(settings[0][0], settings[0][0]), "forwards": log}, open(args.marks, "w"))
     print(f"profile run: setting {settings[0][0]}, steps {steps}, {args.preps} forwards each ; marks -> {args.marks}")
     sys.exit(0)
@@ -145,7 +153,7 @@ def timed(fn, n=5):
 
 
 print("settings: " + " ; ".join(f"{n} = items <= {mi}, {'no LDS padding' if not res else f'{res} / CU'}, {'ordered' if o else 'slot'} list"
-                                for n, mi, res, o, _ in settings))
+                                for n, mi, res, o, _, _ in settings))
 print(f"per step (us, median of 5): one launch | " + " | ".join(f"{s[0]:>6s}" for s in settings) + f" | marked share of the carried tile-layers")
 for i in steps:
     if i + 1 >= len(states):

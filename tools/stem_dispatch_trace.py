@@ -13,11 +13,12 @@ depth = int(sys.argv[sys.argv.index("--depth") + 1]) if "--depth" in sys.argv el
 rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Timestamp"]))
 marks = json.load(open(sys.argv[2]))
 ev = [(r["Kernel_Name"], int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in rows]
-starts = [i for i, e in enumerate(ev) if "backbone_worklist_kernel" in e[0]]
+is_seg = lambda name: "backbone_seg_kernel" in name or "backbone_seg_tight_kernel" in name
+starts = [i for i, e in enumerate(ev) if "backbone_worklist_kernel" in e[0] or "backbone_list_kernel" in e[0]]
 forwards = []
-for i in starts:                                         # work list [, order], the segment launches, the tail
+for i in starts:                                         # work list [, order] (or the one list launch), the segment launches, the tail
     j = i + 1
-    while j < len(ev) and ("backbone_order_kernel" in ev[j][0] or "backbone_seg_kernel" in ev[j][0]):
+    while j < len(ev) and ("backbone_order_kernel" in ev[j][0] or is_seg(ev[j][0])):
         j += 1
     assert j < len(ev) and "backbone_kernel" in ev[j][0], ev[j][0] if j < len(ev) else "trace ends inside a forward"
     forwards.append(ev[i:j + 1])
@@ -30,9 +31,9 @@ at = 0
 for f in marks["forwards"]:
     fw = forwards[at:at + f["reps"]]
     at += f["reps"]
-    nseg = sum("backbone_seg_kernel" in e[0] for e in fw[0])
+    nseg = sum(is_seg(e[0]) for e in fw[0])
     assert nseg == len(f["layers"]) and depth in (None, nseg), f"{nseg} segment launches, {len(f['layers'])} layers in the marks, --depth {depth}"
-    head = [e for e in fw[0] if "backbone_seg_kernel" not in e[0]][:-1]
+    head = [e for e in fw[0] if not is_seg(e[0])][:-1]
     print(f"\nstep {f['step']} ({f['changed']} tokens changed), mean of {f['reps']} forwards, us")
     for h, e in enumerate(head):
         print(f"  {e[0].replace('(anonymous namespace)::', '').split('(')[0][-44:]:>44s}  {mean([us(x[h][2] - x[h][1]) for x in fw]):7.1f}")
