@@ -355,7 +355,30 @@ int svdd_hamming_nn(const uint32_t* q, const uint32_t* db, int B, int N, int L, 
                     uint64_t* nn_key, int64_t* hist, void* on_stream);
 
 /*
- * svdd_select — replaces torch.stack(scores,1) -> softmax(dim=1) -> argmax(dim=1) ->
+ * PWM motif scanning (added under ABI 17: one new entry, nothing existing changed; not in the reference). Integer log-odds tables,
+ * int32 sums and integer atomics only: every result is exact and independent of the launch shape and of how the caller cuts its
+ * rows into chunks. The stream is explicit (as svdd_kmer_counts).
+ *
+ * svdd_motif_scan: packed [N, W] u32, W = ceil(L / 16) (svdd_pack_tokens: finished rows, tokens 0..3; the padding bits are never
+ *   read as tokens). pwm [M, 32, 4] i16 in A, C, G, T order, width [M] i32 (1 .. 32; clamped to that range, and a column at or
+ *   beyond a motif's width never contributes), threshold [M] i32, all on the device. For row n, motif m of width w and every start
+ *   p = 0 .. L - w:  forward S+ = sum_i pwm[m, i, x[p + i]];  reverse strand S- = sum_i pwm[m, w - 1 - i, 3 - x[p + i]]  (int32).
+ *   A window is a hit on a strand when that strand's score is >= threshold[m]; the strands count separately (a palindromic site
+ *   counts twice). both_strands = 0: only S+ exists.
+ *   hits [M] i64 and rows_hit [M] i64 are ADDED to (64-bit integer atomics, one per wave and motif): the hits, and the rows with
+ *   at least one hit. row_hits [N, M] i32 is WRITTEN: the row's hits. row_best [N, M] i64 is WRITTEN: the key of the row's best
+ *   window, (uint64(uint32(score) ^ 0x80000000) << 32) | uint32(~(2 start + strand)) with strand 0 = forward, 1 = reverse: the
+ *   largest key is the highest score, among equal scores the lowest start, at one start forward before reverse (the scheme of
+ *   svdd_hamming_nn's key). L < w is valid: no windows, no hits, key 0 (score INT32_MIN, no start). Each of the four outputs may
+ *   be NULL. A workgroup takes 64 rows and 8 motifs at a time; a row's windows for one motif are scanned by one wave, so the
+ *   per-row outputs need no atomics.
+ *   SVDD_E_ARG: N, L or M <= 0, L > 1024, a NULL packed / pwm / width / threshold, all four outputs NULL.
+ */
+int svdd_motif_scan(const uint32_t* packed, int N, int L, const int16_t* pwm, const int32_t* width, const int32_t* threshold, int M,
+                    int both_strands, int64_t* hits, int64_t* rows_hit, int32_t* row_hits, int64_t* row_best, void* on_stream);
+
+/*
+ * svdd_select— replaces torch.stack(scores,1) -> softmax(dim=1) -> argmax(dim=1) ->
  * per-row Python gather + stack                     diffusion_gosai.py:1219-1227 (= :1451-1459)
  *
  *  scores [B,M] fp32 (row b, candidate m) ; cand [B,M,L] u8

@@ -60,6 +60,11 @@ def build_parser(method="mc"):
                    help="also report the set-level quality of the decoded sequences (k-mer Pearson r, diversity, novelty, score "
                         "Wasserstein distance) against the token arrays train / valid / test of FILE.npz (any subset): printed, and "
                         "saved as npz keys quality_<metric>")
+    p.add_argument("--eval_motifs", default=argparse.SUPPRESS, metavar="FILE.meme",      # absent unless given, as --eval_quality
+                   help="with --eval_quality FILE.npz: also scan the decoded sequences for the motifs of FILE.meme (MEME text, as "
+                        "JASPAR and HOCOMOCO are distributed) and report the Spearman correlation of their motif frequencies with "
+                        "each reference set's, the mean number of hits per design and the number of reachable motifs: printed, and "
+                        "saved as npz keys quality_<metric>")
     p.add_argument("--presample", action="store_true",
                    help="pre-sample val_batch_num batches at construction like the reference's BaseModel.__init__")
     p.epilog = ("--method classfier evaluates the value net in eval mode for every task (the reference's decode_classfier.py leaves it in "
@@ -71,7 +76,12 @@ def _guidance_scale(args):
     return args.guidance_scale if args.guidance_scale is not None else GUIDANCE_DEFAULT.get(args.method, 1e5)
 
 
+_MOTIFS_NEED_SETS = "--eval_motifs needs --eval_quality FILE.npz: the reference sets its correlations are taken against"
+
+
 def run(args):
+    if hasattr(args, "eval_motifs") and not getattr(args, "eval_quality", None):
+        raise ValueError(_MOTIFS_NEED_SETS)                     # before any model is built
     from . import synthetic
     from .harness import BaseModel
     from .value_nets import load_reference_state_dict
@@ -123,6 +133,9 @@ def run(args):
         with np.load(args.eval_quality) as f:
             sets = {name: f[name] for name in ("train", "valid", "test") if name in f.files}
         report = model.evaluate_quality(gen_samples, refs=sets, train=sets.get("train"))
+        if getattr(args, "eval_motifs", None):
+            from .motifs import load_meme
+            report.update(model.evaluate_motifs(gen_samples, load_meme(args.eval_motifs), refs=sets))
         extra.update({f"quality_{key}": np.float64(v) for key, v in report.items()})
     np.savez(path, decoding=reward_model_preds.cpu().numpy(), baseline=baseline_preds.cpu().numpy(), **extra)
     print(f"wrote {path}.npz: decoding mean {reward_model_preds.mean().item():.4f} (n={reward_model_preds.numel()}), "
@@ -133,7 +146,11 @@ def run(args):
 
 
 def main(method="mc", argv=None):
-    return run(build_parser(method).parse_args(argv))
+    parser = build_parser(method)
+    args = parser.parse_args(argv)
+    if hasattr(args, "eval_motifs") and not getattr(args, "eval_quality", None):
+        parser.error(_MOTIFS_NEED_SETS)
+    return run(args)
 
 
 # ------------------------------------------------------------------ value-function training (train_value.py) ----

@@ -10,7 +10,8 @@ The reference's `BaseModel.__init__` hard-wires checkpoint paths, Hydra and `.cu
 `gen_batch_num * sample_M` un-guided baseline batches, then the top-k) and return the same
 5-tuple: (samples list, value_func_preds [N], reward_model_preds [N], top_k_values, baseline_preds [N]).
 The tokens of the baseline batches behind baseline_preds are kept in `baseline_samples`; `evaluate_nll` scores any of them
-under the pretrained model (Diffusion.sequence_nll); `evaluate_quality` reports set-level metrics of them (svdd_amd.quality).
+under the pretrained model (Diffusion.sequence_nll); `evaluate_quality` reports set-level metrics of them (svdd_amd.quality),
+`evaluate_motifs` their motif content (svdd_amd.motifs).
 """
 import torch
 from torch import nn
@@ -285,3 +286,14 @@ class BaseModel(nn.Module):
         token_refs = {name: r for name, r in (refs or {}).items() if getattr(r, "ndim", 0) == 2}
         return quality.sample_quality(samples, refs=refs, train=train, k=k, scores=reward(samples),
                                       ref_scores={name: reward(r) for name, r in token_refs.items()})
+
+    @torch.no_grad()
+    def evaluate_motifs(self, samples, mset, refs=None):
+        """Motif content of decoded designs (svdd_amd.motifs; not in the reference) -> a flat dict: motif_spearman_<name> for every
+        set of refs {name: tokens [N', L'] or motif frequencies [M]} (the rank correlation, over the motifs of `mset`, of the share
+        of rows with a hit), motifs_per_row_mean (hits per design, both strands) and motifs_reachable. `samples` as in evaluate_nll."""
+        from . import motifs
+        dev = self.ref_model.device
+        if isinstance(samples, (list, tuple)):
+            samples = torch.cat([torch.as_tensor(s).reshape(-1, s.shape[-1]).to(dev) for s in samples])
+        return motifs.motif_report(torch.as_tensor(samples).to(dev), mset, refs=refs)

@@ -519,6 +519,64 @@ def nn_decode(nn_key):
     return dist, idx
 
 
+MOTIF_MAX_W = 32                                                         # svdd_motif_scan (include/svdd_hip.h)
+
+
+@dataclass
+class MotifTables:
+    """A motif set on the device, as svdd_motif_scan reads it: pwm i16 [M, 32, 4] (A, C, G, T), width i32 [M], threshold i32 [M].
+    Built by motifs.MotifSet.to_device, which has checked the widths (the kernel only clamps them)."""
+    pwm: torch.Tensor
+    width: torch.Tensor
+    threshold: torch.Tensor
+
+
+def motif_scan(packed, L, mset_dev, both_strands=True, hits=None, rows_hit=None, row_hits=None, row_best=None):
+    """svdd_motif_scan on packed rows (pack_tokens): packed int32 [N, ceil(L / 16)], mset_dev a MotifTables of M motifs. hits and
+    rows_hit i64 [M] are ADDED the hits / the rows with a hit; row_hits i32 [N, M] and row_best i64 [N, M] (decode: motif_best_decode)
+    are written. Any of the four may be None, not all. -> (hits, rows_hit, row_hits, row_best)."""
+    if not 1 <= int(L) <= PACK_MAX_L:
+        raise SvddError(f"motif_scan: L = {L} outside 1 .. {PACK_MAX_L}")
+    if not isinstance(mset_dev, MotifTables):
+        raise SvddError(f"motif_scan: mset_dev must be an ops.MotifTables (motifs.MotifSet.to_device), got {type(mset_dev).__name__}")
+    W = packed_words(L)
+    _need(packed, torch.int32, "packed")
+    if packed.dim() != 2 or packed.shape[1] != W or packed.shape[0] == 0 or not packed.is_contiguous():
+        raise SvddError(f"motif_scan: packed must be a contiguous non-empty int32 [N, {W}] tensor, got {tuple(packed.shape)}")
+    N = packed.shape[0]
+    _need(mset_dev.width, torch.int32, "width")
+    M = mset_dev.width.numel()
+    if M == 0:
+        raise SvddError("motif_scan: an empty motif set")
+    _is(mset_dev.width, torch.int32, (M,), "width")
+    _is(mset_dev.threshold, torch.int32, (M,), "threshold")
+    _is(mset_dev.pwm, torch.int16, (M, MOTIF_MAX_W, 4), "pwm")
+    if hits is None and rows_hit is None and row_hits is None and row_best is None:
+        raise SvddError("motif_scan: give at least one of hits, rows_hit, row_hits, row_best")
+    if hits is not None:
+        _is(hits, torch.int64, (M,), "hits")
+    if rows_hit is not None:
+        _is(rows_hit, torch.int64, (M,), "rows_hit")
+    if row_hits is not None:
+        _is(row_hits, torch.int32, (N, M), "row_hits")
+    if row_best is not None:
+        _is(row_best, torch.int64, (N, M), "row_best")
+    _lib.call("svdd_motif_scan", packed, N, int(L), mset_dev.pwm, mset_dev.width, mset_dev.threshold, M, int(bool(both_strands)),
+              hits, rows_hit, row_hits, row_best, _this_stream())
+    return hits, rows_hit, row_hits, row_best
+
+
+def motif_best_decode(row_best):
+    """row_best i64 [...] of motif_scan -> (score i32, start i32, strand i8): strand 0 forward, 1 reverse; a key of 0 (no window:
+    L < w) gives (INT32_MIN, -1, -1)."""
+    none = row_best == 0
+    score = (((row_best >> 32) & 0xFFFFFFFF) - (1 << 31)).to(torch.int32)
+    where = ~row_best & 0xFFFFFFFF                                         # 2 start + strand
+    start = torch.where(none, torch.full_like(where, -1), where >> 1).to(torch.int32)
+    strand = torch.where(none, torch.full_like(where, -1), where & 1).to(torch.int8)
+    return score, start, strand
+
+
 def select(scores, cand, mode=SELECT_ARGMAX, rng=None, want_soft=True, x_next=None):
     """-> (x_next u8 [B,L], soft f32 [B,M] | None, idx i32 [B])."""
     cand = _need(cand, torch.uint8, "cand").contiguous()
