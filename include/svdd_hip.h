@@ -432,18 +432,27 @@ int svdd_subs_logp(const float* logits, const uint8_t* x, int B, int L, int layo
  * and the net kernels take the length as a device pointer (`count` arguments below).
  *
  * svdd_compact_flags — stable compaction of n flags (one workgroup): flags[i] != 0 -> live_idx[k] = i, slot[i] = k with
- *   k = number of live items before i; else slot[i] = -1; count[0] = number of live items.
+ *   k = number of live items before i; else slot[i] = -1; count[0] = number of live items. Both compactions write slot [n] fully,
+ *   count[0], and live_idx at [0, count[0]) ONLY: the rest of live_idx keeps what it held.
  * svdd_compact_by_key — the same compaction ORDERED by key, largest first (stable inside a key; keys clamp to 15, key <= 0 = not
  *   live): live_idx lists the live items by descending key, slot[i] = position of item i in it or -1. With key = row tiles of a
  *   candidate's window (the flags svdd_candidate_windows writes) the windowed tower's long workgroups are dispatched first.
  *   split > 0: count must hold 3 ints; count[1] = min(count[0], split), count[2] = max(count[0] - split, 0) — the lengths of the
  *   list's two parts [0, split) and [split, ...), for callers that run the parts as separate launches (fused.py: the GRU's second round).
- * svdd_gather_rows   — dst[i,:] = src[idx[i],:] for i < count[0] (count may be NULL = n); rows of row_bytes bytes.
+ *   count[1] and count[2] are written ONLY when split > 0: with split == 0 count may hold a single int.
+ * svdd_gather_rows   — dst[i,:] = src[idx[i],:] for i < count[0] (count may be NULL = n); rows of row_bytes bytes; rows of dst at and
+ *   beyond the count are left untouched. No alignment requirement: the copy unit (4, 2 or 1 bytes) is taken from
+ *   row_bytes | src | dst, so every access is aligned to its unit.
  * svdd_advance_rows  — the selected candidate becomes the next parent: for every b, if slot[b*M + sel[b]] >= 0 then
- *   dst[b,:] = src[slot[...],:], else dst[b] is left untouched; rows of row_bytes (multiple of 4).
+ *   dst[b,:] = src[slot[...],:], else dst[b] is left untouched; rows of row_bytes, a multiple of 4, and src and dst aligned to
+ *   4 bytes (anything else: SVDD_E_ARG). 16-byte units are used when row_bytes and both pointers allow, 4-byte units otherwise.
  * svdd_select_compact — svdd_select on compacted scores: candidate (b, m) has score scores[slot[b*M+m]] if its slot is
  *   >= 0, else parent_score[b]. Additionally writes sel_score[b] (the selected candidate's score = the NEXT step's
  *   parent score) and changed[b] (1 iff x_next[b] differs from x[b]). slot == NULL: exactly svdd_select.
+ *   Bound on L (svdd_select too; M <= 64 with the row gather, i.e. x_next != NULL, unless SVDD_OPT_SELECT_ONE_ROW is 1): a wave copies
+ *   the winning rows of its W rows in units of u = 8, 4, 2 or 1 bytes (the largest that divides L, the candidate row stride, cand
+ *   and x_next), W = 64 / pow2(M) times 4 — times 1 below 2^21 (row, candidate) slots — capped at 64, and W * (L / u) must stay
+ *   below 2^22 (SVDD_E_ARG otherwise): L < 65536 is always accepted.
  */
 int svdd_compact_flags(const int32_t* flags, int n, int32_t* live_idx, int32_t* slot, int32_t* count, void* stream);
 int svdd_compact_by_key(const int32_t* key, int n, int32_t* live_idx, int32_t* slot, int32_t* count, int split, void* stream);
@@ -464,6 +473,8 @@ int svdd_select_compact(const float* scores, const int32_t* slot, const float* p
  *  out x_next [B,L] u8 ; idx [B] i32 (may be NULL) ; work [2*B] fp64 scratch (cdf + ratio).
  *  Two launches on `stream`: the CDF (one workgroup; the float64 cumsum is a serial chain by numpy's definition) and the
  *  searchsorted + row gather (whole chip). Any B; the pairwise sum's blocks run in parallel up to B = 131072.
+ *  The row gather copies in units of 8, 4, 2 or 1 bytes taken from L | sample | x_next (no alignment requirement) and finds a
+ *  unit's row by integer division; L < 2^25 (SVDD_E_ARG otherwise: a wave's 64 rows' units are counted in an int).
  */
 int svdd_tds_resample(const float* reward_num, const float* reward_den, double alpha,
                       const uint8_t* sample, const double* u, int B, int L,

@@ -1841,7 +1841,8 @@ __global__ __launch_bounds__(1024) void compact_by_key_kernel(const int32_t* __r
   }
 }
 
-// dst[i, :] = src[idx[i], :] for i < count : rows of `row_bytes` bytes, one wave per row
+// dst[i, :] = src[idx[i], :] for i < count : rows of `row_bytes` bytes, one wave per row. The copy unit (4, 2 or 1 bytes) is the
+// largest that divides row_bytes AND both base pointers, as in the two other row gathers: every access is aligned to its unit.
 __global__ __launch_bounds__(256) void gather_rows_kernel(const uint8_t* __restrict__ src, const int32_t* __restrict__ idx,
                                                           const int32_t* __restrict__ count, int n, int row_bytes,
                                                           uint8_t* __restrict__ dst) {
@@ -1850,24 +1851,31 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const uint8_t* __restr
   const int lane = threadIdx.x & 63;
   const uint8_t* s = src + (size_t)idx[r] * row_bytes;
   uint8_t* d = dst + (size_t)r * row_bytes;
-  if ((row_bytes & 3) == 0) {
+  const uintptr_t al = (uintptr_t)row_bytes | reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst);
+  if ((al & 3) == 0) {
     const uint32_t* s4 = reinterpret_cast<const uint32_t*>(s);
     uint32_t* d4 = reinterpret_cast<uint32_t*>(d);
     for (int i = lane; i < (row_bytes >> 2); i += WAVE) d4[i] = s4[i];
+  } else if ((al & 1) == 0) {
+    const uint16_t* s2 = reinterpret_cast<const uint16_t*>(s);
+    uint16_t* d2 = reinterpret_cast<uint16_t*>(d);
+    for (int i = lane; i < (row_bytes >> 1); i += WAVE) d2[i] = s2[i];
   } else {
     for (int i = lane; i < row_bytes; i += WAVE) d[i] = s[i];
   }
 }
 
 // The selected candidate becomes the next parent: dst[b, :] = src[slot[b*M + sel[b]], :] when that candidate was live
-// (slot >= 0), else dst[b] is left as it is (the parent did not change). Rows of `row_bytes` bytes (multiple of 16).
+// (slot >= 0), else dst[b] is left as it is (the parent did not change). Rows of `row_bytes` bytes, a multiple of 4, behind base
+// pointers aligned to 4 bytes (the host refuses anything else); 16-byte units when row_bytes and both pointers allow, else 4-byte.
 __global__ __launch_bounds__(256) void advance_rows_kernel(const uint8_t* __restrict__ src, const int32_t* __restrict__ slot,
                                                            const int32_t* __restrict__ sel, int B, int M, int row_bytes,
                                                            uint8_t* __restrict__ dst) {
   const int b = blockIdx.x;
   const int sl = slot[(size_t)b * M + sel[b]];
   if (sl < 0) return;
-  if ((row_bytes & 15) == 0) {
+  const uintptr_t al = (uintptr_t)row_bytes | reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst);
+  if ((al & 15) == 0) {
     const uint4* s16 = reinterpret_cast<const uint4*>(src + (size_t)sl * row_bytes);
     uint4* d16 = reinterpret_cast<uint4*>(dst + (size_t)b * row_bytes);
     for (int i = threadIdx.x; i < (row_bytes >> 4); i += 256) d16[i] = s16[i];
@@ -2184,6 +2192,13 @@ int svdd_select_compact(const float* scores, const int32_t* slot, const float* p
     while (mp < M) mp <<= 1;
     const int Rw = g_select_one_row_per_wave == 2 ? 4 : g_select_one_row_per_wave == 3 ? 1 : ((int64_t)B * mp >= (int64_t)1 << 21 ? 4 : 1);
     const int R = Rw > mp ? mp : Rw;
+    if (x_next) {
+      // the row gather of select_rows_kernel finds a copy unit's row with a float reciprocal, exact for indices below 2^22 (checked
+      // for every unit count by tests/test_sampler_contracts_cpu.py): refuse a wave whose R * G rows hold more units than that
+      const uintptr_t al = (uintptr_t)(L | a.ld) | (uintptr_t)cand | (uintptr_t)x_next;
+      const int ub = (al & 7) == 0 ? 8 : (al & 3) == 0 ? 4 : (al & 1) == 0 ? 2 : 1;
+      if ((int64_t)R * (WAVE / mp) * (L / ub) >= (int64_t)1 << 22) return SVDD_E_ARG;
+    }
     const int64_t waves = ((int64_t)B + (WAVE / mp) * R - 1) / ((WAVE / mp) * R);
     grid = dim3((unsigned)((waves + 3) / 4));
     if (M == 10 || M == 20) {                               // the BASELINE widths: the ordered sum stops at M
@@ -2243,6 +2258,7 @@ int svdd_gather_rows(const void* src, const int32_t* idx, const int32_t* count, 
 int svdd_advance_rows(const void* src, const int32_t* slot, const int32_t* sel, int B, int M, int row_bytes, void* dst,
                       void* stream) {
   if (!src || !slot || !sel || !dst || B <= 0 || M <= 0 || row_bytes <= 0 || (row_bytes & 3)) return SVDD_E_ARG;
+  if (((uintptr_t)src | (uintptr_t)dst) & 3) return SVDD_E_ARG;     // the kernel's smallest unit is 4 bytes
   return svdd_launch(advance_rows_kernel, dim3((unsigned)B), dim3(256), 0, stream, (const uint8_t*)src, slot, sel, B, M, row_bytes,
                      (uint8_t*)dst);
 }
@@ -2458,6 +2474,7 @@ int svdd_tds_resample(const float* reward_num, const float* reward_den, double a
                       const double* u, int B, int L, uint8_t* x_next, int32_t* idx, double* work, void* stream) {
   if (!reward_num || !reward_den || !sample || !u || !x_next || !work || B <= 0 || L <= 0 || !(alpha != 0.0))
     return SVDD_E_ARG;
+  if (L >= 1 << 25) return SVDD_E_ARG;         // the gather counts a wave's 64 rows' copy units in an int (and divides in integers)
   TdsArgs a{reward_num, reward_den, alpha, sample, u, B, L, x_next, idx, work};
   SvddSpan span(SVDD_SLOT_TDS_RESAMPLE);       // one timed span over both launches: start of phase 1 .. stop of phase 2
   if (svdd_launch_timed(span.first(), tds_cdf_kernel, dim3(1), dim3(1024), 0, stream, a) != SVDD_OK) return SVDD_E_LAUNCH;

@@ -14,23 +14,29 @@ SENT16 = 0x7FA5                               # a NaN in fp16 and in bf16
 
 
 class _Buf:
-    """numel elements (fp32 / int32, fp16 / bf16, or bytes) between two guards, all sentinel-filled; .ptr is element 0."""
+    """numel elements (fp32 / int32, fp16 / bf16, or bytes) between two guards, all sentinel-filled; .ptr is element 0.
+    int64 / fp64: numel counts the int32 WORDS, two per value — body() and cpu() view them as the 64-bit type, the written / untouched
+    masks stay per word. offset (bytes only): .ptr sits that many bytes into the aligned body — a misaligned view, whose front guard
+    is `offset` bytes longer."""
 
-    def __init__(self, numel, dtype=torch.float32):
+    def __init__(self, numel, dtype=torch.float32, offset=0):
         self.numel, self.dtype = numel, dtype
+        assert offset == 0 or dtype == torch.uint8, "a misaligned view is a view of bytes"
+        self.lo = GUARD + offset                                              # raw index of element 0
         if dtype == torch.uint8:
-            self.raw, self.sent = torch.full((numel + 2 * GUARD,), SENT8, dtype=torch.uint8, device=DEV), SENT8
+            self.raw, self.sent = torch.full((numel + offset + 2 * GUARD,), SENT8, dtype=torch.uint8, device=DEV), SENT8
         elif dtype in (torch.float16, torch.bfloat16):
             self.raw, self.sent = torch.full((numel + 2 * GUARD,), SENT16, dtype=torch.int16, device=DEV), SENT16
         else:
             self.raw, self.sent = torch.full((numel + 2 * GUARD,), SENT32, dtype=torch.int32, device=DEV), SENT32
+        assert self.raw.data_ptr() % 16 == 0
 
     @property
     def ptr(self):
-        return self.raw[GUARD:].data_ptr()
+        return self.raw[self.lo:].data_ptr()
 
     def bits(self):
-        return self.raw[GUARD:GUARD + self.numel]
+        return self.raw[self.lo:self.lo + self.numel]
 
     def body(self):
         return self.bits().view(self.dtype)
@@ -41,7 +47,7 @@ class _Buf:
 
     def untouched(self):
         """Bool mask of elements still holding the sentinel; asserts that both guards are intact."""
-        assert bool((self.raw[:GUARD] == self.sent).all()) and bool((self.raw[GUARD + self.numel:] == self.sent).all()), "guard overwritten"
+        assert bool((self.raw[:self.lo] == self.sent).all()) and bool((self.raw[self.lo + self.numel:] == self.sent).all()), "guard overwritten"
         return self.bits() == self.sent
 
     def assert_written(self, what):

@@ -279,6 +279,31 @@ def test_argument_validation_without_gpu():
     assert L.svdd_gru_bidir_bwd2_f32(one, one, one, one, one, None, None, 1, 1, None) == _lib.E_ARG                        # no output
 
 
+def test_row_movers_refuse_what_their_copy_units_cannot_address():
+    """The bounds include/svdd_hip.h states for the row gathers, refused before anything touches the device:
+    svdd_advance_rows copies 4-byte units at least (rows a multiple of 4, src and dst aligned to 4); svdd_select / _compact with the row
+    gather finds a unit's row with a float reciprocal that is exact below 2^22 units per wave (tests/test_sampler_contracts_cpu.py),
+    the unit taken from L and the pointers; svdd_tds_resample counts a wave's units in an int."""
+    from svdd_amd import _lib
+    L = _lib.lib()
+    al, p = ctypes.c_void_p, 1 << 20                                      # non-NULL addresses that are never dereferenced
+    for src, dst in [(p + 1, p), (p + 2, p), (p, p + 1), (p, p + 2), (p + 3, p + 3)]:
+        assert L.svdd_advance_rows(al(src), al(p), al(p), 1, 1, 16, al(dst), None) == _lib.E_ARG, (src, dst)
+    for row_bytes in (0, 1, 2, 6, 1001):
+        assert L.svdd_advance_rows(al(p), al(p), al(p), 1, 1, row_bytes, al(p), None) == _lib.E_ARG, row_bytes
+
+    def select(B, M, Lx, cand, x_next):
+        return L.svdd_select(al(p), al(cand), B, Lx, M, 0, None, al(x_next), None, None, None)
+
+    assert select(1, 1, 1 << 19, p, p) == _lib.E_ARG                      # 64 rows per wave x (2^19 / 8) units = 2^22
+    assert select(1, 1, 1 << 16, p + 1, p) == _lib.E_ARG                  # a cand view one byte off: 1-byte units, 64 x 2^16
+    assert select(1, 1, 1 << 17, p, p + 2) == _lib.E_ARG                  # an x_next view two bytes off: 2-byte units
+    assert select(1, 64, 1 << 22, p + 1, p) == _lib.E_ARG                 # one row per wave
+    assert select(1 << 18, 10, 1 << 21, p, p) == _lib.E_ARG               # a saturated launch: 4 groups of 4 rows x 2^18 units
+    assert L.svdd_select_compact(al(p), al(p), al(p), al(p), 1, 1 << 19, 1, 0, None, al(p), None, None, None, None, None) == _lib.E_ARG
+    assert L.svdd_tds_resample(al(p), al(p), 1.0, al(p), al(p), 1, 1 << 25, al(p), None, al(p), None) == _lib.E_ARG
+
+
 def test_schedule_table_equals_reference(golden):
     from svdd_amd.noise_schedule import LogLinearNoise, move_chance_table
     g = golden("g3_schedule.npz")
