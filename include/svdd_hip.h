@@ -378,6 +378,32 @@ int svdd_motif_scan(const uint32_t* packed, int N, int L, const int16_t* pwm, co
                     int both_strands, int64_t* hits, int64_t* rows_hit, int32_t* row_hits, int64_t* row_best, void* on_stream);
 
 /*
+ * The motif reward of SVDD-PM decoding (added under ABI 17: one new entry, nothing existing changed; not in the
+ * reference): from u8 token rows to one fp32 score per row in one launch, under a device-side row count, so that it can stand
+ * where a reward net stands in the posterior-mean loop. The stream is explicit (as svdd_motif_scan).
+ *
+ * svdd_motif_reward: tok [n, L] u8, finished rows; a token > 3 sets err[0] = 1 (err: caller-zeroed device word or NULL, read
+ *   later) and is read as 0, as in svdd_pack_tokens. count: a device int32 or NULL; rows >= count[0] are neither read nor written
+ *   (a count below 0 reads as 0, above n as n); NULL means all n rows. pwm / width / threshold and both_strands as svdd_motif_scan
+ *   takes them. hit_coef, hit_cap (>= 0), margin_coef, margin_floor (>= 0): int32 [M] on the device. With hits_m and best_m of
+ *   row r exactly as svdd_motif_scan defines them (the strands count separately; best_m the highest window score on either
+ *   strand; L < w: no window),
+ *     T(r) = sum_m [ hit_coef_m min(hits_m, hit_cap_m) + margin_coef_m max(min(best_m - threshold_m, 0), -margin_floor_m) ]
+ *   in int64, the margin being -margin_floor_m where there is no window (the caller keeps the sum of |hit_coef_m| hit_cap_m +
+ *   |margin_coef_m| margin_floor_m below 2^62). score [n] f32 or NULL: score[r] = __fadd_rn(base[r], __fmul_rn((float)T, unit));
+ *   base [n] f32 or NULL (= 0); score may alias base. term [n] i64 or NULL receives T. Everything before the last two fp32
+ *   operations is integer arithmetic: the result is exact and independent of the launch shape and of how rows are cut into calls.
+ *   A workgroup packs its rows (8; measured against 32 and 64 in profiles/motif_reward_time.txt) into LDS itself and walks all
+ *   motif groups for them, so a row's T is finished in one workgroup: no atomics, no second pass. A workgroup whose first row is
+ *   >= count[0] exits at once.
+ *   SVDD_E_ARG: n, L or M <= 0, L > 1024, a NULL tok, table or coefficient array, score and term both NULL.
+ */
+int svdd_motif_reward(const uint8_t* tok, int n, int L, const int32_t* count, const int16_t* pwm, const int32_t* width,
+                      const int32_t* threshold, int M, int both_strands, const int32_t* hit_coef, const int32_t* hit_cap,
+                      const int32_t* margin_coef, const int32_t* margin_floor, const float* base, float unit, float* score,
+                      int64_t* term, int32_t* err, void* on_stream);
+
+/*
  * svdd_select— replaces torch.stack(scores,1) -> softmax(dim=1) -> argmax(dim=1) ->
  * per-row Python gather + stack                     diffusion_gosai.py:1219-1227 (= :1451-1459)
  *

@@ -136,6 +136,7 @@ SIGNATURES = {
     "svdd_pack_tokens": (vp, i32, i32, vp, vp, vp),
     "svdd_hamming_nn": (vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp),
     "svdd_motif_scan": (vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp),
+    "svdd_motif_reward": (vp, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp),
     "svdd_candidate_parts": (vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp),
     "svdd_conv_tower_parts_f32": (vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp),
     "svdd_backbone_incr4_f32": (vp, vp, vp, vp, vp, vp, i32, i32, i32, pi32, i32, vp, vp, vp, vp, i32, i32, vp, vp, i32, vp, i32, vp),

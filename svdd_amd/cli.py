@@ -65,6 +65,14 @@ def build_parser(method="mc"):
                         "JASPAR and HOCOMOCO are distributed) and report the Spearman correlation of their motif frequencies with "
                         "each reference set's, the mean number of hits per design and the number of reachable motifs: printed, and "
                         "saved as npz keys quality_<metric>")
+    p.add_argument("--guide_motifs", default=argparse.SUPPRESS, metavar="FILE.meme",     # the three --guide_* flags: absent unless given
+                   help="--method tweedie only: decode towards (or away from) the motifs of FILE.meme, the reward net's score plus "
+                        "a motif term (svdd_amd.motifs.MotifReward); give --guide_weights, --guide_margin or both")
+    p.add_argument("--guide_weights", default=argparse.SUPPRESS, metavar="NAME=+2,NAME2=-1",
+                   help="with --guide_motifs: the reward of a hit of motif NAME (negative: a penalty), counted once per design")
+    p.add_argument("--guide_margin", default=argparse.SUPPRESS, metavar="NAME=0.01",
+                   help="with --guide_motifs: the reward per score unit by which a design's best window of motif NAME falls short "
+                        "of the motif's threshold (the dense signal that lets the decode climb towards a site)")
     p.add_argument("--presample", action="store_true",
                    help="pre-sample val_batch_num batches at construction like the reference's BaseModel.__init__")
     p.epilog = ("--method classfier evaluates the value net in eval mode for every task (the reference's decode_classfier.py leaves it in "
@@ -79,9 +87,56 @@ def _guidance_scale(args):
 _MOTIFS_NEED_SETS = "--eval_motifs needs --eval_quality FILE.npz: the reference sets its correlations are taken against"
 
 
+_GUIDE_FLAGS = ("guide_motifs", "guide_weights", "guide_margin")
+
+
+def _guide_error(args):
+    """What is wrong with the --guide_* flags of args, or None."""
+    given = [f for f in _GUIDE_FLAGS if hasattr(args, f)]
+    if not given:
+        return None
+    if args.method != "tweedie":
+        return f"--{given[0]} is for --method tweedie (SVDD-PM scores finished sequences), not --method {args.method}"
+    if "guide_motifs" not in given:
+        return f"--{given[0]} needs --guide_motifs FILE.meme"
+    if len(given) == 1:
+        return "--guide_motifs needs --guide_weights, --guide_margin or both"
+    return None
+
+
+def _name_values(text, flag):
+    """"NAME=+2,NAME2=-1" -> {"NAME": 2.0, "NAME2": -1.0}."""
+    out = {}
+    for item in filter(None, (s.strip() for s in text.split(","))):
+        name, eq, value = item.rpartition("=")
+        try:
+            number = float(value) if eq and name.strip() else None
+        except ValueError:
+            number = None
+        if number is None:
+            raise ValueError(f"--{flag}: expected NAME=NUMBER[,NAME=NUMBER ...], got {item!r}")
+        out[name.strip()] = number
+    if not out:
+        raise ValueError(f"--{flag}: expected NAME=NUMBER[,NAME=NUMBER ...], got {text!r}")
+    return out
+
+
+def guide_reward(args):
+    """The MotifReward of the --guide_* flags, or None."""
+    if not hasattr(args, "guide_motifs"):
+        return None
+    from .motifs import MotifReward, load_meme
+    return MotifReward(load_meme(args.guide_motifs),
+                       hit_weight=_name_values(args.guide_weights, "guide_weights") if hasattr(args, "guide_weights") else None,
+                       margin_weight=_name_values(args.guide_margin, "guide_margin") if hasattr(args, "guide_margin") else None)
+
+
 def run(args):
     if hasattr(args, "eval_motifs") and not getattr(args, "eval_quality", None):
         raise ValueError(_MOTIFS_NEED_SETS)                     # before any model is built
+    if _guide_error(args):
+        raise ValueError(_guide_error(args))                    # so are these
+    guide = guide_reward(args)                                  # ... and a file or a weight that does not parse
     from . import synthetic
     from .harness import BaseModel
     from .value_nets import load_reference_state_dict
@@ -110,6 +165,11 @@ def run(args):
                       val_batch_num=args.val_batch_num if args.presample else 0).cuda().eval()
     if args.method == "mc":
         out = model.controlled_decode(gen_batch_num=args.val_batch_num, sample_M=args.sample_M)
+    elif args.method == "tweedie" and guide is not None:
+        out = model.controlled_decode_motif(gen_batch_num=args.val_batch_num, sample_M=args.sample_M, motif_reward=guide,
+                                            options=args.tweedie)
+        terms = torch.cat(model.motif_terms)
+        print(f"motif term of the guided designs: mean {terms.mean().item():.4f} (n={terms.numel()})")
     elif args.method == "tweedie":
         out = model.controlled_decode_tweedie(gen_batch_num=args.val_batch_num, sample_M=args.sample_M, options=args.tweedie)
     elif args.method == "tds":
@@ -150,6 +210,8 @@ def main(method="mc", argv=None):
     args = parser.parse_args(argv)
     if hasattr(args, "eval_motifs") and not getattr(args, "eval_quality", None):
         parser.error(_MOTIFS_NEED_SETS)
+    if _guide_error(args):
+        parser.error(_guide_error(args))
     return run(args)
 
 

@@ -201,6 +201,14 @@ class WeightCache:
         return value
 
 
+def _refuse_motif_reward(what, *nets):
+    """The gradient-guided samplers and the attributions differentiate their net; a motifs.GuidedReward only has values."""
+    from .motifs import GuidedReward
+    if any(isinstance(n, GuidedReward) for n in nets):
+        raise TypeError(f"{what}: a GuidedReward is not differentiable (its motif term has reward values, no gradient): decode with "
+                        "controlled_sample_tweedie (SVDD-PM) or controlled_sample_TDS")
+
+
 def _decode_scope(fn):
     """Marks one call of a public sampler method: the fused-net caches are validated against the modules' weights once
     per outermost call (a decode), not at every diffusion step."""
@@ -390,7 +398,11 @@ class Diffusion(nn.Module):
 
     def reward_callable(self, reward_model):
         """The callable the engine uses for `reward_model(onehot_t [n,4,L])` -> [n,n_tasks,1]."""
+        from .motifs import GuidedReward
         from .value_nets import RewardModel
+        if isinstance(reward_model, GuidedReward):                  # a reward net plus a motif term (DESIGN 4m): the same wrapper
+            base = reward_model.reward_model                        # around the net's own callable (the fused net, from the cache)
+            return GuidedReward(None if base is None else self.reward_callable(base), reward_model.motif_reward)
         if self.fuse_nets and isinstance(reward_model, RewardModel):
             fused = self.value_callable(reward_model.embedding, reward_model.head)
             if isinstance(fused, nn.Module):
@@ -912,6 +924,7 @@ class Diffusion(nn.Module):
     def controlled_sample_DPS(self, reward_model, guidance_scale, num_steps=None, eps=1e-5, eval_sp_size=None,
                               sample_M=10):
         """DPS baseline decode (:980-1019). Not under no_grad in the reference either: it back-propagates."""
+        _refuse_motif_reward("controlled_sample_DPS", reward_model)
         B, L, S, sched, x = self._decode_start(num_steps, eps, eval_sp_size)
         for i in range(S):
             x = self._dps_step(x, sched[i, 1], sched[i, 2], reward_model, guidance_scale, i)
@@ -993,6 +1006,7 @@ class Diffusion(nn.Module):
         eval mode for every task; the reference's decode_classfier.py leaves it in train mode for task "rna", i.e. dropout on and
         batch-statistics BatchNorm, which makes that run irreproducible). guidance_scale=None raises ValueError (the reference fails
         with a TypeError). A batch-sharded decode is refused."""
+        _refuse_motif_reward("controlled_sample_classfier", pre_scorer_embedding, pre_scorer_head)
         self._classifier_checks(guidance_scale)
         B, L, S, sched, x = self._decode_start(num_steps, eps, eval_sp_size)
         onehot = torch.zeros((B, L, 4), dtype=torch.float32, device=self.device)            # transform_samples of the prior
@@ -1617,6 +1631,7 @@ class Diffusion(nn.Module):
         The B * S (row, step) pairs run in passes of svdd_attr_path, the gradient, svdd_attr_fold; nothing crosses to the host. The
         fused ConvGRU value net (one task, L = 200 or 50) takes mean_score_input_grad as it is, no autograd; any other net or length
         takes torch autograd of the sum of the pass's scores. The gradient is fp32 whatever self.precision says."""
+        _refuse_motif_reward("attributions", pre_scorer_embedding, pre_scorer_head, reward_model)
         x_u8, baseline, alphas, weights, chunk_rows = self._attr_inputs(x, method, baseline, n_steps, quadrature, chunk_rows,
                                                                          return_delta)
         B, L = x_u8.shape
@@ -1670,7 +1685,11 @@ class Diffusion(nn.Module):
         hand-written kernels for the value / reward net and (PM, logits cache) the one-launch backbone kernel."""
         from .fused import FusedValueNet
         from .fused_trunk import FusedEnformerValueNet
-        ok = ((isinstance(fn, FusedValueNet) and fn.kernels_ok(L) and fn.w_eff.shape[1] == 1) or
+        from .motifs import GuidedReward
+        motif_only = isinstance(fn, GuidedReward) and fn.reward_model is None
+        if isinstance(fn, GuidedReward):                            # svdd_motif_reward takes a device-side count itself: what matters
+            fn = fn.reward_model                                    # is the net the wrapper holds; none at all (a pure motif objective) qualifies
+        ok = (motif_only or (isinstance(fn, FusedValueNet) and fn.kernels_ok(L) and fn.w_eff.shape[1] == 1) or
               (isinstance(fn, FusedEnformerValueNet) and fn.head_w.shape[1] == 1))
         return (self.skip_unchanged and self.fuse_nets and self.value_batching == "batched" and M > 1 and ok and
                 self.select_mode in ("argmax", "multinomial"))
@@ -1905,7 +1924,8 @@ class Diffusion(nn.Module):
     def controlled_sample_tweedie(self, reward_model, num_steps=None, eps=1e-5, eval_sp_size=None, sample_M=10,
                                   options=True, task="dna"):
         """SVDD-PM decode (:1105-1145). NB the reference compares `options == "True"` (a string, :1414):
-        the default `options=True` therefore takes the heuristic branch there too."""
+        the default `options=True` therefore takes the heuristic branch there too. reward_model may be a motifs.GuidedReward (a
+        reward net, or None, plus a motif term): with options="True" it takes the same work-skipping loop."""
         B, L, S, sched, x = self._decode_start(num_steps, eps, eval_sp_size)
         M = sample_M
         rf = self.reward_callable(reward_model)

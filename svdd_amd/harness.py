@@ -220,6 +220,23 @@ class BaseModel(nn.Module):
             task=self.task), tweedie_quirks=True)
 
     @torch.no_grad()
+    def controlled_decode_motif(self, gen_batch_num, sample_M, motif_reward, options="True"):
+        """SVDD-PM towards (or away from) motifs (svdd_amd.motifs; not in the reference): every guided batch is decoded
+        under GuidedReward(self.reward_model, motif_reward), the reward net's score plus the motif term. Returns what
+        controlled_decode_tweedie returns, the predictions being the plain reward model's; `motif_terms` holds per guided batch the
+        motif term of its designs (fp32 [NUM_SAMPLES_PER_BATCH], on the device)."""
+        from .motifs import GuidedReward
+        guided_reward = GuidedReward(self.reward_model, motif_reward)
+        self.motif_terms = []
+
+        def guided():
+            x = self.ref_model.controlled_sample_tweedie(guided_reward, eval_sp_size=self.NUM_SAMPLES_PER_BATCH, sample_M=sample_M,
+                                                         options=options, task=self.task)
+            self.motif_terms.append(motif_reward.term(x))
+            return x
+        return self._decode(gen_batch_num, sample_M, guided, tweedie_quirks=True)
+
+    @torch.no_grad()
     def controlled_decode_TDS(self, gen_batch_num, sample_M, alpha):
         """SMC/TDS baseline (reference Enformer.py:479-557)."""
         return self._decode(gen_batch_num, sample_M, lambda: self.ref_model.controlled_sample_TDS(

@@ -7,6 +7,9 @@ its motif usage looks like a reference set's. Not in the reference.
   motif_frequencies / motif_corr
                             per-motif frequencies and their Spearman / Pearson correlation with a reference set
   spearmanr / pearsonr      host-level float64, average ranks for ties
+  MotifReward / GuidedReward
+                            decoding TOWARDS (or away from) motifs: a per-row integer motif term, one svdd_motif_reward
+                            launch from u8 tokens to fp32 scores, and the wrapper the SVDD-PM sampler takes as its reward model
 
 Token inputs are [N, L] integer tensors of finished sequences (tokens 0..3, L <= 1024), as in svdd_amd.quality. The kernel has no
 CPU fallback."""
@@ -366,3 +369,165 @@ def motif_report(x, mset, refs=None):
     out["motifs_per_row_mean"] = int(c["hits"].sum()) / c["rows"]
     out["motifs_reachable"] = int(mset.reachable.sum())
     return out
+
+
+# ------------------------------------------------------------------------------------- motif-guided decoding (4m) ----
+REWARD_CHUNK_ROWS = 1 << 18              # rows per svdd_motif_reward launch of MotifReward.term (any value gives the same bits)
+_I32 = np.iinfo(np.int32)
+TERM_BOUND = 1 << 62                     # the host keeps sum_m (|hit_coef| hit_cap + |margin_coef| margin_floor) below it: T fits int64
+
+
+def _per_motif(value, mset, name, default, missing):
+    """None -> default; a number -> that number for every motif; [M] values; a {motif name: value} dict (the other motifs get
+    `missing`) -> float64 / int64 [M] as `default` is."""
+    M = len(mset)
+    default = np.asarray(default)
+    if value is None:
+        return default.copy()
+    if isinstance(value, dict):
+        unknown = [k for k in value if k not in mset.names]
+        if unknown:
+            raise ValueError(f"{name}: no motif named {unknown[0]!r} (the set has {', '.join(mset.names[:8])}{' ...' if M > 8 else ''})")
+        rest = np.broadcast_to(missing, (M,))
+        value = [value.get(n, rest[m]) for m, n in enumerate(mset.names)]
+    a = np.asarray(value)
+    if a.dtype.kind not in "iuf" or a.ndim > 1 or (a.ndim == 1 and a.size != M):
+        raise ValueError(f"{name}: expected a number, M = {M} numbers or a {{name: value}} dict, got {value!r}")
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f"{name}: a non-finite value")
+    if default.dtype.kind == "i":
+        if a.dtype.kind == "f" and np.any(a != np.rint(a)):
+            raise ValueError(f"{name}: expected integers, got {value!r}")
+        if np.any(a < 0) or np.any(a > _I32.max):
+            raise ValueError(f"{name}: expected values in 0 .. {_I32.max}, got {value!r}")
+    return np.broadcast_to(a, (M,)).astype(default.dtype)
+
+
+class MotifReward:
+    """A motif objective for SVDD-PM decoding: per finished row the integer term of svdd_motif_reward
+        T = sum_m [hit_coef_m min(hits_m, hit_cap_m) + margin_coef_m max(min(best_m - threshold_m, 0), -margin_floor_m)]
+    times `unit`. hit_weight / margin_weight: per motif a float (a number, M numbers, or a {name: value} dict whose unnamed motifs
+    get 0; None = all 0), quantised to hit_coef / margin_coef = round(weight / unit) int32. A hit weight is the reward of one hit,
+    up to hit_cap of them (negative: a penalty); a margin weight is the reward per score unit by which the row's best window
+    falls short of the threshold (0 once a window reaches it), cut off at margin_floor score units (default: the threshold minus
+    the motif's lowest reachable score, i.e. never cut off). hit_cap / margin_floor: a number, M numbers or a dict (unnamed
+    motifs keep the default)."""
+
+    def __init__(self, mset, hit_weight=None, margin_weight=None, hit_cap=1, margin_floor=None, unit=2 ** -10, strands="both"):
+        self.mset = _mset(mset)
+        self.both = _strands(strands)
+        self.strands = strands
+        if isinstance(unit, bool) or not isinstance(unit, (int, float)) or not 0.0 < float(unit) < float("inf"):
+            raise ValueError(f"unit = {unit!r}: expected a positive finite number")
+        self.unit = float(np.float32(unit))
+        if self.unit != float(unit):                                 # (an underflow to 0 included)
+            raise ValueError(f"unit = {unit!r}: expected a number fp32 holds exactly (a power of two, say)")
+        M = len(mset)
+        zeros = np.zeros(M, np.float64)
+        self.hit_coef = self._quantise(_per_motif(hit_weight, mset, "hit_weight", zeros, 0.0), "hit_weight")
+        self.margin_coef = self._quantise(_per_motif(margin_weight, mset, "margin_weight", zeros, 0.0), "margin_weight")
+        self.hit_cap = _per_motif(hit_cap, mset, "hit_cap", np.ones(M, np.int64), 1).astype(np.int32)
+        floor = np.maximum(mset.threshold.astype(np.int64) - mset.min_score.astype(np.int64), 0)
+        if np.any(floor > _I32.max):
+            raise ValueError("margin_floor: a threshold lies more than 2^31 - 1 above its motif's lowest score")
+        self.margin_floor = _per_motif(margin_floor, mset, "margin_floor", floor, floor).astype(np.int32)
+        self.bound = sum(abs(int(h)) * int(c) + abs(int(g)) * int(f)
+                         for h, c, g, f in zip(self.hit_coef, self.hit_cap, self.margin_coef, self.margin_floor))
+        if self.bound >= TERM_BOUND:
+            raise ValueError(f"the term can reach {self.bound} >= 2^62 in magnitude: lower the weights, hit_cap or margin_floor, or raise unit")
+        self._dev = {}
+
+    def _quantise(self, w, name):
+        q = np.rint(w / self.unit)
+        if np.any(np.abs(q) > _I32.max):
+            raise ValueError(f"{name}: round(weight / unit) leaves int32 ({q[np.argmax(np.abs(q))]:.0f}); raise unit or lower the weight")
+        return q.astype(np.int32)
+
+    def __len__(self):
+        return len(self.mset)
+
+    def to_device(self, device="cuda"):
+        """-> (ops.MotifTables, ops.MotifCoefs) on `device` (kept for the next call)."""
+        tables = self.mset.to_device(device)
+        device = tables.width.device
+        if device not in self._dev:
+            self._dev[device] = ops.MotifCoefs(*(torch.from_numpy(a).to(device)
+                                                 for a in (self.hit_coef, self.hit_cap, self.margin_coef, self.margin_floor)))
+        return tables, self._dev[device]
+
+    def term_tokens(self, tok, count=None, base=None, out=None):
+        """tok u8 [n, L] on the device (finished rows) -> fp32 [n]: base + T unit (base fp32 [n] or None = 0; out may be base). count:
+        int32 device tensor [1], the rows beyond count[0] are neither read nor written. One launch, nothing crosses to the host."""
+        if not isinstance(tok, torch.Tensor) or not tok.is_cuda:
+            raise ops.SvddError("tok must be a GPU tensor (the SVDD hot path has no CPU fallback)")
+        tables, coefs = self.to_device(tok.device)
+        return ops.motif_reward(tok, tables, coefs, self.unit, count=count, base=base, out=out, both_strands=self.both)[0]
+
+    def term(self, x, chunk_rows=None, return_int=False):
+        """Any [N, L] token array (tokens 0..3, L <= 1024) -> T unit as fp32 [N] on the device, in chunks of chunk_rows rows (every
+        value gives the same bits). return_int: (that, T int64 [N])."""
+        rows = _chunk_rows(chunk_rows, REWARD_CHUNK_ROWS)
+        x = _checked(x, "x", 3)
+        if x.shape[1] > ops.PACK_MAX_L:
+            raise ValueError(f"L = {x.shape[1]} > {ops.PACK_MAX_L}")
+        x = _on_device(x, "x")
+        tables, coefs = self.to_device(x.device)
+        N = x.shape[0]
+        out = torch.empty(N, dtype=torch.float32, device=x.device)
+        T = torch.empty(N, dtype=torch.int64, device=x.device) if return_int else None
+        err = torch.zeros(1, dtype=torch.int32, device=x.device)
+        for r0 in range(0, N, rows):
+            ops.motif_reward(x[r0:r0 + rows], tables, coefs, self.unit, out=out[r0:r0 + rows], term=None if T is None else T[r0:r0 + rows],
+                             err=err, both_strands=self.both)
+        ops.check_pack_err(err)
+        return (out, T) if return_int else out
+
+
+class GuidedReward:
+    """reward_model (or None: base 0, a pure motif objective that needs no trained net) plus a MotifReward's term on task 0: what
+    the samplers take as `reward_model` (Diffusion.controlled_sample_tweedie, controlled_sample_TDS). It has reward values, no
+    gradient: the gradient samplers refuse it."""
+
+    def __init__(self, reward_model, motif_reward):
+        if not isinstance(motif_reward, MotifReward):
+            raise ValueError(f"motif_reward must be a MotifReward, got {type(motif_reward).__name__}")
+        if reward_model is not None and not callable(reward_model):
+            raise ValueError(f"reward_model must be a reward model (a callable) or None, got {type(reward_model).__name__}")
+        if isinstance(reward_model, GuidedReward):
+            raise ValueError("reward_model is a GuidedReward already: give one MotifReward with all the weights")
+        self.reward_model = reward_model
+        self.motif_reward = motif_reward
+
+    def __call__(self, onehot):
+        """onehot fp32 [n, 4, L] (the reward models' layout) or [n, L, 4] -> [n, n_tasks, 1]; a zero (MASK) row raises."""
+        if not isinstance(onehot, torch.Tensor) or onehot.dim() != 3 or 4 not in onehot.shape[1:]:
+            raise ValueError(f"onehot must be a [n, 4, L] or [n, L, 4] tensor, got {tuple(getattr(onehot, 'shape', ()))}")
+        if not onehot.is_cuda:
+            raise ops.SvddError("onehot must be a GPU tensor (the SVDD hot path has no CPU fallback)")
+        rows = onehot if onehot.shape[1] == 4 else onehot.transpose(1, 2)          # [n, 4, L]
+        if bool((rows.sum(1) == 0).any()):
+            raise ValueError("a row of onehot is zero (MASK): the motif term is defined for finished sequences (tokens 0..3)")
+        term = self.motif_reward.term_tokens(rows.argmax(1).to(torch.uint8).contiguous())
+        if self.reward_model is None:
+            return term.view(-1, 1, 1)
+        out = self.reward_model(onehot).float().clone()
+        out[:, 0, 0] += term
+        return out
+
+    def forward_tokens(self, tok, count=None):
+        """tok u8 [n, L] on the device -> [n, n_tasks, 1]; count as MotifReward.term_tokens (rows beyond it are undefined)."""
+        n = tok.shape[0]
+        if self.reward_model is None:
+            return self.motif_reward.term_tokens(tok, count=count).view(n, 1, 1)
+        if not hasattr(self.reward_model, "forward_tokens"):
+            if count is not None:
+                raise ops.SvddError("a compacted batch (count) needs a reward net with forward_tokens (the fused kernels)")
+            return self(ops.transform_samples(tok, transposed=True))
+        out = self.reward_model.forward_tokens(tok, count=count).float()
+        if out.numel() == n and out.is_contiguous():
+            flat = out.view(n)
+            self.motif_reward.term_tokens(tok, count=count, base=flat, out=flat)
+            return out.view(n, 1, 1)
+        out = out.reshape(n, -1, 1).clone()
+        out[:, 0, 0] = self.motif_reward.term_tokens(tok, count=count, base=out[:, 0, 0].contiguous())
+        return out

@@ -577,6 +577,58 @@ def motif_best_decode(row_best):
     return score, start, strand
 
 
+@dataclass
+class MotifCoefs:
+    """The per-motif integer coefficients of svdd_motif_reward on the device, int32 [M] each: hit_coef, hit_cap (>= 0), margin_coef,
+    margin_floor (>= 0). Built by motifs.MotifReward.to_device, which has checked the signs and the int64 bound."""
+    hit_coef: torch.Tensor
+    hit_cap: torch.Tensor
+    margin_coef: torch.Tensor
+    margin_floor: torch.Tensor
+
+
+def motif_reward(tok, mset_dev, coefs, unit, count=None, base=None, out=None, term=None, err=None, both_strands=True):
+    """svdd_motif_reward: tok u8 [n, L] (finished rows, L <= 1024), mset_dev a MotifTables of M motifs, coefs a MotifCoefs, unit a
+    float -> (out f32 [n] | None, term i64 [n] | None): out[r] = base[r] + float(T(r)) * unit and term[r] = T(r), the integer motif
+    term of include/svdd_hip.h. count: int32 device tensor [1], rows >= count[0] are neither read nor written (None: all rows).
+    base f32 [n] or None (0); out may be base itself. out = None allocates it unless term is given (term only). err: a caller-zeroed
+    device int32 [1] the kernel sets for a token > 3 (checked by the caller later with check_pack_err); None: not reported."""
+    if not isinstance(mset_dev, MotifTables):
+        raise SvddError(f"motif_reward: mset_dev must be an ops.MotifTables (motifs.MotifSet.to_device), got {type(mset_dev).__name__}")
+    if not isinstance(coefs, MotifCoefs):
+        raise SvddError(f"motif_reward: coefs must be an ops.MotifCoefs (motifs.MotifReward.to_device), got {type(coefs).__name__}")
+    if isinstance(unit, torch.Tensor) or not isinstance(unit, (int, float)) or isinstance(unit, bool) or not 0.0 < float(unit) < float("inf"):
+        raise SvddError(f"motif_reward: unit = {unit!r}: expected a positive finite number")
+    tok = _tokens2d(tok, "tok")
+    n, L = tok.shape
+    if L > PACK_MAX_L:
+        raise SvddError(f"motif_reward: L = {L} outside 1 .. {PACK_MAX_L}")
+    _need(mset_dev.width, torch.int32, "width")
+    M = mset_dev.width.numel()
+    if M == 0:
+        raise SvddError("motif_reward: an empty motif set")
+    _is(mset_dev.width, torch.int32, (M,), "width")
+    _is(mset_dev.threshold, torch.int32, (M,), "threshold")
+    _is(mset_dev.pwm, torch.int16, (M, MOTIF_MAX_W, 4), "pwm")
+    for name in ("hit_coef", "hit_cap", "margin_coef", "margin_floor"):
+        _is(getattr(coefs, name), torch.int32, (M,), name)
+    if count is not None:
+        _is(count, torch.int32, (1,), "count")
+    if base is not None:
+        _is(base, torch.float32, (n,), "base")
+    if term is not None:
+        _is(term, torch.int64, (n,), "term")
+    if err is not None:
+        _is(err, torch.int32, (1,), "err")
+    if out is None and term is None:
+        out = torch.empty(n, dtype=torch.float32, device=tok.device)
+    elif out is not None:
+        _is(out, torch.float32, (n,), "out")
+    _lib.call("svdd_motif_reward", tok, n, L, count, mset_dev.pwm, mset_dev.width, mset_dev.threshold, M, int(bool(both_strands)),
+              coefs.hit_coef, coefs.hit_cap, coefs.margin_coef, coefs.margin_floor, base, float(unit), out, term, err, _this_stream())
+    return out, term
+
+
 def select(scores, cand, mode=SELECT_ARGMAX, rng=None, want_soft=True, x_next=None):
     """-> (x_next u8 [B,L], soft f32 [B,M] | None, idx i32 [B])."""
     cand = _need(cand, torch.uint8, "cand").contiguous()
