@@ -4026,42 +4026,8 @@ extern "C" int svdd_backbone_cnn_f32(const uint8_t* x, const float* table0, cons
   return svdd_launch_timed(ev, spt1 ? backbone_kernel<true> : backbone_kernel<false>, dim3(nwg), dim3(512), lds, stream, a, BackboneSave{});
 }
 
-extern "C" int svdd_backbone_incr_f32(const uint8_t* x, const float* table0, const float* tiles, const float* vec, const float* w2,
-                                      float* out, int n, int L, int nlayers, const int* dilations, int lead, float* planes,
-                                      uint8_t* x_prev, int32_t* items, unsigned long long* stat, int first, int max_item,
-                                      void* stream) {
-  if (!x || !table0 || !tiles || !vec || !w2 || !out || !dilations || !planes || !x_prev || !items || n <= 0 || L <= TW_ROWS / 2 ||
-      L > TW_ROWS || nlayers <= 0 || nlayers > BB_MAXL || lead < 2 || lead > nlayers || (max_item != 2 && max_item != 4))
-    return SVDD_E_ARG;
-  for (int i = 0; i < lead; ++i) if (dilations[i] != 1) return SVDD_E_ARG;
-  BackboneArgs a;
-  if (!backbone_args(a, x, table0, tiles, vec, w2, out, n, L, 1, nlayers, dilations)) return SVDD_E_ARG;
-  a.planes = planes; a.planes_P = lead;
-  const SvddLds lds = svdd_lds_raised(backbone_lds_bytes(nlayers, 3));
-  SvddSpan span(SVDD_SLOT_BACKBONE);                      // ONE span per forward over all its launches
-  if (first) {                                            // the whole forward, which also fills the planes; the tokens become the carried ones
-    if (hipMemcpyAsync(x_prev, x, (size_t)n * L, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return SVDD_E_LAUNCH;
-    return svdd_launch_timed(span.all(), backbone_kernel<true, false, 1>, dim3((unsigned)n), dim3(512), lds, stream, a, BackboneSave{});
-  }
-  if (svdd_launch_timed(span.first(), backbone_worklist_kernel<>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, x, x_prev, n, L, lead,
-                        max_item, items, stat, backbone_reach(dilations, lead, lead)) != SVDD_OK)
-    return SVDD_E_LAUNCH;
-  BackboneSegArgs sa{x, table0, tiles, vec, planes, items, n, L, 0, nullptr, nullptr, 0};
-  const int rows = 16 * (max_item + 2);
-  const size_t slds = sizeof(float) * ((size_t)rows * BB_AP + 5 * (size_t)rows + rows + 8);
-  const dim3 sgrid((unsigned)n * SEG_SLOTS);
-  void (*seg)(BackboneSegArgs) = max_item == 4 ? backbone_seg_kernel<4> : backbone_seg_kernel<2>;
-  svdd_raise_lds_limit(seg, slds);                        // once for the `lead` launches below
-  for (int k = 1; k <= lead; ++k) {
-    sa.layer = k;
-    if (svdd_launch(seg, sgrid, dim3(256), slds, stream, sa) != SVDD_OK) return SVDD_E_LAUNCH;
-  }
-  return svdd_launch_timed(span.last(), backbone_kernel<true, false, 2>, dim3((unsigned)n), dim3(512), lds, stream, a, BackboneSave{});
-}
-
-// svdd_backbone_incr2_f32: the same forward with the segment launches reading a compact, size-ordered list. Workgroups per CU of
-// a segment launch: the dynamic-LDS request is padded until only g_incr_residency fit (0: no padding, as many as the kernel's own
-// image and registers allow — 4 for items of <= 2 tiles, 6 for 1-tile items, 3 for <= 4).
+// Workgroups per CU of a padded segment launch: its dynamic-LDS request is raised until only g_incr_residency fit (0: no padding, as
+// many as the kernel's own image and registers allow — 4 for items of <= 2 tiles, 6 for 1-tile items, 3 for <= 4, 5 for tight items).
 constexpr int INCR_DEFAULT_RESIDENCY = 0;
 constexpr size_t CU_LDS_BYTES = 160 * 1024;              // gfx950
 static int g_incr_residency = INCR_DEFAULT_RESIDENCY;
@@ -4072,148 +4038,127 @@ extern "C" int svdd_backbone_incr_set_residency(int wg_per_cu) {
   return SVDD_OK;
 }
 
+// Dynamic LDS of a segment workgroup whose image holds `rows` rows.
+static size_t seg_lds_bytes(int rows, bool pad) {
+  size_t bytes = sizeof(float) * ((size_t)rows * BB_AP + 5 * (size_t)rows + rows + 8);
+  if (pad && g_incr_residency > 0) {                     // one request more than CU_LDS_BYTES / (r + 1): r + 1 workgroups no longer fit
+    const size_t least = (CU_LDS_BYTES / (size_t)(g_incr_residency + 1) / 1024 + 1) * 1024;
+    if (least > bytes) bytes = least;
+  }
+  return bytes;
+}
+
+// The four incremental entries (include/svdd_hip.h states each one's contract) are ONE host path and differ in data: the kind of
+// work list, and the arguments an entry does not have (svdd_backbone_incr_f32 and incr2: depth = lead; all but incr4: parity 0).
+//   INCR_SLOT     svdd_backbone_incr_f32: backbone_worklist_kernel, then backbone_seg_kernel<2 | 4> with one workgroup per (row, slot),
+//                 empty slots included; max_item 2 or 4, any n, never padded.
+//   INCR_ORDERED  incr2, incr3: + backbone_order_kernel (untimed), and the segment launches read its compact, size-ordered list:
+//                 backbone_seg_kernel<1 | 2 | 4, true>; n <= 65536 (order packs row << 16 | item).
+//   INCR_TIGHT    incr4: ONE list launch (backbone_list_kernel) instead of work list + order; the dilation-1 layers run TIGHT items
+//                 (tiles that start at the first row a change reaches, not at a multiple of 16) on backbone_seg_tight_kernel, whose image
+//                 holds the 4 halo rows per side instead of a halo tile; max_item 2. The carried tokens are a ping-pong pair, so the
+//                 list launch never reads what it writes: `parity` names the buffer that holds them (0: x_prev, 1: x_prev2); a
+//                 first == 0 call writes x into the other one.
+// Planes 1 .. depth are carried: layers 1 .. lead (dilation 1) on the list kind's kernel, layers lead + 1 .. depth (dilation 4) on
+// backbone_seg_kernel<.., true, 4> with aligned items, the tail (backbone_kernel<.., 2>) from plane `depth`. first: the whole forward,
+// which also fills the planes; the tokens become the carried ones. Every refusal comes before the span and before any HIP call.
+enum IncrList { INCR_SLOT, INCR_ORDERED, INCR_TIGHT };
+
+struct IncrCall {
+  const uint8_t* x; const float *table0, *tiles, *vec, *w2; float* out; int n, L, nlayers; const int* dilations; int lead;
+  float* planes; uint8_t* x_prev; int32_t* items; unsigned long long* stat; int first, max_item;
+  int32_t *order, *order_count; int depth; uint8_t* x_prev2; int parity; void* stream;
+};
+
+typedef void (*BackboneSegKernel)(BackboneSegArgs);
+static BackboneSegKernel backbone_seg_choice(IncrList list, int mi, bool dilation4) {
+  if (dilation4) return mi == 4 ? backbone_seg_kernel<4, true, 4> : mi == 2 ? backbone_seg_kernel<2, true, 4> : backbone_seg_kernel<1, true, 4>;
+  if (list == INCR_TIGHT) return backbone_seg_tight_kernel;
+  if (list == INCR_SLOT) return mi == 4 ? backbone_seg_kernel<4> : backbone_seg_kernel<2>;
+  return mi == 4 ? backbone_seg_kernel<4, true> : mi == 2 ? backbone_seg_kernel<2, true> : backbone_seg_kernel<1, true>;
+}
+
+static int backbone_incr(IncrList list, const IncrCall& c) {
+  const bool ordered = list != INCR_SLOT, tight = list == INCR_TIGHT;   // ordered: the segment launches read order / order_count
+  const int n = c.n, L = c.L, mi = c.max_item, lead = c.lead, depth = c.depth;
+  if (!c.x || !c.table0 || !c.tiles || !c.vec || !c.w2 || !c.out || !c.dilations || !c.planes || !c.x_prev || !c.items || n <= 0 ||
+      L <= TW_ROWS / 2 || L > TW_ROWS || c.nlayers <= 0 || c.nlayers > BB_MAXL || lead < 2 || lead > c.nlayers || depth < lead ||
+      depth > c.nlayers || !(mi == 2 || (mi == 4 && !tight) || (mi == 1 && list == INCR_ORDERED)) ||
+      (ordered && (!c.order || !c.order_count || n > 65536)) ||
+      (tight && (!c.x_prev2 || c.x_prev2 == c.x_prev || (c.parity != 0 && c.parity != 1))))
+    return SVDD_E_ARG;
+  for (int i = 0; i < depth; ++i) if (c.dilations[i] != (i < lead ? 1 : 4)) return SVDD_E_ARG;
+  BackboneArgs a;
+  if (!backbone_args(a, c.x, c.table0, c.tiles, c.vec, c.w2, c.out, n, L, 1, c.nlayers, c.dilations)) return SVDD_E_ARG;
+  a.planes = c.planes; a.planes_P = depth;
+  uint8_t* x_cur = c.parity ? c.x_prev2 : c.x_prev;      // the carried tokens
+  uint8_t* x_next = c.parity ? c.x_prev : c.x_prev2;     // tight only: where this forward's tokens go
+  const SvddLds lds = svdd_lds_raised(backbone_lds_bytes(c.nlayers, 3));
+  SvddSpan span(SVDD_SLOT_BACKBONE);                      // ONE span per forward over all its launches
+  if (c.first) {
+    if (hipMemcpyAsync(x_cur, c.x, (size_t)n * L, hipMemcpyDeviceToDevice, (hipStream_t)c.stream) != hipSuccess) return SVDD_E_LAUNCH;
+    return svdd_launch_timed(span.all(), backbone_kernel<true, false, 1>, dim3((unsigned)n), dim3(512), lds, c.stream, a, BackboneSave{});
+  }
+  const int slots = mi == 1 ? TW_RT : SEG_SLOTS;          // 13 one-tile items in a row that changed everywhere
+  const BackboneReach reach = backbone_reach(c.dilations, depth, lead);
+  int rc;
+  if (tight) {
+    rc = svdd_launch_timed(span.first(), backbone_list_kernel, dim3((unsigned)depth), dim3(256), 0, c.stream, c.x, (const uint8_t*)x_cur, x_next,
+                           n, L, mi, c.items, c.order, c.order_count, c.stat, reach);
+  } else {
+    rc = svdd_launch_timed(span.first(), mi == 1 ? backbone_worklist_kernel<TW_RT> : backbone_worklist_kernel<SEG_SLOTS>,
+                           dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c.stream, c.x, c.x_prev, n, L, depth, mi, c.items, c.stat, reach);
+    if (rc == SVDD_OK && ordered)
+      rc = svdd_launch(mi == 1 ? backbone_order_kernel<TW_RT> : backbone_order_kernel<SEG_SLOTS>, dim3((unsigned)depth), dim3(256), 0, c.stream,
+                       c.items, n, c.order, c.order_count);
+  }
+  if (rc != SVDD_OK) return SVDD_E_LAUNCH;
+  BackboneSegArgs sa{c.x, c.table0, c.tiles, c.vec, c.planes, c.items, n, L, 0, nullptr, nullptr, 0};
+  if (ordered) { sa.order = c.order; sa.order_count = c.order_count; sa.order_stride = n * slots; }
+  // [0]: the dilation-1 layers, [1]: the dilation-4 layers. An aligned item's image is its tiles and a halo tile per side.
+  const BackboneSegKernel seg[2] = {backbone_seg_choice(list, mi, false), backbone_seg_choice(list, mi, true)};
+  const size_t slds[2] = {seg_lds_bytes(tight ? 16 * mi + 8 : 16 * (mi + 2), ordered), seg_lds_bytes(16 * (mi + 2), ordered)};
+  svdd_raise_lds_limit(seg[0], slds[0]);                  // once per kernel for the launches below
+  if (depth > lead) svdd_raise_lds_limit(seg[1], slds[1]);
+  const dim3 sgrid((unsigned)n * slots);
+  for (int k = 1; k <= depth; ++k) {
+    sa.layer = k;
+    if (svdd_launch(seg[k > lead], sgrid, dim3(256), slds[k > lead], c.stream, sa) != SVDD_OK) return SVDD_E_LAUNCH;
+  }
+  return svdd_launch_timed(span.last(), backbone_kernel<true, false, 2>, dim3((unsigned)n), dim3(512), lds, c.stream, a, BackboneSave{});
+}
+
+extern "C" int svdd_backbone_incr_f32(const uint8_t* x, const float* table0, const float* tiles, const float* vec, const float* w2,
+                                      float* out, int n, int L, int nlayers, const int* dilations, int lead, float* planes,
+                                      uint8_t* x_prev, int32_t* items, unsigned long long* stat, int first, int max_item,
+                                      void* stream) {
+  return backbone_incr(INCR_SLOT, IncrCall{x, table0, tiles, vec, w2, out, n, L, nlayers, dilations, lead, planes, x_prev, items, stat, first,
+                                           max_item, nullptr, nullptr, lead, nullptr, 0, stream});
+}
+
 extern "C" int svdd_backbone_incr2_f32(const uint8_t* x, const float* table0, const float* tiles, const float* vec, const float* w2,
                                        float* out, int n, int L, int nlayers, const int* dilations, int lead, float* planes,
                                        uint8_t* x_prev, int32_t* items, unsigned long long* stat, int first, int max_item,
                                        int32_t* order, int32_t* order_count, void* stream) {
-  if (!x || !table0 || !tiles || !vec || !w2 || !out || !dilations || !planes || !x_prev || !items || !order || !order_count ||
-      n <= 0 || n > 65536 || L <= TW_ROWS / 2 || L > TW_ROWS || nlayers <= 0 || nlayers > BB_MAXL || lead < 2 || lead > nlayers ||
-      (max_item != 1 && max_item != 2 && max_item != 4))
-    return SVDD_E_ARG;
-  for (int i = 0; i < lead; ++i) if (dilations[i] != 1) return SVDD_E_ARG;
-  BackboneArgs a;
-  if (!backbone_args(a, x, table0, tiles, vec, w2, out, n, L, 1, nlayers, dilations)) return SVDD_E_ARG;
-  a.planes = planes; a.planes_P = lead;
-  const SvddLds lds = svdd_lds_raised(backbone_lds_bytes(nlayers, 3));
-  SvddSpan span(SVDD_SLOT_BACKBONE);                      // ONE span per forward over all its launches
-  if (first) {
-    if (hipMemcpyAsync(x_prev, x, (size_t)n * L, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return SVDD_E_LAUNCH;
-    return svdd_launch_timed(span.all(), backbone_kernel<true, false, 1>, dim3((unsigned)n), dim3(512), lds, stream, a, BackboneSave{});
-  }
-  const int slots = max_item == 1 ? TW_RT : SEG_SLOTS;    // 13 one-tile items in a row that changed everywhere
-  if (svdd_launch_timed(span.first(), max_item == 1 ? backbone_worklist_kernel<TW_RT> : backbone_worklist_kernel<SEG_SLOTS>,
-                        dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, x, x_prev, n, L, lead, max_item, items, stat,
-                        backbone_reach(dilations, lead, lead)) != SVDD_OK)
-    return SVDD_E_LAUNCH;
-  if (svdd_launch(max_item == 1 ? backbone_order_kernel<TW_RT> : backbone_order_kernel<SEG_SLOTS>, dim3((unsigned)lead), dim3(256), 0, stream,
-                  items, n, order, order_count) != SVDD_OK)
-    return SVDD_E_LAUNCH;
-  BackboneSegArgs sa{x, table0, tiles, vec, planes, items, n, L, 0, order, order_count, n * slots};
-  const int rows = 16 * (max_item + 2);
-  size_t slds = sizeof(float) * ((size_t)rows * BB_AP + 5 * (size_t)rows + rows + 8);
-  if (g_incr_residency > 0) {                             // one request more than CU_LDS_BYTES / (r + 1): r + 1 workgroups no longer fit
-    const size_t pad = (CU_LDS_BYTES / (size_t)(g_incr_residency + 1) / 1024 + 1) * 1024;
-    if (pad > slds) slds = pad;
-  }
-  const dim3 sgrid((unsigned)(n * slots));
-  void (*seg)(BackboneSegArgs) = max_item == 4 ? backbone_seg_kernel<4, true> : max_item == 2 ? backbone_seg_kernel<2, true>
-                                                                                                : backbone_seg_kernel<1, true>;
-  svdd_raise_lds_limit(seg, slds);                        // once for the `lead` launches below
-  for (int k = 1; k <= lead; ++k) {
-    sa.layer = k;
-    if (svdd_launch(seg, sgrid, dim3(256), slds, stream, sa) != SVDD_OK) return SVDD_E_LAUNCH;
-  }
-  return svdd_launch_timed(span.last(), backbone_kernel<true, false, 2>, dim3((unsigned)n), dim3(512), lds, stream, a, BackboneSave{});
+  return backbone_incr(INCR_ORDERED, IncrCall{x, table0, tiles, vec, w2, out, n, L, nlayers, dilations, lead, planes, x_prev, items, stat, first,
+                                              max_item, order, order_count, lead, nullptr, 0, stream});
 }
 
-// svdd_backbone_incr3_f32: svdd_backbone_incr2_f32 with the carried planes extended through the run of dilation-4 layers behind the
-// `lead` dilation-1 layers: planes 1 .. depth, layers lead + 1 .. depth on backbone_seg_kernel<.., 4>, the tail from plane `depth`.
 extern "C" int svdd_backbone_incr3_f32(const uint8_t* x, const float* table0, const float* tiles, const float* vec, const float* w2,
                                        float* out, int n, int L, int nlayers, const int* dilations, int lead, float* planes,
                                        uint8_t* x_prev, int32_t* items, unsigned long long* stat, int first, int max_item,
                                        int32_t* order, int32_t* order_count, int depth, void* stream) {
-  if (!x || !table0 || !tiles || !vec || !w2 || !out || !dilations || !planes || !x_prev || !items || !order || !order_count ||
-      n <= 0 || n > 65536 || L <= TW_ROWS / 2 || L > TW_ROWS || nlayers <= 0 || nlayers > BB_MAXL || lead < 2 || lead > nlayers ||
-      (max_item != 1 && max_item != 2 && max_item != 4) || depth < lead || depth > nlayers)
-    return SVDD_E_ARG;
-  for (int i = 0; i < depth; ++i) if (dilations[i] != (i < lead ? 1 : 4)) return SVDD_E_ARG;
-  BackboneArgs a;
-  if (!backbone_args(a, x, table0, tiles, vec, w2, out, n, L, 1, nlayers, dilations)) return SVDD_E_ARG;
-  a.planes = planes; a.planes_P = depth;
-  const SvddLds lds = svdd_lds_raised(backbone_lds_bytes(nlayers, 3));
-  SvddSpan span(SVDD_SLOT_BACKBONE);                      // ONE span per forward over all its launches
-  if (first) {
-    if (hipMemcpyAsync(x_prev, x, (size_t)n * L, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return SVDD_E_LAUNCH;
-    return svdd_launch_timed(span.all(), backbone_kernel<true, false, 1>, dim3((unsigned)n), dim3(512), lds, stream, a, BackboneSave{});
-  }
-  const int slots = max_item == 1 ? TW_RT : SEG_SLOTS;
-  if (svdd_launch_timed(span.first(), max_item == 1 ? backbone_worklist_kernel<TW_RT> : backbone_worklist_kernel<SEG_SLOTS>,
-                        dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, x, x_prev, n, L, depth, max_item, items, stat,
-                        backbone_reach(dilations, depth, lead)) != SVDD_OK)
-    return SVDD_E_LAUNCH;
-  if (svdd_launch(max_item == 1 ? backbone_order_kernel<TW_RT> : backbone_order_kernel<SEG_SLOTS>, dim3((unsigned)depth), dim3(256), 0, stream,
-                  items, n, order, order_count) != SVDD_OK)
-    return SVDD_E_LAUNCH;
-  BackboneSegArgs sa{x, table0, tiles, vec, planes, items, n, L, 0, order, order_count, n * slots};
-  const int rows = 16 * (max_item + 2);
-  size_t slds = sizeof(float) * ((size_t)rows * BB_AP + 5 * (size_t)rows + rows + 8);
-  if (g_incr_residency > 0) {
-    const size_t pad = (CU_LDS_BYTES / (size_t)(g_incr_residency + 1) / 1024 + 1) * 1024;
-    if (pad > slds) slds = pad;
-  }
-  const dim3 sgrid((unsigned)(n * slots));
-  void (*seg1)(BackboneSegArgs) = max_item == 4 ? backbone_seg_kernel<4, true> : max_item == 2 ? backbone_seg_kernel<2, true>
-                                                                                                 : backbone_seg_kernel<1, true>;
-  void (*seg4)(BackboneSegArgs) = max_item == 4 ? backbone_seg_kernel<4, true, 4> : max_item == 2 ? backbone_seg_kernel<2, true, 4>
-                                                                                                    : backbone_seg_kernel<1, true, 4>;
-  svdd_raise_lds_limit(seg1, slds);
-  if (depth > lead) svdd_raise_lds_limit(seg4, slds);
-  for (int k = 1; k <= depth; ++k) {
-    sa.layer = k;
-    if (svdd_launch(k <= lead ? seg1 : seg4, sgrid, dim3(256), slds, stream, sa) != SVDD_OK) return SVDD_E_LAUNCH;
-  }
-  return svdd_launch_timed(span.last(), backbone_kernel<true, false, 2>, dim3((unsigned)n), dim3(512), lds, stream, a, BackboneSave{});
+  return backbone_incr(INCR_ORDERED, IncrCall{x, table0, tiles, vec, w2, out, n, L, nlayers, dilations, lead, planes, x_prev, items, stat, first,
+                                              max_item, order, order_count, depth, nullptr, 0, stream});
 }
 
-// svdd_backbone_incr4_f32: svdd_backbone_incr3_f32 with the stem doing less. ONE list launch (backbone_list_kernel) instead of work
-// list + order; the dilation-1 layers run TIGHT items (tiles that start at the first row a change reaches, not at a multiple of 16)
-// on backbone_seg_tight_kernel, whose image holds the 4 halo rows per side instead of a halo tile; the dilation-4 layers keep their
-// aligned items and backbone_seg_kernel<2, true, 4>. The carried tokens are a ping-pong pair, so the list launch never reads what
-// it writes: `parity` names the buffer that holds them (0: x_prev, 1: x_prev2); a first == 0 call writes x into the other one.
 extern "C" int svdd_backbone_incr4_f32(const uint8_t* x, const float* table0, const float* tiles, const float* vec, const float* w2,
                                        float* out, int n, int L, int nlayers, const int* dilations, int lead, float* planes,
                                        uint8_t* x_prev, int32_t* items, unsigned long long* stat, int first, int max_item,
                                        int32_t* order, int32_t* order_count, int depth, uint8_t* x_prev2, int parity,
                                        void* on_stream) {
-  if (!x || !table0 || !tiles || !vec || !w2 || !out || !dilations || !planes || !x_prev || !items || !order || !order_count ||
-      !x_prev2 || x_prev2 == x_prev || n <= 0 || n > 65536 || L <= TW_ROWS / 2 || L > TW_ROWS || nlayers <= 0 || nlayers > BB_MAXL ||
-      lead < 2 || lead > nlayers || max_item != 2 || depth < lead || depth > nlayers || (parity != 0 && parity != 1))
-    return SVDD_E_ARG;
-  for (int i = 0; i < depth; ++i) if (dilations[i] != (i < lead ? 1 : 4)) return SVDD_E_ARG;
-  BackboneArgs a;
-  if (!backbone_args(a, x, table0, tiles, vec, w2, out, n, L, 1, nlayers, dilations)) return SVDD_E_ARG;
-  a.planes = planes; a.planes_P = depth;
-  hipStream_t stream = (hipStream_t)on_stream;
-  uint8_t* x_cur = parity ? x_prev2 : x_prev;
-  uint8_t* x_next = parity ? x_prev : x_prev2;
-  const SvddLds lds = svdd_lds_raised(backbone_lds_bytes(nlayers, 3));
-  SvddSpan span(SVDD_SLOT_BACKBONE);                      // ONE span per forward over all its launches
-  if (first) {
-    if (hipMemcpyAsync(x_cur, x, (size_t)n * L, hipMemcpyDeviceToDevice, stream) != hipSuccess) return SVDD_E_LAUNCH;
-    return svdd_launch_timed(span.all(), backbone_kernel<true, false, 1>, dim3((unsigned)n), dim3(512), lds, stream, a, BackboneSave{});
-  }
-  if (svdd_launch_timed(span.first(), backbone_list_kernel, dim3((unsigned)depth), dim3(256), 0, stream, x, (const uint8_t*)x_cur, x_next, n,
-                        L, max_item, items, order, order_count, stat, backbone_reach(dilations, depth, lead)) != SVDD_OK)
-    return SVDD_E_LAUNCH;
-  BackboneSegArgs sa{x, table0, tiles, vec, planes, items, n, L, 0, order, order_count, n * SEG_SLOTS};
-  const int rows1 = 16 * max_item + 8, rows4 = 16 * (max_item + 2);
-  size_t slds1 = sizeof(float) * ((size_t)rows1 * BB_AP + 5 * (size_t)rows1 + rows1 + 8);
-  size_t slds4 = sizeof(float) * ((size_t)rows4 * BB_AP + 5 * (size_t)rows4 + rows4 + 8);
-  if (g_incr_residency > 0) {
-    const size_t pad = (CU_LDS_BYTES / (size_t)(g_incr_residency + 1) / 1024 + 1) * 1024;
-    if (pad > slds1) slds1 = pad;
-    if (pad > slds4) slds4 = pad;
-  }
-  const dim3 sgrid((unsigned)(n * SEG_SLOTS));
-  void (*seg1)(BackboneSegArgs) = backbone_seg_tight_kernel;
-  void (*seg4)(BackboneSegArgs) = backbone_seg_kernel<2, true, 4>;
-  svdd_raise_lds_limit(seg1, slds1);
-  if (depth > lead) svdd_raise_lds_limit(seg4, slds4);
-  for (int k = 1; k <= depth; ++k) {
-    sa.layer = k;
-    if (svdd_launch(k <= lead ? seg1 : seg4, sgrid, dim3(256), k <= lead ? slds1 : slds4, stream, sa) != SVDD_OK) return SVDD_E_LAUNCH;
-  }
-  return svdd_launch_timed(span.last(), backbone_kernel<true, false, 2>, dim3((unsigned)n), dim3(512), lds, stream, a, BackboneSave{});
+  return backbone_incr(INCR_TIGHT, IncrCall{x, table0, tiles, vec, w2, out, n, L, nlayers, dilations, lead, planes, x_prev, items, stat, first,
+                                            max_item, order, order_count, depth, x_prev2, parity, on_stream});
 }
 
 typedef decltype(&value_tail_kernel<1>) ValueTailKernel;

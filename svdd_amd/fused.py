@@ -446,13 +446,13 @@ def following_dilation4(dil):
 
 
 class IncrementalStem:
-    """Caller-owned state of svdd_backbone_incr2_f32 / svdd_backbone_incr3_f32 for n sequences of length L: the carried planes (the
-    `lead` dilation-1 layers and `deep` dilation-4 layers behind them), the tokens they belong to, the step's work list, its
-    size-ordered form (order, order_count) and the device counters of marked tile-layers (stat[0]: the dilation-1 layers, stat[1]: the
-    deeper ones). Allocated once and reused across decodes (FusedBackbone keeps one per shape); `valid` says whether planes / x_prev
-    describe the tokens of the last forward of THIS decode. tight: forwards go through svdd_backbone_incr4_f32 (tight items for the
-    dilation-1 layers, the list in one launch), which keeps the tokens in the pair (x_prev, x_prev2); `parity` says which of the two
-    holds them."""
+    """Caller-owned state of the incremental backbone entries (backbone_cnn_incremental names which one a stem reaches) for n
+    sequences of length L: the carried planes (the `lead` dilation-1 layers and `deep` dilation-4 layers behind them), the tokens they
+    belong to, the step's work list, its size-ordered form (order, order_count) and the device counters of marked tile-layers (stat[0]:
+    the dilation-1 layers, stat[1]: the deeper ones). Allocated once and reused across decodes (FusedBackbone keeps one per shape);
+    `valid` says whether planes / x_prev describe the tokens of the last forward of THIS decode. tight: svdd_backbone_incr4_f32 (tight
+    items for the dilation-1 layers, the list in one launch), which keeps the tokens in the pair (x_prev, x_prev2); `parity` says
+    which of the two holds them."""
 
     def __init__(self, n, L, lead, dev, deep=0, tight=False):
         self.n, self.L, self.lead, self.deep, self.tight = n, L, lead, deep, tight
@@ -470,33 +470,31 @@ class IncrementalStem:
 
 
 def backbone_cnn_incremental(tokens, pk, st, out=None, max_item=None):
-    """backbone_cnn(tokens, pk) — the same bits — through the carried stem `st` (HIP entry svdd_backbone_incr2_f32; with st.deep > 0
-    svdd_backbone_incr3_f32): the first call after st.valid = False runs the whole forward and fills the planes, every later one
-    recomputes only the tiles of the carried layers that a changed token can reach, then the remaining layers from the last plane.
-    With st.tight (and items of 2 tiles) the entry is svdd_backbone_incr4_f32."""
+    """backbone_cnn(tokens, pk) — the same bits — through the carried stem `st`: the first call after st.valid = False runs the whole
+    forward and fills the planes, every later one recomputes only the tiles of the carried layers that a changed token can reach, then
+    the remaining layers from the last plane. The HIP entry: svdd_backbone_incr4_f32 with st.tight and items of 2 tiles; else
+    svdd_backbone_incr3_f32 with st.deep > 0; else svdd_backbone_incr2_f32, or svdd_backbone_incr_f32 where INCR_ORDERED is off."""
     assert tokens.is_cuda and tokens.dtype == torch.uint8 and tokens.is_contiguous() and tuple(tokens.shape) == (st.n, st.L)
     n, L = tokens.shape
     if out is None:
         out = torch.empty((n, L, 5), dtype=torch.float32, device=tokens.device)
     dil = (ctypes.c_int * len(pk["dil"]))(*pk["dil"])
     first = not st.valid
-    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)        # these entries take their stream as an explicit argument
-    if st.tight and int(max_item or INCR_MAX_ITEM) == 2:
-        _lib.call("svdd_backbone_incr4_f32", tokens, pk["table0"], pk["tiles"], pk["vec"], pk["w2"], out, n, L, len(pk["dil"]), dil,
-                  st.lead, st.planes, st.x_prev, st.items, st.stat, int(first), 2, st.order, st.order_count, st.lead + st.deep,
-                  st.x_prev2, st.parity, stream)
-        st.parity ^= 0 if first else 1                   # an incremental forward leaves the tokens in the other buffer
+    max_item = int(max_item or INCR_MAX_ITEM)
+    tight = st.tight and max_item == 2
+    if tight:
+        entry, extra = "svdd_backbone_incr4_f32", (st.order, st.order_count, st.lead + st.deep, st.x_prev2, st.parity)
     elif st.deep > 0:
-        _lib.call("svdd_backbone_incr3_f32", tokens, pk["table0"], pk["tiles"], pk["vec"], pk["w2"], out, n, L, len(pk["dil"]), dil,
-                  st.lead, st.planes, st.x_prev, st.items, st.stat, int(first), int(max_item or INCR_MAX_ITEM), st.order,
-                  st.order_count, st.lead + st.deep, stream)
+        entry, extra = "svdd_backbone_incr3_f32", (st.order, st.order_count, st.lead + st.deep)
     elif INCR_ORDERED:
-        _lib.call("svdd_backbone_incr2_f32", tokens, pk["table0"], pk["tiles"], pk["vec"], pk["w2"], out, n, L, len(pk["dil"]), dil,
-                  st.lead, st.planes, st.x_prev, st.items, st.stat, int(first), int(max_item or INCR_MAX_ITEM), st.order,
-                  st.order_count, stream)
+        entry, extra = "svdd_backbone_incr2_f32", (st.order, st.order_count)
     else:
-        _lib.call("svdd_backbone_incr_f32", tokens, pk["table0"], pk["tiles"], pk["vec"], pk["w2"], out, n, L, len(pk["dil"]), dil,
-                  st.lead, st.planes, st.x_prev, st.items, st.stat, int(first), int(max_item or INCR_MAX_ITEM), stream)
+        entry, extra = "svdd_backbone_incr_f32", ()
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)        # these entries take their stream as an explicit argument
+    _lib.call(entry, tokens, pk["table0"], pk["tiles"], pk["vec"], pk["w2"], out, n, L, len(pk["dil"]), dil, st.lead, st.planes, st.x_prev,
+              st.items, st.stat, int(first), max_item, *extra, stream)
+    if tight and not first:
+        st.parity ^= 1                                   # an incremental forward leaves the tokens in the other buffer
     st.valid = True
     st.forwards += 0 if first else 1
     return out

@@ -15,15 +15,13 @@ the non-empty (row, item) pairs; tile counts along the list never increase; the 
 made again with x_prev put back gives the same out, planes, items, order_count and the same multiset in order.
 One more case: 300 rows at L = 200, 2 steps, 5 changes per row, at residencies that leave fewer resident workgroup slots than items
 (the dispatcher then hands later entries to CUs as they free up), compared with the one-launch kernel on all rows."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
 from svdd_amd import _lib, fused
-from tests import net_ref as N
-from tests.kernel_harness import DEV, SENT32, _Buf, _st
+from tests.incr_harness import Stem, check_order as _check_lists, distinct_pack, one_launch as _one_launch, slots as _slots
+from tests.kernel_harness import DEV, SENT32
 
 pytestmark = pytest.mark.gpu
 MASK, ROWS, STEPS = 4, 8, 4
@@ -31,14 +29,7 @@ MASK, ROWS, STEPS = 4, 8, 4
 
 @pytest.fixture(scope="module")
 def cnn_pack():
-    from svdd_amd import backbone, config
-    torch.manual_seed(11)
-    cnn = N.distinct_layers(backbone.CNNModel(config.dna_config().model, alphabet_size=5).eval(), 3).to(DEV)
-    return fused.pack_backbone(cnn)
-
-
-def _slots(max_item):
-    return 13 if max_item == 1 else 7
+    return distinct_pack()
 
 
 def _script(L, seed):
@@ -90,65 +81,9 @@ def _expected_items(prev, new, L, P, max_item):
     return torch.from_numpy(items)
 
 
-class _Stem:
-    """Sentinel-guarded buffers of one carried stem of n rows; run() goes to the ordered entry, run_old() to svdd_backbone_incr_f32."""
-
-    def __init__(self, pk, n, L, max_item):
-        self.pk, self.n, self.L, self.mi, self.S, self.P = pk, n, L, max_item, _slots(max_item), fused.leading_dilation1(pk["dil"])
-        self.planes, self.items = _Buf(self.P * n * 208 * 128), _Buf(self.P * n * self.S, torch.int32)
-        self.order, self.count = _Buf(self.P * n * self.S, torch.int32), _Buf(self.P, torch.int32)
-        self.x_prev, self.out = _Buf(n * L, torch.uint8), _Buf(n * L * 5)
-        self.dil = (ctypes.c_int * len(pk["dil"]))(*pk["dil"])
-
-    def _args(self, tok, first):
-        pk = self.pk
-        return (tok, pk["table0"], pk["tiles"], pk["vec"], pk["w2"], self.out.ptr, self.n, self.L, len(pk["dil"]), self.dil, self.P,
-                self.planes.ptr, self.x_prev.ptr, self.items.ptr, None, int(first), self.mi)
-
-    def _done(self):
-        torch.cuda.synchronize()
-        for b in (self.planes, self.items, self.order, self.count, self.x_prev, self.out):
-            b.untouched()                                           # asserts both guards of the buffer
-        return self.out.body().view(self.n, self.L, 5).clone()
-
-    def run(self, tok, first):
-        _lib.call("svdd_backbone_incr2_f32", *self._args(tok, first), self.order.ptr, self.count.ptr, _st())
-        return self._done()
-
-    def run_old(self, tok, first):
-        _lib.call("svdd_backbone_incr_f32", *self._args(tok, first), _st())
-        return self._done()
-
-    def lists(self):
-        """items [P][n][S], order_count [P], order [P][n * S] on the CPU."""
-        return (self.items.body().view(self.P, self.n, self.S).cpu(), self.count.body().cpu(),
-                self.order.body().view(self.P, self.n * self.S).cpu())
-
-
-def _check_lists(st, what):
-    """order_count, the multiset and the size order of `order` against `items`. -> the sorted entries per layer."""
-    items, count, order = st.lists()
-    rows = torch.arange(st.n, dtype=torch.int32)[None, :, None].expand_as(items)
-    ents = []
-    for k in range(st.P):
-        live = items[k] != 0
-        c = int(count[k])
-        assert c == int(live.sum()), f"{what}: order_count[{k}] = {c}, {int(live.sum())} non-empty slots"
-        want = (rows[k][live] << 16 | items[k][live]).sort().values
-        got = order[k, :c]
-        assert torch.equal(got.sort().values, want), f"{what}: order[{k}] is not the set of non-empty (row, item) pairs"
-        tiles = (got >> 8) & 0xFF
-        assert bool((tiles[1:] <= tiles[:-1]).all()), f"{what}: tile counts increase along order[{k}]"
-        ents.append(want)
-    return ents
-
-
-def _one_launch(tok, pk):
-    out = torch.empty((tok.shape[0], tok.shape[1], 5), dtype=torch.float32, device=DEV)
-    dil = (ctypes.c_int * len(pk["dil"]))(*pk["dil"])
-    _lib.call("svdd_backbone_cnn_f32", tok, pk["table0"], pk["tiles"], pk["vec"], pk["w2"], out, tok.shape[0], tok.shape[1],
-              len(pk["dil"]), dil, None, None, 0)
-    return out
+def _stem(pk, n, L, max_item):
+    """run() goes to the ordered entry, run_old() to svdd_backbone_incr_f32; stat is NULL."""
+    return Stem("svdd_backbone_incr2_f32", pk, n, L, None, max_item, stat=0)
 
 
 @pytest.fixture(autouse=True)
@@ -163,8 +98,8 @@ def test_ordered_chain(cnn_pack, L, max_item):
     pk = cnn_pack
     states = _script(L, 7 + L)
     dev = [s.to(DEV) for s in states]
-    new, old = _Stem(pk, ROWS, L, max_item), _Stem(pk, ROWS, L, max(max_item, 2))
-    P = new.P
+    new, old = _stem(pk, ROWS, L, max_item), _stem(pk, ROWS, L, max(max_item, 2))
+    P = new.D
     assert P == 8
     ref = old.run_old(dev[0], True)
     assert torch.equal(new.run(dev[0], True), ref)
@@ -177,7 +112,7 @@ def test_ordered_chain(cnn_pack, L, max_item):
         got, ref = new.run(dev[t], False), old.run_old(dev[t], False)
         assert torch.equal(got, ref), f"{what}: out differs from the old entry's"
         assert torch.equal(new.planes.bits(), old.planes.bits()), f"{what}: planes differ from the old entry's"
-        fresh = _Stem(pk, ROWS, L, max_item)
+        fresh = _stem(pk, ROWS, L, max_item)
         assert torch.equal(fresh.run(dev[t], True), got), f"{what}: out differs from a full forward's"
         assert torch.equal(new.planes.bits(), fresh.planes.bits()), f"{what}: planes differ from a full forward's"
         assert torch.equal(new.x_prev.body().view(ROWS, L), dev[t])
@@ -215,14 +150,14 @@ def test_more_items_than_resident_slots(cnn_pack, max_item, residency):
     states = [s.to(torch.uint8) for s in states]
     dev = [s.to(DEV) for s in states]
     fused.set_incr_residency(residency)
-    st = _Stem(pk, n, L, max_item)
+    st = _stem(pk, n, L, max_item)
     assert torch.equal(st.run(dev[0], True), _one_launch(dev[0], pk))
     ncu = _lib.device_info()[1]
     for t in (1, 2):
         got = st.run(dev[t], False)
         ref = _one_launch(dev[t], pk)
         assert torch.equal(got, ref), f"step {t}: rows {(got != ref).flatten(1).any(1).nonzero().flatten().tolist()[:8]} differ"
-        assert torch.equal(st.lists()[0], _expected_items(states[t - 1], states[t], L, st.P, max_item))
+        assert torch.equal(st.lists()[0], _expected_items(states[t - 1], states[t], L, st.D, max_item))
         _check_lists(st, f"n = 300, items <= {max_item}, step {t}")
         if residency:
             assert int(st.lists()[1].min()) > residency * ncu       # every layer's launch has more items than resident slots

@@ -29,15 +29,12 @@ Teeth, from runs of this file on one MI355X against deliberately broken builds o
     test_dropped_taps_issue_no_mfma fail on "tile .. of plane 9 differs where taps .. are dropped" (infinite weights in exactly
     the dropped taps turn a superfluous product into a NaN).
 The library as committed passes every case."""
-import ctypes
-
 import pytest
 import torch
 
-from svdd_amd import _lib, fused
 from tests import incr3_ref as R
-from tests import net_ref as N
-from tests.kernel_harness import DEV, SENT32, _Buf, _st
+from tests.incr_harness import Stem, check_order as _check_order, distinct_pack, one_launch as _one_launch
+from tests.kernel_harness import DEV, SENT32
 
 pytestmark = pytest.mark.gpu
 MASK, ROWS, STEPS = 4, 16, 12
@@ -45,10 +42,7 @@ MASK, ROWS, STEPS = 4, 16, 12
 
 @pytest.fixture(scope="module")
 def cnn_pack():
-    from svdd_amd import backbone, config
-    torch.manual_seed(11)
-    cnn = N.distinct_layers(backbone.CNNModel(config.dna_config().model, alphabet_size=5).eval(), 3).to(DEV)
-    return fused.pack_backbone(cnn)
+    return distinct_pack()
 
 
 _SCRIPTS = {}
@@ -95,57 +89,8 @@ def _script(L):
     return _SCRIPTS[L]
 
 
-class _Stem:
-    """Sentinel-guarded buffers of one carried stem of ROWS rows and `depth` planes."""
-
-    def __init__(self, pk, L, depth, max_item):
-        self.pk, self.L, self.D, self.mi, self.S = pk, L, depth, max_item, R.slots(max_item)
-        self.lead = fused.leading_dilation1(pk["dil"])
-        self.planes, self.items = _Buf(depth * ROWS * 208 * 128), _Buf(depth * ROWS * self.S, torch.int32)
-        self.order, self.count = _Buf(depth * ROWS * self.S, torch.int32), _Buf(depth, torch.int32)
-        self.x_prev, self.out = _Buf(ROWS * L, torch.uint8), _Buf(ROWS * L * 5)
-        self.stat = torch.zeros(2, dtype=torch.int64, device=DEV)
-        self.dil = (ctypes.c_int * len(pk["dil"]))(*pk["dil"])
-
-    def run(self, tok, first):
-        pk = self.pk
-        _lib.call("svdd_backbone_incr3_f32", tok, pk["table0"], pk["tiles"], pk["vec"], pk["w2"], self.out.ptr, ROWS, self.L,
-                  len(pk["dil"]), self.dil, self.lead, self.planes.ptr, self.x_prev.ptr, self.items.ptr, self.stat, int(first), self.mi,
-                  self.order.ptr, self.count.ptr, self.D, _st())
-        torch.cuda.synchronize()
-        for b in (self.planes, self.items, self.order, self.count, self.x_prev, self.out):
-            b.untouched()                                           # asserts both guards of the buffer
-        return self.out.body().view(ROWS, self.L, 5).clone()
-
-    def lists(self):
-        return (self.items.body().view(self.D, ROWS, self.S).cpu(), self.count.body().cpu(),
-                self.order.body().view(self.D, ROWS * self.S).cpu())
-
-
-def _check_order(st, what):
-    """order_count, the multiset and the size order of `order` against `items`. -> the sorted entries per layer."""
-    items, count, order = st.lists()
-    rows = torch.arange(ROWS, dtype=torch.int32)[None, :, None].expand_as(items)
-    ents = []
-    for k in range(st.D):
-        live = items[k] != 0
-        c = int(count[k])
-        assert c == int(live.sum()), f"{what}: order_count[{k}] = {c}, {int(live.sum())} non-empty slots"
-        want = (rows[k][live] << 16 | items[k][live]).sort().values
-        got = order[k, :c]
-        assert torch.equal(got.sort().values, want), f"{what}: order[{k}] is not the set of non-empty (row, item) pairs"
-        tiles = (got >> 8) & 0xFF
-        assert bool((tiles[1:] <= tiles[:-1]).all()), f"{what}: tile counts increase along order[{k}]"
-        ents.append(want)
-    return ents
-
-
-def _one_launch(tok, pk):
-    out = torch.empty((tok.shape[0], tok.shape[1], 5), dtype=torch.float32, device=DEV)
-    dil = (ctypes.c_int * len(pk["dil"]))(*pk["dil"])
-    _lib.call("svdd_backbone_cnn_f32", tok, pk["table0"], pk["tiles"], pk["vec"], pk["w2"], out, tok.shape[0], tok.shape[1],
-              len(pk["dil"]), dil, None, None, 0)
-    return out
+def _stem(pk, L, depth, max_item):
+    return Stem("svdd_backbone_incr3_f32", pk, ROWS, L, depth, max_item)
 
 
 CASES = [(200, 2, 12), (200, 1, 12), (200, 4, 12), (200, 2, 9), (200, 2, 10), (208, 2, 12), (193, 2, 12), (105, 2, 12)]
@@ -156,7 +101,7 @@ def test_deep_chain(cnn_pack, L, max_item, depth):
     pk = cnn_pack
     states = _script(L)
     dev = [s.to(DEV) for s in states]
-    st, fresh = _Stem(pk, L, depth, max_item), _Stem(pk, L, depth, max_item)
+    st, fresh = _stem(pk, L, depth, max_item), _stem(pk, L, depth, max_item)
     D, lead = depth, st.lead
     assert lead == 8 and list(pk["dil"][8:12]) == [4] * 4
     in_seq = torch.zeros(D, ROWS, 208, 128, dtype=torch.bool, device=DEV)
@@ -236,7 +181,7 @@ def test_dropped_taps_issue_no_mfma(cnn_pack, L, taps, tile):
         w[8, :, t] = float("inf")
     states = _script(L)
     dev = [s.to(DEV) for s in states]
-    st, fresh = _Stem(pk, L, 9, 2), _Stem(pk, L, 9, 2)
+    st, fresh = _stem(pk, L, 9, 2), _stem(pk, L, 9, 2)
     st.run(dev[0], True)
     st.run(dev[1], False)                                           # rows 1 and 2 changed at 0 and at L - 1: both end tiles are marked
     fresh.run(dev[1], True)

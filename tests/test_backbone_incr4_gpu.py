@@ -8,15 +8,13 @@ bit for bit, those of a fresh first = 1 forward of the same tokens; `items` equa
 order / order_count keep svdd_backbone_incr2_f32's contract; nothing outside the items' tiles changed in any plane, no row >= L and
 no guard was written; the tokens moved to the other buffer of the pair; a repeated call from the restored state writes the same
 lists and the same bits. A short SVDD-MC decode gives the same tokens with tight items, aligned items and the stem off."""
-import ctypes
-
 import pytest
 import torch
 
-from svdd_amd import _lib, fused
+from svdd_amd import fused
 from tests import incr4_ref as R
-from tests import net_ref as N
-from tests.kernel_harness import DEV, SENT32, _Buf, _st
+from tests.incr_harness import Stem, check_order as _check_order, distinct_pack, one_launch as _one_launch
+from tests.kernel_harness import DEV, SENT32
 
 pytestmark = pytest.mark.gpu
 MASK, ROWS, S = 4, 5, R.SEG_SLOTS
@@ -24,10 +22,7 @@ MASK, ROWS, S = 4, 5, R.SEG_SLOTS
 
 @pytest.fixture(scope="module")
 def cnn_pack():
-    from svdd_amd import backbone, config
-    torch.manual_seed(11)
-    cnn = N.distinct_layers(backbone.CNNModel(config.dna_config().model, alphabet_size=5).eval(), 3).to(DEV)
-    return fused.pack_backbone(cnn)
+    return distinct_pack()
 
 
 def _changes(L):
@@ -51,50 +46,6 @@ def _states(L):
     return [s.to(torch.uint8) for s in states]
 
 
-class _Stem:
-    """Sentinel-guarded buffers of one carried stem of ROWS rows and `depth` planes."""
-
-    def __init__(self, pk, L, depth):
-        self.pk, self.L, self.D = pk, L, depth
-        self.lead = fused.leading_dilation1(pk["dil"])
-        self.planes, self.items = _Buf(depth * ROWS * 208 * 128), _Buf(depth * ROWS * S, torch.int32)
-        self.order, self.count = _Buf(depth * ROWS * S, torch.int32), _Buf(depth, torch.int32)
-        self.tok = (_Buf(ROWS * L, torch.uint8), _Buf(ROWS * L, torch.uint8))
-        self.out = _Buf(ROWS * L * 5)
-        self.parity = 0
-        self.stat = torch.zeros(2, dtype=torch.int64, device=DEV)
-        self.dil = (ctypes.c_int * len(pk["dil"]))(*pk["dil"])
-
-    def run(self, tok, first):
-        pk = self.pk
-        _lib.call("svdd_backbone_incr4_f32", tok, pk["table0"], pk["tiles"], pk["vec"], pk["w2"], self.out.ptr, ROWS, self.L,
-                  len(pk["dil"]), self.dil, self.lead, self.planes.ptr, self.tok[0].ptr, self.items.ptr, self.stat, int(first), 2,
-                  self.order.ptr, self.count.ptr, self.D, self.tok[1].ptr, self.parity, _st())
-        torch.cuda.synchronize()
-        self.parity ^= 0 if first else 1
-        for b in (self.planes, self.items, self.order, self.count, self.out) + self.tok:
-            b.untouched()                                           # asserts both guards of the buffer
-        return self.out.body().view(ROWS, self.L, 5).clone()
-
-    def lists(self):
-        return (self.items.body().view(self.D, ROWS, S).cpu(), self.count.body().cpu(), self.order.body().view(self.D, ROWS * S).cpu())
-
-
-def _check_order(st, what):
-    """svdd_backbone_incr2_f32's contract: order_count, the multiset and the size order of `order` against `items`."""
-    items, count, order = st.lists()
-    rows = torch.arange(ROWS, dtype=torch.int32)[None, :, None].expand_as(items)
-    for k in range(st.D):
-        live = items[k] != 0
-        c = int(count[k])
-        assert c == int(live.sum()), f"{what}: order_count[{k}] = {c}, {int(live.sum())} non-empty slots"
-        want = (rows[k][live] << 16 | items[k][live]).sort().values
-        got = order[k, :c]
-        assert torch.equal(got.sort().values, want), f"{what}: order[{k}] is not the set of non-empty (row, item) pairs"
-        tiles = (got >> 8) & 0xFF
-        assert bool((tiles[1:] <= tiles[:-1]).all()), f"{what}: tile counts increase along order[{k}]"
-
-
 def _item_rows(items, lead, D):
     """bool [D][ROWS][208]: the rows of plane k that the items of layer k may write."""
     m = torch.zeros(D, ROWS, 208 + 16 * 2, dtype=torch.bool)
@@ -107,21 +58,13 @@ def _item_rows(items, lead, D):
     return m[:, :, :208]
 
 
-def _one_launch(tok, pk):
-    out = torch.empty((tok.shape[0], tok.shape[1], 5), dtype=torch.float32, device=DEV)
-    dil = (ctypes.c_int * len(pk["dil"]))(*pk["dil"])
-    _lib.call("svdd_backbone_cnn_f32", tok, pk["table0"], pk["tiles"], pk["vec"], pk["w2"], out, tok.shape[0], tok.shape[1],
-              len(pk["dil"]), dil, None, None, 0)
-    return out
-
-
 @pytest.mark.parametrize("depth", [8, 10, 12])
 @pytest.mark.parametrize("L", [105, 200, 208])
 def test_tight_chain(cnn_pack, L, depth):
     pk = cnn_pack
     states = _states(L)
     dev = [s.to(DEV) for s in states]
-    st, fresh = _Stem(pk, L, depth), _Stem(pk, L, depth)
+    st, fresh = (Stem("svdd_backbone_incr4_f32", pk, ROWS, L, depth) for _ in range(2))
     D, lead = depth, st.lead
     assert lead == 8 and list(pk["dil"][8:12]) == [4] * 4
     in_seq = torch.zeros(D, ROWS, 208, 128, dtype=torch.bool, device=DEV)

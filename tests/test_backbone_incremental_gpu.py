@@ -26,9 +26,9 @@ import ctypes
 import pytest
 import torch
 
-from svdd_amd import _lib, fused
-from tests import net_ref as N
-from tests.kernel_harness import DEV, SENT32, _Buf, _st
+from svdd_amd import _lib
+from tests.incr_harness import Stem, distinct_pack, one_launch as _one_launch
+from tests.kernel_harness import DEV, SENT32, _st
 
 pytestmark = pytest.mark.gpu
 MASK, SLOTS, STEPS, ROWS = 4, 7, 13, 16
@@ -36,10 +36,7 @@ MASK, SLOTS, STEPS, ROWS = 4, 7, 13, 16
 
 @pytest.fixture(scope="module")
 def cnn_pack():
-    from svdd_amd import backbone, config
-    torch.manual_seed(11)
-    cnn = N.distinct_layers(backbone.CNNModel(config.dna_config().model, alphabet_size=5).eval(), 3).to(DEV)
-    return fused.pack_backbone(cnn)
+    return distinct_pack()
 
 
 def _script(L, seed):
@@ -124,32 +121,6 @@ def _tile_elems(masks, P):
     return masks.repeat_interleave(16, dim=2)[..., None].expand(P, ROWS, 208, 128)
 
 
-class _Stem:
-    def __init__(self, pk, L):
-        self.pk, self.L, self.P = pk, L, fused.leading_dilation1(pk["dil"])
-        self.planes, self.items = _Buf(self.P * ROWS * 208 * 128), _Buf(self.P * ROWS * SLOTS, torch.int32)
-        self.x_prev, self.out = _Buf(ROWS * L, torch.uint8), _Buf(ROWS * L * 5)
-        self.stat = torch.zeros(1, dtype=torch.int64, device=DEV)
-        self.dil = (ctypes.c_int * len(pk["dil"]))(*pk["dil"])
-
-    def run(self, tok, first, max_item):
-        pk = self.pk
-        _lib.call("svdd_backbone_incr_f32", tok, pk["table0"], pk["tiles"], pk["vec"], pk["w2"], self.out.ptr, ROWS, self.L,
-                  len(pk["dil"]), self.dil, self.P, self.planes.ptr, self.x_prev.ptr, self.items.ptr, self.stat, int(first), max_item, _st())
-        torch.cuda.synchronize()
-        for b in (self.planes, self.items, self.x_prev, self.out):
-            b.untouched()                                           # guards intact
-        return self.out.body().view(ROWS, self.L, 5).clone()
-
-
-def _one_launch(tok, pk):
-    out = torch.empty((tok.shape[0], tok.shape[1], 5), dtype=torch.float32, device=DEV)
-    dil = (ctypes.c_int * len(pk["dil"]))(*pk["dil"])
-    _lib.call("svdd_backbone_cnn_f32", tok, pk["table0"], pk["tiles"], pk["vec"], pk["w2"], out, tok.shape[0], tok.shape[1],
-              len(pk["dil"]), dil, None, None, 0)
-    return out
-
-
 @pytest.mark.parametrize("max_item", [2, 4])
 @pytest.mark.parametrize("L", [200, 137])
 def test_incremental_chain(cnn_pack, L, max_item):
@@ -159,13 +130,13 @@ def test_incremental_chain(cnn_pack, L, max_item):
     full forward's" (layer 1 has no plane to confuse: it builds f_0 from the tokens)."""
     pk = cnn_pack
     states = [s.to(DEV) for s in _script(L, 5 + L)]
-    st = _Stem(pk, L)
-    P = st.P
+    st = Stem("svdd_backbone_incr_f32", pk, ROWS, L, None, max_item, stat=1)
+    P = st.D
     assert P == 8 and pk["dil"][P] != 1
     in_seq = torch.zeros(P, ROWS, 208, 128, dtype=torch.bool, device=DEV)
     in_seq[:, :, :L] = True
 
-    got = st.run(states[0], True, max_item)
+    got = st.run(states[0], True)
     assert torch.equal(got, _one_launch(states[0], pk))
     st.planes.assert_written_where("planes after the full forward", in_seq)
     st.x_prev.assert_written("x_prev")
@@ -187,7 +158,7 @@ def test_incremental_chain(cnn_pack, L, max_item):
         saved = (st.planes.bits().clone(), st.x_prev.bits().clone())
         st.planes.bits()[poison] = SENT32
         poisoned = st.planes.bits().clone()
-        got = st.run(tok, False, max_item)
+        got = st.run(tok, False)
         assert torch.equal(st.items.body().view(P, ROWS, SLOTS).cpu(), items), f"step {t}: work list"
         st.items.assert_written(f"step {t}: work list")
         left = st.planes.untouched()
@@ -199,8 +170,8 @@ def test_incremental_chain(cnn_pack, L, max_item):
         ref = _one_launch(tok, pk)
         assert torch.equal(st.x_prev.body().view(ROWS, L), tok)
         # the planes of a fresh full forward on the same tokens
-        fresh = _Stem(pk, L)
-        assert torch.equal(fresh.run(tok, True, max_item), ref)
+        fresh = Stem("svdd_backbone_incr_f32", pk, ROWS, L, None, max_item, stat=1)
+        assert torch.equal(fresh.run(tok, True), ref)
         keep = in_seq.reshape(-1)
         bad = (after != fresh.planes.bits()) & keep
         assert not bool(bad.any()), f"step {t}: plane {int(bad.nonzero()[0]) // (ROWS * 208 * 128) + 1} differs from a full forward's"
@@ -209,7 +180,7 @@ def test_incremental_chain(cnn_pack, L, max_item):
         st.planes.bits().copy_(poisoned)
         st.x_prev.bits().copy_(saved[1])
         st.items.bits().fill_(SENT32)
-        again = st.run(tok, False, max_item)
+        again = st.run(tok, False)
         assert torch.equal(again, got) and torch.equal(st.items.body().view(P, ROWS, SLOTS).cpu(), items)
         again_planes = st.planes.bits().clone()
         again_planes[poison] = saved[0][poison]
@@ -221,7 +192,7 @@ def test_incremental_chain(cnn_pack, L, max_item):
 def test_incremental_entry_rejects_what_it_cannot_run(cnn_pack):
     pk = cnn_pack
     tok = torch.zeros((ROWS, 200), dtype=torch.uint8, device=DEV)
-    st = _Stem(pk, 200)
+    st = Stem("svdd_backbone_incr_f32", pk, ROWS, 200, stat=1)
     dil = (ctypes.c_int * len(pk["dil"]))(*pk["dil"])
     args = lambda L, lead, mi: ("svdd_backbone_incr_f32", tok, pk["table0"], pk["tiles"], pk["vec"], pk["w2"], st.out.ptr, ROWS, L,
                                 len(pk["dil"]), dil, lead, st.planes.ptr, st.x_prev.ptr, st.items.ptr, None, 1, mi, _st())

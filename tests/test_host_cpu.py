@@ -279,6 +279,58 @@ def test_argument_validation_without_gpu():
     assert L.svdd_gru_bidir_bwd2_f32(one, one, one, one, one, None, None, 1, 1, None) == _lib.E_ARG                        # no output
 
 
+def test_incremental_backbone_entries_refuse_bad_arguments_without_gpu():
+    """The refusals of svdd_backbone_incr_f32 / incr2 / incr3 / incr4, per entry: every call differs in ONE argument from a call the
+    entry accepts (n = 1, L = 200, the dna config's 20 layers, lead = 8, depth 10 where there is one, items of 2 tiles, every pointer
+    non-NULL) and must answer E_ARG before the profile span and before any HIP call. Only refused calls are made: an accepted one would
+    go on to the device."""
+    from svdd_amd import _lib
+    lib = _lib.lib()
+    one, two = ctypes.c_void_p(64), ctypes.c_void_p(128)                   # non-NULL pointers that are never dereferenced
+    dna = (1,) * 8 + (4,) * 4 + (16,) * 4 + (64,) * 4
+    pointers = ("x", "table0", "tiles", "vec", "w2", "out", "dil", "planes", "x_prev", "items")
+    entries = {   # name: (has order lists, has depth, has the token pair, accepted max_item)
+        "svdd_backbone_incr_f32": (False, False, False, {2, 4}),
+        "svdd_backbone_incr2_f32": (True, False, False, {1, 2, 4}),
+        "svdd_backbone_incr3_f32": (True, True, False, {1, 2, 4}),
+        "svdd_backbone_incr4_f32": (True, True, True, {2}),
+    }
+
+    def with_dil(i, d):
+        return tuple(d if k == i else v for k, v in enumerate(dna))
+
+    for name, (ordered, deep, pair, accepted) in entries.items():
+        def call(**kw):
+            a = dict({p: one for p in pointers + ("stat", "order", "order_count")}, x_prev2=two, dil=dna, n=1, L=200, nlayers=20, lead=8,
+                     first=0, max_item=2, depth=10, parity=0)
+            assert set(kw) <= set(a), kw
+            a.update(kw)
+            dil = None if a["dil"] is None else (ctypes.c_int * len(a["dil"]))(*a["dil"])
+            args = [a["x"], a["table0"], a["tiles"], a["vec"], a["w2"], a["out"], a["n"], a["L"], a["nlayers"], dil, a["lead"], a["planes"],
+                    a["x_prev"], a["items"], a["stat"], a["first"], a["max_item"]]
+            args += [a["order"], a["order_count"]] if ordered else []
+            args += [a["depth"]] if deep else []
+            args += [a["x_prev2"], a["parity"]] if pair else []
+            return getattr(lib, name)(*args, None)
+
+        cases = [{p: None} for p in pointers]
+        cases += [dict(n=0), dict(L=104), dict(L=209), dict(nlayers=0), dict(nlayers=33), dict(lead=1), dict(lead=9)]
+        cases += [dict(max_item=m) for m in (0, 1, 2, 3, 4, 8) if m not in accepted]
+        cases += [dict(dil=with_dil(0, 0)), dict(dil=with_dil(19, 0)), dict(dil=with_dil(3, 2))]
+        if ordered:
+            cases += [dict(order=None), dict(order_count=None), dict(n=65537)]
+        if deep:
+            cases += [dict(depth=7), dict(depth=13), dict(depth=21), dict(dil=with_dil(8, 1)), dict(dil=with_dil(9, 1))]
+        if pair:
+            cases += [dict(x_prev2=None), dict(x_prev2=one), dict(parity=-1), dict(parity=2)]
+        assert len(cases) == {"svdd_backbone_incr_f32": 24, "svdd_backbone_incr2_f32": 26, "svdd_backbone_incr3_f32": 31,
+                              "svdd_backbone_incr4_f32": 37}[name]
+        for kw in cases:
+            assert call(**kw) == _lib.E_ARG, (name, kw)
+        for first in (0, 1):                                               # the refusals come before the `first` branch too
+            assert call(first=first, max_item=3) == _lib.E_ARG, (name, first)
+
+
 def test_row_movers_refuse_what_their_copy_units_cannot_address():
     """The bounds include/svdd_hip.h states for the row gathers, refused before anything touches the device:
     svdd_advance_rows copies 4-byte units at least (rows a multiple of 4, src and dst aligned to 4); svdd_select / _compact with the row
