@@ -22,22 +22,14 @@
 //   dn = dh' (1 - z) ; dz = dh' (h - n) ; da_n = dn (1 - n^2) ; da_r = da_n (W_hn h + b_hn) r (1 - r) ; da_z = dz z (1 - z)
 //   dx = W_ir^T da_r + W_iz^T da_z + W_in^T da_n ; dh = dh' z + W_hr^T da_r + W_hz^T da_z + W_hn^T (da_n r)
 #include "svdd_host.h"
+#include "svdd_device.h"   // sigmoid_fast / tanh_fast: the inference GRU's, so the forward pass gives the same bits
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int H = 64;          // hidden = input width
 // TS = 16 sequences per workgroup (MFMA M): svdd_host.h, shared with the inference GRU of svdd_nets.hip
 constexpr int HPAD = H + 4;    // LDS row stride of the hidden state (floats)
 constexpr int DP = 3 * H + 4;  // LDS row stride of a gate-derivative matrix (floats): 196 = 4 mod 64 banks per row
-
-__device__ __forceinline__ float sigmoid_fast(float a) {        // as in svdd_nets.hip: the forward pass must give the same bits
-  return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896f * a));
-}
-__device__ __forceinline__ float tanh_fast(float a) {
-  return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.88539008177793f * a));
-}
 
 // ---- forward with saved gates. x [n, L, 64]; wpack / bpack as svdd_gru_bidir_f32 (svdd_amd.fused.pack_gru);
 //      out [2][n][L][64]; save [2][n][L][4][64] = r, z, n, W_hn h + b_hn. One workgroup (4 waves) per (tile, direction).

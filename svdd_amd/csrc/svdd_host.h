@@ -1,4 +1,4 @@
-// svdd_host.h — the host side that all eight translation units share: the library's internal cross-file functions, the geometry
+// svdd_host.h — the host side that all nine translation units share: the library's internal cross-file functions, the geometry
 // constants that the fp32 and the split-precision kernels must agree on, the names of the profiling slots, and the ONE way a kernel
 // is launched (svdd_launch / svdd_launch_timed). No device code lives here.
 //

@@ -18,10 +18,10 @@
 // biases, the 128 -> 5 output map) is computed in fp32 exactly as in the fp32 kernels.
 #pragma once
 #include "svdd_host.h"
+#include "svdd_device.h"   // f32x4, group16_sum, the GRU gates: the fp32 kernels' own
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef __bf16 b8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
@@ -43,15 +43,6 @@ __device__ __forceinline__ void split2(float v0, float v1, typename Lp<T>::V2& h
   const T h0 = (T)v0, h1 = (T)v1;
   hi[0] = h0; hi[1] = h1;
   lo[0] = (T)(v0 - (float)h0); lo[1] = (T)(v1 - (float)h1);
-}
-
-template <int N>
-__device__ __forceinline__ float row_ror(float v) {            // rotate right by N inside each 16-lane DPP row
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float group16_sum(float v) {
-  v += row_ror<8>(v); v += row_ror<4>(v); v += row_ror<2>(v); v += row_ror<1>(v);
-  return v;
 }
 
 // TW_ROWS, TW_RT, BB_C, BB_AP (also the fp32 row stride of the final-stage image) and BB_MAXL: svdd_host.h

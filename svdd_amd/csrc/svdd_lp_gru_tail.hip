@@ -1,6 +1,6 @@
 // svdd_lp_gru_tail.hip — the value net's bidirectional GRU and tail, split precision
 // (split-precision net kernels on the 16-bit matrix cores: see svdd_lp_common.h for the arithmetic)
-#include "svdd_lp_common.h"
+#include "svdd_lp_common.h"   // and through it svdd_device.h: sigmoid_fast / tanh_fast, the fp32 GRU's
 
 namespace {
 
@@ -13,13 +13,6 @@ namespace {
 // Gates (sigmoid / tanh via v_exp_f32 / v_rcp_f32), the state update and the outputs are fp32 as in the fp32 kernel.
 // `count` (device scalar, may be NULL = n): number of valid sequences — exact work-skipping without a host round trip.
 constexpr int GLSB = 160;                  // bytes per hidden-state row of a 16-bit plane (64 x 2 B + 32 B pad)
-
-__device__ __forceinline__ float sigmoid_fast(float a) {
-  return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896f * a));
-}
-__device__ __forceinline__ float tanh_fast(float a) {
-  return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.88539008177793f * a));
-}
 
 struct GruLpArgs {
   const float* x;          // [n, L, 64] fp32, or NULL when x16 is given

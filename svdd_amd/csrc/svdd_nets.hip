@@ -12,28 +12,13 @@
 //   value_tail_kernel   direction sum + LayerNorm + FFN dense1 + ReLU + (dense2 o head) + mean over length
 //   conv1d_cl_*_kernel  one dilated conv layer (layer-wise path, small batches) ; epilogue_ln_kernel its epilogue
 #include "svdd_host.h"
+#include "svdd_device.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 
 constexpr int H = 64;          // hidden = input width
 // TS = 16 sequences per workgroup (MFMA M): svdd_host.h
 constexpr int HPAD = H + 4;    // LDS row stride (floats): shifts rows by 16 B -> ds_read_b128 conflict-light
-
-__device__ __forceinline__ float sigmoid_fast(float a) {
-  return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896f * a));
-}
-__device__ __forceinline__ float tanh_fast(float a) {
-  return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.88539008177793f * a));
-}
 
 // x      [n, L, 64] fp32 (channels-last conv-tower output)
 // wpack  [2 dirs][4 waves][64 lanes][96] : lane (j = lane&15, g = lane>>4) of wave w holds, for
@@ -1676,14 +1661,138 @@ struct BackboneSave {
   unsigned long long* mask;
 };
 
-template <int N>
-__device__ __forceinline__ float row_ror(float v) {            // rotate right by N inside each 16-lane DPP row
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float group16_sum(float v) {        // sum over the 16 lanes sharing lane >> 4 (VALU DPP, no LDS)
-  v += row_ror<8>(v); v += row_ror<4>(v); v += row_ror<2>(v); v += row_ror<1>(v);
-  return v;
-}
+// ---------------------------------------------------------------- the conv entry of the fp32 backbone family, defined ONCE ----
+// backbone_kernel, backbone_grad_kernel, backbone_split_kernel and the segment kernels (svdd_seg_body.h) must give each other's
+// bits, so the pieces of a (chunk, tap) entry are text they share, not text they copy. They are macros on purpose: they name the
+// locals of the kernel that uses them (bf0 / bf1, arow0, a_lo, a_hi, sched, wsrc, tile_of, it, en, rh, dil ...), and textual sharing
+// keeps every kernel's instruction stream what it was. Each kernel keeps its own entry SCHEDULE (which row tile's fragment is
+// requested under which MFMA group): those differ.
+//
+// BB_MM16: the 16-MFMA group of one row tile, two column tiles x 8 k-steps alternating the accumulators ACC[0] / ACC[1]; U = the
+// tile's A fragment (float4[2]), bf0 / bf1 = the unpacked weight tile, LIVE = the tile takes part in this entry. The user puts it
+// between two sched_barrier(0) and behind its own s_waitcnt.
+#define BB_MM16(ACC, U, LIVE)                                                                                \
+      if (LIVE) {                                                                                            \
+        _Pragma("unroll") for (int q_ = 0; q_ < 2; ++q_) {                                                   \
+          ACC[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q_].x, bf0[4 * q_], ACC[0], 0, 0, 0);              \
+          ACC[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q_].x, bf1[4 * q_], ACC[1], 0, 0, 0);              \
+          ACC[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q_].y, bf0[4 * q_ + 1], ACC[0], 0, 0, 0);          \
+          ACC[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q_].y, bf1[4 * q_ + 1], ACC[1], 0, 0, 0);          \
+          ACC[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q_].z, bf0[4 * q_ + 2], ACC[0], 0, 0, 0);          \
+          ACC[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q_].z, bf1[4 * q_ + 2], ACC[1], 0, 0, 0);          \
+          ACC[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q_].w, bf0[4 * q_ + 3], ACC[0], 0, 0, 0);          \
+          ACC[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q_].w, bf1[4 * q_ + 3], ACC[1], 0, 0, 0);          \
+        }                                                                                                    \
+      }
+// the current weight tile (float4[4]: W[col0][8 g ..], W[col0 + 16][8 g ..]) as the B operands of the 8 k-steps
+#define BB_UNPACK(BC)                                                                                        \
+      const float bf0[8] = {BC[0].x, BC[0].y, BC[0].z, BC[0].w, BC[1].x, BC[1].y, BC[1].z, BC[1].w};         \
+      const float bf1[8] = {BC[2].x, BC[2].y, BC[2].z, BC[2].w, BC[3].x, BC[3].y, BC[3].z, BC[3].w};
+// a weight tile's four float4 of this lane, from SRC = wsrc + the tile's offset, into the register set B (prologue: the first
+// tile; inside an entry: the next tile into the idle set)
+#define BB_WLOAD(B, SRC)                                                                                     \
+      { const float* src_ = (SRC);                                                                           \
+        B[0] = *reinterpret_cast<const float4*>(src_);                                                       \
+        B[1] = *reinterpret_cast<const float4*>(src_ + 4);                                                   \
+        B[2] = *reinterpret_cast<const float4*>(src_ + 16 * CH);                                             \
+        B[3] = *reinterpret_cast<const float4*>(src_ + 16 * CH + 4); }
+// an A fragment (two ds_read_b128) from the LDS BYTE address ADDR, which already contains the image's base, into V (float4[2])
+#define BB_ALOAD(V, ADDR)                                                                                    \
+      { const LdsF4* ap_ = reinterpret_cast<const LdsF4*>(ADDR);                                             \
+        const f32x4 t0_ = ap_[0], t1_ = ap_[1];                                                              \
+        V[0] = make_float4(t0_[0], t0_[1], t0_[2], t0_[3]); V[1] = make_float4(t1_[0], t1_[1], t1_[2], t1_[3]); }
+// ... with the address clamped to LO .. HI (the image's zero rows -1 and TW_ROWS).
+// (VALU work does not run under fp32 MFMAs on this SIMD: the clamp is ONE v_med3_i32, and the fragment is read through an
+//  LDS address kept as an integer that already contains the image's base — as "imgb + o_" every request carried a
+//  v_add_u32 of the dynamic-LDS symbol, which is 0)
+#define BB_ALOAD_CLAMPED(V, ADDR, LO, HI)                                                                    \
+      { int o_;                                                                                              \
+        asm("v_med3_i32 %0, %1, %2, %3" : "=v"(o_) : "v"(ADDR), "v"(LO), "v"(HI));                           \
+        BB_ALOAD(V, o_) }
+
+// ---- backbone_kernel's and backbone_grad_kernel's entry: the gradient pass walks the forward's work split with the forward's text.
+#define B2_ALOAD(R, V, DELTA, COFF, DBYTES)                                                                  \
+      BB_ALOAD_CLAMPED(V, arow0 + (DBYTES) + (R) * (32 * BB_AP * 4), a_lo + (COFF), a_hi + (COFF))
+#define B2_WAIT(NOUT) __builtin_amdgcn_s_waitcnt(0xC07F | ((NOUT) << 8));
+#define B2_MM(R, U, NOUT)                                                                                    \
+      __builtin_amdgcn_sched_barrier(0);                                                                     \
+      B2_WAIT(NOUT)                                                                                          \
+      BB_MM16(acc[R], U, live & (1 << (2 * (R))))                                                            \
+      __builtin_amdgcn_sched_barrier(0);
+// entry parameters from a schedule word
+#define B2_PARAMS(EN, DELTA, COFF, DBYTES)                                                                   \
+      const int DELTA = ((((EN) >> 15) & 15) - 4) * dil;                                                     \
+      const int COFF = (((EN) >> 13) & 3) * (CH * 4);                                                        \
+      const int DBYTES = DELTA * (BB_AP * 4) + COFF;
+// what every entry body begins with: the next schedule word is requested, the current tile unpacked, the next entry's tile sent to
+// the idle set (after the last entry: this entry's again, never used — unconditional, so that the compiler's vmcnt model has one
+// path), this entry's parameters decoded
+#define B2_ENTRY_HEAD(BC, BN)                                                                                \
+      const int nxt = en >> 19;                                                                              \
+      const int en_next_v = sched[nxt < it_end ? nxt : it];                                                  \
+      BB_UNPACK(BC)                                                                                          \
+      BB_WLOAD(BN, wsrc + (size_t)tile_of(nxt < it_end ? nxt : it) * BB_C * CH)                              \
+      B2_PARAMS(en, delta, coff, dbytes)                                                                     \
+      const int live = en >> rh;                          /* bit 2 r = owned tile r */
+// A fragments of row tiles 0 and 1 of an entry are requested during the LAST MFMA groups of the entry before it (first
+// entry of a layer: right here), so that the matrix pipe does not run dry at every (chunk, tap) boundary while both waves
+// of a SIMD wait for their first LDS reads (round 3; same bits: only the loads move). A wave with 7 row tiles ends an
+// entry on the fragment set it began with, so its two sets trade roles from entry to entry (two copies of the body).
+// one (chunk, tap) entry of a wave with 7 / 6 owned row tiles; UA holds (or is receiving) row tile 0, UB row tile 1
+#define B2_ENTRY(UA, UB, BC, BN)                                                                             \
+    { B2_ENTRY_HEAD(BC, BN)                                                                                  \
+      /* (after a layer's last entry the "next entry" loads below read the dying image with the wrong dilation: clamped \
+         addresses, values never used — the layer prologue reloads both sets; cheaper than a second copy of the MFMA groups) */ \
+      B2_MM(0, UA, 3)                                     /* in flight: tile 1 (2 reads) + the schedule word */ \
+      B2_ALOAD(2, UA, delta, coff, dbytes)                                                                   \
+      B2_MM(1, UB, 2)                                                                                        \
+      const int en2 = __builtin_amdgcn_readfirstlane(en_next_v);                                             \
+      B2_PARAMS(en2, delta2, coff2, dbytes2)                                                                 \
+      B2_ALOAD(3, UB, delta, coff, dbytes)                                                                   \
+      B2_MM(2, UA, 2)                                                                                        \
+      B2_ALOAD(4, UA, delta, coff, dbytes)                                                                   \
+      B2_MM(3, UB, 2)                                                                                        \
+      B2_ALOAD(5, UB, delta, coff, dbytes)                                                                   \
+      B2_MM(4, UA, 2)                                                                                        \
+      if (rh == 0) {                                                                                         \
+        B2_ALOAD(6, UA, delta, coff, dbytes)                                                                 \
+        B2_MM(5, UB, 2)                                                                                      \
+        B2_ALOAD(0, UB, delta2, coff2, dbytes2)           /* next entry: tile 0 in UB, tile 1 in UA */       \
+        B2_MM(6, UA, 2)                                                                                      \
+        B2_ALOAD(1, UA, delta2, coff2, dbytes2)                                                              \
+      } else {                                                                                               \
+        B2_ALOAD(0, UA, delta2, coff2, dbytes2)                                                              \
+        B2_MM(5, UB, 2)                                                                                      \
+        B2_ALOAD(1, UB, delta2, coff2, dbytes2)                                                              \
+      }                                                                                                      \
+      it = nxt;                                                                                              \
+      en = en2; }
+// the same entry for a wave with at most FOUR / TWO owned row tiles (tiles of <= 8 / <= 4 row tiles): both waves of a SIMD take the
+// same even number of slots, so the fragment sets keep their roles from entry to entry
+#define B2_ENTRY4(UA, UB, BC, BN)                                                                            \
+    { B2_ENTRY_HEAD(BC, BN)                                                                                  \
+      B2_MM(0, UA, 3)                                                                                        \
+      B2_ALOAD(2, UA, delta, coff, dbytes)                                                                   \
+      B2_MM(1, UB, 2)                                                                                        \
+      const int en2 = __builtin_amdgcn_readfirstlane(en_next_v);                                             \
+      B2_PARAMS(en2, delta2, coff2, dbytes2)                                                                 \
+      B2_ALOAD(3, UB, delta, coff, dbytes)                                                                   \
+      B2_MM(2, UA, 2)                                                                                        \
+      B2_ALOAD(0, UA, delta2, coff2, dbytes2)                                                                \
+      B2_MM(3, UB, 2)                                                                                        \
+      B2_ALOAD(1, UB, delta2, coff2, dbytes2)                                                                \
+      it = nxt;                                                                                              \
+      en = en2; }
+#define B2_ENTRY2(UA, UB, BC, BN)                                                                            \
+    { B2_ENTRY_HEAD(BC, BN)                                                                                  \
+      B2_MM(0, UA, 3)                                                                                        \
+      const int en2 = __builtin_amdgcn_readfirstlane(en_next_v);                                             \
+      B2_PARAMS(en2, delta2, coff2, dbytes2)                                                                 \
+      B2_ALOAD(0, UA, delta2, coff2, dbytes2)                                                                \
+      B2_MM(1, UB, 2)                                                                                        \
+      B2_ALOAD(1, UB, delta2, coff2, dbytes2)                                                                \
+      it = nxt;                                                                                              \
+      en = en2; }
 
 // Work split: wave w owns 32 output channels (column group w & 3) of the row tiles of parity w >> 2 (7 / 6 tiles; the
 // two waves of a SIMD share a column group and split the rows). An MFMA group is ONE row tile x two column tiles x
@@ -1833,7 +1942,6 @@ __global__ __launch_bounds__(512, 2) void backbone_kernel(BackboneArgs a, Backbo
   __syncthreads();                                        // sched is visible
 
   // A operand addressing: this lane feeds row 16 (rh + 2 r) + j of its tiles, channels 32 c + 8 g .. + 8
-  typedef __attribute__((address_space(3))) f32x4 LdsF4;
   const int img_lds = (int)(unsigned)(size_t)(const __attribute__((address_space(3))) float*)img;              // LDS byte address of img
   const int arow0 = img_lds + ((16 * rh + j) * BB_AP + 8 * g) * 4;  // LDS byte address of (row 16 rh + j, col 8 g) of img
   const int a_lo = arow0 - (16 * rh + j + 1) * BB_AP * 4; // row -1
@@ -1851,14 +1959,8 @@ __global__ __launch_bounds__(512, 2) void backbone_kernel(BackboneArgs a, Backbo
   // two weight-fragment sets that trade roles from entry to entry (round 4d: with ONE set refilled in place the current tile
   // had to be copied out first, 8 v_mov_b64 at each end of an entry, and VALU work does not run under fp32 MFMAs on this SIMD)
   float4 bA[4], bB[4];
-  {
-    const float* src = wsrc + (size_t)tile_of(it) * BB_C * CH;
-    bA[0] = *reinterpret_cast<const float4*>(src);
-    bA[1] = *reinterpret_cast<const float4*>(src + 4);
-    bA[2] = *reinterpret_cast<const float4*>(src + 16 * CH);
-    bA[3] = *reinterpret_cast<const float4*>(src + 16 * CH + 4);
-    bB[0] = bA[0]; bB[1] = bA[1]; bB[2] = bA[2]; bB[3] = bA[3];
-  }
+  BB_WLOAD(bA, wsrc + (size_t)tile_of(it) * BB_C * CH)
+  bB[0] = bA[0]; bB[1] = bA[1]; bB[2] = bA[2]; bB[3] = bA[3];
 
   for (int layer = layer0; layer <= nl; ++layer) {        // layer == nl: the first 1x1 conv of final_conv
     const float* vl = a.vec + (size_t)(layer + 1) * 4 * BB_C;
@@ -1947,122 +2049,7 @@ __global__ __launch_bounds__(512, 2) void backbone_kernel(BackboneArgs a, Backbo
     const int dil = __builtin_amdgcn_readfirstlane(sdil[layer < nl ? layer : BB_MAXL]) * il;   // in tile rows
     const int layer_end = (layer + 1) * 36;
     __syncthreads();                                      // the image is complete
-    // A fragments of row tiles 0 and 1 of an entry are requested during the LAST MFMA groups of the entry before it (first
-    // entry of a layer: right here), so that the matrix pipe does not run dry at every (chunk, tap) boundary while both waves
-    // of a SIMD wait for their first LDS reads (round 3; same bits: only the loads move). A wave with 7 row tiles ends an
-    // entry on the fragment set it began with, so its two sets trade roles from entry to entry (two copies of the body).
-    // (VALU work does not run under fp32 MFMAs on this SIMD: the clamp is ONE v_med3_i32, and the fragment is read through an
-    //  LDS address kept as an integer that already contains the image's base — as "imgb + o_" every request carried a
-    //  v_add_u32 of the dynamic-LDS symbol, which is 0)
-#define B2_ALOAD(R, V, DELTA, COFF, DBYTES)                                                                  \
-      { int o_;                                                                                              \
-        asm("v_med3_i32 %0, %1, %2, %3" : "=v"(o_) : "v"(arow0 + (DBYTES) + (R) * (32 * BB_AP * 4)), "v"(a_lo + (COFF)), "v"(a_hi + (COFF))); \
-        const LdsF4* ap_ = reinterpret_cast<const LdsF4*>(o_);                                               \
-        const f32x4 t0_ = ap_[0], t1_ = ap_[1];                                                              \
-        V[0] = make_float4(t0_[0], t0_[1], t0_[2], t0_[3]); V[1] = make_float4(t1_[0], t1_[1], t1_[2], t1_[3]); }
-#define B2_WAIT(NOUT) __builtin_amdgcn_s_waitcnt(0xC07F | ((NOUT) << 8));
-#define B2_MM(R, U, NOUT)                                                                                    \
-      __builtin_amdgcn_sched_barrier(0);                                                                     \
-      B2_WAIT(NOUT)                                                                                          \
-      if (live & (1 << (2 * (R)))) {                                                                         \
-        _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                                      \
-          acc[R][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].x, bf0[4 * q], acc[R][0], 0, 0, 0);          \
-          acc[R][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].x, bf1[4 * q], acc[R][1], 0, 0, 0);          \
-          acc[R][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].y, bf0[4 * q + 1], acc[R][0], 0, 0, 0);      \
-          acc[R][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].y, bf1[4 * q + 1], acc[R][1], 0, 0, 0);      \
-          acc[R][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].z, bf0[4 * q + 2], acc[R][0], 0, 0, 0);      \
-          acc[R][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].z, bf1[4 * q + 2], acc[R][1], 0, 0, 0);      \
-          acc[R][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].w, bf0[4 * q + 3], acc[R][0], 0, 0, 0);      \
-          acc[R][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].w, bf1[4 * q + 3], acc[R][1], 0, 0, 0);      \
-        }                                                                                                    \
-      }                                                                                                      \
-      __builtin_amdgcn_sched_barrier(0);
-    // entry parameters from a schedule word
-#define B2_PARAMS(EN, DELTA, COFF, DBYTES)                                                                   \
-      const int DELTA = ((((EN) >> 15) & 15) - 4) * dil;                                                     \
-      const int COFF = (((EN) >> 13) & 3) * (CH * 4);                                                        \
-      const int DBYTES = DELTA * (BB_AP * 4) + COFF;
-    // one (chunk, tap) entry; UA holds (or is receiving) row tile 0, UB row tile 1
-#define B2_ENTRY(UA, UB, BC, BN)                                                                             \
-    { const int nxt = en >> 19;                                                                              \
-      const int en_next_v = sched[nxt < it_end ? nxt : it];                                                  \
-      const float bf0[8] = {BC[0].x, BC[0].y, BC[0].z, BC[0].w, BC[1].x, BC[1].y, BC[1].z, BC[1].w};         \
-      const float bf1[8] = {BC[2].x, BC[2].y, BC[2].z, BC[2].w, BC[3].x, BC[3].y, BC[3].z, BC[3].w};         \
-      { /* the next entry's tile into the idle set; after the last entry: this entry's again (never used) — unconditional, \
-           so that the compiler's vmcnt model has one path */                                                \
-        const float* src = wsrc + (size_t)tile_of(nxt < it_end ? nxt : it) * BB_C * CH;                      \
-        BN[0] = *reinterpret_cast<const float4*>(src);                                                       \
-        BN[1] = *reinterpret_cast<const float4*>(src + 4);                                                   \
-        BN[2] = *reinterpret_cast<const float4*>(src + 16 * CH);                                             \
-        BN[3] = *reinterpret_cast<const float4*>(src + 16 * CH + 4);                                         \
-      }                                                                                                      \
-      B2_PARAMS(en, delta, coff, dbytes)                                                                     \
-      const int live = en >> rh;                          /* bit 2 r = owned tile r */                       \
-      /* (after a layer's last entry the "next entry" loads below read the dying image with the wrong dilation: clamped \
-         addresses, values never used — the layer prologue reloads both sets; cheaper than a second copy of the MFMA groups) */ \
-      B2_MM(0, UA, 3)                                     /* in flight: tile 1 (2 reads) + the schedule word */ \
-      B2_ALOAD(2, UA, delta, coff, dbytes)                                                                   \
-      B2_MM(1, UB, 2)                                                                                        \
-      const int en2 = __builtin_amdgcn_readfirstlane(en_next_v);                                             \
-      B2_PARAMS(en2, delta2, coff2, dbytes2)                                                                 \
-      B2_ALOAD(3, UB, delta, coff, dbytes)                                                                   \
-      B2_MM(2, UA, 2)                                                                                        \
-      B2_ALOAD(4, UA, delta, coff, dbytes)                                                                   \
-      B2_MM(3, UB, 2)                                                                                        \
-      B2_ALOAD(5, UB, delta, coff, dbytes)                                                                   \
-      B2_MM(4, UA, 2)                                                                                        \
-      if (rh == 0) {                                                                                         \
-        B2_ALOAD(6, UA, delta, coff, dbytes)                                                                 \
-        B2_MM(5, UB, 2)                                                                                      \
-        B2_ALOAD(0, UB, delta2, coff2, dbytes2)           /* next entry: tile 0 in UB, tile 1 in UA */       \
-        B2_MM(6, UA, 2)                                                                                      \
-        B2_ALOAD(1, UA, delta2, coff2, dbytes2)                                                              \
-      } else {                                                                                               \
-        B2_ALOAD(0, UA, delta2, coff2, dbytes2)                                                              \
-        B2_MM(5, UB, 2)                                                                                      \
-        B2_ALOAD(1, UB, delta2, coff2, dbytes2)                                                              \
-      }                                                                                                      \
-      it = nxt;                                                                                              \
-      en = en2; }
-    // the same entry for a wave with at most FOUR / TWO owned row tiles (tiles of <= 8 / <= 4 row tiles): both waves of a SIMD take the
-    // same even number of slots, so the fragment sets keep their roles from entry to entry
-#define B2_ENTRY_HEAD(BC, BN)                                                                                \
-      const int nxt = en >> 19;                                                                              \
-      const int en_next_v = sched[nxt < it_end ? nxt : it];                                                  \
-      const float bf0[8] = {BC[0].x, BC[0].y, BC[0].z, BC[0].w, BC[1].x, BC[1].y, BC[1].z, BC[1].w};         \
-      const float bf1[8] = {BC[2].x, BC[2].y, BC[2].z, BC[2].w, BC[3].x, BC[3].y, BC[3].z, BC[3].w};         \
-      { const float* src = wsrc + (size_t)tile_of(nxt < it_end ? nxt : it) * BB_C * CH;                      \
-        BN[0] = *reinterpret_cast<const float4*>(src);                                                       \
-        BN[1] = *reinterpret_cast<const float4*>(src + 4);                                                   \
-        BN[2] = *reinterpret_cast<const float4*>(src + 16 * CH);                                             \
-        BN[3] = *reinterpret_cast<const float4*>(src + 16 * CH + 4);                                         \
-      }                                                                                                      \
-      B2_PARAMS(en, delta, coff, dbytes)                                                                     \
-      const int live = en >> rh;
-#define B2_ENTRY4(UA, UB, BC, BN)                                                                            \
-    { B2_ENTRY_HEAD(BC, BN)                                                                                  \
-      B2_MM(0, UA, 3)                                                                                        \
-      B2_ALOAD(2, UA, delta, coff, dbytes)                                                                   \
-      B2_MM(1, UB, 2)                                                                                        \
-      const int en2 = __builtin_amdgcn_readfirstlane(en_next_v);                                             \
-      B2_PARAMS(en2, delta2, coff2, dbytes2)                                                                 \
-      B2_ALOAD(3, UB, delta, coff, dbytes)                                                                   \
-      B2_MM(2, UA, 2)                                                                                        \
-      B2_ALOAD(0, UA, delta2, coff2, dbytes2)                                                                \
-      B2_MM(3, UB, 2)                                                                                        \
-      B2_ALOAD(1, UB, delta2, coff2, dbytes2)                                                                \
-      it = nxt;                                                                                              \
-      en = en2; }
-#define B2_ENTRY2(UA, UB, BC, BN)                                                                            \
-    { B2_ENTRY_HEAD(BC, BN)                                                                                  \
-      B2_MM(0, UA, 3)                                                                                        \
-      const int en2 = __builtin_amdgcn_readfirstlane(en_next_v);                                             \
-      B2_PARAMS(en2, delta2, coff2, dbytes2)                                                                 \
-      B2_ALOAD(0, UA, delta2, coff2, dbytes2)                                                                \
-      B2_MM(1, UB, 2)                                                                                        \
-      B2_ALOAD(1, UB, delta2, coff2, dbytes2)                                                                \
-      it = nxt;                                                                                              \
-      en = en2; }
+    // the entry loop: B2_* at file scope, shared with backbone_grad_kernel
     float4 ua[2], ub[2];
     if (it < layer_end) {
       B2_PARAMS(en, delta0, coff0, dbytes0)
@@ -2098,14 +2085,6 @@ __global__ __launch_bounds__(512, 2) void backbone_kernel(BackboneArgs a, Backbo
       }
     }
     if (odd) { bA[0] = bB[0]; bA[1] = bB[1]; bA[2] = bB[2]; bA[3] = bB[3]; }
-#undef B2_ENTRY
-#undef B2_ENTRY4
-#undef B2_ENTRY2
-#undef B2_ENTRY_HEAD
-#undef B2_PARAMS
-#undef B2_MM
-#undef B2_WAIT
-#undef B2_ALOAD
     __syncthreads();                                      // every wave is done reading the image
     if (SAVE) {
       relu_bits = 0ull;
@@ -2511,493 +2490,54 @@ __global__ __launch_bounds__(256) void backbone_list_kernel(const uint8_t* __res
   }
 }
 
-// NC = the most own tiles an item may have (2 / 4); 4 waves, wave cg owns 32 output channels of EVERY tile of the item (slots
-// 0 .. NC + 1 = halo, own tiles, halo), so a weight fragment feeds up to NC row tiles and the register arrays are sized to the item.
-// ORD: workgroup b takes entry b of the layer's size-ordered list (svdd_backbone_incr2_f32) instead of slot b of `items`; NC = 1
-// exists for that list only (3 image slots, one fragment set per entry, 4 workgroups per CU).
-// DIL = the layer's dilation, 1 or 4 (svdd_backbone_incr3_f32): tap t reads image row + (t - 4) DIL, at most the 16 rows of one halo
-// tile away. At dilation 4 backbone_kernel's schedule drops a (row tile, tap) pair whose inputs are all padding — with
-// d = (t - 4) DIL, tile T is live iff max(0, -d) < 16 T + 16 and min(L, L - d) > 16 T; at L = 200 tile 0 drops tap -16, tile 12 taps
-// +8, +12, +16 — and exactly those pairs issue no MFMA here (tapmask), so the accumulators see the same operations in the same order.
-template <int NC, bool ORD = false, int DIL = 1>
-__global__ __launch_bounds__(256, NC == 4 ? 2 : NC == 1 ? 4 : 3) void backbone_seg_kernel(BackboneSegArgs a) {
-  static_assert(DIL == 1 || DIL == 4, "one halo tile per side holds taps of dilation <= 4");
-  constexpr int NS = NC + 2, ROWS = 16 * NS;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* img = smem;                                      // [ROWS][BB_AP] image row i = sequence row 16 (t0 - 1) + i
-  float* psum = img + ROWS * BB_AP;                       // [4][ROWS]
-  float* rstat = psum + 4 * ROWS;                         // [ROWS]
-  int* toks = reinterpret_cast<int*>(rstat + ROWS);       // [ROWS + 8] tokens of sequence rows 16 (t0 - 1) - 4 ..   (layer 1)
+// The segment kernels: 4 waves, wave cg owns 32 output channels of EVERY tile of an item, so a weight fragment feeds up to NC row tiles
+// and the register arrays are sized to the item. There are two LAYOUTS of an item's rows over the image and the register slots, and
+// ONE body, svdd_seg_body.h, that both kernels compile: the token fetch, layer 1 through the image, the three LayerNorm passes, the
+// accumulators starting at the bias, the 36 entries and relu(conv + b) + f are written once. A layout is compile-time constants only;
+// what differs between the two is decided on them where the body needs it (SEG_LIVE / SEG_MINE / SEG_IROW ... in svdd_seg_body.h):
+//   NC, NS, ROWS   the most own tiles of an item, the register slots, the image rows
+//   PK             TIGHT: the slot that packs both halos
+//   ORD            workgroup b takes entry b of the layer's size-ordered list; false: slot b of `items`
+//   DIL            the layer's dilation
+// The body is text that each kernel includes, not a function both call: as an inlined function (and with the layout as an object with
+// methods) every one of the nine kernels came out with other instructions than before, as included text with none
+// (profiles/backbone_shared_code.txt).
+//
+// SegAligned<NC, ORD, DIL> (backbone_seg_kernel): items of whole tiles, slots 0 .. NC + 1 = halo tile, own tiles, halo tile; image
+// row i = sequence row 16 (t0 - 1) + i. ORD: svdd_backbone_incr2_f32's list; NC = 1 exists for that list only (3 image slots, one
+// fragment set per entry, 4 workgroups per CU).
+// DIL = 1 or 4 (svdd_backbone_incr3_f32): tap t reads image row + (t - 4) DIL, at most the 16 rows of one halo tile away. At dilation
+// 4 backbone_kernel's schedule drops a (row tile, tap) pair whose inputs are all padding — with d = (t - 4) DIL, tile T is live iff
+// max(0, -d) < 16 T + 16 and min(L, L - d) > 16 T; at L = 200 tile 0 drops tap -16, tile 12 taps +8, +12, +16 — and exactly those
+// pairs issue no MFMA here (tapmask), so the accumulators see the same operations in the same order.
+template <int NC_, bool ORD_, int DIL_>
+struct SegAligned {
+  static_assert(DIL_ == 1 || DIL_ == 4, "one halo tile per side holds taps of dilation <= 4");
+  static constexpr int NC = NC_, NS = NC_ + 2, PK = NS, ROWS = 16 * NS, DIL = DIL_;
+  static constexpr bool ORD = ORD_, TIGHT = false;
+};
 
-  int item, seq;
-  if (ORD) {
-    if ((int)blockIdx.x >= a.order_count[a.layer - 1]) return;
-    const unsigned ent = (unsigned)__builtin_amdgcn_readfirstlane(a.order[(size_t)(a.layer - 1) * a.order_stride + blockIdx.x]);
-    item = (int)(ent & 0xFFFFu);
-    seq = (int)(ent >> 16);
-  } else {
-    item = __builtin_amdgcn_readfirstlane(a.items[(size_t)(a.layer - 1) * a.n * SEG_SLOTS + blockIdx.x]);
-    seq = blockIdx.x / SEG_SLOTS;
-  }
-  const int nown = min(item >> 8, NC);
-  if (nown == 0) return;
-  const int t0 = item & 255;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int cg = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int j = lane & 15, g = lane >> 4;
-  const int col0 = 32 * cg + j;
-  const int L = a.L;
-  const int r0 = 16 * (t0 - 1);                           // sequence row of image row 0
-  const size_t pl_stride = (size_t)a.n * TW_ROWS * BB_C;
-  float* pl0 = a.planes + (size_t)seq * TW_ROWS * BB_C;
-  const int cl = a.layer - 1;                             // the conv layer this launch runs
-#define SEG_LIVE(S) ((S) <= nown + 1)
+// SegTight (backbone_seg_tight_kernel): SegAligned<2, true, 1> for the TIGHT items of svdd_backbone_incr4_f32 (origin row |
+// tiles << 8, any origin), with the halo packed: a dilation-1 item reads 4 rows beyond its tiles on each side, so the image is rows
+// origin - 4 .. origin + 16 nown + 3 (40 rows for two tiles where the aligned layout holds 64) and the register arrays have THREE
+// slots, not four: slots 0, 1 = the own tiles (image rows 4 + 16 s + 4 g + e), slot 2 = both halos — the lanes with g = 0 hold the
+// left one (image rows 0 .. 3), those with g = 1 the right one (image rows 16 nown + 4 .. + 7), those with g = 2, 3 nothing (they
+// neither load nor store; the VALU runs them along). A row's LayerNorm sums over the 16 lanes of one g and the four waves, so it is
+// the same tree whichever slot holds the row. Output row j of tile c reads image rows 16 c + j + t, t = 0 .. 8.
+struct SegTight {
+  static constexpr int NC = 2, NS = NC + 1, PK = NC, ROWS = 16 * NC + 8, DIL = 1;
+  static constexpr bool ORD = true, TIGHT = true;
+};
 
-  f32x4 f[NS][2], acc[NS][2];
-  if (a.layer == 1) {
-    for (int e = tid; e < ROWS + 8; e += 256) {
-      const int p = r0 - 4 + e;
-      toks[e] = (p >= 0 && p < L) ? (int)a.x[(size_t)seq * L + p] : -1;
-    }
-    __syncthreads();
-    // f_0 of the item's rows goes through the (still unused) image: thread (ri, c) builds row ri, channel c with its nine table
-    // reads issued together, at a clamped index and with no branch between them — four elements (36 reads) per wait, 32 (ri, c)
-    // pairs per thread for a 2-tile item. (Built straight into the MFMA layout, every lane made 9 dependent, branch-guarded reads
-    // for each of its 32 elements: 288 round trips to L2 in a row, 24 us per launch; batching them THERE costs 128 - 168 VGPRs and
-    // scratch.) A wave shares the row, so the reads of a tap are 256 consecutive bytes and the tokens are wave-uniform. The sum is
-    // backbone_kernel's: start b0, taps in order, a tap outside the sequence SKIPPED (a select, never an added 0.0f: -0.0 must
-    // stay -0.0).
-    {
-      const int c = tid & (BB_C - 1);
-      const float b0 = a.vec[c];
-#pragma unroll 4
-      for (int ri = tid >> 7; ri < 16 * (nown + 2); ri += 2) {
-        int tk[9];
-        float tv[9];
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-          tk[t] = toks[ri + t];                           // sequence row r0 + ri + t - 4 ; -1 outside the sequence
-          tv[t] = a.table0[(unsigned)((t * 5 + max(tk[t], 0)) * BB_C + c)];
-        }
-        float v = b0;
-#pragma unroll
-        for (int t = 0; t < 9; ++t) v = tk[t] >= 0 ? v + tv[t] : v;
-        const int row = r0 + ri;
-        img[ri * BB_AP + c] = (row >= 0 && row < L) ? fmaxf(v, 0.0f) : 0.0f;
-      }
-    }
-    __syncthreads();                                      // (the image is next written behind the LayerNorm barriers below)
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      if (!SEG_LIVE(s)) continue;
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) f[s][ct][e] = img[(16 * s + 4 * g + e) * BB_AP + col0 + 16 * ct];
-    }
-  } else {
-    const float* src = pl0 + (size_t)(a.layer - 2) * pl_stride;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      if (!SEG_LIVE(s)) continue;
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int row = r0 + 16 * s + 4 * g + e;
-          f[s][ct][e] = (row >= 0 && row < L) ? src[row * BB_C + col0 + 16 * ct] : 0.0f;
-        }
-    }
-  }
-
-  // ---- LayerNorm(f + tb) of the item's tiles and its halo -> image (backbone_kernel's passes, row for row)
-  const float* vl = a.vec + (size_t)(cl + 1) * 4 * BB_C;
-  {
-    const float tb0 = vl[BB_C + col0], tb1 = vl[BB_C + col0 + 16];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      if (!SEG_LIVE(s)) continue;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float sm = group16_sum((f[s][0][e] + tb0) + (f[s][1][e] + tb1));
-        if (j == 0) psum[cg * ROWS + 16 * s + 4 * g + e] = sm;
-      }
-    }
-    __syncthreads();
-    if (tid < 16 * (nown + 2))
-      rstat[tid] = ((psum[tid] + psum[ROWS + tid]) + (psum[2 * ROWS + tid] + psum[3 * ROWS + tid])) * (1.0f / BB_C);
-    __syncthreads();
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      if (!SEG_LIVE(s)) continue;
-      const float4 cur4 = *reinterpret_cast<const float4*>(rstat + 16 * s + 4 * g);
-      const float mean4[4] = {cur4.x, cur4.y, cur4.z, cur4.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float mean = mean4[e];
-        const float d0 = f[s][0][e] + tb0 - mean, d1 = f[s][1][e] + tb1 - mean;
-        acc[s][0][e] = d0; acc[s][1][e] = d1;
-        const float sq = group16_sum(d0 * d0 + d1 * d1);
-        if (j == 0) psum[cg * ROWS + 16 * s + 4 * g + e] = sq;
-      }
-    }
-    __syncthreads();
-    if (tid < 16 * (nown + 2))
-      rstat[tid] = rsqrtf(((psum[tid] + psum[ROWS + tid]) + (psum[2 * ROWS + tid] + psum[3 * ROWS + tid])) * (1.0f / BB_C) + 1e-5f);
-    __syncthreads();
-    const float gm0 = vl[2 * BB_C + col0], gm1 = vl[2 * BB_C + col0 + 16];
-    const float bt0 = vl[3 * BB_C + col0], bt1 = vl[3 * BB_C + col0 + 16];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      if (!SEG_LIVE(s)) continue;
-      const float4 cur4 = *reinterpret_cast<const float4*>(rstat + 16 * s + 4 * g);
-      const float rs4[4] = {cur4.x, cur4.y, cur4.z, cur4.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int ri = 16 * s + 4 * g + e, row = r0 + ri;
-        const float rs = rs4[e];
-        const bool in = row >= 0 && row < L;              // rows outside the sequence are the zero padding of the convolution
-        img[ri * BB_AP + col0] = in ? acc[s][0][e] * rs * gm0 + bt0 : 0.0f;
-        img[ri * BB_AP + col0 + 16] = in ? acc[s][1][e] * rs * gm1 + bt1 : 0.0f;
-      }
-    }
-  }
-
-  // ---- the convolution of the own tiles (slots 1 .. nown): 36 (chunk, tap) entries, chunk outer
-  const float bl0 = vl[col0], bl1 = vl[col0 + 16];
-  f32x4 cacc[NC][2];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) { cacc[c][0] = f32x4{bl0, bl0, bl0, bl0}; cacc[c][1] = f32x4{bl1, bl1, bl1, bl1}; }
-  typedef __attribute__((address_space(3))) f32x4 LdsF4;
-  const int img_lds = (int)(unsigned)(size_t)(const __attribute__((address_space(3))) float*)img;
-  const int arow0 = img_lds + ((16 + j) * BB_AP + 8 * g) * 4;       // LDS byte address of (row j of slot 1, col 8 g)
-  const float* wsrc = a.tiles + (size_t)cl * 36 * BB_C * CH + col0 * CH + 8 * g;
-  const int live = (1 << nown) - 1;
-  int tapmask[NC];                                        // DIL > 1: bit t = tap t of own tile c is live in backbone_kernel's schedule (wave-uniform)
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    int m = 0;
-    if (DIL > 1 && c < nown) {
-      const int T = t0 + c;
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        const int d = (t - 4) * DIL;
-        if (max(0, -d) < 16 * T + 16 && min(L, L - d) > 16 * T) m |= 1 << t;
-      }
-    }
-    tapmask[c] = __builtin_amdgcn_readfirstlane(m);
-  }
-  float4 bA[4], bB[4];
-  bA[0] = *reinterpret_cast<const float4*>(wsrc);
-  bA[1] = *reinterpret_cast<const float4*>(wsrc + 4);
-  bA[2] = *reinterpret_cast<const float4*>(wsrc + 16 * CH);
-  bA[3] = *reinterpret_cast<const float4*>(wsrc + 16 * CH + 4);
-  bB[0] = bA[0]; bB[1] = bA[1]; bB[2] = bA[2]; bB[3] = bA[3];
-  __syncthreads();                                        // the image is complete
-#define SG_DBYTES(IT) ((((IT) % 9) - 4) * DIL * (BB_AP * 4) + ((IT) / 9) * (CH * 4))
-#define SG_ALOAD(C, V, DBYTES)                                                                               \
-      { const LdsF4* ap_ = reinterpret_cast<const LdsF4*>(arow0 + (DBYTES) + (C) * (16 * BB_AP * 4));         \
-        const f32x4 t0_ = ap_[0], t1_ = ap_[1];                                                              \
-        V[0] = make_float4(t0_[0], t0_[1], t0_[2], t0_[3]); V[1] = make_float4(t1_[0], t1_[1], t1_[2], t1_[3]); }
-#define SG_MM(C, U)                                                                                          \
-      __builtin_amdgcn_sched_barrier(0);                                                                     \
-      __builtin_amdgcn_s_waitcnt(0xC07F | (2 << 8));      /* at most the two reads of the other fragment set in flight */ \
-      if (DIL == 1 ? (live & (1 << (C))) : (tapmask[C] >> (it % 9) & 1)) {                                   \
-        _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                                      \
-          cacc[C][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].x, bf0[4 * q], cacc[C][0], 0, 0, 0);        \
-          cacc[C][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].x, bf1[4 * q], cacc[C][1], 0, 0, 0);        \
-          cacc[C][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].y, bf0[4 * q + 1], cacc[C][0], 0, 0, 0);    \
-          cacc[C][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].y, bf1[4 * q + 1], cacc[C][1], 0, 0, 0);    \
-          cacc[C][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].z, bf0[4 * q + 2], cacc[C][0], 0, 0, 0);    \
-          cacc[C][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].z, bf1[4 * q + 2], cacc[C][1], 0, 0, 0);    \
-          cacc[C][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].w, bf0[4 * q + 3], cacc[C][0], 0, 0, 0);    \
-          cacc[C][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].w, bf1[4 * q + 3], cacc[C][1], 0, 0, 0);    \
-        }                                                                                                    \
-      }                                                                                                      \
-      __builtin_amdgcn_sched_barrier(0);
-  // one entry: the next entry's weight tile goes to the idle fragment set, the A fragments of its first two tiles are requested
-  // under this entry's last MFMA groups (backbone_kernel's B2_ENTRY4 / B2_ENTRY2 without the schedule word)
-#define SG_ENTRY(BC, BN, UC, UN)                                                                             \
-    { const int nxt = it + 1 < 36 ? it + 1 : it;                                                             \
-      const float bf0[8] = {BC[0].x, BC[0].y, BC[0].z, BC[0].w, BC[1].x, BC[1].y, BC[1].z, BC[1].w};         \
-      const float bf1[8] = {BC[2].x, BC[2].y, BC[2].z, BC[2].w, BC[3].x, BC[3].y, BC[3].z, BC[3].w};         \
-      { const float* src = wsrc + (size_t)nxt * BB_C * CH;                                                   \
-        BN[0] = *reinterpret_cast<const float4*>(src);                                                       \
-        BN[1] = *reinterpret_cast<const float4*>(src + 4);                                                   \
-        BN[2] = *reinterpret_cast<const float4*>(src + 16 * CH);                                             \
-        BN[3] = *reinterpret_cast<const float4*>(src + 16 * CH + 4);                                         \
-      }                                                                                                      \
-      const int dbytes = SG_DBYTES(it), dbytes2 = SG_DBYTES(nxt);                                            \
-      if constexpr (NC == 4) {                                                                               \
-        SG_MM(0, ua)                                                                                         \
-        SG_ALOAD(2, ua, dbytes)                                                                              \
-        SG_MM(1, ub)                                                                                         \
-        SG_ALOAD(3, ub, dbytes)                                                                              \
-        SG_MM(NC - 2, ua)                                                                                    \
-        SG_ALOAD(0, ua, dbytes2)                                                                             \
-        SG_MM(NC - 1, ub)                                                                                    \
-        SG_ALOAD(1, ub, dbytes2)                                                                             \
-      } else if constexpr (NC == 1) {                    /* one tile: the fragment sets alternate by entry */ \
-        SG_ALOAD(0, UN, dbytes2)                                                                             \
-        SG_MM(0, UC)                                                                                         \
-      } else {                                                                                               \
-        SG_MM(0, ua)                                                                                         \
-        SG_ALOAD(0, ua, dbytes2)                                                                             \
-        SG_MM(1, ub)                                                                                         \
-        SG_ALOAD(1, ub, dbytes2)                                                                             \
-      }                                                                                                      \
-      ++it; }
-  float4 ua[2], ub[2];
-  SG_ALOAD(0, ua, SG_DBYTES(0))
-  if constexpr (NC > 1) SG_ALOAD(1, ub, SG_DBYTES(0))
-  for (int it = 0; it < 36;) {
-    SG_ENTRY(bA, bB, ua, ub)
-    SG_ENTRY(bB, bA, ub, ua)
-  }
-#undef SG_ENTRY
-#undef SG_MM
-#undef SG_ALOAD
-#undef SG_DBYTES
-
-  float* dst = pl0 + (size_t)cl * pl_stride;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    if (c >= nown) continue;
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int row = r0 + 16 * (c + 1) + 4 * g + e;
-        if (row < L) dst[row * BB_C + col0 + 16 * ct] = fmaxf(cacc[c][ct][e], 0.0f) + f[c + 1][ct][e];   // relu(conv + b) + f
-      }
-  }
-#undef SEG_LIVE
+// the two kernels: a layout each, and the occupancy its LDS image and register arrays allow
+template <int NC_, bool ORD_ = false, int DIL_ = 1>
+__global__ __launch_bounds__(256, NC_ == 4 ? 2 : NC_ == 1 ? 4 : 3) void backbone_seg_kernel(BackboneSegArgs a) {
+  using LAY = SegAligned<NC_, ORD_, DIL_>;
+#include "svdd_seg_body.h"
 }
-
-// backbone_seg_kernel<2, true, 1> for the TIGHT items of svdd_backbone_incr4_f32 (origin row | tiles << 8, any origin), with the
-// halo packed: a dilation-1 item reads 4 rows beyond its tiles on each side, so the image is rows origin - 4 .. origin + 16 nown + 3
-// (40 rows for two tiles where the aligned kernel holds 64) and the register arrays have THREE slots, not four: slots 0, 1 = the own
-// tiles (image rows 4 + 16 s + 4 g + e), slot 2 = both halos — the lanes with g = 0 hold the left one (image rows 0 .. 3), those
-// with g = 1 the right one (image rows 16 nown + 4 .. + 7), those with g = 2, 3 nothing (they neither load nor store; the VALU runs
-// them along). A row's LayerNorm sums over the 16 lanes of one g and the four waves, so it is the same tree whichever slot holds the
-// row. Everything else is backbone_seg_kernel's, line for line: lane-to-column ownership, (p0 + p1) + (p2 + p3), rsqrtf, the
-// accumulator starting at the bias, chunk outer / tap inner / 8 k-steps, a zero image row for a tap that leaves the sequence,
-// layer 1 through the image with the batched, clamped, select-not-add table reads, row < L on the plane stores.
 __global__ __launch_bounds__(256, 5) void backbone_seg_tight_kernel(BackboneSegArgs a) {
-  constexpr int NC = 2, NS = NC + 1, PK = NC, ROWS = 16 * NC + 8;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* img = smem;                                      // [ROWS][BB_AP] image row i = sequence row origin - 4 + i
-  float* psum = img + ROWS * BB_AP;                       // [4][ROWS]
-  float* rstat = psum + 4 * ROWS;                         // [ROWS]
-  int* toks = reinterpret_cast<int*>(rstat + ROWS);       // [ROWS + 8] tokens of sequence rows origin - 8 ..   (layer 1)
-
-  if ((int)blockIdx.x >= a.order_count[a.layer - 1]) return;
-  const unsigned ent = (unsigned)__builtin_amdgcn_readfirstlane(a.order[(size_t)(a.layer - 1) * a.order_stride + blockIdx.x]);
-  const int item = (int)(ent & 0xFFFFu), seq = (int)(ent >> 16);
-  const int nown = min(item >> 8, NC);
-  if (nown == 0) return;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int cg = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int j = lane & 15, g = lane >> 4;
-  const int col0 = 32 * cg + j;
-  const int L = a.L;
-  const int r0 = (item & 255) - 4;                        // sequence row of image row 0
-  const int nrows = 16 * nown + 8;                        // image rows the item uses
-  const bool halo = g < 2;                                // this lane holds rows of the packed slot
-  const int hrow = g == 1 ? 16 * nown + 4 : 0;            // ... from this image row on
-  const size_t pl_stride = (size_t)a.n * TW_ROWS * BB_C;
-  float* pl0 = a.planes + (size_t)seq * TW_ROWS * BB_C;
-  const int cl = a.layer - 1;                             // the conv layer this launch runs
-#define SGT_LIVE(S) ((S) < nown || (S) == PK)
-#define SGT_MINE(S) ((S) < PK || halo)
-#define SGT_IROW(S) ((S) < PK ? 4 + 16 * (S) + 4 * g : hrow)
-
-  f32x4 f[NS][2], acc[NS][2];
-  if (a.layer == 1) {
-    for (int e = tid; e < nrows + 8; e += 256) {
-      const int p = r0 - 4 + e;
-      toks[e] = (p >= 0 && p < L) ? (int)a.x[(size_t)seq * L + p] : -1;
-    }
-    __syncthreads();
-    {                                                     // f_0 of the item's rows through the image (see backbone_seg_kernel)
-      const int c = tid & (BB_C - 1);
-      const float b0 = a.vec[c];
-#pragma unroll 4
-      for (int ri = tid >> 7; ri < nrows; ri += 2) {
-        int tk[9];
-        float tv[9];
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-          tk[t] = toks[ri + t];                           // sequence row r0 + ri + t - 4 ; -1 outside the sequence
-          tv[t] = a.table0[(unsigned)((t * 5 + max(tk[t], 0)) * BB_C + c)];
-        }
-        float v = b0;
-#pragma unroll
-        for (int t = 0; t < 9; ++t) v = tk[t] >= 0 ? v + tv[t] : v;
-        const int row = r0 + ri;
-        img[ri * BB_AP + c] = (row >= 0 && row < L) ? fmaxf(v, 0.0f) : 0.0f;
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      if (!SGT_LIVE(s)) continue;
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) f[s][ct][e] = SGT_MINE(s) ? img[(SGT_IROW(s) + e) * BB_AP + col0 + 16 * ct] : 0.0f;
-    }
-  } else {
-    const float* src = pl0 + (size_t)(a.layer - 2) * pl_stride;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      if (!SGT_LIVE(s)) continue;
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int row = r0 + SGT_IROW(s) + e;
-          f[s][ct][e] = (SGT_MINE(s) && row >= 0 && row < L) ? src[row * BB_C + col0 + 16 * ct] : 0.0f;
-        }
-    }
-  }
-
-  // ---- LayerNorm(f + tb) of the item's tiles and its halo rows -> image
-  const float* vl = a.vec + (size_t)(cl + 1) * 4 * BB_C;
-  {
-    const float tb0 = vl[BB_C + col0], tb1 = vl[BB_C + col0 + 16];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      if (!SGT_LIVE(s)) continue;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float sm = group16_sum((f[s][0][e] + tb0) + (f[s][1][e] + tb1));
-        if (j == 0 && SGT_MINE(s)) psum[cg * ROWS + SGT_IROW(s) + e] = sm;
-      }
-    }
-    __syncthreads();
-    if (tid < nrows)
-      rstat[tid] = ((psum[tid] + psum[ROWS + tid]) + (psum[2 * ROWS + tid] + psum[3 * ROWS + tid])) * (1.0f / BB_C);
-    __syncthreads();
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      if (!SGT_LIVE(s)) continue;
-      const float4 cur4 = *reinterpret_cast<const float4*>(rstat + SGT_IROW(s));
-      const float mean4[4] = {cur4.x, cur4.y, cur4.z, cur4.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float mean = mean4[e];
-        const float d0 = f[s][0][e] + tb0 - mean, d1 = f[s][1][e] + tb1 - mean;
-        acc[s][0][e] = d0; acc[s][1][e] = d1;
-        const float sq = group16_sum(d0 * d0 + d1 * d1);
-        if (j == 0 && SGT_MINE(s)) psum[cg * ROWS + SGT_IROW(s) + e] = sq;
-      }
-    }
-    __syncthreads();
-    if (tid < nrows)
-      rstat[tid] = rsqrtf(((psum[tid] + psum[ROWS + tid]) + (psum[2 * ROWS + tid] + psum[3 * ROWS + tid])) * (1.0f / BB_C) + 1e-5f);
-    __syncthreads();
-    const float gm0 = vl[2 * BB_C + col0], gm1 = vl[2 * BB_C + col0 + 16];
-    const float bt0 = vl[3 * BB_C + col0], bt1 = vl[3 * BB_C + col0 + 16];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      if (!SGT_LIVE(s)) continue;
-      const float4 cur4 = *reinterpret_cast<const float4*>(rstat + SGT_IROW(s));
-      const float rs4[4] = {cur4.x, cur4.y, cur4.z, cur4.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int ri = SGT_IROW(s) + e, row = r0 + ri;
-        const float rs = rs4[e];
-        const bool in = row >= 0 && row < L;              // rows outside the sequence are the zero padding of the convolution
-        if (SGT_MINE(s)) {
-          img[ri * BB_AP + col0] = in ? acc[s][0][e] * rs * gm0 + bt0 : 0.0f;
-          img[ri * BB_AP + col0 + 16] = in ? acc[s][1][e] * rs * gm1 + bt1 : 0.0f;
-        }
-      }
-    }
-  }
-
-  // ---- the convolution of the own tiles: output row j of tile c reads image rows 16 c + j + t, t = 0 .. 8
-  const float bl0 = vl[col0], bl1 = vl[col0 + 16];
-  f32x4 cacc[NC][2];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) { cacc[c][0] = f32x4{bl0, bl0, bl0, bl0}; cacc[c][1] = f32x4{bl1, bl1, bl1, bl1}; }
-  typedef __attribute__((address_space(3))) f32x4 LdsF4;
-  const int img_lds = (int)(unsigned)(size_t)(const __attribute__((address_space(3))) float*)img;
-  const int arow0 = img_lds + (j * BB_AP + 8 * g) * 4;    // LDS byte address of (image row j, col 8 g)
-  const float* wsrc = a.tiles + (size_t)cl * 36 * BB_C * CH + col0 * CH + 8 * g;
-  const int live = (1 << nown) - 1;
-  float4 bA[4], bB[4];
-  bA[0] = *reinterpret_cast<const float4*>(wsrc);
-  bA[1] = *reinterpret_cast<const float4*>(wsrc + 4);
-  bA[2] = *reinterpret_cast<const float4*>(wsrc + 16 * CH);
-  bA[3] = *reinterpret_cast<const float4*>(wsrc + 16 * CH + 4);
-  bB[0] = bA[0]; bB[1] = bA[1]; bB[2] = bA[2]; bB[3] = bA[3];
-  __syncthreads();                                        // the image is complete
-#define SGT_DBYTES(IT) (((IT) % 9) * (BB_AP * 4) + ((IT) / 9) * (CH * 4))
-#define SGT_ALOAD(C, V, DBYTES)                                                                              \
-      { const LdsF4* ap_ = reinterpret_cast<const LdsF4*>(arow0 + (DBYTES) + (C) * (16 * BB_AP * 4));         \
-        const f32x4 t0_ = ap_[0], t1_ = ap_[1];                                                              \
-        V[0] = make_float4(t0_[0], t0_[1], t0_[2], t0_[3]); V[1] = make_float4(t1_[0], t1_[1], t1_[2], t1_[3]); }
-#define SGT_MM(C, U)                                                                                         \
-      __builtin_amdgcn_sched_barrier(0);                                                                     \
-      __builtin_amdgcn_s_waitcnt(0xC07F | (2 << 8));      /* at most the two reads of the other fragment set in flight */ \
-      if (live & (1 << (C))) {                                                                               \
-        _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                                      \
-          cacc[C][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].x, bf0[4 * q], cacc[C][0], 0, 0, 0);        \
-          cacc[C][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].x, bf1[4 * q], cacc[C][1], 0, 0, 0);        \
-          cacc[C][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].y, bf0[4 * q + 1], cacc[C][0], 0, 0, 0);    \
-          cacc[C][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].y, bf1[4 * q + 1], cacc[C][1], 0, 0, 0);    \
-          cacc[C][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].z, bf0[4 * q + 2], cacc[C][0], 0, 0, 0);    \
-          cacc[C][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].z, bf1[4 * q + 2], cacc[C][1], 0, 0, 0);    \
-          cacc[C][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].w, bf0[4 * q + 3], cacc[C][0], 0, 0, 0);    \
-          cacc[C][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].w, bf1[4 * q + 3], cacc[C][1], 0, 0, 0);    \
-        }                                                                                                    \
-      }                                                                                                      \
-      __builtin_amdgcn_sched_barrier(0);
-#define SGT_ENTRY(BC, BN)                                                                                    \
-    { const int nxt = it + 1 < 36 ? it + 1 : it;                                                             \
-      const float bf0[8] = {BC[0].x, BC[0].y, BC[0].z, BC[0].w, BC[1].x, BC[1].y, BC[1].z, BC[1].w};         \
-      const float bf1[8] = {BC[2].x, BC[2].y, BC[2].z, BC[2].w, BC[3].x, BC[3].y, BC[3].z, BC[3].w};         \
-      { const float* src = wsrc + (size_t)nxt * BB_C * CH;                                                   \
-        BN[0] = *reinterpret_cast<const float4*>(src);                                                       \
-        BN[1] = *reinterpret_cast<const float4*>(src + 4);                                                   \
-        BN[2] = *reinterpret_cast<const float4*>(src + 16 * CH);                                             \
-        BN[3] = *reinterpret_cast<const float4*>(src + 16 * CH + 4);                                         \
-      }                                                                                                      \
-      const int dbytes2 = SGT_DBYTES(nxt);                                                                   \
-      SGT_MM(0, ua)                                                                                          \
-      SGT_ALOAD(0, ua, dbytes2)                                                                              \
-      SGT_MM(1, ub)                                                                                          \
-      SGT_ALOAD(1, ub, dbytes2)                                                                              \
-      ++it; }
-  float4 ua[2], ub[2];
-  SGT_ALOAD(0, ua, SGT_DBYTES(0))
-  SGT_ALOAD(1, ub, SGT_DBYTES(0))
-  for (int it = 0; it < 36;) {
-    SGT_ENTRY(bA, bB)
-    SGT_ENTRY(bB, bA)
-  }
-#undef SGT_ENTRY
-#undef SGT_MM
-#undef SGT_ALOAD
-#undef SGT_DBYTES
-
-  float* dst = pl0 + (size_t)cl * pl_stride;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    if (c >= nown) continue;
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int row = r0 + 4 + 16 * c + 4 * g + e;
-        if (row < L) dst[row * BB_C + col0 + 16 * ct] = fmaxf(cacc[c][ct][e], 0.0f) + f[c][ct][e];   // relu(conv + b) + f
-      }
-  }
-#undef SGT_LIVE
-#undef SGT_MINE
-#undef SGT_IROW
+  using LAY = SegTight;
+#include "svdd_seg_body.h"
 }
 
 // ------------------------------------------- gradient of the backbone with respect to its one-hot input, ONE launch (round 5) ----
@@ -3091,7 +2631,6 @@ __global__ __launch_bounds__(512, 2) void backbone_grad_kernel(BackboneGradArgs 
   }
   __syncthreads();                                        // sched and the image are visible
 
-  typedef __attribute__((address_space(3))) f32x4 LdsF4;
   const int img_lds = (int)(unsigned)(size_t)(const __attribute__((address_space(3))) float*)img;
   const int arow0 = img_lds + ((16 * rh + j) * BB_AP + 8 * g) * 4;
   const int a_lo = arow0 - (16 * rh + j + 1) * BB_AP * 4;
@@ -3104,14 +2643,8 @@ __global__ __launch_bounds__(512, 2) void backbone_grad_kernel(BackboneGradArgs 
   it = __builtin_amdgcn_readfirstlane(it);
   int en = __builtin_amdgcn_readfirstlane(sched[it]);
   float4 bA[4], bB[4];
-  {
-    const float* src = wsrc + (size_t)tile_of(it) * BB_C * CH;
-    bA[0] = *reinterpret_cast<const float4*>(src);
-    bA[1] = *reinterpret_cast<const float4*>(src + 4);
-    bA[2] = *reinterpret_cast<const float4*>(src + 16 * CH);
-    bA[3] = *reinterpret_cast<const float4*>(src + 16 * CH + 4);
-    bB[0] = bA[0]; bB[1] = bA[1]; bB[2] = bA[2]; bB[3] = bA[3];
-  }
+  BB_WLOAD(bA, wsrc + (size_t)tile_of(it) * BB_C * CH)
+  bB[0] = bA[0]; bB[1] = bA[1]; bB[2] = bA[2]; bB[3] = bA[3];
 
   for (int step = 0; step <= nl; ++step) {
     const int layer = nl - step;                          // step >= 1: the conv layer whose transpose this step applies
@@ -3134,70 +2667,7 @@ __global__ __launch_bounds__(512, 2) void backbone_grad_kernel(BackboneGradArgs 
     const int dil = __builtin_amdgcn_readfirstlane(sdil[step]);
     const int layer_end = (step + 1) * 36;
     __syncthreads();                                      // the image is complete
-#define B2_ALOAD(R, V, DELTA, COFF, DBYTES)                                                                  \
-      { int o_;                                                                                              \
-        asm("v_med3_i32 %0, %1, %2, %3" : "=v"(o_) : "v"(arow0 + (DBYTES) + (R) * (32 * BB_AP * 4)), "v"(a_lo + (COFF)), "v"(a_hi + (COFF))); \
-        const LdsF4* ap_ = reinterpret_cast<const LdsF4*>(o_);                                               \
-        const f32x4 t0_ = ap_[0], t1_ = ap_[1];                                                              \
-        V[0] = make_float4(t0_[0], t0_[1], t0_[2], t0_[3]); V[1] = make_float4(t1_[0], t1_[1], t1_[2], t1_[3]); }
-#define B2_WAIT(NOUT) __builtin_amdgcn_s_waitcnt(0xC07F | ((NOUT) << 8));
-#define B2_MM(R, U, NOUT)                                                                                    \
-      __builtin_amdgcn_sched_barrier(0);                                                                     \
-      B2_WAIT(NOUT)                                                                                          \
-      if (live & (1 << (2 * (R)))) {                                                                         \
-        _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                                      \
-          acc[R][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].x, bf0[4 * q], acc[R][0], 0, 0, 0);          \
-          acc[R][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].x, bf1[4 * q], acc[R][1], 0, 0, 0);          \
-          acc[R][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].y, bf0[4 * q + 1], acc[R][0], 0, 0, 0);      \
-          acc[R][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].y, bf1[4 * q + 1], acc[R][1], 0, 0, 0);      \
-          acc[R][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].z, bf0[4 * q + 2], acc[R][0], 0, 0, 0);      \
-          acc[R][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].z, bf1[4 * q + 2], acc[R][1], 0, 0, 0);      \
-          acc[R][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].w, bf0[4 * q + 3], acc[R][0], 0, 0, 0);      \
-          acc[R][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].w, bf1[4 * q + 3], acc[R][1], 0, 0, 0);      \
-        }                                                                                                    \
-      }                                                                                                      \
-      __builtin_amdgcn_sched_barrier(0);
-#define B2_PARAMS(EN, DELTA, COFF, DBYTES)                                                                   \
-      const int DELTA = ((((EN) >> 15) & 15) - 4) * dil;                                                     \
-      const int COFF = (((EN) >> 13) & 3) * (CH * 4);                                                        \
-      const int DBYTES = DELTA * (BB_AP * 4) + COFF;
-#define B2_ENTRY(UA, UB, BC, BN)                                                                             \
-    { const int nxt = en >> 19;                                                                              \
-      const int en_next_v = sched[nxt < it_end ? nxt : it];                                                  \
-      const float bf0[8] = {BC[0].x, BC[0].y, BC[0].z, BC[0].w, BC[1].x, BC[1].y, BC[1].z, BC[1].w};         \
-      const float bf1[8] = {BC[2].x, BC[2].y, BC[2].z, BC[2].w, BC[3].x, BC[3].y, BC[3].z, BC[3].w};         \
-      { const float* src = wsrc + (size_t)tile_of(nxt < it_end ? nxt : it) * BB_C * CH;                      \
-        BN[0] = *reinterpret_cast<const float4*>(src);                                                       \
-        BN[1] = *reinterpret_cast<const float4*>(src + 4);                                                   \
-        BN[2] = *reinterpret_cast<const float4*>(src + 16 * CH);                                             \
-        BN[3] = *reinterpret_cast<const float4*>(src + 16 * CH + 4);                                         \
-      }                                                                                                      \
-      B2_PARAMS(en, delta, coff, dbytes)                                                                     \
-      const int live = en >> rh;                                                                             \
-      B2_MM(0, UA, 3)                                                                                        \
-      B2_ALOAD(2, UA, delta, coff, dbytes)                                                                   \
-      B2_MM(1, UB, 2)                                                                                        \
-      const int en2 = __builtin_amdgcn_readfirstlane(en_next_v);                                             \
-      B2_PARAMS(en2, delta2, coff2, dbytes2)                                                                 \
-      B2_ALOAD(3, UB, delta, coff, dbytes)                                                                   \
-      B2_MM(2, UA, 2)                                                                                        \
-      B2_ALOAD(4, UA, delta, coff, dbytes)                                                                   \
-      B2_MM(3, UB, 2)                                                                                        \
-      B2_ALOAD(5, UB, delta, coff, dbytes)                                                                   \
-      B2_MM(4, UA, 2)                                                                                        \
-      if (rh == 0) {                                                                                         \
-        B2_ALOAD(6, UA, delta, coff, dbytes)                                                                 \
-        B2_MM(5, UB, 2)                                                                                      \
-        B2_ALOAD(0, UB, delta2, coff2, dbytes2)                                                              \
-        B2_MM(6, UA, 2)                                                                                      \
-        B2_ALOAD(1, UA, delta2, coff2, dbytes2)                                                              \
-      } else {                                                                                               \
-        B2_ALOAD(0, UA, delta2, coff2, dbytes2)                                                              \
-        B2_MM(5, UB, 2)                                                                                      \
-        B2_ALOAD(1, UB, delta2, coff2, dbytes2)                                                              \
-      }                                                                                                      \
-      it = nxt;                                                                                              \
-      en = en2; }
+    // the forward kernel's entry loop (B2_* at file scope)
     float4 ua[2], ub[2];
     if (it < layer_end) {
       B2_PARAMS(en, delta0, coff0, dbytes0)
@@ -3219,11 +2689,6 @@ __global__ __launch_bounds__(512, 2) void backbone_grad_kernel(BackboneGradArgs 
       }
     }
     if (odd) { bA[0] = bB[0]; bA[1] = bB[1]; bA[2] = bB[2]; bA[3] = bB[3]; }
-#undef B2_ENTRY
-#undef B2_PARAMS
-#undef B2_MM
-#undef B2_WAIT
-#undef B2_ALOAD
     __syncthreads();                                      // every wave is done reading the image
     if (step == 0) {
 #pragma unroll
@@ -3418,13 +2883,7 @@ __global__ __launch_bounds__(512, 2) void backbone_split_kernel(BackboneArgs a, 
   it = __builtin_amdgcn_readfirstlane(it);
   int en = __builtin_amdgcn_readfirstlane(sched[it]);
   float4 bn[4];
-  {
-    const float* src = wsrc + (size_t)tile_of(it) * BB_C * CH;
-    bn[0] = *reinterpret_cast<const float4*>(src);
-    bn[1] = *reinterpret_cast<const float4*>(src + 4);
-    bn[2] = *reinterpret_cast<const float4*>(src + 16 * CH);
-    bn[3] = *reinterpret_cast<const float4*>(src + 16 * CH + 4);
-  }
+  BB_WLOAD(bn, wsrc + (size_t)tile_of(it) * BB_C * CH)
   float* const xg = ws.xchg + (size_t)grp * 2 * TW_ROWS * BB_C;      // this group's two scratch images
   int* const gcnt = ws.cnt + grp;
 
@@ -3553,18 +3012,7 @@ __global__ __launch_bounds__(512, 2) void backbone_split_kernel(BackboneArgs a, 
 #define S_MM(R_, U)                                                                                          \
       __builtin_amdgcn_sched_barrier(0);                                                                     \
       __builtin_amdgcn_s_waitcnt(0xC07F | (2 << 8));      /* at least two LDS reads (the other set's) were issued after U's */ \
-      if (live & (1 << (TS * (R_)))) {                                                                       \
-        _Pragma("unroll") for (int qq = 0; qq < 2; ++qq) {                                                   \
-          acc[R_][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[qq].x, bf0[4 * qq], acc[R_][0], 0, 0, 0);      \
-          acc[R_][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[qq].x, bf1[4 * qq], acc[R_][1], 0, 0, 0);      \
-          acc[R_][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[qq].y, bf0[4 * qq + 1], acc[R_][0], 0, 0, 0);  \
-          acc[R_][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[qq].y, bf1[4 * qq + 1], acc[R_][1], 0, 0, 0);  \
-          acc[R_][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[qq].z, bf0[4 * qq + 2], acc[R_][0], 0, 0, 0);  \
-          acc[R_][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[qq].z, bf1[4 * qq + 2], acc[R_][1], 0, 0, 0);  \
-          acc[R_][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[qq].w, bf0[4 * qq + 3], acc[R_][0], 0, 0, 0);  \
-          acc[R_][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[qq].w, bf1[4 * qq + 3], acc[R_][1], 0, 0, 0);  \
-        }                                                                                                    \
-      }                                                                                                      \
+      BB_MM16(acc[R_], U, live & (1 << (TS * (R_))))                                                         \
       __builtin_amdgcn_sched_barrier(0);
 #define S_PARAMS(EN, COFF, DBYTES)                                                                           \
       const int COFF = (((EN) >> 13) & 3) * (CH * 4);                                                        \
@@ -3578,15 +3026,8 @@ __global__ __launch_bounds__(512, 2) void backbone_split_kernel(BackboneArgs a, 
     while (it < layer_end) {
       const int nxt = en >> 19;
       const int en_next_v = sched[nxt < it_end ? nxt : it];
-      const float bf0[8] = {bn[0].x, bn[0].y, bn[0].z, bn[0].w, bn[1].x, bn[1].y, bn[1].z, bn[1].w};
-      const float bf1[8] = {bn[2].x, bn[2].y, bn[2].z, bn[2].w, bn[3].x, bn[3].y, bn[3].z, bn[3].w};
-      if (nxt < it_end) {
-        const float* src = wsrc + (size_t)tile_of(nxt) * BB_C * CH;
-        bn[0] = *reinterpret_cast<const float4*>(src);
-        bn[1] = *reinterpret_cast<const float4*>(src + 4);
-        bn[2] = *reinterpret_cast<const float4*>(src + 16 * CH);
-        bn[3] = *reinterpret_cast<const float4*>(src + 16 * CH + 4);
-      }
+      BB_UNPACK(bn)
+      if (nxt < it_end) BB_WLOAD(bn, wsrc + (size_t)tile_of(nxt) * BB_C * CH)
       S_PARAMS(en, coff, dbytes)
       const int live = (en & 0x1fff) >> t0;               // bit TS r = owned tile r (tiles >= 13 do not exist)
       S_MM(0, ua)
