@@ -32,4 +32,33 @@ __device__ __forceinline__ float group16_sum(float v) {        // sum over the 1
   return v;
 }
 
+// s_waitcnt lgkmcnt(NOUT): wait until at most NOUT LDS reads are outstanding, vmcnt and expcnt untouched. The MFMA groups of the
+// conv tower and of the backbone are fenced behind one such wait (svdd_nets.hip)
+#define LGKM_WAIT(NOUT) __builtin_amdgcn_s_waitcnt(0xC07F | ((NOUT) << 8));
+
+// The value net's tower the window and part rules are written for: TP_BLOCKS conv blocks after the stem. A row next to a window
+// edge that is no sequence end sees zeros for its real neighbours and is wrong by up to two rows per block: TW_EDGE rows.
+constexpr int TP_BLOCKS = 5;
+constexpr int TW_EDGE = 2 * TP_BLOCKS;
+
+// Head of a tower kernel that may run on candidate WINDOWS (the fp32 towers of svdd_nets.hip and tower_lp_kernel): A holds count /
+// live_idx / win. Workgroup blockIdx.x computes candidate cand's rows [w0, w1), nt row tiles of 16, and KEEPS rows [keep_lo,
+// keep_hi) of them (a window edge that is a sequence end is exact); every other row is its parent's. !WIN: all zero.
+// CAND = TW_CAND_BRANCH or TW_CAND_SELECT: the same choice as a branch or as a select, each kernel's former shape (the other one
+// changes its instructions).
+#define TW_CAND_BRANCH(A) if (A.live_idx) cand = __builtin_amdgcn_readfirstlane(A.live_idx[blockIdx.x]);
+#define TW_CAND_SELECT(A) cand = A.live_idx ? __builtin_amdgcn_readfirstlane(A.live_idx[blockIdx.x]) : (int)blockIdx.x;
+#define TW_WIN_DECODE(A, WIN, CAND)                                                                           \
+  int cand = blockIdx.x, w0 = 0, w1 = 0;                                                                      \
+  if (WIN) {                                                                                                  \
+    if (A.count && (int)blockIdx.x >= __builtin_amdgcn_readfirstlane(*A.count)) return;                       \
+    CAND(A)                                                                                                   \
+    w0 = __builtin_amdgcn_readfirstlane(A.win[2 * cand]);                                                     \
+    w1 = __builtin_amdgcn_readfirstlane(A.win[2 * cand + 1]);                                                 \
+  }                                                                                                           \
+  const int nt = (w1 - w0) >> 4;
+#define TW_WIN_KEEP(WIN, L)                                                                                   \
+  const int keep_lo = !(WIN) ? 0 : (nt == 0 ? 0 : (w0 == 0 ? 0 : w0 + TW_EDGE));                              \
+  const int keep_hi = !(WIN) ? 0 : (nt == 0 ? 0 : (w1 >= L ? L : w1 - TW_EDGE));
+
 }  // namespace

@@ -193,21 +193,12 @@ __global__ __launch_bounds__(512, 4) void tower_lp_kernel(TowerLpArgs a) {
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int L = a.L;
 
-  int cand = blockIdx.x;
-  int w0 = 0, w1 = 0;
-  if (WIN) {
-    if (a.count && (int)blockIdx.x >= __builtin_amdgcn_readfirstlane(*a.count)) return;
-    if (a.live_idx) cand = __builtin_amdgcn_readfirstlane(a.live_idx[blockIdx.x]);
-    w0 = __builtin_amdgcn_readfirstlane(a.win[2 * cand]);
-    w1 = __builtin_amdgcn_readfirstlane(a.win[2 * cand + 1]);
-  }
-  const int nt = (w1 - w0) >> 4;
+  TW_WIN_DECODE(a, WIN, TW_CAND_BRANCH)                                     // cand, w0, w1, nt: svdd_device.h, the fp32 window towers' own
   const int tile_rows = WIN ? min(L, w1) - w0 : a.spt * L;       // valid local rows
   const int64_t row0 = WIN ? 0 : (int64_t)blockIdx.x * tile_rows;
   const int64_t total_rows = (int64_t)((!WIN && a.count) ? __builtin_amdgcn_readfirstlane(*a.count) : a.n) * L;
   if (!WIN && row0 >= total_rows) return;
-  const int keep_lo = !WIN ? 0 : (nt == 0 ? 0 : (w0 == 0 ? 0 : w0 + 10));
-  const int keep_hi = !WIN ? 0 : (nt == 0 ? 0 : (w1 >= L ? L : w1 - 10));
+  TW_WIN_KEEP(WIN, L)                                            // keep_lo, keep_hi
   constexpr int ROW16 = NPARTS * 8;                              // 16-byte pieces per output row
   uint4* outc = reinterpret_cast<uint4*>(a.out) + (WIN ? (size_t)blockIdx.x * L * ROW16 : 0);
 
@@ -308,7 +299,7 @@ extern "C" int svdd_conv_tower_windows_lp(const uint8_t* cand, const void* tiles
                                           int nlayers, int residual_mask, const int32_t* live_idx, const int32_t* count,
                                           int prec, void* stream) {
   if (!cand || !tiles || !bias || !inv || !win || !parent_out || !out || n <= 0 || M <= 0 || n % M || L <= TW_ROWS / 2 ||
-      L > TW_ROWS || nlayers != 5 || prec < SVDD_PREC_F16X3 || prec > SVDD_PREC_BF16)
+      L > TW_ROWS || nlayers != TP_BLOCKS || prec < SVDD_PREC_F16X3 || prec > SVDD_PREC_BF16)
     return SVDD_E_ARG;
   TowerLpArgs a{cand, tiles, bias, inv, out, n, L, 1, nlayers, residual_mask, win, parent_out, M, live_idx, count};
   return launch_tower_lp(a, true, prec, (unsigned)n, stream);

@@ -784,6 +784,137 @@ struct TowerArgs {
   const int* count;      // device scalar: valid rows of a compacted batch (NULL: n) ; conv_tower_kernel only
 };
 
+// ------------------------------------------------------------------- the pieces of the fp32 tower family, defined ONCE ----
+// conv_tower_kernel, conv_tower_win_kernel (generation 1), conv_tower2_kernel (generation 2) and conv_tower_parts_kernel must give
+// each other's bits: a candidate's rows are either copied from its parent's tower output or recomputed, by whichever of them. So
+// what decides a bit is text they share: the weight stream (which tile, which k-step feeds which MFMA), the order of the MFMAs of
+// one accumulator, which image bytes a tap reads and what a row past the sequence reads (the zero rows -1 and TW_ROWS), and the
+// epilogue bias -> residual -> ReLU. What MAY differ between kernels, and only that: which wave and lane owns which (row tile,
+// column tile), the orientation of the accumulator (generation 2 is transposed), how many tiles are live and where a tile's first
+// row lies, the schedule of fragment requests against MFMA groups, and which rows are staged, kept and stored. The pieces are macros
+// on purpose, as BB_* / B2_* below: they name the locals of the kernel that uses them (wsrc, it, nit, actb, a_lo, a_hi, chk, delta,
+// xs, acc ...), and textual sharing keeps every kernel's instruction stream what it was.
+//
+// Weight stream: BN = float4[2 CT], this lane's slice of the next tile for CT column tiles; B[CT][8] the current one, unpacked.
+// TW_WLOAD1 / TW_UNPACK1 are one column tile of them, its two float4 named by the user; the *_ONE forms are for the kernels with one
+// column tile per wave, which name them directly (generation 1: two variables, the parts kernel: bn[0], bn[1]): through the CT
+// loop, or in generation 1 through an array, their instructions change.
+#define TW_WLOAD1(BN0, BN1, SRC)                                                                              \
+  BN0 = *reinterpret_cast<const float4*>(SRC);                                                                \
+  BN1 = *reinterpret_cast<const float4*>((SRC) + 4);
+#define TW_UNPACK1(B, BN0, BN1)                                                                               \
+  B[0] = BN0.x; B[1] = BN0.y; B[2] = BN0.z; B[3] = BN0.w; B[4] = BN1.x; B[5] = BN1.y; B[6] = BN1.z; B[7] = BN1.w;
+#define TW_WLOAD(BN, SRC, CT)                                                                                 \
+  { const float* src_ = (SRC);                                                                                \
+    _Pragma("unroll") for (int ct_ = 0; ct_ < CT; ++ct_) { TW_WLOAD1(BN[2 * ct_], BN[2 * ct_ + 1], src_ + ct_ * 16 * CH) } }
+#define TW_WLOAD_ONE(BN0, BN1, SRC) { const float* src_ = (SRC); TW_WLOAD1(BN0, BN1, src_) }
+#define TW_UNPACK(B, BN, CT)                                                                                  \
+  float B[CT][8];                                                                                             \
+  _Pragma("unroll") for (int ct_ = 0; ct_ < CT; ++ct_) { TW_UNPACK1(B[ct_], BN[2 * ct_], BN[2 * ct_ + 1]) }
+#define TW_UNPACK_ONE(B, BN0, BN1) float B[1][8]; TW_UNPACK1(B[0], BN0, BN1)
+// the tile of iteration it + 1 flies under the MFMAs of iteration it (tiles are stored in execution order)
+#define TW_WNEXT(BN, CT) if (it + 1 < nit) TW_WLOAD(BN, wsrc + (size_t)(it + 1) * TW_C * CH, CT)
+#define TW_WNEXT_ONE(BN0, BN1) if (it + 1 < nit) TW_WLOAD_ONE(BN0, BN1, wsrc + (size_t)(it + 1) * TW_C * CH)
+// iteration ci of a conv block: 32-channel chunk chk, tap delta = -2 .. 2 ; dbytes = what both add to an image byte offset
+#define TW_TAP(CI)                                                                                            \
+  const int chk = (CI) / 5, delta = (CI) - 5 * chk - 2;                                                       \
+  const int dbytes = delta * (TW_AP * 4) + chk * (CH * 4);
+// A fragment V (float4[2]) of the image at byte offset OFF ; CLAMPED: one sequence per image, a row before / past the image reads
+// the zero row -1 / TW_ROWS ; APOS: several sequences per image, POS = the row's position in its sequence
+#define TW_ALOAD(V, OFF)                                                                                      \
+  { const float4* ap_ = reinterpret_cast<const float4*>(actb + (OFF)); V[0] = ap_[0]; V[1] = ap_[1]; }
+#define TW_ALOAD_CLAMPED(V, OFF) TW_ALOAD(V, min(max((OFF), a_lo + chk * (CH * 4)), a_hi + chk * (CH * 4)))
+#define TW_ALOAD_APOS(V, POS, OFF) TW_ALOAD(V, (unsigned)((POS) + delta) < (unsigned)L ? (OFF) : a_hi + chk * (CH * 4))
+// the stem's fragment: k = 32 ci + 8 g + s covers taps t0 = 8 ci + 2 g and t0 + 1 (4 channels each): V[Q] = one-hot row IDX
+#define TW_XLOAD(V, Q, IDX) V[Q] = *reinterpret_cast<const float4*>(xs + 4 * (IDX));
+// Generation 1: wave parity rh owns the row tiles rh + 2 r, r < 7 ; the last one (12 = 0 + 2 * 6) belongs to parity 0
+#define TW_OWNED(R) (!((R) == 6 && rh == 1))
+// Generation 1: the MFMAs of CNT row tiles R0 .. of one weight tile bf, k-step by k-step across the tiles (8 per accumulator, in
+// k order); AF[r_] = tile R0 + r_'s fragment, LIVE (it may name r_) = the tile exists
+#define TW_MM1(AF, R0, CNT, LIVE)                                                                             \
+  _Pragma("unroll") for (int q_ = 0; q_ < 2; ++q_) {                                                          \
+    _Pragma("unroll") for (int r_ = 0; r_ < CNT; ++r_) if (LIVE) acc[R0 + r_] = __builtin_amdgcn_mfma_f32_16x16x4f32(AF[r_][q_].x, bf[0][4 * q_], acc[R0 + r_], 0, 0, 0);     \
+    _Pragma("unroll") for (int r_ = 0; r_ < CNT; ++r_) if (LIVE) acc[R0 + r_] = __builtin_amdgcn_mfma_f32_16x16x4f32(AF[r_][q_].y, bf[0][4 * q_ + 1], acc[R0 + r_], 0, 0, 0); \
+    _Pragma("unroll") for (int r_ = 0; r_ < CNT; ++r_) if (LIVE) acc[R0 + r_] = __builtin_amdgcn_mfma_f32_16x16x4f32(AF[r_][q_].z, bf[0][4 * q_ + 2], acc[R0 + r_], 0, 0, 0); \
+    _Pragma("unroll") for (int r_ = 0; r_ < CNT; ++r_) if (LIVE) acc[R0 + r_] = __builtin_amdgcn_mfma_f32_16x16x4f32(AF[r_][q_].w, bf[0][4 * q_ + 3], acc[R0 + r_], 0, 0, 0); \
+  }
+// Generation 1's schedule of a (chunk, tap) iteration: tile groups (0,1,2)(3,4)(5,6) through two register buffers, each group's
+// reads one group ahead. LD(R, V) requests tile R's fragment (and skips tile 6 for parity 1), G3 / G2(AF, R0) = the MFMAs of 3 / 2 tiles
+#define TW_SCHED322(LD, G3, G2)                                                                               \
+  LD(0, fa[0]) LD(1, fa[1]) LD(2, fa[2])                                                                      \
+  LD(3, fb[0]) LD(4, fb[1])                                                                                   \
+  __builtin_amdgcn_sched_barrier(0);                                                                          \
+  LGKM_WAIT(4)                                                                                                \
+  G3(fa, 0)                                                                                                   \
+  __builtin_amdgcn_sched_barrier(0);                                                                          \
+  LD(5, fa[0]) LD(6, fa[1])                                                                                   \
+  __builtin_amdgcn_sched_barrier(0);                                                                          \
+  if (rh == 1) { LGKM_WAIT(2) } else { LGKM_WAIT(4) }                                                         \
+  G2(fb, 3)                                                                                                   \
+  __builtin_amdgcn_sched_barrier(0);                                                                          \
+  LGKM_WAIT(0)                                                                                                \
+  G2(fa, 5)                                                                                                   \
+  __builtin_amdgcn_sched_barrier(0);
+// Generation 1's layer epilogue (C/D layout: reg e -> row 4 g + e, column j): every wave must be done reading the image before its
+// owners overwrite it (the stem reads xs, not the image); rows from NROWS on stay zero
+#define TW_EPILOGUE1(LIVE, NROWS)                                                                             \
+  if (layer >= 0) __syncthreads();                                                                            \
+  const bool res = layer >= 0 && ((a.residual_mask >> layer) & 1);                                            \
+  _Pragma("unroll") for (int r = 0; r < 7; ++r) {                                                             \
+    if (!(LIVE)) continue;                                                                                    \
+    _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                                           \
+      const int row = 16 * (rh + 2 * r) + 4 * g + e;                                                          \
+      const int o = row * TW_AP + 16 * cs + j;                                                                \
+      const float v = acc[r][e] + (res ? act[o] : 0.0f);                                                      \
+      act[o] = row < (NROWS) ? fmaxf(v, 0.0f) : 0.0f;                                                         \
+    }                                                                                                         \
+  }                                                                                                           \
+  __syncthreads();                                       /* the image is complete */
+// Generation 2 (transposed: the weight fragment is the A operand): the MFMAs of NL row tiles x CT column tiles of one weight tile b
+#define TW_MM2(NL, CT)                                                                                        \
+  _Pragma("unroll") for (int r = 0; r < NL; ++r)                                                              \
+    _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                                           \
+      const float av[4] = {af[r][q].x, af[r][q].y, af[r][q].z, af[r][q].w};                                   \
+      _Pragma("unroll") for (int s4 = 0; s4 < 4; ++s4)                                                        \
+        _Pragma("unroll") for (int ct = 0; ct < CT; ++ct)                                                     \
+          acc[r][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[ct][4 * q + s4], av[s4], acc[r][ct], 0, 0, 0);  \
+    }
+// Heads and tails. The one-hot image xs: rows -HALO .. TW_ROWS + HALO of a tile of whole sequences (zero outside the tile), or
+// rows W0 - 8 .. of the sequence XC (real data beyond a window, zero outside the sequence)
+#define TW_STAGE_SEQ(XC, HALO)                                                                                \
+  for (int e = tid - (HALO); e < TW_ROWS + (HALO); e += 512) {                                                \
+    float4 v = {0.0f, 0.0f, 0.0f, 0.0f};                                                                      \
+    if (e >= 0 && e < tile_rows && row0 + e < total_rows) v = *reinterpret_cast<const float4*>((XC) + (row0 + e) * 4); \
+    *reinterpret_cast<float4*>(xs + 4 * e) = v;                                                               \
+  }
+#define TW_STAGE_WIN(XC, W0)                                                                                  \
+  for (int e = tid - 8; e < TW_ROWS + 8; e += 512) {                                                          \
+    const int gl = (W0) + e;                                                                                  \
+    float4 v = {0.0f, 0.0f, 0.0f, 0.0f};                                                                      \
+    if (gl >= 0 && gl < L) v = *reinterpret_cast<const float4*>((XC) + (size_t)gl * 4);                       \
+    *reinterpret_cast<float4*>(xs + 4 * e) = v;                                                               \
+  }
+// a window candidate's rows outside [keep_lo, keep_hi) are its parent's, straight from its output ; the kept ones are the image's
+#define TW_COPY_PARENT_WIN(PAR)                                                                               \
+  for (int e = tid; e < L * 16; e += 512) {                                                                   \
+    const int row = e >> 4;                                                                                   \
+    if (row < keep_lo || row >= keep_hi)                                                                      \
+      *reinterpret_cast<float4*>(outc + (size_t)row * TW_C + 4 * (e & 15)) = *reinterpret_cast<const float4*>((PAR) + (size_t)row * TW_C + 4 * (e & 15)); \
+  }
+#define TW_STORE_WIN                                                                                          \
+  for (int e = tid; e < L * 16; e += 512) {                                                                   \
+    const int row = e >> 4, q = e & 15;                                                                       \
+    if (row >= keep_lo && row < keep_hi)                                                                      \
+      *reinterpret_cast<float4*>(outc + (size_t)row * TW_C + 4 * q) = *reinterpret_cast<const float4*>(act + (row - w0) * TW_AP + 4 * q); \
+  }
+// final image of a tile of whole sequences -> HBM, 16 B per thread, rows contiguous
+#define TW_STORE_SEQ                                                                                          \
+  for (int e = tid; e < tile_rows * 16; e += 512) {                                                           \
+    const int row = e >> 4, q = e & 15;                                                                       \
+    if (row0 + row < total_rows)                                                                              \
+      *reinterpret_cast<float4*>(a.out + (row0 + row) * TW_C + 4 * q) = *reinterpret_cast<const float4*>(act + row * TW_AP + 4 * q); \
+  }
+
 // One LDS activation image only: a layer's outputs wait in the accumulators until every wave has finished reading
 // the image, then each wave overwrites the positions it owns (reading its own residual first). 57 KB of LDS and
 // <= 128 VGPRs per wave => TWO workgroups (16 waves) per CU, which overlap each other's barriers, LDS latency and
@@ -809,14 +940,11 @@ __global__ __launch_bounds__(512, 4) void conv_tower_kernel(TowerArgs a) {
   const int64_t total_rows = (int64_t)(a.count ? __builtin_amdgcn_readfirstlane(*a.count) : a.n) * L;
   if (row0 >= total_rows) return;
 
-  for (int e = tid - 1; e < TW_ROWS + 1; e += 512) {
-    float4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (e >= 0 && e < tile_rows && row0 + e < total_rows) v = *reinterpret_cast<const float4*>(a.x + (row0 + e) * 4);
-    *reinterpret_cast<float4*>(xs + 4 * e) = v;
-  }
+  TW_STAGE_SEQ(a.x, 1)
   for (int e = tid; e < TW_AP; e += 512) { smem[e] = 0.0f; act[TW_ROWS * TW_AP + e] = 0.0f; }
   const float* wsrc = a.tiles + (16 * cs + j) * CH + 8 * g;
-  float4 bn0 = *reinterpret_cast<const float4*>(wsrc), bn1 = *reinterpret_cast<const float4*>(wsrc + 4);
+  float4 bn0, bn1;
+  TW_WLOAD_ONE(bn0, bn1, wsrc)
 
   const int arow0 = 16 * rh + j;                        // this lane feeds rows arow0 + 32 r as the A operand
   int apos[SPT1 ? 1 : 7];
@@ -834,14 +962,8 @@ __global__ __launch_bounds__(512, 4) void conv_tower_kernel(TowerArgs a) {
   f32x4 acc[7];
   __syncthreads();                                       // xs and the zero rows are visible
 
-#define TW_WAIT(NOUT) __builtin_amdgcn_s_waitcnt(0xC07F | ((NOUT) << 8));
-#define TW_MMA(AF, R0, R1)                                                                                    \
-  _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                                             \
-    _Pragma("unroll") for (int r = R0; r < R1; ++r) if (!(r == 6 && rh == 1)) acc[r] = __builtin_amdgcn_mfma_f32_16x16x4f32(AF[r - R0][q].x, bf[4 * q], acc[r], 0, 0, 0);     \
-    _Pragma("unroll") for (int r = R0; r < R1; ++r) if (!(r == 6 && rh == 1)) acc[r] = __builtin_amdgcn_mfma_f32_16x16x4f32(AF[r - R0][q].y, bf[4 * q + 1], acc[r], 0, 0, 0); \
-    _Pragma("unroll") for (int r = R0; r < R1; ++r) if (!(r == 6 && rh == 1)) acc[r] = __builtin_amdgcn_mfma_f32_16x16x4f32(AF[r - R0][q].z, bf[4 * q + 2], acc[r], 0, 0, 0); \
-    _Pragma("unroll") for (int r = R0; r < R1; ++r) if (!(r == 6 && rh == 1)) acc[r] = __builtin_amdgcn_mfma_f32_16x16x4f32(AF[r - R0][q].w, bf[4 * q + 3], acc[r], 0, 0, 0); \
-  }
+#define TW_GROUP3(AF, R0) TW_MM1(AF, R0, 3, TW_OWNED((R0) + r_))
+#define TW_GROUP2(AF, R0) TW_MM1(AF, R0, 2, TW_OWNED((R0) + r_))
 
   for (int layer = -1; layer < a.nlayers; ++layer) {     // layer -1 = the stem (15 taps x 4 channels as K = 64)
     const float bl = a.bias[(layer + 1) * TW_C + 16 * cs + j];
@@ -849,14 +971,9 @@ __global__ __launch_bounds__(512, 4) void conv_tower_kernel(TowerArgs a) {
     for (int r = 0; r < 7; ++r) acc[r] = f32x4{bl, bl, bl, bl};
     const int niter = layer < 0 ? 2 : 10;
     for (int ci = 0; ci < niter; ++ci, ++it) {
-      const float bf[8] = {bn0.x, bn0.y, bn0.z, bn0.w, bn1.x, bn1.y, bn1.z, bn1.w};
-      if (it + 1 < nit) {                                // the next tile's slice flies under the MFMAs
-        const float* src = wsrc + (size_t)(it + 1) * TW_C * CH;
-        bn0 = *reinterpret_cast<const float4*>(src);
-        bn1 = *reinterpret_cast<const float4*>(src + 4);
-      }
+      TW_UNPACK_ONE(bf, bn0, bn1)
+      TW_WNEXT_ONE(bn0, bn1)
       if (layer < 0) {
-        // k = 32 ci + 8 g + s covers taps t0 = 8 ci + 2 g and t0 + 1 (4 channels each): two float4 of the one-hot tile
         const int t0 = 8 * ci + 2 * g;
         float4 af[4][2];
 #pragma unroll
@@ -871,65 +988,28 @@ __global__ __launch_bounds__(512, 4) void conv_tower_kernel(TowerArgs a) {
               int idx;
               if (SPT1) idx = min(max(rr, -1), TW_ROWS);
               else idx = (unsigned)(apos[SPT1 ? 0 : r] + t0 + q - 7) < (unsigned)L ? rr : TW_ROWS;
-              af[r - r0][q] = *reinterpret_cast<const float4*>(xs + 4 * idx);
+              TW_XLOAD(af[r - r0], q, idx)
             }
           }
-          if (half == 0) { TW_MMA(af, 0, 4) } else { TW_MMA(af, 4, 7) }
+          if (half == 0) { TW_MM1(af, 0, 4, TW_OWNED(r_)) } else { TW_MM1(af, 4, 3, TW_OWNED(4 + r_)) }
         }
       } else {
-        const int c = ci / 5, delta = ci - 5 * c - 2;
-        const int dbytes = delta * (TW_AP * 4) + c * (CH * 4);
-        // tile groups (0,1,2)(3,4)(5,6) through two register buffers, each group's reads one group ahead
+        TW_TAP(ci)
         float4 fa[3][2], fb[2][2];
-#define TW_ALOAD(R, V)                                                                                        \
-        if (!((R) == 6 && rh == 1)) {                                                                         \
-          int o_;                                                                                             \
-          if (SPT1) o_ = min(max(abase + dbytes + (R) * (32 * TW_AP * 4), a_lo + c * (CH * 4)), a_hi + c * (CH * 4)); \
-          else o_ = (unsigned)(apos[SPT1 ? 0 : (R)] + delta) < (unsigned)L ? abase + dbytes + (R) * (32 * TW_AP * 4) \
-                                                                         : a_hi + c * (CH * 4);               \
-          const float4* ap_ = reinterpret_cast<const float4*>(actb + o_);                                     \
-          V[0] = ap_[0]; V[1] = ap_[1];                                                                       \
+#define TW_LD(R, V)                                                                                           \
+        if (TW_OWNED(R)) {                                                                                    \
+          if (SPT1) { TW_ALOAD_CLAMPED(V, abase + dbytes + (R) * (32 * TW_AP * 4)) }                          \
+          else { TW_ALOAD_APOS(V, apos[SPT1 ? 0 : (R)], abase + dbytes + (R) * (32 * TW_AP * 4)) }            \
         }
-        TW_ALOAD(0, fa[0]) TW_ALOAD(1, fa[1]) TW_ALOAD(2, fa[2])
-        TW_ALOAD(3, fb[0]) TW_ALOAD(4, fb[1])
-        __builtin_amdgcn_sched_barrier(0);
-        TW_WAIT(4)
-        TW_MMA(fa, 0, 3)
-        __builtin_amdgcn_sched_barrier(0);
-        TW_ALOAD(5, fa[0]) TW_ALOAD(6, fa[1])
-        __builtin_amdgcn_sched_barrier(0);
-        if (rh == 1) { TW_WAIT(2) } else { TW_WAIT(4) }
-        TW_MMA(fb, 3, 5)
-        __builtin_amdgcn_sched_barrier(0);
-        TW_WAIT(0)
-        TW_MMA(fa, 5, 7)
-        __builtin_amdgcn_sched_barrier(0);
-#undef TW_ALOAD
+        TW_SCHED322(TW_LD, TW_GROUP3, TW_GROUP2)
+#undef TW_LD
       }
     }
-    // every wave must be done reading the image before its owners overwrite it (the stem reads xs, not the image)
-    if (layer >= 0) __syncthreads();
-    const bool res = layer >= 0 && ((a.residual_mask >> layer) & 1);
-#pragma unroll
-    for (int r = 0; r < 7; ++r) {
-      if (r == 6 && rh == 1) continue;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {                      // C/D layout: reg e -> row 4 g + e, column j
-        const int row = 16 * (rh + 2 * r) + 4 * g + e;
-        const int o = row * TW_AP + 16 * cs + j;
-        const float v = acc[r][e] + (res ? act[o] : 0.0f);
-        act[o] = row < tile_rows ? fmaxf(v, 0.0f) : 0.0f;
-      }
-    }
-    __syncthreads();                                     // the image is complete
+    TW_EPILOGUE1(TW_OWNED(r), tile_rows)
   }
-#undef TW_MMA
-#undef TW_WAIT
-  for (int e = tid; e < tile_rows * 16; e += 512) {      // final image -> HBM, 16 B per thread, rows contiguous
-    const int row = e >> 4, q = e & 15;
-    if (row0 + row < total_rows)
-      *reinterpret_cast<float4*>(a.out + (row0 + row) * TW_C + 4 * q) = *reinterpret_cast<const float4*>(act + row * TW_AP + 4 * q);
-  }
+#undef TW_GROUP2
+#undef TW_GROUP3
+  TW_STORE_SEQ
 }
 
 // ---------------------------------------------- conv tower on candidate WINDOWS (SVDD-MC: M candidates per parent) ----
@@ -939,7 +1019,7 @@ __global__ __launch_bounds__(512, 4) void conv_tower_kernel(TowerArgs a) {
 // products in the same order). This kernel computes, per candidate, only a contiguous row window [w0, w1) (multiples
 // of 16) that covers the changed positions +-27 rows: +-17 for the receptive field, +10 because rows next to a window
 // edge see zeros instead of their real neighbours and are wrong by up to 2 rows per conv layer (the stem reads the real
-// one-hot rows beyond the window). Rows [w0 + 10, w1 - 10) come from this computation (a window edge that is a
+// one-hot rows beyond the window). Rows [w0 + TW_EDGE, w1 - TW_EDGE) come from this computation (a window edge that is a
 // sequence end is exact), all other rows are copied from the parent's tower output (computed once per parent by
 // conv_tower_kernel). At L = 200, 128 steps, M = 10: 42 % of the row tiles, 21 % of the candidates need none at all.
 struct TowerWinArgs {
@@ -962,34 +1042,21 @@ __global__ __launch_bounds__(512, 4) void conv_tower_win_kernel(TowerWinArgs wa)
   const int cs = w & 3, rh = w >> 2;
   const int j = lane & 15, g = lane >> 4;
   const int L = a.L;
-  if (wa.count && (int)blockIdx.x >= __builtin_amdgcn_readfirstlane(*wa.count)) return;
-  const int cand = wa.live_idx ? __builtin_amdgcn_readfirstlane(wa.live_idx[blockIdx.x]) : (int)blockIdx.x;
-  const int w0 = __builtin_amdgcn_readfirstlane(wa.win[2 * cand]);
-  const int w1 = __builtin_amdgcn_readfirstlane(wa.win[2 * cand + 1]);
-  const int nt = (w1 - w0) >> 4;                        // live row tiles
+  TW_WIN_DECODE(wa, true, TW_CAND_SELECT)               // cand, w0, w1, nt = live row tiles
   const int lrows = min(L, w1) - w0;                    // valid local rows
-  const int keep_lo = nt == 0 ? 0 : (w0 == 0 ? 0 : w0 + 10);
-  const int keep_hi = nt == 0 ? 0 : (w1 >= L ? L : w1 - 10);
+  TW_WIN_KEEP(true, L)                                  // keep_lo, keep_hi
   float* outc = a.out + (size_t)blockIdx.x * L * TW_C;
   const float* par = wa.parent_out + (size_t)(cand / wa.M) * L * TW_C;
 
-  for (int e = tid; e < L * 16; e += 512) {             // rows that are the parent's, straight from its output
-    const int row = e >> 4;
-    if (row < keep_lo || row >= keep_hi)
-      *reinterpret_cast<float4*>(outc + (size_t)row * TW_C + 4 * (e & 15)) = *reinterpret_cast<const float4*>(par + (size_t)row * TW_C + 4 * (e & 15));
-  }
+  TW_COPY_PARENT_WIN(par)
   if (nt == 0) return;
 
   const float* xc = a.x + (size_t)cand * L * 4;
-  for (int e = tid - 8; e < TW_ROWS + 8; e += 512) {
-    const int gl = w0 + e;
-    float4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (gl >= 0 && gl < L) v = *reinterpret_cast<const float4*>(xc + (size_t)gl * 4);
-    *reinterpret_cast<float4*>(xs + 4 * e) = v;
-  }
+  TW_STAGE_WIN(xc, w0)
   for (int e = tid; e < (TW_ROWS + 2) * TW_AP; e += 512) smem[e] = 0.0f;     // rows beyond the window must read as zero
   const float* wsrc = a.tiles + (16 * cs + j) * CH + 8 * g;
-  float4 bn0 = *reinterpret_cast<const float4*>(wsrc), bn1 = *reinterpret_cast<const float4*>(wsrc + 4);
+  float4 bn0, bn1;
+  TW_WLOAD_ONE(bn0, bn1, wsrc)
 
   const int arow0 = 16 * rh + j;
   const int abase = ((16 * rh + j) * TW_AP + 8 * g) * 4;
@@ -1002,16 +1069,9 @@ __global__ __launch_bounds__(512, 4) void conv_tower_win_kernel(TowerWinArgs wa)
   f32x4 acc[7];
   __syncthreads();
 
-#define TW_WAIT(NOUT) __builtin_amdgcn_s_waitcnt(0xC07F | ((NOUT) << 8));
-#define TWW_MMA(AF, R0, CNT)                                                                                  \
-  _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                                             \
-    _Pragma("unroll") for (int r = 0; r < CNT; ++r) acc[R0 + r] = __builtin_amdgcn_mfma_f32_16x16x4f32(AF[r][q].x, bf[4 * q], acc[R0 + r], 0, 0, 0);     \
-    _Pragma("unroll") for (int r = 0; r < CNT; ++r) acc[R0 + r] = __builtin_amdgcn_mfma_f32_16x16x4f32(AF[r][q].y, bf[4 * q + 1], acc[R0 + r], 0, 0, 0); \
-    _Pragma("unroll") for (int r = 0; r < CNT; ++r) acc[R0 + r] = __builtin_amdgcn_mfma_f32_16x16x4f32(AF[r][q].z, bf[4 * q + 2], acc[R0 + r], 0, 0, 0); \
-    _Pragma("unroll") for (int r = 0; r < CNT; ++r) acc[R0 + r] = __builtin_amdgcn_mfma_f32_16x16x4f32(AF[r][q].w, bf[4 * q + 3], acc[R0 + r], 0, 0, 0); \
-  }
-#define TWW_GROUP3(AF, R0) { const int c_ = nlive - (R0); if (c_ >= 3) { TWW_MMA(AF, R0, 3) } else if (c_ == 2) { TWW_MMA(AF, R0, 2) } else if (c_ == 1) { TWW_MMA(AF, R0, 1) } }
-#define TWW_GROUP2(AF, R0) { const int c_ = nlive - (R0); if (c_ >= 2) { TWW_MMA(AF, R0, 2) } else if (c_ == 1) { TWW_MMA(AF, R0, 1) } }
+  // the live tiles of a group are a prefix of it: straight-line MFMAs for each count, no per-tile predicate
+#define TWW_GROUP3(AF, R0) { const int c_ = nlive - (R0); if (c_ >= 3) { TW_MM1(AF, R0, 3, true) } else if (c_ == 2) { TW_MM1(AF, R0, 2, true) } else if (c_ == 1) { TW_MM1(AF, R0, 1, true) } }
+#define TWW_GROUP2(AF, R0) { const int c_ = nlive - (R0); if (c_ >= 2) { TW_MM1(AF, R0, 2, true) } else if (c_ == 1) { TW_MM1(AF, R0, 1, true) } }
 
   for (int layer = -1; layer < a.nlayers; ++layer) {
     const float bl = a.bias[(layer + 1) * TW_C + 16 * cs + j];
@@ -1019,84 +1079,26 @@ __global__ __launch_bounds__(512, 4) void conv_tower_win_kernel(TowerWinArgs wa)
     for (int r = 0; r < 7; ++r) acc[r] = f32x4{bl, bl, bl, bl};
     const int niter = layer < 0 ? 2 : 10;
     for (int ci = 0; ci < niter; ++ci, ++it) {
-      const float bf[8] = {bn0.x, bn0.y, bn0.z, bn0.w, bn1.x, bn1.y, bn1.z, bn1.w};
-      if (it + 1 < nit) {
-        const float* src = wsrc + (size_t)(it + 1) * TW_C * CH;
-        bn0 = *reinterpret_cast<const float4*>(src);
-        bn1 = *reinterpret_cast<const float4*>(src + 4);
-      }
-      if (layer < 0) {
+      TW_UNPACK_ONE(bf, bn0, bn1)
+      TW_WNEXT_ONE(bn0, bn1)
+      float4 fa[3][2], fb[2][2];
+      if (layer < 0) {                                   // xs holds real rows beyond the window and zero rows outside the sequence
         const int t0 = 8 * ci + 2 * g;
-        float4 fa[3][2], fb[2][2];
-#define TWW_XLOAD(R, V)                                                                                       \
-        { const float* xp_ = xs + 4 * (arow0 + 32 * (R) + t0 - 7);                                            \
-          V[0] = *reinterpret_cast<const float4*>(xp_); V[1] = *reinterpret_cast<const float4*>(xp_ + 4); }
-        TWW_XLOAD(0, fa[0]) TWW_XLOAD(1, fa[1]) TWW_XLOAD(2, fa[2])
-        TWW_XLOAD(3, fb[0]) TWW_XLOAD(4, fb[1])
-        __builtin_amdgcn_sched_barrier(0);
-        TW_WAIT(4)
-        TWW_GROUP3(fa, 0)
-        __builtin_amdgcn_sched_barrier(0);
-        TWW_XLOAD(5, fa[0])
-        if (rh == 0) TWW_XLOAD(6, fa[1])
-        __builtin_amdgcn_sched_barrier(0);
-        if (rh == 1) { TW_WAIT(2) } else { TW_WAIT(4) }
-        TWW_GROUP2(fb, 3)
-        __builtin_amdgcn_sched_barrier(0);
-        TW_WAIT(0)
-        TWW_GROUP2(fa, 5)
-        __builtin_amdgcn_sched_barrier(0);
-#undef TWW_XLOAD
+#define TWW_XLD(R, V) if ((R) < 6 || rh == 0) { TW_XLOAD(V, 0, arow0 + 32 * (R) + t0 - 7) TW_XLOAD(V, 1, arow0 + 32 * (R) + t0 - 7 + 1) }
+        TW_SCHED322(TWW_XLD, TWW_GROUP3, TWW_GROUP2)
+#undef TWW_XLD
       } else {
-        const int c = ci / 5, delta = ci - 5 * c - 2;
-        const int dbytes = delta * (TW_AP * 4) + c * (CH * 4);
-        float4 fa[3][2], fb[2][2];
-#define TWW_ALOAD(R, V)                                                                                       \
-        { const int o_ = min(max(abase + dbytes + (R) * (32 * TW_AP * 4), a_lo + c * (CH * 4)), a_hi + c * (CH * 4)); \
-          const float4* ap_ = reinterpret_cast<const float4*>(actb + o_);                                     \
-          V[0] = ap_[0]; V[1] = ap_[1]; }
-        TWW_ALOAD(0, fa[0]) TWW_ALOAD(1, fa[1]) TWW_ALOAD(2, fa[2])
-        TWW_ALOAD(3, fb[0]) TWW_ALOAD(4, fb[1])
-        __builtin_amdgcn_sched_barrier(0);
-        TW_WAIT(4)
-        TWW_GROUP3(fa, 0)
-        __builtin_amdgcn_sched_barrier(0);
-        TWW_ALOAD(5, fa[0])
-        if (rh == 0) TWW_ALOAD(6, fa[1])
-        __builtin_amdgcn_sched_barrier(0);
-        if (rh == 1) { TW_WAIT(2) } else { TW_WAIT(4) }
-        TWW_GROUP2(fb, 3)
-        __builtin_amdgcn_sched_barrier(0);
-        TW_WAIT(0)
-        TWW_GROUP2(fa, 5)
-        __builtin_amdgcn_sched_barrier(0);
-#undef TWW_ALOAD
+        TW_TAP(ci)
+#define TWW_ALD(R, V) if ((R) < 6 || rh == 0) TW_ALOAD_CLAMPED(V, abase + dbytes + (R) * (32 * TW_AP * 4))
+        TW_SCHED322(TWW_ALD, TWW_GROUP3, TWW_GROUP2)
+#undef TWW_ALD
       }
     }
-    if (layer >= 0) __syncthreads();
-    const bool res = layer >= 0 && ((a.residual_mask >> layer) & 1);
-#pragma unroll
-    for (int r = 0; r < 7; ++r) {
-      if (r >= nlive) continue;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int row = 16 * (rh + 2 * r) + 4 * g + e;
-        const int o = row * TW_AP + 16 * cs + j;
-        const float v = acc[r][e] + (res ? act[o] : 0.0f);
-        act[o] = row < lrows ? fmaxf(v, 0.0f) : 0.0f;
-      }
-    }
-    __syncthreads();
+    TW_EPILOGUE1(r < nlive, lrows)
   }
 #undef TWW_GROUP2
 #undef TWW_GROUP3
-#undef TWW_MMA
-#undef TW_WAIT
-  for (int e = tid; e < L * 16; e += 512) {
-    const int row = e >> 4, q = e & 15;
-    if (row >= keep_lo && row < keep_hi)
-      *reinterpret_cast<float4*>(outc + (size_t)row * TW_C + 4 * q) = *reinterpret_cast<const float4*>(act + (row - w0) * TW_AP + 4 * q);
-  }
+  TW_STORE_WIN
 }
 
 // ----------------------------------------------------- conv tower, second generation (whole sequences AND windows) ----
@@ -1131,20 +1133,16 @@ __device__ __forceinline__ void tower2_layers(const TowerCtx2& c) {
   const char* actb = reinterpret_cast<const char*>(c.act);
   const int cb = 16 * CT * c.cp + 4 * g;                         // this lane's OUTPUT channels: cb + 16 ct + e (transposed tiles)
   const int nit = 2 + 10 * c.nlayers;
+  const float* wsrc = c.wsrc;
+  const float* xs = c.xs;
   float4 bn[2 * CT];                                             // [ct][half]: W[ch0 + 16 ct][8 g .. 8 g + 8] of the next tile
-#pragma unroll
-  for (int ct = 0; ct < CT; ++ct) {
-    bn[2 * ct] = *reinterpret_cast<const float4*>(c.wsrc + ct * 16 * CH);
-    bn[2 * ct + 1] = *reinterpret_cast<const float4*>(c.wsrc + ct * 16 * CH + 4);
-  }
+  TW_WLOAD(bn, wsrc, CT)
   int it = 0;
   f32x4 acc[NA][CT];
 
   for (int layer = -1; layer < c.nlayers; ++layer) {
-    // TRANSPOSED accumulators (round 4d, as in the 16-bit twin): the weight fragment is the A operand, the activation fragment
-    // the B operand — the same registers either way and the same products in the same order — so lane (j, g) register e of
-    // column tile ct holds channel cb + 16 ct + e, cb = 16 CT cp + 4 g, of ONE position (row 16 (rq + RS r) + j): the
-    // epilogue is one 16-byte LDS load and store per (row tile, column tile) instead of four 4-byte ones
+    // TRANSPOSED accumulators (as in the 16-bit twin): lane (j, g) register e of column tile ct holds channel cb + 16 ct + e of
+    // ONE position (row 16 (rq + RS r) + j): the epilogue is one 16-byte LDS load and store per (row tile, column tile)
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
       const f32x4 bl = *reinterpret_cast<const f32x4*>(c.bias + (layer + 1) * TW_C + cb + 16 * ct);
@@ -1153,23 +1151,11 @@ __device__ __forceinline__ void tower2_layers(const TowerCtx2& c) {
     }
     const int niter = layer < 0 ? 2 : 10;
     for (int ci = 0; ci < niter; ++ci, ++it) {
-      float b[CT][8];
-#pragma unroll
-      for (int ct = 0; ct < CT; ++ct) {
-        b[ct][0] = bn[2 * ct].x; b[ct][1] = bn[2 * ct].y; b[ct][2] = bn[2 * ct].z; b[ct][3] = bn[2 * ct].w;
-        b[ct][4] = bn[2 * ct + 1].x; b[ct][5] = bn[2 * ct + 1].y; b[ct][6] = bn[2 * ct + 1].z; b[ct][7] = bn[2 * ct + 1].w;
-      }
-      if (it + 1 < nit) {
-        const float* src = c.wsrc + (size_t)(it + 1) * TW_C * CH;
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) {
-          bn[2 * ct] = *reinterpret_cast<const float4*>(src + ct * 16 * CH);
-          bn[2 * ct + 1] = *reinterpret_cast<const float4*>(src + ct * 16 * CH + 4);
-        }
-      }
+      TW_UNPACK(b, bn, CT)
+      TW_WNEXT(bn, CT)
       float4 af[NA][2];
       if (layer < 0) {
-        const int t0 = 8 * ci + 2 * g;                           // k = 32 ci + 8 g + s: taps t0, t0 + 1 (4 channels each)
+        const int t0 = 8 * ci + 2 * g;
 #pragma unroll
         for (int r = 0; r < NL; ++r)
 #pragma unroll
@@ -1178,37 +1164,23 @@ __device__ __forceinline__ void tower2_layers(const TowerCtx2& c) {
             int idx;
             if (CLAMP) idx = rr;                                 // xs holds zero rows outside the sequence / window
             else idx = (unsigned)(c.apos[r] + t0 + q - 7) < (unsigned)L ? rr : TW_ROWS + 7;
-            af[r][q] = *reinterpret_cast<const float4*>(c.xs + 4 * idx);
+            TW_XLOAD(af[r], q, idx)
           }
       } else {
-        const int chk = ci / 5, delta = ci - 5 * chk - 2;
-        const int dbytes = delta * (TW_AP * 4) + chk * (CH * 4);
+        TW_TAP(ci)
 #pragma unroll
         for (int r = 0; r < NL; ++r) {
-          int o;
-          if (CLAMP) o = min(max(abase + dbytes + r * (16 * RS * TW_AP * 4), a_lo + chk * (CH * 4)), a_hi + chk * (CH * 4));
-          else o = (unsigned)(c.apos[r] + delta) < (unsigned)L ? abase + dbytes + r * (16 * RS * TW_AP * 4) : a_hi + chk * (CH * 4);
-          const float4* ap = reinterpret_cast<const float4*>(actb + o);
-          af[r][0] = ap[0]; af[r][1] = ap[1];
+          if (CLAMP) { TW_ALOAD_CLAMPED(af[r], abase + dbytes + r * (16 * RS * TW_AP * 4)) }
+          else { TW_ALOAD_APOS(af[r], c.apos[r], abase + dbytes + r * (16 * RS * TW_AP * 4)) }
         }
       }
-#pragma unroll
-      for (int r = 0; r < NL; ++r)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const float av[4] = {af[r][q].x, af[r][q].y, af[r][q].z, af[r][q].w};
-#pragma unroll
-          for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-              acc[r][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[ct][4 * q + s4], av[s4], acc[r][ct], 0, 0, 0);
-        }
+      TW_MM2(NL, CT)
     }
     if (layer >= 0) __syncthreads();                     // every wave is done reading the image (the stem reads xs)
     const bool res = layer >= 0 && ((c.residual_mask >> layer) & 1);
 #pragma unroll
     for (int r = 0; r < NL; ++r) {
-      const int row = 16 * (c.rq + RS * r) + j;          // C/D layout, transposed: reg e -> channel cb + 16 ct + e at position j
+      const int row = 16 * (c.rq + RS * r) + j;
 #pragma unroll
       for (int ct = 0; ct < CT; ++ct) {
         f32x4* dst = reinterpret_cast<f32x4*>(c.act + row * TW_AP + cb + 16 * ct);
@@ -1255,39 +1227,22 @@ __global__ __launch_bounds__(512, 4) void conv_tower2_kernel(TowerWinArgs wa) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int L = a.L;
-  int cand = blockIdx.x, w0 = 0, w1 = 0;
-  if (WIN) {
-    if (wa.count && (int)blockIdx.x >= __builtin_amdgcn_readfirstlane(*wa.count)) return;
-    if (wa.live_idx) cand = __builtin_amdgcn_readfirstlane(wa.live_idx[blockIdx.x]);
-    w0 = __builtin_amdgcn_readfirstlane(wa.win[2 * cand]);
-    w1 = __builtin_amdgcn_readfirstlane(wa.win[2 * cand + 1]);
-  }
-  const int nt = (w1 - w0) >> 4;
+  TW_WIN_DECODE(wa, WIN, TW_CAND_BRANCH)                // cand, w0, w1, nt
   const int tile_rows = WIN ? min(L, w1) - w0 : a.spt * L;
   const int64_t row0 = WIN ? 0 : (int64_t)blockIdx.x * tile_rows;
   const int64_t total_rows = (int64_t)((!WIN && a.count) ? __builtin_amdgcn_readfirstlane(*a.count) : a.n) * L;
   if (!WIN && row0 >= total_rows) return;
-  const int keep_lo = !WIN ? 0 : (nt == 0 ? 0 : (w0 == 0 ? 0 : w0 + 10));
-  const int keep_hi = !WIN ? 0 : (nt == 0 ? 0 : (w1 >= L ? L : w1 - 10));
+  TW_WIN_KEEP(WIN, L)                                   // keep_lo, keep_hi
   float* outc = a.out + (WIN ? (size_t)blockIdx.x * L * TW_C : 0);
 
   if (WIN) {
     const float* par = wa.parent_out + (size_t)(cand / wa.M) * L * TW_C;
-    for (int e = tid; e < L * 16; e += 512) {           // rows that are the parent's, straight from its output
-      const int row = e >> 4;
-      if (row < keep_lo || row >= keep_hi)
-        *reinterpret_cast<float4*>(outc + (size_t)row * TW_C + 4 * (e & 15)) = *reinterpret_cast<const float4*>(par + (size_t)row * TW_C + 4 * (e & 15));
-    }
+    TW_COPY_PARENT_WIN(par)
     if (nt == 0) return;
   }
   {
     const float* xc = a.x + (WIN ? (size_t)cand * L * 4 : 0);
-    for (int e = tid - 8; e < TW_ROWS + 8; e += 512) {
-      float4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-      if (WIN) { const int gl = w0 + e; if (gl >= 0 && gl < L) v = *reinterpret_cast<const float4*>(xc + (size_t)gl * 4); }
-      else if (e >= 0 && e < tile_rows && row0 + e < total_rows) v = *reinterpret_cast<const float4*>(xc + (row0 + e) * 4);
-      *reinterpret_cast<float4*>(xs + 4 * e) = v;
-    }
+    if (WIN) { TW_STAGE_WIN(xc, w0) } else { TW_STAGE_SEQ(xc, 8) }
   }
   for (int e = tid; e < (TW_ROWS + 2) * TW_AP; e += 512) smem[e] = 0.0f;      // image incl. the zero rows
 
@@ -1305,19 +1260,7 @@ __global__ __launch_bounds__(512, 4) void conv_tower2_kernel(TowerWinArgs wa) {
   const int nlive = ((WIN ? nt : TW_ROWS / 16) - c.rq + RS - 1) / RS;
   __syncthreads();
   tower2_dispatch<SPT1 || WIN, WIN, CT>(c, nlive);
-  if (WIN) {
-    for (int e = tid; e < L * 16; e += 512) {
-      const int row = e >> 4, q = e & 15;
-      if (row >= keep_lo && row < keep_hi)
-        *reinterpret_cast<float4*>(outc + (size_t)row * TW_C + 4 * q) = *reinterpret_cast<const float4*>(act + (row - w0) * TW_AP + 4 * q);
-    }
-  } else {
-    for (int e = tid; e < tile_rows * 16; e += 512) {
-      const int row = e >> 4, q = e & 15;
-      if (row0 + row < total_rows)
-        *reinterpret_cast<float4*>(a.out + (row0 + row) * TW_C + 4 * q) = *reinterpret_cast<const float4*>(act + row * TW_AP + 4 * q);
-    }
-  }
+  if (WIN) { TW_STORE_WIN } else { TW_STORE_SEQ }
 }
 
 // (w0, w1) of every candidate: one wave per candidate compares it with its parent. TIGHT (svdd_candidate_windows_tight): the window
@@ -1365,7 +1308,7 @@ __global__ __launch_bounds__(256) void candidate_windows_kernel(const uint8_t* _
 // parts' computed tiles disjoint on every layer. A kept row is the same chain of MFMAs on the same inputs as in the whole-sequence
 // kernel, whichever tile and lane it sits in: same bits (tests/test_tower_parts_gpu.py).
 constexpr int TP_PARTS = 3;        // parts per candidate
-constexpr int TP_BLOCKS = 5;       // conv blocks after the stem: the tower the part rule is written for
+// TP_BLOCKS = 5 conv blocks after the stem, the tower the part rule is written for: svdd_device.h
 constexpr int TP_REACH = 17;       // receptive field of that tower, rows per side: the reach svdd_conv_tower_parts_f32 takes
 constexpr int TP_LT = 16;          // stride of a layer's tile-origin list in LDS: <= TW_RT origins, [TP_LT - 1] = their number
 
@@ -1430,19 +1373,18 @@ struct TowerPartArgs {
 };
 
 // One layer (layer = -1: the stem) on this wave's NL tiles: the origins tl[rq], tl[rq + 2], ... of the layer's list. The image is
-// addressed by SEQUENCE row (row r at act + r TW_AP). Same weight stream, same products in the same order as tower2_layers<true, NL, 1>.
+// addressed by SEQUENCE row (row r at act + r TW_AP). The layer is tower2_layers<true, NL, 1>'s, out of the same pieces (TW_UNPACK1 /
+// TW_WLOAD1, TW_TAP, TW_ALOAD_CLAMPED, TW_XLOAD, TW_MM2), but its own text: as one body with tower2_layers this kernel's instructions change.
 template <int NL>
 __device__ __forceinline__ void tower_parts_layer(const TowerCtx2& c, int layer, const int* tl, float4 (&bn)[2], int& it) {
   constexpr int NA = NL > 0 ? NL : 1;
   const int niter = layer < 0 ? 2 : 10;
   const int nit = 2 + 10 * c.nlayers;
+  const float* wsrc = c.wsrc;
+  const float* xs = c.xs;
   if constexpr (NL == 0) {                                       // no tile on this layer: keep the weight stream and the barriers in step
     it += niter;
-    if (it < nit) {
-      const float* src = c.wsrc + (size_t)it * TW_C * CH;
-      bn[0] = *reinterpret_cast<const float4*>(src);
-      bn[1] = *reinterpret_cast<const float4*>(src + 4);
-    }
+    if (it < nit) TW_WLOAD_ONE(bn[0], bn[1], wsrc + (size_t)it * TW_C * CH)
     if (layer >= 0) __syncthreads();
     __syncthreads();
     return;
@@ -1456,19 +1398,15 @@ __device__ __forceinline__ void tower_parts_layer(const TowerCtx2& c, int layer,
   const int a_hi = (TW_ROWS * TW_AP + 8 * g) * 4;                // row TW_ROWS
   const char* actb = reinterpret_cast<const char*>(c.act);
   const int cb = 16 * c.cp + 4 * g;                              // this lane's OUTPUT channels cb + e (transposed tiles)
-  f32x4 acc[NA];
+  f32x4 acc[NA][1];
   {
     const f32x4 bl = *reinterpret_cast<const f32x4*>(c.bias + (layer + 1) * TW_C + cb);
 #pragma unroll
-    for (int r = 0; r < NL; ++r) acc[r] = bl;
+    for (int r = 0; r < NL; ++r) acc[r][0] = bl;
   }
   for (int ci = 0; ci < niter; ++ci, ++it) {
-    const float b[8] = {bn[0].x, bn[0].y, bn[0].z, bn[0].w, bn[1].x, bn[1].y, bn[1].z, bn[1].w};
-    if (it + 1 < nit) {
-      const float* src = c.wsrc + (size_t)(it + 1) * TW_C * CH;
-      bn[0] = *reinterpret_cast<const float4*>(src);
-      bn[1] = *reinterpret_cast<const float4*>(src + 4);
-    }
+    TW_UNPACK_ONE(b, bn[0], bn[1])
+    TW_WNEXT_ONE(bn[0], bn[1])
     float4 af[NA][2];
     int og[NA];                                                  // the origins, opaque per iteration: the lane's addresses are summed
 #pragma unroll                                                   // here, one at a time — hoisted out of the loop they would hold 7 VGPRs
@@ -1479,25 +1417,15 @@ __device__ __forceinline__ void tower_parts_layer(const TowerCtx2& c, int layer,
       for (int r = 0; r < NL; ++r)
 #pragma unroll
         for (int q = 0; q < 2; ++q)                              // xs holds zero rows outside the sequence, up to row TW_ROWS + 7
-          af[r][q] = *reinterpret_cast<const float4*>(c.xs + 4 * min(og[r] + j + t0 + q - 7, TW_ROWS + 7));
+          { TW_XLOAD(af[r], q, min(og[r] + j + t0 + q - 7, TW_ROWS + 7)) }
     } else {
-      const int chk = ci / 5, delta = ci - 5 * chk - 2;
-      const int dbytes = delta * (TW_AP * 4) + chk * (CH * 4);
+      TW_TAP(ci)
 #pragma unroll
       for (int r = 0; r < NL; ++r) {                             // rows before 0 read the zero row -1, rows past TW_ROWS the zero row TW_ROWS
-        const int o = min(max(lbase + dbytes + og[r] * (TW_AP * 4), a_lo + chk * (CH * 4)), a_hi + chk * (CH * 4));
-        const float4* ap = reinterpret_cast<const float4*>(actb + o);
-        af[r][0] = ap[0]; af[r][1] = ap[1];
+        TW_ALOAD_CLAMPED(af[r], lbase + dbytes + og[r] * (TW_AP * 4))
       }
     }
-#pragma unroll
-    for (int r = 0; r < NL; ++r)
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const float av[4] = {af[r][q].x, af[r][q].y, af[r][q].z, af[r][q].w};
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) acc[r] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[4 * q + s4], av[s4], acc[r], 0, 0, 0);
-      }
+    TW_MM2(NL, 1)
   }
   if (layer >= 0) __syncthreads();                               // every wave is done reading the image (the stem reads xs)
   const bool res = layer >= 0 && ((c.residual_mask >> layer) & 1);
@@ -1507,7 +1435,7 @@ __device__ __forceinline__ void tower_parts_layer(const TowerCtx2& c, int layer,
     if (row < c.L) {                                             // rows from L on are never written: they stay the zeros the taps past the end read
       f32x4* dst = reinterpret_cast<f32x4*>(c.act + row * TW_AP + cb);
       const f32x4 z = {0.0f, 0.0f, 0.0f, 0.0f};
-      const f32x4 v = acc[r] + (res ? *dst : z);
+      const f32x4 v = acc[r][0] + (res ? *dst : z);
       *dst = __builtin_elementwise_max(v, z);
     }
   }
@@ -1550,11 +1478,7 @@ __global__ __launch_bounds__(512, 4) void conv_tower_parts_kernel(TowerPartArgs 
   }
   {
     const float* xc = a.x + (size_t)cand * L * 4;
-    for (int e = tid - 8; e < TW_ROWS + 8; e += 512) {
-      float4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-      if (e >= 0 && e < L) v = *reinterpret_cast<const float4*>(xc + (size_t)e * 4);
-      *reinterpret_cast<float4*>(xs + 4 * e) = v;
-    }
+    TW_STAGE_WIN(xc, 0)                                 // the image is the whole sequence
   }
   // Zero only the image rows that are read: a block reads two rows around its tiles, so per part everything any layer reads lies
   // in [s - 2, e + 18), s / e = the stem's needed range (the tiles of a layer pass its needed end by at most 15 rows) — the rows
@@ -1585,7 +1509,8 @@ __global__ __launch_bounds__(512, 4) void conv_tower_parts_kernel(TowerPartArgs 
   c.cp = w & 3; c.rq = w >> 2; c.j = lane & 15; c.g = lane >> 4;
   c.wsrc = a.tiles + (16 * c.cp + c.j) * CH + 8 * c.g;
   __syncthreads();
-  float4 bn[2] = {*reinterpret_cast<const float4*>(c.wsrc), *reinterpret_cast<const float4*>(c.wsrc + 4)};
+  float4 bn[2];
+  TW_WLOAD_ONE(bn[0], bn[1], c.wsrc)
   int it = 0;
   for (int layer = -1; layer < nl; ++layer) {
     const int* tlk = tl[layer + 1];
@@ -1713,10 +1638,9 @@ struct BackboneSave {
 // ---- backbone_kernel's and backbone_grad_kernel's entry: the gradient pass walks the forward's work split with the forward's text.
 #define B2_ALOAD(R, V, DELTA, COFF, DBYTES)                                                                  \
       BB_ALOAD_CLAMPED(V, arow0 + (DBYTES) + (R) * (32 * BB_AP * 4), a_lo + (COFF), a_hi + (COFF))
-#define B2_WAIT(NOUT) __builtin_amdgcn_s_waitcnt(0xC07F | ((NOUT) << 8));
 #define B2_MM(R, U, NOUT)                                                                                    \
       __builtin_amdgcn_sched_barrier(0);                                                                     \
-      B2_WAIT(NOUT)                                                                                          \
+      LGKM_WAIT(NOUT)                                                                                        \
       BB_MM16(acc[R], U, live & (1 << (2 * (R))))                                                            \
       __builtin_amdgcn_sched_barrier(0);
 // entry parameters from a schedule word
@@ -3641,7 +3565,7 @@ extern "C" int svdd_conv_tower_windows_f32(const float* onehot, const float* til
                                            const float* parent_out, float* out, int n, int L, int M, int nlayers,
                                            int residual_mask, const int32_t* live_idx, const int32_t* count, void* stream) {
   if (!onehot || !tiles || !bias || !win || !parent_out || !out || n <= 0 || M <= 0 || (n % M && !live_idx) || L <= TW_ROWS / 2 ||
-      L > TW_ROWS || nlayers != 5)
+      L > TW_ROWS || nlayers != TP_BLOCKS)
     return SVDD_E_ARG;                                   // one sequence per tile; margins below assume the 5-layer tower
   // (with an index list, n is only the number of list entries this launch may take: a launch over PART of a compacted list)
   TowerWinArgs wa{TowerArgs{onehot, tiles, bias, out, n, L, 1, nlayers, residual_mask, nullptr}, win, parent_out, M, live_idx, count};

@@ -108,22 +108,22 @@ TOWER2 = {
     "bench": ["python", "tools/tower_ab.py", "1", "3"],
     "variants": {
         "baseline": [],
-        "nocopy": [("      if (row < keep_lo || row >= keep_hi)\n        *reinterpret_cast<float4*>(outc + (size_t)row * TW_C + 4 * (e & 15)) = *reinterpret_cast<const float4*>(par + (size_t)row * TW_C + 4 * (e & 15));",
-                    "      if ((row < keep_lo || row >= keep_hi) && a.n == 12345)\n        *reinterpret_cast<float4*>(outc + (size_t)row * TW_C + 4 * (e & 15)) = *reinterpret_cast<const float4*>(par + (size_t)row * TW_C + 4 * (e & 15));")],
-        "noB": [("      if (it + 1 < nit) {\n        const float* src = c.wsrc + (size_t)(it + 1) * TW_C * CH;",
-                 "      if (it + 1 < nit && c.L == 12345) {\n        const float* src = c.wsrc + (size_t)(it + 1) * TW_C * CH;")],
-        "nomfma": [("              acc[r][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s4], b[ct][4 * q + s4], acc[r][ct], 0, 0, 0);",
-                    "              acc[r][ct][s4] += av[s4] * b[ct][4 * q + s4];")],
+        # the tower family's shared pieces are macros at file scope: a patch there reaches every kernel that uses the piece
+        "nocopy": [("    if (row < keep_lo || row >= keep_hi)                                                                      \\\n",
+                    "    if ((row < keep_lo || row >= keep_hi) && a.n == 12345)                                                    \\\n")],
+        "noB": [("#define TW_WNEXT(BN, CT) if (it + 1 < nit) TW_WLOAD(", "#define TW_WNEXT(BN, CT) if (it + 1 < nit && nit == 12345) TW_WLOAD(")],
+        "nomfma": [("          acc[r][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[ct][4 * q + s4], av[s4], acc[r][ct], 0, 0, 0);",
+                    "          acc[r][ct][s4] += av[s4] * b[ct][4 * q + s4];")],
         "nozero": [("  for (int e = tid; e < (TW_ROWS + 2) * TW_AP; e += 512) smem[e] = 0.0f;      // image incl. the zero rows",
                     "  for (int e = tid; e < (TW_ROWS + 2) * TW_AP && a.n == 12345; e += 512) smem[e] = 0.0f;")],
-        "nowriteback": [("      if (row >= keep_lo && row < keep_hi)\n        *reinterpret_cast<float4*>(outc + (size_t)row * TW_C + 4 * q) = *reinterpret_cast<const float4*>(act + (row - w0) * TW_AP + 4 * q);",
-                         "      if (row >= keep_lo && row < keep_hi && a.n == 12345)\n        *reinterpret_cast<float4*>(outc + (size_t)row * TW_C + 4 * q) = *reinterpret_cast<const float4*>(act + (row - w0) * TW_AP + 4 * q);")],
+        "nowriteback": [("    if (row >= keep_lo && row < keep_hi)                                                                      \\\n",
+                         "    if (row >= keep_lo && row < keep_hi && a.n == 12345)                                                      \\\n")],
     },
 }
-TOWER2["variants"]["nomfma0"] = [("              acc[r][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s4], b[ct][4 * q + s4], acc[r][ct], 0, 0, 0);",
-                                  "              if (c.L == 12345) acc[r][ct][s4] += av[s4] * b[ct][4 * q + s4];")]
-TOWER2["variants"]["noA"] = [("          const float4* ap = reinterpret_cast<const float4*>(actb + o);\n          af[r][0] = ap[0]; af[r][1] = ap[1];",
-                              "          af[r][0] = bn[0]; af[r][1] = bn[1]; (void)o;")]
+TOWER2["variants"]["nomfma0"] = [("          acc[r][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[ct][4 * q + s4], av[s4], acc[r][ct], 0, 0, 0);",
+                                  "          if (c.L == 12345) acc[r][ct][s4] += av[s4] * b[ct][4 * q + s4];")]
+TOWER2["variants"]["noA"] = [("  { const float4* ap_ = reinterpret_cast<const float4*>(actb + (OFF)); V[0] = ap_[0]; V[1] = ap_[1]; }",
+                              "  { const float4* ap_ = reinterpret_cast<const float4*>(actb + (OFF)); V[0] = V[1] = make_float4((float)delta, (float)chk, 0.0f, 0.0f); (void)ap_; }")]
 TOWER2["variants"]["noepi"] = [("          c.act[o] = row < c.tile_rows ? fmaxf(v, 0.0f) : 0.0f;", "          if (v == 12345.0f) c.act[o] = row < c.tile_rows ? fmaxf(v, 0.0f) : 0.0f;")]
 TOWER2["variants"]["nolayers"] = [("  tower2_dispatch<SPT1 || WIN, WIN, CT>(c, nlive);", "  if (a.n == 12345) tower2_dispatch<SPT1 || WIN, WIN, CT>(c, nlive);")]
 TOWER2["variants"]["nomfma0_noA_noB"] = TOWER2["variants"]["nomfma0"] + TOWER2["variants"]["noA"] + TOWER2["variants"]["noB"]
@@ -270,8 +270,8 @@ _F["timing_nobranch"] = _F["timing"] + [("      if (live & (1 << (2 * (R)))) {  
                                           "      {                                                                         \\\n        _Pragma(\"unroll\") for (int q = 0; q < 2; ++q) {                                                      \\\n          acc[R][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(U[q].x, bf0[4 * q], acc[R][0], 0, 0, 0);          \\")]
 _FSTAMP = "if (dbg_on) { const unsigned long long t_ = __builtin_readcyclecounter(); if (lane == 0 && cnt < 62) g_lpt_dbg[8192 + (blockIdx.x * 8 + w) * 64 + cnt] = t_; ++cnt; }"
 _F["stamps"] = [_F["timing"][0], _F["timing"][-1],
-    ("#define B2_MM(R, U, NOUT)                                                                                    \\\n      __builtin_amdgcn_sched_barrier(0);                                                                     \\\n      B2_WAIT(NOUT)                                                                                          \\\n",
-     "#define B2_MM(R, U, NOUT)                                                                                    \\\n      __builtin_amdgcn_sched_barrier(0);                                                                     \\\n      B2_WAIT(NOUT)                                                                                          \\\n      " + _FSTAMP + " \\\n"),
+    ("#define B2_MM(R, U, NOUT)                                                                                    \\\n      __builtin_amdgcn_sched_barrier(0);                                                                     \\\n      LGKM_WAIT(NOUT)                                                                                        \\\n",
+     "#define B2_MM(R, U, NOUT)                                                                                    \\\n      __builtin_amdgcn_sched_barrier(0);                                                                     \\\n      LGKM_WAIT(NOUT)                                                                                        \\\n      " + _FSTAMP + " \\\n"),
     ("    float4 ua[2], ub[2];\n    if (it < layer_end) {\n      B2_PARAMS(en, delta0, coff0, dbytes0)", "    const bool dbg_on = blockIdx.x < 2 && layer == 2;\n    int cnt = 0;\n    float4 ua[2], ub[2];\n    if (it < layer_end) {\n      B2_PARAMS(en, delta0, coff0, dbytes0)")]
 _F["stamps_solo0"] = _F["stamps"] + _F["timing_solo0"][-1:]
 _F["timing_solo0_noX"] = _F["timing_solo0"] + [("        V[0] = ap_[0]; V[1] = ap_[1]; }\n#define B2_WAIT", "        if (a.n == 12345) { V[0] = ap_[0]; V[1] = ap_[1]; } }\n#define B2_WAIT")]
@@ -294,8 +294,8 @@ TOWER_LP_TIMING = {
          "    __syncthreads();                                             // the image is complete\n    " + _TT % 3 + "\n  }\n  if ((threadIdx.x & 63) == 0) for (int k = 1; k < 4; ++k) g_tw_dbg[(blockIdx.x * 8 + (threadIdx.x >> 6)) * 8 + k] = tacc[k];\n}"),
         ("  const int nlive = WIN ? (nt - c.rq + 3) >> 2 : (c.rq == 0 ? 4 : 3);    // owned live tiles rq + 4 r, r < nlive\n  __syncthreads();",
          "  const int nlive = WIN ? (nt - c.rq + 3) >> 2 : (c.rq == 0 ? 4 : 3);    // owned live tiles rq + 4 r, r < nlive\n  __syncthreads();\n  const unsigned long long tp1 = __builtin_readcyclecounter();\n  if (lane == 0) g_tw_dbg[(blockIdx.x * 8 + w) * 8 + 0] = tp1 - tp0;"),
-        ("  const int tid = threadIdx.x, lane = tid & 63;\n  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);\n  const int L = a.L;\n\n  int cand = blockIdx.x;",
-         "  const unsigned long long tp0 = __builtin_readcyclecounter();\n  const int tid = threadIdx.x, lane = tid & 63;\n  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);\n  const int L = a.L;\n\n  int cand = blockIdx.x;"),
+        ("  const int tid = threadIdx.x, lane = tid & 63;\n  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);\n  const int L = a.L;\n\n  TW_WIN_DECODE(a, WIN, ",
+         "  const unsigned long long tp0 = __builtin_readcyclecounter();\n  const int tid = threadIdx.x, lane = tid & 63;\n  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);\n  const int L = a.L;\n\n  TW_WIN_DECODE(a, WIN, "),
         ("  // the last image IS the output: rows [hi 128 B | lo 128 B], 16 bytes per thread\n  if (WIN) {",
          "  const unsigned long long tp2 = __builtin_readcyclecounter();\n  // the last image IS the output: rows [hi 128 B | lo 128 B], 16 bytes per thread\n  if (WIN) {"),
         ("        outc[(row0 + row) * ROW16 + q] = *reinterpret_cast<const uint4*>(plane + (q >> 3) * TPLANE_B + row * TLSB + 16 * (q & 7));\n    }\n  }\n}",
