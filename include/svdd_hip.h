@@ -355,6 +355,28 @@ int svdd_hamming_nn(const uint32_t* q, const uint32_t* db, int B, int N, int L, 
                     uint64_t* nn_key, int64_t* hist, void* on_stream);
 
 /*
+ * Edit-distance nearest neighbour (added under ABI 17: one new entry, nothing existing changed; not in the reference). A design
+ * that is a training row shifted by a few bases is a copy, and its Hamming distance is that of an unrelated row.
+ *
+ * svdd_edit_nn: q [B, ceil(Lq / 16)] and db [N, ceil(Ld / 16)] packed u32 (svdd_pack_tokens; the padding bits are never read).
+ *   Lq and Ld may differ, both 1 .. 1024. For every pair (i, j), d = the Levenshtein distance of the two rows: substitution,
+ *   insertion and deletion cost 1 each, global (no free ends). cap = 0 .. max(Lq, Ld); a pair with d > cap is "beyond".
+ *   exclude_diag, q_base and db_base as for svdd_hamming_nn. nn_key [B] u64 or NULL, started by the caller at all ones or at any
+ *   earlier key: every pair with d <= cap does nn_key[i] = min(nn_key[i], (uint64(d) << 32) | uint32(db_base + j)) (the lowest
+ *   database index among ties); pairs beyond never touch it, so an untouched key means "no neighbour within cap". hist [cap + 2]
+ *   i64 or NULL, ACCUMULATED INTO: the pairs at each distance 0 .. cap, and in bin cap + 1 all pairs beyond. Exact integers,
+ *   independent of the launch shape and of how queries and database are cut into calls. With hist NULL the kernel skips, or
+ *   leaves part-way, a pair that cannot lower the key it read for that query (so a caller may seed nn_key with a cheap upper
+ *   bound); the result is the same. With hist every pair lands in its exact bin. A thread keeps one query as four bit planes of
+ *   ceil(Lq / 32) <= 32 words and runs Myers' bit-vector recurrence (Hyyro's edit-distance form) on them as one multi-word
+ *   integer, one step per database token; a workgroup of 256 queries walks a segment of at most 2^22 database rows in tiles
+ *   staged in LDS and counts into u32 bins in LDS. SVDD_E_ARG: B, N, Lq or Ld <= 0, Lq or Ld > 1024, cap outside 0 .. max(Lq, Ld),
+ *   a negative base, db_base + N or q_base + B >= 2^31, a NULL q or db, neither output.
+ */
+int svdd_edit_nn(const uint32_t* q, const uint32_t* db, int B, int N, int Lq, int Ld, int cap, int q_base, int db_base,
+                 int exclude_diag, uint64_t* nn_key, int64_t* hist, void* on_stream);
+
+/*
  * PWM motif scanning (added under ABI 17: one new entry, nothing existing changed; not in the reference). Integer log-odds tables,
  * int32 sums and integer atomics only: every result is exact and independent of the launch shape and of how the caller cuts its
  * rows into chunks. The stream is explicit (as svdd_kmer_counts).

@@ -65,6 +65,11 @@ def build_parser(method="mc"):
                         "JASPAR and HOCOMOCO are distributed) and report the Spearman correlation of their motif frequencies with "
                         "each reference set's, the mean number of hits per design and the number of reachable motifs: printed, and "
                         "saved as npz keys quality_<metric>")
+    p.add_argument("--eval_edit", type=int, default=argparse.SUPPRESS, metavar="K",      # absent unless given, as --eval_quality
+                   help="with --eval_quality FILE.npz: also report the near copies by edit distance (substitutions, insertions and "
+                        "deletions), which the Hamming novelty cannot see: the share of designs with another design, and with a row "
+                        "of `train`, within K edits, the smallest such distance, and the share the Hamming report misses: printed, "
+                        "and saved as npz keys quality_<metric>")
     p.add_argument("--guide_motifs", default=argparse.SUPPRESS, metavar="FILE.meme",     # the three --guide_* flags: absent unless given
                    help="--method tweedie only: decode towards (or away from) the motifs of FILE.meme, the reward net's score plus "
                         "a motif term (svdd_amd.motifs.MotifReward); give --guide_weights, --guide_margin or both")
@@ -85,6 +90,14 @@ def _guidance_scale(args):
 
 
 _MOTIFS_NEED_SETS = "--eval_motifs needs --eval_quality FILE.npz: the reference sets its correlations are taken against"
+_EDIT_NEEDS_SETS = "--eval_edit needs --eval_quality FILE.npz: the training set its near copies are looked for in"
+
+
+def _eval_error(args):
+    """What is wrong with the --eval_* flags of args, or None."""
+    if getattr(args, "eval_quality", None):
+        return None
+    return _MOTIFS_NEED_SETS if hasattr(args, "eval_motifs") else _EDIT_NEEDS_SETS if hasattr(args, "eval_edit") else None
 
 
 _GUIDE_FLAGS = ("guide_motifs", "guide_weights", "guide_margin")
@@ -132,8 +145,8 @@ def guide_reward(args):
 
 
 def run(args):
-    if hasattr(args, "eval_motifs") and not getattr(args, "eval_quality", None):
-        raise ValueError(_MOTIFS_NEED_SETS)                     # before any model is built
+    if _eval_error(args):
+        raise ValueError(_eval_error(args))                     # before any model is built
     if _guide_error(args):
         raise ValueError(_guide_error(args))                    # so are these
     guide = guide_reward(args)                                  # ... and a file or a weight that does not parse
@@ -196,6 +209,8 @@ def run(args):
         if getattr(args, "eval_motifs", None):
             from .motifs import load_meme
             report.update(model.evaluate_motifs(gen_samples, load_meme(args.eval_motifs), refs=sets))
+        if hasattr(args, "eval_edit"):
+            report.update(model.evaluate_edit(gen_samples, args.eval_edit, train=sets.get("train")))
         extra.update({f"quality_{key}": np.float64(v) for key, v in report.items()})
     np.savez(path, decoding=reward_model_preds.cpu().numpy(), baseline=baseline_preds.cpu().numpy(), **extra)
     print(f"wrote {path}.npz: decoding mean {reward_model_preds.mean().item():.4f} (n={reward_model_preds.numel()}), "
@@ -208,8 +223,8 @@ def run(args):
 def main(method="mc", argv=None):
     parser = build_parser(method)
     args = parser.parse_args(argv)
-    if hasattr(args, "eval_motifs") and not getattr(args, "eval_quality", None):
-        parser.error(_MOTIFS_NEED_SETS)
+    if _eval_error(args):
+        parser.error(_eval_error(args))
     if _guide_error(args):
         parser.error(_guide_error(args))
     return run(args)

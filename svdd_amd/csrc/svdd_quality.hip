@@ -12,6 +12,9 @@
 //                      one LDS atomic. The query's minimum is kept in registers (ascending rows, strictly smaller wins: the first
 //                      row of a tie) and meets the other segments' in one 64-bit atomic min per query on the key
 //                      (distance << 32 | database index).
+//   svdd_edit_nn       the same skeleton for the Levenshtein distance: a thread keeps one query as four bit planes
+//                      and runs the bit-vector recurrence on them as one multi-word integer, one step per database token; the
+//                      token is wave-uniform, so the plane is chosen by a scalar branch.
 #include "svdd_host.h"
 
 namespace {
@@ -173,6 +176,155 @@ __global__ __launch_bounds__(QB) void hamming_nn_kernel(HammingArgs a) {
   }
 }
 
+constexpr int ED_TILE = 64;                 // database rows per LDS tile of the edit-distance kernel
+constexpr int ED_MAXW = HM_MAXL / 16;       // packed words of the longest database row
+
+struct EditArgs {
+  const uint32_t* q;
+  const uint32_t* db;
+  int B, N, Lq, Ld, Wq, Wd, cap;
+  int q_base, db_base, exclude_diag, seg_rows;
+  unsigned long long* nn_key;
+  unsigned long long* hist;
+};
+
+// One database token against the whole query: Myers' / Hyyro's bit-vector step on ONE integer of 32 WT bits (word 0 lowest).
+// eq: the positions of the query that hold this token. The only traffic between words is the carry of (eq & Pv) + Pv and the
+// two one-bit left shifts. The query's LAST position is bit 31 of word WT - 1, so that is where the score bit is read.
+template <int WT>
+__device__ __forceinline__ void edit_column(const uint32_t (&eq)[WT], uint32_t (&Pv)[WT], uint32_t (&Mv)[WT], int& score) {
+  uint32_t carry = 0, ph_in = 1, mh_in = 0;                       // Ph = (Ph << 1) | 1, Mh <<= 1
+#pragma unroll
+  for (int w = 0; w < WT; ++w) {
+    const uint32_t e = eq[w], pv = Pv[w], mv = Mv[w];
+    const uint32_t xv = e | mv;
+    const uint32_t sum = __builtin_addc(e & pv, pv, carry, &carry);
+    const uint32_t xh = (sum ^ pv) | e;
+    const uint32_t ph = mv | ~(xh | pv);
+    const uint32_t mh = pv & xh;
+    const uint32_t phs = (ph << 1) | ph_in, mhs = (mh << 1) | mh_in;
+    ph_in = ph >> 31;
+    mh_in = mh >> 31;
+    Pv[w] = mhs | ~(xv | phs);
+    Mv[w] = phs & xv;
+  }
+  score += (int)ph_in - (int)mh_in;
+}
+
+// The table's value on the diagonal that ends in its last cell, `rest` columns before the end: the score (the last row) minus the
+// vertical steps of the `rest` rows above it, which are the top `rest` bits of Pv (+1) and Mv (-1). Values never fall along a
+// diagonal, so the final distance is at least this. rest >= the query's length: the mask takes every row, the value is the column
+// number, which is no more than the difference of the lengths and so a bound as well. rest is wave-uniform: the masks are scalar.
+template <int WT>
+__device__ __forceinline__ int edit_diagonal(const uint32_t (&Pv)[WT], const uint32_t (&Mv)[WT], int score, int rest) {
+  int up = 0, down = 0;
+#pragma unroll
+  for (int w = 0; w < WT; ++w) {
+    const int lo = 32 * (WT - w) - rest;                            // the word's bits below this one are below the diagonal's row
+    const uint32_t mask = lo <= 0 ? 0xFFFFFFFFu : lo >= 32 ? 0u : 0xFFFFFFFFu << lo;
+    up += __popc(Pv[w] & mask);
+    down += __popc(Mv[w] & mask);
+  }
+  return score - up + down;
+}
+
+// grid (ceil(B / QB), segments of seg_rows database rows). A thread owns one query of m = Lq <= 32 WT positions as four bit planes
+// (one per token) placed at the TOP of the 32 WT bits: position i is bit off + i, off = 32 WT - m. The off bits below hold no
+// plane bit and start with Pv = Mv = 0; such a bit keeps Pv = Mv = 0 for ever and hands Ph = 1, Mh = 0 and no carry upwards, which
+// is what row 0 of the table hands to row 1 — so a shorter query needs no other code and the score bit never moves. The database
+// token is read from the LDS tile by every lane at one address and made scalar, so the plane is chosen by a scalar branch.
+// Every 16 columns a wave leaves the row if no lane can still use it: the diagonal's value (edit_diagonal) is a lower bound of the
+// final distance, and a lane's limit is cap with hist and, without, min(cap, the distance of the key it read, the best it found).
+// A workgroup's u32 bins hold at most QB * seg_rows < 2^32 pairs (the host keeps seg_rows <= 2^22).
+template <int WT>
+__global__ __launch_bounds__(QB) void edit_nn_kernel(EditArgs a) {
+  __shared__ uint32_t tile[ED_TILE * ED_MAXW];
+  __shared__ unsigned int h[HM_MAXL + 2];
+  const bool want_hist = a.hist != nullptr;
+  if (want_hist) {
+    for (int i = threadIdx.x; i < a.cap + 2; i += QB) h[i] = 0;
+  }
+  const int qi = blockIdx.x * QB + threadIdx.x;
+  const bool live = qi < a.B;
+  const int m = a.Lq, off = 32 * WT - m;
+  uint32_t eA[WT], eC[WT], eG[WT], eT[WT];
+#pragma unroll
+  for (int w = 0; w < WT; ++w) {
+    uint32_t pa = 0, pc = 0, pg = 0, pt = 0;
+    if (live && 32 * (w + 1) > off) {
+      const uint32_t* row = a.q + (long long)qi * a.Wq;
+      for (int b = max(0, off - 32 * w); b < 32; ++b) {
+        const int i = 32 * w + b - off;                              // 0 <= i < m: the padding bits of the row are never read
+        const uint32_t t = (row[i >> 4] >> (2 * (i & 15))) & 3u;
+        const uint32_t bit = 1u << b;
+        pa |= t == 0u ? bit : 0u;
+        pc |= t == 1u ? bit : 0u;
+        pg |= t == 2u ? bit : 0u;
+        pt |= t == 3u ? bit : 0u;
+      }
+    }
+    eA[w] = pa, eC[w] = pc, eG[w] = pg, eT[w] = pt;
+  }
+  const int seg0 = (int)min((long long)blockIdx.y * a.seg_rows, (long long)a.N);
+  const int seg1 = (int)min((long long)seg0 + a.seg_rows, (long long)a.N);
+  const long long diag = a.exclude_diag ? (long long)a.q_base + qi - a.db_base : -1;
+  int limit = a.cap;                                               // the largest distance this lane can still use
+  if (!want_hist && live) {
+    const unsigned long long k = __atomic_load_n(&a.nn_key[qi], __ATOMIC_RELAXED);
+    limit = (int)min((unsigned long long)a.cap, k >> 32);
+  }
+  unsigned int best_d = 0xFFFFFFFFu, beyond = 0;
+  int best_j = 0;
+  for (int t0 = seg0; t0 < seg1; t0 += ED_TILE) {
+    const int nr = min(ED_TILE, seg1 - t0);
+    __syncthreads();                                              // the previous tile is read (and h is zeroed)
+    for (int i = threadIdx.x; i < nr * a.Wd; i += QB) tile[i] = a.db[(long long)t0 * a.Wd + i];
+    __syncthreads();
+    for (int r = 0; r < nr; ++r) {
+      const bool mine = live && (long long)(t0 + r) != diag;
+      uint32_t Pv[WT], Mv[WT];
+#pragma unroll
+      for (int w = 0; w < WT; ++w) Pv[w] = eA[w] | eC[w] | eG[w] | eT[w], Mv[w] = 0u;
+      int score = m;
+      bool left = false;
+      for (int j0 = 0; j0 < a.Ld; j0 += 16) {
+        uint32_t word = __builtin_amdgcn_readfirstlane(tile[r * a.Wd + (j0 >> 4)]);
+        const int nj = min(16, a.Ld - j0);
+        for (int jj = 0; jj < nj; ++jj, word >>= 2) {
+          switch (word & 3u) {
+            case 0: edit_column<WT>(eA, Pv, Mv, score); break;
+            case 1: edit_column<WT>(eC, Pv, Mv, score); break;
+            case 2: edit_column<WT>(eG, Pv, Mv, score); break;
+            default: edit_column<WT>(eT, Pv, Mv, score); break;
+          }
+        }
+        const int rest = a.Ld - j0 - nj;                            // columns still to come
+        if (rest > 0 && __all(!mine || edit_diagonal<WT>(Pv, Mv, score, rest) > limit)) { left = true; break; }
+      }
+      if (mine) {
+        const unsigned int d = left ? 0xFFFFFFFFu : (unsigned int)score;
+        if (d <= (unsigned int)a.cap) {
+          if (want_hist) atomicAdd(&h[d], 1u);
+          if (d < best_d && d <= (unsigned int)limit) {
+            best_d = d, best_j = t0 + r;
+            if (!want_hist) limit = (int)d;
+          }
+        } else {
+          ++beyond;
+        }
+      }
+    }
+  }
+  if (live && a.nn_key && best_d != 0xFFFFFFFFu)
+    atomicMin(&a.nn_key[qi], ((unsigned long long)best_d << 32) | (unsigned long long)(uint32_t)(a.db_base + best_j));
+  if (want_hist) {
+    if (beyond) atomicAdd(&h[a.cap + 1], beyond);
+    __syncthreads();
+    for (int i = threadIdx.x; i < a.cap + 2; i += QB)
+      if (h[i]) atomicAdd(&a.hist[i], (unsigned long long)h[i]);
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -216,6 +368,27 @@ int svdd_hamming_nn(const uint32_t* q, const uint32_t* db, int B, int N, int L, 
   void (*k)(HammingArgs) = W <= 1 ? hamming_nn_kernel<1, 1> : W <= 2 ? hamming_nn_kernel<2, 2> : W <= 4 ? hamming_nn_kernel<4, 4>
                          : W <= 8 ? hamming_nn_kernel<8, 8> : W <= 13 ? hamming_nn_kernel<13, 16> : W <= 16 ? hamming_nn_kernel<16, 16>
                          : W <= 32 ? hamming_nn_kernel<32, 32> : hamming_nn_kernel<64, 64>;
+  return svdd_launch(k, dim3(gx, gy), dim3(QB), 0, on_stream, a);
+}
+
+int svdd_edit_nn(const uint32_t* q, const uint32_t* db, int B, int N, int Lq, int Ld, int cap, int q_base, int db_base,
+                 int exclude_diag, uint64_t* nn_key, int64_t* hist, void* on_stream) {
+  if (!q || !db || (!nn_key && !hist) || B <= 0 || N <= 0 || Lq <= 0 || Ld <= 0 || Lq > HM_MAXL || Ld > HM_MAXL) return SVDD_E_ARG;
+  if (cap < 0 || cap > (Lq > Ld ? Lq : Ld) || q_base < 0 || db_base < 0) return SVDD_E_ARG;
+  if ((long long)db_base + N >= (long long)1 << 31 || (long long)q_base + B >= (long long)1 << 31) return SVDD_E_ARG;
+  const unsigned gx = (unsigned)((B + QB - 1) / QB);
+  // a pair costs Ld columns of ceil(Lq / 32) words, thousands of times a Hamming pair: about 4096 workgroups in all so that the
+  // last ones to finish are short; whole tiles, at most 2^22 rows (QB * 2^22 pairs < 2^32 in a workgroup's u32 bins)
+  const long long want = (4096 + gx - 1) / gx;
+  long long seg = ((long long)N + want - 1) / want;
+  seg = (seg + ED_TILE - 1) / ED_TILE * ED_TILE;
+  if (seg > (1 << 22)) seg = 1 << 22;
+  const unsigned gy = (unsigned)(((long long)N + seg - 1) / seg);
+  const EditArgs a{q, db, B, N, Lq, Ld, (Lq + 15) / 16, (Ld + 15) / 16, cap, q_base, db_base, exclude_diag, (int)seg,
+                   (unsigned long long*)nn_key, (unsigned long long*)hist};
+  const int W = (Lq + 31) / 32;
+  void (*k)(EditArgs) = W <= 1 ? edit_nn_kernel<1> : W <= 2 ? edit_nn_kernel<2> : W <= 4 ? edit_nn_kernel<4> : W <= 7 ? edit_nn_kernel<7>
+                      : W <= 8 ? edit_nn_kernel<8> : W <= 16 ? edit_nn_kernel<16> : edit_nn_kernel<32>;
   return svdd_launch(k, dim3(gx, gy), dim3(QB), 0, on_stream, a);
 }
 

@@ -305,6 +305,17 @@ class BaseModel(nn.Module):
                                       ref_scores={name: reward(r) for name, r in token_refs.items()})
 
     @torch.no_grad()
+    def evaluate_edit(self, samples, edit_cap, train=None):
+        """Near copies of decoded designs by edit distance (svdd_amd.quality.edit_quality; not in the reference) -> a flat dict:
+        edit_near_batch_fraction, and with train [N, L'] edit_near_train_fraction, edit_near_train_min and (equal lengths)
+        hamming_missed_fraction, all within edit_cap edits. `samples` as in evaluate_nll."""
+        from . import quality
+        dev = self.ref_model.device
+        if isinstance(samples, (list, tuple)):
+            samples = torch.cat([torch.as_tensor(s).reshape(-1, s.shape[-1]).to(dev) for s in samples])
+        return quality.edit_quality(torch.as_tensor(samples).to(dev), edit_cap, train=train)
+
+    @torch.no_grad()
     def evaluate_motifs(self, samples, mset, refs=None):
         """Motif content of decoded designs (svdd_amd.motifs; not in the reference) -> a flat dict: motif_spearman_<name> for every
         set of refs {name: tokens [N', L'] or motif frequencies [M]} (the rank correlation, over the motifs of `mset`, of the share

@@ -511,6 +511,34 @@ def hamming_nn(q, db, L, nn_key=None, hist=None, q_base=0, db_base=0, exclude_di
     return nn_key, hist
 
 
+def edit_nn(q, db, Lq, Ld, cap, nn_key=None, hist=None, q_base=0, db_base=0, exclude_diag=False):
+    """svdd_edit_nn on packed rows (pack_tokens): q int32 [B, ceil(Lq / 16)], db int32 [N, ceil(Ld / 16)]; the Levenshtein distance
+    of every pair, cap in 0 .. max(Lq, Ld). nn_key i64 [B] (or None), started by the caller at NN_KEY_INIT or at any earlier key, is
+    lowered to (distance << 32) | (db_base + j) of the nearest database row within cap (the lowest index among ties; a pair beyond
+    cap never touches it); hist i64 [cap + 2] (or None) is ADDED the number of pairs at each distance 0 .. cap and, in its last
+    bin, the pairs beyond. exclude_diag: the pairs with q_base + i == db_base + j are left out. Decode a key with nn_decode."""
+    Lq, Ld = int(Lq), int(Ld)
+    if not 1 <= Lq <= PACK_MAX_L or not 1 <= Ld <= PACK_MAX_L:
+        raise SvddError(f"edit_nn: Lq = {Lq}, Ld = {Ld} outside 1 .. {PACK_MAX_L}")
+    if not isinstance(cap, int) or isinstance(cap, bool) or not 0 <= cap <= max(Lq, Ld):
+        raise SvddError(f"edit_nn: cap = {cap!r} outside 0 .. max(Lq, Ld) = {max(Lq, Ld)}")
+    Wq, Wd = packed_words(Lq), packed_words(Ld)
+    _need(q, torch.int32, "q"), _need(db, torch.int32, "db")
+    if q.dim() != 2 or db.dim() != 2 or q.shape[1] != Wq or db.shape[1] != Wd or not q.is_contiguous() or not db.is_contiguous() \
+            or q.shape[0] == 0 or db.shape[0] == 0:
+        raise SvddError(f"edit_nn: q and db must be contiguous non-empty int32 [*, {Wq}] and [*, {Wd}] tensors, got {tuple(q.shape)} "
+                        f"and {tuple(db.shape)}")
+    B, N = q.shape[0], db.shape[0]
+    if nn_key is None and hist is None:
+        raise SvddError("edit_nn: give nn_key, hist or both")
+    if nn_key is not None:
+        _is(nn_key, torch.int64, (B,), "nn_key")
+    if hist is not None:
+        _is(hist, torch.int64, (cap + 2,), "hist")
+    _lib.call("svdd_edit_nn", q, db, B, N, Lq, Ld, cap, int(q_base), int(db_base), int(bool(exclude_diag)), nn_key, hist, _this_stream())
+    return nn_key, hist
+
+
 def nn_decode(nn_key):
     """nn_key i64 [B] of hamming_nn -> (dist i32 [B], idx i64 [B]); a key nobody lowered (no pair) gives (-1, -1)."""
     none = nn_key == NN_KEY_INIT

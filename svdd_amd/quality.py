@@ -6,6 +6,9 @@ standard companions of a reward table that it does not have, diversity and novel
   pack_tokens / hamming_nn / pairwise_hamming_hist
                                     Hamming distances on 2-bit-packed rows (svdd_pack_tokens, svdd_hamming_nn): exact integers,
                                     independent of every chunking
+  edit_nn / pairwise_edit_hist / edit_quality
+                                    Levenshtein distances on the same packed rows (svdd_edit_nn): the near copies that
+                                    Hamming distance cannot see (a shifted training row)
   wasserstein_1d / frechet_distance host-level float64 (torch), no kernel
   sample_quality                    the flat report
 
@@ -20,6 +23,7 @@ from . import ops
 from .ops import SvddError
 
 HAMMING_CHUNK_ROWS = 1 << 20             # database rows per svdd_hamming_nn call (any value gives the same result)
+EDIT_CHUNK_ROWS = 1 << 20                # database rows per svdd_edit_nn call (likewise)
 KMER_CHUNK_ROWS = 1 << 22
 
 
@@ -159,6 +163,90 @@ def hamming_nn(x, db=None, chunk_rows=None):
 def pairwise_hamming_hist(x, db=None):
     """i64 [L + 1]: the number of pairs (row of x, row of db) at each Hamming distance; db None: the ordered pairs i != j of x."""
     return _hamming(x, db, None, False, True)[1]
+
+
+# ---------------------------------------------------------------------------------------------------- edit distances ----
+def _check_cap(cap, Lq, Ld, name="cap"):
+    if cap is None:
+        return max(Lq, Ld)
+    if not isinstance(cap, int) or isinstance(cap, bool) or not 0 <= cap <= max(Lq, Ld):
+        raise ValueError(f"{name} = {cap!r}: expected an int in 0 .. max(Lq, Ld) = {max(Lq, Ld)} or None")
+    return cap
+
+
+def _edit(x, db, cap, chunk_rows, want_key, want_hist, seed_hamming=True):
+    """-> (nn_key i64 [B] | None, hist i64 [cap + 2] | None) of x against db (None: x against itself without the diagonal) by
+    Levenshtein distance. The two sets may have different lengths."""
+    rows = _chunk_rows(chunk_rows, EDIT_CHUNK_ROWS)
+    x = _checked(x, "x", 3)
+    xd = None if db is None else _checked(db, "db", 3)
+    Lq, Ld = x.shape[1], x.shape[1] if xd is None else xd.shape[1]
+    if max(Lq, Ld) > ops.PACK_MAX_L:
+        raise ValueError(f"L = {max(Lq, Ld)} > {ops.PACK_MAX_L}")
+    cap = _check_cap(cap, Lq, Ld)
+    x, xd = _on_device(x, "x"), None if xd is None else _on_device(xd, "db")
+    B = x.shape[0]
+    err = torch.zeros(1, dtype=torch.int32, device=x.device)
+    q = ops.pack_tokens(x, err=err)
+    src = x if xd is None else xd
+    chunks = [(r0, q[r0:r0 + rows] if xd is None else ops.pack_tokens(xd[r0:r0 + rows], err=err)) for r0 in range(0, src.shape[0], rows)]
+    key = torch.full((B,), ops.NN_KEY_INIT, dtype=torch.int64, device=x.device) if want_key else None
+    hist = torch.zeros(cap + 2, dtype=torch.int64, device=x.device) if want_hist else None
+    if want_key and not want_hist and seed_hamming and Lq == Ld:
+        # the Hamming neighbour is an upper bound (edit distance <= Hamming distance of the same pair): a seed within cap lets the
+        # edit pass leave every pair that cannot beat it
+        seed = torch.full_like(key, ops.NN_KEY_INIT)
+        for r0, d in chunks:
+            ops.hamming_nn(q, d, Lq, seed, None, db_base=r0, exclude_diag=xd is None)
+        key = torch.where((seed != ops.NN_KEY_INIT) & ((seed >> 32) <= cap), seed, key)
+    for r0, d in chunks:
+        ops.edit_nn(q, d, Lq, Ld, cap, key, hist, db_base=r0, exclude_diag=xd is None)
+    ops.check_pack_err(err)
+    return key, hist
+
+
+def edit_nn(x, db=None, cap=None, chunk_rows=None, seed_hamming=True):
+    """Nearest neighbour of every row of x in db by Levenshtein distance (substitution, insertion, deletion: 1 each; global) within
+    cap edits -> (dist i32 [B], idx i64 [B]); among equally near rows the lowest index, (-1, -1) where no row is within cap.
+    db None: x against itself with the diagonal excluded. cap None: max(Lq, Ld), so every row gets an answer. x and db may have
+    different lengths. chunk_rows: database rows per launch. seed_hamming (equal lengths): start from one Hamming pass, whose
+    neighbour bounds the edit distance from above. Neither changes the result."""
+    return ops.nn_decode(_edit(x, db, cap, chunk_rows, True, False, seed_hamming)[0])
+
+
+def pairwise_edit_hist(x, db=None, cap=None):
+    """i64 [cap + 2]: the number of pairs (row of x, row of db) at each Levenshtein distance 0 .. cap, and in the last bin the pairs
+    beyond cap; db None: the ordered pairs i != j of x. cap None: max(Lq, Ld) (the last bin is then 0)."""
+    return _edit(x, db, cap, None, False, True)[1]
+
+
+def edit_quality(x, edit_cap, train=None):
+    """The near-copy report sample_quality's Hamming keys cannot give (a training row shifted by three bases is 6 edits away and
+    about 0.75 L by Hamming) -> a flat dict, k = edit_cap:
+      edit_near_batch_fraction   the share of designs with ANOTHER design within k edits
+      edit_near_train_fraction / edit_near_train_min   with train [N, L']: the share of designs with a training row within k
+                                 edits, and the smallest such distance (-1 if none)
+      hamming_missed_fraction    with train of the designs' length: the share of designs with a training row within k edits whose
+                                 nearest training row by Hamming is farther than k (the designs the Hamming report calls novel)"""
+    x = _checked(x, "x", 3)
+    train = None if train is None else _checked(train, "train", 3)
+    B, L = x.shape
+    if edit_cap is None or _check_cap(edit_cap, L, L if train is None else train.shape[1], "edit_cap") != edit_cap:
+        raise ValueError("edit_cap = None: expected an int in 0 .. max(Lq, Ld)")
+    x = _on_device(x, "x")
+    out = {}
+    dist, _ = ops.nn_decode(_edit(x, None, min(edit_cap, L), None, True, False)[0])      # two rows of length L: at most L edits
+    out["edit_near_batch_fraction"] = int((dist >= 0).sum()) / B
+    if train is not None:
+        train = _on_device(train, "train")
+        dist, _ = ops.nn_decode(_edit(x, train, edit_cap, None, True, False)[0])
+        near = dist >= 0
+        out["edit_near_train_fraction"] = int(near.sum()) / B
+        out["edit_near_train_min"] = int(dist[near].min()) if bool(near.any()) else -1
+        if train.shape[1] == L:
+            hd, _ = hamming_nn(x, train)
+            out["hamming_missed_fraction"] = int((near & (hd > edit_cap)).sum()) / B
+    return out
 
 
 # ------------------------------------------------------------------------------------------ host-level float64 rules ----
