@@ -2248,8 +2248,12 @@ __global__ __launch_bounds__(256) void backbone_order_kernel(const int* __restri
 // the same cover, so the tiles of a row are disjoint (at most 13, origins < L). Runs of adjacent tiles are cut to max_item as ever.
 // Tight cutting can need SEG_SLOTS + 1 items (four 3-tile runs cut 2 + 1 each): such a (layer, row) takes the aligned cover, as
 // origins 16 T. The deeper layers get backbone_worklist_kernel's aligned items, first tile | tiles << 8, unchanged. At dilation 1
-// no bit depends on the origin: every tap of every live tile runs in backbone_kernel's schedule, and an output row's accumulator
-// and a row's LayerNorm do not depend on which tile holds the row (the tight windows of the tower rest on the same fact).
+// no bit depends on the origin: an output row's accumulator and a row's LayerNorm do not depend on which tile holds the row (the
+// tight windows of the tower rest on the same fact), and the segment kernels run every tap of every own tile at dilation 1 (they
+// mask taps only at DIL > 1). backbone_kernel's schedule runs the same taps EXCEPT where the last tile holds fewer than five live
+// rows (L mod 16 in 1 .. 4): there it drops (last tile, tap + d) for every d >= L mod 16, all of whose rows read past the end. The
+// segment kernels issue those MFMAs on image rows >= L, which are zero: every extra product is a zero, the accumulator (it starts
+// at the bias) keeps its bits, and the two kernels still agree bit for bit (tests/test_lengths_gpu.py, every residue mod 16).
 // stat[0] += the tiles cut for layers <= lead1, stat[1] += those of the deeper layers, one add per wave.
 __global__ __launch_bounds__(256) void backbone_list_kernel(const uint8_t* __restrict__ x, const uint8_t* __restrict__ x_cur,
                                                             uint8_t* __restrict__ x_next, int n, int L, int max_item,
