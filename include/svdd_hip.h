@@ -377,6 +377,46 @@ int svdd_edit_nn(const uint32_t* q, const uint32_t* db, int B, int N, int Lq, in
                  int exclude_diag, uint64_t* nn_key, int64_t* hist, void* on_stream);
 
 /*
+ * Greedy selection under a minimum distance (added under ABI 17: two new entries, nothing existing changed; not in the
+ * reference): the two device steps of "walk the rows from the best down, keep a row that is at least min_dist from every row kept".
+ * Integer arithmetic only; every output is exact and independent of the launch shape. The stream is explicit (as svdd_edit_nn).
+ *
+ * svdd_within: q [B, W] and db [N, W] packed u32 (svdd_pack_tokens), W = ceil(L / 16); q_rc [B, W] or NULL: the packed reverse
+ *   complements of the queries (row i of q_rc is rc(row i of q), rc(a)[l] = 3 - a[L - 1 - l]). d(i, j) = the Hamming distance of
+ *   q_i and db_j (svdd_hamming_nn's; the padding bits of the last word are masked out on both sides) or, with q_rc, the smaller of
+ *   that and the distance of q_rc_i and db_j. db_count: a device int32 or NULL; only the database rows j < n = min(N, *db_count)
+ *   exist (a count below 0 reads as 0); NULL: n = N. radius = 0 .. L - 1; a pair is a hit when d <= radius.
+ *   first [B] i32 or NULL, started by the caller at INT32_MAX or at any earlier value: first[i] = min(first[i], the lowest j < n
+ *   that is a hit) by integer atomic min; a query without a hit keeps its value. mask [B, mask_words] u32 or NULL, mask_words >=
+ *   ceil(N / 32): EVERY word of every row i < B is WRITTEN by a plain store (the caller need not zero it): bit j % 32 of word
+ *   j / 32 is set iff j < n and (i, j) is a hit; all other bits, the words at and beyond ceil(N / 32) included, are zero. A
+ *   thread keeps one query (and its reverse complement) in registers, a workgroup of 256 queries walks a segment of the database
+ *   in tiles of 64 rows staged in LDS and the owning thread gathers 32 rows into one mask word. The grid is sized from N; a
+ *   workgroup whose segment starts at or beyond n computes nothing (it stores its zero words of mask).
+ *   SVDD_E_ARG: B, N or L <= 0, L > 1024, radius outside 0 .. L - 1, a NULL q or db, neither output, mask with mask_words <
+ *   ceil(N / 32).
+ *
+ * svdd_greedy_pick: the serial walk over ONE block of T <= 4096 rows in rank order, in one launch of one wave. mask [T, mask_words]
+ *   u32, mask_words >= ceil(T / 32): bit j of row i set = rows i and j of the block are closer than the minimum distance (svdd_within
+ *   of the block against itself; only the bits j > i of row i matter, and only the first ceil(T / 32) words of a row are read).
+ *   first [T] i32 or NULL: the number of the earliest pick of EARLIER blocks that row i is too close to, or INT32_MAX (svdd_within
+ *   against reps). rows [T, W] packed u32, W = ceil(L / 16); base: the rank of the block's first row. State, read and advanced:
+ *   count (device int32: the picks so far), reps [cap, W] u32 and picked_rank [cap] i32 (appended at index count). For i = 0 ..
+ *   T - 1 in order: first[i] != INT32_MAX -> rep_pick[i] = first[i]; else a pick p of this block with bit i set in its mask row
+ *   exists -> rep_pick[i] = the earliest such p; else *count < min(k, cap) -> the row is picked: p = (*count)++, reps[p] = rows[i],
+ *   picked_rank[p] = base + i, rep_pick[i] = p; else rep_pick[i] = -1. rep_pick [T] i32 is WRITTEN in full; reps and picked_rank
+ *   are written at the new picks' indices only, never at or beyond cap. A *count outside 0 .. cap when the kernel starts: nothing
+ *   at all is written. The set of settled rows is held in registers (two words per lane); a row that is not picked never loads
+ *   its mask row, and nothing the walk branches on differs between lanes.
+ *   SVDD_E_ARG: T outside 1 .. 4096, L outside 1 .. 1024, k < 1, cap < 1, mask_words < ceil(T / 32), base < 0 or base + T >= 2^31,
+ *   a NULL mask, rows, count, reps, picked_rank or rep_pick.
+ */
+int svdd_within(const uint32_t* q, const uint32_t* q_rc, const uint32_t* db, const int32_t* db_count, int B, int N, int L, int radius,
+                int32_t* first, uint32_t* mask, int mask_words, void* on_stream);
+int svdd_greedy_pick(const uint32_t* mask, int mask_words, const int32_t* first, const uint32_t* rows, int T, int L, int base, int k,
+                     int32_t* count, uint32_t* reps, int32_t* picked_rank, int cap, int32_t* rep_pick, void* on_stream);
+
+/*
  * PWM motif scanning (added under ABI 17: one new entry, nothing existing changed; not in the reference). Integer log-odds tables,
  * int32 sums and integer atomics only: every result is exact and independent of the launch shape and of how the caller cuts its
  * rows into chunks. The stream is explicit (as svdd_kmer_counts).

@@ -70,6 +70,16 @@ def build_parser(method="mc"):
                         "deletions), which the Hamming novelty cannot see: the share of designs with another design, and with a row "
                         "of `train`, within K edits, the smallest such distance, and the share the Hamming report misses: printed, "
                         "and saved as npz keys quality_<metric>")
+    p.add_argument("--select", type=int, default=argparse.SUPPRESS, metavar="K",         # the three --select* flags: absent unless given
+                   help="also choose a library of the K best decoded sequences that are no near copies of each other: walk them "
+                        "from the highest reward prediction down and keep one when it is at least --select_min_dist substitutions "
+                        "from every sequence kept: one line printed, and saved as npz keys selected (tokens), selected_idx, "
+                        "selected_scores and library_<metric>")
+    p.add_argument("--select_min_dist", type=int, default=argparse.SUPPRESS, metavar="D",
+                   help="with --select: the smallest Hamming distance between two sequences of the library (default 1: no exact "
+                        "duplicates)")
+    p.add_argument("--select_revcomp", action="store_true", default=argparse.SUPPRESS,
+                   help="with --select: a sequence is also a near copy of another's reverse complement")
     p.add_argument("--guide_motifs", default=argparse.SUPPRESS, metavar="FILE.meme",     # the three --guide_* flags: absent unless given
                    help="--method tweedie only: decode towards (or away from) the motifs of FILE.meme, the reward net's score plus "
                         "a motif term (svdd_amd.motifs.MotifReward); give --guide_weights, --guide_margin or both")
@@ -91,10 +101,15 @@ def _guidance_scale(args):
 
 _MOTIFS_NEED_SETS = "--eval_motifs needs --eval_quality FILE.npz: the reference sets its correlations are taken against"
 _EDIT_NEEDS_SETS = "--eval_edit needs --eval_quality FILE.npz: the training set its near copies are looked for in"
+_SELECT_NEEDS_K = "--{} needs --select K: the size of the library it shapes"
 
 
 def _eval_error(args):
-    """What is wrong with the --eval_* flags of args, or None."""
+    """What is wrong with the --eval_* and --select* flags of args, or None."""
+    if not hasattr(args, "select"):
+        for flag in ("select_min_dist", "select_revcomp"):
+            if hasattr(args, flag):
+                return _SELECT_NEEDS_K.format(flag)
     if getattr(args, "eval_quality", None):
         return None
     return _MOTIFS_NEED_SETS if hasattr(args, "eval_motifs") else _EDIT_NEEDS_SETS if hasattr(args, "eval_edit") else None
@@ -212,9 +227,17 @@ def run(args):
         if hasattr(args, "eval_edit"):
             report.update(model.evaluate_edit(gen_samples, args.eval_edit, train=sets.get("train")))
         extra.update({f"quality_{key}": np.float64(v) for key, v in report.items()})
+    library = None
+    if hasattr(args, "select"):
+        tokens, scores, idx, library = model.select_library(gen_samples, args.select, getattr(args, "select_min_dist", 1),
+                                                            revcomp=getattr(args, "select_revcomp", False))
+        extra.update(selected=tokens.cpu().numpy(), selected_idx=idx.cpu().numpy(), selected_scores=scores.cpu().numpy())
+        extra.update({key if key.startswith("library_") else f"library_{key}": np.float64(v) for key, v in library.items()})
     np.savez(path, decoding=reward_model_preds.cpu().numpy(), baseline=baseline_preds.cpu().numpy(), **extra)
     print(f"wrote {path}.npz: decoding mean {reward_model_preds.mean().item():.4f} (n={reward_model_preds.numel()}), "
           f"baseline mean {baseline_preds.mean().item():.4f}{nll_note}")
+    if library is not None:
+        print("library: " + ", ".join(f"{key} {v:.4f}" for key, v in library.items()))
     if report is not None:
         print("quality: " + ", ".join(f"{key} {v:.4f}" for key, v in report.items()))
     return path + ".npz", out

@@ -59,6 +59,8 @@ enum SvddProfileSlot {
   SVDD_SLOT_BACKBONE_GRAD = 10,  // svdd_backbone_cnn_grad_f32
   SVDD_SLOT_GRU_TRAIN = 11,      // DPS: the GRU forward that saves its gates (svdd_gru_bidir_train[2]_f32)
   SVDD_SLOT_GRU_BPTT = 12,       // DPS: the GRU's back-propagation through time (svdd_gru_bidir_bwd[2]_f32)
+  SVDD_SLOT_WITHIN = 13,         // svdd_within
+  SVDD_SLOT_GREEDY_PICK = 14,    // svdd_greedy_pick
   SVDD_SLOT_COUNT
 };
 

@@ -15,6 +15,12 @@
 //   svdd_edit_nn       the same skeleton for the Levenshtein distance: a thread keeps one query as four bit planes
 //                      and runs the bit-vector recurrence on them as one multi-word integer, one step per database token; the
 //                      token is wave-uniform, so the plane is chosen by a scalar branch.
+//   svdd_within        svdd_hamming_nn's skeleton with a radius: which database rows are within it, as a bit matrix
+//                      (the owning thread gathers 32 rows into a word: plain stores) and / or as the lowest such row; optionally
+//                      the smaller of the distances to the query and to its reverse complement; the database's length may live
+//                      on the device
+//   svdd_greedy_pick   the serial walk of greedy selection over one block of rows, in one wave: the settled set lives in
+//                      registers, only the rows that are picked load their row of the bit matrix
 #include "svdd_host.h"
 
 namespace {
@@ -325,6 +331,159 @@ __global__ __launch_bounds__(QB) void edit_nn_kernel(EditArgs a) {
   }
 }
 
+struct WithinArgs {
+  const uint32_t* q;
+  const uint32_t* q_rc;                      // the packed reverse complements of the queries, or NULL
+  const uint32_t* db;
+  const int32_t* db_count;                   // device: only the rows j < min(N, *db_count) exist; NULL: all N
+  int B, N, W, radius, seg_rows, mask_words;
+  uint32_t last_mask;
+  int32_t* first;
+  uint32_t* mask;
+};
+
+// grid (ceil(B / QB), segments of seg_rows database rows, seg_rows a multiple of HM_TILE). hamming_nn_kernel's skeleton with a
+// threshold in place of the minimum: d = row_distance to the query, with RC the smaller of that and the distance to the query's
+// reverse complement. A tile is two mask words: the owning thread gathers 32 database rows into a register and stores the word, so
+// mask needs neither atomics nor zeroing; the words of its segment that no live tile covers (rows beyond the device count, and for
+// the last segment everything up to mask_words) are stored as zeros. first: the lowest hit of the segment (ascending rows: the
+// first one seen), one integer atomic min per query that has one.
+template <int WT, int WS, bool RC>
+__global__ __launch_bounds__(QB) void within_kernel(WithinArgs a) {
+  __shared__ __attribute__((aligned(16))) uint32_t tile[HM_TILE * WS];
+  const int qi = blockIdx.x * QB + threadIdx.x;
+  const bool live = qi < a.B;
+  const int n = a.db_count ? max(0, min(a.N, *a.db_count)) : a.N;   // one address for the whole grid: a scalar load
+  const long long seg_lo = (long long)blockIdx.y * a.seg_rows;     // < N: the host sizes the grid from N
+  const bool last_seg = blockIdx.y == gridDim.y - 1;
+  const int word_lo = (int)(seg_lo / 32);
+  const int word_hi = last_seg ? a.mask_words : (int)((seg_lo + a.seg_rows) / 32);    // <= ceil(N / 32) <= mask_words otherwise
+  uint32_t* mrow = a.mask && live ? a.mask + (long long)qi * a.mask_words : nullptr;
+  const int seg0 = (int)min(seg_lo, (long long)n);
+  const int seg1 = (int)min(seg_lo + a.seg_rows, (long long)n);
+  if (seg0 >= seg1) {                                              // the segment starts at or beyond the device count
+    if (mrow)
+      for (int w = word_lo; w < word_hi; ++w) mrow[w] = 0u;
+    return;
+  }
+  uint32_t q[WT], qr[RC ? WT : 1];
+#pragma unroll
+  for (int w = 0; w < WT; ++w) {
+    const uint32_t keep = w == a.W - 1 ? a.last_mask : 0xFFFFFFFFu;
+    q[w] = live && w < a.W ? a.q[(long long)qi * a.W + w] & keep : 0u;
+    if constexpr (RC) qr[w] = live && w < a.W ? a.q_rc[(long long)qi * a.W + w] & keep : 0u;
+  }
+  int hit = INT32_MAX;
+  int word = word_lo;                                              // the next mask word this thread stores
+  for (int t0 = seg0; t0 < seg1; t0 += HM_TILE) {
+    const int nr = min(HM_TILE, seg1 - t0);
+    __syncthreads();                                              // the previous tile is read
+    for (int i = threadIdx.x; i < nr * WS; i += QB) {
+      const int r = i / WS, w = i - r * WS;
+      tile[i] = w < a.W ? a.db[(long long)(t0 + r) * a.W + w] & (w == a.W - 1 ? a.last_mask : 0xFFFFFFFFu) : 0u;
+    }
+    __syncthreads();
+    if (live) {
+#pragma unroll
+      for (int half = 0; half < HM_TILE / 32; ++half) {
+        uint32_t bits = 0;
+        const int r1 = min(32, nr - 32 * half);
+#pragma unroll 2
+        for (int r = 0; r < r1; ++r) {
+          int d = row_distance<WT, WS>(q, &tile[(32 * half + r) * WS]);
+          if constexpr (RC) d = min(d, row_distance<WT, WS>(qr, &tile[(32 * half + r) * WS]));
+          if (d <= a.radius) {
+            bits |= 1u << r;
+            hit = min(hit, t0 + 32 * half + r);
+          }
+        }
+        if (mrow && word < word_hi) mrow[word] = bits;
+        ++word;
+      }
+    }
+  }
+  if (mrow)
+    for (; word < word_hi; ++word) mrow[word] = 0u;
+  if (live && a.first && hit != INT32_MAX) atomicMin(&a.first[qi], hit);
+}
+
+template <bool RC>
+int launch_within(const WithinArgs& a, dim3 grid, void* on_stream) {
+  SvddSpan span(SVDD_SLOT_WITHIN);
+  const int W = a.W;
+  void (*k)(WithinArgs) = W <= 1 ? within_kernel<1, 1, RC> : W <= 2 ? within_kernel<2, 2, RC> : W <= 4 ? within_kernel<4, 4, RC>
+                        : W <= 8 ? within_kernel<8, 8, RC> : W <= 13 ? within_kernel<13, 16, RC> : W <= 16 ? within_kernel<16, 16, RC>
+                        : W <= 32 ? within_kernel<32, 32, RC> : within_kernel<64, 64, RC>;
+  return svdd_launch_timed(span.all(), k, grid, dim3(QB), 0, on_stream, a);
+}
+
+constexpr int GP_MAXT = 4096;              // rows of one greedy_pick block: 128 words of the suppressed set, two per lane
+constexpr int GP_WAVE = 64;
+
+struct PickArgs {
+  const uint32_t* mask;
+  const int32_t* first;
+  const uint32_t* rows;
+  int T, W, mask_words, base, k, cap;
+  int32_t* count;
+  uint32_t* reps;
+  int32_t* picked_rank;
+  int32_t* rep_pick;
+};
+
+__device__ __forceinline__ uint32_t lane_word(uint32_t s0, uint32_t s1, int w) {    // word w of the set, w wave-uniform
+  return w < GP_WAVE ? __builtin_amdgcn_readlane(s0, w) : __builtin_amdgcn_readlane(s1, w - GP_WAVE);
+}
+
+// ONE wave. The set of rows that are settled (suppressed, picked, or represented by an earlier block's pick through `first`) is a
+// bit set of T <= 4096 bits held in registers: lane l has words l and 64 + l. The walk reads the current word with a cross-lane
+// read and visits only its zero bits, in order; everything it branches on is wave-uniform. A pick loads its own mask row (lane l
+// the words l and 64 + l), ORs it in, and every lane writes the pick's number to the rows its words newly settle — the pick
+// itself among them. Bits j <= i of the row change nothing: those rows are settled already. Rows settled later never load their
+// mask row. When min(k, cap) picks exist the walk ends and the rows still open get -1.
+__global__ __launch_bounds__(GP_WAVE) void greedy_pick_kernel(PickArgs a) {
+  const int lane = threadIdx.x;
+  int count = *a.count;
+  if (count < 0 || count > a.cap) return;                          // a count the state cannot hold: nothing is written
+  const int limit = min(a.k, a.cap);
+  const int nw = (a.T + 31) / 32;
+  // padding bits of the last word count as settled: never visited, never written
+  auto valid = [&](int w) { return w >= nw ? 0u : w == nw - 1 && a.T % 32 ? (1u << (a.T % 32)) - 1u : 0xFFFFFFFFu; };
+  uint32_t s0 = ~valid(lane), s1 = ~valid(GP_WAVE + lane);
+  if (a.first) {
+    for (int c = 0; 64 * c < a.T; ++c) {                           // 64 rows at a time, coalesced; the ballot is two words of the set
+      const int i = 64 * c + lane;
+      const int f = i < a.T ? a.first[i] : INT32_MAX;
+      if (f != INT32_MAX) a.rep_pick[i] = f;
+      const unsigned long long has = __ballot(f != INT32_MAX);
+      const int w = 2 * c;
+      if (lane == (w & 63)) (w < GP_WAVE ? s0 : s1) |= (uint32_t)has;
+      if (lane == ((w + 1) & 63)) (w + 1 < GP_WAVE ? s0 : s1) |= (uint32_t)(has >> 32);
+    }
+  }
+  bool full = false;
+  for (int wi = 0; wi < nw && !full; ++wi) {
+    uint32_t open = ~lane_word(s0, s1, wi);
+    while (open) {
+      if (count >= limit) { full = true; break; }
+      const int b = __ffs(open) - 1, i = 32 * wi + b, p = count++;
+      const uint32_t* mr = a.mask + (long long)i * a.mask_words;
+      uint32_t m0 = lane < nw ? mr[lane] : 0u, m1 = GP_WAVE + lane < nw ? mr[GP_WAVE + lane] : 0u;
+      if (lane == (wi & 63)) (wi < GP_WAVE ? m0 : m1) |= 1u << b;   // the pick settles itself, whatever the diagonal holds
+      const uint32_t n0 = m0 & ~s0, n1 = m1 & ~s1;
+      s0 |= n0, s1 |= n1;
+      for (uint32_t v = n0; v; v &= v - 1) a.rep_pick[32 * lane + __ffs(v) - 1] = p;
+      for (uint32_t v = n1; v; v &= v - 1) a.rep_pick[32 * (GP_WAVE + lane) + __ffs(v) - 1] = p;
+      if (lane < a.W) a.reps[(long long)p * a.W + lane] = a.rows[(long long)i * a.W + lane];
+      if (lane == 0) a.picked_rank[p] = a.base + i;
+      open = ~lane_word(s0, s1, wi);
+    }
+  }
+  for (uint32_t v = ~s0; v; v &= v - 1) a.rep_pick[32 * lane + __ffs(v) - 1] = -1;
+  for (uint32_t v = ~s1; v; v &= v - 1) a.rep_pick[32 * (GP_WAVE + lane) + __ffs(v) - 1] = -1;
+  if (lane == 0) *a.count = count;
+}
+
 }  // namespace
 
 extern "C" {
@@ -390,6 +549,34 @@ int svdd_edit_nn(const uint32_t* q, const uint32_t* db, int B, int N, int Lq, in
   void (*k)(EditArgs) = W <= 1 ? edit_nn_kernel<1> : W <= 2 ? edit_nn_kernel<2> : W <= 4 ? edit_nn_kernel<4> : W <= 7 ? edit_nn_kernel<7>
                       : W <= 8 ? edit_nn_kernel<8> : W <= 16 ? edit_nn_kernel<16> : edit_nn_kernel<32>;
   return svdd_launch(k, dim3(gx, gy), dim3(QB), 0, on_stream, a);
+}
+
+int svdd_within(const uint32_t* q, const uint32_t* q_rc, const uint32_t* db, const int32_t* db_count, int B, int N, int L, int radius,
+                int32_t* first, uint32_t* mask, int mask_words, void* on_stream) {
+  if (!q || !db || (!first && !mask) || B <= 0 || N <= 0 || L <= 0 || L > HM_MAXL || radius < 0 || radius >= L) return SVDD_E_ARG;
+  if (mask && (long long)mask_words * 32 < N) return SVDD_E_ARG;
+  const int W = (L + 15) / 16;
+  const unsigned gx = (unsigned)((B + QB - 1) / QB);
+  // segments as svdd_hamming_nn's: about 1024 workgroups in all, whole tiles (so whole mask words), sized from N, the host's
+  // upper bound of the device count
+  const long long want = (1024 + gx - 1) / gx;
+  long long seg = ((long long)N + want - 1) / want;
+  seg = (seg + HM_TILE - 1) / HM_TILE * HM_TILE;
+  if (seg > (1 << 22)) seg = 1 << 22;
+  const unsigned gy = (unsigned)(((long long)N + seg - 1) / seg);
+  const uint32_t last_mask = L % 16 ? (1u << (2 * (L % 16))) - 1u : 0xFFFFFFFFu;
+  const WithinArgs a{q, q_rc, db, db_count, B, N, W, radius, (int)seg, mask ? mask_words : 0, last_mask, first, mask};
+  return q_rc ? launch_within<true>(a, dim3(gx, gy), on_stream) : launch_within<false>(a, dim3(gx, gy), on_stream);
+}
+
+int svdd_greedy_pick(const uint32_t* mask, int mask_words, const int32_t* first, const uint32_t* rows, int T, int L, int base, int k,
+                     int32_t* count, uint32_t* reps, int32_t* picked_rank, int cap, int32_t* rep_pick, void* on_stream) {
+  if (!mask || !rows || !count || !reps || !picked_rank || !rep_pick) return SVDD_E_ARG;
+  if (T < 1 || T > GP_MAXT || L <= 0 || L > HM_MAXL || k < 1 || cap < 1 || (long long)mask_words * 32 < T) return SVDD_E_ARG;
+  if (base < 0 || (long long)base + T >= (long long)1 << 31) return SVDD_E_ARG;
+  SvddSpan span(SVDD_SLOT_GREEDY_PICK);
+  const PickArgs a{mask, first, rows, T, (L + 15) / 16, mask_words, base, k, cap, count, reps, picked_rank, rep_pick};
+  return svdd_launch_timed(span.all(), greedy_pick_kernel, dim3(1), dim3(GP_WAVE), 0, on_stream, a);
 }
 
 }  // extern "C"

@@ -11,7 +11,7 @@ The reference's `BaseModel.__init__` hard-wires checkpoint paths, Hydra and `.cu
 5-tuple: (samples list, value_func_preds [N], reward_model_preds [N], top_k_values, baseline_preds [N]).
 The tokens of the baseline batches behind baseline_preds are kept in `baseline_samples`; `evaluate_nll` scores any of them
 under the pretrained model (Diffusion.sequence_nll); `evaluate_quality` reports set-level metrics of them (svdd_amd.quality),
-`evaluate_motifs` their motif content (svdd_amd.motifs).
+`evaluate_motifs` their motif content (svdd_amd.motifs); `select_library` picks the best of them that are no near copies of each other.
 """
 import torch
 from torch import nn
@@ -303,6 +303,25 @@ class BaseModel(nn.Module):
         token_refs = {name: r for name, r in (refs or {}).items() if getattr(r, "ndim", 0) == 2}
         return quality.sample_quality(samples, refs=refs, train=train, k=k, scores=reward(samples),
                                       ref_scores={name: reward(r) for name, r in token_refs.items()})
+
+    @torch.no_grad()
+    def select_library(self, samples, k, min_dist, revcomp=False):
+        """The k best designs that are no near copies of each other (svdd_amd.quality.select_diverse; not in the
+        reference): walk the designs from the highest reward prediction down and keep one when it is at least min_dist
+        substitutions from every design kept (revcomp: on either strand) -> (tokens [P, L], scores [P], idx [P], report), P <= k,
+        idx the kept rows of `samples` in pick order, report the flat dict of quality.library_quality. The scores are the
+        harness's reward model's, task 0, as evaluate_quality computes them. `samples` as in evaluate_nll."""
+        from . import quality
+        dev = self.ref_model.device
+        if isinstance(samples, (list, tuple)):
+            samples = torch.cat([torch.as_tensor(s).reshape(-1, s.shape[-1]).to(dev) for s in samples])
+        samples = torch.as_tensor(samples).to(dev)
+        n = self.NUM_SAMPLES_PER_BATCH
+        pred = torch.cat([self._reward(samples[i:i + n].long()) for i in range(0, samples.shape[0], n)])
+        scores = (pred if self.n_tasks == 1 else pred[:, 0]).reshape(-1).float()
+        sel, _, report = quality._library(samples, scores, k, min_dist, revcomp)
+        idx = sel.picked[:k]
+        return samples[idx], scores[idx], idx, report
 
     @torch.no_grad()
     def evaluate_edit(self, samples, edit_cap, train=None):

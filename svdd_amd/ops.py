@@ -547,7 +547,79 @@ def nn_decode(nn_key):
     return dist, idx
 
 
-MOTIF_MAX_W = 32                                                         # svdd_motif_scan (include/svdd_hip.h)
+FIRST_INIT = 2 ** 31 - 1                                                 # INT32_MAX: the value svdd_within's `first` starts from
+PICK_MAX_ROWS = 4096                                                     # rows of one svdd_greedy_pick block (include/svdd_hip.h)
+
+
+def _int_in(v, lo, hi, what):
+    if not isinstance(v, int) or isinstance(v, bool) or not lo <= v <= hi:
+        raise SvddError(f"{what} = {v!r} outside {lo} .. {hi}")
+    return v
+
+
+def within(q, db, L, radius, q_rc=None, db_count=None, first=None, mask=None):
+    """svdd_within on packed rows (pack_tokens): q int32 [B, W], db int32 [N, W], W = ceil(L / 16); q_rc int32 [B, W] (or None): the
+    packed reverse complements of q's rows, which makes the distance the smaller of the two strands'. A pair is a hit when its
+    distance is <= radius (0 .. L - 1). db_count int32 [1] on the device (or None): only the rows j < min(N, db_count) exist.
+    first int32 [B] (or None), started by the caller at FIRST_INIT, is lowered to the lowest hit; mask int32 [B, mask_words] (or
+    None), mask_words >= ceil(N / 32), is WRITTEN in full: bit j of row i = (i, j) is a hit."""
+    L = _int_in(L, 1, PACK_MAX_L, "within: L")
+    radius = _int_in(radius, 0, L - 1, "within: radius")
+    W = packed_words(L)
+    _need(q, torch.int32, "q"), _need(db, torch.int32, "db")
+    if q.dim() != 2 or db.dim() != 2 or q.shape[1] != W or db.shape[1] != W or not q.is_contiguous() or not db.is_contiguous() \
+            or q.shape[0] == 0 or db.shape[0] == 0:
+        raise SvddError(f"within: q and db must be contiguous non-empty int32 [*, {W}] tensors, got {tuple(q.shape)} and {tuple(db.shape)}")
+    B, N = q.shape[0], db.shape[0]
+    if q_rc is not None:
+        _is(q_rc, torch.int32, (B, W), "q_rc")
+    if db_count is not None:
+        _is(db_count, torch.int32, (1,), "db_count")
+    if first is None and mask is None:
+        raise SvddError("within: give first, mask or both")
+    if first is not None:
+        _is(first, torch.int32, (B,), "first")
+    mask_words = 0
+    if mask is not None:
+        _need(mask, torch.int32, "mask")
+        if mask.dim() != 2 or mask.shape[0] != B or mask.shape[1] * 32 < N or not mask.is_contiguous():
+            raise SvddError(f"within: mask must be a contiguous int32 [{B}, >= {(N + 31) // 32}] tensor, got {tuple(mask.shape)}")
+        mask_words = mask.shape[1]
+    _lib.call("svdd_within", q, q_rc, db, db_count, B, N, L, radius, first, mask, mask_words, _this_stream())
+    return first, mask
+
+
+def greedy_pick(mask, first, rows, L, base, k, count, reps, picked_rank, rep_pick):
+    """svdd_greedy_pick: the serial walk of greedy selection over one block of T <= PICK_MAX_ROWS rows in rank order. mask int32
+    [T, >= ceil(T / 32)] (within of the block against itself), first int32 [T] (or None; within of the block against reps), rows
+    int32 [T, W] the block's packed rows, base the rank of its first row, k >= 1 the number of picks wanted. State, advanced in
+    place: count int32 [1], reps int32 [cap, W], picked_rank int32 [cap]. rep_pick int32 [T] is WRITTEN: the number of the pick
+    that represents each row (its own if it is picked), -1 for a row that is left over once min(k, cap) picks exist."""
+    L = _int_in(L, 1, PACK_MAX_L, "greedy_pick: L")
+    k = _int_in(k, 1, 2 ** 31 - 1, "greedy_pick: k")
+    base = _int_in(base, 0, 2 ** 31 - 1, "greedy_pick: base")
+    W = packed_words(L)
+    _need(rows, torch.int32, "rows")
+    if rows.dim() != 2 or rows.shape[1] != W or not rows.is_contiguous() or not 1 <= rows.shape[0] <= PICK_MAX_ROWS:
+        raise SvddError(f"greedy_pick: rows must be a contiguous int32 [1 .. {PICK_MAX_ROWS}, {W}] tensor, got {tuple(rows.shape)}")
+    T = rows.shape[0]
+    _int_in(base, 0, 2 ** 31 - 1 - T, "greedy_pick: base")
+    _need(mask, torch.int32, "mask")
+    if mask.dim() != 2 or mask.shape[0] != T or mask.shape[1] * 32 < T or not mask.is_contiguous():
+        raise SvddError(f"greedy_pick: mask must be a contiguous int32 [{T}, >= {(T + 31) // 32}] tensor, got {tuple(mask.shape)}")
+    if first is not None:
+        _is(first, torch.int32, (T,), "first")
+    _is(count, torch.int32, (1,), "count")
+    _need(reps, torch.int32, "reps")
+    if reps.dim() != 2 or reps.shape[1] != W or reps.shape[0] == 0 or not reps.is_contiguous():
+        raise SvddError(f"greedy_pick: reps must be a contiguous non-empty int32 [cap, {W}] tensor, got {tuple(reps.shape)}")
+    cap = reps.shape[0]
+    _is(picked_rank, torch.int32, (cap,), "picked_rank"), _is(rep_pick, torch.int32, (T,), "rep_pick")
+    _lib.call("svdd_greedy_pick", mask, mask.shape[1], first, rows, T, L, base, k, count, reps, picked_rank, cap, rep_pick, _this_stream())
+    return rep_pick
+
+
+MOTIF_MAX_W = 32                                                      # svdd_motif_scan (include/svdd_hip.h)
 
 
 @dataclass

@@ -9,11 +9,14 @@ standard companions of a reward table that it does not have, diversity and novel
   edit_nn / pairwise_edit_hist / edit_quality
                                     Levenshtein distances on the same packed rows (svdd_edit_nn): the near copies that
                                     Hamming distance cannot see (a shifted training row)
+  select_diverse / library_quality  greedy selection under a minimum Hamming distance (svdd_within, svdd_greedy_pick): the
+                                    best rows that are no near copies of each other, and the families of the set
   wasserstein_1d / frechet_distance host-level float64 (torch), no kernel
   sample_quality                    the flat report
 
 Token inputs are [N, L] integer tensors (any integer dtype; a CPU tensor or a numpy array is checked on the host and moved to the
 GPU). The kernels have no CPU fallback."""
+import collections
 import math
 
 import numpy as np
@@ -25,6 +28,7 @@ from .ops import SvddError
 HAMMING_CHUNK_ROWS = 1 << 20             # database rows per svdd_hamming_nn call (any value gives the same result)
 EDIT_CHUNK_ROWS = 1 << 20                # database rows per svdd_edit_nn call (likewise)
 KMER_CHUNK_ROWS = 1 << 22
+SELECT_BLOCK_ROWS = 4096                 # rows per block of select_diverse's walk (likewise; measured in profiles/select_time.txt)
 
 
 def _checked(x, name, max_token):
@@ -247,6 +251,135 @@ def edit_quality(x, edit_cap, train=None):
             hd, _ = hamming_nn(x, train)
             out["hamming_missed_fraction"] = int((near & (hd > edit_cap)).sum()) / B
     return out
+
+
+# ------------------------------------------------------------------------------------------- diverse library selection ----
+Selection = collections.namedtuple("Selection", ["picked", "rep", "rep_dist"])
+
+
+def _check_select(x, scores, k, min_dist, block_rows):
+    """The host-side checks of select_diverse, before anything is launched -> (tokens, scores | None, k | None, rows per block)."""
+    x = _checked(x, "x", 3)
+    N, L = x.shape
+    if L > ops.PACK_MAX_L:
+        raise ValueError(f"L = {L} > {ops.PACK_MAX_L}")
+    if k is not None and (not isinstance(k, int) or isinstance(k, bool) or k < 1):
+        raise ValueError(f"k = {k!r}: expected an int >= 1 or None")
+    if not isinstance(min_dist, int) or isinstance(min_dist, bool) or not 1 <= min_dist <= L:
+        raise ValueError(f"min_dist = {min_dist!r}: expected an int in 1 .. L = {L}")
+    if block_rows is not None and (not isinstance(block_rows, int) or isinstance(block_rows, bool)
+                                   or not 1 <= block_rows <= ops.PICK_MAX_ROWS):
+        raise ValueError(f"block_rows = {block_rows!r}: expected an int in 1 .. {ops.PICK_MAX_ROWS} or None")
+    if scores is not None:
+        if isinstance(scores, np.ndarray):
+            scores = torch.from_numpy(np.ascontiguousarray(scores))
+        if not isinstance(scores, torch.Tensor) or not scores.dtype.is_floating_point or tuple(scores.shape) != (N,):
+            raise ValueError(f"scores must be a float tensor [{N}] or None, got {getattr(scores, 'dtype', type(scores))} "
+                             f"{tuple(getattr(scores, 'shape', ()))}")
+        if bool(torch.isnan(scores).any()):
+            raise ValueError("scores holds a NaN: the order of the walk would be undefined")
+    return x, scores, k, SELECT_BLOCK_ROWS if block_rows is None else block_rows
+
+
+def _revcomp(x):
+    return (3 - x).flip(1)
+
+
+def select_diverse(x, scores=None, k=None, min_dist=1, revcomp=False, block_rows=None):
+    """Greedy selection under a minimum distance: walk the rows of x [N, L] (tokens 0..3) from the highest score down
+    (equal scores: the lower index first; scores None: the given order) and pick a row when it is at least min_dist (1 .. L) away
+    from every row picked so far, until k rows are picked (None: no limit). The distance is the Hamming distance; with revcomp the
+    smaller of that and the distance to the reverse complement. -> Selection(picked, rep, rep_dist) on the device:
+      picked   i64 [P]  the picked rows in pick order
+      rep      i64 [N]  a row's representative: itself if it is picked, else the EARLIEST pick closer than min_dist, else -1 (a
+                        row that is far from every pick and came when k picks existed; never with k None)
+      rep_dist i32 [N]  the distance to the representative (0 for a pick, -1 where rep is -1)
+    min_dist = 1 removes exact duplicates. The first k picks of a run without limit are the run with k (the prefix property).
+    block_rows (1 .. 4096): the rows per block of the walk, a tuning knob only: every value gives the same result."""
+    x, scores, k, T = _check_select(x, scores, k, min_dist, block_rows)
+    x = _on_device(x, "x")
+    N, L = x.shape
+    dev = x.device
+    order = torch.arange(N, device=dev) if scores is None else torch.sort(scores.to(dev), descending=True, stable=True).indices
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    rows = ops.pack_tokens(x, err=err)[order].contiguous()
+    rows_rc = ops.pack_tokens(_revcomp(x).contiguous(), err=err)[order].contiguous() if revcomp else None
+    cap = N if k is None else min(k, N)
+    W = rows.shape[1]
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    reps = torch.empty((cap, W), dtype=torch.int32, device=dev)
+    picked_rank = torch.empty(cap, dtype=torch.int32, device=dev)
+    first = torch.full((N,), ops.FIRST_INIT, dtype=torch.int32, device=dev)
+    rep_pick = torch.empty(N, dtype=torch.int32, device=dev)
+    mask = torch.empty((min(T, N), (min(T, N) + 31) // 32), dtype=torch.int32, device=dev)
+    for r0 in range(0, N, T):                                     # no host synchronisation in here: the number of picks is `count`
+        r1 = min(r0 + T, N)
+        blk, blk_rc = rows[r0:r1], None if rows_rc is None else rows_rc[r0:r1]
+        if r0:
+            ops.within(blk, reps[:min(cap, r0)], L, min_dist - 1, q_rc=blk_rc, db_count=count, first=first[r0:r1])
+        ops.within(blk, blk, L, min_dist - 1, q_rc=blk_rc, mask=mask[:r1 - r0])
+        ops.greedy_pick(mask[:r1 - r0], first[r0:r1] if r0 else None, blk, L, r0, cap, count, reps, picked_rank, rep_pick[r0:r1])
+    ops.check_pack_err(err)
+    picked = order[picked_rank[:int(count[0])].long()]
+    rep = torch.empty(N, dtype=torch.int64, device=dev)
+    rep[order] = torch.where(rep_pick >= 0, picked[rep_pick.clamp(min=0).long()], torch.full_like(rep_pick, -1, dtype=torch.int64))
+    # a row against its ONE representative on the unpacked tokens: O(N L), not hot
+    rep_dist = torch.full((N,), -1, dtype=torch.int32, device=dev)
+    for c0 in range(0, N, 1 << 16):
+        r = rep[c0:c0 + (1 << 16)]
+        a, b = x[c0:c0 + (1 << 16)], x[r.clamp(min=0)]
+        d = (a != b).sum(1)
+        if revcomp:
+            d = torch.minimum(d, (_revcomp(a) != b).sum(1))
+        rep_dist[c0:c0 + (1 << 16)] = torch.where(r >= 0, d, torch.full_like(d, -1)).to(torch.int32)
+    return Selection(picked, rep, rep_dist)
+
+
+def _exact_mean(v):
+    """The correctly rounded mean of a float64 vector (math.fsum: independent of the order); NaN where +inf meets -inf."""
+    try:
+        return math.fsum(v.tolist()) / v.numel()
+    except (ValueError, OverflowError):
+        return float("nan")
+
+
+def _library(x, scores, k, min_dist, revcomp):
+    """One run without limit -> (its Selection, scores on the device, the report of library_quality)."""
+    if not isinstance(k, int) or isinstance(k, bool) or k < 1:
+        raise ValueError(f"k = {k!r}: expected an int >= 1")
+    if scores is None:
+        raise ValueError("scores = None: a library is chosen by score")
+    sel = select_diverse(x, scores, None, min_dist, revcomp)
+    picked, rep = sel.picked, sel.rep
+    N, P = rep.shape[0], picked.shape[0]
+    s = (torch.from_numpy(np.ascontiguousarray(scores)) if isinstance(scores, np.ndarray) else scores).to(picked.device).double()
+    n = min(k, P)
+    pick_no = torch.full((N,), -1, dtype=torch.int64, device=picked.device)
+    pick_no[picked] = torch.arange(P, device=picked.device)
+    rep_no = pick_no[rep]                                         # k None: every row has a representative
+    lib = s[picked[:n]]
+    report = {
+        "library_size": n,
+        "library_score_mean": _exact_mean(lib),
+        "library_score_min": float(lib.min()),
+        "topk_score_mean": _exact_mean(s.sort(descending=True).values[:n]),
+        "families": P,
+        "largest_family_fraction": int(torch.bincount(rep_no, minlength=P).max()) / N,
+        "library_family_coverage": int((rep_no < n).sum()) / N,
+    }
+    return sel, s, report
+
+
+def library_quality(x, scores, k, min_dist, revcomp=False):
+    """What a library of k designs chosen by select_diverse(x, scores, k, min_dist, revcomp) is worth -> a flat dict, from ONE run
+    without limit (its first k picks are the library, by the prefix property):
+      library_size              min(k, families)
+      library_score_mean / library_score_min   of the library's rows
+      topk_score_mean           the mean of the same number of rows taken by score alone: the price of diversity is the difference
+      families                  the picks of the run without limit: the distinct families the set holds at this min_dist
+      largest_family_fraction   the share of rows represented by the largest family's pick
+      library_family_coverage   the share of rows whose representative is in the library"""
+    return _library(x, scores, k, min_dist, revcomp)[2]
 
 
 # ------------------------------------------------------------------------------------------ host-level float64 rules ----
