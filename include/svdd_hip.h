@@ -417,6 +417,43 @@ int svdd_greedy_pick(const uint32_t* mask, int mask_words, const int32_t* first,
                      int32_t* count, uint32_t* reps, int32_t* picked_rank, int cap, int32_t* rep_pick, void* on_stream);
 
 /*
+ * Greedy selection under a minimum EDIT distance (added under ABI 17: two new entries, nothing existing changed; not in
+ * the reference). A design and its copy shifted by one base are far apart by Hamming distance and one edit from each other twice
+ * over; svdd_edit_within is the bit matrix svdd_greedy_pick needs by Levenshtein distance, svdd_edit_pairs the distance of chosen
+ * pairs. Integer arithmetic only; every output is exact and independent of the launch shape. The stream is explicit.
+ *
+ * svdd_edit_within: q [B, W] and db [N, W] packed u32 (svdd_pack_tokens) of ONE length L = 1 .. 1024, W = ceil(L / 16); the padding
+ *   bits of the last word are never read. d(i, j) = the Levenshtein distance of q_i and db_j (svdd_edit_nn's: substitution,
+ *   insertion and deletion cost 1 each, global) or, with both_strands != 0, the smaller of that and the distance of rc(q_i) and
+ *   db_j, rc(a)[l] = 3 - a[L - 1 - l]. The distance is unchanged when both rows are reversed and when both pass through one
+ *   bijection of the alphabet, so lev(rc(q), db) = lev(q, rc(db)): the kernel walks the staged database row backwards with every
+ *   token t read as 3 - t against the SAME four bit planes of the query, and only for the rows a lane of the wave did not hit on
+ *   the first strand; the caller passes no reverse complements. db_count: a device int32 or NULL; only the database rows
+ *   j < n = min(N, *db_count) exist (a count below 0 reads as 0); NULL: n = N. radius = 0 .. L - 1; a pair is a hit when
+ *   d <= radius. first [B] i32 or NULL, started by the caller at INT32_MAX or at any earlier value: first[i] = min(first[i], the
+ *   lowest j < n that is a hit) by integer atomic min; a query without a hit keeps its value. mask [B, mask_words] u32 or NULL,
+ *   mask_words >= ceil(N / 32): EVERY word of every row i < B is WRITTEN by a plain store (the caller need not zero it): bit
+ *   j % 32 of word j / 32 is set iff j < n and (i, j) is a hit; all other bits, the words at and beyond ceil(N / 32) and the
+ *   words of segments beyond the device count included, are zero. A thread keeps one query as four bit planes of ceil(L / 32)
+ *   <= 32 words (svdd_edit_nn's recurrence and its classes of 1, 2, 4, 7, 8, 16 and 32 words), a workgroup of 256 queries walks
+ *   a segment of the database in tiles of 64 rows staged in LDS, and the owning thread gathers 32 rows into one mask word. Every
+ *   16 columns a wave leaves a database row once the diagonal's lower bound exceeds the radius for all its lanes. The grid is
+ *   sized from N; a workgroup whose segment starts at or beyond n computes nothing (it stores its zero words of mask).
+ *   SVDD_E_ARG: B, N or L <= 0, L > 1024, radius outside 0 .. L - 1, a NULL q or db, neither output, mask with mask_words <
+ *   ceil(N / 32).
+ *
+ * svdd_edit_pairs: q [B, ceil(Lq / 16)] and db [N, ceil(Ld / 16)] packed u32, Lq and Ld 1 .. 1024 (they may differ); idx [B] i32.
+ *   dist [B] i32 is WRITTEN in full: dist[i] = the Levenshtein distance of q_i and db[idx[i]] (with both_strands != 0 the smaller
+ *   of that and the distance of rc(q_i) and db[idx[i]]), or -1 where idx[i] < 0, where idx[i] >= N (no row is read) or where the
+ *   distance exceeds cap = 0 .. max(Lq, Ld). One thread per pair, the plane chosen per lane: B pairs, not B N.
+ *   SVDD_E_ARG: B, N, Lq or Ld <= 0, Lq or Ld > 1024, cap outside 0 .. max(Lq, Ld), a NULL q, db, idx or dist.
+ */
+int svdd_edit_within(const uint32_t* q, const uint32_t* db, const int32_t* db_count, int B, int N, int L, int radius,
+                     int both_strands, int32_t* first, uint32_t* mask, int mask_words, void* on_stream);
+int svdd_edit_pairs(const uint32_t* q, const uint32_t* db, const int32_t* idx, int B, int N, int Lq, int Ld, int cap,
+                    int both_strands, int32_t* dist, void* on_stream);
+
+/*
  * PWM motif scanning (added under ABI 17: one new entry, nothing existing changed; not in the reference). Integer log-odds tables,
  * int32 sums and integer atomics only: every result is exact and independent of the launch shape and of how the caller cuts its
  * rows into chunks. The stream is explicit (as svdd_kmer_counts).

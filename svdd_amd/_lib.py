@@ -138,6 +138,8 @@ SIGNATURES = {
     "svdd_edit_nn": (vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp),
     "svdd_within": (vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp),
     "svdd_greedy_pick": (vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp),
+    "svdd_edit_within": (vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp),
+    "svdd_edit_pairs": (vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp),
     "svdd_motif_scan": (vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp),
     "svdd_motif_reward": (vp, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp),
     "svdd_candidate_parts": (vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp),

@@ -70,7 +70,7 @@ def build_parser(method="mc"):
                         "deletions), which the Hamming novelty cannot see: the share of designs with another design, and with a row "
                         "of `train`, within K edits, the smallest such distance, and the share the Hamming report misses: printed, "
                         "and saved as npz keys quality_<metric>")
-    p.add_argument("--select", type=int, default=argparse.SUPPRESS, metavar="K",         # the three --select* flags: absent unless given
+    p.add_argument("--select", type=int, default=argparse.SUPPRESS, metavar="K",         # the four --select* flags: absent unless given
                    help="also choose a library of the K best decoded sequences that are no near copies of each other: walk them "
                         "from the highest reward prediction down and keep one when it is at least --select_min_dist substitutions "
                         "from every sequence kept: one line printed, and saved as npz keys selected (tokens), selected_idx, "
@@ -80,6 +80,10 @@ def build_parser(method="mc"):
                         "duplicates)")
     p.add_argument("--select_revcomp", action="store_true", default=argparse.SUPPRESS,
                    help="with --select: a sequence is also a near copy of another's reverse complement")
+    p.add_argument("--select_metric", choices=("hamming", "edit"), default=argparse.SUPPRESS,
+                   help="with --select: what --select_min_dist counts. hamming (the default): substitutions. edit: substitutions, "
+                        "insertions and deletions, so that a sequence and its copy shifted by a few bases are near copies too; the "
+                        "same npz keys, and library_metric")
     p.add_argument("--guide_motifs", default=argparse.SUPPRESS, metavar="FILE.meme",     # the three --guide_* flags: absent unless given
                    help="--method tweedie only: decode towards (or away from) the motifs of FILE.meme, the reward net's score plus "
                         "a motif term (svdd_amd.motifs.MotifReward); give --guide_weights, --guide_margin or both")
@@ -107,7 +111,7 @@ _SELECT_NEEDS_K = "--{} needs --select K: the size of the library it shapes"
 def _eval_error(args):
     """What is wrong with the --eval_* and --select* flags of args, or None."""
     if not hasattr(args, "select"):
-        for flag in ("select_min_dist", "select_revcomp"):
+        for flag in ("select_min_dist", "select_revcomp", "select_metric"):
             if hasattr(args, flag):
                 return _SELECT_NEEDS_K.format(flag)
     if getattr(args, "eval_quality", None):
@@ -229,9 +233,12 @@ def run(args):
         extra.update({f"quality_{key}": np.float64(v) for key, v in report.items()})
     library = None
     if hasattr(args, "select"):
-        tokens, scores, idx, library = model.select_library(gen_samples, args.select, getattr(args, "select_min_dist", 1),
-                                                            revcomp=getattr(args, "select_revcomp", False))
+        edit = getattr(args, "select_metric", "hamming") == "edit"
+        tokens, scores, idx, library = (model.select_library_edit if edit else model.select_library)(
+            gen_samples, args.select, getattr(args, "select_min_dist", 1), revcomp=getattr(args, "select_revcomp", False))
         extra.update(selected=tokens.cpu().numpy(), selected_idx=idx.cpu().numpy(), selected_scores=scores.cpu().numpy())
+        if edit:
+            extra.update(library_metric=np.str_("edit"))
         extra.update({key if key.startswith("library_") else f"library_{key}": np.float64(v) for key, v in library.items()})
     np.savez(path, decoding=reward_model_preds.cpu().numpy(), baseline=baseline_preds.cpu().numpy(), **extra)
     print(f"wrote {path}.npz: decoding mean {reward_model_preds.mean().item():.4f} (n={reward_model_preds.numel()}), "

@@ -61,6 +61,7 @@ enum SvddProfileSlot {
   SVDD_SLOT_GRU_BPTT = 12,       // DPS: the GRU's back-propagation through time (svdd_gru_bidir_bwd[2]_f32)
   SVDD_SLOT_WITHIN = 13,         // svdd_within
   SVDD_SLOT_GREEDY_PICK = 14,    // svdd_greedy_pick
+  SVDD_SLOT_EDIT_WITHIN = 15,    // svdd_edit_within
   SVDD_SLOT_COUNT
 };
 

@@ -21,6 +21,10 @@
 //                      on the device
 //   svdd_greedy_pick   the serial walk of greedy selection over one block of rows, in one wave: the settled set lives in
 //                      registers, only the rows that are picked load their row of the bit matrix
+//   svdd_edit_within   svdd_edit_nn's skeleton with svdd_within's outputs: which database rows are within a Levenshtein
+//                      radius, on one strand or on both; the second strand walks the staged row backwards with complemented
+//                      tokens against the same planes
+//   svdd_edit_pairs    row i against ONE database row each: one thread per pair, the plane chosen per lane
 #include "svdd_host.h"
 
 namespace {
@@ -417,6 +421,183 @@ int launch_within(const WithinArgs& a, dim3 grid, void* on_stream) {
   return svdd_launch_timed(span.all(), k, grid, dim3(QB), 0, on_stream, a);
 }
 
+struct EditWithinArgs {
+  const uint32_t* q;
+  const uint32_t* db;
+  const int32_t* db_count;                   // device: only the rows j < min(N, *db_count) exist; NULL: all N
+  int B, N, L, W, radius, both, seg_rows, mask_words;
+  int32_t* first;
+  uint32_t* mask;
+};
+
+// One staged database row (W packed words in LDS, every lane at one address) against the lane's query planes: edit_nn_kernel's
+// row walk with ONE limit for the whole wave. REV: the row is walked from its last token to its first and every token t is read
+// as 3 - t, which is the walk over the row's reverse complement; lev(rc(q), row) = lev(q, rc(row)) (reversing both strings, and
+// passing both through one bijection of the alphabet, leaves the distance as it is), so the second strand needs no second set of
+// planes. At every packed word (16 columns) the wave leaves the row when the diagonal bound of every lane that still `need`s the
+// row is beyond the limit -> true, and score means nothing; false: score is the distance. Nothing here differs between lanes but
+// the planes: the token is scalar, the plane is chosen by a scalar branch, `rest` is scalar.
+template <int WT, bool REV>
+__device__ __forceinline__ bool edit_row_walk(const uint32_t (&eA)[WT], const uint32_t (&eC)[WT], const uint32_t (&eG)[WT],
+                                              const uint32_t (&eT)[WT], const uint32_t* row, int L, int W, bool need, int limit,
+                                              int& score) {
+  uint32_t Pv[WT], Mv[WT];
+#pragma unroll
+  for (int w = 0; w < WT; ++w) Pv[w] = eA[w] | eC[w] | eG[w] | eT[w], Mv[w] = 0u;
+  for (int c = 0; c < W; ++c) {
+    const int w = REV ? W - 1 - c : c;
+    uint32_t word = __builtin_amdgcn_readfirstlane(row[w]);
+    const int nj = min(16, L - 16 * w);
+    if (REV) word <<= 2 * (16 - nj);                                // the word's last token to the top; the padding bits fall out
+    for (int jj = 0; jj < nj; ++jj) {
+      const uint32_t t = REV ? 3u - (word >> 30) : word & 3u;
+      word = REV ? word << 2 : word >> 2;
+      switch (t) {
+        case 0: edit_column<WT>(eA, Pv, Mv, score); break;
+        case 1: edit_column<WT>(eC, Pv, Mv, score); break;
+        case 2: edit_column<WT>(eG, Pv, Mv, score); break;
+        default: edit_column<WT>(eT, Pv, Mv, score); break;
+      }
+    }
+    const int rest = REV ? 16 * w : L - 16 * w - nj;                // columns still to come
+    if (rest > 0 && __all(!need || edit_diagonal<WT>(Pv, Mv, score, rest) > limit)) return true;
+  }
+  return false;
+}
+
+// grid (ceil(B / QB), segments of seg_rows database rows, seg_rows a multiple of ED_TILE). edit_nn_kernel's skeleton (a thread owns
+// one query as four bit planes at the top of 32 WT bits; 256 queries walk a segment in LDS tiles of 64 rows) with within_kernel's
+// outputs: a tile is two mask words, the owning thread gathers 32 rows into a register and stores the word; the words of the
+// segment that no live tile covers are stored as zeros; first takes one integer atomic min per query that has a hit. The limit of
+// every lane is the radius. With both strands the row is walked a second time (edit_row_walk<REV>) only when a lane of the wave
+// did not hit on the first.
+template <int WT>
+__global__ __launch_bounds__(QB) void edit_within_kernel(EditWithinArgs a) {
+  __shared__ uint32_t tile[ED_TILE * ED_MAXW];
+  const int qi = blockIdx.x * QB + threadIdx.x;
+  const bool live = qi < a.B;
+  const int n = a.db_count ? max(0, min(a.N, *a.db_count)) : a.N;   // one address for the whole grid: a scalar load
+  const long long seg_lo = (long long)blockIdx.y * a.seg_rows;     // < N: the host sizes the grid from N
+  const bool last_seg = blockIdx.y == gridDim.y - 1;
+  const int word_lo = (int)(seg_lo / 32);
+  const int word_hi = last_seg ? a.mask_words : (int)((seg_lo + a.seg_rows) / 32);    // <= ceil(N / 32) <= mask_words otherwise
+  uint32_t* mrow = a.mask && live ? a.mask + (long long)qi * a.mask_words : nullptr;
+  const int seg0 = (int)min(seg_lo, (long long)n);
+  const int seg1 = (int)min(seg_lo + a.seg_rows, (long long)n);
+  if (seg0 >= seg1) {                                              // the segment starts at or beyond the device count
+    if (mrow)
+      for (int w = word_lo; w < word_hi; ++w) mrow[w] = 0u;
+    return;
+  }
+  const int m = a.L, off = 32 * WT - m;
+  uint32_t eA[WT], eC[WT], eG[WT], eT[WT];
+#pragma unroll
+  for (int w = 0; w < WT; ++w) {
+    uint32_t pa = 0, pc = 0, pg = 0, pt = 0;
+    if (live && 32 * (w + 1) > off) {
+      const uint32_t* row = a.q + (long long)qi * a.W;
+      for (int b = max(0, off - 32 * w); b < 32; ++b) {
+        const int i = 32 * w + b - off;                              // 0 <= i < m: the padding bits of the row are never read
+        const uint32_t t = (row[i >> 4] >> (2 * (i & 15))) & 3u;
+        const uint32_t bit = 1u << b;
+        pa |= t == 0u ? bit : 0u;
+        pc |= t == 1u ? bit : 0u;
+        pg |= t == 2u ? bit : 0u;
+        pt |= t == 3u ? bit : 0u;
+      }
+    }
+    eA[w] = pa, eC[w] = pc, eG[w] = pg, eT[w] = pt;
+  }
+  int hit = INT32_MAX;
+  int word = word_lo;                                              // the next mask word this thread stores
+  for (int t0 = seg0; t0 < seg1; t0 += ED_TILE) {
+    const int nr = min(ED_TILE, seg1 - t0);
+    __syncthreads();                                              // the previous tile is read
+    for (int i = threadIdx.x; i < nr * a.W; i += QB) tile[i] = a.db[(long long)t0 * a.W + i];
+    __syncthreads();
+    for (int half = 0; half < ED_TILE / 32; ++half) {
+      uint32_t bits = 0;
+      const int r1 = min(32, nr - 32 * half);
+      for (int r = 0; r < r1; ++r) {
+        const uint32_t* row = &tile[(32 * half + r) * a.W];
+        int score = m;
+        bool in = !edit_row_walk<WT, false>(eA, eC, eG, eT, row, a.L, a.W, live, a.radius, score) && score <= a.radius;
+        if (a.both && __any(live && !in)) {
+          score = m;
+          in = in || (!edit_row_walk<WT, true>(eA, eC, eG, eT, row, a.L, a.W, live && !in, a.radius, score) && score <= a.radius);
+        }
+        if (live && in) {
+          bits |= 1u << r;
+          hit = min(hit, t0 + 32 * half + r);
+        }
+      }
+      if (mrow && word < word_hi) mrow[word] = bits;
+      ++word;
+    }
+  }
+  if (mrow)
+    for (; word < word_hi; ++word) mrow[word] = 0u;
+  if (live && a.first && hit != INT32_MAX) atomicMin(&a.first[qi], hit);
+}
+
+struct EditPairsArgs {
+  const uint32_t* q;
+  const uint32_t* db;
+  const int32_t* idx;
+  int B, N, Lq, Ld, Wq, Wd, cap, both;
+  int32_t* dist;
+};
+
+// One thread per pair (q_i, db[idx[i]]): the same planes and the same column step, but every lane has a database row of its own,
+// so the plane is chosen per lane by selects and the row's words are read from global memory as they are needed. B pairs, not
+// B N: this is not a hot path. The second strand as in edit_row_walk: the row backwards, every token t read as 3 - t.
+template <int WT>
+__global__ __launch_bounds__(64) void edit_pairs_kernel(EditPairsArgs a) {
+  const int qi = blockIdx.x * 64 + threadIdx.x;
+  if (qi >= a.B) return;
+  const int j = a.idx[qi];
+  if (j < 0 || j >= a.N) {
+    a.dist[qi] = -1;
+    return;
+  }
+  const int m = a.Lq, off = 32 * WT - m;
+  const uint32_t* qrow = a.q + (long long)qi * a.Wq;
+  const uint32_t* row = a.db + (long long)j * a.Wd;
+  uint32_t eA[WT], eC[WT], eG[WT], eT[WT];
+#pragma unroll
+  for (int w = 0; w < WT; ++w) {
+    uint32_t pa = 0, pc = 0, pg = 0, pt = 0;
+    for (int b = max(0, off - 32 * w); b < 32; ++b) {
+      const int i = 32 * w + b - off;                                // 0 <= i < m: the padding bits of the row are never read
+      const uint32_t t = (qrow[i >> 4] >> (2 * (i & 15))) & 3u;
+      const uint32_t bit = 1u << b;
+      pa |= t == 0u ? bit : 0u;
+      pc |= t == 1u ? bit : 0u;
+      pg |= t == 2u ? bit : 0u;
+      pt |= t == 3u ? bit : 0u;
+    }
+    eA[w] = pa, eC[w] = pc, eG[w] = pg, eT[w] = pt;
+  }
+  int best = INT32_MAX;
+  for (int strand = 0; strand < (a.both ? 2 : 1); ++strand) {
+    uint32_t Pv[WT], Mv[WT];
+#pragma unroll
+    for (int w = 0; w < WT; ++w) Pv[w] = eA[w] | eC[w] | eG[w] | eT[w], Mv[w] = 0u;
+    int score = m;
+    for (int c = 0; c < a.Ld; ++c) {
+      const int l = strand ? a.Ld - 1 - c : c;
+      uint32_t t = (row[l >> 4] >> (2 * (l & 15))) & 3u;
+      if (strand) t = 3u - t;
+      uint32_t eq[WT];
+#pragma unroll
+      for (int w = 0; w < WT; ++w) eq[w] = t == 0u ? eA[w] : t == 1u ? eC[w] : t == 2u ? eG[w] : eT[w];
+      edit_column<WT>(eq, Pv, Mv, score);
+    }
+    best = min(best, score);
+  }
+  a.dist[qi] = best <= a.cap ? best : -1;
+}
+
 constexpr int GP_MAXT = 4096;              // rows of one greedy_pick block: 128 words of the suppressed set, two per lane
 constexpr int GP_WAVE = 64;
 
@@ -567,6 +748,38 @@ int svdd_within(const uint32_t* q, const uint32_t* q_rc, const uint32_t* db, con
   const uint32_t last_mask = L % 16 ? (1u << (2 * (L % 16))) - 1u : 0xFFFFFFFFu;
   const WithinArgs a{q, q_rc, db, db_count, B, N, W, radius, (int)seg, mask ? mask_words : 0, last_mask, first, mask};
   return q_rc ? launch_within<true>(a, dim3(gx, gy), on_stream) : launch_within<false>(a, dim3(gx, gy), on_stream);
+}
+
+int svdd_edit_within(const uint32_t* q, const uint32_t* db, const int32_t* db_count, int B, int N, int L, int radius,
+                     int both_strands, int32_t* first, uint32_t* mask, int mask_words, void* on_stream) {
+  if (!q || !db || (!first && !mask) || B <= 0 || N <= 0 || L <= 0 || L > HM_MAXL || radius < 0 || radius >= L) return SVDD_E_ARG;
+  if (mask && (long long)mask_words * 32 < N) return SVDD_E_ARG;
+  const unsigned gx = (unsigned)((B + QB - 1) / QB);
+  // segments as svdd_edit_nn's (a pair costs thousands of times a Hamming pair: about 4096 workgroups in all), whole tiles (so
+  // whole mask words), sized from N, the host's upper bound of the device count
+  const long long want = (4096 + gx - 1) / gx;
+  long long seg = ((long long)N + want - 1) / want;
+  seg = (seg + ED_TILE - 1) / ED_TILE * ED_TILE;
+  const unsigned gy = (unsigned)(((long long)N + seg - 1) / seg);
+  const EditWithinArgs a{q, db, db_count, B, N, L, (L + 15) / 16, radius, both_strands != 0, (int)seg, mask ? mask_words : 0, first, mask};
+  const int W = (L + 31) / 32;
+  void (*k)(EditWithinArgs) = W <= 1 ? edit_within_kernel<1> : W <= 2 ? edit_within_kernel<2> : W <= 4 ? edit_within_kernel<4>
+                            : W <= 7 ? edit_within_kernel<7> : W <= 8 ? edit_within_kernel<8> : W <= 16 ? edit_within_kernel<16>
+                            : edit_within_kernel<32>;
+  SvddSpan span(SVDD_SLOT_EDIT_WITHIN);
+  return svdd_launch_timed(span.all(), k, dim3(gx, gy), dim3(QB), 0, on_stream, a);
+}
+
+int svdd_edit_pairs(const uint32_t* q, const uint32_t* db, const int32_t* idx, int B, int N, int Lq, int Ld, int cap,
+                    int both_strands, int32_t* dist, void* on_stream) {
+  if (!q || !db || !idx || !dist || B <= 0 || N <= 0 || Lq <= 0 || Ld <= 0 || Lq > HM_MAXL || Ld > HM_MAXL) return SVDD_E_ARG;
+  if (cap < 0 || cap > (Lq > Ld ? Lq : Ld)) return SVDD_E_ARG;
+  const EditPairsArgs a{q, db, idx, B, N, Lq, Ld, (Lq + 15) / 16, (Ld + 15) / 16, cap, both_strands != 0, dist};
+  const int W = (Lq + 31) / 32;
+  void (*k)(EditPairsArgs) = W <= 1 ? edit_pairs_kernel<1> : W <= 2 ? edit_pairs_kernel<2> : W <= 4 ? edit_pairs_kernel<4>
+                           : W <= 7 ? edit_pairs_kernel<7> : W <= 8 ? edit_pairs_kernel<8> : W <= 16 ? edit_pairs_kernel<16>
+                           : edit_pairs_kernel<32>;
+  return svdd_launch(k, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, on_stream, a);
 }
 
 int svdd_greedy_pick(const uint32_t* mask, int mask_words, const int32_t* first, const uint32_t* rows, int T, int L, int base, int k,

@@ -312,6 +312,19 @@ class BaseModel(nn.Module):
         idx the kept rows of `samples` in pick order, report the flat dict of quality.library_quality. The scores are the
         harness's reward model's, task 0, as evaluate_quality computes them. `samples` as in evaluate_nll."""
         from . import quality
+        return self._select_library(samples, k, min_dist, revcomp, quality.select_diverse)
+
+    @torch.no_grad()
+    def select_library_edit(self, samples, k, min_dist, revcomp=False):
+        """select_library under a minimum EDIT distance (svdd_amd.quality.select_diverse_edit): a design is kept when it
+        is at least min_dist edits (substitution, insertion, deletion) from every design kept, so a design and its copy shifted by
+        a base or two are one family -> (tokens [P, L], scores [P], idx [P], report), report the flat dict of
+        quality.library_quality_edit."""
+        from . import quality
+        return self._select_library(samples, k, min_dist, revcomp, quality.select_diverse_edit)
+
+    def _select_library(self, samples, k, min_dist, revcomp, select):
+        from . import quality
         dev = self.ref_model.device
         if isinstance(samples, (list, tuple)):
             samples = torch.cat([torch.as_tensor(s).reshape(-1, s.shape[-1]).to(dev) for s in samples])
@@ -319,7 +332,7 @@ class BaseModel(nn.Module):
         n = self.NUM_SAMPLES_PER_BATCH
         pred = torch.cat([self._reward(samples[i:i + n].long()) for i in range(0, samples.shape[0], n)])
         scores = (pred if self.n_tasks == 1 else pred[:, 0]).reshape(-1).float()
-        sel, _, report = quality._library(samples, scores, k, min_dist, revcomp)
+        sel, _, report = quality._library(samples, scores, k, min_dist, revcomp, select)
         idx = sel.picked[:k]
         return samples[idx], scores[idx], idx, report
 

@@ -619,6 +619,58 @@ def greedy_pick(mask, first, rows, L, base, k, count, reps, picked_rank, rep_pic
     return rep_pick
 
 
+def edit_within(q, db, L, radius, both_strands=False, db_count=None, first=None, mask=None):
+    """svdd_edit_within on packed rows (pack_tokens) of one length: q int32 [B, W], db int32 [N, W], W = ceil(L / 16). A pair is a
+    hit when its Levenshtein distance (with both_strands: the smaller of that and the distance of the query's reverse complement)
+    is <= radius (0 .. L - 1). db_count, first and mask as for within: db_count int32 [1] on the device (or None): only the rows
+    j < min(N, db_count) exist; first int32 [B] (or None), started by the caller at FIRST_INIT, is lowered to the lowest hit; mask
+    int32 [B, mask_words] (or None), mask_words >= ceil(N / 32), is WRITTEN in full: bit j of row i = (i, j) is a hit."""
+    L = _int_in(L, 1, PACK_MAX_L, "edit_within: L")
+    radius = _int_in(radius, 0, L - 1, "edit_within: radius")
+    W = packed_words(L)
+    _need(q, torch.int32, "q"), _need(db, torch.int32, "db")
+    if q.dim() != 2 or db.dim() != 2 or q.shape[1] != W or db.shape[1] != W or not q.is_contiguous() or not db.is_contiguous() \
+            or q.shape[0] == 0 or db.shape[0] == 0:
+        raise SvddError(f"edit_within: q and db must be contiguous non-empty int32 [*, {W}] tensors, got {tuple(q.shape)} and "
+                        f"{tuple(db.shape)}")
+    B, N = q.shape[0], db.shape[0]
+    if db_count is not None:
+        _is(db_count, torch.int32, (1,), "db_count")
+    if first is None and mask is None:
+        raise SvddError("edit_within: give first, mask or both")
+    if first is not None:
+        _is(first, torch.int32, (B,), "first")
+    mask_words = 0
+    if mask is not None:
+        _need(mask, torch.int32, "mask")
+        if mask.dim() != 2 or mask.shape[0] != B or mask.shape[1] * 32 < N or not mask.is_contiguous():
+            raise SvddError(f"edit_within: mask must be a contiguous int32 [{B}, >= {(N + 31) // 32}] tensor, got {tuple(mask.shape)}")
+        mask_words = mask.shape[1]
+    _lib.call("svdd_edit_within", q, db, db_count, B, N, L, radius, int(bool(both_strands)), first, mask, mask_words, _this_stream())
+    return first, mask
+
+
+def edit_pairs(q, db, idx, Lq, Ld, cap, both_strands=False, dist=None):
+    """svdd_edit_pairs on packed rows (pack_tokens): q int32 [B, ceil(Lq / 16)], db int32 [N, ceil(Ld / 16)], idx int32 [B] -> dist
+    int32 [B], WRITTEN in full: the Levenshtein distance of q's row i and db's row idx[i] (with both_strands: the smaller of that
+    and the distance of the query's reverse complement), -1 where idx[i] is outside 0 .. N - 1 or the distance exceeds cap
+    (0 .. max(Lq, Ld))."""
+    Lq = _int_in(Lq, 1, PACK_MAX_L, "edit_pairs: Lq")
+    Ld = _int_in(Ld, 1, PACK_MAX_L, "edit_pairs: Ld")
+    cap = _int_in(cap, 0, max(Lq, Ld), "edit_pairs: cap")
+    Wq, Wd = packed_words(Lq), packed_words(Ld)
+    _need(q, torch.int32, "q"), _need(db, torch.int32, "db")
+    if q.dim() != 2 or db.dim() != 2 or q.shape[1] != Wq or db.shape[1] != Wd or not q.is_contiguous() or not db.is_contiguous() \
+            or q.shape[0] == 0 or db.shape[0] == 0:
+        raise SvddError(f"edit_pairs: q and db must be contiguous non-empty int32 [*, {Wq}] and [*, {Wd}] tensors, got "
+                        f"{tuple(q.shape)} and {tuple(db.shape)}")
+    B, N = q.shape[0], db.shape[0]
+    _is(idx, torch.int32, (B,), "idx")
+    dist = torch.empty(B, dtype=torch.int32, device=q.device) if dist is None else _is(dist, torch.int32, (B,), "dist")
+    _lib.call("svdd_edit_pairs", q, db, idx, B, N, Lq, Ld, cap, int(bool(both_strands)), dist, _this_stream())
+    return dist
+
+
 MOTIF_MAX_W = 32                                                      # svdd_motif_scan (include/svdd_hip.h)
 
 

@@ -11,6 +11,9 @@ standard companions of a reward table that it does not have, diversity and novel
                                     Hamming distance cannot see (a shifted training row)
   select_diverse / library_quality  greedy selection under a minimum Hamming distance (svdd_within, svdd_greedy_pick): the
                                     best rows that are no near copies of each other, and the families of the set
+  select_diverse_edit / library_quality_edit / edit_distance
+                                    the same selection under a minimum EDIT distance (svdd_edit_within, svdd_edit_pairs):
+                                    a design and its shifted copy are one family; and the row-wise Levenshtein distance
   wasserstein_1d / frechet_distance host-level float64 (torch), no kernel
   sample_quality                    the flat report
 
@@ -29,6 +32,7 @@ HAMMING_CHUNK_ROWS = 1 << 20             # database rows per svdd_hamming_nn cal
 EDIT_CHUNK_ROWS = 1 << 20                # database rows per svdd_edit_nn call (likewise)
 KMER_CHUNK_ROWS = 1 << 22
 SELECT_BLOCK_ROWS = 4096                 # rows per block of select_diverse's walk (likewise; measured in profiles/select_time.txt)
+SELECT_EDIT_BLOCK_ROWS = 4096            # ... of select_diverse_edit's (likewise; measured in profiles/select_edit_time.txt)
 
 
 def _checked(x, name, max_token):
@@ -285,6 +289,41 @@ def _revcomp(x):
     return (3 - x).flip(1)
 
 
+def _greedy_walk(x, scores, k, T, hits_of):
+    """The walk that both metrics share: rank the rows, pack them, and per block of T rows in rank order mark the rows that an
+    earlier block's pick settles (`first`), build the block's own bit matrix, and let svdd_greedy_pick walk it.
+    hits_of(order, rows, err), rows = the packed rows in rank order -> hits(r0, r1, db, **outputs): the metric's within-radius
+    kernel with the ranked rows r0 .. r1 as queries (db_count / first / mask as ops.within's).
+    -> (packed rows in the GIVEN order, picked i64 [P], rep i64 [N])."""
+    N, L = x.shape
+    dev = x.device
+    order = torch.arange(N, device=dev) if scores is None else torch.sort(scores.to(dev), descending=True, stable=True).indices
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    packed = ops.pack_tokens(x, err=err)
+    rows = packed[order].contiguous()
+    hits = hits_of(order, rows, err)
+    cap = N if k is None else min(k, N)
+    W = rows.shape[1]
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    reps = torch.empty((cap, W), dtype=torch.int32, device=dev)
+    picked_rank = torch.empty(cap, dtype=torch.int32, device=dev)
+    first = torch.full((N,), ops.FIRST_INIT, dtype=torch.int32, device=dev)
+    rep_pick = torch.empty(N, dtype=torch.int32, device=dev)
+    mask = torch.empty((min(T, N), (min(T, N) + 31) // 32), dtype=torch.int32, device=dev)
+    for r0 in range(0, N, T):                                     # no host synchronisation in here: the number of picks is `count`
+        r1 = min(r0 + T, N)
+        blk = rows[r0:r1]
+        if r0:
+            hits(r0, r1, reps[:min(cap, r0)], db_count=count, first=first[r0:r1])
+        hits(r0, r1, blk, mask=mask[:r1 - r0])
+        ops.greedy_pick(mask[:r1 - r0], first[r0:r1] if r0 else None, blk, L, r0, cap, count, reps, picked_rank, rep_pick[r0:r1])
+    ops.check_pack_err(err)
+    picked = order[picked_rank[:int(count[0])].long()]
+    rep = torch.empty(N, dtype=torch.int64, device=dev)
+    rep[order] = torch.where(rep_pick >= 0, picked[rep_pick.clamp(min=0).long()], torch.full_like(rep_pick, -1, dtype=torch.int64))
+    return packed, picked, rep
+
+
 def select_diverse(x, scores=None, k=None, min_dist=1, revcomp=False, block_rows=None):
     """Greedy selection under a minimum distance: walk the rows of x [N, L] (tokens 0..3) from the highest score down
     (equal scores: the lower index first; scores None: the given order) and pick a row when it is at least min_dist (1 .. L) away
@@ -300,29 +339,12 @@ def select_diverse(x, scores=None, k=None, min_dist=1, revcomp=False, block_rows
     x = _on_device(x, "x")
     N, L = x.shape
     dev = x.device
-    order = torch.arange(N, device=dev) if scores is None else torch.sort(scores.to(dev), descending=True, stable=True).indices
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    rows = ops.pack_tokens(x, err=err)[order].contiguous()
-    rows_rc = ops.pack_tokens(_revcomp(x).contiguous(), err=err)[order].contiguous() if revcomp else None
-    cap = N if k is None else min(k, N)
-    W = rows.shape[1]
-    count = torch.zeros(1, dtype=torch.int32, device=dev)
-    reps = torch.empty((cap, W), dtype=torch.int32, device=dev)
-    picked_rank = torch.empty(cap, dtype=torch.int32, device=dev)
-    first = torch.full((N,), ops.FIRST_INIT, dtype=torch.int32, device=dev)
-    rep_pick = torch.empty(N, dtype=torch.int32, device=dev)
-    mask = torch.empty((min(T, N), (min(T, N) + 31) // 32), dtype=torch.int32, device=dev)
-    for r0 in range(0, N, T):                                     # no host synchronisation in here: the number of picks is `count`
-        r1 = min(r0 + T, N)
-        blk, blk_rc = rows[r0:r1], None if rows_rc is None else rows_rc[r0:r1]
-        if r0:
-            ops.within(blk, reps[:min(cap, r0)], L, min_dist - 1, q_rc=blk_rc, db_count=count, first=first[r0:r1])
-        ops.within(blk, blk, L, min_dist - 1, q_rc=blk_rc, mask=mask[:r1 - r0])
-        ops.greedy_pick(mask[:r1 - r0], first[r0:r1] if r0 else None, blk, L, r0, cap, count, reps, picked_rank, rep_pick[r0:r1])
-    ops.check_pack_err(err)
-    picked = order[picked_rank[:int(count[0])].long()]
-    rep = torch.empty(N, dtype=torch.int64, device=dev)
-    rep[order] = torch.where(rep_pick >= 0, picked[rep_pick.clamp(min=0).long()], torch.full_like(rep_pick, -1, dtype=torch.int64))
+
+    def hits_of(order, rows, err):
+        rows_rc = ops.pack_tokens(_revcomp(x).contiguous(), err=err)[order].contiguous() if revcomp else None
+        return lambda r0, r1, db, **out: ops.within(rows[r0:r1], db, L, min_dist - 1,
+                                                    q_rc=None if rows_rc is None else rows_rc[r0:r1], **out)
+    _, picked, rep = _greedy_walk(x, scores, k, T, hits_of)
     # a row against its ONE representative on the unpacked tokens: O(N L), not hot
     rep_dist = torch.full((N,), -1, dtype=torch.int32, device=dev)
     for c0 in range(0, N, 1 << 16):
@@ -335,6 +357,27 @@ def select_diverse(x, scores=None, k=None, min_dist=1, revcomp=False, block_rows
     return Selection(picked, rep, rep_dist)
 
 
+def select_diverse_edit(x, scores=None, k=None, min_dist=1, revcomp=False, block_rows=None):
+    """select_diverse under a minimum EDIT distance: the same walk, the same Selection(picked, rep, rep_dist), the same
+    tie rules and prefix property, with the Levenshtein distance (substitution, insertion, deletion: 1 each; global) in place of
+    the Hamming distance; with revcomp the smaller of that and the edit distance to the reverse complement. min_dist is 1 .. L
+    edits: a row and its copy shifted by one base are 2 edits apart, and 0.75 L apart for select_diverse. rep_dist is the edit
+    distance to the representative. min_dist = 1 is select_diverse's (distance 0 means equal rows). block_rows (1 .. 4096; None:
+    SELECT_EDIT_BLOCK_ROWS): a tuning knob only."""
+    x, scores, k, T = _check_select(x, scores, k, min_dist, block_rows)
+    if block_rows is None:
+        T = SELECT_EDIT_BLOCK_ROWS
+    x = _on_device(x, "x")
+    N, L = x.shape
+
+    def hits_of(order, rows, err):
+        return lambda r0, r1, db, **out: ops.edit_within(rows[r0:r1], db, L, min_dist - 1, both_strands=revcomp, **out)
+    packed, picked, rep = _greedy_walk(x, scores, k, T, hits_of)
+    # a row against its ONE representative: N pairs (svdd_edit_pairs), -1 where there is none
+    rep_dist = ops.edit_pairs(packed, packed, rep.to(torch.int32), L, L, L, both_strands=revcomp)
+    return Selection(picked, rep, rep_dist)
+
+
 def _exact_mean(v):
     """The correctly rounded mean of a float64 vector (math.fsum: independent of the order); NaN where +inf meets -inf."""
     try:
@@ -343,13 +386,32 @@ def _exact_mean(v):
         return float("nan")
 
 
-def _library(x, scores, k, min_dist, revcomp):
-    """One run without limit -> (its Selection, scores on the device, the report of library_quality)."""
+def edit_distance(a, b, cap=None, revcomp=False):
+    """Row i of a [B, La] against row i of b [B, Lb] (tokens 0..3; the two lengths may differ) -> int32 [B] on the device: the
+    Levenshtein distance (substitution, insertion, deletion: 1 each; global), with revcomp the smaller of that and the distance
+    of a's reverse complement; -1 where it exceeds cap (0 .. max(La, Lb); None: no limit)."""
+    a, b = _checked(a, "a", 3), _checked(b, "b", 3)
+    if a.shape[0] != b.shape[0]:
+        raise ValueError(f"a and b must have one number of rows, got {a.shape[0]} and {b.shape[0]}")
+    La, Lb = a.shape[1], b.shape[1]
+    if max(La, Lb) > ops.PACK_MAX_L:
+        raise ValueError(f"L = {max(La, Lb)} > {ops.PACK_MAX_L}")
+    cap = _check_cap(cap, La, Lb)
+    a, b = _on_device(a, "a"), _on_device(b, "b")
+    err = torch.zeros(1, dtype=torch.int32, device=a.device)
+    q, d = ops.pack_tokens(a, err=err), ops.pack_tokens(b, err=err)
+    dist = ops.edit_pairs(q, d, torch.arange(a.shape[0], dtype=torch.int32, device=a.device), La, Lb, cap, both_strands=revcomp)
+    ops.check_pack_err(err)
+    return dist
+
+
+def _library(x, scores, k, min_dist, revcomp, select=select_diverse):
+    """One run of `select` without limit -> (its Selection, scores on the device, the report of library_quality)."""
     if not isinstance(k, int) or isinstance(k, bool) or k < 1:
         raise ValueError(f"k = {k!r}: expected an int >= 1")
     if scores is None:
         raise ValueError("scores = None: a library is chosen by score")
-    sel = select_diverse(x, scores, None, min_dist, revcomp)
+    sel = select(x, scores, None, min_dist, revcomp)
     picked, rep = sel.picked, sel.rep
     N, P = rep.shape[0], picked.shape[0]
     s = (torch.from_numpy(np.ascontiguousarray(scores)) if isinstance(scores, np.ndarray) else scores).to(picked.device).double()
@@ -380,6 +442,12 @@ def library_quality(x, scores, k, min_dist, revcomp=False):
       largest_family_fraction   the share of rows represented by the largest family's pick
       library_family_coverage   the share of rows whose representative is in the library"""
     return _library(x, scores, k, min_dist, revcomp)[2]
+
+
+def library_quality_edit(x, scores, k, min_dist, revcomp=False):
+    """library_quality of a library chosen by select_diverse_edit(x, scores, k, min_dist, revcomp): the same seven keys from ONE
+    run without limit, families and coverage counted by edit distance (a design and its shifted copy are one family)."""
+    return _library(x, scores, k, min_dist, revcomp, select_diverse_edit)[2]
 
 
 # ------------------------------------------------------------------------------------------ host-level float64 rules ----
