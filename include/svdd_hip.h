@@ -320,6 +320,70 @@ int svdd_attr_fold(const float* grad, float scale, const float* weight, const ui
                    int B, int L, int S, int r0, int n_rows, int mode, float* acc, float* attr, float* rowsum, void* on_stream);
 
 /*
+ * Ledidi gradient-based sequence design (added under ABI 17: one new entry, nothing existing changed): editing of given sequences
+ * through a Gumbel-softmax relaxation (reference design.py ledidi; the `ledidi` package's Ledidi.forward / fit_transform). The
+ * boundary kernel around an unchanged scoring pass and an unchanged input-gradient pass. Designs are independent: design d of B
+ * has S samples, weights w / AdamW moments m, v [B, L, 4] f32 (channels last), and best-so-far state. The stream is explicit.
+ *
+ * svdd_ledidi_step: ONE launch per iteration boundary and chunk of designs d0 .. d0 + nd - 1 (one workgroup per design, a thread
+ *   owns a position; L > 256 strides). With grad given it closes iteration `iter` (losses, bookkeeping, update) and, sample != 0,
+ *   draws the samples of iteration iter + 1; with grad NULL (the first launch) it only draws the samples of iteration `iter`.
+ *   Arrays indexed by the design are whole-batch arrays ([B, ...], indexed by d); grad and xin belong to the chunk's pass (row
+ *   (d - d0) * S + s). A design with stopped[d] != 0 at entry is left alone entirely: nothing of it is read or written.
+ *
+ *   losses (iteration iter; sc [B, S] f32 = the scores of tok, edits [B, S] i32 = what the sampling launch left):
+ *     out = -((sum_s sc) / S), or with target [B] f32 non-NULL (sum_s (sc - target)^2) / S; the sum sequential in ascending s from 0
+ *     inp = float(sum_s edits) / float(S)            total = out + l * inp                    (one rounding per operation)
+ *   bookkeeping (the caller starts best_total / best_output from the same formula on S copies of the start score, with a
+ *     correctly rounded division, so that an
+ *     iteration without an edit ties with it): total < best_total[d] (strictly; a NaN never): best_total / best_output / best_input = total / out / inp,
+ *     best_iter = iter, x_best[d] = tok[d] (all S rows, [B, S, L] u8), score_best[d] = sc[d] ([B, S]), wo[d] = 0. Otherwise
+ *     wo[d] += 1 and, wo[d] == cfg->patience, stopped[d] = 1 and live[0] -= 1 (integer atomic; live: one device word the caller
+ *     set to the number of live designs). trace_total / trace_out / trace_in [B] f32 (each may be NULL): this iteration's three.
+ *   update (editable positions; editable [L] u8 or NULL = all), per position, for s ascending, c = 0..3:
+ *     G_c   = coef_s * (scale * grad[s, c]) + pen_c       coef_s = -(1 / S), or with a target (2 (sc_s - target)) / S
+ *             pen_c = +lam at the sample's base where it differs from x0's, -lam at x0's base there, 0 otherwise; lam = l / (2 S)
+ *     dot   = ((y_0 G_0 + y_1 G_1) + y_2 G_2) + y_3 G_3                                        (y [B, S, L, 4]: the samples' softmax)
+ *     gw_c  = gw_c + ((1 / tau) * y_c) * (G_c - dot)                                           (from 0)
+ *     then AdamW: w = w * decay; m = m + w1 * (gw - m); v = v * beta2 + (w2 * gw) * gw;
+ *                 w = w - (step_size * m) / (sqrt(v) / bc2_sqrt + adam_eps)
+ *     with the host's float64 values rounded once: decay = 1 - lr wd, w1 = 1 - beta1, w2 = 1 - beta2, step_size = lr / (1 -
+ *     beta1^(iter+1)), bc2_sqrt = sqrt(1 - beta2^(iter+1)). A design that stops in this launch still takes this update.
+ *   sampling (iteration it = iter + 1, or iter with grad NULL; not for a design that stopped in this launch), per editable
+ *     position j, sample s, channel c, u = the uniform:
+ *     g = -log(1e-10 - log(u + 1e-10));  z = ((c == x0[j] ? la : lb) + w_c) + g;  zt = z / tau         (log: correctly rounded)
+ *     tok[d, s, j] = the first argmax of zt; y_c = exp(zt_c - max) / (((e_0 + e_1) + e_2) + e_3)       (exp: correctly rounded)
+ *     A frozen position copies x0[j] and writes no y. xin [nd S + n_pad, L, 4] f32: row (d - d0) S + s = onehot(tok[d, s]) (a
+ *     token > 3: a zero row); the n_pad rows after the chunk's are copies of its row 0, written by design d0's workgroup (and, like
+ *     that row, left alone once design d0 has stopped). edits[d, s] = positions with tok != x0.
+ *     REPLAY: rng->uniforms [B, S, L, 4] f32, this iteration's uniforms of the WHOLE batch (indexed by d); uniforms_rows must be 0.
+ *     PHILOX: counter (word 0, 1, 2, 3) = (row_offset + d low, high, it, s << 20 | j << 8 | 4): the iteration has a word of its own
+ *       (32 bits), and word 3's low byte is the stream word 4 (0 = svdd_propose / svdd_classifier_propose, 1 = re-mask, 2 = the
+ *       multinomial select, 3 = ELBO: their word 3 is 0..3 as a whole). The four words' top 24 bits are channels 0..3. The key is
+ *       rng->seed. rng->step is not used. rng may be NULL when sample == 0.
+ *   err: device i32 (may be NULL, caller-zeroed): set to 1 if x0 holds a token > 3 at a sampled position (no base gets la there).
+ *   No float atomics; every float of a position is computed by one thread in a fixed order, the edit counts are integer sums:
+ *   no result depends on the launch shape, on the chunking (d0, nd) or on the other designs.
+ *   SVDD_E_ARG: B, nd <= 0, d0 < 0, d0 + nd > B, L outside 1..1024, S outside 1..64, n_pad < 0, iter < 0, a NULL x0, cfg, w, m, v,
+ *   y, tok, xin or edits; tau not > 0; with grad: a NULL sc, best_*, x_best, score_best, wo, stopped or live; without: sample == 0;
+ *   sample != 0 with a NULL rng, REPLAY without uniforms or with uniforms_rows != 0; grad, xin, y, w, m, v or the uniforms not
+ *   16-byte aligned (a position's four channels move as one 16-byte access).
+ */
+typedef struct svdd_ledidi_cfg {
+  float tau, l;                 /* softmax temperature; weight of the input loss */
+  float la, lb;                 /* fp32(log(1 + eps)), fp32(log(eps)): the logits of x0's base and of the other three */
+  float scale;                  /* turns the pass's gradient into the row's (the row count of a mean's gradient pass, else 1) */
+  float decay, w1, beta2, w2, adam_eps, step_size, bc2_sqrt;   /* AdamW, as above (step_size and bc2_sqrt change per iteration) */
+  int32_t patience;             /* early_stopping_iter */
+} svdd_ledidi_cfg_t;
+int svdd_ledidi_step(const uint8_t* x0, const uint8_t* editable, const float* grad, const float* sc, const float* target,
+                     const svdd_ledidi_cfg_t* cfg, const svdd_rng_t* rng, int B, int L, int S, int d0, int nd, int n_pad, int iter,
+                     int sample, float* w, float* m, float* v, float* y, uint8_t* tok, float* xin, int32_t* edits, float* best_total,
+                     float* best_output, float* best_input, int32_t* best_iter, uint8_t* x_best, float* score_best, int32_t* wo,
+                     int32_t* stopped, int32_t* live, float* trace_total, float* trace_out, float* trace_in, int32_t* err,
+                     void* on_stream);
+
+/*
  * Sample-quality metrics of a set of sequences (added under ABI 17: three new entries, nothing existing changed): k-mer spectra
  * (reference oracle.py count_kmers, diffusion_gosai.py compare_kmer) and Hamming distances on 2-bit-packed rows (nearest
  * neighbour and the histogram of all pairs: diversity and novelty, which the reference does not have). All three are integer

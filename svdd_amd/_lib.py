@@ -37,12 +37,19 @@ class SvddRng(ctypes.Structure):
                 ("uniforms_layout", ctypes.c_int32), ("uniforms_rows", ctypes.c_int32)]
 
 
+class SvddLedidiCfg(ctypes.Structure):
+    """struct svdd_ledidi_cfg (include/svdd_hip.h)."""
+    _fields_ = [(n, ctypes.c_float) for n in ("tau", "l", "la", "lb", "scale", "decay", "w1", "beta2", "w2", "adam_eps", "step_size",
+                                              "bc2_sqrt")] + [("patience", ctypes.c_int32)]
+
+
 class SvddError(RuntimeError):
     pass
 
 
 vp, cstr, i32, i64, f32, f64 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double
 pi32, pf64, RNG = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(SvddRng)      # host pointers
+LCFG = ctypes.POINTER(SvddLedidiCfg)
 
 
 class STREAM(ctypes.c_void_p):
@@ -131,6 +138,8 @@ SIGNATURES = {
     "svdd_evolve_apply": (vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp),
     "svdd_attr_path": (vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp),
     "svdd_attr_fold": (vp, f32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp),
+    "svdd_ledidi_step": (vp, vp, vp, vp, vp, LCFG, RNG, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                         vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp),
     "svdd_candidate_windows_tight": (vp, vp, i32, i32, i32, i32, vp, vp, vp),
     "svdd_kmer_counts": (vp, i32, i32, i32, vp, vp, vp),
     "svdd_pack_tokens": (vp, i32, i32, vp, vp, vp),

@@ -19,6 +19,8 @@
 //       batch, their scores folded into the ISM table and a per-row best, one iteration's boundary of ISM-driven evolution
 //   K18 attr_path_kernel / K19 attr_fold_kernel  gradient attributions: the interpolants of a chunk of (row, step) pairs, their
 //       gradients folded into the per-row accumulator and the finished [B, 4, L] table
+//   K20 ledidi_step_kernel  Ledidi design: one iteration's boundary (losses, best-so-far, AdamW on the logit weights, the next
+//       iteration's Gumbel-softmax samples) around the unchanged scoring and gradient passes
 //   K4 tds_resample_kernel  SMC/TDS resampling (baseline)
 #include <float.h>
 #include <stdlib.h>
@@ -1597,6 +1599,181 @@ __global__ __launch_bounds__(256) void attr_fold_kernel(AttrFoldArgs a) {
   if (lane == 0) a.rowsum[b] = sum;
 }
 
+// ------------------------------------------------- K20 Ledidi design step (under ABI 17) ----
+// K20 ledidi_step_kernel: one workgroup per design of the chunk; thread tid owns the positions j = tid, tid + 256, ... in BOTH
+// halves, so every word of w / m / v / y / tok a thread reads was written by itself (in this launch or an earlier one) and no
+// barrier stands between the update and the sampling. Every thread evaluates the design's losses and the bookkeeping decision
+// redundantly from the same S scores and S edit counts (broadcast loads): the one barrier of the first half only orders those reads
+// before thread 0 rewrites best_total / wo. The sampling counts a sample's edits with a wave ballot and one LDS integer add per wave.
+// The float order is the one tests/ledidi_ref.py states, one rounding per operation.
+constexpr uint32_t LEDIDI_STREAM = 4u;      // low byte of Philox counter word 3 (words 3 of the other entries are 0..3 as a whole)
+
+struct LedidiArgs {
+  const uint8_t* x0; const uint8_t* editable; const float* grad; const float* sc; const float* target; const float* noise;
+  svdd_ledidi_cfg_t c; int L, S, d0, nd, n_pad, iter, sample; uint64_t seed, row_offset;
+  float* w; float* m; float* v; float* y; uint8_t* tok; float* xin; int32_t* edits;
+  float* best_total; float* best_output; float* best_input; int32_t* best_iter; uint8_t* x_best; float* score_best;
+  int32_t* wo; int32_t* stopped; int32_t* live; float* trace_total; float* trace_out; float* trace_in; int32_t* err;
+};
+
+__device__ __forceinline__ float ledidi_adamw(const svdd_ledidi_cfg_t& c, float g, float& w, float& m, float& v) {
+  w = __fmul_rn(w, c.decay);
+  m = __fadd_rn(m, __fmul_rn(c.w1, __fsub_rn(g, m)));
+  v = __fadd_rn(__fmul_rn(v, c.beta2), __fmul_rn(__fmul_rn(c.w2, g), g));
+  const float denom = __fadd_rn(__fdiv_rn(sqrtf(v), c.bc2_sqrt), c.adam_eps);   // sqrtf: correctly rounded (__fsqrt_rn is the native one)
+  w = __fsub_rn(w, __fdiv_rn(__fmul_rn(c.step_size, m), denom));
+  return w;
+}
+
+__global__ __launch_bounds__(256) void ledidi_step_kernel(LedidiArgs a) {
+  __shared__ int s_edits[64];
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+  const int dl = blockIdx.x, L = a.L, S = a.S;
+  const int64_t d = (int64_t)a.d0 + dl;
+  const float fS = (float)S;
+  const uint8_t* x0 = a.x0 + d * L;
+  uint8_t* tok = a.tok + d * S * L;
+  float* yb = a.y + d * S * L * 4;
+  bool stops = false;
+  if (a.grad) {
+    if (a.stopped[d] != 0) return;                                  // uniform over the workgroup: a stopped design is left alone
+    const bool tgt = a.target != nullptr;
+    const float target = tgt ? a.target[d] : 0.0f;
+    const float* sc = a.sc + d * S;
+    float sum = 0.0f;
+    int esum = 0;
+    for (int s = 0; s < S; ++s) {
+      const float df = __fsub_rn(sc[s], target);
+      sum = __fadd_rn(sum, tgt ? __fmul_rn(df, df) : sc[s]);
+      esum += a.edits[d * S + s];
+    }
+    const float q = __fdiv_rn(sum, fS);
+    const float out = tgt ? q : -q;
+    const float inp = __fdiv_rn((float)esum, fS);
+    const float total = __fadd_rn(out, __fmul_rn(a.c.l, inp));
+    const bool better = total < a.best_total[d];
+    stops = !better && a.wo[d] + 1 == a.c.patience;
+    __syncthreads();                                                // every thread has read best_total / wo
+    if (tid == 0) {
+      if (better) {
+        a.best_total[d] = total; a.best_output[d] = out; a.best_input[d] = inp; a.best_iter[d] = a.iter; a.wo[d] = 0;
+      } else {
+        a.wo[d] = a.wo[d] + 1;
+        if (stops) { a.stopped[d] = 1; atomicSub(a.live, 1); }
+      }
+      if (a.trace_total) a.trace_total[d] = total;
+      if (a.trace_out) a.trace_out[d] = out;
+      if (a.trace_in) a.trace_in[d] = inp;
+    }
+    if (better && tid < S) a.score_best[d * S + tid] = sc[tid];
+    const float lam = __fdiv_rn(a.c.l, (float)(2 * S));
+    const float inv_tau = __fdiv_rn(1.0f, a.c.tau);
+    const float coef_max = -__fdiv_rn(1.0f, fS);
+    const float* grad = a.grad + (int64_t)dl * S * L * 4;
+    uint8_t* xb = a.x_best + d * S * L;
+    for (int j = tid; j < L; j += 256) {
+      const uint32_t xj = x0[j];
+      const bool ed = !a.editable || a.editable[j] != 0;
+      float gw[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      for (int s = 0; s < S; ++s) {
+        const uint32_t t = tok[s * L + j];
+        if (better) xb[s * L + j] = (uint8_t)t;
+        if (!ed) continue;
+        const float4 g4 = *reinterpret_cast<const float4*>(grad + ((int64_t)s * L + j) * 4);
+        const float4 y4 = *reinterpret_cast<const float4*>(yb + ((int64_t)s * L + j) * 4);
+        const float gr[4] = {g4.x, g4.y, g4.z, g4.w}, y[4] = {y4.x, y4.y, y4.z, y4.w};
+        const float coef = tgt ? __fdiv_rn(__fmul_rn(2.0f, __fsub_rn(sc[s], target)), fS) : coef_max;
+        float G[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const float pen = t == xj ? 0.0f : ((uint32_t)c == t ? lam : ((uint32_t)c == xj ? -lam : 0.0f));
+          G[c] = __fadd_rn(__fmul_rn(coef, __fmul_rn(a.c.scale, gr[c])), pen);
+        }
+        float dot = __fmul_rn(y[0], G[0]);
+#pragma unroll
+        for (int c = 1; c < 4; ++c) dot = __fadd_rn(dot, __fmul_rn(y[c], G[c]));
+#pragma unroll
+        for (int c = 0; c < 4; ++c) gw[c] = __fadd_rn(gw[c], __fmul_rn(__fmul_rn(inv_tau, y[c]), __fsub_rn(G[c], dot)));
+      }
+      if (!ed) continue;
+      float4* wp = reinterpret_cast<float4*>(a.w + (d * L + j) * 4);
+      float4* mp = reinterpret_cast<float4*>(a.m + (d * L + j) * 4);
+      float4* vp = reinterpret_cast<float4*>(a.v + (d * L + j) * 4);
+      float4 w4 = *wp, m4 = *mp, v4 = *vp;
+      ledidi_adamw(a.c, gw[0], w4.x, m4.x, v4.x);
+      ledidi_adamw(a.c, gw[1], w4.y, m4.y, v4.y);
+      ledidi_adamw(a.c, gw[2], w4.z, m4.z, v4.z);
+      ledidi_adamw(a.c, gw[3], w4.w, m4.w, v4.w);
+      *wp = w4; *mp = m4; *vp = v4;
+    }
+  }
+  if (!a.sample || stops) return;                                   // uniform over the workgroup
+  if (tid < 64) s_edits[tid] = 0;
+  __syncthreads();
+  const uint32_t it = (uint32_t)(a.grad ? a.iter + 1 : a.iter);
+  const uint64_t row = a.row_offset + (uint64_t)d;
+  float* xin = a.xin + (int64_t)dl * S * L * 4;
+  float* pad = a.xin + (int64_t)a.nd * S * L * 4;
+  bool bad = false;
+  for (int j0 = 0; j0 < L; j0 += 256) {                             // whole waves run every trip: the ballot below needs them
+    const int j = j0 + tid;
+    const bool act = j < L;
+    const uint32_t xj = act ? x0[j] : 0u;
+    const bool ed = act && (!a.editable || a.editable[j] != 0);
+    if (ed && xj > 3u) bad = true;
+    float wv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (ed) {
+      const float4 w4 = *reinterpret_cast<const float4*>(a.w + (d * L + j) * 4);
+      wv[0] = w4.x; wv[1] = w4.y; wv[2] = w4.z; wv[3] = w4.w;
+    }
+    for (int s = 0; s < S; ++s) {
+      uint32_t t = xj;
+      if (ed) {
+        float u[4];
+        if (a.noise) {
+          const float4 u4 = *reinterpret_cast<const float4*>(a.noise + ((d * S + s) * L + j) * 4);
+          u[0] = u4.x; u[1] = u4.y; u[2] = u4.z; u[3] = u4.w;
+        } else {
+          uint32_t c[4] = {(uint32_t)row, (uint32_t)(row >> 32), it, ((uint32_t)s << 20) | ((uint32_t)j << 8) | LEDIDI_STREAM};
+          philox4x32_10(c, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
+          u[0] = u24(c[0]); u[1] = u24(c[1]); u[2] = u24(c[2]); u[3] = u24(c[3]);
+        }
+        float zt[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const float e = __fsub_rn(1e-10f, logf_cr(__fadd_rn(u[c], 1e-10f)));
+          const float g = -logf_cr(e);
+          const float z = __fadd_rn(__fadd_rn((uint32_t)c == xj ? a.c.la : a.c.lb, wv[c]), g);
+          zt[c] = __fdiv_rn(z, a.c.tau);
+        }
+        int best = 0;
+        float mx = zt[0];
+#pragma unroll
+        for (int c = 1; c < 4; ++c) if (zt[c] > mx) { mx = zt[c]; best = c; }
+        float e[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) e[c] = expf_cr(__fsub_rn(zt[c], mx));
+        const float sum = __fadd_rn(__fadd_rn(__fadd_rn(e[0], e[1]), e[2]), e[3]);
+        *reinterpret_cast<float4*>(yb + ((int64_t)s * L + j) * 4) =
+            make_float4(__fdiv_rn(e[0], sum), __fdiv_rn(e[1], sum), __fdiv_rn(e[2], sum), __fdiv_rn(e[3], sum));
+        t = (uint32_t)best;
+      }
+      if (act) {
+        tok[s * L + j] = (uint8_t)t;
+        const float4 oh = attr_onehot(t);
+        *reinterpret_cast<float4*>(xin + ((int64_t)s * L + j) * 4) = oh;
+        if (dl == 0 && s == 0)
+          for (int p = 0; p < a.n_pad; ++p) *reinterpret_cast<float4*>(pad + ((int64_t)p * L + j) * 4) = oh;
+      }
+      const unsigned long long bal = __ballot(ed && t != xj);
+      if (lane == 0 && bal) atomicAdd(&s_edits[s], __popcll(bal));
+    }
+  }
+  __syncthreads();
+  if (tid < S) a.edits[d * S + tid] = s_edits[tid];
+  if (bad && a.err) a.err[0] = 1;
+}
+
 // -------------------------------------------------------------------- K4 TDS resample ----
 // numpy's pairwise float32 sum (np.add.reduce), the order `ratio.sum()` uses at :1282: the array is halved (left half
 // rounded down to a multiple of 8) until a block has <= 128 elements; a block is summed with 8 running accumulators.
@@ -2468,6 +2645,43 @@ int svdd_attr_fold(const float* grad, float scale, const float* weight, const ui
   const AttrFoldArgs a{grad, scale, weight, x, baseline, baseline && baseline_rows != 1, B, L, S, r0, n_rows, mode, acc, attr, rowsum};
   const int64_t rows = ((int64_t)r0 + n_rows - 1) / S - r0 / S + 1;
   return svdd_launch(vec ? attr_fold_kernel<true> : attr_fold_kernel<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, on_stream, a);
+}
+
+int svdd_ledidi_step(const uint8_t* x0, const uint8_t* editable, const float* grad, const float* sc, const float* target,
+                     const svdd_ledidi_cfg_t* cfg, const svdd_rng_t* rng, int B, int L, int S, int d0, int nd, int n_pad, int iter,
+                     int sample, float* w, float* m, float* v, float* y, uint8_t* tok, float* xin, int32_t* edits, float* best_total,
+                     float* best_output, float* best_input, int32_t* best_iter, uint8_t* x_best, float* score_best, int32_t* wo,
+                     int32_t* stopped, int32_t* live, float* trace_total, float* trace_out, float* trace_in, int32_t* err,
+                     void* on_stream) {
+  if (!x0 || !cfg || !w || !m || !v || !y || !tok || !xin || !edits) return SVDD_E_ARG;
+  if (B <= 0 || nd <= 0 || d0 < 0 || (int64_t)d0 + nd > B || L < 1 || L > 1024 || S < 1 || S > 64 || n_pad < 0 || iter < 0) return SVDD_E_ARG;
+  if (!(cfg->tau > 0.0f)) return SVDD_E_ARG;
+  if (grad) {
+    if (!sc || !best_total || !best_output || !best_input || !best_iter || !x_best || !score_best || !wo || !stopped || !live)
+      return SVDD_E_ARG;
+  } else if (!sample) {
+    return SVDD_E_ARG;
+  }
+  const float* noise = nullptr;
+  uint64_t seed = 0, row_offset = 0;
+  if (sample) {
+    if (!rng) return SVDD_E_ARG;
+    if (rng->kind == SVDD_RNG_REPLAY) {
+      if (!rng->uniforms || rng->uniforms_rows != 0) return SVDD_E_ARG;
+      noise = rng->uniforms;
+    } else if (rng->kind == SVDD_RNG_PHILOX) {
+      seed = rng->seed;
+      row_offset = rng->row_offset;
+    } else {
+      return SVDD_E_ARG;
+    }
+  }
+  const auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+  if (!al(grad) || !al(xin) || !al(y) || !al(w) || !al(m) || !al(v) || !al(noise)) return SVDD_E_ARG;
+  const LedidiArgs a{x0, editable, grad, sc, target, noise, *cfg, L, S, d0, nd, n_pad, iter, sample, seed, row_offset, w, m, v, y, tok,
+                     xin, edits, best_total, best_output, best_input, best_iter, x_best, score_best, wo, stopped, live, trace_total,
+                     trace_out, trace_in, err};
+  return svdd_launch(ledidi_step_kernel, dim3((unsigned)nd), dim3(256), 0, on_stream, a);
 }
 
 int svdd_tds_resample(const float* reward_num, const float* reward_den, double alpha, const uint8_t* sample,

@@ -132,6 +132,47 @@ class ValueTargets:
     x0: torch.Tensor
 
 
+@dataclass
+class LedidiResult:
+    """What Diffusion.ledidi returns, per design b of B with S samples: the S hard samples of the iteration with the lowest total
+    loss (x_best u8 [B, S, L]; the S copies of the start while best_iter == -1) and their scores (score_best f32 [B, S]), that
+    iteration's total / output / input loss (f32 [B]) and index (best_iter i32 [B]), n_iter = the iterations the longest-running
+    design executed, trace f32 [n_iter, B, 3] (total, output, input loss per iteration; NaN after a design stopped) or None; x0 u8
+    [B, L] and score0 f32 [B]: the start sequences and their scores."""
+    x_best: torch.Tensor
+    score_best: torch.Tensor
+    best_total: torch.Tensor
+    best_output: torch.Tensor
+    best_input: torch.Tensor
+    best_iter: torch.Tensor
+    n_iter: int
+    trace: Optional[torch.Tensor]
+    x0: torch.Tensor
+    score0: torch.Tensor
+
+
+def design_pick(result, target=None):
+    """One sequence per design from a LedidiResult: the best of the design's S best-iteration samples by the design's own objective
+    (the highest score, or with target — a float or [B] — the score closest to it), the lowest s among ties; a design whose
+    objectives are all NaN gives s = 0. -> (tokens u8 [B, L], score f32 [B], edits int64 [B] = positions that differ from x0)."""
+    sc = result.score_best
+    B, S = sc.shape
+    if target is None:
+        key = sc
+    else:
+        t = torch.as_tensor(target, dtype=torch.float32, device=sc.device).reshape(-1)
+        if t.numel() not in (1, B):
+            raise ValueError(f"target must be a float or hold {B} values, got {t.numel()}")
+        key = -(sc - t.expand(B)[:, None]) ** 2
+    key = torch.where(key != key, torch.full_like(key, float("-inf")), key)
+    best = key.max(dim=1, keepdim=True).values
+    s_idx = torch.arange(S, device=sc.device).expand(B, S)
+    s = torch.where(key == best, s_idx, torch.full_like(s_idx, S)).min(dim=1).values.clamp(max=S - 1)
+    rows = torch.arange(B, device=sc.device)
+    tokens = result.x_best[rows, s]
+    return tokens, sc[rows, s], (tokens != result.x0).sum(dim=1)
+
+
 def _capturing():
     return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
 
@@ -1678,6 +1719,152 @@ class Diffusion(nn.Module):
             ends[B:] = 0.0 if baseline is None else baseline
             sc = score_fn(ends)
             return attr, rowsum - (sc[:B] - sc[B:])
+
+    # ------------------------------------------------------------- Ledidi: gradient-based editing ----
+    LEDIDI_BETAS, LEDIDI_ADAM_EPS, LEDIDI_WEIGHT_DECAY = (0.9, 0.999), 1e-8, 0.01      # torch.optim.AdamW's defaults
+
+    def _ledidi_inputs(self, x, max_iter, batch_size, tau, l, lr, eps, early_stopping_iter, positions, target, chunk_rows, check_every,
+                       noise):
+        """Every check that needs no device, ValueError naming the argument -> (max_iter, S, editable bool list | None, target as a
+        float64 numpy [B] | None)."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] == 0 or x.shape[1] == 0:
+            raise ValueError(f"x must be a [B, L] tensor with B, L > 0, got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)}")
+        B, L = x.shape
+        if x.dtype.is_floating_point or x.dtype == torch.bool:
+            raise ValueError(f"x must hold integer tokens, got {x.dtype}")
+        if L > ops.LEDIDI_MAX_L:
+            raise ValueError(f"x has L = {L} positions, beyond the {ops.LEDIDI_MAX_L} svdd_ledidi_step takes")
+        S = int(batch_size)
+        if not 1 <= S <= ops.LEDIDI_MAX_S:
+            raise ValueError(f"batch_size must lie in 1..{ops.LEDIDI_MAX_S}, got {batch_size}")
+        max_iter = int(max_iter)
+        if not 0 <= max_iter < 2 ** 31 - 1:
+            raise ValueError(f"max_iter must lie in 0..{2 ** 31 - 2} (the Philox counter's iteration word and the kernel's int), got {max_iter}")
+        for name, val, positive in (("tau", tau, True), ("eps", eps, True), ("lr", lr, False), ("l", l, False)):
+            if not math.isfinite(float(val)) or (positive and not float(val) > 0) or float(val) < 0:
+                raise ValueError(f"{name} must be a finite number{' > 0' if positive else ' >= 0'}, got {val}")
+        if int(early_stopping_iter) < 1:
+            raise ValueError(f"early_stopping_iter must be >= 1, got {early_stopping_iter}")
+        if int(check_every) < 1:
+            raise ValueError(f"check_every must be >= 1, got {check_every}")
+        if chunk_rows is not None and int(chunk_rows) <= 0:
+            raise ValueError(f"chunk_rows must be positive, got {chunk_rows}")
+        editable = None
+        if positions is not None:
+            pos = [int(p) for p in (positions.tolist() if isinstance(positions, torch.Tensor) else positions)]
+            if any(p < 0 or p >= L for p in pos):
+                raise ValueError(f"positions must lie in 0..{L - 1}, got {pos}")
+            if len(set(pos)) != len(pos):
+                raise ValueError(f"positions must not repeat, got {pos}")
+            editable = [p in set(pos) for p in range(L)]
+        tgt = None
+        if target is not None:
+            tgt = np.asarray(target.detach().cpu() if isinstance(target, torch.Tensor) else target, dtype=np.float64).reshape(-1)
+            if tgt.size not in (1, B) or not np.isfinite(tgt).all():
+                raise ValueError(f"target must be a finite float or hold {B} finite values, got {target}")
+            tgt = np.broadcast_to(tgt, (B,)).astype(np.float32)
+        if noise is not None:
+            if not isinstance(noise, torch.Tensor) or noise.dtype != torch.float32 or tuple(noise.shape) != (max_iter + 1, B, S, L, 4):
+                raise ValueError(f"noise must be an fp32 tensor of uniforms [{max_iter + 1}, {B}, {S}, {L}, 4] (max_iter + 1, B, "
+                                 f"batch_size, L, 4), got {tuple(noise.shape) if isinstance(noise, torch.Tensor) else type(noise)}")
+        lo, hi = torch.aminmax(x)
+        if int(lo) < 0 or int(hi) > 3:
+            raise ValueError("x holds a token outside 0..3: Ledidi edits finished sequences (A, C, G, T; MASK is refused)")
+        return max_iter, S, editable, tgt
+
+    def ledidi(self, x, pre_scorer_embedding, pre_scorer_head, reward_model=None, *, max_iter=1000, batch_size=10, tau=1.0, l=0.1,
+               lr=1.0, eps=1e-4, early_stopping_iter=100, positions=None, target=None, chunk_rows=None, check_every=32,
+               return_trace=False, noise=None):
+        """Ledidi (reference design.py ledidi, the `ledidi` package's fit_transform): gradient-based editing of the sequences x [B, L]
+        (tokens 0..3 on the GPU) towards a higher score, or with target (a float or [B]) towards that score, with as few edits as
+        the weight l asks for. Per design: logit weights w [L, 4] on log(onehot(x) + eps), batch_size Gumbel-softmax samples per
+        iteration at temperature tau, straight-through hard samples, total loss = output loss + l * (edits per sample), AdamW(lr) on
+        w, the best iteration's samples kept, stop after early_stopping_iter iterations without a lower total loss. The score is
+        pre_scorer_head(pre_scorer_embedding(.)), or reward_model's if given (task 0). Designs are independent and stop one by one.
+          positions    None = every position may change, or the positions that may (the others are frozen: never sampled)
+          chunk_rows   sample rows per scoring / gradient pass (whole designs; default ATTR_CHUNK_ROWS). On the fused route a pass runs
+                       on a power-of-two number of rows (padded with copies of its first row), so no result depends on chunk_rows
+          check_every  the host reads the one-word live count every check_every iterations; no result depends on it
+          noise        None: Philox uniforms keyed by (philox_seed, row_offset + b, iteration, sample, position); or the uniforms
+                       themselves, fp32 [max_iter + 1, B, batch_size, L, 4] on the GPU
+        Per iteration and chunk of designs: the scores of the hard samples (forward_tokens on a fused net: the bits every other entry
+        reports), their input gradient (mean_score_input_grad on the fused one-task ConvGRU net at L = 200 / 50, torch autograd
+        otherwise: attributions' routes), one svdd_ledidi_step launch. -> LedidiResult."""
+        _refuse_motif_reward("ledidi", pre_scorer_embedding, pre_scorer_head, reward_model)
+        max_iter, S, editable, tgt = self._ledidi_inputs(x, max_iter, batch_size, tau, l, lr, eps, early_stopping_iter, positions, target,
+                                                         chunk_rows, check_every, noise)
+        x0, _ = self._refine_inputs(x, None)
+        self._require_gpu()
+        dev = self.device
+        if noise is not None and noise.device != dev:
+            raise ops.SvddError("noise must be a tensor on the model's GPU (the SVDD hot path has no CPU fallback)")
+        B, L = x0.shape
+        chunk_rows = self.ATTR_CHUNK_ROWS if chunk_rows is None else int(chunk_rows)
+        patience, check_every = int(early_stopping_iter), int(check_every)
+        fused, grad_fn = self._attr_route(pre_scorer_embedding, pre_scorer_head, reward_model, L)
+        score_fn = self._design_scorer(pre_scorer_embedding, pre_scorer_head, reward_model)
+        cap = 1 << (chunk_rows.bit_length() - 1) if fused is not None else chunk_rows
+        per = max(1, cap // S)                                      # designs per pass: whole designs only, never less than one
+        chunks = []
+        for d0 in range(0, B, per):
+            nd = min(per, B - d0)
+            n_pass = 1 << (nd * S - 1).bit_length() if fused is not None else nd * S
+            chunks.append((d0, nd, n_pass - nd * S, torch.empty((n_pass, L, 4), dtype=torch.float32, device=dev)))
+        with torch.no_grad():
+            target_dev = None if tgt is None else torch.from_numpy(tgt).to(dev)
+            editable_dev = None if editable is None else torch.tensor(editable, dtype=torch.uint8, device=dev)
+            score0 = score_fn(x0)
+            # the loss of S copies of the start by the kernel's own formula (a sequential fp32 sum of S equal terms, ONE correctly
+            # rounded division), so that an iteration that edits nothing ties with it and is no improvement. On the host in numpy:
+            # a device division by a host scalar multiplies by the reciprocal, which is 1 ulp off for a fifth of the values at S = 10
+            s0 = score0.cpu().numpy()
+            term0 = s0 if tgt is None else (s0 - tgt) * (s0 - tgt)
+            acc0 = np.zeros_like(s0)
+            with np.errstate(all="ignore"):
+                for _ in range(S):
+                    acc0 = acc0 + term0
+                q0 = acc0 / np.float32(S)
+            output0 = torch.from_numpy(q0 if tgt is not None else -q0).to(dev)
+            st = ops.LedidiState(x0, S, score0, output0)
+            cfg = ops.LedidiConfig(S, tau=tau, l=l, lr=lr, eps=eps, patience=patience, betas=self.LEDIDI_BETAS,
+                                   adam_eps=self.LEDIDI_ADAM_EPS, weight_decay=self.LEDIDI_WEIGHT_DECAY)
+            sc = torch.empty((B, S), dtype=torch.float32, device=dev)
+            err = torch.zeros(1, dtype=torch.int32, device=dev)
+            trace = torch.full((max_iter + 1, 3, B), float("nan"), dtype=torch.float32, device=dev) if return_trace else None
+            rng_of = lambda it: (ops.Rng(uniforms=noise[it]) if noise is not None                   # noqa: E731
+                                 else ops.Rng(seed=self.philox_seed, row_offset=self.row_offset))
+            tok_rows, sc_rows = st.tok.view(B * S, L), sc.view(B * S)
+            for d0, nd, n_pad, xin in chunks:
+                ops.ledidi_step(x0, st, cfg.at(0), xin, d0, nd, 0, rng=rng_of(0), editable=editable_dev, n_pad=n_pad, err=err)
+        for i in range(max_iter + 1):
+            more = i < max_iter
+            for d0, nd, n_pad, xin in chunks:
+                r0, r1 = d0 * S, (d0 + nd) * S
+                with torch.no_grad():
+                    sc_rows[r0:r1] = score_fn(tok_rows[r0:r1])
+                if fused is not None:
+                    with torch.no_grad():
+                        grad, scale = fused.mean_score_input_grad(xin), float(xin.shape[0])
+                else:
+                    xg = xin.detach().requires_grad_(True)
+                    with torch.enable_grad():                       # the gradient of the SUM of the pass's scores: scale 1
+                        out = grad_fn(xg)
+                        grad = out[1] if isinstance(out, tuple) else torch.autograd.grad(out.sum(), xg)[0]
+                    grad, scale = grad.contiguous(), 1.0
+                with torch.no_grad():
+                    ops.ledidi_step(x0, st, cfg.at(i, scale), xin, d0, nd, i, rng=rng_of(i + 1) if more else None, grad=grad, sc=sc,
+                                    target=target_dev, editable=editable_dev, n_pad=n_pad, sample=more,
+                                    trace=None if trace is None else (trace[i, 0], trace[i, 1], trace[i, 2]), err=err)
+            if (i + 1) % check_every == 0 and int(st.live[0]) == 0:  # the one word the host reads
+                break
+        ops.check_ledidi_err(err)
+        # iterations the longest-running design executed: a stopped design ran best_iter + patience + 1 of them
+        ran = torch.where(st.stopped != 0, st.best_iter + (patience + 1), torch.full_like(st.best_iter, max_iter + 1))
+        n_iter = int(ran.max())
+        if trace is not None:
+            trace = trace[:n_iter].permute(0, 2, 1).contiguous()
+        return LedidiResult(st.x_best, st.score_best, st.best_total, st.best_output, st.best_input, st.best_iter, n_iter, trace, x0,
+                            score0)
 
     # ------------------------------------------------------------- exact work-skipping ----
     def _can_skip(self, fn, L, M):

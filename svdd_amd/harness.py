@@ -212,6 +212,18 @@ class BaseModel(nn.Module):
         chunk_rows, return_delta) -> fp32 [B, 4, L]."""
         return self.ref_model.attributions(samples, self.embedding, self.head, reward_model=self.reward_model, method=method, **kw)
 
+    def ledidi(self, samples, **kw):
+        """Ledidi gradient-based editing of samples [B, L] under the harness's reward model (reference design.py ledidi;
+        Diffusion.ledidi's keyword arguments) -> (tokens u8 [B, L], scores fp32 [B], edits int64 [B], report): each design's best
+        sample by its own objective (design_pick) and report = {"ledidi_score_gain_mean": mean of score - start score,
+        "ledidi_edits_mean", "ledidi_improved_fraction": designs whose total loss fell below the start's, "ledidi_iters"}."""
+        from .diffusion import design_pick
+        res = self.ref_model.ledidi(samples, self.embedding, self.head, reward_model=self.reward_model, **kw)
+        tokens, scores, edits = design_pick(res, kw.get("target"))
+        report = {"ledidi_score_gain_mean": float((scores - res.score0).mean()), "ledidi_edits_mean": float(edits.float().mean()),
+                  "ledidi_improved_fraction": float((res.best_iter >= 0).float().mean()), "ledidi_iters": res.n_iter}
+        return tokens, scores, edits, report
+
     @torch.no_grad()
     def controlled_decode_tweedie(self, gen_batch_num, sample_M, options):
         """SVDD-PM (reference Enformer.py:719-813)."""

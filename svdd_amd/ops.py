@@ -432,6 +432,110 @@ def attr_fold(grad, scale, weight, x, r0, n_rows, acc, attr, mode="times_input",
               ATTR_MODE[mode], acc, attr, rowsum, _this_stream())
 
 
+LEDIDI_MAX_L, LEDIDI_MAX_S = 1024, 64                                     # svdd_ledidi_step (include/svdd_hip.h)
+
+
+class LedidiConfig:
+    """The hyper-parameters of svdd_ledidi_step as the kernel takes them: every derived constant is computed here in float64 and
+    rounded once to fp32 (struct svdd_ledidi_cfg). at(i, scale) -> the struct for the launch that closes iteration i (AdamW step
+    count i + 1)."""
+
+    def __init__(self, S, tau=1.0, l=0.1, lr=1.0, eps=1e-4, patience=100, betas=(0.9, 0.999), adam_eps=1e-8, weight_decay=0.01):
+        import math
+        self.S, self.lr, self.betas = int(S), float(lr), (float(betas[0]), float(betas[1]))
+        self.c = _lib.SvddLedidiCfg(tau=float(tau), l=float(l), la=math.log(1.0 + float(eps)), lb=math.log(float(eps)), scale=1.0,
+                                    decay=1.0 - float(lr) * float(weight_decay), w1=1.0 - self.betas[0], beta2=self.betas[1],
+                                    w2=1.0 - self.betas[1], adam_eps=float(adam_eps), step_size=float(lr), bc2_sqrt=1.0,
+                                    patience=int(patience))
+
+    def at(self, i, scale=1.0):
+        import math
+        t = int(i) + 1
+        self.c.scale = float(scale)
+        self.c.step_size = self.lr / (1.0 - self.betas[0] ** t)
+        self.c.bc2_sqrt = math.sqrt(1.0 - self.betas[1] ** t)
+        return self.c
+
+
+class LedidiState:
+    """The caller-owned buffers of svdd_ledidi_step for B designs of S samples at length L: the logit weights and AdamW moments
+    (zero), the samples' softmax, the hard samples and their edit counts, the best-so-far fields, the patience counters and the live
+    count. best_total / best_output start from output0 [B] fp32 (the output loss of the start sequences), x_best / score_best from
+    the S copies of x0 and score0."""
+
+    def __init__(self, x0, S, score0, output0):
+        B, L = x0.shape
+        dev = x0.device
+        self.B, self.L, self.S = B, L, S
+        self.w, self.m, self.v = (torch.zeros((B, L, 4), dtype=torch.float32, device=dev) for _ in range(3))
+        self.y = torch.zeros((B, S, L, 4), dtype=torch.float32, device=dev)
+        self.tok = x0[:, None, :].expand(B, S, L).contiguous()
+        self.edits = torch.zeros((B, S), dtype=torch.int32, device=dev)
+        self.best_total, self.best_output = output0.clone(), output0.clone()
+        self.best_input = torch.zeros(B, dtype=torch.float32, device=dev)
+        self.best_iter = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        self.x_best = self.tok.clone()
+        self.score_best = score0[:, None].expand(B, S).contiguous()
+        self.wo, self.stopped = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(2))
+        self.live = torch.full((1,), B, dtype=torch.int32, device=dev)
+
+
+def ledidi_step(x0, st, cfg, xin, d0, nd, iter, rng=None, grad=None, sc=None, target=None, editable=None, n_pad=0, sample=True,
+                trace=None, err=None):
+    """svdd_ledidi_step, one launch for the designs d0 .. d0 + nd - 1 of x0 u8 [B, L] on the state st (LedidiState, updated in place).
+    grad f32 [>= nd S, L, 4] (the chunk's gradient pass, row (d - d0) S + s) and sc f32 [B, S] given: close iteration `iter` (losses,
+    best-so-far, patience, AdamW), then with sample draw iteration iter + 1's samples; grad None: draw iteration `iter`'s samples only.
+    cfg: the struct LedidiConfig.at(iter, scale) returns. xin f32 [nd S + n_pad, L, 4]: the chunk's one-hot rows, pads = copies of
+    row 0. rng: ops.Rng, replay (uniforms f32 [B, S, L, 4] of the sampled iteration) or philox (seed, row_offset). target f32 [B],
+    editable u8 [L], trace = (total, out, inp) f32 [B] each, err i32 [1] (caller-zeroed; a start token > 3): each may be None."""
+    x0 = _need(x0, torch.uint8, "x0")
+    B, L, S = st.B, st.L, st.S
+    _is(x0, torch.uint8, (B, L), "x0")
+    d0, nd, n_pad = int(d0), int(nd), int(n_pad)
+    _is(xin, torch.float32, (nd * S + n_pad, L, 4), "xin")
+    for name, t, dtype, shape in (("w", st.w, torch.float32, (B, L, 4)), ("m", st.m, torch.float32, (B, L, 4)),
+                                  ("v", st.v, torch.float32, (B, L, 4)), ("y", st.y, torch.float32, (B, S, L, 4)),
+                                  ("tok", st.tok, torch.uint8, (B, S, L)), ("edits", st.edits, torch.int32, (B, S)),
+                                  ("best_total", st.best_total, torch.float32, (B,)), ("best_output", st.best_output, torch.float32, (B,)),
+                                  ("best_input", st.best_input, torch.float32, (B,)), ("best_iter", st.best_iter, torch.int32, (B,)),
+                                  ("x_best", st.x_best, torch.uint8, (B, S, L)), ("score_best", st.score_best, torch.float32, (B, S)),
+                                  ("wo", st.wo, torch.int32, (B,)), ("stopped", st.stopped, torch.int32, (B,)),
+                                  ("live", st.live, torch.int32, (1,))):
+        _is(t, dtype, shape, name)
+    if grad is not None:
+        _need(grad, torch.float32, "grad")
+        if not grad.is_contiguous() or grad.dim() != 3 or grad.shape[0] < nd * S or tuple(grad.shape[1:]) != (L, 4):
+            raise SvddError(f"grad must be a contiguous fp32 [>= {nd * S}, {L}, 4] tensor, got {tuple(grad.shape)}")
+        _is(sc, torch.float32, (B, S), "sc")
+    if target is not None:
+        _is(target, torch.float32, (B,), "target")
+    if editable is not None:
+        _is(editable, torch.uint8, (L,), "editable")
+    if err is not None:
+        _is(err, torch.int32, (1,), "err")
+    tt = to = ti = None
+    if trace is not None:
+        tt, to, ti = trace
+        for name, t in (("trace total", tt), ("trace out", to), ("trace in", ti)):
+            _is(t, torch.float32, (B,), name)
+    rs = None
+    if sample:
+        if rng is None:
+            raise SvddError("ledidi_step: sampling needs an Rng")
+        if rng.uniforms is not None:
+            _is(rng.uniforms, torch.float32, (B, S, L, 4), "rng.uniforms")
+        rs = ctypes.byref(rng.c_struct())
+    _lib.call("svdd_ledidi_step", x0, editable, grad, sc, target, ctypes.byref(cfg), rs, B, L, S, d0, nd, n_pad, int(iter),
+              int(bool(sample)), st.w, st.m, st.v, st.y, st.tok, xin, st.edits, st.best_total, st.best_output, st.best_input,
+              st.best_iter, st.x_best, st.score_best, st.wo, st.stopped, st.live, tt, to, ti, err, _this_stream())
+
+
+def check_ledidi_err(err):
+    """Raise if svdd_ledidi_step flagged a start token > 3 (SVDD_E_ARG)."""
+    if int(err[0]) != 0:
+        _lib.check(_lib.E_ARG, "svdd_ledidi_step: a start sequence holds a token > 3")
+
+
 KMER_MAX_K, PACK_MAX_L = 6, 1024                                          # svdd_kmer_counts / svdd_pack_tokens (include/svdd_hip.h)
 NN_KEY_INIT = -1                                                         # all ones: the value svdd_hamming_nn's nn_key starts from
 
