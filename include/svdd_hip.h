@@ -282,6 +282,57 @@ int svdd_evolve_apply(const float* best_score, const int32_t* best_pos, const in
                       float* score_best, int32_t* tr_pos, int32_t* tr_allele, float* tr_score, uint8_t* tr_taken, void* on_stream);
 
 /*
+ * Pattern scanning and pattern-driven directed evolution (added under ABI 17: three new entries, nothing existing changed): the
+ * three entries above with a pattern of 1 .. SVDD_PATTERN_MAX_WIDTH tokens written at a start position in place of one base
+ * (reference design.py evolve(method="pattern", for_each=True); grelu's MotifScanDataset restated). A replacement, not
+ * an insertion: the length stays L. Every entry takes its stream explicitly.
+ *   patterns [K, SVDD_PATTERN_MAX_WIDTH] u8, 4-byte aligned: row k holds pattern k's widths[k] tokens 0..3, the rest is ignored.
+ *   widths [K] i32, positions [P] i32 ascending start positions (both on the device).
+ *
+ * svdd_pattern_mutants: cand [B, P K, L] u8; onehot [B * P K, L, 4] f32 or NULL. Mutant (b, j, k), row (b P + j) K + k (the
+ *   pattern index runs fastest), is row b with x[b, positions[j] : positions[j] + widths[k]] overwritten by pattern k. An exact
+ *   copy of row b is written for a row with live[b] == 0 (live [B] u8 or NULL) and, with err[0] = 1 (err [1] i32 or NULL, zeroed
+ *   by the caller, never cleared here), for a width outside 1..32, a window that leaves the row (positions[j] < 0 or positions[j] +
+ *   widths[k] > L), a parent token > 3 ANYWHERE in row b and a pattern token > 3: nothing is read or written out of bounds.
+ *   A mutant may equal its parent (the pattern is already there): svdd_candidate_windows / svdd_candidate_parts flag it 0.
+ *   One wave per mutant; word accesses when L % 4 == 0 and x, cand (4) and onehot (16) are aligned, bytes otherwise, same result.
+ *   SVDD_E_ARG: B, L, P or K <= 0, a NULL x, positions, patterns, widths or cand, cand == x, patterns not 4-byte aligned,
+ *   P K > 2^30, B P K L >= 2^40.
+ *
+ * svdd_pattern_fold: folds the scores of one chunk of positions (columns p0 .. p0 + Pc - 1) into the table and the per-row
+ *   running best. scores: dense [B, Pc K] f32 in the order above when slot is NULL; with slot [B * Pc K] i32 (svdd_compact_flags'
+ *   map) the score of mutant i is scores[slot[i]], or parent_score[b] where slot[i] < 0 (an exact copy, not computed: the same
+ *   bits as the parent's score). table [B, P, K] f32 or NULL. best_score [B] f32, best_pos [B] i32, best_pattern [B] i32 (all
+ *   three or none; table or the three must be given): best_pos is the INDEX j into positions, best_pattern the index k. The rules
+ *   are svdd_ism_fold's: the chunk with p0 == 0 starts at (-inf, -1, -1), chunks are folded in ascending p0, an entry replaces the
+ *   running best only if STRICTLY greater (the first entry in (position, pattern) order wins a tie, the running best of the
+ *   earlier chunks wins a tie, a NaN and -inf never win: a row whose every entry is NaN keeps (-1, -1)); a row with live[b] == 0
+ *   offers no pick, its table columns are still written. One wave per row, reduced by comparison on (score, order index).
+ *   SVDD_E_ARG: B, P, K or Pc <= 0, p0 < 0, p0 + Pc > P, P K > 2^30, a NULL scores or parent_score, neither output, a partial best
+ *   triple, table == scores.
+ *
+ * svdd_pattern_apply: svdd_evolve_apply for a pick (best_pos = index into positions, best_pattern): ONE launch of ONE workgroup,
+ *   both stop rules as there, nothing written if stopped[0] != 0 at entry. A row's pick is valid when the row is live (live NULL:
+ *   every row), 0 <= best_pos < P, 0 <= best_pattern < K and the pattern's window lies inside the row. Taking a pick writes the
+ *   pattern's widths[k] bytes into x[b] at positions[best_pos] (possibly the bytes already there: a no-op pick) and sets
+ *   score_cur[b] = best_score[b]; then, if that is > score_best[b] (strictly), x_best[b, :] = x[b, :] and score_best[b] = it.
+ *   Trace (each NULL or [B]): tr_pos i32 = the START POSITION positions[best_pos], tr_pattern i32 = best_pattern (-1, -1 without a
+ *   valid pick), tr_score f32 = best_score[b] (score_cur[b] without a valid pick), tr_taken u8. Pattern tokens are not checked
+ *   here: they are the patterns svdd_pattern_mutants accepted.
+ *   SVDD_E_ARG: B, L, P or K <= 0, a stop mode other than the two, a NULL among the required pointers (everything but live and
+ *   the trace), ROW without live, x_best == x, patterns not 4-byte aligned.
+ */
+#define SVDD_PATTERN_MAX_WIDTH 32
+int svdd_pattern_mutants(const uint8_t* x, const int32_t* positions, const uint8_t* patterns, const int32_t* widths,
+                         const uint8_t* live, int B, int L, int P, int K, uint8_t* cand, float* onehot, int32_t* err, void* on_stream);
+int svdd_pattern_fold(const float* scores, const int32_t* slot, const float* parent_score, const uint8_t* live, int B, int P, int K,
+                      int p0, int Pc, float* table, float* best_score, int32_t* best_pos, int32_t* best_pattern, void* on_stream);
+int svdd_pattern_apply(const float* best_score, const int32_t* best_pos, const int32_t* best_pattern, const int32_t* positions,
+                       const uint8_t* patterns, const int32_t* widths, int B, int L, int P, int K, int stop, uint8_t* x,
+                       float* score_cur, uint8_t* live, float* best_so_far, int32_t* stopped, uint8_t* x_best, float* score_best,
+                       int32_t* tr_pos, int32_t* tr_pattern, float* tr_score, uint8_t* tr_taken, void* on_stream);
+
+/*
  * Gradient attributions (added under ABI 17: two new entries, nothing existing changed): gradient, input x gradient and integrated
  * gradients of a row's score (reference score.py get_attributions). The boundary kernels around an unchanged input-gradient pass.
  * A call's work is the B * S (row, step) pairs r = b * S + k in that order (S = 1 for the one-pass methods); a pass takes the

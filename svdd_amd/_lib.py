@@ -24,6 +24,7 @@ EVOLVE_GLOBAL, EVOLVE_ROW = 0, 1                                   # SVDD_EVOLVE
 ATTR_GRADIENT, ATTR_TIMES_INPUT = 0, 1                             # SVDD_ATTR_* of include/svdd_hip.h
 PRECISIONS = {"f32": 0, "f16x3": 1, "bf16x3": 2, "f16": 3, "bf16": 4}      # enum SVDD_PREC_* of include/svdd_hip.h
 MAX_M = 1024
+PATTERN_MAX_WIDTH = 32                                             # SVDD_PATTERN_MAX_WIDTH of include/svdd_hip.h (= motifs.MAX_WIDTH)
 
 # enum SVDD_OPT_* of include/svdd_hip.h (tests/test_host_cpu.py compares names and values with the header)
 OPT_FORCE_EXACT, OPT_MSPLIT, OPT_SELECT_ONE_ROW, OPT_BACKBONE_LP_VERSION, OPT_TRUNK_GEMM_VERSION = 0, 1, 2, 3, 4
@@ -154,6 +155,9 @@ SIGNATURES = {
     "svdd_candidate_parts": (vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp),
     "svdd_conv_tower_parts_f32": (vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp),
     "svdd_backbone_incr4_f32": (vp, vp, vp, vp, vp, vp, i32, i32, i32, pi32, i32, vp, vp, vp, vp, i32, i32, vp, vp, i32, vp, i32, vp),
+    "svdd_pattern_mutants": (vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp),
+    "svdd_pattern_fold": (vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp),
+    "svdd_pattern_apply": (vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp),
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -21,6 +21,8 @@
 //       gradients folded into the per-row accumulator and the finished [B, 4, L] table
 //   K20 ledidi_step_kernel  Ledidi design: one iteration's boundary (losses, best-so-far, AdamW on the logit weights, the next
 //       iteration's Gumbel-softmax samples) around the unchanged scoring and gradient passes
+//   K21 pattern_mutants_kernel / K22 pattern_fold_kernel / K23 pattern_apply_kernel  pattern scanning: K15-K17 with a pattern of
+//       up to 32 tokens written at a start position in place of one base
 //   K4 tds_resample_kernel  SMC/TDS resampling (baseline)
 #include <float.h>
 #include <stdlib.h>
@@ -1491,6 +1493,227 @@ __global__ __launch_bounds__(1024) void evolve_apply_kernel(EvolveArgs a) {
   }
 }
 
+// ------------------------------------------------- K21-K23 pattern scanning and pattern-driven evolution (under ABI 17) ----
+// K15-K17 with a pattern of w <= 32 tokens written at a start position in place of one base. (Declared next to their siblings;
+// the numbers follow K20, the Ledidi step.)
+// Byte d (0 <= d < 32) of a pattern held as eight wave-uniform words: selects, no indexed register array.
+__device__ __forceinline__ uint32_t pattern_byte(const uint32_t (&pw)[SVDD_PATTERN_MAX_WIDTH / 4], int d) {
+  uint32_t word = 0;
+#pragma unroll
+  for (int q = 0; q < SVDD_PATTERN_MAX_WIDTH / 4; ++q) word = (d >> 2) == q ? pw[q] : word;
+  return (word >> (8 * (d & 3))) & 0xFFu;
+}
+
+// The four tokens at l0 .. l0 + 3 with the pattern's bytes merged in where [l0, l0 + 4) meets [pos, pos + w); w == 0: unchanged.
+__device__ __forceinline__ uint32_t pattern_merge(uint32_t tok4, int l0, int pos, int w, const uint32_t (&pw)[SVDD_PATTERN_MAX_WIDTH / 4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int d = l0 + i - pos;
+    if (d >= 0 && d < w) tok4 = (tok4 & ~(0xFFu << (8 * i))) | (pattern_byte(pw, d) << (8 * i));
+  }
+  return tok4;
+}
+
+// K21 pattern_mutants_kernel: one wave per mutant (b, j, k) = row b with positions[j] .. positions[j] + widths[k] - 1 overwritten by
+// pattern k (the pattern index runs fastest). A first pass over the row looks for a parent token > 3 (the wave votes), the second
+// copies it four positions per lane with the pattern merged into every word it meets. A dead row, a window that leaves the row,
+// a parent token > 3 anywhere in the row or a pattern token > 3 gives an exact copy.
+struct PatternMutantsArgs {
+  const uint8_t* x; const int32_t* positions; const uint8_t* patterns; const int32_t* widths; const uint8_t* live; int B, L, P, K;
+  uint8_t* cand; float* onehot; int32_t* err;
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void pattern_mutants_kernel(PatternMutantsArgs a) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t M = (int64_t)a.P * a.K;
+  if (c >= (int64_t)a.B * M) return;                                // whole waves only: the mutant is the wave's
+  const int64_t b = c / M;
+  const int r = (int)(c - b * M), j = r / a.K, k = r - j * a.K;
+  const uint8_t* src = a.x + b * a.L;
+  const int pos = a.positions[j];
+  int w = a.widths[k];
+  bool bad = w < 1 || w > SVDD_PATTERN_MAX_WIDTH || pos < 0 || (int64_t)pos + w > a.L;
+  uint32_t pw[SVDD_PATTERN_MAX_WIDTH / 4];
+  const uint32_t* pk = reinterpret_cast<const uint32_t*>(a.patterns) + (int64_t)k * (SVDD_PATTERN_MAX_WIDTH / 4);   // wave-uniform
+#pragma unroll
+  for (int q = 0; q < SVDD_PATTERN_MAX_WIDTH / 4; ++q) {
+    pw[q] = pk[q];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) bad |= 4 * q + i < w && ((pw[q] >> (8 * i)) & 0xFFu) > 3u;
+  }
+  bool badtok = false;
+  for (int l0 = lane * 4; l0 < a.L; l0 += 4 * WAVE) {
+    const uint32_t tok4 = load4_u8<VEC>(src, l0, a.L);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) badtok |= ((tok4 >> (8 * i)) & 0xFFu) > 3u;
+  }
+  bad |= __any(badtok) != 0;
+  if (bad || (a.live && a.live[b] == 0)) w = 0;                     // an exact copy
+  uint8_t* dst = a.cand + c * a.L;
+  float* oh = a.onehot ? a.onehot + c * a.L * 4 : nullptr;
+  for (int l0 = lane * 4; l0 < a.L; l0 += 4 * WAVE) {
+    const uint32_t tok4 = pattern_merge(load4_u8<VEC>(src, l0, a.L), l0, pos, w, pw);
+    store4_u8<VEC>(dst, l0, a.L, tok4);
+    if (!oh) continue;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const uint32_t t = (tok4 >> (8 * i)) & 0xFFu;
+      float4 v;
+      v.x = t == 0u ? 1.0f : 0.0f; v.y = t == 1u ? 1.0f : 0.0f; v.z = t == 2u ? 1.0f : 0.0f; v.w = t == 3u ? 1.0f : 0.0f;
+      if (VEC) {
+        reinterpret_cast<float4*>(oh)[l0 + i] = v;
+      } else if (l0 + i < a.L) {
+        float* o = oh + (int64_t)(l0 + i) * 4;
+        o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+      }
+    }
+  }
+  if (bad && a.err) a.err[0] = 1;
+}
+
+// K22 pattern_fold_kernel: K16 over the chunk's Pc K (position, pattern) entries. A lane takes the entries e = lane, lane + 64, ...
+// in ascending order and keeps its own best (score, order index p0 K + e) under `strictly greater`; the wave reduces by
+// comparison on (score, index), the smaller index winning equal scores, and lane 0 merges with the running best of the earlier
+// chunks, which wins a tie because it comes first. A NaN compares false everywhere: it never wins.
+struct PatternFoldArgs {
+  const float* scores; const int32_t* slot; const float* parent_score; const uint8_t* live; int B, P, K, p0, Pc;
+  float* table; float* best_score; int32_t* best_pos; int32_t* best_pattern;
+};
+
+__global__ __launch_bounds__(256) void pattern_fold_kernel(PatternFoldArgs a) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= a.B) return;
+  const float ps = a.parent_score[b];
+  const bool offers = !a.live || a.live[b] != 0;
+  const int n = a.Pc * a.K, e0 = a.p0 * a.K;
+  float bs = -INFINITY;
+  int bi = -1;
+  for (int e = lane; e < n; e += WAVE) {
+    const int64_t i = b * n + e;
+    float s;
+    if (a.slot) {
+      const int sl = a.slot[i];
+      s = sl >= 0 ? a.scores[sl] : ps;
+    } else {
+      s = a.scores[i];
+    }
+    if (a.table) a.table[b * a.P * a.K + e0 + e] = s;
+    if (offers && s > bs) { bs = s; bi = e0 + e; }
+  }
+  if (!a.best_score) return;
+#pragma unroll
+  for (int off = WAVE / 2; off > 0; off >>= 1) {
+    const float os = __shfl_xor(bs, off, WAVE);
+    const int oi = __shfl_xor(bi, off, WAVE);
+    if (os > bs || (os == bs && oi >= 0 && (bi < 0 || oi < bi))) { bs = os; bi = oi; }
+  }
+  if (lane == 0) {
+    float rs = -INFINITY;
+    int rp = -1, rk = -1;
+    if (a.p0 > 0) { rs = a.best_score[b]; rp = a.best_pos[b]; rk = a.best_pattern[b]; }
+    if (bi >= 0 && bs > rs) { rs = bs; rp = bi / a.K; rk = bi - rp * a.K; }
+    a.best_score[b] = rs; a.best_pos[b] = rp; a.best_pattern[b] = rk;
+  }
+}
+
+// K23 pattern_apply_kernel: K17 with a pick (index into positions, pattern index) that writes widths[pattern] bytes. ONE
+// workgroup of 16 waves, the same two phases: every global word another row's decision depends on (best_so_far, stopped) is read
+// before the first barrier, written after it by thread 0 only, and not read again; score_cur / live of a row are read by that
+// row's phase-1 thread before the barriers and, in phase 2 (after the second), read and written by that row's wave alone. A word
+// of x is read by one lane only, which is the lane that then rewrites it.
+struct PatternApplyArgs {
+  const float* best_score; const int32_t* best_pos; const int32_t* best_pattern; const int32_t* positions; const uint8_t* patterns;
+  const int32_t* widths; int B, L, P, K, stop;
+  uint8_t* x; float* score_cur; uint8_t* live; float* best_so_far; int32_t* stopped; uint8_t* x_best; float* score_best;
+  int32_t* tr_pos; int32_t* tr_pattern; float* tr_score; uint8_t* tr_taken;
+};
+
+// The pick of row b -> valid, with its start position and width.
+__device__ __forceinline__ bool pattern_pick(const PatternApplyArgs& a, int b, int& pos, int& k, int& w) {
+  const int j = a.best_pos[b];
+  k = a.best_pattern[b];
+  pos = -1;
+  w = 0;
+  if ((a.live && a.live[b] == 0) || j < 0 || j >= a.P || k < 0 || k >= a.K) return false;
+  pos = a.positions[j];
+  w = a.widths[k];
+  return w >= 1 && w <= SVDD_PATTERN_MAX_WIDTH && pos >= 0 && (int64_t)pos + w <= a.L;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(1024) void pattern_apply_kernel(PatternApplyArgs a) {
+  __shared__ float s_max[16];
+  __shared__ int s_any[16];
+  __shared__ int s_go;
+  if (a.stopped[0] != 0) return;                                    // uniform: nothing is written once stopped
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid >> 6;
+  const bool global = a.stop == SVDD_EVOLVE_GLOBAL;
+  float m = -INFINITY;
+  int any = 0;
+  for (int b = tid; b < a.B; b += 1024) {
+    int pos, k, w;
+    const bool valid = pattern_pick(a, b, pos, k, w);
+    const float s = a.best_score[b];
+    if (valid && global && s > m) m = s;
+    if (valid && !global && s > a.score_cur[b]) any = 1;
+  }
+#pragma unroll
+  for (int off = WAVE / 2; off > 0; off >>= 1) {
+    const float om = __shfl_xor(m, off, WAVE);
+    m = om > m ? om : m;
+    any |= __shfl_xor(any, off, WAVE);
+  }
+  if (lane == 0) { s_max[wave] = m; s_any[wave] = any; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 0; w < 16; ++w) { m = s_max[w] > m ? s_max[w] : m; any |= s_any[w]; }
+    int go;
+    if (global) {
+      go = m > a.best_so_far[0] ? 1 : 0;
+      if (go) a.best_so_far[0] = m; else a.stopped[0] = 1;
+    } else {
+      go = 1;
+      if (!any) a.stopped[0] = 1;
+    }
+    s_go = go;
+  }
+  __syncthreads();
+  const bool go = s_go != 0;
+  for (int b = wave; b < a.B; b += 16) {
+    const bool lv = !a.live || a.live[b] != 0;
+    int pos, k, w;
+    const bool valid = pattern_pick(a, b, pos, k, w);
+    const float s = a.best_score[b], cur = a.score_cur[b], sb = a.score_best[b];
+    const bool take = valid && (global ? go : s > cur);
+    const bool better = take && s > sb;                             // the first occurrence of the row's highest score stays
+    uint32_t pw[SVDD_PATTERN_MAX_WIDTH / 4];
+    const uint32_t* pk = reinterpret_cast<const uint32_t*>(a.patterns) + (int64_t)(valid ? k : 0) * (SVDD_PATTERN_MAX_WIDTH / 4);
+#pragma unroll
+    for (int q = 0; q < SVDD_PATTERN_MAX_WIDTH / 4; ++q) pw[q] = pk[q];
+    uint8_t* xr = a.x + (int64_t)b * a.L;
+    uint8_t* xb = a.x_best + (int64_t)b * a.L;
+    if (lane == 0) {
+      if (a.tr_pos) a.tr_pos[b] = valid ? pos : -1;
+      if (a.tr_pattern) a.tr_pattern[b] = valid ? k : -1;
+      if (a.tr_score) a.tr_score[b] = valid ? s : cur;
+      if (a.tr_taken) a.tr_taken[b] = take ? 1 : 0;
+      if (better) a.score_best[b] = s;
+      if (!global && lv && !take) a.live[b] = 0;
+      if (take) a.score_cur[b] = s;
+    }
+    if (!take) continue;                                            // wave-uniform
+    // the row's bytes go last: a lane rewrites only the words it read itself, so no lane reads a word after its store
+    for (int l0 = lane * 4; l0 < a.L; l0 += 4 * WAVE) {
+      const uint32_t tok4 = pattern_merge(load4_u8<VEC>(xr, l0, a.L), l0, pos, w, pw);
+      if (better) store4_u8<VEC>(xb, l0, a.L, tok4);                // x_best[b, :] = the row with its pick applied
+      if (l0 + 4 > pos && l0 < pos + w) store4_u8<VEC>(xr, l0, a.L, tok4);
+    }
+  }
+}
+
 // ------------------------------------------------- K18-K19 gradient attributions (under ABI 17) ----
 // A position's four channels as one 16-byte access where the pointers are 16-byte aligned (VEC), four scalars otherwise.
 template <bool VEC>
@@ -2615,6 +2838,48 @@ int svdd_evolve_apply(const float* best_score, const int32_t* best_pos, const in
   const EvolveArgs a{best_score, best_pos, best_allele, B, L, stop, x, score_cur, live, best_so_far, stopped, x_best, score_best,
                      tr_pos, tr_allele, tr_score, tr_taken};
   return svdd_launch(vec ? evolve_apply_kernel<true> : evolve_apply_kernel<false>, dim3(1), dim3(1024), 0, on_stream, a);
+}
+
+int svdd_pattern_mutants(const uint8_t* x, const int32_t* positions, const uint8_t* patterns, const int32_t* widths,
+                         const uint8_t* live, int B, int L, int P, int K, uint8_t* cand, float* onehot, int32_t* err, void* on_stream) {
+  if (!x || !positions || !patterns || !widths || !cand || B <= 0 || L <= 0 || P <= 0 || K <= 0 || cand == x) return SVDD_E_ARG;
+  if (P > (1 << 24) || K > (1 << 24) || (int64_t)P * K > (int64_t)1 << 30) return SVDD_E_ARG;
+  if ((int64_t)B * P * K * L >= (int64_t)1 << 40 || (int64_t)B * P * K >= (int64_t)1 << 32) return SVDD_E_ARG;
+  const auto al = [](const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; };
+  if (!al(patterns, 4)) return SVDD_E_ARG;                          // a pattern's 32 bytes are read as eight words
+  const bool vec = L % 4 == 0 && al(x, 4) && al(cand, 4) && al(onehot, 16);
+  const PatternMutantsArgs a{x, positions, patterns, widths, live, B, L, P, K, cand, onehot, err};
+  return svdd_launch(vec ? pattern_mutants_kernel<true> : pattern_mutants_kernel<false>,
+                     dim3((unsigned)(((int64_t)B * P * K + 3) / 4)), dim3(256), 0, on_stream, a);
+}
+
+int svdd_pattern_fold(const float* scores, const int32_t* slot, const float* parent_score, const uint8_t* live, int B, int P, int K,
+                      int p0, int Pc, float* table, float* best_score, int32_t* best_pos, int32_t* best_pattern, void* on_stream) {
+  if (!scores || !parent_score || B <= 0 || P <= 0 || K <= 0 || Pc <= 0 || p0 < 0) return SVDD_E_ARG;
+  if (P > (1 << 24) || K > (1 << 24) || (int64_t)P * K > (int64_t)1 << 30 || (int64_t)p0 + Pc > P) return SVDD_E_ARG;
+  const int nbest = (best_score != nullptr) + (best_pos != nullptr) + (best_pattern != nullptr);
+  if ((nbest != 0 && nbest != 3) || (!table && nbest == 0)) return SVDD_E_ARG;   // a partial triple, or nothing to write
+  if ((const float*)table == scores || (const float*)best_score == scores || (const float*)best_score == parent_score) return SVDD_E_ARG;
+  if ((int64_t)B * P * K >= (int64_t)1 << 40) return SVDD_E_ARG;
+  const PatternFoldArgs a{scores, slot, parent_score, live, B, P, K, p0, Pc, table, best_score, best_pos, best_pattern};
+  return svdd_launch(pattern_fold_kernel, dim3((unsigned)(((int64_t)B + 3) / 4)), dim3(256), 0, on_stream, a);
+}
+
+int svdd_pattern_apply(const float* best_score, const int32_t* best_pos, const int32_t* best_pattern, const int32_t* positions,
+                       const uint8_t* patterns, const int32_t* widths, int B, int L, int P, int K, int stop, uint8_t* x,
+                       float* score_cur, uint8_t* live, float* best_so_far, int32_t* stopped, uint8_t* x_best, float* score_best,
+                       int32_t* tr_pos, int32_t* tr_pattern, float* tr_score, uint8_t* tr_taken, void* on_stream) {
+  if (B <= 0 || L <= 0 || P <= 0 || K <= 0 || (stop != SVDD_EVOLVE_GLOBAL && stop != SVDD_EVOLVE_ROW)) return SVDD_E_ARG;
+  if (!best_score || !best_pos || !best_pattern || !positions || !patterns || !widths) return SVDD_E_ARG;
+  if (!x || !score_cur || !best_so_far || !stopped || !x_best || !score_best) return SVDD_E_ARG;
+  if ((stop == SVDD_EVOLVE_ROW && !live) || x_best == x || score_best == score_cur) return SVDD_E_ARG;
+  if ((const float*)score_cur == best_score || (const float*)score_best == best_score) return SVDD_E_ARG;
+  const auto al = [](const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; };
+  if (!al(patterns, 4)) return SVDD_E_ARG;
+  const bool vec = L % 4 == 0 && al(x, 4) && al(x_best, 4);
+  const PatternApplyArgs a{best_score, best_pos, best_pattern, positions, patterns, widths, B, L, P, K, stop, x, score_cur, live,
+                           best_so_far, stopped, x_best, score_best, tr_pos, tr_pattern, tr_score, tr_taken};
+  return svdd_launch(vec ? pattern_apply_kernel<true> : pattern_apply_kernel<false>, dim3(1), dim3(1024), 0, on_stream, a);
 }
 
 int svdd_attr_path(const uint8_t* x, const float* baseline, int baseline_rows, const float* alpha, int B, int L, int S, int r0,

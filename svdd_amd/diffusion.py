@@ -1571,6 +1571,203 @@ class Diffusion(nn.Module):
                  "score": tr_score[:iters + 1]}
         return x_best.long(), score_best, trace
 
+    # ------------------------------------------------------------- pattern scanning, pattern-driven evolution ----
+    @staticmethod
+    def _pattern_list(patterns):
+        """patterns (strings over ACGT and / or integer sequences over 0..3, each of width 1..32) -> (uint8 numpy [K, 32] zero
+        padded, int32 numpy [K]). No device."""
+        from .motifs import MAX_WIDTH
+        if isinstance(patterns, (str, bytes)) or not hasattr(patterns, "__len__"):
+            raise ValueError("patterns must be a list of strings over ACGT and / or integer sequences over 0..3")
+        if len(patterns) == 0:
+            raise ValueError("patterns must not be empty")
+        pat, widths = np.zeros((len(patterns), MAX_WIDTH), np.uint8), np.zeros(len(patterns), np.int32)
+        for k, p in enumerate(patterns):
+            if isinstance(p, str):
+                tok = ["ACGT".find(c) for c in p]
+                if any(t < 0 for t in tok):
+                    raise ValueError(f"patterns[{k}] = {p!r}: a pattern is written over the letters ACGT")
+            else:
+                arr = np.asarray(p.detach().cpu() if isinstance(p, torch.Tensor) else p)
+                if arr.ndim != 1 or (arr.size and arr.dtype.kind not in "iu"):
+                    raise ValueError(f"patterns[{k}]: expected a string or a 1-D sequence of integer tokens, got {arr.dtype} {arr.shape}")
+                tok = [int(t) for t in arr]
+                if any(t < 0 or t > 3 for t in tok):
+                    raise ValueError(f"patterns[{k}] holds a token outside 0..3")
+            if not 1 <= len(tok) <= MAX_WIDTH:
+                raise ValueError(f"patterns[{k}] has width {len(tok)}: a pattern has 1..{MAX_WIDTH} tokens")
+            pat[k, :len(tok)], widths[k] = tok, len(tok)
+        return pat, widths
+
+    def _pattern_inputs(self, x, patterns, reward_model, positions, chunk_rows, what):
+        """Checks in an order that needs no device until the last ones (as _ism_inputs): the reward's type, the patterns, the shape,
+        the start positions, chunk_rows, a MASK token, then _refine_inputs' (a CPU tensor, a token outside 0..4).
+        -> (x u8 [B, L], pos_dev i32 [P], pat_dev u8 [K, 32], widths_dev i32 [K], P, K, Pc)."""
+        from .motifs import GuidedReward
+        if isinstance(reward_model, GuidedReward):
+            raise TypeError(f"{what}: a motifs.GuidedReward is not a net of this route (its motif term scores whole decodes): pass "
+                            "the reward model it wraps")
+        pat, widths = self._pattern_list(patterns)
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] == 0 or x.shape[1] == 0:
+            raise ValueError(f"x must be a [B, L] tensor with B, L > 0, got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)}")
+        L, wmax = x.shape[1], int(widths.max())
+        if wmax > L:
+            raise ValueError(f"the longest pattern has {wmax} tokens, the sequences {L}: patterns must fit into the sequence")
+        if positions is None:
+            pos = list(range(L - wmax + 1))                         # every start at which the longest pattern fits
+        else:
+            pos = [int(p) for p in (positions.tolist() if isinstance(positions, torch.Tensor) else positions)]
+            if not pos:
+                raise ValueError("positions must not be empty")
+            if any(p < 0 or p + wmax > L for p in pos):
+                raise ValueError(f"positions are starts in 0..{L - wmax} (the longest pattern, {wmax} tokens, must fit), got {pos}")
+            if any(b <= a for a, b in zip(pos, pos[1:])):
+                raise ValueError(f"positions must be strictly ascending (no duplicates), got {pos}")
+        if chunk_rows is not None and int(chunk_rows) <= 0:
+            raise ValueError(f"chunk_rows must be positive, got {chunk_rows}")
+        if not x.dtype.is_floating_point and x.dtype != torch.bool and bool((x == self.mask_index).any()):
+            raise ops.SvddError("x holds a MASK token: patterns are written into finished sequences (tokens 0..3)")
+        x_u8, _ = self._refine_inputs(x, None)
+        self._require_gpu()
+        B, K = x_u8.shape[0], len(widths)
+        if chunk_rows is None:
+            chunk_rows = self.ISM_WAVES_PER_CHUNK * torch.cuda.get_device_properties(self.device).multi_processor_count
+        Pc = max(1, min(len(pos), int(chunk_rows) // (K * B)))      # B * K * Pc <= chunk_rows (never less than one position)
+        dev = self.device
+        return (x_u8, torch.tensor(pos, dtype=torch.int32, device=dev), torch.from_numpy(pat).to(dev), torch.from_numpy(widths).to(dev),
+                len(pos), K, Pc)
+
+    class _PatternWorkspace:
+        def __init__(self, B, L, K, Pc, dev, windowed, onehot):
+            n = B * K * Pc
+            self.cand = torch.empty(n * L, dtype=torch.uint8, device=dev)
+            self.onehot = self.live_idx = self.slot = self.count = self.iota = None
+            self.flags = torch.empty(n, dtype=torch.int32, device=dev)
+            if windowed:
+                self.onehot = torch.empty(n * L * 4, dtype=torch.float32, device=dev) if onehot else None
+                self.live_idx, self.slot = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
+                self.count = torch.zeros(1, dtype=torch.int32, device=dev)
+            else:
+                self.iota = torch.arange(n, dtype=torch.int32, device=dev)
+            self.err = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def _pattern_workspace(self, B, L, K, Pc, fused):
+        return self._PatternWorkspace(B, L, K, Pc, self.device, fused is not None, fused is not None and not fused.lp_ok(L))
+
+    def _pattern_pass(self, x, pos_dev, pat_dev, widths_dev, P, K, Pc, score_fn, fused, ws, parent_score, live=None, table=None,
+                      best=None):
+        """The pattern mutants of x at every start position, chunk by chunk in ascending position order: svdd_pattern_mutants, the
+        value net, and svdd_pattern_fold into table [B, P, K] and / or the running best. On the windowed route the copies (a
+        pattern that is already there, a stopped row) are always compacted away; on the whole-mutant route they pass through
+        score_fn with the rest and the fold takes the parent's score in their place. Nothing returns to the host."""
+        from .fused import candidate_windows
+        B, L = x.shape
+        if fused is not None:                                       # the parents' tower output, once per pass
+            parent_out = fused.parent_tower(x)
+        for p0 in range(0, P, Pc):
+            pc = min(Pc, P - p0)
+            n = B * K * pc
+            cand = ws.cand[:n * L].view(B, K * pc, L)
+            flags = ws.flags[:n]
+            if fused is None:                                       # whole mutants through score_fn; a copy's entry is its parent's score
+                ops.pattern_mutants(x, pos_dev[p0:p0 + pc], pat_dev, widths_dev, live, cand=cand, want_onehot=False, err=ws.err)
+                candidate_windows(cand, x, flags=flags)             # flags > 0: the mutant differs from its parent
+                slot = torch.where(flags > 0, ws.iota[:n], ws.iota[:n] - n)
+                ops.pattern_fold(score_fn(cand.view(n, L)), parent_score, P, K, p0, pc, slot=slot, live=live, table=table, best=best)
+                continue
+            onehot = None if ws.onehot is None else ws.onehot[:n * L * 4].view(n, L, 4)
+            ops.pattern_mutants(x, pos_dev[p0:p0 + pc], pat_dev, widths_dev, live, cand=cand, onehot=onehot, want_onehot=False, err=ws.err)
+            live_idx, slot = ws.live_idx[:n], ws.slot[:n]
+            win = fused.tower_ranges_of(cand, x, key=flags)
+            ops.compact_flags(flags, live_idx, slot, ws.count)
+            sc = fused.forward_candidates_from(onehot, cand, win, parent_out, live_idx=live_idx, count=ws.count)
+            sc = sc.reshape(n, -1)
+            sc = sc.reshape(n) if sc.shape[1] == 1 else sc[:, 0].contiguous()
+            ops.pattern_fold(sc, parent_score, P, K, p0, pc, slot=slot, live=live, table=table, best=best)
+
+    @torch.no_grad()
+    def pattern_scores(self, x, patterns, pre_scorer_embedding, pre_scorer_head, reward_model=None, positions=None, compare=None,
+                       chunk_rows=None):
+        """Pattern scanning (reference design.py evolve(method="pattern")'s table; grelu's MotifScanDataset restated): the score of
+        every row of x [B, L] (tokens 0..3, on the GPU) with each of `patterns` written into it at each start position -> fp32
+        [B, P, K]; entry (b, j, k) is the score of row b with x[b, positions[j] : positions[j] + w_k] overwritten by pattern k
+        (a replacement: the length stays L). A mutant that equals its parent has the parent's score, the same bits (on the
+        windowed route it is not computed). patterns: a list of strings over ACGT and / or integer sequences over 0..3, widths 1..32, possibly different
+        (motifs.consensus_patterns gives such a list). positions: None = every start at which the longest pattern fits
+        (0 .. L - w_max), or a strictly ascending list of such starts. compare, reward_model: as ism_scores. chunk_rows: mutant rows
+        per value-net pass (whole positions, never fewer than one; default 32 x the CU count). Per chunk of positions:
+        svdd_pattern_mutants, the value net (a fused ConvGRU net at 104 < L <= 208 computes each mutant's tower on the rows around
+        the positions it changed, the same bits as the whole tower), svdd_pattern_fold. No mutant and no score crosses to the host."""
+        if compare not in self.ISM_COMPARE:
+            raise ValueError(f"compare = {compare!r}: expected None, 'subtract', 'divide' or 'log2FC'")
+        x_u8, pos_dev, pat_dev, widths_dev, P, K, Pc = self._pattern_inputs(x, patterns, reward_model, positions, chunk_rows,
+                                                                             "pattern_scores")
+        B, L = x_u8.shape
+        score_fn, fused = self._ism_route(pre_scorer_embedding, pre_scorer_head, reward_model, L)
+        ws = self._pattern_workspace(B, L, K, Pc, fused)
+        parent_score = score_fn(x_u8)
+        table = torch.empty((B, P, K), dtype=torch.float32, device=self.device)
+        self._pattern_pass(x_u8, pos_dev, pat_dev, widths_dev, P, K, Pc, score_fn, fused, ws, parent_score, table=table)
+        ops.check_pattern_err(ws.err)
+        if compare is not None:
+            ref = parent_score[:, None, None]
+            table = table - ref if compare == "subtract" else table / ref if compare == "divide" else torch.log2(table / ref)
+        return table
+
+    @torch.no_grad()
+    def evolve_patterns(self, x, patterns, pre_scorer_embedding, pre_scorer_head, reward_model=None, max_iter=10, positions=None,
+                        stop="global", chunk_rows=None):
+        """Greedy directed evolution on the pattern table (reference design.py evolve(method="pattern", for_each=True)): per
+        iteration every row's P K pattern mutants are scored (pattern_scores' path) and the row's best one (the first in (position,
+        pattern) order among equal scores; a NaN never) is its pick. A pick may be a no-op: a pattern that is already there, with
+        the row's own score.
+          stop = "global"  the reference's rule: every row takes its pick whether or not it improves on the row's score; the run
+                           stops at the first iteration whose best pick over the batch does not beat the best seen so far (that
+                           iteration changes no row but is in the trace).
+          stop = "row"     a row takes its pick only if it strictly beats the row's score, otherwise it stops for good (its mutants
+                           are not computed again); the run stops at the iteration in which no row moved.
+        -> (x_best int64 [B, L], score_best fp32 [B], trace), evolve's contract: the highest-scoring state along each row's
+        trajectory (the first among equals) and trace = {"iters", "position" (the pick's start position), "pattern" (index into
+        `patterns`), "taken": [iters, B] (-1 / -1 / 0: a row without a pick), "score": [iters + 1, B]}. max_iter = 0 returns the
+        input and its score. Per iteration one pass folded into a per-row best and one svdd_pattern_apply launch; the host reads the
+        one `stopped` word per iteration and nothing else before the end."""
+        if stop not in ops.EVOLVE_STOP:
+            raise ValueError(f"stop = {stop!r}: expected 'global' or 'row'")
+        max_iter = int(max_iter)
+        if max_iter < 0:
+            raise ValueError(f"max_iter must be >= 0, got {max_iter}")
+        x_u8, pos_dev, pat_dev, widths_dev, P, K, Pc = self._pattern_inputs(x, patterns, reward_model, positions, chunk_rows,
+                                                                             "evolve_patterns")
+        x_u8 = x_u8.clone()
+        B, L = x_u8.shape
+        dev = self.device
+        score_fn, fused = self._ism_route(pre_scorer_embedding, pre_scorer_head, reward_model, L)
+        ws = self._pattern_workspace(B, L, K, Pc, fused)
+        score_cur = score_fn(x_u8).clone()
+        x_best, score_best = x_u8.clone(), score_cur.clone()
+        neg = torch.full_like(score_cur, float("-inf"))
+        best_so_far = torch.where(score_cur != score_cur, neg, score_cur).max().reshape(1)   # iteration 0 of the reference: the inputs
+        stopped = torch.zeros(1, dtype=torch.int32, device=dev)
+        live = torch.ones(B, dtype=torch.uint8, device=dev) if stop == "row" else None
+        best = (torch.empty(B, device=dev), torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+        rows = max(max_iter, 1)
+        tr_pos, tr_pat = (torch.full((rows, B), -1, dtype=torch.int32, device=dev) for _ in range(2))
+        tr_taken = torch.zeros((rows, B), dtype=torch.uint8, device=dev)
+        tr_score = torch.empty((rows + 1, B), dtype=torch.float32, device=dev)
+        tr_score[0] = score_cur
+        iters = 0
+        for it in range(max_iter):
+            self._pattern_pass(x_u8, pos_dev, pat_dev, widths_dev, P, K, Pc, score_fn, fused, ws, score_cur, live=live, best=best)
+            ops.pattern_apply(best, pos_dev, pat_dev, widths_dev, x_u8, score_cur, best_so_far, stopped, x_best, score_best, stop=stop,
+                              live=live, trace=(tr_pos[it], tr_pat[it], tr_score[it + 1], tr_taken[it]))
+            iters = it + 1
+            if int(stopped[0]) != 0:                                # the one word the host reads per iteration
+                break
+        ops.check_pattern_err(ws.err)
+        trace = {"iters": iters, "position": tr_pos[:iters], "pattern": tr_pat[:iters], "taken": tr_taken[:iters],
+                 "score": tr_score[:iters + 1]}
+        return x_best.long(), score_best, trace
+
     # ------------------------------------------------------------- gradient attributions ----
     ATTR_METHODS = ("gradient", "inputxgradient", "integratedgradients")
     ATTR_CHUNK_ROWS = 1024                # default rows per gradient pass: mean_score_input_grad's work buffers (save, gates, out, gout,

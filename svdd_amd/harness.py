@@ -206,6 +206,20 @@ class BaseModel(nn.Module):
         return self.ref_model.evolve(samples, self.embedding, self.head, reward_model=self.reward_model, max_iter=max_iter,
                                      positions=positions, stop=stop)
 
+    @torch.no_grad()
+    def pattern_scan(self, samples, patterns, positions=None, compare=None):
+        """What each of `patterns` is worth at each start position of finished designs under the harness's reward model (reference
+        design.py evolve(method="pattern")'s table): samples [B, L] tokens 0..3 -> fp32 [B, P, K] (Diffusion.pattern_scores)."""
+        return self.ref_model.pattern_scores(samples, patterns, self.embedding, self.head, reward_model=self.reward_model,
+                                             positions=positions, compare=compare)
+
+    @torch.no_grad()
+    def evolve_patterns(self, samples, patterns, max_iter=10, positions=None, stop="global"):
+        """Pattern-driven directed evolution of samples [B, L] under the harness's reward model (reference design.py
+        evolve(method="pattern", for_each=True); Diffusion.evolve_patterns) -> (x_best int64 [B, L], score_best fp32 [B], trace)."""
+        return self.ref_model.evolve_patterns(samples, patterns, self.embedding, self.head, reward_model=self.reward_model,
+                                              max_iter=max_iter, positions=positions, stop=stop)
+
     def get_attributions(self, samples, method="inputxgradient", **kw):
         """Per-nucleotide attributions of samples [B, L] under the harness's reward model (reference score.py get_attributions;
         Diffusion.attributions: method "gradient" / "inputxgradient" / "integratedgradients", baseline, n_steps, quadrature,

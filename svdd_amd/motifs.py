@@ -324,6 +324,24 @@ def scan_rows(x, mset, strands="both", chunk_rows=None):
     return (row_hits,) + ops.motif_best_decode(row_best)
 
 
+def consensus_patterns(mset, names=None):
+    """-> a list of uint8 token arrays, one per motif of `names` (None: every motif, in the set's order): the highest log-odds base
+    of each of the motif's `width` columns, the lowest base among equal entries. A consensus scores the motif's max_score on the
+    forward strand, so Diffusion.evolve_patterns(x, consensus_patterns(mset, ["HNF1A"]), ...) implants sites scan_rows finds.
+    No device."""
+    _mset(mset)
+    if names is None:
+        idx = range(len(mset))
+    else:
+        if isinstance(names, str):
+            names = [names]
+        missing = [n for n in names if n not in mset.names]
+        if missing:
+            raise ValueError(f"consensus_patterns: no motif named {missing} in the set")
+        idx = [mset.names.index(n) for n in names]
+    return [mset.pwm[m, :int(mset.width[m])].argmax(1).astype(np.uint8) for m in idx]      # argmax: the first among equals
+
+
 def _per(per):
     if per not in ("row", "site"):
         raise ValueError(f"per = {per!r}: expected 'row' or 'site'")

@@ -371,6 +371,106 @@ def evolve_apply(best, x, score_cur, best_so_far, stopped, x_best, score_best, s
               tp, ta, ts, tt, _this_stream())
 
 
+def _pattern_args(patterns, widths):
+    """patterns u8 [K, 32] and widths i32 [K] of the three pattern entries -> K."""
+    _need(patterns, torch.uint8, "patterns"), _need(widths, torch.int32, "widths")
+    K = widths.numel()
+    _is(patterns, torch.uint8, (K, _lib.PATTERN_MAX_WIDTH), "patterns"), _is(widths, torch.int32, (K,), "widths")
+    return K
+
+
+def pattern_mutants(x, positions, patterns, widths, live=None, cand=None, onehot=None, want_onehot=True, err=None):
+    """svdd_pattern_mutants: the P K pattern mutants of every row of x u8 [B, L]: mutant (b, j, k) = row b with
+    x[b, positions[j] : positions[j] + widths[k]] overwritten by patterns[k, :widths[k]] (the pattern index runs fastest).
+    positions i32 [P] (device, ascending starts), patterns u8 [K, 32], widths i32 [K]. -> (cand u8 [B, P K, L], onehot f32
+    [B * P K, L, 4] | None). live u8 [B]: a row with live[b] == 0 gets exact copies. err: a caller-zeroed device int32 [1] the kernel
+    sets for a parent token > 3, a pattern token > 3 or a window that leaves the row (checked by the caller later with
+    check_pattern_err); None: checked here (one synchronisation)."""
+    x = _need(x, torch.uint8, "x").contiguous()
+    if x.dim() != 2:
+        raise SvddError(f"x must be u8 [B, L], got {tuple(x.shape)}")
+    B, L = x.shape
+    positions = _need(positions, torch.int32, "positions").contiguous()
+    P = positions.numel()
+    K = _pattern_args(patterns, widths)
+    dev = x.device
+    if live is not None:
+        _is(live, torch.uint8, (B,), "live")
+    cand = torch.empty((B, P * K, L), dtype=torch.uint8, device=dev) if cand is None else _is(cand, torch.uint8, (B, P * K, L), "cand")
+    if onehot is None and want_onehot:
+        onehot = torch.empty((B * P * K, L, 4), dtype=torch.float32, device=dev)
+    elif onehot is not None:
+        _is(onehot, torch.float32, (B * P * K, L, 4), "onehot")
+    check_here = err is None
+    if check_here:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.call("svdd_pattern_mutants", x, positions, patterns, widths, live, B, L, P, K, cand, onehot, err, _this_stream())
+    if check_here:
+        check_pattern_err(err)
+    return cand, onehot
+
+
+def check_pattern_err(err):
+    """Raise if svdd_pattern_mutants flagged a token > 3 in a row or a pattern, or a pattern that does not fit at a position."""
+    if int(err[0]) != 0:
+        _lib.check(_lib.E_ARG, "svdd_pattern_mutants: a row or a pattern holds a token > 3, or a pattern's window lies outside 0..L-1")
+
+
+def pattern_fold(scores, parent_score, P, K, p0, Pc, slot=None, live=None, table=None, best=None):
+    """svdd_pattern_fold: fold the scores of the mutants of positions[p0 : p0 + Pc] into table f32 [B, P, K] (or None) and the
+    running best = (best_score f32 [B], best_pos i32 [B]: the index into positions, best_pattern i32 [B]) (or None). scores: dense
+    f32 [B, Pc K], or with slot (i32 [B * Pc K], svdd_compact_flags' map) the compacted scores: mutant i has scores[slot[i]], or
+    the parent's score where slot[i] < 0. The chunk with p0 == 0 starts the running best at (-inf, -1, -1); fold in ascending p0."""
+    parent_score = _need(parent_score, torch.float32, "parent_score")
+    B = parent_score.numel()
+    P, K, p0, Pc = int(P), int(K), int(p0), int(Pc)
+    _is(parent_score, torch.float32, (B,), "parent_score")
+    scores = _need(scores, torch.float32, "scores")
+    if not scores.is_contiguous() or (slot is None and scores.numel() != B * Pc * K):
+        raise SvddError(f"pattern_fold: scores must be contiguous f32 [{B}, {Pc * K}], got {tuple(scores.shape)}")
+    if slot is not None:
+        _is(slot, torch.int32, (B * Pc * K,), "slot")
+    if live is not None:
+        _is(live, torch.uint8, (B,), "live")
+    if table is not None:
+        _is(table, torch.float32, (B, P, K), "table")
+    bs = bp = bk = None
+    if best is not None:
+        bs, bp, bk = best
+        _is(bs, torch.float32, (B,), "best_score"), _is(bp, torch.int32, (B,), "best_pos"), _is(bk, torch.int32, (B,), "best_pattern")
+    _lib.call("svdd_pattern_fold", scores, slot, parent_score, live, B, P, K, p0, Pc, table, bs, bp, bk, _this_stream())
+
+
+def pattern_apply(best, positions, patterns, widths, x, score_cur, best_so_far, stopped, x_best, score_best, stop="global", live=None,
+                  trace=None):
+    """svdd_pattern_apply, one iteration's boundary of pattern-driven evolution, one launch: best = (best_score, best_pos,
+    best_pattern) of svdd_pattern_fold; x u8 [B, L], score_cur f32 [B], live u8 [B] (required for stop = "row"), best_so_far f32
+    [1], stopped i32 [1], x_best u8 [B, L], score_best f32 [B] are updated in place; trace = (start position i32 [B], pattern i32
+    [B], score f32 [B], taken u8 [B]) of this iteration or None. Nothing is written once stopped[0] != 0."""
+    if stop not in EVOLVE_STOP:
+        raise ValueError(f"stop = {stop!r}: expected 'global' or 'row'")
+    _need(x, torch.uint8, "x")
+    B, L = x.shape
+    positions = _need(positions, torch.int32, "positions")
+    P = positions.numel()
+    _is(positions, torch.int32, (P,), "positions")
+    K = _pattern_args(patterns, widths)
+    bs, bp, bk = best
+    _is(bs, torch.float32, (B,), "best_score"), _is(bp, torch.int32, (B,), "best_pos"), _is(bk, torch.int32, (B,), "best_pattern")
+    _is(x, torch.uint8, (B, L), "x"), _is(x_best, torch.uint8, (B, L), "x_best")
+    _is(score_cur, torch.float32, (B,), "score_cur"), _is(score_best, torch.float32, (B,), "score_best")
+    _is(best_so_far, torch.float32, (1,), "best_so_far"), _is(stopped, torch.int32, (1,), "stopped")
+    if live is not None:
+        _is(live, torch.uint8, (B,), "live")
+    tp = tk = ts = tt = None
+    if trace is not None:
+        tp, tk, ts, tt = trace
+        _is(tp, torch.int32, (B,), "trace position"), _is(tk, torch.int32, (B,), "trace pattern")
+        _is(ts, torch.float32, (B,), "trace score"), _is(tt, torch.uint8, (B,), "trace taken")
+    _lib.call("svdd_pattern_apply", bs, bp, bk, positions, patterns, widths, B, L, P, K, EVOLVE_STOP[stop], x, score_cur, live,
+              best_so_far, stopped, x_best, score_best, tp, tk, ts, tt, _this_stream())
+
+
 ATTR_MODE = {"gradient": _lib.ATTR_GRADIENT, "times_input": _lib.ATTR_TIMES_INPUT}
 
 
