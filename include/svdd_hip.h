@@ -894,6 +894,23 @@ int svdd_candidate_parts(const uint8_t* cand, const uint8_t* x, int B, int L, in
 int svdd_conv_tower_parts_f32(const float* onehot, const float* tiles, const float* bias, const int32_t* parts,
                               const float* parent_out, float* out, int n, int L, int M, int nlayers, int residual_mask,
                               int reach, const int32_t* live_idx, const int32_t* count, void* on_stream);
+/* svdd_value_late_step_f32 — the fp32 value net (parts tower, GRU, tail) on a compacted, size-ordered list of live candidates that may
+ *   exceed ONE round of the GRU's (16 sequences, direction) units on the chip's CUs, as two parts sized ON THE DEVICE:
+ *   count3 [3] i32 = what svdd_compact_by_key wrote for this `split` (live entries, of them in the first part <= split, in the second);
+ *   A = entries [0, count3[1]) of live_idx, B = entries [split, split + count3[2]) — B is non-empty only when A is full.
+ *       tower(B) -> [ GRU(B) || tower(A) ] in ONE launch -> GRU(A) -> tail(rows 0 .. count3[0])
+ *   The middle launch runs the GRU kernel's body in its leading workgroups and the parts tower's body in the others, so B's GRU — a
+ *   second round with most of the chip idle — hides under A's tower. No host decision, no event, no second stream: a launch whose
+ *   part is empty leaves at its count check. onehot, tiles, bias, parts, parent_out, M, nlayers, residual_mask, reach, live_idx: as
+ *   svdd_conv_tower_parts_f32 over the n = B * M candidates; wpack, bpack: as svdd_gru_bidir_f32; w1pack, b1, w_eff, b_eff, n_tasks:
+ *   as svdd_value_tail_f32. seq [n][L][64], h [2][n][L][64]: work buffers (row i = list entry i); out [n][n_tasks]: the scores of
+ *   entries 0 .. count3[0], the SAME BITS as the three entries named above give for them; rows from count3[0] on are not written.
+ *   0 < split < n. All four launches go to `on_stream`. */
+int svdd_value_late_step_f32(const float* onehot, const float* tiles, const float* bias, const int32_t* parts,
+                             const float* parent_out, float* seq, int n, int L, int M, int nlayers, int residual_mask, int reach,
+                             const int32_t* live_idx, const int32_t* count3, int split, const float* wpack, const float* bpack,
+                             float* h, const float* w1pack, const float* b1, const float* w_eff, const float* b_eff, float* out,
+                             int n_tasks, void* on_stream);
 
 /* svdd_backbone_cnn_f32 — the whole dilated-CNN masked-diffusion backbone at sigma = 0 in ONE launch
  *   (reference models/dnaconv.py:176-210 as called from diffusion_gosai.py:334-340): one-hot + 9-tap first conv,
@@ -1000,6 +1017,17 @@ int svdd_backbone_incr4_f32(const uint8_t* x, const float* table0, const float* 
                             float* out, int n, int L, int nlayers, const int* dilations, int lead, float* planes,
                             uint8_t* x_prev, int32_t* items, unsigned long long* stat, int first, int max_item,
                             int32_t* order, int32_t* order_count, int depth, uint8_t* x_prev2, int parity, void* on_stream);
+/* svdd_backbone_incr_seed_f32 — the state a first != 0 call of the entries above leaves on n IDENTICAL rows, broadcast from ONE row's
+ *   state in one launch (the prior of a decode is n all-MASK rows; what the backbone makes of that row depends on the weights alone,
+ *   so a caller computes it once with a first != 0 call at n = 1 and keeps it while the weights stand).
+ *   row_planes [depth][1][208][128] f32, row_logits [L][5] f32, row_x [L] u8: planes, `out` and carried tokens of that one-row call.
+ *   Writes rows < L of every row of planes [depth][n][208][128] (rows >= L are never written), out [n][L][5], and the n token rows of
+ *   the buffer `parity` names (0 = x_prev, 1 = x_prev2; x_prev2 may be NULL with parity 0: the entries without the pair) — the same
+ *   bits as the first != 0 forward of n copies of row_x; like that forward it writes neither the other token buffer nor a list nor
+ *   stat, and the next call passes the same parity. 104 < L <= 208, 1 <= depth <= 32, row_planes and planes 16-byte aligned. The
+ *   launch goes to `on_stream` (passed by the caller, as for the entries above); profile slot 6 records it as one span. */
+int svdd_backbone_incr_seed_f32(const float* row_planes, const float* row_logits, const uint8_t* row_x, int n, int L, int depth,
+                                float* planes, float* out, uint8_t* x_prev, uint8_t* x_prev2, int parity, void* on_stream);
 int svdd_backbone_incr_set_residency(int wg_per_cu);
 /* svdd_backbone_set_workspace — caller-owned scratch for the small-batch form of svdd_backbone_cnn_f32 (several workgroups per
  * sequence exchange the LayerNorm'd image of every layer through it): ws = device memory of `bytes` >= n_max * (2 * 208 * 128 * 4

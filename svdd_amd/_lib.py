@@ -158,6 +158,8 @@ SIGNATURES = {
     "svdd_pattern_mutants": (vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp),
     "svdd_pattern_fold": (vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp),
     "svdd_pattern_apply": (vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp),
+    "svdd_backbone_incr_seed_f32": (vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp),
+    "svdd_value_late_step_f32": (vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp),
 }
 EXPORTS = tuple(SIGNATURES)
 

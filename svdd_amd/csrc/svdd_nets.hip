@@ -150,11 +150,13 @@ __global__ __launch_bounds__(BOTH ? 512 : 256) void gru_bidir_kernel(const float
 // at n = 2560 — the step stays at ~1.8 us against the 1.28 us the 96 MFMAs of a wave pair need; wave priorities
 // (s_setprio 3 for the consumers) changed nothing.
 // (The 16-bit twin gru_lp_kernel, svdd_lp_gru_tail.hip, was built this way first.)
-__global__ __launch_bounds__(512) void gru_pc_kernel(const float* __restrict__ x, const float* __restrict__ wpack,
-                                                     const float* __restrict__ bpack, float* __restrict__ out,
-                                                     int n_alloc, int L, const int* __restrict__ count) {
-  __shared__ __attribute__((aligned(16))) float hbuf[2][TS][HPAD];
-  __shared__ __attribute__((aligned(16))) float xproj[2][4][3][64 * 4];        // [slot][wave][gate][lane x 4]
+// The body is a device function so that gru_tower_parts_kernel (below the parts tower) can run it in its LEADING workgroups (the unit
+// is blockIdx.x in both kernels); hbuf / xproj: the workgroup's LDS (GRU_PC_LDS_FLOATS in all).
+constexpr int GRU_PC_LDS_FLOATS = 2 * TS * HPAD + 2 * 4 * 3 * 64 * 4;
+__device__ __forceinline__ void gru_pc_body(const float* __restrict__ x, const float* __restrict__ wpack,
+                                            const float* __restrict__ bpack, float* __restrict__ out, int n_alloc, int L,
+                                            const int* __restrict__ count, float (*hbuf)[TS][HPAD],
+                                            float (*xproj)[4][3][64 * 4]) {
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const bool producer = wv >= 4;
@@ -268,6 +270,14 @@ __global__ __launch_bounds__(512) void gru_pc_kernel(const float* __restrict__ x
     }
     __syncthreads();
   }
+}
+
+__global__ __launch_bounds__(512) void gru_pc_kernel(const float* __restrict__ x, const float* __restrict__ wpack,
+                                                     const float* __restrict__ bpack, float* __restrict__ out,
+                                                     int n_alloc, int L, const int* __restrict__ count) {
+  __shared__ __attribute__((aligned(16))) float hbuf[2][TS][HPAD];
+  __shared__ __attribute__((aligned(16))) float xproj[2][4][3][64 * 4];        // [slot][wave][gate][lane x 4]
+  gru_pc_body(x, wpack, bpack, out, n_alloc, L, count, hbuf, xproj);
 }
 
 // ------------------------------------------------------------------ fused conv epilogue + LayerNorm ----
@@ -1442,9 +1452,10 @@ __device__ __forceinline__ void tower_parts_layer(const TowerCtx2& c, int layer,
   __syncthreads();                                               // the image is complete
 }
 
-__global__ __launch_bounds__(512, 4) void conv_tower_parts_kernel(TowerPartArgs pa) {
+// The body is a device function so that gru_tower_parts_kernel can run it in the workgroups behind its GRU units: blk = the
+// workgroup's place in this launch's list, smem its dynamic LDS (tower2_lds_bytes).
+__device__ __forceinline__ void tower_parts_body(const TowerPartArgs& pa, unsigned blk, float* smem) {
   const TowerArgs& a = pa.t;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
   __shared__ int tl[TP_BLOCKS + 1][TP_LT];              // per layer: the tile origins of all parts, then their number
   float* act = smem + TW_AP;                            // rows -1 .. TW_ROWS, by SEQUENCE row ; [-1] and [TW_ROWS] are zero where read
   float* xs = smem + (TW_ROWS + 2) * TW_AP + 8 * 4;     // one-hot rows -8 .. TW_ROWS + 8
@@ -1452,9 +1463,9 @@ __global__ __launch_bounds__(512, 4) void conv_tower_parts_kernel(TowerPartArgs 
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int L = a.L, R = pa.reach, nl = a.nlayers;
-  if (pa.count && (int)blockIdx.x >= __builtin_amdgcn_readfirstlane(*pa.count)) return;
-  int cand = blockIdx.x;
-  if (pa.live_idx) cand = __builtin_amdgcn_readfirstlane(pa.live_idx[blockIdx.x]);
+  if (pa.count && (int)blk >= __builtin_amdgcn_readfirstlane(*pa.count)) return;
+  int cand = blk;
+  if (pa.live_idx) cand = __builtin_amdgcn_readfirstlane(pa.live_idx[blk]);
   int np = 0, p0[TP_PARTS], p1[TP_PARTS];               // the parts, clamped into the sequence (whatever the array holds)
 #pragma unroll
   for (int p = 0; p < TP_PARTS; ++p) {
@@ -1463,7 +1474,7 @@ __global__ __launch_bounds__(512, 4) void conv_tower_parts_kernel(TowerPartArgs 
     p0[p] = min(max(f, 0), L - 1); p1[p] = min(max(l, p0[p]), L - 1);
     if (f >= 0 && np == p) np = p + 1;                  // parts are listed without holes
   }
-  float* outc = a.out + (size_t)blockIdx.x * L * TW_C;
+  float* outc = a.out + (size_t)blk * L * TW_C;
   {
     const float* par = pa.parent_out + (size_t)(cand / pa.M) * L * TW_C;
     for (int e = tid; e < L * 16; e += 512) {           // rows that are the parent's, straight from its output
@@ -1535,6 +1546,34 @@ __global__ __launch_bounds__(512, 4) void conv_tower_parts_kernel(TowerPartArgs 
       *reinterpret_cast<float4*>(outc + (size_t)row * TW_C + 4 * q) = *reinterpret_cast<const float4*>(act + row * TW_AP + 4 * q);
     }
   }
+}
+
+__global__ __launch_bounds__(512, 4) void conv_tower_parts_kernel(TowerPartArgs pa) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  tower_parts_body(pa, blockIdx.x, smem);
+}
+
+// The middle launch of a two-part late step (svdd_value_late_step_f32): workgroups 0 .. gru_units - 1 run gru_pc_kernel's body on the
+// second part's rows, the workgroups behind them conv_tower_parts_kernel's body on the first part's list. The GRU units come first:
+// the dispatcher hands workgroups out in index order and their 200-step chains are the longest thing in the launch. Their LDS
+// (33 KB) lies in the launch's dynamic LDS, which is the tower's (57 KB): as static LDS it would cost the tower its second workgroup
+// per CU. Same bodies, same rows: same bits.
+struct GruPartArgs {
+  const float *x, *wpack, *bpack;
+  float* out;
+  int n_alloc, L;
+  const int* count;
+};
+static_assert(GRU_PC_LDS_FLOATS <= (TW_ROWS + 2) * TW_AP, "the GRU unit's LDS must fit into the tower's image");
+
+__global__ __launch_bounds__(512, 4) void gru_tower_parts_kernel(GruPartArgs ga, TowerPartArgs pa, unsigned gru_units) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  if (blockIdx.x < gru_units) {
+    gru_pc_body(ga.x, ga.wpack, ga.bpack, ga.out, ga.n_alloc, ga.L, ga.count, reinterpret_cast<float (*)[TS][HPAD]>(smem),
+                reinterpret_cast<float (*)[4][3][64 * 4]>(smem + 2 * TS * HPAD));
+    return;
+  }
+  tower_parts_body(pa, blockIdx.x - gru_units, smem);
 }
 
 // --------------------------------------------------------- fused dilated-CNN backbone (one launch per forward) ----
@@ -2466,6 +2505,26 @@ __global__ __launch_bounds__(256, NC_ == 4 ? 2 : NC_ == 1 ? 4 : 3) void backbone
 __global__ __launch_bounds__(256, 5) void backbone_seg_tight_kernel(BackboneSegArgs a) {
   using LAY = SegTight;
 #include "svdd_seg_body.h"
+}
+
+// svdd_backbone_incr_seed_f32: the state a first = 1 forward leaves on n IDENTICAL rows, from one row's planes, logits and tokens (the
+// prior of a decode is n all-MASK rows, and what the backbone makes of that row depends on the weights alone). A plain broadcast,
+// grid-stride: rows < L of every carried plane as 16-byte vectors (the 1 MB source stays in L2), then the logits, then the tokens.
+__global__ __launch_bounds__(256) void backbone_seed_kernel(const float4* __restrict__ row_planes, const float* __restrict__ row_logits,
+                                                            const uint8_t* __restrict__ row_x, int n, int L, int depth,
+                                                            float4* __restrict__ planes, float* __restrict__ out,
+                                                            uint8_t* __restrict__ x_cur) {
+  const int rowv = L * (BB_C / 4), planev = TW_ROWS * (BB_C / 4);       // vectors of a sequence's L rows / of a whole plane row
+  const int tid = threadIdx.x;
+  for (int pr = blockIdx.x; pr < depth * n; pr += gridDim.x) {         // pr = plane * n + row (depth * n < 2^31: the entry checks)
+    const float4* src = row_planes + (size_t)(pr / n) * planev;
+    float4* dst = planes + (size_t)pr * planev;
+    for (int e = tid; e < rowv; e += 256) dst[e] = src[e];
+  }
+  for (int r = blockIdx.x; r < n; r += gridDim.x) {
+    for (int e = tid; e < L * 5; e += 256) out[(size_t)r * (L * 5) + e] = row_logits[e];
+    for (int e = tid; e < L; e += 256) x_cur[(size_t)r * L + e] = row_x[e];
+  }
 }
 
 // ------------------------------------------- gradient of the backbone with respect to its one-hot input, ONE launch (round 5) ----
@@ -3530,6 +3589,20 @@ extern "C" int svdd_backbone_incr4_f32(const uint8_t* x, const float* table0, co
                                             max_item, order, order_count, depth, x_prev2, parity, on_stream});
 }
 
+extern "C" int svdd_backbone_incr_seed_f32(const float* row_planes, const float* row_logits, const uint8_t* row_x, int n, int L,
+                                           int depth, float* planes, float* out, uint8_t* x_prev, uint8_t* x_prev2, int parity,
+                                           void* on_stream) {
+  if (!row_planes || !row_logits || !row_x || !planes || !out || !x_prev || n <= 0 || L <= TW_ROWS / 2 || L > TW_ROWS || depth <= 0 ||
+      depth > BB_MAXL || (parity != 0 && parity != 1) || (parity == 1 && !x_prev2) || x_prev2 == x_prev ||
+      (long long)depth * n > 0x7fffffffLL || ((uintptr_t)row_planes | (uintptr_t)planes) % 16 != 0)
+    return SVDD_E_ARG;
+  const long long units = (long long)depth * n;           // one workgroup per (plane, row), grid-stride beyond 2^20 of them
+  SvddSpan span(SVDD_SLOT_BACKBONE);
+  return svdd_launch_timed(span.all(), backbone_seed_kernel, dim3((unsigned)(units < (1 << 20) ? units : (1 << 20))), dim3(256), 0, on_stream,
+                           reinterpret_cast<const float4*>(row_planes), row_logits, row_x, n, L, depth, reinterpret_cast<float4*>(planes), out,
+                           parity ? x_prev2 : x_prev);
+}
+
 typedef decltype(&value_tail_kernel<1>) ValueTailKernel;
 
 extern "C" int svdd_value_tail_f32(const float* h_fwd, const float* h_bwd, const float* w1pack, const float* b1,
@@ -3599,4 +3672,54 @@ extern "C" int svdd_conv_tower_parts_f32(const float* onehot, const float* tiles
   TowerPartArgs pa{TowerArgs{onehot, tiles, bias, out, n, L, 1, nlayers, residual_mask, nullptr}, parts, parent_out, M, reach, live_idx, count};
   SvddSpan span(SVDD_SLOT_CONV_TOWER);
   return svdd_launch_timed(span.all(), conv_tower_parts_kernel, dim3((unsigned)n), dim3(512), svdd_lds_raised(tower2_lds_bytes()), on_stream, pa);
+}
+
+// The value net on a compacted, size-ordered list of live candidates that may exceed one round of the GRU's units, as two parts sized
+// on the device (count3 of svdd_compact_by_key with this `split`): A = the first count3[1] <= split entries, B = the count3[2] behind
+// them (non-empty only when A is full, so the live rows are contiguous).
+//     tower(B) -> [ GRU(B) || tower(A) ] in one launch (gru_tower_parts_kernel) -> GRU(A) -> tail(all count3[0] rows)
+// B's GRU — a second round that would run with 3/4 of the chip idle — hides under A's tower. A launch whose part is empty leaves at
+// its count check. Same kernels' bodies on the same rows as the one-part sequence: the same bits per candidate.
+extern "C" int svdd_value_late_step_f32(const float* onehot, const float* tiles, const float* bias, const int32_t* parts,
+                                        const float* parent_out, float* seq, int n, int L, int M, int nlayers, int residual_mask,
+                                        int reach, const int32_t* live_idx, const int32_t* count3, int split, const float* wpack,
+                                        const float* bpack, float* h, const float* w1pack, const float* b1, const float* w_eff,
+                                        const float* b_eff, float* out, int n_tasks, void* on_stream) {
+  if (!onehot || !tiles || !bias || !parts || !parent_out || !seq || !live_idx || !count3 || !wpack || !bpack || !h || !w1pack || !b1 ||
+      !w_eff || !b_eff || !out || n <= 0 || M <= 0 || L <= TW_ROWS / 2 || L > TW_ROWS || nlayers != TP_BLOCKS || reach != TP_REACH ||
+      split <= 0 || split >= n || n_tasks < 1 || n_tasks > 4)
+    return SVDD_E_ARG;
+  const size_t rowf = (size_t)L * TW_C;                   // floats of one row of seq and of one direction of h (TW_C = H = 64)
+  const int nb = n - split;
+  const unsigned units_a = 2 * (unsigned)((split + TS - 1) / TS), units_b = 2 * (unsigned)((nb + TS - 1) / TS);
+  const SvddLds lds = svdd_lds_raised(tower2_lds_bytes());
+  const TowerPartArgs tb{TowerArgs{onehot, tiles, bias, seq + split * rowf, nb, L, 1, nlayers, residual_mask, nullptr}, parts, parent_out, M,
+                         reach, live_idx + split, count3 + 2};
+  const TowerPartArgs ta{TowerArgs{onehot, tiles, bias, seq, split, L, 1, nlayers, residual_mask, nullptr}, parts, parent_out, M, reach,
+                         live_idx, count3 + 1};
+  const GruPartArgs gb{seq + split * rowf, wpack, bpack, h + split * rowf, n, L, count3 + 2};
+  ValueTailKernel tail;
+  switch (n_tasks) {
+    case 1: tail = value_tail_kernel<1>; break;
+    case 2: tail = value_tail_kernel<2>; break;
+    case 3: tail = value_tail_kernel<3>; break;
+    default: tail = value_tail_kernel<4>; break;
+  }
+  int rc;
+  {
+    SvddSpan span(SVDD_SLOT_CONV_TOWER);
+    rc = svdd_launch_timed(span.all(), conv_tower_parts_kernel, dim3((unsigned)nb), dim3(512), lds, on_stream, tb);
+  }
+  if (rc != SVDD_OK) return rc;
+  {
+    SvddSpan span(SVDD_SLOT_GRU);                         // one span over the middle launch (A's tower included) and A's GRU
+    rc = svdd_launch_timed(span.first(), gru_tower_parts_kernel, dim3(units_b + (unsigned)split), dim3(512), lds, on_stream, gb, ta, units_b);
+    if (rc != SVDD_OK) return rc;
+    rc = svdd_launch_timed(span.last(), gru_pc_kernel, dim3(units_a), dim3(512), 0, on_stream, (const float*)seq, wpack, bpack, h, n, L,
+                           count3 + 1);
+  }
+  if (rc != SVDD_OK) return rc;
+  SvddSpan span(SVDD_SLOT_VALUE_TAIL);
+  return svdd_launch_timed(span.all(), tail, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, on_stream, (const float*)h,
+                           (const float*)(h + (size_t)n * rowf), w1pack, b1, w_eff, b_eff, out, n, L, count3);
 }

@@ -62,8 +62,8 @@ Engine knobs (attributes; defaults reproduce the reference's observable behaviou
                    across the steps and recomputes, per step, only the 16-row tiles a changed token can reach
                    (svdd_backbone_incr2_f32; the remaining layers run from the last carried plane). Same logits bit for bit
                    (tests/test_backbone_incremental_gpu.py). "on": wherever the kernels apply, whatever the batch; "off". Off under
-                   graph capture. The first forward of such a decode runs on all B rows (it fills the planes): dedup_prior does not
-                   apply to it.
+                   graph capture. The first forward of such a decode fills the planes of all B rows: with dedup_prior it is one
+                   broadcast of the all-MASK row's cached planes and logits (svdd_backbone_incr_seed_f32), else the whole forward.
   incremental_depth  how many conv layers the incremental backbone carries: an int from the leading run of dilation-1 layers (8)
                    up to the end of the dilation-4 run behind them (12; svdd_backbone_incr3_f32 — a change has reached +- 52 .. 100
                    rows there), or "auto" (default) = fused.INCR_DEPTH_AUTO, the depth the measurement of
@@ -77,6 +77,9 @@ Engine knobs (attributes; defaults reproduce the reference's observable behaviou
                    kernels a row's net output does not depend on the batch around it — so the FIRST backbone forward of a decode, the
                    parents' first value / reward score and their first tower pass run on one row and are broadcast. Bit-identical to
                    forwarding all B rows (tests/test_skip_gpu.py); one backbone launch of 129 and a value-net pass less per decode.
+                   In the SVDD-MC skipping loop that one row's results are constants of the weights and are computed once, not once
+                   per decode: the fused nets keep them (fused.PriorSeeds, dropped with the nets when the weights change) and a
+                   decode broadcasts them (tests/test_prior_seed_gpu.py). False switches all of it off.
   dps_one_launch   True (default): the differentiable backbone pass of a DPS step (forward2 on one_hot(x_t) + its input gradient) is ONE
                    launch each way (fp32, CNN backbone, 104 < L <= 208): the forward is the inference kernel bit for bit, so its logits
                    also give q_xs and the reference's second, identical forward (:1306 vs :1324) is not run. False: the layer-wise
@@ -314,10 +317,16 @@ class Diffusion(nn.Module):
         self.fuse_nets = True
         self.precision = "f32"
         self.skip_unchanged = True
-        self.late_steps_from = "auto"    # when FusedValueNet may run the live candidates as two parts (split_gru_rounds): "auto" = when the LAST
-                                         # step's live count (read back asynchronously, never waited for) came within 3 % of one GRU round;
-                                         # a number = from that fraction of the steps on (rounds 4-5: 0.8, tuned to the random-init benchmark)
+        self.late_steps_from = os.environ.get("SVDD_LATE_STEPS_FROM") or "auto"   # (the environment variable: A/B runs)
+                                         # when FusedValueNet may run the live candidates as two parts (split_gru_rounds): "auto" = on every
+                                         # step, as one fixed launch sequence whose parts the DEVICE sizes from the step's live counts
+                                         # (svdd_value_late_step_f32; nothing is read back); a number = the host-decided side-stream form
+                                         # from that fraction of the steps on (rounds 4-5: 0.8, tuned to the random-init benchmark; A/B)
         self.dedup_prior = True          # the prior's rows are identical (all MASK): its net evaluations run on ONE row (exact; see _prior_logits)
+        self.seed_prior = os.environ.get("SVDD_SEED_PRIOR", "1") != "0"   # SVDD-MC skipping loop with dedup_prior: the all-MASK row's results (carried
+                                         # planes, logits, tower output, score) come from the fused nets' per-weights cache and a decode
+                                         # broadcasts them; False (A/B; the environment variable sets what a new model starts with):
+                                         # the row is evaluated once per decode and the first stem forward runs on all B rows
         self.dps_fused = True            # DPS: the whole step on hand-written kernels, no autograd (_dps_fused_nets); False: round 5's autograd path between the same big kernels
         self.dps_one_launch = True       # DPS: the differentiable backbone pass as one launch each way (svdd_backbone_cnn_save_f32 / _grad_f32) where it applies
         self._dps_hard_onehot, self._dps_raw_logits, self._dps_logp = False, None, None
@@ -2100,7 +2109,9 @@ class Diffusion(nn.Module):
             self.n_live = torch.zeros(1, dtype=torch.int64, device=dev)
             self.n_changed = torch.zeros(1, dtype=torch.int64, device=dev)
             self.late = False                   # set by the sampler per step: the live candidates may exceed one GRU round (FusedValueNet.split_gru_rounds)
-            self.split_bufs = None              # persistent buffers + side stream of that path
+            self.late_on_device = False         # ... and the device sizes the two parts (FusedValueNet._late_step), not the host
+            self.split_bufs = None              # persistent buffers (+ side stream) of that path
+            self.prior_parent_out = None        # the all-MASK row's cached tower output [1, L, 64], where the sampler seeds from it
             self.prior_rows_identical = False   # set by the sampler when x is the prior: the parents' first tower pass runs on one row
             self.n_win_rows = None          # with skip_stats: rows the value net's tower computed (the candidates' row windows; with per-layer
                                             # ranges the FLOP-equivalent number of full-depth rows) ...
@@ -2175,28 +2186,36 @@ class Diffusion(nn.Module):
             ws.n_tile_layers = torch.zeros(1, dtype=torch.int64, device=self.device)
         from .fused import FusedValueNet
         dedup = self._prior_dedup_ok(x) and isinstance(fn, FusedValueNet)   # the parents are B copies of the all-MASK row
-        ws.parent_score.copy_(fn.forward_tokens(x[:1].contiguous()).reshape(1).expand(B) if dedup
-                              else fn.forward_tokens(x).reshape(B))          # scores of the all-MASK parents
-        ws.prior_rows_identical = dedup                                      # -> the parents' first tower pass too (FusedValueNet)
-        fb = self._fused_backbone_or_none(L) if self._use_logits_cache(L) else None
         share = hasattr(fn, "candidates_ok") and fn.candidates_ok(L, M)
+        if dedup and self.seed_prior:   # that row's score and tower output are constants of the weights: computed once (FusedValueNet.prior_score), broadcast
+            ws.parent_score.copy_(fn.prior_score(L, self.mask_index).expand(B))
+            ws.prior_parent_out = fn.prior_tower(L, self.mask_index) if share else None
+        elif dedup:                     # ... or once per decode, on one row
+            ws.parent_score.copy_(fn.forward_tokens(x[:1].contiguous()).reshape(1).expand(B))
+        else:
+            ws.parent_score.copy_(fn.forward_tokens(x).reshape(B))           # scores of the parents
+        ws.prior_rows_identical = dedup                                      # -> the parents' tower output too (candidate_scores_compact)
+        fb = self._fused_backbone_or_none(L) if self._use_logits_cache(L) else None
         toks_c = None if share else torch.empty((B * M, L), dtype=torch.uint8, device=self.device)
         logits = None
         inc, stem = (None, None) if fb is not None else self._incremental_stem(B, L)
         if stem is not None:
             stem.stat.zero_()
             stem.forwards = 0
-        # the two-part late steps adapt to the decode in hand: the live count of a step is copied to pinned host memory without
-        # waiting; a later step looks at the newest count that has arrived (a trained value net, another M or L, another chip change
-        # when the live candidates outgrow one GRU round — the fixed "last 20 % of the steps" of rounds 4-5 fitted random-init nets)
+            if self.seed_prior and self._prior_dedup_ok(x):
+                # the first forward fills the planes with B copies of what the all-MASK row gives — a constant of the weights, kept
+                # by the fused backbone (prior_row): one broadcast launch leaves the stem and the logits as that forward would
+                logits = inc.seed_incremental(stem, mask=self.mask_index)
+        # the two-part late steps adapt to the decode in hand ON THE DEVICE: every step issues the same launches
+        # (FusedValueNet._late_step) and the live counts the compaction leaves there size them — a trained value net, another M or L,
+        # another chip change when the live candidates outgrow one GRU round, and a count read back by the host, which runs many
+        # steps ahead of the GPU, came too late to say (profiles/prior_seed_late_steps_trace.txt)
         auto_late = share and self.late_steps_from == "auto" and not _capturing() and hasattr(fn, "gru_round_rows")
-        if auto_late:
-            live_host = torch.empty(1, dtype=torch.int32).pin_memory()
-            live_ev, live_pending, live_last = torch.cuda.Event(), False, 0
-            late_thr = 0.97 * fn.gru_round_rows()
+        ws.late_on_device = auto_late
         for i in range(S):
             if inc is not None:                                               # only the stem tiles the last select's tokens reach
-                logits = inc.forward_incremental(x, stem, out=logits)
+                if i > 0 or not stem.valid:                                   # (step 0 of a seeded stem: its logits are there)
+                    logits = inc.forward_incremental(x, stem, out=logits)
             elif fb is None or logits is None:
                 logits = self._prior_logits(x) if i == 0 else self._backbone_logits(x)
             else:                                                             # only the rows the last select changed
@@ -2205,17 +2224,11 @@ class Diffusion(nn.Module):
             ops.propose(logits, x, sched[i, 2], sched[i, 1], M, self._rng(i, M, B, L, logits), cand=cand, onehot=onehot)
             if share:
                 if auto_late:
-                    if live_pending and live_ev.query():
-                        live_last, live_pending = int(live_host[0]), False
-                    ws.late = live_last > late_thr
-                else:
+                    ws.late = True                                           # every step; the device sizes the second part (often empty)
+                else:                                                        # a number: the host-decided form from that fraction of the steps on
                     frac = 0.8 if self.late_steps_from == "auto" else float(self.late_steps_from)
                     ws.late = i >= int(frac * S)                             # late steps: (almost) every candidate is live
                 sc = fn.candidate_scores_compact(onehot, cand, x, ws).reshape(-1)
-                if auto_late and not live_pending:
-                    live_host.copy_(ws.count, non_blocking=True)
-                    live_ev.record()
-                    live_pending = True
             else:
                 candidate_windows(cand, x, margin=0, flags=ws.flags)
                 ops.compact_flags(ws.flags, ws.live_idx, ws.slot, ws.count)

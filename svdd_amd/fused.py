@@ -500,6 +500,45 @@ def backbone_cnn_incremental(tokens, pk, st, out=None, max_item=None):
     return out
 
 
+class PriorSeeds:
+    """What a net makes of ONE all-MASK row (the prior of every decode is B copies of it): a function of the weights and of the few
+    shape settings in the key, of nothing a sampler draws. Held BY the fused net (FusedBackbone.prior_seeds, FusedValueNet.prior_seeds),
+    which is itself the value of Diffusion's weight-validated cache: changed weights give a new fused net and with it an empty set.
+    `builds` counts what was computed (tests)."""
+    MOST = 4                                              # keys kept (a backbone row is ~1 MB per 10 carried layers)
+
+    def __init__(self):
+        self._rows, self.builds = {}, 0
+
+    def __len__(self):
+        return len(self._rows)
+
+    def get(self, key, build):
+        v = self._rows.get(key)
+        if v is None:
+            if len(self._rows) >= self.MOST:
+                self._rows.clear()
+            v = self._rows[key] = build()
+            self.builds += 1
+        return v
+
+
+def backbone_seed_incremental(st, row, out=None):
+    """Leaves the carried stem `st` (and `out` [n, L, 5]) as the first forward of n copies of one row leaves them, from that row's state
+    `row` = (planes [depth, 1, 208, 128], logits [1, L, 5], tokens [1, L]; FusedBackbone.prior_row): svdd_backbone_incr_seed_f32, one
+    broadcast launch instead of the whole forward on every row. Same bits in every plane, in the tokens and in `out`."""
+    planes, logits, tok = row
+    depth = st.lead + st.deep
+    assert tuple(planes.shape) == (depth, 1, 208, 128) and tuple(logits.shape) == (1, st.L, 5) and tuple(tok.shape) == (1, st.L)
+    if out is None:
+        out = torch.empty((st.n, st.L, 5), dtype=torch.float32, device=planes.device)
+    parity = st.parity if (st.tight and INCR_MAX_ITEM == 2) else 0        # the buffer backbone_cnn_incremental's entry reads next
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _lib.call("svdd_backbone_incr_seed_f32", planes, logits, tok, st.n, st.L, depth, st.planes, out, st.x_prev, st.x_prev2, parity, stream)
+    st.valid = True
+    return out
+
+
 LP_DTYPES = {"f16x3": (torch.float16, 2), "bf16x3": (torch.bfloat16, 2), "f16": (torch.float16, 1), "bf16": (torch.bfloat16, 1)}
 
 
@@ -820,7 +859,8 @@ class FusedValueNet(nn.Module):
         self.use_fused_tail = True
         self.share_parent_tower = True
         self.split_gru_rounds = True         # candidate_scores_compact, late steps: the live candidates as two parts so that the GRU's second round
-                                             # hides under the first part's tower (same bits; _windows_gru_tail_split)
+                                             # hides under the first part's tower (same bits; _late_step: the parts sized on the device,
+                                             # one launch sequence on every step; _windows_gru_tail_split: the host-decided form)
         self.sort_live_by_window = True      # candidate_scores_compact: live candidates ordered by window size, largest first (A/B knob; same bits)
         self.tight_windows = True            # fp32 windowed tower: windows aligned at one end only (candidate_windows(tight=True); A/B knob; same bits).
                                              # Reached only with tower_parts = "off": the parts path has no windows
@@ -844,6 +884,22 @@ class FusedValueNet(nn.Module):
         self._ln_eps = d1.norm.layer.eps
         self.keep_grad_pass = False          # tests: mean_score_input_grad leaves its tower activations, GRU outputs, tail gradient and result in
         self.last_grad_pass = None           # last_grad_pass (the buffers it worked on: no launch and no copy more)
+        self.prior_seeds = PriorSeeds()      # the all-MASK row's tower output and score (prior_value)
+
+    def prior_score(self, L, mask=4):
+        """Score [1] fp32 of ONE all-`mask` row of length L: the parent score of a decode's prior, computed once per (L, precision,
+        mask) for this module, i.e. for these weights (PriorSeeds) — by forward_tokens on that row, so the same bits."""
+        def build():
+            tok = torch.full((1, L), int(mask), dtype=torch.uint8, device=self.tw_bias.device)
+            return self.forward_tokens(tok).reshape(1).clone()
+        return self.prior_seeds.get(("score", int(L), self.precision, int(mask)), build)
+
+    def prior_tower(self, L, mask=4):
+        """Tower output [1, L, 64] (in the module's precision) of that row: the parents' tower output of a decode's first step
+        (candidate_scores_compact), by parent_tower on the row, cached like prior_score."""
+        def build():
+            return self.parent_tower(torch.full((1, L), int(mask), dtype=torch.uint8, device=self.tw_bias.device))
+        return self.prior_seeds.get(("tower", int(L), self.precision, int(mask)), build)
 
     def lp_ok(self, L):
         return self.precision != "f32" and self.tower_ok and self.tail_ok and L <= 208
@@ -972,6 +1028,8 @@ class FusedValueNet(nn.Module):
         # 487 -> 395 us per launch on a C2 decode's states, tools/tower_order_probe.py). A row's result does not depend on its
         # place in the compacted batch: same bits, same tokens.
         split = self._gru_split(B * M) if (self.precision == "f32" and getattr(ws, "late", False)) else 0
+        if split and getattr(ws, "late_on_device", False) and win.dim() != 3:
+            split = 0                                     # the device-sized form runs the parts tower; with windows: one part
         if split:
             ops.compact_by_key(ws.flags, ws.live_idx, ws.slot, ws.count3, split=split)
         else:
@@ -991,9 +1049,13 @@ class FusedValueNet(nn.Module):
         lp = self.precision != "f32"
         if ws.parent_out is None or ws.parent_out_lp != self.precision:
             # (the parents of the first step are B copies of the all-MASK row: one row through the tower, broadcast — a row's output
-            #  does not depend on the batch around it; Diffusion.dedup_prior)
+            #  does not depend on the batch around it; Diffusion.dedup_prior. That row's output is a constant of the weights:
+            #  ws.prior_parent_out, where the sampler set it, is prior_value's cached copy and no tower pass runs at all)
             xp = x[:1].contiguous() if getattr(ws, "prior_rows_identical", False) else x
-            if lp:
+            seeded = getattr(ws, "prior_parent_out", None) if xp is not x else None
+            if seeded is not None:
+                po = seeded
+            elif lp:
                 pk = self._lp_pack()
                 po = conv_tower_lp(xp, pk["tiles"], self.tw_bias, pk["tinv"], self.tw_resmask, pk["prec"])
             else:
@@ -1006,6 +1068,8 @@ class FusedValueNet(nn.Module):
             ws.seq = conv_tower_windows_lp(cand, win, ws.parent_out, pk["tiles"], self.tw_bias, pk["tinv"], self.tw_resmask,
                                            pk["prec"], live_idx=ws.live_idx, count=ws.count)
             return self._after_tower_lp(ws.seq, pk, ws.count)[:, :, 0]
+        if split and win.dim() == 3 and getattr(ws, "late_on_device", False):
+            return self._late_step(onehot, win, ws, B * M, L, M, split)
         if split:
             return self._windows_gru_tail_split(onehot, win, ws, B * M, L, M, split)
         ws.seq = conv_tower_windows(onehot, win, ws.parent_out, M, self.tw_tiles, self.tw_bias, self.tw_resmask,
@@ -1014,6 +1078,8 @@ class FusedValueNet(nn.Module):
 
     GRU_ROUND_ROWS = None        # rows of ONE round of the GRU's (tile of 16 sequences, direction) units on this chip's CUs; None: from
                                  # the device (gru_round_rows: 8 x CUs = 2048 on MI355X's 256), an int: override (tests, A/B)
+
+    GRU_SECOND_PART = (5, 16)    # _gru_split: the second part may hold at most this fraction of a round (tests widen it)
 
     def gru_round_rows(self):
         """One workgroup = 16 sequences in one direction, one workgroup per CU per round: a round covers CUs / 2 tiles = 8 x CUs rows."""
@@ -1030,10 +1096,34 @@ class FusedValueNet(nn.Module):
         if not (self.split_gru_rounds and self.use_fused_tail and self.tail_ok) or torch.cuda.is_current_stream_capturing():
             return 0
         r = self.gru_round_rows()
-        return r if r < n <= r + (5 * r) // 16 else 0
+        num, den = self.GRU_SECOND_PART
+        return r if r < n <= r + (num * r) // den else 0
+
+    def _late_step(self, onehot, parts, ws, n, L, M, split):
+        """The two-part form sized ON THE DEVICE (svdd_value_late_step_f32): with ws.count3 from compact_by_key(split=split),
+             tower(B) -> [GRU(B) || tower(A)] in one launch -> GRU(A) -> tail(all live rows),
+        B = the list's entries from `split` on, non-empty only when the live candidates outgrow one GRU round. No host decision, no
+        event, no side stream: the sampler issues it on EVERY step of a decode whose B * M exceeds one round, and a launch whose
+        part is empty leaves at its count check. Same bodies on the same rows as the one-part path: the same bits per candidate."""
+        dev = onehot.device
+        key = ("late", n, L, str(dev))
+        cache = self.__dict__.setdefault("_split_bufs", {})
+        sb = cache.get(key)
+        if sb is None:
+            cache.clear()                                 # one set of buffers at a time (decodes on one stream follow each other)
+            sb = cache[key] = dict(seq=torch.empty((n, L, 64), device=dev), h=torch.empty((2, n, L, 64), device=dev),
+                                   sc=torch.empty((n, self.w_eff.shape[1]), device=dev))
+        ws.split_bufs = sb
+        _lib.call("svdd_value_late_step_f32", onehot, self.tw_tiles, self.tw_bias, parts, ws.parent_out, sb["seq"], n, L, M,
+                  self.tw_bias.shape[0] - 1, int(self.tw_resmask), TOWER_REACH, ws.live_idx, ws.count3, split, self.wpack, self.bpack,
+                  sb["h"], self.w1pack, self.b1f, self.w_eff, self.b_eff, sb["sc"], self.w_eff.shape[1],
+                  ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        ws.seq = sb["seq"]
+        return sb["sc"][:, 0]
 
     def _windows_gru_tail_split(self, onehot, win, ws, n, L, M, split):
-        """The late steps of a decode have more live candidates than ONE round of the GRU's (tile, direction) units on the chip's
+        """The host-decided two-part form (Diffusion.late_steps_from = a number; the default is _late_step): the late steps of a
+        decode have more live candidates than ONE round of the GRU's (tile, direction) units on the chip's
         CUs (2048 rows on 256): the launch then takes two rounds, the second with 3/4 of the chip idle (0.67 instead of 0.36 ms).
         Here the compacted list runs as two parts: B = the entries from `split` on (the smallest windows, the list being sorted),
         A = the first `split`:   tower(B) -> [GRU(B), tail(B) on a side stream || tower(A)] -> GRU(A) -> tail(A).
@@ -1218,6 +1308,7 @@ class FusedBackbone(nn.Module):
         self._lp = {}
         self._grad_pack = None
         self._incr = {}
+        self.prior_seeds = PriorSeeds()                 # the all-MASK row's carried planes and logits (prior_row)
         if self.one_launch:
             pk = pack_backbone(cnn)
             self.ol_dil = pk.pop("dil")
@@ -1270,6 +1361,22 @@ class FusedBackbone(nn.Module):
 
     def forward_incremental(self, tok, st, out=None):
         return backbone_cnn_incremental(tok, self.ol_pack(), st, out)
+
+    def prior_row(self, L, depth, tight=False, mask=4):
+        """(planes [depth, 1, 208, 128], logits [1, L, 5], tokens [1, L]) of ONE all-`mask` row of length L after the first forward of
+        a one-row carried stem of `depth` layers — computed once per (L, depth, tight, mask) for this module, i.e. for these weights
+        (PriorSeeds). The first forward is one workgroup per sequence at any batch size: the bits of a row of a larger batch."""
+        def build():
+            lead, dev = leading_dilation1(self.ol_dil), self.ol_tiles.device
+            st = IncrementalStem(1, L, lead, dev, int(depth) - lead, tight)
+            tok = torch.full((1, L), int(mask), dtype=torch.uint8, device=dev)
+            logits = backbone_cnn_incremental(tok, self.ol_pack(), st)
+            return st.planes, logits, tok
+        return self.prior_seeds.get((int(L), int(depth), bool(tight), int(mask)), build)
+
+    def seed_incremental(self, st, out=None, mask=4):
+        """forward_incremental's first forward for a batch of all-`mask` rows (a decode's prior), from the cached row."""
+        return backbone_seed_incremental(st, self.prior_row(st.L, st.lead + st.deep, st.tight, mask), out)
 
     def _lp_pack(self):
         """Operand images of svdd_backbone_cnn_lp for self.precision (packed on first use)."""
