@@ -22,7 +22,9 @@
 //   K20 ledidi_step_kernel  Ledidi design: one iteration's boundary (losses, best-so-far, AdamW on the logit weights, the next
 //       iteration's Gumbel-softmax samples) around the unchanged scoring and gradient passes
 //   K21 pattern_mutants_kernel / K22 pattern_fold_kernel / K23 pattern_apply_kernel  pattern scanning: K15-K17 with a pattern of
-//       up to 32 tokens written at a start position in place of one base
+//       up to 32 tokens written at a start position in place of one base. The two kinds share their device code (the one-hot
+//       emit, a mutant's score, the fold's tail, the evolve decision and trace writes: store4_onehot .. evolve_trace); a kind keeps
+//       its copy loop, its pick's validity and the order of the pick's writes
 //   K4 tds_resample_kernel  SMC/TDS resampling (baseline)
 #include <float.h>
 #include <stdlib.h>
@@ -1298,7 +1300,131 @@ __global__ __launch_bounds__(256) void value_target_kernel(ValueTargetArgs a) {
   if (lane == 0) a.target[b] = out;
 }
 
-// ------------------------------------------------- K15-K17 in-silico mutagenesis and ISM-driven evolution (under ABI 17) ----
+// ------------------------------------------------- K15-K17 / K21-K23 mutant scans: what the two kinds share (under ABI 17) ----
+// In-silico mutagenesis (K15-K17) and pattern scanning (K21-K23) are one algorithm over two kinds of mutant. Defined once here:
+// the one-hot emit, a mutant's score, the fold's tail and the evolve decision with its trace writes. A kind keeps its own copy loop,
+// the decoding of a winning index, the validity of a pick and the order in which a taken pick is written.
+__device__ __forceinline__ float4 attr_onehot(uint32_t t) {
+  return make_float4(t == 0u ? 1.0f : 0.0f, t == 1u ? 1.0f : 0.0f, t == 2u ? 1.0f : 0.0f, t == 3u ? 1.0f : 0.0f);
+}
+
+// The one-hot rows of the four tokens tok4 at l0 .. l0 + 3 (K15, K21).
+template <bool VEC>
+__device__ __forceinline__ void store4_onehot(float* oh, int l0, int L, uint32_t tok4) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float4 v = attr_onehot((tok4 >> (8 * i)) & 0xFFu);
+    if (VEC) {
+      reinterpret_cast<float4*>(oh)[l0 + i] = v;
+    } else if (l0 + i < L) {
+      float* o = oh + (int64_t)(l0 + i) * 4;
+      o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+    }
+  }
+}
+
+// Mutant i's score (K16, K22): dense, or through svdd_compact_flags' map, where a negative slot (a copy) has the parent's score ps.
+__device__ __forceinline__ float mutant_score(const float* scores, const int32_t* slot, int64_t i, float ps) {
+  if (!slot) return scores[i];
+  const int sl = slot[i];
+  return sl >= 0 ? scores[sl] : ps;
+}
+
+// The fold's tail (K16, K22). Every lane comes with its own best (bs, order index bi or -1) under `strictly greater`; the wave
+// reduces by comparison on (score, index), the smaller index winning equal scores, and lane 0 merges with the running best of
+// the earlier chunks (p0 > 0), which wins a tie because it comes first. A NaN compares false everywhere: it never wins.
+// decode(bi, first, second) turns the winning order index into the two integers the kind stores.
+template <class Decode>
+__device__ __forceinline__ void fold_tail(float bs, int bi, int lane, int p0, int64_t b, float* best_score, int32_t* best_first,
+                                          int32_t* best_second, Decode decode) {
+#pragma unroll
+  for (int off = WAVE / 2; off > 0; off >>= 1) {
+    const float os = __shfl_xor(bs, off, WAVE);
+    const int oi = __shfl_xor(bi, off, WAVE);
+    if (os > bs || (os == bs && oi >= 0 && (bi < 0 || oi < bi))) { bs = os; bi = oi; }
+  }
+  if (lane != 0) return;
+  float rs = -INFINITY;
+  int r1 = -1, r2 = -1;
+  if (p0 > 0) { rs = best_score[b]; r1 = best_first[b]; r2 = best_second[b]; }
+  if (bi >= 0 && bs > rs) { rs = bs; decode(bi, r1, r2); }
+  best_score[b] = rs; best_first[b] = r1; best_second[b] = r2;
+}
+
+// What K17 and K23 share of their arguments: the picks' scores, the evolution state and this iteration's trace row (tr_pick: the
+// pick's allele / pattern index).
+struct EvolveState {
+  const float* best_score; int B, L, stop;
+  uint8_t* x; float* score_cur; uint8_t* live; float* best_so_far; int32_t* stopped; uint8_t* x_best; float* score_best;
+  int32_t* tr_pos; int32_t* tr_pick; float* tr_score; uint8_t* tr_taken;
+};
+
+// Phase 1 of K17 / K23, by ONE workgroup of 16 waves: a thread per row (strided) asks valid(b) of the row's pick; the batch maximum
+// (GLOBAL) or `any row takes` (ROW) is reduced by comparison through the waves and LDS; thread 0 settles best_so_far / stopped.
+// -> go, the same in every thread. Every global word another row's decision depends on (best_so_far, stopped) is read before the
+// first barrier, written after it by thread 0 only, and not read again.
+template <class Valid>
+__device__ __forceinline__ bool evolve_decide(const EvolveState& a, Valid valid) {
+  __shared__ float s_max[16];
+  __shared__ int s_any[16];
+  __shared__ int s_go;
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid >> 6;
+  const bool global = a.stop == SVDD_EVOLVE_GLOBAL;
+  float m = -INFINITY;
+  int any = 0;
+  for (int b = tid; b < a.B; b += 1024) {
+    const bool ok = valid(b);
+    const float s = a.best_score[b];
+    if (ok && global && s > m) m = s;
+    if (ok && !global && s > a.score_cur[b]) any = 1;
+  }
+#pragma unroll
+  for (int off = WAVE / 2; off > 0; off >>= 1) {
+    const float om = __shfl_xor(m, off, WAVE);
+    m = om > m ? om : m;
+    any |= __shfl_xor(any, off, WAVE);
+  }
+  if (lane == 0) { s_max[wave] = m; s_any[wave] = any; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 0; w < 16; ++w) { m = s_max[w] > m ? s_max[w] : m; any |= s_any[w]; }
+    int go;
+    if (global) {
+      go = m > a.best_so_far[0] ? 1 : 0;
+      if (go) a.best_so_far[0] = m; else a.stopped[0] = 1;
+    } else {
+      go = 1;
+      if (!any) a.stopped[0] = 1;
+    }
+    s_go = go;
+  }
+  __syncthreads();
+  return s_go != 0;
+}
+
+// Phase 2 of K17 / K23, row b by its wave alone. evolve_row: whether the row takes its pick (valid as phase 1 found it) and whether
+// that beats the row's best. evolve_trace: lane 0's writes of the trace (pos, pick: the pick's position and allele / pattern),
+// score_best and live. The row's bytes and score_cur are the caller's, and so is the order of the three.
+struct EvolveRow { bool lv, valid, take, better; float s, cur; };
+
+__device__ __forceinline__ EvolveRow evolve_row(const EvolveState& a, int b, bool go, bool valid) {
+  const bool lv = !a.live || a.live[b] != 0;
+  const float s = a.best_score[b], cur = a.score_cur[b], sb = a.score_best[b];
+  const bool take = valid && (a.stop == SVDD_EVOLVE_GLOBAL ? go : s > cur);
+  return {lv, valid, take, take && s > sb, s, cur};                 // better: the first occurrence of the row's highest score stays
+}
+
+__device__ __forceinline__ void evolve_trace(const EvolveState& a, int b, int lane, const EvolveRow& r, int pos, int pick) {
+  if (lane != 0) return;
+  if (a.tr_pos) a.tr_pos[b] = r.valid ? pos : -1;
+  if (a.tr_pick) a.tr_pick[b] = r.valid ? pick : -1;
+  if (a.tr_score) a.tr_score[b] = r.valid ? r.s : r.cur;
+  if (a.tr_taken) a.tr_taken[b] = r.take ? 1 : 0;
+  if (r.better) a.score_best[b] = r.s;
+  if (a.stop != SVDD_EVOLVE_GLOBAL && r.lv && !r.take) a.live[b] = 0;
+}
+
+// ------------------------------------------------- K15-K17 in-silico mutagenesis and ISM-driven evolution ----
 // K15 ism_mutants_kernel: one wave per mutant (b, j, k) = row b with position positions[j] replaced by the k-th base that is not
 // the parent's (ISMDataset(drop_ref=True) order). The wave copies the parent row four positions per lane and swaps the one byte;
 // a dead row (live[b] == 0), a parent token > 3 at the position or a position out of range gives an exact copy.
@@ -1332,27 +1458,14 @@ __global__ __launch_bounds__(256) void ism_mutants_kernel(IsmMutantsArgs a) {
       tok4 = (tok4 & ~(0xFFu << sh)) | (alt << sh);
     }
     store4_u8<VEC>(dst, l0, a.L, tok4);
-    if (!oh) continue;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const uint32_t t = (tok4 >> (8 * i)) & 0xFFu;
-      float4 v;
-      v.x = t == 0u ? 1.0f : 0.0f; v.y = t == 1u ? 1.0f : 0.0f; v.z = t == 2u ? 1.0f : 0.0f; v.w = t == 3u ? 1.0f : 0.0f;
-      if (VEC) {
-        reinterpret_cast<float4*>(oh)[l0 + i] = v;
-      } else if (l0 + i < a.L) {
-        float* o = oh + (int64_t)(l0 + i) * 4;
-        o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-      }
-    }
+    if (oh) store4_onehot<VEC>(oh, l0, a.L, tok4);
   }
   if (bad && a.err) a.err[0] = 1;
 }
 
 // K16 ism_fold_kernel: one wave per row folds one chunk of positions. A lane takes the chunk's positions j = lane, lane + 64, ...
-// in ascending order and keeps its own best (score, order index 4 (p0 + j) + allele) under `strictly greater`; the wave then
-// reduces by comparison on (score, index), the smaller index winning equal scores, and lane 0 merges with the running best of
-// the earlier chunks, which wins a tie because it comes first. A NaN compares false everywhere: it never wins.
+// in ascending order and keeps its own best (score, order index 4 (p0 + j) + allele) under `strictly greater`; fold_tail does
+// the rest.
 struct IsmFoldArgs {
   const float* scores; const int32_t* slot; const float* parent_score; const uint8_t* x; const int32_t* positions;
   const uint8_t* live; int B, L, P, p0, Pc;
@@ -1376,14 +1489,7 @@ __global__ __launch_bounds__(256) void ism_fold_kernel(IsmFoldArgs a) {
     if (ref <= 3u) {
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
-        const int64_t i = (b * a.Pc + j) * 3 + k;
-        float s;
-        if (a.slot) {
-          const int sl = a.slot[i];
-          s = sl >= 0 ? a.scores[sl] : ps;
-        } else {
-          s = a.scores[i];
-        }
+        const float s = mutant_score(a.scores, a.slot, (b * a.Pc + j) * 3 + k, ps);
         const int al = k + ((uint32_t)k >= ref ? 1 : 0);
 #pragma unroll
         for (int q = 0; q < 4; ++q) row[q] = q == al ? s : row[q];
@@ -1396,104 +1502,50 @@ __global__ __launch_bounds__(256) void ism_fold_kernel(IsmFoldArgs a) {
     }
   }
   if (!a.best_score) return;
-#pragma unroll
-  for (int off = WAVE / 2; off > 0; off >>= 1) {
-    const float os = __shfl_xor(bs, off, WAVE);
-    const int oi = __shfl_xor(bi, off, WAVE);
-    if (os > bs || (os == bs && oi >= 0 && (bi < 0 || oi < bi))) { bs = os; bi = oi; }
-  }
-  if (lane == 0) {
-    float rs = -INFINITY;
-    int rp = -1, ra = -1;
-    if (a.p0 > 0) { rs = a.best_score[b]; rp = a.best_pos[b]; ra = a.best_allele[b]; }
-    if (bi >= 0 && bs > rs) { rs = bs; rp = a.positions[bi >> 2]; ra = bi & 3; }
-    a.best_score[b] = rs; a.best_pos[b] = rp; a.best_allele[b] = ra;
-  }
+  fold_tail(bs, bi, lane, a.p0, b, a.best_score, a.best_pos, a.best_allele,
+            [&](int i, int& pos, int& al) { pos = a.positions[i >> 2]; al = i & 3; });
 }
 
-// K17 evolve_apply_kernel: ONE workgroup of 16 waves. Phase 1: a thread per row (strided) reads the row's pick and decides; the
-// batch maximum (GLOBAL) or `any row takes` (ROW) is reduced by comparison through the waves and LDS. Thread 0 settles
-// best_so_far / stopped. Phase 2: a wave per row (strided) writes the trace, applies the pick and keeps x_best. Every global
-// word another row's decision depends on (best_so_far, stopped) is read before the first barrier and written after the second;
-// score_cur / live of a row are read by that row's wave alone in phase 2 and by its phase-1 thread before the barriers.
-struct EvolveArgs {
-  const float* best_score; const int32_t* best_pos; const int32_t* best_allele; int B, L, stop;
-  uint8_t* x; float* score_cur; uint8_t* live; float* best_so_far; int32_t* stopped; uint8_t* x_best; float* score_best;
-  int32_t* tr_pos; int32_t* tr_allele; float* tr_score; uint8_t* tr_taken;
-};
+// K17 evolve_apply_kernel: evolve_decide, then a wave per row (strided) keeps x_best, writes the trace (evolve_trace) and applies
+// the pick. score_cur / live of a row are read by that row's wave alone in phase 2 and by its phase-1 thread before the
+// barriers.
+struct EvolveArgs { EvolveState s; const int32_t* best_pos; const int32_t* best_allele; };
+
+// The pick of row b -> valid, with its position and allele.
+__device__ __forceinline__ bool evolve_pick(const EvolveArgs& a, int b, int& pos, int& al) {
+  pos = a.best_pos[b];
+  al = a.best_allele[b];
+  return (!a.s.live || a.s.live[b] != 0) && pos >= 0 && pos < a.s.L && al >= 0 && al <= 3;
+}
 
 template <bool VEC>
 __global__ __launch_bounds__(1024) void evolve_apply_kernel(EvolveArgs a) {
-  __shared__ float s_max[16];
-  __shared__ int s_any[16];
-  __shared__ int s_go;
-  if (a.stopped[0] != 0) return;                                    // uniform: nothing is written once stopped
-  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid >> 6;
-  const bool global = a.stop == SVDD_EVOLVE_GLOBAL;
-  float m = -INFINITY;
-  int any = 0;
-  for (int b = tid; b < a.B; b += 1024) {
-    const int pos = a.best_pos[b], al = a.best_allele[b];
-    const bool valid = (!a.live || a.live[b] != 0) && pos >= 0 && pos < a.L && al >= 0 && al <= 3;
-    const float s = a.best_score[b];
-    if (valid && global && s > m) m = s;
-    if (valid && !global && s > a.score_cur[b]) any = 1;
-  }
-#pragma unroll
-  for (int off = WAVE / 2; off > 0; off >>= 1) {
-    const float om = __shfl_xor(m, off, WAVE);
-    m = om > m ? om : m;
-    any |= __shfl_xor(any, off, WAVE);
-  }
-  if (lane == 0) { s_max[wave] = m; s_any[wave] = any; }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 0; w < 16; ++w) { m = s_max[w] > m ? s_max[w] : m; any |= s_any[w]; }
-    int go;
-    if (global) {
-      go = m > a.best_so_far[0] ? 1 : 0;
-      if (go) a.best_so_far[0] = m; else a.stopped[0] = 1;
-    } else {
-      go = 1;
-      if (!any) a.stopped[0] = 1;
-    }
-    s_go = go;
-  }
-  __syncthreads();
-  const bool go = s_go != 0;
-  for (int b = wave; b < a.B; b += 16) {
-    const bool lv = !a.live || a.live[b] != 0;
-    const int pos = a.best_pos[b], al = a.best_allele[b];
-    const bool valid = lv && pos >= 0 && pos < a.L && al >= 0 && al <= 3;
-    const float s = a.best_score[b], cur = a.score_cur[b], sb = a.score_best[b];
-    const bool take = valid && (global ? go : s > cur);
-    const bool better = take && s > sb;                             // the first occurrence of the row's highest score stays
-    uint8_t* xr = a.x + (int64_t)b * a.L;
-    if (better) {                                                   // x_best[b, :] = the row with its pick applied
-      uint8_t* xb = a.x_best + (int64_t)b * a.L;
-      for (int l0 = lane * 4; l0 < a.L; l0 += 4 * WAVE) {
-        uint32_t tok4 = load4_u8<VEC>(xr, l0, a.L);
+  if (a.s.stopped[0] != 0) return;                                  // uniform: nothing is written once stopped
+  const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6, L = a.s.L;
+  const bool go = evolve_decide(a.s, [&](int b) { int pos, al; return evolve_pick(a, b, pos, al); });
+  for (int b = wave; b < a.s.B; b += 16) {
+    int pos, al;
+    const bool valid = evolve_pick(a, b, pos, al);
+    const EvolveRow r = evolve_row(a.s, b, go, valid);
+    uint8_t* xr = a.s.x + (int64_t)b * L;
+    if (r.better) {                                                 // x_best[b, :] = the row with its pick applied
+      uint8_t* xb = a.s.x_best + (int64_t)b * L;
+      for (int l0 = lane * 4; l0 < L; l0 += 4 * WAVE) {
+        uint32_t tok4 = load4_u8<VEC>(xr, l0, L);
         if (pos >= l0 && pos < l0 + 4) {
           const int sh = 8 * (pos - l0);
           tok4 = (tok4 & ~(0xFFu << sh)) | ((uint32_t)al << sh);
         }
-        store4_u8<VEC>(xb, l0, a.L, tok4);
+        store4_u8<VEC>(xb, l0, L, tok4);
       }
     }
-    if (lane == 0) {
-      if (a.tr_pos) a.tr_pos[b] = valid ? pos : -1;
-      if (a.tr_allele) a.tr_allele[b] = valid ? al : -1;
-      if (a.tr_score) a.tr_score[b] = valid ? s : cur;
-      if (a.tr_taken) a.tr_taken[b] = take ? 1 : 0;
-      if (better) a.score_best[b] = s;
-      if (!global && lv && !take) a.live[b] = 0;
-    }
+    evolve_trace(a.s, b, lane, r, pos, al);
     // the one byte of x goes last, by the lane that read its word above: no lane reads the row after this store
-    if (take && lane == ((pos >> 2) & (WAVE - 1))) { xr[pos] = (uint8_t)al; a.score_cur[b] = s; }
+    if (r.take && lane == ((pos >> 2) & (WAVE - 1))) { xr[pos] = (uint8_t)al; a.s.score_cur[b] = r.s; }
   }
 }
 
-// ------------------------------------------------- K21-K23 pattern scanning and pattern-driven evolution (under ABI 17) ----
+// ------------------------------------------------- K21-K23 pattern scanning and pattern-driven evolution ----
 // K15-K17 with a pattern of w <= 32 tokens written at a start position in place of one base. (Declared next to their siblings;
 // the numbers follow K20, the Ledidi step.)
 // Byte d (0 <= d < 32) of a pattern held as eight wave-uniform words: selects, no indexed register array.
@@ -1556,27 +1608,13 @@ __global__ __launch_bounds__(256) void pattern_mutants_kernel(PatternMutantsArgs
   for (int l0 = lane * 4; l0 < a.L; l0 += 4 * WAVE) {
     const uint32_t tok4 = pattern_merge(load4_u8<VEC>(src, l0, a.L), l0, pos, w, pw);
     store4_u8<VEC>(dst, l0, a.L, tok4);
-    if (!oh) continue;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const uint32_t t = (tok4 >> (8 * i)) & 0xFFu;
-      float4 v;
-      v.x = t == 0u ? 1.0f : 0.0f; v.y = t == 1u ? 1.0f : 0.0f; v.z = t == 2u ? 1.0f : 0.0f; v.w = t == 3u ? 1.0f : 0.0f;
-      if (VEC) {
-        reinterpret_cast<float4*>(oh)[l0 + i] = v;
-      } else if (l0 + i < a.L) {
-        float* o = oh + (int64_t)(l0 + i) * 4;
-        o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-      }
-    }
+    if (oh) store4_onehot<VEC>(oh, l0, a.L, tok4);
   }
   if (bad && a.err) a.err[0] = 1;
 }
 
 // K22 pattern_fold_kernel: K16 over the chunk's Pc K (position, pattern) entries. A lane takes the entries e = lane, lane + 64, ...
-// in ascending order and keeps its own best (score, order index p0 K + e) under `strictly greater`; the wave reduces by
-// comparison on (score, index), the smaller index winning equal scores, and lane 0 merges with the running best of the earlier
-// chunks, which wins a tie because it comes first. A NaN compares false everywhere: it never wins.
+// in ascending order and keeps its own best (score, order index p0 K + e) under `strictly greater`; fold_tail does the rest.
 struct PatternFoldArgs {
   const float* scores; const int32_t* slot; const float* parent_score; const uint8_t* live; int B, P, K, p0, Pc;
   float* table; float* best_score; int32_t* best_pos; int32_t* best_pattern;
@@ -1592,43 +1630,22 @@ __global__ __launch_bounds__(256) void pattern_fold_kernel(PatternFoldArgs a) {
   float bs = -INFINITY;
   int bi = -1;
   for (int e = lane; e < n; e += WAVE) {
-    const int64_t i = b * n + e;
-    float s;
-    if (a.slot) {
-      const int sl = a.slot[i];
-      s = sl >= 0 ? a.scores[sl] : ps;
-    } else {
-      s = a.scores[i];
-    }
+    const float s = mutant_score(a.scores, a.slot, b * n + e, ps);
     if (a.table) a.table[b * a.P * a.K + e0 + e] = s;
     if (offers && s > bs) { bs = s; bi = e0 + e; }
   }
   if (!a.best_score) return;
-#pragma unroll
-  for (int off = WAVE / 2; off > 0; off >>= 1) {
-    const float os = __shfl_xor(bs, off, WAVE);
-    const int oi = __shfl_xor(bi, off, WAVE);
-    if (os > bs || (os == bs && oi >= 0 && (bi < 0 || oi < bi))) { bs = os; bi = oi; }
-  }
-  if (lane == 0) {
-    float rs = -INFINITY;
-    int rp = -1, rk = -1;
-    if (a.p0 > 0) { rs = a.best_score[b]; rp = a.best_pos[b]; rk = a.best_pattern[b]; }
-    if (bi >= 0 && bs > rs) { rs = bs; rp = bi / a.K; rk = bi - rp * a.K; }
-    a.best_score[b] = rs; a.best_pos[b] = rp; a.best_pattern[b] = rk;
-  }
+  fold_tail(bs, bi, lane, a.p0, b, a.best_score, a.best_pos, a.best_pattern,
+            [&](int i, int& j, int& k) { j = i / a.K; k = i - j * a.K; });
 }
 
-// K23 pattern_apply_kernel: K17 with a pick (index into positions, pattern index) that writes widths[pattern] bytes. ONE
-// workgroup of 16 waves, the same two phases: every global word another row's decision depends on (best_so_far, stopped) is read
-// before the first barrier, written after it by thread 0 only, and not read again; score_cur / live of a row are read by that
-// row's phase-1 thread before the barriers and, in phase 2 (after the second), read and written by that row's wave alone. A word
-// of x is read by one lane only, which is the lane that then rewrites it.
+// K23 pattern_apply_kernel: K17 with a pick (index into positions, pattern index) that writes widths[pattern] bytes:
+// evolve_decide, then a wave per row (strided). score_cur / live of a row are read by that row's phase-1 thread before the
+// barriers and, in phase 2 (after the second), read and written by that row's wave alone. A word of x is read by one lane only,
+// which is the lane that then rewrites it.
 struct PatternApplyArgs {
-  const float* best_score; const int32_t* best_pos; const int32_t* best_pattern; const int32_t* positions; const uint8_t* patterns;
-  const int32_t* widths; int B, L, P, K, stop;
-  uint8_t* x; float* score_cur; uint8_t* live; float* best_so_far; int32_t* stopped; uint8_t* x_best; float* score_best;
-  int32_t* tr_pos; int32_t* tr_pattern; float* tr_score; uint8_t* tr_taken;
+  EvolveState s; const int32_t* best_pos; const int32_t* best_pattern; const int32_t* positions; const uint8_t* patterns;
+  const int32_t* widths; int P, K;
 };
 
 // The pick of row b -> valid, with its start position and width.
@@ -1637,79 +1654,35 @@ __device__ __forceinline__ bool pattern_pick(const PatternApplyArgs& a, int b, i
   k = a.best_pattern[b];
   pos = -1;
   w = 0;
-  if ((a.live && a.live[b] == 0) || j < 0 || j >= a.P || k < 0 || k >= a.K) return false;
+  if ((a.s.live && a.s.live[b] == 0) || j < 0 || j >= a.P || k < 0 || k >= a.K) return false;
   pos = a.positions[j];
   w = a.widths[k];
-  return w >= 1 && w <= SVDD_PATTERN_MAX_WIDTH && pos >= 0 && (int64_t)pos + w <= a.L;
+  return w >= 1 && w <= SVDD_PATTERN_MAX_WIDTH && pos >= 0 && (int64_t)pos + w <= a.s.L;
 }
 
 template <bool VEC>
 __global__ __launch_bounds__(1024) void pattern_apply_kernel(PatternApplyArgs a) {
-  __shared__ float s_max[16];
-  __shared__ int s_any[16];
-  __shared__ int s_go;
-  if (a.stopped[0] != 0) return;                                    // uniform: nothing is written once stopped
-  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid >> 6;
-  const bool global = a.stop == SVDD_EVOLVE_GLOBAL;
-  float m = -INFINITY;
-  int any = 0;
-  for (int b = tid; b < a.B; b += 1024) {
+  if (a.s.stopped[0] != 0) return;                                  // uniform: nothing is written once stopped
+  const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6, L = a.s.L;
+  const bool go = evolve_decide(a.s, [&](int b) { int pos, k, w; return pattern_pick(a, b, pos, k, w); });
+  for (int b = wave; b < a.s.B; b += 16) {
     int pos, k, w;
     const bool valid = pattern_pick(a, b, pos, k, w);
-    const float s = a.best_score[b];
-    if (valid && global && s > m) m = s;
-    if (valid && !global && s > a.score_cur[b]) any = 1;
-  }
-#pragma unroll
-  for (int off = WAVE / 2; off > 0; off >>= 1) {
-    const float om = __shfl_xor(m, off, WAVE);
-    m = om > m ? om : m;
-    any |= __shfl_xor(any, off, WAVE);
-  }
-  if (lane == 0) { s_max[wave] = m; s_any[wave] = any; }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 0; w < 16; ++w) { m = s_max[w] > m ? s_max[w] : m; any |= s_any[w]; }
-    int go;
-    if (global) {
-      go = m > a.best_so_far[0] ? 1 : 0;
-      if (go) a.best_so_far[0] = m; else a.stopped[0] = 1;
-    } else {
-      go = 1;
-      if (!any) a.stopped[0] = 1;
-    }
-    s_go = go;
-  }
-  __syncthreads();
-  const bool go = s_go != 0;
-  for (int b = wave; b < a.B; b += 16) {
-    const bool lv = !a.live || a.live[b] != 0;
-    int pos, k, w;
-    const bool valid = pattern_pick(a, b, pos, k, w);
-    const float s = a.best_score[b], cur = a.score_cur[b], sb = a.score_best[b];
-    const bool take = valid && (global ? go : s > cur);
-    const bool better = take && s > sb;                             // the first occurrence of the row's highest score stays
     uint32_t pw[SVDD_PATTERN_MAX_WIDTH / 4];
     const uint32_t* pk = reinterpret_cast<const uint32_t*>(a.patterns) + (int64_t)(valid ? k : 0) * (SVDD_PATTERN_MAX_WIDTH / 4);
 #pragma unroll
     for (int q = 0; q < SVDD_PATTERN_MAX_WIDTH / 4; ++q) pw[q] = pk[q];
-    uint8_t* xr = a.x + (int64_t)b * a.L;
-    uint8_t* xb = a.x_best + (int64_t)b * a.L;
-    if (lane == 0) {
-      if (a.tr_pos) a.tr_pos[b] = valid ? pos : -1;
-      if (a.tr_pattern) a.tr_pattern[b] = valid ? k : -1;
-      if (a.tr_score) a.tr_score[b] = valid ? s : cur;
-      if (a.tr_taken) a.tr_taken[b] = take ? 1 : 0;
-      if (better) a.score_best[b] = s;
-      if (!global && lv && !take) a.live[b] = 0;
-      if (take) a.score_cur[b] = s;
-    }
-    if (!take) continue;                                            // wave-uniform
+    const EvolveRow r = evolve_row(a.s, b, go, valid);
+    evolve_trace(a.s, b, lane, r, pos, k);
+    if (r.take && lane == 0) a.s.score_cur[b] = r.s;
+    if (!r.take) continue;                                          // wave-uniform
+    uint8_t* xr = a.s.x + (int64_t)b * L;
+    uint8_t* xb = a.s.x_best + (int64_t)b * L;
     // the row's bytes go last: a lane rewrites only the words it read itself, so no lane reads a word after its store
-    for (int l0 = lane * 4; l0 < a.L; l0 += 4 * WAVE) {
-      const uint32_t tok4 = pattern_merge(load4_u8<VEC>(xr, l0, a.L), l0, pos, w, pw);
-      if (better) store4_u8<VEC>(xb, l0, a.L, tok4);                // x_best[b, :] = the row with its pick applied
-      if (l0 + 4 > pos && l0 < pos + w) store4_u8<VEC>(xr, l0, a.L, tok4);
+    for (int l0 = lane * 4; l0 < L; l0 += 4 * WAVE) {
+      const uint32_t tok4 = pattern_merge(load4_u8<VEC>(xr, l0, L), l0, pos, w, pw);
+      if (r.better) store4_u8<VEC>(xb, l0, L, tok4);                // x_best[b, :] = the row with its pick applied
+      if (l0 + 4 > pos && l0 < pos + w) store4_u8<VEC>(xr, l0, L, tok4);
     }
   }
 }
@@ -1729,10 +1702,6 @@ __device__ __forceinline__ void attr_st4(float* p, float4 v) {
   } else {
     p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
   }
-}
-
-__device__ __forceinline__ float4 attr_onehot(uint32_t t) {
-  return make_float4(t == 0u ? 1.0f : 0.0f, t == 1u ? 1.0f : 0.0f, t == 2u ? 1.0f : 0.0f, t == 3u ? 1.0f : 0.0f);
 }
 
 // K18 attr_path_kernel: one thread per (output row, position), grid-stride. Output row i < n_rows is the global (row, step) pair
@@ -2835,8 +2804,8 @@ int svdd_evolve_apply(const float* best_score, const int32_t* best_pos, const in
   if ((const float*)score_cur == best_score || (const float*)score_best == best_score) return SVDD_E_ARG;
   const auto al = [](const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; };
   const bool vec = L % 4 == 0 && al(x, 4) && al(x_best, 4);
-  const EvolveArgs a{best_score, best_pos, best_allele, B, L, stop, x, score_cur, live, best_so_far, stopped, x_best, score_best,
-                     tr_pos, tr_allele, tr_score, tr_taken};
+  const EvolveArgs a{{best_score, B, L, stop, x, score_cur, live, best_so_far, stopped, x_best, score_best, tr_pos, tr_allele, tr_score,
+                      tr_taken}, best_pos, best_allele};
   return svdd_launch(vec ? evolve_apply_kernel<true> : evolve_apply_kernel<false>, dim3(1), dim3(1024), 0, on_stream, a);
 }
 
@@ -2877,8 +2846,8 @@ int svdd_pattern_apply(const float* best_score, const int32_t* best_pos, const i
   const auto al = [](const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; };
   if (!al(patterns, 4)) return SVDD_E_ARG;
   const bool vec = L % 4 == 0 && al(x, 4) && al(x_best, 4);
-  const PatternApplyArgs a{best_score, best_pos, best_pattern, positions, patterns, widths, B, L, P, K, stop, x, score_cur, live,
-                           best_so_far, stopped, x_best, score_best, tr_pos, tr_pattern, tr_score, tr_taken};
+  const PatternApplyArgs a{{best_score, B, L, stop, x, score_cur, live, best_so_far, stopped, x_best, score_best, tr_pos, tr_pattern,
+                            tr_score, tr_taken}, best_pos, best_pattern, positions, patterns, widths, P, K};
   return svdd_launch(vec ? pattern_apply_kernel<true> : pattern_apply_kernel<false>, dim3(1), dim3(1024), 0, on_stream, a);
 }
 

@@ -1326,6 +1326,13 @@ class Diffusion(nn.Module):
         fz = None if frozen is None else (frozen != 0).to(torch.uint8).contiguous()
         return self._tokens_u8(x0).contiguous(), fz
 
+    @staticmethod
+    def _require_rows(x):
+        """The first check of the design entries (ISM, patterns, attributions, Ledidi); no device. -> x's shape (B, L)."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] == 0 or x.shape[1] == 0:
+            raise ValueError(f"x must be a [B, L] tensor with B, L > 0, got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)}")
+        return x.shape
+
     def _design_scorer(self, pre_scorer_embedding, pre_scorer_head, reward_model):
         """tokens u8 [B, L] -> fp32 [B]: the score refine() judges a finished row by — the value function on the clean tokens, or
         (reward_model given) the reward; task 0 of a multi-task net. One kernel path for every call, so scores compare exactly."""
@@ -1418,47 +1425,76 @@ class Diffusion(nn.Module):
                                           # tower buffer and the GRU's two output planes are 1.26 GB at L = 200
     ISM_COMPARE = (None, "subtract", "divide", "log2FC")
 
-    def _ism_positions(self, positions, L):
-        """-> (python list, int32 device tensor [P]); None = every position."""
+    @dataclass
+    class _MutantKind:
+        """One kind of mutant scan, built per call (_ism_kind, _pattern_kind): the positions and their chunking, and everything in
+        which in-silico mutagenesis and pattern scanning differ. The scan itself (_ScanWorkspace, _scan_pass, _scan_scores,
+        _scan_evolve) is written once behind it."""
+        pos_dev: torch.Tensor             # i32 [P], ascending
+        P: int
+        Pc: int                           # positions per chunk: B * per_pos * Pc <= chunk_rows (never less than one position)
+        per_pos: int                      # mutants per position: 3 | K
+        width: int                        # table entries per position: 4 | K
+        copies: bool                      # can a live row's mutant equal the row? (a pattern that is already there; ISM: never)
+        trace_key: str                    # the trace's second key: the pick's "allele" | "pattern"
+        mutants: object                   # (x, p0, pc, live, cand=, onehot=, err=): ops.ism_mutants | ops.pattern_mutants
+        fold: object                      # (scores, parent_score, x, p0, pc, slot=, live=, table=, best=): ops.ism_fold | pattern_fold
+        apply: object                     # (best, x, score_cur, ..., stop=, live=, trace=): ops.evolve_apply | pattern_apply
+        check_err: object                 # ops.check_ism_err | ops.check_pattern_err
+        pat_dev: Optional[torch.Tensor] = None       # patterns only: u8 [K, 32], i32 [K]
+        widths_dev: Optional[torch.Tensor] = None
+
+    def _scan_inputs(self, x, positions, chunk_rows, n_pos, per_pos, range_text, mask_text):
+        """The checks the two kinds share after the shape's, in an order that needs no device until the last one: the positions
+        (None = all n_pos), chunk_rows, a MASK token, then _refine_inputs' (a CPU tensor, a token outside 0..4).
+        -> (x u8 [B, L], pos_dev i32 [P], P, Pc)."""
         if positions is None:
-            pos = list(range(L))
+            pos = list(range(n_pos))
         else:
             pos = [int(p) for p in (positions.tolist() if isinstance(positions, torch.Tensor) else positions)]
             if not pos:
                 raise ValueError("positions must not be empty")
-            if any(p < 0 or p >= L for p in pos):
-                raise ValueError(f"positions must lie in 0..{L - 1}, got {pos}")
+            if any(p < 0 or p >= n_pos for p in pos):
+                raise ValueError(f"{range_text}, got {pos}")
             if any(b <= a for a, b in zip(pos, pos[1:])):
                 raise ValueError(f"positions must be strictly ascending (no duplicates), got {pos}")
-        return pos, torch.tensor(pos, dtype=torch.int32, device=self.device)
-
-    def _ism_inputs(self, x, positions, chunk_rows):
-        """Checks in an order that needs no device until the last one: the shape, the positions, a MASK token, then
-        _refine_inputs' (a CPU tensor, a token outside 0..4)."""
-        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] == 0 or x.shape[1] == 0:
-            raise ValueError(f"x must be a [B, L] tensor with B, L > 0, got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)}")
-        pos, pos_dev = self._ism_positions(positions, x.shape[1])
         if chunk_rows is not None and int(chunk_rows) <= 0:
             raise ValueError(f"chunk_rows must be positive, got {chunk_rows}")
         if not x.dtype.is_floating_point and x.dtype != torch.bool and bool((x == self.mask_index).any()):
-            raise ops.SvddError("x holds a MASK token: in-silico mutagenesis scores finished sequences (tokens 0..3)")
+            raise ops.SvddError(f"x holds a MASK token: {mask_text} (tokens 0..3)")
         x_u8, _ = self._refine_inputs(x, None)
         self._require_gpu()
-        B, L = x_u8.shape
         if chunk_rows is None:
             chunk_rows = self.ISM_WAVES_PER_CHUNK * torch.cuda.get_device_properties(self.device).multi_processor_count
-        Pc = max(1, min(len(pos), int(chunk_rows) // (3 * B)))      # B * 3 * Pc <= chunk_rows (never less than one position)
-        return x_u8, pos_dev, len(pos), Pc
+        Pc = max(1, min(len(pos), int(chunk_rows) // (per_pos * x_u8.shape[0])))
+        return x_u8, torch.tensor(pos, dtype=torch.int32, device=self.device), len(pos), Pc
 
-    class _IsmWorkspace:
-        def __init__(self, B, L, Pc, dev, windowed):
-            n = B * 3 * Pc
+    def _ism_kind(self, x, positions, chunk_rows):
+        """ism_scores' / evolve's input checks -> (x u8 [B, L], the kind of the single-base mutants at `positions`)."""
+        L = self._require_rows(x)[1]
+        x_u8, pos_dev, P, Pc = self._scan_inputs(x, positions, chunk_rows, L, 3, f"positions must lie in 0..{L - 1}",
+                                                 "in-silico mutagenesis scores finished sequences")
+        return x_u8, self._MutantKind(
+            pos_dev, P, Pc, per_pos=3, width=4, copies=False, trace_key="allele",
+            mutants=lambda x, p0, pc, live, **out: ops.ism_mutants(x, pos_dev[p0:p0 + pc], live, want_onehot=False, **out),
+            fold=lambda sc, parent, x, p0, pc, table=None, **kw: ops.ism_fold(sc, parent, x, pos_dev, p0, pc, ism=table, **kw),
+            apply=ops.evolve_apply, check_err=ops.check_ism_err)
+
+    class _ScanWorkspace:
+        """The buffers of one scan, sized for a full chunk. The one-hot rows exist only where a kernel reads them (the fp32 windowed
+        tower); flags / iota only where copies are told apart (the windowed route; patterns on the whole-mutant route)."""
+        def __init__(self, kind, B, L, dev, fused):
+            n = B * kind.per_pos * kind.Pc
             self.cand = torch.empty(n * L, dtype=torch.uint8, device=dev)
-            self.onehot = self.flags = self.live_idx = self.slot = self.count = None
-            if windowed:
-                self.onehot = torch.empty(n * L * 4, dtype=torch.float32, device=dev)
+            self.onehot = self.flags = self.live_idx = self.slot = self.count = self.iota = None
+            if fused is not None:
+                if not fused.lp_ok(L):
+                    self.onehot = torch.empty(n * L * 4, dtype=torch.float32, device=dev)
                 self.flags, self.live_idx, self.slot = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
                 self.count = torch.zeros(1, dtype=torch.int32, device=dev)
+            elif kind.copies:
+                self.flags = torch.empty(n, dtype=torch.int32, device=dev)
+                self.iota = torch.arange(n, dtype=torch.int32, device=dev)
             self.err = torch.zeros(1, dtype=torch.int32, device=dev)
 
     def _ism_route(self, pre_scorer_embedding, pre_scorer_head, reward_model, L):
@@ -1472,35 +1508,97 @@ class Diffusion(nn.Module):
         windowed = isinstance(fn, FusedValueNet) and fn.kernels_ok(L) and fn.candidates_ok(L, 3)
         return score_fn, (fn if windowed else None)
 
-    def _ism_pass(self, x, pos_dev, P, Pc, score_fn, fused, ws, parent_score, live=None, ism=None, best=None):
-        """The mutants of x at every position, chunk by chunk in ascending position order: svdd_ism_mutants, the value net, and
-        svdd_ism_fold into ism [B, P, 4] and / or the running best. Nothing returns to the host."""
+    def _scan_pass(self, kind, x, score_fn, fused, ws, parent_score, live=None, table=None, best=None):
+        """The mutants of x at every position, chunk by chunk in ascending position order: kind.mutants, the value net, and kind.fold
+        into table [B, P, width] and / or the running best. Copies (a stopped row's mutants; a pattern that is already there) are
+        compacted away on the windowed route, and on the whole-mutant route pass through score_fn with the rest, where the fold
+        takes the parent's score in a pattern's place; ISM without `live` has none and does neither. Nothing returns to the host."""
+        from .fused import candidate_windows
         B, L = x.shape
-        lp = fused is not None and fused.precision != "f32"
         if fused is not None:                                       # the parents' tower output, once per pass
             parent_out = fused.parent_tower(x)
-        for p0 in range(0, P, Pc):
-            pc = min(Pc, P - p0)
-            n = B * 3 * pc
-            cand = ws.cand[:n * L].view(B, 3 * pc, L)
-            if fused is None:
-                ops.ism_mutants(x, pos_dev[p0:p0 + pc], live, cand=cand, want_onehot=False, err=ws.err)
-                ops.ism_fold(score_fn(cand.view(n, L)), parent_score, x, pos_dev, p0, pc, live=live, ism=ism, best=best)
-                continue
-            onehot = None if lp else ws.onehot[:n * L * 4].view(n, L, 4)
-            ops.ism_mutants(x, pos_dev[p0:p0 + pc], live, cand=cand, onehot=onehot, want_onehot=False, err=ws.err)
-            if live is None:
-                win = fused.tower_ranges_of(cand, x)
-                sc = fused.forward_candidates_from(onehot, cand, win, parent_out)
-                slot = None
-            else:                                                   # stopped rows' mutants are exact copies: flagged 0, dropped
-                flags, live_idx, slot = ws.flags[:n], ws.live_idx[:n], ws.slot[:n]
-                win = fused.tower_ranges_of(cand, x, key=flags)
-                ops.compact_flags(flags, live_idx, slot, ws.count)
-                sc = fused.forward_candidates_from(onehot, cand, win, parent_out, live_idx=live_idx, count=ws.count)
-            sc = sc.reshape(n, -1)
-            sc = sc.reshape(n) if sc.shape[1] == 1 else sc[:, 0].contiguous()
-            ops.ism_fold(sc, parent_score, x, pos_dev, p0, pc, slot=slot, live=live, ism=ism, best=best)
+        for p0 in range(0, kind.P, kind.Pc):
+            pc = min(kind.Pc, kind.P - p0)
+            n = B * kind.per_pos * pc
+            cand = ws.cand[:n * L].view(B, kind.per_pos * pc, L)
+            onehot = None if ws.onehot is None else ws.onehot[:n * L * 4].view(n, L, 4)
+            kind.mutants(x, p0, pc, live, cand=cand, onehot=onehot, err=ws.err)
+            slot = None
+            if fused is None:                                       # whole mutants through score_fn
+                if kind.copies:                                     # flags > 0: the mutant differs from its parent
+                    candidate_windows(cand, x, flags=ws.flags[:n])
+                    slot = torch.where(ws.flags[:n] > 0, ws.iota[:n], ws.iota[:n] - n)
+                sc = score_fn(cand.view(n, L))
+            else:
+                if kind.copies or live is not None:
+                    flags, live_idx, slot = ws.flags[:n], ws.live_idx[:n], ws.slot[:n]
+                    win = fused.tower_ranges_of(cand, x, key=flags)
+                    ops.compact_flags(flags, live_idx, slot, ws.count)
+                    sc = fused.forward_candidates_from(onehot, cand, win, parent_out, live_idx=live_idx, count=ws.count)
+                else:
+                    sc = fused.forward_candidates_from(onehot, cand, fused.tower_ranges_of(cand, x), parent_out)
+                sc = sc.reshape(n, -1)
+                sc = sc.reshape(n) if sc.shape[1] == 1 else sc[:, 0].contiguous()      # task 0 of a multi-task net
+            kind.fold(sc, parent_score, x, p0, pc, slot=slot, live=live, table=table, best=best)
+
+    @staticmethod
+    def _compare_to(table, parent_score, compare):
+        if compare is None:
+            return table
+        ref = parent_score[:, None, None]
+        return table - ref if compare == "subtract" else table / ref if compare == "divide" else torch.log2(table / ref)
+
+    def _scan_scores(self, x_u8, kind, nets, compare):
+        """The table of one scan, fp32 [B, P, kind.width]; nets = (pre_scorer_embedding, pre_scorer_head, reward_model)."""
+        B, L = x_u8.shape
+        score_fn, fused = self._ism_route(*nets, L)
+        ws = self._ScanWorkspace(kind, B, L, self.device, fused)
+        parent_score = score_fn(x_u8)
+        table = torch.empty((B, kind.P, kind.width), dtype=torch.float32, device=self.device)
+        self._scan_pass(kind, x_u8, score_fn, fused, ws, parent_score, table=table)
+        kind.check_err(ws.err)
+        return self._compare_to(table, parent_score, compare)
+
+    def _scan_evolve(self, x_u8, kind, nets, max_iter, stop):
+        """Greedy evolution on one kind's table (evolve's and evolve_patterns' contract): per iteration one pass folded into a
+        per-row best and one kind.apply launch; the host reads the one `stopped` word per iteration."""
+        x_u8 = x_u8.clone()
+        B, L = x_u8.shape
+        dev = self.device
+        score_fn, fused = self._ism_route(*nets, L)
+        ws = self._ScanWorkspace(kind, B, L, dev, fused)
+        score_cur = score_fn(x_u8).clone()
+        x_best, score_best = x_u8.clone(), score_cur.clone()
+        neg = torch.full_like(score_cur, float("-inf"))
+        best_so_far = torch.where(score_cur != score_cur, neg, score_cur).max().reshape(1)   # iteration 0 of the reference: the inputs
+        stopped = torch.zeros(1, dtype=torch.int32, device=dev)
+        live = torch.ones(B, dtype=torch.uint8, device=dev) if stop == "row" else None
+        best = (torch.empty(B, device=dev), torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+        rows = max(max_iter, 1)
+        tr_pos, tr_pick = (torch.full((rows, B), -1, dtype=torch.int32, device=dev) for _ in range(2))
+        tr_taken = torch.zeros((rows, B), dtype=torch.uint8, device=dev)
+        tr_score = torch.empty((rows + 1, B), dtype=torch.float32, device=dev)
+        tr_score[0] = score_cur
+        iters = 0
+        for it in range(max_iter):
+            self._scan_pass(kind, x_u8, score_fn, fused, ws, score_cur, live=live, best=best)
+            kind.apply(best, x_u8, score_cur, best_so_far, stopped, x_best, score_best, stop=stop, live=live,
+                       trace=(tr_pos[it], tr_pick[it], tr_score[it + 1], tr_taken[it]))
+            iters = it + 1
+            if int(stopped[0]) != 0:                                # the one word the host reads per iteration
+                break
+        kind.check_err(ws.err)
+        trace = {"iters": iters, "position": tr_pos[:iters], kind.trace_key: tr_pick[:iters], "taken": tr_taken[:iters],
+                 "score": tr_score[:iters + 1]}
+        return x_best.long(), score_best, trace
+
+    @staticmethod
+    def _evolve_args(stop, max_iter):
+        if stop not in ops.EVOLVE_STOP:
+            raise ValueError(f"stop = {stop!r}: expected 'global' or 'row'")
+        if int(max_iter) < 0:
+            raise ValueError(f"max_iter must be >= 0, got {int(max_iter)}")
+        return int(max_iter)
 
     @torch.no_grad()
     def ism_scores(self, x, pre_scorer_embedding, pre_scorer_head, reward_model=None, positions=None, compare=None, chunk_rows=None):
@@ -1514,18 +1612,8 @@ class Diffusion(nn.Module):
         bits as the whole tower), svdd_ism_fold. No mutant and no score crosses to the host."""
         if compare not in self.ISM_COMPARE:
             raise ValueError(f"compare = {compare!r}: expected None, 'subtract', 'divide' or 'log2FC'")
-        x_u8, pos_dev, P, Pc = self._ism_inputs(x, positions, chunk_rows)
-        B, L = x_u8.shape
-        score_fn, fused = self._ism_route(pre_scorer_embedding, pre_scorer_head, reward_model, L)
-        ws = self._IsmWorkspace(B, L, Pc, self.device, fused is not None)
-        parent_score = score_fn(x_u8)
-        ism = torch.empty((B, P, 4), dtype=torch.float32, device=self.device)
-        self._ism_pass(x_u8, pos_dev, P, Pc, score_fn, fused, ws, parent_score, ism=ism)
-        ops.check_ism_err(ws.err)
-        if compare is not None:
-            ref = parent_score[:, None, None]
-            ism = ism - ref if compare == "subtract" else ism / ref if compare == "divide" else torch.log2(ism / ref)
-        return ism
+        x_u8, kind = self._ism_kind(x, positions, chunk_rows)
+        return self._scan_scores(x_u8, kind, (pre_scorer_embedding, pre_scorer_head, reward_model), compare)
 
     @torch.no_grad()
     def evolve(self, x, pre_scorer_embedding, pre_scorer_head, reward_model=None, max_iter=10, positions=None, stop="global",
@@ -1544,41 +1632,9 @@ class Diffusion(nn.Module):
         picks' scores of iteration i}: the reference dataframe's best_in_iter rows. max_iter = 0 returns the input and its score.
         Per iteration: one pass of ism_scores' path folded into a per-row best, one svdd_evolve_apply launch; the host reads the
         one `stopped` word per iteration and nothing else before the end."""
-        if stop not in ops.EVOLVE_STOP:
-            raise ValueError(f"stop = {stop!r}: expected 'global' or 'row'")
-        max_iter = int(max_iter)
-        if max_iter < 0:
-            raise ValueError(f"max_iter must be >= 0, got {max_iter}")
-        x_u8, pos_dev, P, Pc = self._ism_inputs(x, positions, chunk_rows)
-        x_u8 = x_u8.clone()
-        B, L = x_u8.shape
-        dev = self.device
-        score_fn, fused = self._ism_route(pre_scorer_embedding, pre_scorer_head, reward_model, L)
-        ws = self._IsmWorkspace(B, L, Pc, dev, fused is not None)
-        score_cur = score_fn(x_u8).clone()
-        x_best, score_best = x_u8.clone(), score_cur.clone()
-        neg = torch.full_like(score_cur, float("-inf"))
-        best_so_far = torch.where(score_cur != score_cur, neg, score_cur).max().reshape(1)   # iteration 0 of the reference: the inputs
-        stopped = torch.zeros(1, dtype=torch.int32, device=dev)
-        live = torch.ones(B, dtype=torch.uint8, device=dev) if stop == "row" else None
-        best = (torch.empty(B, device=dev), torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
-        rows = max(max_iter, 1)
-        tr_pos, tr_al = (torch.full((rows, B), -1, dtype=torch.int32, device=dev) for _ in range(2))
-        tr_taken = torch.zeros((rows, B), dtype=torch.uint8, device=dev)
-        tr_score = torch.empty((rows + 1, B), dtype=torch.float32, device=dev)
-        tr_score[0] = score_cur
-        iters = 0
-        for it in range(max_iter):
-            self._ism_pass(x_u8, pos_dev, P, Pc, score_fn, fused, ws, score_cur, live=live, best=best)
-            ops.evolve_apply(best, x_u8, score_cur, best_so_far, stopped, x_best, score_best, stop=stop, live=live,
-                             trace=(tr_pos[it], tr_al[it], tr_score[it + 1], tr_taken[it]))
-            iters = it + 1
-            if int(stopped[0]) != 0:                                # the one word the host reads per iteration
-                break
-        ops.check_ism_err(ws.err)
-        trace = {"iters": iters, "position": tr_pos[:iters], "allele": tr_al[:iters], "taken": tr_taken[:iters],
-                 "score": tr_score[:iters + 1]}
-        return x_best.long(), score_best, trace
+        max_iter = self._evolve_args(stop, max_iter)
+        x_u8, kind = self._ism_kind(x, positions, chunk_rows)
+        return self._scan_evolve(x_u8, kind, (pre_scorer_embedding, pre_scorer_head, reward_model), max_iter, stop)
 
     # ------------------------------------------------------------- pattern scanning, pattern-driven evolution ----
     @staticmethod
@@ -1608,91 +1664,29 @@ class Diffusion(nn.Module):
             pat[k, :len(tok)], widths[k] = tok, len(tok)
         return pat, widths
 
-    def _pattern_inputs(self, x, patterns, reward_model, positions, chunk_rows, what):
-        """Checks in an order that needs no device until the last ones (as _ism_inputs): the reward's type, the patterns, the shape,
-        the start positions, chunk_rows, a MASK token, then _refine_inputs' (a CPU tensor, a token outside 0..4).
-        -> (x u8 [B, L], pos_dev i32 [P], pat_dev u8 [K, 32], widths_dev i32 [K], P, K, Pc)."""
+    def _pattern_kind(self, x, patterns, reward_model, positions, chunk_rows, what):
+        """pattern_scores' / evolve_patterns' input checks: the reward's type, the patterns, the shape, then _scan_inputs' with the
+        starts at which the longest pattern fits -> (x u8 [B, L], the kind of the pattern mutants at `positions`)."""
         from .motifs import GuidedReward
         if isinstance(reward_model, GuidedReward):
             raise TypeError(f"{what}: a motifs.GuidedReward is not a net of this route (its motif term scores whole decodes): pass "
                             "the reward model it wraps")
         pat, widths = self._pattern_list(patterns)
-        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] == 0 or x.shape[1] == 0:
-            raise ValueError(f"x must be a [B, L] tensor with B, L > 0, got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)}")
-        L, wmax = x.shape[1], int(widths.max())
+        L, K, wmax = self._require_rows(x)[1], len(widths), int(widths.max())
         if wmax > L:
             raise ValueError(f"the longest pattern has {wmax} tokens, the sequences {L}: patterns must fit into the sequence")
-        if positions is None:
-            pos = list(range(L - wmax + 1))                         # every start at which the longest pattern fits
-        else:
-            pos = [int(p) for p in (positions.tolist() if isinstance(positions, torch.Tensor) else positions)]
-            if not pos:
-                raise ValueError("positions must not be empty")
-            if any(p < 0 or p + wmax > L for p in pos):
-                raise ValueError(f"positions are starts in 0..{L - wmax} (the longest pattern, {wmax} tokens, must fit), got {pos}")
-            if any(b <= a for a, b in zip(pos, pos[1:])):
-                raise ValueError(f"positions must be strictly ascending (no duplicates), got {pos}")
-        if chunk_rows is not None and int(chunk_rows) <= 0:
-            raise ValueError(f"chunk_rows must be positive, got {chunk_rows}")
-        if not x.dtype.is_floating_point and x.dtype != torch.bool and bool((x == self.mask_index).any()):
-            raise ops.SvddError("x holds a MASK token: patterns are written into finished sequences (tokens 0..3)")
-        x_u8, _ = self._refine_inputs(x, None)
-        self._require_gpu()
-        B, K = x_u8.shape[0], len(widths)
-        if chunk_rows is None:
-            chunk_rows = self.ISM_WAVES_PER_CHUNK * torch.cuda.get_device_properties(self.device).multi_processor_count
-        Pc = max(1, min(len(pos), int(chunk_rows) // (K * B)))      # B * K * Pc <= chunk_rows (never less than one position)
-        dev = self.device
-        return (x_u8, torch.tensor(pos, dtype=torch.int32, device=dev), torch.from_numpy(pat).to(dev), torch.from_numpy(widths).to(dev),
-                len(pos), K, Pc)
-
-    class _PatternWorkspace:
-        def __init__(self, B, L, K, Pc, dev, windowed, onehot):
-            n = B * K * Pc
-            self.cand = torch.empty(n * L, dtype=torch.uint8, device=dev)
-            self.onehot = self.live_idx = self.slot = self.count = self.iota = None
-            self.flags = torch.empty(n, dtype=torch.int32, device=dev)
-            if windowed:
-                self.onehot = torch.empty(n * L * 4, dtype=torch.float32, device=dev) if onehot else None
-                self.live_idx, self.slot = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
-                self.count = torch.zeros(1, dtype=torch.int32, device=dev)
-            else:
-                self.iota = torch.arange(n, dtype=torch.int32, device=dev)
-            self.err = torch.zeros(1, dtype=torch.int32, device=dev)
-
-    def _pattern_workspace(self, B, L, K, Pc, fused):
-        return self._PatternWorkspace(B, L, K, Pc, self.device, fused is not None, fused is not None and not fused.lp_ok(L))
-
-    def _pattern_pass(self, x, pos_dev, pat_dev, widths_dev, P, K, Pc, score_fn, fused, ws, parent_score, live=None, table=None,
-                      best=None):
-        """The pattern mutants of x at every start position, chunk by chunk in ascending position order: svdd_pattern_mutants, the
-        value net, and svdd_pattern_fold into table [B, P, K] and / or the running best. On the windowed route the copies (a
-        pattern that is already there, a stopped row) are always compacted away; on the whole-mutant route they pass through
-        score_fn with the rest and the fold takes the parent's score in their place. Nothing returns to the host."""
-        from .fused import candidate_windows
-        B, L = x.shape
-        if fused is not None:                                       # the parents' tower output, once per pass
-            parent_out = fused.parent_tower(x)
-        for p0 in range(0, P, Pc):
-            pc = min(Pc, P - p0)
-            n = B * K * pc
-            cand = ws.cand[:n * L].view(B, K * pc, L)
-            flags = ws.flags[:n]
-            if fused is None:                                       # whole mutants through score_fn; a copy's entry is its parent's score
-                ops.pattern_mutants(x, pos_dev[p0:p0 + pc], pat_dev, widths_dev, live, cand=cand, want_onehot=False, err=ws.err)
-                candidate_windows(cand, x, flags=flags)             # flags > 0: the mutant differs from its parent
-                slot = torch.where(flags > 0, ws.iota[:n], ws.iota[:n] - n)
-                ops.pattern_fold(score_fn(cand.view(n, L)), parent_score, P, K, p0, pc, slot=slot, live=live, table=table, best=best)
-                continue
-            onehot = None if ws.onehot is None else ws.onehot[:n * L * 4].view(n, L, 4)
-            ops.pattern_mutants(x, pos_dev[p0:p0 + pc], pat_dev, widths_dev, live, cand=cand, onehot=onehot, want_onehot=False, err=ws.err)
-            live_idx, slot = ws.live_idx[:n], ws.slot[:n]
-            win = fused.tower_ranges_of(cand, x, key=flags)
-            ops.compact_flags(flags, live_idx, slot, ws.count)
-            sc = fused.forward_candidates_from(onehot, cand, win, parent_out, live_idx=live_idx, count=ws.count)
-            sc = sc.reshape(n, -1)
-            sc = sc.reshape(n) if sc.shape[1] == 1 else sc[:, 0].contiguous()
-            ops.pattern_fold(sc, parent_score, P, K, p0, pc, slot=slot, live=live, table=table, best=best)
+        x_u8, pos_dev, P, Pc = self._scan_inputs(
+            x, positions, chunk_rows, L - wmax + 1, K,
+            f"positions are starts in 0..{L - wmax} (the longest pattern, {wmax} tokens, must fit)",
+            "patterns are written into finished sequences")
+        pat_dev, widths_dev = torch.from_numpy(pat).to(self.device), torch.from_numpy(widths).to(self.device)
+        return x_u8, self._MutantKind(
+            pos_dev, P, Pc, per_pos=K, width=K, copies=True, trace_key="pattern", pat_dev=pat_dev, widths_dev=widths_dev,
+            mutants=lambda x, p0, pc, live, **out: ops.pattern_mutants(x, pos_dev[p0:p0 + pc], pat_dev, widths_dev, live,
+                                                                       want_onehot=False, **out),
+            fold=lambda sc, parent, x, p0, pc, **kw: ops.pattern_fold(sc, parent, P, K, p0, pc, **kw),
+            apply=lambda best, *state, **kw: ops.pattern_apply(best, pos_dev, pat_dev, widths_dev, *state, **kw),
+            check_err=ops.check_pattern_err)
 
     @torch.no_grad()
     def pattern_scores(self, x, patterns, pre_scorer_embedding, pre_scorer_head, reward_model=None, positions=None, compare=None,
@@ -1709,19 +1703,8 @@ class Diffusion(nn.Module):
         the positions it changed, the same bits as the whole tower), svdd_pattern_fold. No mutant and no score crosses to the host."""
         if compare not in self.ISM_COMPARE:
             raise ValueError(f"compare = {compare!r}: expected None, 'subtract', 'divide' or 'log2FC'")
-        x_u8, pos_dev, pat_dev, widths_dev, P, K, Pc = self._pattern_inputs(x, patterns, reward_model, positions, chunk_rows,
-                                                                             "pattern_scores")
-        B, L = x_u8.shape
-        score_fn, fused = self._ism_route(pre_scorer_embedding, pre_scorer_head, reward_model, L)
-        ws = self._pattern_workspace(B, L, K, Pc, fused)
-        parent_score = score_fn(x_u8)
-        table = torch.empty((B, P, K), dtype=torch.float32, device=self.device)
-        self._pattern_pass(x_u8, pos_dev, pat_dev, widths_dev, P, K, Pc, score_fn, fused, ws, parent_score, table=table)
-        ops.check_pattern_err(ws.err)
-        if compare is not None:
-            ref = parent_score[:, None, None]
-            table = table - ref if compare == "subtract" else table / ref if compare == "divide" else torch.log2(table / ref)
-        return table
+        x_u8, kind = self._pattern_kind(x, patterns, reward_model, positions, chunk_rows, "pattern_scores")
+        return self._scan_scores(x_u8, kind, (pre_scorer_embedding, pre_scorer_head, reward_model), compare)
 
     @torch.no_grad()
     def evolve_patterns(self, x, patterns, pre_scorer_embedding, pre_scorer_head, reward_model=None, max_iter=10, positions=None,
@@ -1740,42 +1723,9 @@ class Diffusion(nn.Module):
         `patterns`), "taken": [iters, B] (-1 / -1 / 0: a row without a pick), "score": [iters + 1, B]}. max_iter = 0 returns the
         input and its score. Per iteration one pass folded into a per-row best and one svdd_pattern_apply launch; the host reads the
         one `stopped` word per iteration and nothing else before the end."""
-        if stop not in ops.EVOLVE_STOP:
-            raise ValueError(f"stop = {stop!r}: expected 'global' or 'row'")
-        max_iter = int(max_iter)
-        if max_iter < 0:
-            raise ValueError(f"max_iter must be >= 0, got {max_iter}")
-        x_u8, pos_dev, pat_dev, widths_dev, P, K, Pc = self._pattern_inputs(x, patterns, reward_model, positions, chunk_rows,
-                                                                             "evolve_patterns")
-        x_u8 = x_u8.clone()
-        B, L = x_u8.shape
-        dev = self.device
-        score_fn, fused = self._ism_route(pre_scorer_embedding, pre_scorer_head, reward_model, L)
-        ws = self._pattern_workspace(B, L, K, Pc, fused)
-        score_cur = score_fn(x_u8).clone()
-        x_best, score_best = x_u8.clone(), score_cur.clone()
-        neg = torch.full_like(score_cur, float("-inf"))
-        best_so_far = torch.where(score_cur != score_cur, neg, score_cur).max().reshape(1)   # iteration 0 of the reference: the inputs
-        stopped = torch.zeros(1, dtype=torch.int32, device=dev)
-        live = torch.ones(B, dtype=torch.uint8, device=dev) if stop == "row" else None
-        best = (torch.empty(B, device=dev), torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
-        rows = max(max_iter, 1)
-        tr_pos, tr_pat = (torch.full((rows, B), -1, dtype=torch.int32, device=dev) for _ in range(2))
-        tr_taken = torch.zeros((rows, B), dtype=torch.uint8, device=dev)
-        tr_score = torch.empty((rows + 1, B), dtype=torch.float32, device=dev)
-        tr_score[0] = score_cur
-        iters = 0
-        for it in range(max_iter):
-            self._pattern_pass(x_u8, pos_dev, pat_dev, widths_dev, P, K, Pc, score_fn, fused, ws, score_cur, live=live, best=best)
-            ops.pattern_apply(best, pos_dev, pat_dev, widths_dev, x_u8, score_cur, best_so_far, stopped, x_best, score_best, stop=stop,
-                              live=live, trace=(tr_pos[it], tr_pat[it], tr_score[it + 1], tr_taken[it]))
-            iters = it + 1
-            if int(stopped[0]) != 0:                                # the one word the host reads per iteration
-                break
-        ops.check_pattern_err(ws.err)
-        trace = {"iters": iters, "position": tr_pos[:iters], "pattern": tr_pat[:iters], "taken": tr_taken[:iters],
-                 "score": tr_score[:iters + 1]}
-        return x_best.long(), score_best, trace
+        max_iter = self._evolve_args(stop, max_iter)
+        x_u8, kind = self._pattern_kind(x, patterns, reward_model, positions, chunk_rows, "evolve_patterns")
+        return self._scan_evolve(x_u8, kind, (pre_scorer_embedding, pre_scorer_head, reward_model), max_iter, stop)
 
     # ------------------------------------------------------------- gradient attributions ----
     ATTR_METHODS = ("gradient", "inputxgradient", "integratedgradients")
@@ -1797,11 +1747,9 @@ class Diffusion(nn.Module):
         return a.astype(np.float32), w.astype(np.float32)
 
     def _attr_inputs(self, x, method, baseline, n_steps, quadrature, chunk_rows, return_delta):
-        """Checks in an order that needs no device until the last one (as _ism_inputs) -> (x u8 [B, L], baseline | None, alphas,
+        """Checks in an order that needs no device until the last one (as _scan_inputs) -> (x u8 [B, L], baseline | None, alphas,
         weights: fp32 device [S], chunk_rows)."""
-        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] == 0 or x.shape[1] == 0:
-            raise ValueError(f"x must be a [B, L] tensor with B, L > 0, got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)}")
-        B, L = x.shape
+        B, L = self._require_rows(x)
         if method not in self.ATTR_METHODS:
             raise ValueError(f"method = {method!r}: expected one of {self.ATTR_METHODS}")
         ig = method == "integratedgradients"
@@ -1933,9 +1881,7 @@ class Diffusion(nn.Module):
                        noise):
         """Every check that needs no device, ValueError naming the argument -> (max_iter, S, editable bool list | None, target as a
         float64 numpy [B] | None)."""
-        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] == 0 or x.shape[1] == 0:
-            raise ValueError(f"x must be a [B, L] tensor with B, L > 0, got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)}")
-        B, L = x.shape
+        B, L = self._require_rows(x)
         if x.dtype.is_floating_point or x.dtype == torch.bool:
             raise ValueError(f"x must hold integer tokens, got {x.dtype}")
         if L > ops.LEDIDI_MAX_L:

@@ -285,29 +285,67 @@ def _is(t, dtype, shape, name):
     return t
 
 
+# The argument checks the ISM entries (svdd_ism_mutants / _fold / svdd_evolve_apply) share with their pattern siblings.
+def _mutant_parents(x, positions):
+    x = _need(x, torch.uint8, "x").contiguous()
+    if x.dim() != 2:
+        raise SvddError(f"x must be u8 [B, L], got {tuple(x.shape)}")
+    return x, _need(positions, torch.int32, "positions").contiguous()
+
+
+def _mutant_buffers(x, M, live, cand, onehot, want_onehot, err):
+    """live and the outputs of a mutants entry with M mutants per row -> (cand, onehot, err, whether err is checked here)."""
+    (B, L), dev = x.shape, x.device
+    if live is not None:
+        _is(live, torch.uint8, (B,), "live")
+    cand = torch.empty((B, M, L), dtype=torch.uint8, device=dev) if cand is None else _is(cand, torch.uint8, (B, M, L), "cand")
+    if onehot is None and want_onehot:
+        onehot = torch.empty((B * M, L, 4), dtype=torch.float32, device=dev)
+    elif onehot is not None:
+        _is(onehot, torch.float32, (B * M, L, 4), "onehot")
+    if err is None:
+        return cand, onehot, torch.zeros(1, dtype=torch.int32, device=dev), True
+    return cand, onehot, err, False
+
+
+def _best_triple(best, B, second):
+    """best = (best_score f32 [B], best_pos i32 [B], `second` i32 [B]) of a fold entry, checked."""
+    bs, bp, b2 = best
+    _is(bs, torch.float32, (B,), "best_score"), _is(bp, torch.int32, (B,), "best_pos"), _is(b2, torch.int32, (B,), second)
+    return bs, bp, b2
+
+
+def _evolve_stop(stop, x):
+    if stop not in EVOLVE_STOP:
+        raise ValueError(f"stop = {stop!r}: expected 'global' or 'row'")
+    return _need(x, torch.uint8, "x").shape
+
+
+def _evolve_state(x, score_cur, best_so_far, stopped, x_best, score_best, live, trace, second):
+    """The state an apply entry updates in place, checked -> the trace's four rows (None each without a trace)."""
+    B, L = x.shape
+    _is(x, torch.uint8, (B, L), "x"), _is(x_best, torch.uint8, (B, L), "x_best")
+    _is(score_cur, torch.float32, (B,), "score_cur"), _is(score_best, torch.float32, (B,), "score_best")
+    _is(best_so_far, torch.float32, (1,), "best_so_far"), _is(stopped, torch.int32, (1,), "stopped")
+    if live is not None:
+        _is(live, torch.uint8, (B,), "live")
+    if trace is None:
+        return None, None, None, None
+    tp, t2, ts, tt = trace
+    _is(tp, torch.int32, (B,), "trace position"), _is(t2, torch.int32, (B,), f"trace {second}")
+    _is(ts, torch.float32, (B,), "trace score"), _is(tt, torch.uint8, (B,), "trace taken")
+    return tp, t2, ts, tt
+
+
 def ism_mutants(x, positions, live=None, cand=None, onehot=None, want_onehot=True, err=None):
     """svdd_ism_mutants: the 3 P single-base mutants of every row of x u8 [B, L] at positions i32 [P] (device, ascending), in
     ISMDataset(drop_ref=True) order: mutant (b, j, k) = row b with positions[j] set to the k-th base that is not the parent's.
     -> (cand u8 [B, 3P, L], onehot f32 [B * 3P, L, 4] | None). live u8 [B]: a row with live[b] == 0 gets exact copies. err: a
     caller-zeroed device int32 [1] the kernel sets for a parent token > 3 or a position outside 0..L-1 (checked by the caller later
     with check_ism_err); None: checked here (one synchronisation)."""
-    x = _need(x, torch.uint8, "x").contiguous()
-    if x.dim() != 2:
-        raise SvddError(f"x must be u8 [B, L], got {tuple(x.shape)}")
-    B, L = x.shape
-    positions = _need(positions, torch.int32, "positions").contiguous()
-    P = positions.numel()
-    dev = x.device
-    if live is not None:
-        _is(live, torch.uint8, (B,), "live")
-    cand = torch.empty((B, 3 * P, L), dtype=torch.uint8, device=dev) if cand is None else _is(cand, torch.uint8, (B, 3 * P, L), "cand")
-    if onehot is None and want_onehot:
-        onehot = torch.empty((B * 3 * P, L, 4), dtype=torch.float32, device=dev)
-    elif onehot is not None:
-        _is(onehot, torch.float32, (B * 3 * P, L, 4), "onehot")
-    check_here = err is None
-    if check_here:
-        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    x, positions = _mutant_parents(x, positions)
+    (B, L), P = x.shape, positions.numel()
+    cand, onehot, err, check_here = _mutant_buffers(x, 3 * P, live, cand, onehot, want_onehot, err)
     _lib.call("svdd_ism_mutants", x, positions, live, B, L, P, cand, onehot, err, _this_stream())
     if check_here:
         check_ism_err(err)
@@ -339,10 +377,7 @@ def ism_fold(scores, parent_score, x, positions, p0, Pc, slot=None, live=None, i
         _is(live, torch.uint8, (B,), "live")
     if ism is not None:
         _is(ism, torch.float32, (B, P, 4), "ism")
-    bs = bp = ba = None
-    if best is not None:
-        bs, bp, ba = best
-        _is(bs, torch.float32, (B,), "best_score"), _is(bp, torch.int32, (B,), "best_pos"), _is(ba, torch.int32, (B,), "best_allele")
+    bs, bp, ba = (None, None, None) if best is None else _best_triple(best, B, "best_allele")
     _lib.call("svdd_ism_fold", scores, slot, parent_score, x, positions, live, B, L, P, int(p0), int(Pc), ism, bs, bp, ba, _this_stream())
 
 
@@ -351,22 +386,9 @@ def evolve_apply(best, x, score_cur, best_so_far, stopped, x_best, score_best, s
     of svdd_ism_fold; x u8 [B, L], score_cur f32 [B], live u8 [B] (required for stop = "row"), best_so_far f32 [1], stopped i32 [1],
     x_best u8 [B, L], score_best f32 [B] are updated in place; trace = (position i32 [B], allele i32 [B], score f32 [B], taken u8 [B])
     of this iteration or None. Nothing is written once stopped[0] != 0."""
-    if stop not in EVOLVE_STOP:
-        raise ValueError(f"stop = {stop!r}: expected 'global' or 'row'")
-    _need(x, torch.uint8, "x")
-    B, L = x.shape
-    bs, bp, ba = best
-    _is(bs, torch.float32, (B,), "best_score"), _is(bp, torch.int32, (B,), "best_pos"), _is(ba, torch.int32, (B,), "best_allele")
-    _is(x, torch.uint8, (B, L), "x"), _is(x_best, torch.uint8, (B, L), "x_best")
-    _is(score_cur, torch.float32, (B,), "score_cur"), _is(score_best, torch.float32, (B,), "score_best")
-    _is(best_so_far, torch.float32, (1,), "best_so_far"), _is(stopped, torch.int32, (1,), "stopped")
-    if live is not None:
-        _is(live, torch.uint8, (B,), "live")
-    tp = ta = ts = tt = None
-    if trace is not None:
-        tp, ta, ts, tt = trace
-        _is(tp, torch.int32, (B,), "trace position"), _is(ta, torch.int32, (B,), "trace allele")
-        _is(ts, torch.float32, (B,), "trace score"), _is(tt, torch.uint8, (B,), "trace taken")
+    B, L = _evolve_stop(stop, x)
+    bs, bp, ba = _best_triple(best, B, "best_allele")
+    tp, ta, ts, tt = _evolve_state(x, score_cur, best_so_far, stopped, x_best, score_best, live, trace, "allele")
     _lib.call("svdd_evolve_apply", bs, bp, ba, B, L, EVOLVE_STOP[stop], x, score_cur, live, best_so_far, stopped, x_best, score_best,
               tp, ta, ts, tt, _this_stream())
 
@@ -386,24 +408,10 @@ def pattern_mutants(x, positions, patterns, widths, live=None, cand=None, onehot
     [B * P K, L, 4] | None). live u8 [B]: a row with live[b] == 0 gets exact copies. err: a caller-zeroed device int32 [1] the kernel
     sets for a parent token > 3, a pattern token > 3 or a window that leaves the row (checked by the caller later with
     check_pattern_err); None: checked here (one synchronisation)."""
-    x = _need(x, torch.uint8, "x").contiguous()
-    if x.dim() != 2:
-        raise SvddError(f"x must be u8 [B, L], got {tuple(x.shape)}")
-    B, L = x.shape
-    positions = _need(positions, torch.int32, "positions").contiguous()
-    P = positions.numel()
+    x, positions = _mutant_parents(x, positions)
+    (B, L), P = x.shape, positions.numel()
     K = _pattern_args(patterns, widths)
-    dev = x.device
-    if live is not None:
-        _is(live, torch.uint8, (B,), "live")
-    cand = torch.empty((B, P * K, L), dtype=torch.uint8, device=dev) if cand is None else _is(cand, torch.uint8, (B, P * K, L), "cand")
-    if onehot is None and want_onehot:
-        onehot = torch.empty((B * P * K, L, 4), dtype=torch.float32, device=dev)
-    elif onehot is not None:
-        _is(onehot, torch.float32, (B * P * K, L, 4), "onehot")
-    check_here = err is None
-    if check_here:
-        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    cand, onehot, err, check_here = _mutant_buffers(x, P * K, live, cand, onehot, want_onehot, err)
     _lib.call("svdd_pattern_mutants", x, positions, patterns, widths, live, B, L, P, K, cand, onehot, err, _this_stream())
     if check_here:
         check_pattern_err(err)
@@ -434,10 +442,7 @@ def pattern_fold(scores, parent_score, P, K, p0, Pc, slot=None, live=None, table
         _is(live, torch.uint8, (B,), "live")
     if table is not None:
         _is(table, torch.float32, (B, P, K), "table")
-    bs = bp = bk = None
-    if best is not None:
-        bs, bp, bk = best
-        _is(bs, torch.float32, (B,), "best_score"), _is(bp, torch.int32, (B,), "best_pos"), _is(bk, torch.int32, (B,), "best_pattern")
+    bs, bp, bk = (None, None, None) if best is None else _best_triple(best, B, "best_pattern")
     _lib.call("svdd_pattern_fold", scores, slot, parent_score, live, B, P, K, p0, Pc, table, bs, bp, bk, _this_stream())
 
 
@@ -447,26 +452,13 @@ def pattern_apply(best, positions, patterns, widths, x, score_cur, best_so_far, 
     best_pattern) of svdd_pattern_fold; x u8 [B, L], score_cur f32 [B], live u8 [B] (required for stop = "row"), best_so_far f32
     [1], stopped i32 [1], x_best u8 [B, L], score_best f32 [B] are updated in place; trace = (start position i32 [B], pattern i32
     [B], score f32 [B], taken u8 [B]) of this iteration or None. Nothing is written once stopped[0] != 0."""
-    if stop not in EVOLVE_STOP:
-        raise ValueError(f"stop = {stop!r}: expected 'global' or 'row'")
-    _need(x, torch.uint8, "x")
-    B, L = x.shape
+    B, L = _evolve_stop(stop, x)
     positions = _need(positions, torch.int32, "positions")
     P = positions.numel()
     _is(positions, torch.int32, (P,), "positions")
     K = _pattern_args(patterns, widths)
-    bs, bp, bk = best
-    _is(bs, torch.float32, (B,), "best_score"), _is(bp, torch.int32, (B,), "best_pos"), _is(bk, torch.int32, (B,), "best_pattern")
-    _is(x, torch.uint8, (B, L), "x"), _is(x_best, torch.uint8, (B, L), "x_best")
-    _is(score_cur, torch.float32, (B,), "score_cur"), _is(score_best, torch.float32, (B,), "score_best")
-    _is(best_so_far, torch.float32, (1,), "best_so_far"), _is(stopped, torch.int32, (1,), "stopped")
-    if live is not None:
-        _is(live, torch.uint8, (B,), "live")
-    tp = tk = ts = tt = None
-    if trace is not None:
-        tp, tk, ts, tt = trace
-        _is(tp, torch.int32, (B,), "trace position"), _is(tk, torch.int32, (B,), "trace pattern")
-        _is(ts, torch.float32, (B,), "trace score"), _is(tt, torch.uint8, (B,), "trace taken")
+    bs, bp, bk = _best_triple(best, B, "best_pattern")
+    tp, tk, ts, tt = _evolve_state(x, score_cur, best_so_far, stopped, x_best, score_best, live, trace, "pattern")
     _lib.call("svdd_pattern_apply", bs, bp, bk, positions, patterns, widths, B, L, P, K, EVOLVE_STOP[stop], x, score_cur, live,
               best_so_far, stopped, x_best, score_best, tp, tk, ts, tt, _this_stream())
 

@@ -683,3 +683,30 @@ def test_recorded_reference_table_full_size_nets(nets, precision):
         err, perr, spread = _fixture(g, model, emb, head)
     print(f"ERR pattern_g43 {precision} {err:.3e} (parent {perr:.3e}) bar {SOFT_BAR:.0e}; mean |mutant - parent| recorded {spread:.3e}")
     assert err <= SOFT_BAR and perr <= SOFT_BAR
+
+
+@pytest.mark.parametrize("net, precision, L, ism_rows, pattern_rows", [
+    ("full", "f32", 105, 360, 389), ("full", "f16x3", 105, 360, 389),        # the shortest windowed length
+    ("full", "f32", 33, 130, 125), ("full", "f16x3", 33, 130, 125),          # the fused net's forward_tokens route
+    ("tiny", "f32", 33, 130, 125)])                                           # PyTorch modules: the opaque callable
+def test_width_one_patterns_equal_ism_bit_for_bit(nets, net, precision, L, ism_rows, pattern_rows):
+    """The two kinds meet in one driver: the four width-1 patterns A, C, G, T at every position are ism_scores' table [B, L, 4],
+    bit for bit, on every route (both sides are pinned to forward_tokens / the opaque call by the tests above: no tolerance). The
+    pattern whose base is already there is a copy that the pattern side does not compute; the ISM side has no copies. Each call
+    runs in at least two chunks with a ragged last one, of different sizes for the two calls (B = 3: 9 and 12 rows per position)."""
+    from svdd_amd.fused import FusedValueNet
+    model, emb, head = nets[net][:3]
+    x = _x(3, L, L + 7)
+    chunks = [rows // per for rows, per in ((ism_rows, 9), (pattern_rows, 12))]
+    assert chunks[0] != chunks[1] and all(pc < L and L % pc for pc in chunks)
+    with knobs(model, precision=precision), torch.no_grad():
+        fn = model.value_callable(emb, head)
+        if net == "tiny":
+            assert not hasattr(fn, "forward_tokens") and model._ism_route(emb, head, None, L)[1] is None
+        else:
+            assert isinstance(fn, FusedValueNet) and fn.precision == precision
+            assert (model._ism_route(emb, head, None, L)[1] is fn) == (L > 104)
+        ism = model.ism_scores(dev(x), emb, head, chunk_rows=ism_rows)
+        table = model.pattern_scores(dev(x), ["A", "C", "G", "T"], emb, head, positions=None, chunk_rows=pattern_rows)
+    assert ism.shape == table.shape == (3, L, 4) and not torch.isnan(ism).any()
+    assert torch.equal(table, ism)

@@ -50,8 +50,8 @@ def timed(fn, reps):
 
 
 def chunk_positions():
-    _, _, P, Pc = model._ism_inputs(x, None, None)
-    return P, Pc
+    kind = model._ism_kind(x, None, None)[1]
+    return kind.P, kind.Pc
 
 
 @torch.no_grad()

@@ -53,8 +53,8 @@ def timed(fn, reps):
 
 
 def inputs():
-    _, pos_dev, pat_dev, widths_dev, P, _, Pc = model._pattern_inputs(x, PATTERNS, None, None, None, "pattern_time")
-    return pos_dev, pat_dev, widths_dev, P, Pc
+    kind = model._pattern_kind(x, PATTERNS, None, None, None, "pattern_time")[1]
+    return kind.pos_dev, kind.pat_dev, kind.widths_dev, kind.P, kind.Pc
 
 
 @torch.no_grad()
